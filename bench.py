@@ -11,10 +11,16 @@ N = 1 / 2 / 4 / 8), i.e. STRONG scaling; at N = 1 that is the 1024-frame batch t
 every rank its own `--batch` frames instead (and says so in "scaling").  Frames are independent: NO collective on the
 data path; torch.distributed carries the barriers and the max-over-ranks of the elapsed time only.
 
-Prints ONE JSON line (rank 0).  value = frames/s over all ranks.
+Prints ONE JSON line (rank 0).  value = frames/s over all ranks; ms_per_step = wall-clock milliseconds of one timed step.
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints that line.
   roofline      whole cascade of one step on one GPU: algorithmic bytes (8 B/px: sparse f32 in + dense f32 out, intermediates
-                count zero) / mean GPU time per step, HIP events on the launch stream; .per_kernel = the library's own events
-                around its two kernels (dcmt_set_kernel_timing; named by dcmt_last_path) in an extra untimed pass; .valu = the instruction-issue
+                count zero) / mean GPU time per step, HIP events on the launch stream.
+  --dump-outputs DIR   after the timed steps: a fixed, seeded sample of the output frames of the last timed step, DIR/dense.npy
+                (float32 [n][rows][cols]; DIR/dense_rank<r>.npy per rank when N > 1), at most 64 MB in all.
+--full adds everything else (each with runs of its own, after the timed steps):
+  verified      frames of the timed output buffer (first, middle, last of every rank's shard) against the CPU oracle, bit for bit.
+  roofline      .single_context and .per_kernel = the same frames through one context, the library's own events around its two
+                kernels (dcmt_set_kernel_timing; named by dcmt_last_path) in an extra untimed pass; .valu = the instruction-issue
                 side (what actually binds both kernels), from the SQ counters of profiles/valu_latest.json; .traffic from the
                 PMC passes of profiles/traffic_latest.json (both written by tools/collect_profiles.sh on the builder's box).
   configs       (rank 0, N = 1) the other BASELINE configs, each with its own roofline: [1] batch = 1 streamed,
@@ -149,6 +155,20 @@ def verify_against_oracle(np, out_frames, in_frames, what: str):
             bad = int((got.view(np.uint32) != want.view(np.uint32)).sum())
             return f"{what}: checked frame {k} differs from the oracle in {bad} pixels"
     return None
+
+
+DUMP_FRAMES = 32        # frames sampled by --dump-outputs over all ranks: 32 x 1.7 MB = 55 MB, under the 64 MB the dump may take
+
+
+def dump_outputs(np, torch, out_dir: str, d_dst, rank: int, world: int) -> None:
+    """--dump-outputs: the frames a caller of the timed path receives (its output buffer after the last timed step), as a
+    seeded sample -- the same frame indices in every run with the same arguments -- in float32."""
+    B = d_dst.shape[0]
+    n = min(B, max(1, DUMP_FRAMES // world))
+    idx = np.sort(np.random.default_rng(0).choice(B, size=n, replace=False))
+    frames = d_dst[torch.from_numpy(idx).to(d_dst.device)].cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dense.npy" if world == 1 else f"dense_rank{rank}.npy"), frames)
 
 
 def hbm_roofline(bytes_per_step: float, ms: float) -> dict:
@@ -423,6 +443,55 @@ def batch1_extras(torch, np, L, local_rank, host, uniq, d_src, d_dst, params):
     return extra
 
 
+def single_context_rooflines(torch, local_rank, B, d_src, d_dst, params, stream, steps, gpu_ms_per_step):
+    """--full: the roofline figures that take runs of their own (single_context, per_kernel) or come from profiles/ (traffic,
+    valu).  Returns them with the kernel path of the single-context step."""
+    from depth_completion_mt_amd import Context
+    # the same frames through ONE context on one stream (what a single call gives), and its live per-kernel split: untimed
+    # steps with the library's own events around its kernel groups
+    ctx = Context(local_rank, ROWS, COLS, B)
+    one_ms = timed(torch, lambda: ctx.complete_dev(d_src, d_dst, params, stream=stream.cuda_stream), steps, stream)
+    ctx.set_kernel_timing(True)
+    kt = [0.0, 0.0, 0.0, 0.0]
+    nk = 5
+    for _ in range(nk):
+        ctx.complete_dev(d_src, d_dst, params, stream=stream.cuda_stream)
+        t = ctx.last_kernel_times()
+        kt = [a + b / nk for a, b in zip(kt, (t["front"], t["k_pre"], t["k_fp_s"], t["behind"]))]
+    ctx.set_kernel_timing(False)
+    path = ctx.last_path()                      # e.g. "k_pre_p<Q16OUT> + k_fp_q"
+    k_pre_name, k_fp_name = (path.split(" + ") + ["?"])[:2] if " + " in path else (path, "?")
+    ctx.close()
+    roof = {}
+    roof["single_context"] = dict(hbm_roofline(B * BYTES_PER_FRAME, one_ms), value=B * 1e3 / one_ms, unit="frames/s",
+                                  note="one dcmt_complete_f32_dev call per step on one stream: the kernels run one after the other")
+    roof["per_kernel"] = {k_pre_name: dict(hbm_roofline(B * ROWS * COLS * 4 * 2, kt[1]), ms=kt[1], note="H2..H6: reads the sparse frame, writes X6 (algorithmic bytes of this kernel alone: 8 B/px)"),
+                          k_fp_name: dict(hbm_roofline(B * ROWS * COLS * 4 * 2, kt[2]), ms=kt[2], note="H7..H11 (and the gated rerun launches behind it, which return at once): reads X6, writes the dense frame"),
+                          "redo_launches_ms": kt[3]}
+    tr = load_profile_json("traffic_latest.json")
+    roof["traffic"] = tr.get("hbm_bytes_per_step") if tr else None
+    if tr and B == 1024:
+        roof["traffic_over_algorithmic"] = tr["hbm_bytes_per_step"] / (B * BYTES_PER_FRAME)
+    roof["traffic_source"] = "profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the 1024-frame step on the builder's box (tools/collect_profiles.sh), not measured in this run"
+    va = load_profile_json("valu_latest.json")
+    if va and B == 1024:
+        # instruction-issue side: what binds both kernels.  SQ_ACTIVE_INST_VALU counts quad-cycles (x4 = SIMD cycles issuing VALU)
+        issue_ms = {k: v["active_inst_valu"] * 4.0 / (N_SIMD * CLOCK_HZ) * 1e3 for k, v in va["kernels"].items()}
+        tot_issue = sum(issue_ms.values())
+        roof["valu"] = {"insts_per_step": sum(v["insts_valu"] for v in va["kernels"].values()),
+                        "insts_per_step_by_kernel": {k: v["insts_valu"] for k, v in va["kernels"].items()},
+                        "cycles_per_inst": sum(v["active_inst_valu"] for v in va["kernels"].values()) * 4.0 / sum(v["insts_valu"] for v in va["kernels"].values()),
+                        "issue_ms_per_step": tot_issue, "issue_ms_by_kernel": issue_ms,
+                        "frac_of_issue": tot_issue / gpu_ms_per_step,
+                        "peak": f"{N_SIMD} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz; min/max/med3/cmp/cndmask/DPP issue at ~4.4 cycles per wave64 instruction (tools/issue_probe.hip)",
+                        "source": "profiles/valu_latest.json: rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU pass of this step on the builder's box"}
+        roof["valu_frac"] = roof["valu"]["frac_of_issue"]     # share of the step's GPU time the SIMDs spend issuing VALU instructions
+        roof["limiter"] = "valu-issue" if roof["valu_frac"] > 0.6 else "mixed"
+        roof["bound_note"] = ("bound = the roofline the PATH is priced against (stencils at 8 algorithmic B/px: HBM; the contract's enum); "
+                              "limiter = what the kernels are limited by TODAY (valu_frac of the step is VALU issue time)")
+    return roof, path
+
+
 def load_profile_json(name):
     path = os.path.join(ROOT, "profiles", name)
     try:
@@ -445,8 +514,13 @@ def main():
     ap.add_argument("--parts", type=int, default=1,
                     help="contexts (one stream each) a rank's frames are spread over, never joined inside the timed region (default 1: one call "
                          "per step; configs['4_in_flight'] reports four)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the sub-results for BASELINE configs [1] [2] [3]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's output frames to DIR/dense.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also verify the timed output against the CPU oracle and measure the single-context and "
+                         "per-kernel rooflines, the other BASELINE configs, the next rows and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the sub-results for BASELINE configs [1] [2] [3] and the next rows")
     ap.add_argument("--batch1", action="store_true", help="also time the PCIe-inclusive forms of configs[1]")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank protocol (gloo, no GPU work, value is meaningless): tests only")
@@ -460,6 +534,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
     if not args.weak and args.total_frames < world:
         raise SystemExit("--total-frames must give every rank at least one frame")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.dry_run:
         return dry_run(args, rank, world)
 
@@ -526,6 +602,8 @@ def main():
     elapsed = time.perf_counter() - t0
     # HIP events on the launch streams: from the first stream's start to the last stream's end
     gpu_ms_per_step = max(a.elapsed_time(b) for a in ev0 for b in ev1) / args.steps
+    if args.dump_outputs:                               # before anything else writes to the timed output buffer
+        dump_outputs(np, torch, args.dump_outputs, d_dst, rank, world)
 
     # every frame must have converged inside the timed configuration (no skipped work).  The status goes through the same
     # all-reduce as the times, so that a failing rank cannot leave the others waiting in a collective.
@@ -534,9 +612,11 @@ def main():
         it_k, st_k = c.last_fill_iters(e - b)
         iters += list(it_k)
         st = st if st_k == L.OK else st_k
-    # ... and what was timed must be RIGHT: frames of the timed output buffer (first, middle, last of this rank's shard) against the oracle
+    # ... and with --full, what was timed must be RIGHT: frames of the timed output buffer (first, middle, last of this rank's shard) against the oracle
     check = sorted({0, B // 2, B - 1})
-    mismatch = verify_against_oracle(np, [d_dst[i].cpu().numpy() for i in check], [host[i % uniq] for i in check], f"rank {rank}")
+    mismatch = None
+    if args.full:
+        mismatch = verify_against_oracle(np, [d_dst[i].cpu().numpy() for i in check], [host[i % uniq] for i in check], f"rank {rank}")
     failed, wrong, elapsed, gpu_ms_per_step = all_reduce_max(dist, [0.0 if st == L.OK else 1.0, 0.0 if mismatch is None else 1.0, elapsed, gpu_ms_per_step], device="cuda")
     if failed or wrong:
         if dist is not None:
@@ -545,54 +625,19 @@ def main():
                                       "a frame needed more hole-closure applications than were enqueued: result invalid"))
 
     if rank == 0:
-        # the same frames through ONE context on one stream (what a single call gives), and its live per-kernel split: untimed
-        # steps with the library's own events around its kernel groups
-        ctx = Context(local_rank, ROWS, COLS, B)
-        one_ms = timed(torch, lambda: ctx.complete_dev(d_src, d_dst, params, stream=stream.cuda_stream), args.steps, stream)
-        ctx.set_kernel_timing(True)
-        kt = [0.0, 0.0, 0.0, 0.0]
-        nk = 5
-        for _ in range(nk):
-            ctx.complete_dev(d_src, d_dst, params, stream=stream.cuda_stream)
-            t = ctx.last_kernel_times()
-            kt = [a + b / nk for a, b in zip(kt, (t["front"], t["k_pre"], t["k_fp_s"], t["behind"]))]
-        ctx.set_kernel_timing(False)
-        path = ctx.last_path()                      # e.g. "k_pre_p<Q16OUT> + k_fp_q"
-        k_pre_name, k_fp_name = (path.split(" + ") + ["?"])[:2] if " + " in path else (path, "?")
-        ctx.close()
         roof = hbm_roofline(B * BYTES_PER_FRAME, gpu_ms_per_step)
+        path = ctxs[0].last_path()                  # e.g. "k_pre_p<Q16OUT> + k_fp_q"
+        kernel_note = ""
+        if args.full:
+            extra, path = single_context_rooflines(torch, local_rank, B, d_src, d_dst, params, stream, args.steps, gpu_ms_per_step)
+            roof.update(extra)
+            kernel_note = ("; per_kernel and single_context: the same frames through ONE context on one stream "
+                           "(the library's own events, dcmt_set_kernel_timing, 5 extra steps); rocprofv3 averages of that single-context step in profiles/")
         roof["kernel"] = (f"whole cascade per step = {path} (on frames that are multiples of 1/256 m, the KITTI depth format, X6 crosses HBM as 16-bit codes; "
                           "+ the gated f32 rerun and 3 redo launches, which return at once) of every part, HIP events on the launch streams "
                           "around the K timed steps (first start to last end); with more than one part the kernels of different parts overlap, so the per-kernel "
-                          "durations of a profile add up to more than the step; per_kernel and single_context: the same frames through ONE context on one stream "
-                          "(the library's own events, dcmt_set_kernel_timing, 5 extra steps); rocprofv3 averages of that single-context step in profiles/")
-        roof["single_context"] = dict(hbm_roofline(B * BYTES_PER_FRAME, one_ms), value=B * 1e3 / one_ms, unit="frames/s",
-                                      note="one dcmt_complete_f32_dev call per step on one stream: the kernels run one after the other")
+                          "durations of a profile add up to more than the step" + kernel_note)
         roof["kernels"] = path
-        roof["per_kernel"] = {k_pre_name: dict(hbm_roofline(B * ROWS * COLS * 4 * 2, kt[1]), ms=kt[1], note="H2..H6: reads the sparse frame, writes X6 (algorithmic bytes of this kernel alone: 8 B/px)"),
-                              k_fp_name: dict(hbm_roofline(B * ROWS * COLS * 4 * 2, kt[2]), ms=kt[2], note="H7..H11 (and the gated rerun launches behind it, which return at once): reads X6, writes the dense frame"),
-                              "redo_launches_ms": kt[3]}
-        tr = load_profile_json("traffic_latest.json")
-        roof["traffic"] = tr.get("hbm_bytes_per_step") if tr else None
-        if tr and B == 1024:
-            roof["traffic_over_algorithmic"] = tr["hbm_bytes_per_step"] / (B * BYTES_PER_FRAME)
-        roof["traffic_source"] = "profiles/traffic_latest.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the 1024-frame step on the builder's box (tools/collect_profiles.sh), not measured in this run"
-        va = load_profile_json("valu_latest.json")
-        if va and B == 1024:
-            # instruction-issue side: what binds both kernels.  SQ_ACTIVE_INST_VALU counts quad-cycles (x4 = SIMD cycles issuing VALU)
-            issue_ms = {k: v["active_inst_valu"] * 4.0 / (N_SIMD * CLOCK_HZ) * 1e3 for k, v in va["kernels"].items()}
-            tot_issue = sum(issue_ms.values())
-            roof["valu"] = {"insts_per_step": sum(v["insts_valu"] for v in va["kernels"].values()),
-                            "insts_per_step_by_kernel": {k: v["insts_valu"] for k, v in va["kernels"].items()},
-                            "cycles_per_inst": sum(v["active_inst_valu"] for v in va["kernels"].values()) * 4.0 / sum(v["insts_valu"] for v in va["kernels"].values()),
-                            "issue_ms_per_step": tot_issue, "issue_ms_by_kernel": issue_ms,
-                            "frac_of_issue": tot_issue / gpu_ms_per_step,
-                            "peak": f"{N_SIMD} SIMDs x {CLOCK_HZ / 1e9:.1f} GHz; min/max/med3/cmp/cndmask/DPP issue at ~4.4 cycles per wave64 instruction (tools/issue_probe.hip)",
-                            "source": "profiles/valu_latest.json: rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU pass of this step on the builder's box"}
-            roof["valu_frac"] = roof["valu"]["frac_of_issue"]     # share of the step's GPU time the SIMDs spend issuing VALU instructions
-            roof["limiter"] = "valu-issue" if roof["valu_frac"] > 0.6 else "mixed"
-            roof["bound_note"] = ("bound = the roofline the PATH is priced against (stencils at 8 algorithmic B/px: HBM; the contract's enum); "
-                                  "limiter = what the kernels are limited by TODAY (valu_frac of the step is VALU issue time)")
         line = {
             "metric": METRIC, "value": total * args.steps / elapsed, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak" if args.weak else "strong",
@@ -606,17 +651,18 @@ def main():
                        "contexts_per_gpu": parts, "frames_per_context": [e - b for b, e in bounds],
                        "in_flight": "one call per context and step, one stream per context, joined only at the ends of the timed region"},
             "roofline": roof,
-            "verified": True,
-            "verified_how": f"frames {check} of the timed output buffer (every rank: first, middle, last of its shard) bit-identical to the CPU oracle on the same inputs",
             "fill_iters_max": max(iters),
         }
-        if world == 1 and not args.no_configs:
+        if args.full:
+            line["verified"] = True
+            line["verified_how"] = f"frames {check} of the timed output buffer (every rank: first, middle, last of its shard) bit-identical to the CPU oracle on the same inputs"
+        if args.full and world == 1 and not args.no_configs:
             line["configs"] = other_configs(torch, local_rank, d_src, d_dst, params, stream, args.steps)
-        if world == 1 and not args.no_configs:
+        if args.full and world == 1 and not args.no_configs:
             line["next_rows"] = next_rows(torch, np, local_rank, d_src, d_dst, stream)
         if args.batch1:
             line.update(batch1_extras(torch, np, L, local_rank, host, uniq, d_src, d_dst, params))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(min(16, len(os.sched_getaffinity(0))))   # the box's CPU share for one GPU is 16
         print(json.dumps(line))
     for c in ctxs:

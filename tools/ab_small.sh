@@ -6,11 +6,10 @@ cp $LIB /tmp/libdcmt_hip.keep
 for rep in 1 2; do
 for v in "$@"; do
     cp "$v" $LIB; n=$(basename $v .so)
-    python bench.py --total-frames $N --no-configs --no-cpu-baseline > gpurun_out/ab_${n}_${N}_$rep.json 2> gpurun_out/ab_${n}_${N}_$rep.err || { cp /tmp/libdcmt_hip.keep $LIB; exit 1; }
-    python - <<P
-import json
-d=json.load(open('gpurun_out/ab_${n}_${N}_$rep.json')); print('$n', $N, round(d['value']), round(d['ms_per_step'],4), {k:(round(v['ms'],4) if isinstance(v,dict) else round(v,4)) for k,v in d['roofline']['per_kernel'].items()}, flush=True)
-P
+    out=$(python bench.py --full --total-frames $N --no-configs --no-cpu-baseline) || { cp /tmp/libdcmt_hip.keep $LIB; exit 1; }
+    echo "$out" | python -c "
+import json, sys
+d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$n', $N, round(d['value']), round(d['ms_per_step'],4), {k:(round(v['ms'],4) if isinstance(v,dict) else round(v,4)) for k,v in d['roofline']['per_kernel'].items()}, flush=True)"
 done
 done
 cp /tmp/libdcmt_hip.keep $LIB

@@ -9,7 +9,7 @@ R=$(pwd)
 OUT=$R/gpurun_out/$TAG
 SUM=$OUT/summary
 mkdir -p $OUT $SUM
-python bench.py > $SUM/${TAG}_bench.json 2> $OUT/bench.err
+python bench.py --full > $SUM/${TAG}_bench.json 2> $OUT/bench.err
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp
 B="$R/bench.py --no-cpu-baseline --no-configs"

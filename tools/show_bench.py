@@ -1,4 +1,4 @@
-"""Prints the numbers of one bench.py JSON line that are looked at while tuning.  usage: python tools/show_bench.py <file.json>"""
+"""Prints the numbers of one bench.py JSON line that are looked at while tuning.  usage: python tools/show_bench.py <file.json> (a bench.py --full line)"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 print("headline", round(d["value"]), "f/s", round(d["ms_per_step"], 4), "ms  frac", round(d["roofline"]["frac"], 4), "verified", d.get("verified"))
