@@ -13,15 +13,14 @@
 #include <cstring>
 #include <algorithm>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "dcmt.h"
 #include "dcmt_kernels_v1.h"
 #include "dcmt_kernels_fused.h"
 #include "dcmt_kernels_pair.h"
-#include "dcmt_kernels_fp_pair.h"
 #include "dcmt_kernels_fp_q16.h"
-#include "dcmt_kernels_fp_h16.h"
 #include "dcmt_kernels_slic.h"
 
 using namespace dcmt;
@@ -55,7 +54,6 @@ struct dcmt_ctx {
     hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int tev_valid = 0;                // the last call recorded all five
     int poison = 0;                   // env DCMT_POISON=1: fill the staging output with NaN before every host call
-    int chunk = 0;                    // frames per chunk of the fused path (0 = whole batch); env DCMT_CHUNK
     int xcd_map = 1;                  // XCD-aware workgroup->frame mapping; env DCMT_XCD_MAP=0 disables
     int wide = 1;                     // LDS-DMA row loads where alignment allows; env DCMT_WIDE=0 disables
     int fuse_fp = 1;                  // H7..H11 in one kernel (k_fp_s); env DCMT_FUSE_FP=0 keeps k_fill_s + k_post_s
@@ -63,15 +61,9 @@ struct dcmt_ctx {
     int pair = 1;                     // two columns per lane in H2..H6 (k_pre_p) where the width is even; env DCMT_PAIR=0 keeps k_pre_s
     int bands = 0;                    // row bands per strip in k_pre_p (0 = by batch size); env DCMT_BANDS
     int fbands = 0;                   // row bands per strip in k_fp_s (0 = by batch size); env DCMT_FBANDS
-    int fp_pair = 0;                  // env DCMT_FP_PAIR=1: two columns per lane in H7..H11 (k_fp_p: 8 % fewer VALU instructions, but its ~200 VGPRs leave 2 waves per SIMD and it is slower)
     int fp_q16 = 1;                   // X6 as 16-bit codes + k_fp_q wherever the frames allow it (multiples of 1/256 m: checked on the device, the f32
                                       // kernels rerun behind a raised flag); env DCMT_FP_Q16=0 disables
     int assume_filled = 1;            // k_fp_s / k_fp_q without the median >= thr select where the redo chain follows; env DCMT_ASSUME_FILLED=0 keeps it
-    int fp_h = 0;                     // env DCMT_FP_H=1: k_fp_h (the horizontal 31-maximum as a row pipeline through LDS: fewer VALU instructions, measured slower) instead of
-                                      // k_fp_q
-    int q16_breg = 1;                 // k_fp_q with the halo columns in a second register (120 output columns per wave, 3 waves per SIMD); 0 = wider strip
-                                      // overlap instead (88 output columns, 4 waves per SIMD: measured 2.5 % slower -- the kernel is bound by issue, not by
-                                      // occupancy); env DCMT_Q16_BREG
     int q16_min_waves = 2600;         // ... and the batch is large enough: k_fp_q has half as many, longer waves than k_fp_s (3 per SIMD instead of 4), so it
                                       // only pays from about one round of them on (measured, 352x1216, frames per call, whole step against the f32 kernels:
                                       // 128 -12 %, 256 +3 %, 512 +4 %, 1024 +5 %; threshold = 236 frames); env DCMT_Q16_MIN_WAVES
@@ -89,6 +81,7 @@ struct dcmt_ctx {
     int* bb_min = nullptr;            // LC fast path: per (frame, label) bounding boxes, grown on demand
     int* bb_max = nullptr;
     size_t bb_ints = 0;
+    int bbox_global = 0;              // LC fast path: the bounding-box pass without its per-workgroup LDS table; env DCMT_BBOX_GLOBAL
     // N3 (SLIC) scratch, allocated by the first dcmt_slic_labels_dev call
     int* slic_cells = nullptr;                  // two cell sets: counts [batch][cells] + overflow flags [batch] each, then the index lists [batch][cells][kSlicCellCap] each
     size_t slic_cell_cap = 0;                   // cells per frame that buffer holds
@@ -191,11 +184,6 @@ dim3 wave_grid(int strips, int batch, int xcd_map)
     return dim3(xcd_map ? 8 * (((batch / 8) * strips + 3) / 4) : (batch * strips + 3) / 4);
 }
 
-dim3 wave_grid_n(int strips, int batch, int xcd_map, int wpb)
-{
-    return dim3(xcd_map ? 8 * (((batch / 8) * strips + wpb - 1) / wpb) : (batch * strips + wpb - 1) / wpb);
-}
-
 dim3 tile_grid(int rows, int cols, int batch) { return dim3((cols + TW - 1) / TW, (rows + TH - 1) / TH, batch); }
 
 int k0_preset(uint32_t kb)
@@ -206,6 +194,14 @@ int k0_preset(uint32_t kb)
     dcmt_k0_diamond(k);
     if (kb == k0_bits(k)) return K0_DIAMOND;
     return -1;
+}
+
+// f(kind) with the k0 preset (a k0_preset result >= 0) as a compile-time constant
+template <typename F>
+void with_k0(int k0kind, F f)
+{
+    if (k0kind == K0_AS_COMPILED) f(std::integral_constant<int, K0_AS_COMPILED>{});
+    else f(std::integral_constant<int, K0_DIAMOND>{});
 }
 
 // The hole-closure loop shared by both paths.  `launch_app(i)` enqueues application i
@@ -249,12 +245,11 @@ int fill_loop(dcmt_ctx* ctx, int batch, const dcmt_params* p, hipStream_t st, bo
 // Fast path.  Whole chain: k_pre_s -> k_fp_s, then three launches that return at once for every frame
 // k_fp_s finished (k_fill_s redo, k_fill_s loop applications, k_post_s only_if_holes).  stop_after probes:
 // k_pre_s -> k_fill_s (-> loop) -> k_post_s / copy.  Preconditions are checked by the caller.
-// ctx->chunk (env DCMT_CHUNK, default 0 = off) walks the batch in chunks; measured slower, kept as a knob.
 // d_x4 != nullptr: X4 is already there (LC fast path): k_pre_s only runs H5 + H6 on it.
-// d_src16 != nullptr: uint16 ingest fused into k_pre_s.
-int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* d_dst, int rows, int cols, int batch,
+// src16 != nullptr: uint16 ingest fused into k_pre_s.  cf: N1's (a, b) per frame, applied while k_pre_s loads.
+int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, int rows, int cols, int batch,
                     const dcmt_params* p, hipStream_t st, bool sync_loop, const float* d_x4 = nullptr,
-                    const uint16_t* d_src16 = nullptr, float in_scale = 1.0f, const float* coef = nullptr)
+                    const uint16_t* src16 = nullptr, float in_scale = 1.0f, const float* cf = nullptr)
 {
     const int stop = p->stop_after;
     ctx->last_stream = st;
@@ -265,10 +260,14 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* d_dst,
     auto stamp = [&](int i) { if (ctx->timing && ctx->tev[i]) (void)hipEventRecord(ctx->tev[i], st); };
     stamp(1);
     const size_t fe = (size_t)rows * cols;
-    const int chunk = (ctx->chunk > 0 && !sync_loop) ? ctx->chunk : batch;   // the host-synchronised loop works on the whole batch
-    const hipStream_t ps = st;
     const bool bl = p->blur == DCMT_BLUR_GAUSSIAN;
-    int rc = DCMT_OK, apps_all = 0;
+    const int xm = (ctx->xcd_map && batch % 8 == 0) ? 1 : 0;
+    const dim3 b256(256);
+    const float* src = d_x4 ? d_x4 : d_src;
+    float* x6 = ctx->x5;
+    float* pp0 = ctx->pp[0];
+    float* pp1 = ctx->pp[1];
+    int* cnt = ctx->counters;
     // 16-bit X6: a frame that is no multiple of 1/256 m costs the attempt AND the f32 rerun; once a call has raised the flag (seen
     // here at the start of a later call, without synchronising) the next 63 calls go straight to the f32 kernels.  (The uint16 entry
     // point's depths are multiples of 1/256 m by construction, but a payload beyond 30719 -- 119.996 m -- has no code either.)
@@ -277,209 +276,163 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* d_dst,
         if (*(volatile int*)ctx->q16_seen) { *(volatile int*)ctx->q16_seen = 0; ctx->q16_skip = 63; }
         if (ctx->q16_skip > 0) { --ctx->q16_skip; q16_try = false; }
     }
-    for (int f0 = 0; f0 < batch; f0 += chunk) {
-        const int nb = batch - f0 < chunk ? batch - f0 : chunk;
-        const int xm = (ctx->xcd_map && nb % 8 == 0) ? 1 : 0;
-        const float* src = (d_x4 ? d_x4 : d_src) + f0 * fe;
-        float* dst = d_dst + f0 * fe;
-        float* x6 = ctx->x5 + f0 * fe;
-        float* pp0 = ctx->pp[0] + f0 * fe;
-        float* pp1 = ctx->pp[1] + f0 * fe;
-        int* cnt = ctx->counters + (size_t)f0 * kCntStride;
-        const float* cf = coef ? coef + 2 * (size_t)f0 : nullptr;
-        // table mode: only the k_fp_s path reads X6 through the per-column table (the probes and the unfused kernels get a fully written X6)
-        int bands = 1;                      // row bands of k_pre_p = table slots per frame
-        bool q16 = false;                   // this chunk's X6 is 16-bit codes (in ctx->x6q)
-        int* qbad = ctx->q16_bad;           // ... and the flag its attempt raises on a frame that has none
-        int* tc = (stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table) ? ctx->tb : nullptr;   // chunks follow each other in the stream: each may use the whole table
-        {
-            float* o6 = stop == DCMT_STAGE_EXTEND ? dst : x6;
-            // LDS-DMA rows need 16-byte aligned sources: cols % 4 == 0 and a 16-byte aligned base
-            const bool wide = ctx->wide && cols % 4 == 0 && ((uintptr_t)src % 16 == 0) && !d_src16;
-            const uint16_t* src16 = d_src16 ? d_src16 + f0 * fe : nullptr;
-#define DCMT_PRE(KIND, WIDE) { using G = PreS<KIND, WIDE>; const int strips = (cols + G::VW - 1) / G::VW; \
-                if (d_x4) hipLaunchKernelGGL((k_pre_s<KIND, WIDE, true, false>), wave_grid(strips, nb, xm), dim3(256), 0, ps, (const void*)src, o6, \
-                                             rows, cols, strips, nb, xm, p->max_depth, p->valid_thresh, 1.0f, (const float*)nullptr, tc, cnt); \
-                else if (src16) hipLaunchKernelGGL((k_pre_s<KIND, false, false, true>), wave_grid(strips, nb, xm), dim3(256), 0, ps, (const void*)src16, o6, \
-                                             rows, cols, strips, nb, xm, p->max_depth, p->valid_thresh, in_scale, (const float*)nullptr, tc, cnt); \
-                else if (cf) hipLaunchKernelGGL((k_pre_s<KIND, WIDE, false, false, true>), wave_grid(strips, nb, xm), dim3(256), 0, ps, (const void*)src, o6, \
-                                        rows, cols, strips, nb, xm, p->max_depth, p->valid_thresh, 1.0f, cf, tc, cnt); \
-                else hipLaunchKernelGGL((k_pre_s<KIND, WIDE, false, false>), wave_grid(strips, nb, xm), dim3(256), 0, ps, (const void*)src, o6, \
-                                        rows, cols, strips, nb, xm, p->max_depth, p->valid_thresh, 1.0f, (const float*)nullptr, tc, cnt); }
-            // two columns per lane (k_pre_p) wherever a lane's 8-byte accesses are aligned: even width, 8-byte aligned frames
-            const bool pair = ctx->pair && cols % 2 == 0 && cols >= 8 && ((uintptr_t)(src16 ? (const void*)src16 : (const void*)src) % (src16 ? 4 : 8) == 0) &&
-                              ((uintptr_t)o6 % 8 == 0);
-            // row bands: full-height strips of a small batch leave most wave slots empty; bands need the (ti, bi) table (one slot per band)
-            if (pair && tc) {
-                const int pstr = (cols + PreP<K0_AS_COMPILED, false>::VW - 1) / PreP<K0_AS_COMPILED, false>::VW;
-                bands = ctx->bands > 0 ? ctx->bands : ((long long)nb * pstr >= 2560 ? 1 : (int)((2560 + (long long)nb * pstr - 1) / ((long long)nb * pstr)));
-                if (bands > rows / 32) bands = rows / 32 > 0 ? rows / 32 : 1;
-                if (bands > kMaxBands) bands = kMaxBands;
-            }
-#define DCMT_PREP(KIND, QOUT, O6, QBAD, GATE, QCLR) { using G4 = PreP<KIND, true>; using G0 = PreP<KIND, false>; \
-                if (d_x4) { const int strips = (cols + G4::VW - 1) / G4::VW; \
-                    hipLaunchKernelGGL((k_pre_p<KIND, true, false, false, QOUT>), wave_grid(strips * bands, nb, xm), dim3(256), 0, ps, (const void*)src, O6, \
-                                       rows, cols, strips, bands, nb, xm, p->max_depth, p->valid_thresh, 1.0f, (const float*)nullptr, tc, cnt, QBAD, GATE, ctx->q16_seen_dev, QCLR); } \
-                else { const int strips = (cols + G0::VW - 1) / G0::VW; \
-                    if (src16) hipLaunchKernelGGL((k_pre_p<KIND, false, true, false, QOUT>), wave_grid(strips * bands, nb, xm), dim3(256), 0, ps, (const void*)src16, O6, \
-                                       rows, cols, strips, bands, nb, xm, p->max_depth, p->valid_thresh, in_scale, (const float*)nullptr, tc, cnt, QBAD, GATE, ctx->q16_seen_dev, QCLR); \
-                    else if (cf) { if constexpr (!QOUT) hipLaunchKernelGGL((k_pre_p<KIND, false, false, true>), wave_grid(strips * bands, nb, xm), dim3(256), 0, ps, (const void*)src, O6, \
-                                       rows, cols, strips, bands, nb, xm, p->max_depth, p->valid_thresh, 1.0f, cf, tc, cnt, QBAD, GATE, ctx->q16_seen_dev, QCLR); } \
-                    else hipLaunchKernelGGL((k_pre_p<KIND, false, false, false, QOUT>), wave_grid(strips * bands, nb, xm), dim3(256), 0, ps, (const void*)src, O6, \
-                                       rows, cols, strips, bands, nb, xm, p->max_depth, p->valid_thresh, 1.0f, (const float*)nullptr, tc, cnt, QBAD, GATE, ctx->q16_seen_dev, QCLR); } }
-            // 16-bit X6 (k_pre_p<Q16OUT> -> k_fp_q): the whole chain in table mode, two columns per lane, the reference's constants, no
-            // normalisation in front (normalised depths are no multiples of 1/256)
-            // in place (or overlapping) f32 calls never take the 16-bit attempt: k_fp_q writes dst BEFORE the gated f32 rerun would read src again
-            // (the f32 kernels alone are alias-safe: src is only read by k_pre into ctx scratch, dst is written last)
-            const bool src_dst_overlap = !src16 && (uintptr_t)src < (uintptr_t)(dst + (size_t)nb * fe) && (uintptr_t)dst < (uintptr_t)(src + (size_t)nb * fe);
-            q16 = q16_try && (long long)nb * ((cols + FpP::VW - 1) / FpP::VW) >= ctx->q16_min_waves && pair && tc && !cf && Q16::params_ok(p->max_depth, p->valid_thresh) && (uintptr_t)dst % 8 == 0 &&
-                  (!src16 || in_scale == 0.00390625f) && !src_dst_overlap;
-            if (q16) { const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc; }
-            float* x6q = reinterpret_cast<float*>(ctx->x6q + f0 * fe);
-            if (q16) {
-                // this attempt's flag (cleared by the previous attempt's kernel, or by dcmt_create) and the next one's, which this attempt's kernel clears
-                qbad = ctx->q16_bad + ctx->q16_attempts % kQ16Flags;
-                int* qnext = ctx->q16_bad + (ctx->q16_attempts + 1) % kQ16Flags;
-                ++ctx->q16_attempts;
-                if (k0kind == K0_AS_COMPILED) DCMT_PREP(K0_AS_COMPILED, true, x6q, qbad, (const int*)nullptr, qnext) else DCMT_PREP(K0_DIAMOND, true, x6q, qbad, (const int*)nullptr, qnext)
-            } else if (pair) {
-                if (k0kind == K0_AS_COMPILED) DCMT_PREP(K0_AS_COMPILED, false, o6, (int*)nullptr, (const int*)nullptr, (int*)nullptr) else DCMT_PREP(K0_DIAMOND, false, o6, (int*)nullptr, (const int*)nullptr, (int*)nullptr)
-            } else {
-                if (k0kind == K0_AS_COMPILED) { if (wide) DCMT_PRE(K0_AS_COMPILED, true) else DCMT_PRE(K0_AS_COMPILED, false) }
-                else { if (wide) DCMT_PRE(K0_DIAMOND, true) else DCMT_PRE(K0_DIAMOND, false) }
-            }
-#undef DCMT_PRE
-            DCMT_HIP(ctx, hipGetLastError());
-            stamp(2);
-            std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s%s%s", d_x4 ? "k_label_bbox + k_label_stage + " : "",
-                          q16 ? (src16 ? "k_pre_p<U16,Q16OUT>" : "k_pre_p<Q16OUT>") : pair ? (d_x4 ? "k_pre_p<START4>" : src16 ? "k_pre_p<U16>" : cf ? "k_pre_p<NORM>" : "k_pre_p") : "k_pre_s",
-                          bands > 1 ? " (row bands)" : "");
-            if (stop == DCMT_STAGE_EXTEND) continue;
-        }
-        const int fstrips = (cols + FillS::VW - 1) / FillS::VW;
-        const dim3 fgrid(((fstrips + 3) / 4) * nb);
-        if (stop == DCMT_STAGE_FINAL && ctx->fuse_fp) {
-            // one kernel for H7..H11; frames it leaves with holes are redone by the unfused kernels below
-            const int pstrips = (cols + PostS::VW - 1) / PostS::VW;
-            const dim3 pg(((pstrips + 3) / 4) * nb), b256(256);
-            // k_fp_s deals (frame, strip) pairs to waves in one flat sequence (per XCD with the XCD map): no half-empty workgroups
-            // row bands for k_fp_s: a batch whose strips are fewer than two waves per SIMD runs every strip as fb_s bands, about one
-            // round of three waves per SIMD in all (a band pays 19 + 19 rows of halo and 19 steps of pipeline: only worth it while the
-            // GPU is not full -- from ~100 frames of 1216 columns on there is one band)
-            int fb_s = 1;
-            if (tc) {
-                const long long w1 = (long long)nb * pstrips;
-                fb_s = ctx->fbands > 0 ? ctx->fbands : (w1 >= 2048 ? 1 : (int)((3072 + w1 / 2) / w1));
-                if (fb_s > rows / 32) fb_s = rows / 32 > 0 ? rows / 32 : 1;
-                if (fb_s < 1) fb_s = 1;
-            }
-            const dim3 fpg = wave_grid(pstrips * fb_s, nb, xm);
-            // two columns per lane (k_fp_p) wherever a lane's 8-byte stores are aligned: even width, 8-byte aligned frames
-            const bool fpp = ctx->fp_pair && cols % 2 == 0 && cols >= 8 && ((uintptr_t)dst % 8 == 0);
-            // frames this kernel leaves with holes are recomputed by the redo chain below whenever that chain is enqueued (always on the host
-            // entry points, with spec_fill_iters >= 1 on the device ones): then the kernel may leave out the select that only such frames need
-            const bool filled = bl && ctx->assume_filled && (sync_loop || (p->spec_fill_iters >= 1 && p->max_fill_iters >= 1));
-            if (q16) {
-                const void* xq = ctx->x6q + f0 * fe;
-#define DCMT_FPQ(BL, BREG, FILLED) { const int qstrips = (cols + FpQ::vw<BREG>() - 1) / FpQ::vw<BREG>(); \
-                    hipLaunchKernelGGL((k_fp_q<BL, true, BREG, FILLED>), wave_grid(qstrips, nb, xm), b256, 0, st, xq, dst, cnt, rows, cols, qstrips, nb, xm, \
-                                       p->max_depth, p->valid_thresh, (const int*)tc, bands); }
-#define DCMT_FPH(BL, FILLED) { const int qstrips = (cols + FpP::VW - 1) / FpP::VW; \
-                    hipLaunchKernelGGL((k_fp_h<BL, FILLED>), wave_grid(qstrips, nb, xm), b256, 0, st, xq, dst, cnt, rows, cols, qstrips, nb, xm, \
-                                       p->max_depth, p->valid_thresh, (const int*)tc, bands); }
-                // (k_fp_h<BLUR, !FILLED> -- the select of LO :184 kept, only where a device caller asks for no speculative loop applications -- needs more
-                //  than the 168 registers three waves per SIMD leave: that combination stays with k_fp_q)
-                const bool fph = ctx->fp_h && ctx->q16_breg && (filled || !bl);
-                if (fph) { if (filled) DCMT_FPH(true, true) else DCMT_FPH(false, false) }
-                else if (ctx->q16_breg) { if (filled) DCMT_FPQ(true, true, true) else if (bl) DCMT_FPQ(true, true, false) else DCMT_FPQ(false, true, false) }
-                else               { if (bl) DCMT_FPQ(true, false, false) else DCMT_FPQ(false, false, false) }
-#undef DCMT_FPQ
-#undef DCMT_FPH
-                {
-                    // frames that are no multiples of 1/256 m: both f32 kernels again, gated on the flag the attempt raised (they return at once otherwise)
-                    // (the uint16 entry point too: a payload beyond 30719 = 119.996 m has no code)
-                    float* o6 = x6;
-                    const uint16_t* src16 = d_src16 ? d_src16 + f0 * fe : nullptr; const float* cf = nullptr; const hipStream_t ps = st;
-                    const float* src = (d_x4 ? d_x4 : d_src) + f0 * fe;
-                    if (k0kind == K0_AS_COMPILED) DCMT_PREP(K0_AS_COMPILED, false, o6, (int*)nullptr, (const int*)qbad, (int*)nullptr) else DCMT_PREP(K0_DIAMOND, false, o6, (int*)nullptr, (const int*)qbad, (int*)nullptr)
-                    if (filled) hipLaunchKernelGGL((k_fp_s<true, true>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)qbad, fb_s);
-                    else if (bl) hipLaunchKernelGGL((k_fp_s<true>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)qbad, fb_s);
-                    else    hipLaunchKernelGGL((k_fp_s<false>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)qbad, fb_s);
-                }
-            }
-            else if (fpp) {
-                const int qstrips = (cols + FpP::VW - 1) / FpP::VW;
-                const dim3 qg = wave_grid_n(qstrips, nb, xm, FpP::WPB), qb(64 * FpP::WPB);
-                if (bl) hipLaunchKernelGGL((k_fp_p<true>), qg, qb, 0, st, x6, dst, cnt, rows, cols, qstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands);
-                else    hipLaunchKernelGGL((k_fp_p<false>), qg, qb, 0, st, x6, dst, cnt, rows, cols, qstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands);
-            }
-            else if (filled) hipLaunchKernelGGL((k_fp_s<true, true>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)nullptr, fb_s);
-            else if (bl) hipLaunchKernelGGL((k_fp_s<true>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)nullptr, fb_s);
-            else    hipLaunchKernelGGL((k_fp_s<false>), fpg, b256, 0, st, x6, dst, cnt, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, (const int*)tc, bands, (const int*)nullptr, fb_s);
-#undef DCMT_PREP
-            DCMT_HIP(ctx, hipGetLastError());
-            stamp(3);
-            { const size_t n_ = std::strlen(ctx->last_path);
-              std::snprintf(ctx->last_path + n_, sizeof ctx->last_path - n_, " + %s", q16 ? (ctx->fp_h && ctx->q16_breg && (filled || !bl) ? "k_fp_h" : "k_fp_q") : fpp ? "k_fp_p" : (fb_s > 1 ? "k_fp_s (row bands)" : "k_fp_s")); }
-            ctx->last_has_loop = 1;
-            const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
-            if (n_redo > 0) {
-                if (sync_loop) {      // host entry points: look before launching anything else
-                    DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride, hipMemcpyDeviceToHost, st));
-                    DCMT_HIP(ctx, hipStreamSynchronize(st));
-                    bool any = false;
-                    for (int f = 0; f < batch; ++f) any |= ctx->h_counters[(size_t)f * kCntStride + 1] > 0;
-                    if (!any) { if (p->verbose) for (int f = 0; f < batch; ++f) std::printf("0\n"); continue; }
-                }
-                hipLaunchKernelGGL(k_fill_s, fgrid, b256, 0, st, x6, pp0, cnt, rows, cols, fstrips, nb, xm, p->valid_thresh, 0, 1, (const int*)tc, bands,
-                                   q16 ? (const unsigned short*)(ctx->x6q + f0 * fe) : (const unsigned short*)nullptr, (const int*)qbad);
-                int apps = 0;
-                const int lrc = fill_loop(ctx, batch, p, st, sync_loop, [&](int i) {
-                    hipLaunchKernelGGL(k_fill_s, fgrid, b256, 0, st, (i & 1) ? pp0 : pp1, (i & 1) ? pp1 : pp0, cnt, rows, cols,
-                                       fstrips, nb, xm, p->valid_thresh, i, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
-                }, &apps);
-                if (lrc != DCMT_OK && lrc != DCMT_E_NOT_CONVERGED) return lrc;
-                if (lrc != DCMT_OK) rc = lrc;
-                apps_all = apps;
-                if (bl) hipLaunchKernelGGL((k_post_s<11, true>), pg, b256, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, 1);
-                else    hipLaunchKernelGGL((k_post_s<11, false>), pg, b256, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, pstrips, nb, xm, p->max_depth, p->valid_thresh, 1);
-                DCMT_HIP(ctx, hipGetLastError());
-            }
-            stamp(4);
-            ctx->tev_valid = ctx->timing && chunk == batch;
-            continue;
-        }
-        hipLaunchKernelGGL(k_fill_s, fgrid, dim3(256), 0, st, x6, stop == DCMT_STAGE_FILL31 ? dst : pp0, cnt, rows, cols,
-                           fstrips, nb, xm, p->valid_thresh, 0, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
-        DCMT_HIP(ctx, hipGetLastError());
-        if (stop == DCMT_STAGE_FILL31) continue;
-
-        ctx->last_has_loop = 1;
-        int apps = 0;
-        const int lrc = fill_loop(ctx, batch, p, st, sync_loop, [&](int i) {
-            hipLaunchKernelGGL(k_fill_s, fgrid, dim3(256), 0, st, (i & 1) ? pp0 : pp1, (i & 1) ? pp1 : pp0, cnt, rows, cols,
-                               fstrips, nb, xm, p->valid_thresh, i, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
-        }, &apps);
-        if (lrc != DCMT_OK && lrc != DCMT_E_NOT_CONVERGED) return lrc;
-        if (lrc != DCMT_OK) rc = lrc;
-        apps_all = apps;
-
-        if (stop <= DCMT_STAGE_FILLLOOP) {
-            hipLaunchKernelGGL((k_post_v1<TH, TW>), tile_grid(rows, cols, nb), dim3(kThreads), 0, st, pp0, pp1, dst, cnt, apps,
-                               rows, cols, p->max_depth, p->valid_thresh, p->blur, 8);
-        } else {
-            const int strips = (cols + PostS::VW - 1) / PostS::VW;
-            const dim3 g(((strips + 3) / 4) * nb), b(256);
-#define DCMT_POST(MODE, BLUR) hipLaunchKernelGGL((k_post_s<MODE, BLUR>), g, b, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, strips, \
-                                                 nb, xm, p->max_depth, p->valid_thresh, 0)
-            if (stop == DCMT_STAGE_MEDIAN5) DCMT_POST(9, false);
-            else if (stop == DCMT_STAGE_BLUR) { if (bl) DCMT_POST(10, true); else DCMT_POST(10, false); }
-            else { if (bl) DCMT_POST(11, true); else DCMT_POST(11, false); }
-#undef DCMT_POST
-        }
-        DCMT_HIP(ctx, hipGetLastError());
+    // table mode: only the k_fp_s path reads X6 through the per-column table (the probes and the unfused kernels get a fully written X6)
+    int* tc = (stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table) ? ctx->tb : nullptr;
+    float* o6 = stop == DCMT_STAGE_EXTEND ? dst : x6;
+    // LDS-DMA rows need 16-byte aligned sources: cols % 4 == 0 and a 16-byte aligned base
+    const bool wide = ctx->wide && cols % 4 == 0 && ((uintptr_t)src % 16 == 0) && !src16;
+    // two columns per lane (k_pre_p) wherever a lane's 8-byte accesses are aligned: even width, 8-byte aligned frames
+    const bool pair = ctx->pair && cols % 2 == 0 && cols >= 8 && ((uintptr_t)(src16 ? (const void*)src16 : (const void*)src) % (src16 ? 4 : 8) == 0) &&
+                      ((uintptr_t)o6 % 8 == 0);
+    // row bands: full-height strips of a small batch leave most wave slots empty; bands need the (ti, bi) table (one slot per band)
+    int bands = 1;                          // row bands of k_pre_p = table slots per frame
+    if (pair && tc) {
+        const int pstr = (cols + PreP<K0_AS_COMPILED, false>::VW - 1) / PreP<K0_AS_COMPILED, false>::VW;
+        bands = ctx->bands > 0 ? ctx->bands : ((long long)batch * pstr >= 2560 ? 1 : (int)((2560 + (long long)batch * pstr - 1) / ((long long)batch * pstr)));
+        if (bands > rows / 32) bands = rows / 32 > 0 ? rows / 32 : 1;
+        if (bands > kMaxBands) bands = kMaxBands;
     }
-    ctx->last_apps_launched = apps_all;
+    // 16-bit X6 (k_pre_p<Q16OUT> -> k_fp_q): the whole chain in table mode, two columns per lane, the reference's constants, no
+    // normalisation in front (normalised depths are no multiples of 1/256)
+    // in place (or overlapping) f32 calls never take the 16-bit attempt: k_fp_q writes dst BEFORE the gated f32 rerun would read src again
+    // (the f32 kernels alone are alias-safe: src is only read by k_pre into ctx scratch, dst is written last)
+    const bool src_dst_overlap = !src16 && (uintptr_t)src < (uintptr_t)(dst + (size_t)batch * fe) && (uintptr_t)dst < (uintptr_t)(src + (size_t)batch * fe);
+    const bool q16 = q16_try && (long long)batch * ((cols + FpQ::VW - 1) / FpQ::VW) >= ctx->q16_min_waves && pair && tc && !cf &&
+                     Q16::params_ok(p->max_depth, p->valid_thresh) && (uintptr_t)dst % 8 == 0 && (!src16 || in_scale == 0.00390625f) && !src_dst_overlap;
+    if (q16) { const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc; }
+
+    const void* in = src16 ? (const void*)src16 : (const void*)src;    // (cf is nullptr with d_x4 and with src16)
+    const float scale = src16 ? in_scale : 1.0f;
+    // k_pre_s (one column per lane) into o6
+    auto pre_s = [&](auto kind, auto wide_) {
+        constexpr int KIND = decltype(kind)::value;
+        constexpr bool WIDE = decltype(wide_)::value;
+        auto* k = d_x4 ? k_pre_s<KIND, WIDE, true, false> : src16 ? k_pre_s<KIND, false, false, true> :
+                  cf ? k_pre_s<KIND, WIDE, false, false, true> : k_pre_s<KIND, WIDE, false, false>;
+        const int strips = (cols + PreS<KIND, WIDE>::VW - 1) / PreS<KIND, WIDE>::VW;
+        hipLaunchKernelGGL(k, wave_grid(strips, batch, xm), b256, 0, st, in, o6, rows, cols, strips, batch, xm, p->max_depth, p->valid_thresh,
+                           scale, cf, tc, cnt);
+    };
+    // k_pre_p (two columns per lane) into o: X6 in f32, or as 16-bit codes (QOUT) that raise *qbad where a value has none and clear
+    // *qclr; gate != nullptr: the launch returns at once unless *gate is raised.  (The 16-bit attempt never has cf.)
+    auto pre_p = [&](auto kind, auto qout, float* o, int* qbad, const int* gate, int* qclr) {
+        constexpr int KIND = decltype(kind)::value;
+        constexpr bool QOUT = decltype(qout)::value;
+        auto* k = d_x4 ? k_pre_p<KIND, true, false, false, QOUT> : src16 ? k_pre_p<KIND, false, true, false, QOUT> :
+                  cf ? k_pre_p<KIND, false, false, true> : k_pre_p<KIND, false, false, false, QOUT>;
+        const int vw = d_x4 ? PreP<KIND, true>::VW : PreP<KIND, false>::VW;
+        const int strips = (cols + vw - 1) / vw;
+        hipLaunchKernelGGL(k, wave_grid(strips * bands, batch, xm), b256, 0, st, in, o, rows, cols, strips, bands, batch, xm, p->max_depth,
+                           p->valid_thresh, scale, cf, tc, cnt, qbad, gate, ctx->q16_seen_dev, qclr);
+    };
+    int* qbad = ctx->q16_bad;               // the flag of this call's 16-bit attempt
+    if (q16) {
+        // this attempt's flag (cleared by the previous attempt's kernel, or by dcmt_create) and the next one's, which this attempt's kernel clears
+        qbad = ctx->q16_bad + ctx->q16_attempts % kQ16Flags;
+        int* qnext = ctx->q16_bad + (ctx->q16_attempts + 1) % kQ16Flags;
+        ++ctx->q16_attempts;
+        with_k0(k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q), qbad, nullptr, qnext); });
+    } else if (pair) {
+        with_k0(k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, o6, nullptr, nullptr, nullptr); });
+    } else {
+        with_k0(k0kind, [&](auto kind) { if (wide) pre_s(kind, std::true_type{}); else pre_s(kind, std::false_type{}); });
+    }
+    DCMT_HIP(ctx, hipGetLastError());
+    stamp(2);
+    std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s%s%s", d_x4 ? "k_label_bbox + k_label_stage + " : "",
+                  q16 ? (src16 ? "k_pre_p<U16,Q16OUT>" : "k_pre_p<Q16OUT>") : pair ? (d_x4 ? "k_pre_p<START4>" : src16 ? "k_pre_p<U16>" : cf ? "k_pre_p<NORM>" : "k_pre_p") : "k_pre_s",
+                  bands > 1 ? " (row bands)" : "");
+    if (stop == DCMT_STAGE_EXTEND) return DCMT_OK;
+
+    const int fstrips = (cols + FillS::VW - 1) / FillS::VW;
+    const dim3 fgrid(((fstrips + 3) / 4) * batch);
+    // the hole-closure loop's applications 1, 2, ... (pp[0] <-> pp[1])
+    auto fill_apps = [&](int* apps) {
+        return fill_loop(ctx, batch, p, st, sync_loop, [&](int i) {
+            hipLaunchKernelGGL(k_fill_s, fgrid, b256, 0, st, (i & 1) ? pp0 : pp1, (i & 1) ? pp1 : pp0, cnt, rows, cols,
+                               fstrips, batch, xm, p->valid_thresh, i, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
+        }, apps);
+    };
+    if (stop == DCMT_STAGE_FINAL && ctx->fuse_fp) {
+        // one kernel for H7..H11; frames it leaves with holes are redone by the unfused kernels below
+        const int pstrips = (cols + PostS::VW - 1) / PostS::VW;
+        // k_fp_s deals (frame, strip) pairs to waves in one flat sequence (per XCD with the XCD map): no half-empty workgroups
+        // row bands for k_fp_s: a batch whose strips are fewer than two waves per SIMD runs every strip as fb_s bands, about one
+        // round of three waves per SIMD in all (a band pays 19 + 19 rows of halo and 19 steps of pipeline: only worth it while the
+        // GPU is not full -- from ~100 frames of 1216 columns on there is one band)
+        int fb_s = 1;
+        if (tc) {
+            const long long w1 = (long long)batch * pstrips;
+            fb_s = ctx->fbands > 0 ? ctx->fbands : (w1 >= 2048 ? 1 : (int)((3072 + w1 / 2) / w1));
+            if (fb_s > rows / 32) fb_s = rows / 32 > 0 ? rows / 32 : 1;
+            if (fb_s < 1) fb_s = 1;
+        }
+        // frames this kernel leaves with holes are recomputed by the redo chain below whenever that chain is enqueued (always on the host
+        // entry points, with spec_fill_iters >= 1 on the device ones): then the kernel may leave out the select that only such frames need
+        const bool filled = bl && ctx->assume_filled && (sync_loop || (p->spec_fill_iters >= 1 && p->max_fill_iters >= 1));
+        const int* gate = nullptr;          // k_fp_s below: the path itself, or the f32 rerun behind the 16-bit attempt
+        if (q16) {
+            auto* fpq = filled ? k_fp_q<true, true> : bl ? k_fp_q<true, false> : k_fp_q<false, false>;
+            const int qstrips = (cols + FpQ::VW - 1) / FpQ::VW;
+            hipLaunchKernelGGL(fpq, wave_grid(qstrips, batch, xm), b256, 0, st, (const void*)ctx->x6q, dst, cnt, rows, cols, qstrips, batch, xm,
+                               p->max_depth, p->valid_thresh, (const int*)tc, bands);
+            // frames that are no multiples of 1/256 m: both f32 kernels again, gated on the flag the attempt raised (they return at once otherwise)
+            // (the uint16 entry point too: a payload beyond 30719 = 119.996 m has no code)
+            with_k0(k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, x6, nullptr, qbad, nullptr); });
+            gate = qbad;
+        }
+        auto* fps = filled ? k_fp_s<true, true> : bl ? k_fp_s<true> : k_fp_s<false>;
+        hipLaunchKernelGGL(fps, wave_grid(pstrips * fb_s, batch, xm), b256, 0, st, x6, dst, cnt, rows, cols, pstrips, batch, xm, p->max_depth,
+                           p->valid_thresh, (const int*)tc, bands, gate, fb_s);
+        DCMT_HIP(ctx, hipGetLastError());
+        stamp(3);
+        { const size_t n_ = std::strlen(ctx->last_path);
+          std::snprintf(ctx->last_path + n_, sizeof ctx->last_path - n_, " + %s", q16 ? "k_fp_q" : (fb_s > 1 ? "k_fp_s (row bands)" : "k_fp_s")); }
+        ctx->last_has_loop = 1;
+        int rc = DCMT_OK, apps = 0;
+        const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
+        if (n_redo > 0) {
+            if (sync_loop) {      // host entry points: look before launching anything else
+                DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride, hipMemcpyDeviceToHost, st));
+                DCMT_HIP(ctx, hipStreamSynchronize(st));
+                bool any = false;
+                for (int f = 0; f < batch; ++f) any |= ctx->h_counters[(size_t)f * kCntStride + 1] > 0;
+                if (!any) { if (p->verbose) for (int f = 0; f < batch; ++f) std::printf("0\n"); return DCMT_OK; }
+            }
+            hipLaunchKernelGGL(k_fill_s, fgrid, b256, 0, st, x6, pp0, cnt, rows, cols, fstrips, batch, xm, p->valid_thresh, 0, 1, (const int*)tc, bands,
+                               q16 ? (const unsigned short*)ctx->x6q : (const unsigned short*)nullptr, (const int*)qbad);
+            rc = fill_apps(&apps);
+            if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
+            hipLaunchKernelGGL((bl ? k_post_s<11, true> : k_post_s<11, false>), dim3(((pstrips + 3) / 4) * batch), b256, 0, st, pp0, pp1, dst, cnt, apps,
+                               rows, cols, pstrips, batch, xm, p->max_depth, p->valid_thresh, 1);
+            DCMT_HIP(ctx, hipGetLastError());
+        }
+        stamp(4);
+        ctx->tev_valid = ctx->timing;
+        ctx->last_apps_launched = apps;
+        return rc;
+    }
+    hipLaunchKernelGGL(k_fill_s, fgrid, b256, 0, st, x6, stop == DCMT_STAGE_FILL31 ? dst : pp0, cnt, rows, cols,
+                       fstrips, batch, xm, p->valid_thresh, 0, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
+    DCMT_HIP(ctx, hipGetLastError());
+    if (stop == DCMT_STAGE_FILL31) return DCMT_OK;
+
+    ctx->last_has_loop = 1;
+    int apps = 0;
+    const int rc = fill_apps(&apps);
+    if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
+    if (stop <= DCMT_STAGE_FILLLOOP) {
+        hipLaunchKernelGGL((k_post_v1<TH, TW>), tile_grid(rows, cols, batch), dim3(kThreads), 0, st, pp0, pp1, dst, cnt, apps,
+                           rows, cols, p->max_depth, p->valid_thresh, p->blur, 8);
+    } else {
+        auto* post = stop == DCMT_STAGE_MEDIAN5 ? k_post_s<9, false> : stop == DCMT_STAGE_BLUR ? (bl ? k_post_s<10, true> : k_post_s<10, false>) :
+                     (bl ? k_post_s<11, true> : k_post_s<11, false>);
+        const int strips = (cols + PostS::VW - 1) / PostS::VW;
+        hipLaunchKernelGGL(post, dim3(((strips + 3) / 4) * batch), b256, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, strips, batch, xm,
+                           p->max_depth, p->valid_thresh, 0);
+    }
+    DCMT_HIP(ctx, hipGetLastError());
+    ctx->last_apps_launched = apps;
     return rc;
 }
 
@@ -543,7 +496,7 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
             float* x4 = stop == DCMT_STAGE_CLOSE5 ? d_dst : ctx->pp[0];       // (dead before the redo chain writes pp[0]; x5 shares pp[1])
             const dim3 bg((cols + 63) / 64, (rows + kBboxRows - 1) / kBboxRows, batch);
             const size_t table = sizeof(int) * 4 * (size_t)n_labels;
-            if (table <= 48 * 1024 && !std::getenv("DCMT_BBOX_GLOBAL"))
+            if (table <= 48 * 1024 && !ctx->bbox_global)
                 hipLaunchKernelGGL(k_label_bbox<true>, bg, dim3(256), table, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
                                    rows, cols, p->max_depth, p->valid_thresh, coef);
             else
@@ -798,15 +751,11 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     ctx->max_rows = max_rows; ctx->max_cols = max_cols; ctx->max_batch = max_batch;
     ctx->frame_elems = (size_t)max_rows * max_cols;
     { const char* e = std::getenv("DCMT_POISON"); ctx->poison = e && e[0] == '1'; }
-    { const char* e = std::getenv("DCMT_CHUNK"); if (e) ctx->chunk = std::atoi(e); }
     { const char* e = std::getenv("DCMT_XCD_MAP"); if (e) ctx->xcd_map = std::atoi(e); }
     { const char* e = std::getenv("DCMT_WIDE"); if (e) ctx->wide = std::atoi(e); }
     { const char* e = std::getenv("DCMT_FUSE_FP"); if (e) ctx->fuse_fp = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_FP_PAIR"); if (e) ctx->fp_pair = std::atoi(e); }
     { const char* e = std::getenv("DCMT_FP_Q16"); if (e) ctx->fp_q16 = std::atoi(e); }
     { const char* e = std::getenv("DCMT_Q16_MIN_WAVES"); if (e) ctx->q16_min_waves = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_Q16_BREG"); if (e) ctx->q16_breg = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_FP_H"); if (e) ctx->fp_h = std::atoi(e); }
     { const char* e = std::getenv("DCMT_ASSUME_FILLED"); if (e) ctx->assume_filled = std::atoi(e); }
     { const char* e = std::getenv("DCMT_TOP_TABLE"); if (e) ctx->top_table = std::atoi(e); }
     { const char* e = std::getenv("DCMT_PAIR"); if (e) ctx->pair = std::atoi(e); }
@@ -815,6 +764,7 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     { const char* e = std::getenv("DCMT_MIN_FUSED_BATCH"); if (e) ctx->min_fused_batch = std::atoi(e); }
     { const char* e = std::getenv("DCMT_LABEL_PAIRS"); if (e) ctx->label_pairs = std::atoi(e); }
     { const char* e = std::getenv("DCMT_LABEL_GROUP"); if (e) ctx->label_group = std::atoi(e); }
+    ctx->bbox_global = std::getenv("DCMT_BBOX_GLOBAL") != nullptr;
     DeviceGuard dev_guard_(ctx);                    // allocate on the context's device, leave the caller's current device as it was
     auto fail = [&](int rc) { dcmt_destroy(ctx); return rc; };
     if (dev_guard_.rc != DCMT_OK) return fail(dev_guard_.rc);

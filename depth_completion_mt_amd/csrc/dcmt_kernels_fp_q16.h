@@ -7,8 +7,8 @@
 // -- with max_depth = 100 and thr = 0.1 (the reference's constants; other values run the f32 kernels).  code = j + 6143 (Q16,
 // dcmt_kernels_fused.h) is 0x0400 .. 0x7bff: the map is strictly increasing, so maxima / minima / medians of codes are the codes of the
 // f32 results, and a hole (x < 0.1f) is code <= 6168.  Two adjacent columns then fit ONE register (low half = column 2l, high half =
-// column 2l + 1) and packed instructions work on both at the price of one v_max_f32: what k_fp_p (dcmt_kernels_fp_pair.h) gains from two
-// columns per lane, without its doubled register state -- this kernel keeps 3 waves per SIMD.
+// column 2l + 1) and packed instructions work on both at the price of one v_max_f32: two columns per lane without a doubled register
+// state -- this kernel keeps 3 waves per SIMD.
 //
 // Which packed instructions: the code range is the bit patterns of the positive NORMAL half-floats, which order as f16 exactly as they
 // do as u16.  gfx950 has packed two-input minima / maxima for u16 AND packed THREE-input ones for f16 (v_pk_maximum3_f16 /
@@ -22,18 +22,30 @@
 // Behind the median: where the redo chain follows (FILLED), Gaussian and final invert run on the codes as integer-valued floats --
 // exact arithmetic, nothing rounds in the oracle's sequence either (PostPipeP::after_median_codes has the argument); otherwise the
 // median is converted back (code -> f32 is exact: one v_cvt and one fused multiply-add) and the Gaussian, the masked select and the
-// final invert are the f32 code of k_fp_p (PostPipeP::after_median).  Either way the output is bit-identical to k_fp_s's.
+// final invert run in f32 (PostPipeP::after_median).  Either way the output is bit-identical to k_fp_s's.
 //
-// Fill: the vertical 31-maximum runs packed; the horizontal one, on rows that have a hole, unpacks the two halves and is k_fp_p's
-// scheme on unsigned integers (0 is the neutral element; register B holds the 30 halo columns unpacked, one per lane), with the two
-// values a lane fetches from lane l - 8 in one word and the two from lane l + 8 in another: two ds_bpermutes.
+// Lane layout: a wave owns 128 columns, lane l the columns c0 + 2l ("E", low half) and c0 + 2l + 1 ("O", high half), 120 of them output
+// (2 + 2 per side go to the median and the Gaussian).  The 15 + 15 halo columns of the 31-wide maximum ride in a second register B, one
+// column per lane, unpacked: even columns of the right halo in lanes 0..7, odd ones in 8..15, even columns of the left halo in lanes
+// 56..63, odd ones in 48..55; lanes 16..47 are dead.  137..144 VGPRs: 3 waves per SIMD.
+// Fill: the vertical 31-maximum runs packed; the horizontal one, on rows that have a hole, works on the unpacked halves (unsigned
+// integers: 0 is the neutral element).  tests/test_lane_schemes.py restates this index arithmetic in numpy and checks it lane by lane
+// against the definition.  m = max(E, O) per lane; PX / SX = EXCLUSIVE prefix / suffix maxima of m inside each 16-lane DPP row (the
+// inclusive row scans, then one row_shr:1 / row_shl:1 that leaves 0 in the lane without a source).  The window of column 2l is O[l-8],
+// lanes l-7 .. l+7; that of column 2l+1 is lanes l-7 .. l+7, E[l+8]:
+//     out_E(l) = max( SO(l-8), PX(l+8) )        SO = max(O, SX)   (suffix starting at a lane's odd column)
+//     out_O(l) = max( SX(l-8), PE(l+8) )        PE = max(E, PX)   (prefix ending at a lane's even column)
+// -- lanes l-8 and l+8 lie in neighbouring DPP rows, each term covers its row's part of the window, and where the window lies inside
+// ONE row (l = 8 mod 16 for E, 7 mod 16 for O) the other term is the 0 of an exclusive scan's first lane.  The halo: virtual lanes
+// 64..71 (the 16 columns right of the strip) and -8..-1 (left) wrap onto physical lanes 0..7 and 56..63 of B's scans; one row_ror:8
+// puts a virtual lane's odd column beside its even one, and the values handed on are selected per SOURCE lane.  The two values a lane
+// fetches from lane l - 8 ride in one word, so do the two from lane l + 8: two ds_bpermutes.
 //
-// X6U16 = true: X6 arrives as the codes themselves (k_pre_p<Q16OUT>, which has checked the frame's values and raised a flag
-// otherwise -- dcmt.hip reruns the f32 kernels behind that flag, so what this kernel makes of a frame that is no grid is never
-// looked at).  X6U16 = false (X6 as f32, converted while loading) was the first stage of this work and is kept for experiments.
+// X6 arrives as the codes themselves (k_pre_p<Q16OUT>, which has checked the frame's values and raised a flag otherwise -- dcmt.hip
+// reruns the f32 kernels behind that flag, so what this kernel makes of a frame that is no grid is never looked at).
 #pragma once
 
-#include "dcmt_kernels_fp_pair.h"
+#include "dcmt_kernels_pair.h"
 #include "median_pk3_nets.h"
 
 namespace dcmt {
@@ -68,9 +80,6 @@ __device__ __forceinline__ unsigned hmin3(unsigned a, unsigned b, unsigned c)
 {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_minimum(__builtin_elementwise_minimum(__builtin_bit_cast(hf2v, a), __builtin_bit_cast(hf2v, b)), __builtin_bit_cast(hf2v, c)));
 }
-__device__ __forceinline__ unsigned umax3(unsigned a, unsigned b, unsigned c) { return umax2(umax2(a, b), c); }
-
-
 
 // shifts with 0 in the lane without a source (unsigned codes: 0 is the neutral element of max)
 __device__ __forceinline__ unsigned u_left(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /*wave_shr:1*/, 0xf, 0xf, true); }
@@ -96,17 +105,6 @@ __device__ __forceinline__ void u_row_scans4(unsigned a, unsigned b, unsigned& p
         "v_max_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
         "v_max_u32_dpp %1, %1, %1 row_shl:8 row_mask:0xf bank_mask:0xf\n\t" : "=&v"(pa), "=&v"(sa), "=&v"(pb), "=&v"(sb) : "v"(a), "v"(b));
 #undef DCMT_U4
-}
-
-__device__ __forceinline__ void u_row_scans2(unsigned a, unsigned& pa, unsigned& sa)
-{
-#define DCMT_U2(N) "v_max_u32_dpp %0, %0, %0 row_shr:" #N " row_mask:0xf bank_mask:0xf\n\t" \
-                   "v_max_u32_dpp %1, %1, %1 row_shl:" #N " row_mask:0xf bank_mask:0xf\n\t"
-    asm("s_nop 1\n\t"
-        "v_max_u32_dpp %0, %2, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_max_u32_dpp %1, %2, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "s_nop 0\n\t" DCMT_U2(2) "s_nop 0\n\t" DCMT_U2(4) "s_nop 0\n\t" DCMT_U2(8) : "=&v"(pa), "=&v"(sa) : "v"(a));
-#undef DCMT_U2
 }
 
 // The exact 5x5 median of dcmt_median.h on packed pairs: the two-input MERGE55 of median_shared_nets.h (the three-input forms
@@ -193,21 +191,137 @@ struct MedianColumnQ {       // MedianColumn (dcmt_median.h) on packed pairs
     }
 };
 
+struct FpQ {
+    static constexpr int H = 4;                  // columns lost per side: 2 (median) + 2 (Gaussian)
+    static constexpr int VW = 128 - 2 * H;       // output columns per wave
+};
+
+// k_fp_q's tail behind the median, two columns per lane.  Step u finishes the output of image row u - 6 from the median of image
+// row u - 4.
+template <bool BLUR>
+struct PostPipeP {
+    F2 G1[8], MR[8];
+    F2 last_out;
+    FrameBuf of;
+    unsigned ob;             // byte offset of this lane's (clamped) column pair
+    int rows, cols, gx, rle, rlo;
+    bool outlane, edge_strip, outside;
+    float max_depth, thr;
+
+    __device__ __forceinline__ void init(float* out_frame, int rows_, int cols_, int gx0, int lane, float max_depth_, float thr_)
+    {
+        of.init(out_frame, (size_t)rows_ * cols_); rows = rows_; cols = cols_; max_depth = max_depth_; thr = thr_;
+        gx = gx0 + 2 * lane;
+        ob = 4u * (unsigned)min(max(gx, 0), cols - 2);
+        outside = gx < 0 || gx >= cols;                            // cols and gx are even: both columns inside or both outside
+        outlane = !outside && 2 * lane >= FpQ::H && 2 * lane < 128 - FpQ::H;
+        // reflect-101 sources of the Gaussian's out-of-image columns: parity is preserved (cols is even), so E comes from an E slot, O from an O slot
+        rle = (reflect101(gx, cols) - gx0) >> 1;
+        rlo = (reflect101(gx + 1, cols) - 1 - gx0) >> 1;
+        edge_strip = gx0 < 0 || gx0 + 127 >= cols;
+        last_out = {0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { G1[q] = {0.f, 0.f}; MR[q] = {0.f, 0.f}; }
+    }
+
+    // everything behind the median of image row u - 4 (me, mo = its two columns) in f32: H10, H11, the store of output row u - 6
+    template <int PP>
+    __device__ __forceinline__ void after_median(float me, float mo, int u)
+    {
+        MR[(PP + 4) & 7] = {me, mo};
+        // ---- H10 (LO :179): horizontal [1 4 6 4 1]/16 with reflect-101 columns
+        if constexpr (BLUR) {
+            F2 mf = {me, mo};
+            if (edge_strip) {
+                const float re = __shfl(me, rle, 64), ro = __shfl(mo, rlo, 64);
+                if (outside) mf = {re, ro};
+            }
+            const float el = from_left(mf.e), ol = from_left(mf.o), er = from_right(mf.e), orr = from_right(mf.o);
+            // column 2l: neighbours O[l-1], O | E[l-1], E[l+1];  column 2l+1: E, E[l+1] | O[l-1], O[l+1]
+            G1[(PP + 4) & 7] = {gauss_taps(mf.e, __fadd_rn(ol, mf.o), __fadd_rn(el, er)), gauss_taps(mf.o, __fadd_rn(mf.e, er), __fadd_rn(ol, orr))};
+        }
+        // ---- vertical pass + select + invert for output row o = u - 6
+        const int o = u - 6;
+        if ((unsigned)o < (unsigned)rows) {
+            const F2 mo_ = MR[(PP + 2) & 7];
+            auto finish = [&](F2 u1, F2 u2, F2 d1, F2 d2) {
+                F2 val = mo_;
+                if constexpr (BLUR) {
+                    const F2 g0 = G1[(PP + 2) & 7];
+                    const float ae = gauss_taps(g0.e, __fadd_rn(u1.e, d1.e), __fadd_rn(u2.e, d2.e));
+                    const float ao = gauss_taps(g0.o, __fadd_rn(u1.o, d1.o), __fadd_rn(u2.o, d2.o));
+                    if (mo_.e >= thr) val.e = ae;                        // LO :184
+                    if (mo_.o >= thr) val.o = ao;
+                }
+                val = {invert_valid(val.e, max_depth, thr), invert_valid(val.o, max_depth, thr)};   // LO :191-202
+                st2(of, outlane ? ob : kDropOffset, o, cols, val);
+                last_out = val;
+            };
+            const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
+            if (BLUR && (o < 2 || o + 2 >= rows)) {                      // reflect-101 rows (rows >= 8 guaranteed)
+                finish(o >= 1 ? g_m1 : g_p1,
+                       o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),
+                       o + 1 < rows ? g_p1 : g_m1,
+                       o + 2 < rows ? g_p2 : (o + 2 == rows ? g_0 : g_m2));
+            } else {
+                finish(g_m1, g_m2, g_p1, g_p2);
+            }
+        }
+    }
+
+    // The same on the packed medians m = (code_E, code_O), where the redo chain follows (k_fp_q<BLUR, FILLED>): IN EXACT ARITHMETIC.  A code is an integer
+    // below 2^15, value = (code - 6143) / 256.  The horizontal pass of the reference order  c*k0 + s1*k1 + s2*k2  on such values only
+    // ever forms multiples of 2^-12 below 128 (19 bits), the vertical pass multiples of 2^-16 below 128 (23 bits), and the final
+    // 100 - value is a multiple of 2^-16 below 128 too: no operation of the oracle's sequence rounds, so any other sequence
+    // without a rounding gives the same bits.  This one works on the codes as integer-valued floats with the weights 1 4 6 4 1
+    // (horizontal sums <= 16 * 31743 < 2^19, vertical <= 256 * 31743 < 2^23) and scales once at the end:
+    //     out = 100 - (N / 65536 - 6143 / 256) = fma(N, -2^-16, 123.99609375).
+    // Horizontal, two columns per lane, four lane shifts (each folded into an add):  S1 = O[l-1] + O,  S2 = E + E[l+1],
+    //     G_E = 4 (E + S1) + (S2[l-1] + S2) = 6 E + 4 (O[l-1] + O) + E[l-1] + E[l+1],   G_O = 4 (O + S2) + (S1 + S1[l+1]):
+    // 2 conversions + 8 + 2 * 4 + 2 instructions per row step instead of 4 + 14 + 10 + 2.
+    template <int PP>
+    __device__ __forceinline__ void after_median_codes(unsigned m, int u)
+    {
+        static_assert(BLUR, "exact only on grid values; the select of LO :184 is not in here");
+        float ce = (float)(m & 0xffffu), co = (float)(m >> 16);
+        if (edge_strip) {
+            const float re = __shfl(ce, rle, 64), ro = __shfl(co, rlo, 64);
+            if (outside) { ce = re; co = ro; }
+        }
+        const float s1 = __fadd_rn(from_left(co), co), s2 = __fadd_rn(ce, from_right(ce));
+        const float ue = __fadd_rn(from_left(s2), s2), wo = __fadd_rn(from_right(s1), s1);
+        G1[(PP + 4) & 7] = {__builtin_fmaf(__fadd_rn(ce, s1), 4.0f, ue), __builtin_fmaf(__fadd_rn(co, s2), 4.0f, wo)};
+        const int o = u - 6;
+        if ((unsigned)o < (unsigned)rows) {
+            const float top = __fadd_rn(max_depth, (float)Q16::OFFSET * 0.00390625f);     // 100 + 6143 / 256: exact
+            auto finish = [&](F2 u1, F2 u2, F2 d1, F2 d2) {
+                const F2 g0 = G1[(PP + 2) & 7];
+                const float ne = __builtin_fmaf(g0.e, 6.0f, __builtin_fmaf(__fadd_rn(u1.e, d1.e), 4.0f, __fadd_rn(u2.e, d2.e)));
+                const float no = __builtin_fmaf(g0.o, 6.0f, __builtin_fmaf(__fadd_rn(u1.o, d1.o), 4.0f, __fadd_rn(u2.o, d2.o)));
+                const F2 val = {__builtin_fmaf(ne, -0x1p-16f, top), __builtin_fmaf(no, -0x1p-16f, top)};
+                st2(of, outlane ? ob : kDropOffset, o, cols, val);
+                last_out = val;
+            };
+            const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
+            if (o < 2 || o + 2 >= rows) {                                // reflect-101 rows, as above
+                finish(o >= 1 ? g_m1 : g_p1,
+                       o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),
+                       o + 1 < rows ? g_p1 : g_m1,
+                       o + 2 < rows ? g_p2 : (o + 2 == rows ? g_0 : g_m2));
+            } else {
+                finish(g_m1, g_m2, g_p1, g_p2);
+            }
+        }
+    }
+};
+
 #ifndef DCMT_FPQ_WAVES
 #define DCMT_FPQ_WAVES 0
 #endif
 #ifndef DCMT_FPQ_PFD
 #define DCMT_FPQ_PFD 6
 #endif
-// BREG = true: the 30 halo columns of the 31-wide maximum ride in a second register (k_fp_p's layout): 120 output columns per wave,
-//   144 VGPRs, 3 waves per SIMD.  BREG = false: no second register -- the strips overlap by the halo instead (X7 is exact for the
-//   lanes 8..55 = 96 columns, 88 of them output): a fifth less work per wave, a quarter more waves, and few enough VGPRs for 4
-//   waves per SIMD.
-struct FpQ {
-    template <bool BREG> static constexpr int halo() { return BREG ? FpP::H : 16 + FpP::H; }
-    template <bool BREG> static constexpr int vw() { return 128 - 2 * halo<BREG>(); }
-};
-template <bool BLUR, bool X6U16, bool BREG = true, bool FILLED = false>
+template <bool BLUR, bool FILLED>
 __global__ __launch_bounds__(256)
 #if DCMT_FPQ_WAVES
 __attribute__((amdgpu_waves_per_eu(DCMT_FPQ_WAVES, DCMT_FPQ_WAVES)))
@@ -217,17 +331,16 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
             int tbands)
 {
     // per wave: centre values and A's 18-row maxima (packed pairs, one word per lane), B's 18-row maxima
-    __shared__ unsigned s_delay[4][16 * (64 + 64 + (BREG ? 32 : 0))];   // 10 (8) KiB per wave, 40 (32) KiB per workgroup
+    __shared__ unsigned s_delay[4][16 * (64 + 64 + 32)];            // 10 KiB per wave, 40 KiB per workgroup
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int f, strip;
     if (!wave_strip(blockIdx.x, wave, strips, batch, xcd_map, f, strip)) return;
     int* cnt = frame_counters(counters, f);
     const size_t fo = (size_t)f * rows_all * cols;
-    constexpr int HALO = FpQ::halo<BREG>(), VW = FpQ::vw<BREG>();
-    const int gx0 = strip * VW - HALO;
+    const int gx0 = strip * FpQ::VW - FpQ::H;
     const int gxe = gx0 + 2 * lane;
-    // B, one column per lane, unpacked (k_fp_p's layout).  The dead lanes 16..47 (two whole DPP rows) shadow lane 0: same column,
+    // B, one column per lane, unpacked (header comment).  The dead lanes 16..47 (two whole DPP rows) shadow lane 0: same column,
     // same values, same delay-line word -- their stores write what lane 0 writes
     const int gxb = lane < 8 ? gx0 + 128 + 2 * lane : (lane < 16 ? gx0 + 128 + 2 * (lane - 8) + 1 :
                     (lane >= 56 ? gx0 - 16 + 2 * (lane - 56) : (lane >= 48 ? gx0 - 16 + 2 * (lane - 48) + 1 : gx0 + 128)));
@@ -236,12 +349,11 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     if (tb) {
         table_rows(tb, f, cols, tbands, rows_all, gxec, tie, bie);
         table_rows(tb, f, cols, tbands, rows_all, gxoc, tio, bio);
-        if constexpr (BREG) table_rows(tb, f, cols, tbands, rows_all, gxbc, tib, bib);
-        else tib = 0x7fffffff;
+        table_rows(tb, f, cols, tbands, rows_all, gxbc, tib, bib);
         V = __builtin_amdgcn_readfirstlane(max(wave_min_i(min(min(tie, tio), tib)) - 8, 0));
     }
     const int rows = rows_all - V;
-    constexpr unsigned EB = X6U16 ? 2u : 4u;                         // bytes per X6 element
+    constexpr unsigned EB = 2;                                       // bytes per code
     FrameBuf sf;
     sf.init(reinterpret_cast<const float*>(static_cast<const char*>(x6_) + fo * EB), (size_t)rows_all * cols * EB / 4);
     const unsigned rowb = EB * (unsigned)cols;
@@ -251,19 +363,15 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     const unsigned flb = EB * (unsigned)gxbc + (unsigned)max(tib, V) * rowb, ceb = EB * (unsigned)gxbc + (unsigned)max(bib, V) * rowb;
     auto clamp3 = [](unsigned a, unsigned lo, unsigned hi) -> unsigned { unsigned r; asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(lo), "v"(hi)); return r; };
     // one column's code at a (clamped) byte offset
-    auto ld_code = [&](unsigned off) -> unsigned {
-        if constexpr (X6U16) return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(sf.rs, off, 0, 0);
-        else return Q16::code(sf.ld_at(off));
-    };
+    auto ld_code = [&](unsigned off) -> unsigned { return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(sf.rs, off, 0, 0); };
     struct Raw { unsigned e, o, b; };
     auto ld_row = [&](int row) -> Raw {                              // row relative to V, already clamped to [0, rows)
-        Raw r = {ld_code(clamp3(sbe + (unsigned)row * rowb, fle, cee)), ld_code(clamp3(sbo + (unsigned)row * rowb, flo, ceo)), 0u};
-        if constexpr (BREG) r.b = ld_code(clamp3(sbb + (unsigned)row * rowb, flb, ceb));
-        return r;
+        return Raw{ld_code(clamp3(sbe + (unsigned)row * rowb, fle, cee)), ld_code(clamp3(sbo + (unsigned)row * rowb, flo, ceo)),
+                   ld_code(clamp3(sbb + (unsigned)row * rowb, flb, ceb))};
     };
     auto pack = [](unsigned e, unsigned o) -> unsigned { return e | (o << 16); };
     const bool outside = gxe < 0 || gxe >= cols;
-    const bool own = !outside && 2 * lane >= HALO && 2 * lane < 128 - HALO;
+    const bool own = !outside && 2 * lane >= FpQ::H && 2 * lane < 128 - FpQ::H;
     const unsigned long long own_mask = __ballot(own);
     const bool edge_strip = gx0 < 0 || gx0 + 127 >= cols;
     const int rep_l = min(max((0 - gx0) >> 1, 0), 63), rep_r = min(max((cols - 2 - gx0) >> 1, 0), 63);
@@ -275,7 +383,7 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     unsigned (*dl_b)[32] = reinterpret_cast<unsigned (*)[32]>(sd + 16 * 128);
     const int lb = lane < 16 ? lane : (lane >= 48 ? lane - 32 : 0);
 
-    PostPipeP<BLUR, HALO, FILLED, FILLED> pipe;                      // codes are grid values                                      // only its after_median() half is used
+    PostPipeP<BLUR> pipe;
     pipe.init(dst + fo + (size_t)V * cols, rows, cols, gx0, lane, max_depth, thr);
     MedianColumnQ mc;
     mc.init();
@@ -287,7 +395,7 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
 #pragma unroll
     for (int q = 0; q < 16; ++q) { PFA[q] = PFB[q] = 0; W2A[q] = W6A[q] = xa0; W2B[q] = W6B[q] = xb0; }
 #pragma unroll
-    for (int q = 0; q < 16; ++q) { dl_c[q][lane] = xa0; dl_a[q][lane] = xa0; if constexpr (BREG) dl_b[q][lb] = xb0; }
+    for (int q = 0; q < 16; ++q) { dl_c[q][lane] = xa0; dl_a[q][lane] = xa0; dl_b[q][lb] = xb0; }
     constexpr int PFD = DCMT_FPQ_PFD;        // rows of load lookahead
 #pragma unroll
     for (int q = 0; q < PFD; ++q) {
@@ -341,42 +449,30 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
         dl_c[p][lane] = xa;
         dl_a[p][lane] = w18a;
         const unsigned w31a = hmax2(w18a, w18a_old);
-        unsigned w31b = 0;
-        if constexpr (BREG) {
-            // (one code per lane in the low half, 0 above it: the packed f16 forms order these words too, and their three-input one is
-            // formed reliably -- of two chained v_max_u32 the compiler fuses only one)
-            const unsigned w2b = hmax2(xb, vpb);
-            vpb = xb;
-            W2B[p] = w2b;
-            const unsigned w6b = hmax3(w2b, W2B[(p + 14) & 15], W2B[(p + 12) & 15]);
-            W6B[p] = w6b;
-            const unsigned w18b = hmax3(w6b, W6B[(p + 10) & 15], W6B[(p + 4) & 15]);
-            const unsigned w18b_old = nxt_b;
-            nxt_b = dl_b[(p + 4) & 15][lb];
-            dl_b[p][lb] = w18b;
-            w31b = hmax2(w18b, w18b_old);
-        }
+        // (B: one code per lane in the low half, 0 above it: the packed f16 forms order these words too, and their three-input one is
+        // formed reliably -- of two chained v_max_u32 the compiler fuses only one)
+        const unsigned w2b = hmax2(xb, vpb);
+        vpb = xb;
+        W2B[p] = w2b;
+        const unsigned w6b = hmax3(w2b, W2B[(p + 14) & 15], W2B[(p + 12) & 15]);
+        W6B[p] = w6b;
+        const unsigned w18b = hmax3(w6b, W6B[(p + 10) & 15], W6B[(p + 4) & 15]);
+        const unsigned w18b_old = nxt_b;
+        nxt_b = dl_b[(p + 4) & 15][lb];
+        dl_b[p][lb] = w18b;
+        const unsigned w31b = hmax2(w18b, w18b_old);
         const unsigned long long vme = __builtin_amdgcn_ballot_w64((v << 16) <= Q16::HOLE_MAX_HI), vmo = __builtin_amdgcn_ballot_w64(v <= Q16::HOLE_MAX_HI);
         if ((vme | vmo) != 0ull) {
-            // horizontal 31-max: k_fp_p's scheme on the unpacked halves
+            // horizontal 31-max (header comment) on the unpacked halves
             const unsigned e = w31a & 0xffffu, od = w31a >> 16;
-            unsigned sx, so, px, pe;
-            if constexpr (BREG) {
-                const unsigned bo = u_row_ror8(w31b);
-                unsigned pa, sa, pb, sb;
-                u_row_scans4(umax2(e, od), umax2(w31b, bo), pa, sa, pb, sb);
-                // exclusive scans = the inclusive ones shifted by a lane; which register a lane hands on is chosen BEFORE the shift, at
-                // the source lane (lanes 0..6 feed the halo lanes 1..7, lane 7 feeds lane 8 of A; lanes 57..63 likewise): two shifts, not four
-                px = u_row_shr1(lane < 7 ? pb : pa); sx = u_row_shl1(lane > 56 ? sb : sa);
-                so = umax2(b_hi ? bo : od, sx);
-                pe = umax2(b_lo ? w31b : e, px);
-            } else {
-                // (the fetches of lanes 0..7 and 56..63 wrap around the wave: their X7 is not exact, and nothing reads it)
-                unsigned pa, sa;
-                u_row_scans2(umax2(e, od), pa, sa);
-                px = u_row_shr1(pa); sx = u_row_shl1(sa);
-                so = umax2(od, sx); pe = umax2(e, px);
-            }
+            const unsigned bo = u_row_ror8(w31b);
+            unsigned pa, sa, pb, sb;
+            u_row_scans4(umax2(e, od), umax2(w31b, bo), pa, sa, pb, sb);
+            // exclusive scans = the inclusive ones shifted by a lane; which register a lane hands on is chosen BEFORE the shift, at
+            // the source lane (lanes 0..6 feed the halo lanes 1..7, lane 7 feeds lane 8 of A; lanes 57..63 likewise): two shifts, not four
+            const unsigned px = u_row_shr1(lane < 7 ? pb : pa), sx = u_row_shl1(lane > 56 ? sb : sa);
+            const unsigned so = umax2(b_hi ? bo : od, sx);
+            const unsigned pe = umax2(b_lo ? w31b : e, px);
             // out_E(l) = max(SO(l-8), PX(l+8)), out_O(l) = max(SX(l-8), PE(l+8)): the two values a lane fetches from lane l-8 ride in one
             // word (SO low, SX high), so do the two from lane l+8 (PX low, PE high) -- two ds_bpermutes, not four, and their packed maximum
             // is the pair (out_E, out_O) as it is needed

@@ -80,7 +80,7 @@ struct FrameBuf {
 };
 
 
-// 16-bit codes of depths that are multiples of 1/256 m (k_pre_p<Q16OUT> -> k_fp_h / k_fp_q, dcmt_kernels_fp_q16.h has the argument).
+// 16-bit codes of depths that are multiples of 1/256 m (k_pre_p<Q16OUT> -> k_fp_q, dcmt_kernels_fp_q16.h has the argument).
 // code = 256 x + 6143 for x = j / 256, j in [-5119, 25600] (an empty pixel, an inverted depth down to 100 - 119.996 m, the 100 of an
 // empty column): 0x0400 .. 0x7bff -- the bit patterns of the positive NORMAL half-floats, which order exactly like the integers they
 // are.  So the codes can be compared as unsigned integers (v_pk_max_u16 ...) AND as f16 (v_pk_maximum3_f16 / v_pk_minimum3_f16:

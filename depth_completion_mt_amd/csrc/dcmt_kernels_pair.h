@@ -75,7 +75,7 @@ constexpr int kMaxBands = 8;                 // row bands per strip (table slots
 // with cold rings (exactly like the start below the leading empty rows) and accounts for the x5 rows [r0, r1) only; the
 // per-column (ti, bi) of the bands go to one table slot per band, which the reader combines (table_rows), which is why
 // bands need table mode.
-// Q16OUT: X6 leaves as 16-bit codes (Q16 in dcmt_kernels_fused.h: code = 256 x + 6143, two columns per dword) for k_fp_h / k_fp_q -- half the X6 traffic.
+// Q16OUT: X6 leaves as 16-bit codes (Q16 in dcmt_kernels_fused.h: code = 256 x + 6143, two columns per dword) for k_fp_q -- half the X6 traffic.
 // Exact only if every value stored is a multiple of 1/256 in the code range, which holds whenever the frame's depths are
 // (the KITTI format); the kernel checks it on every value it really stores and raises *q16_bad otherwise (the caller then
 // reruns the f32 kernels, gated on that flag).  Table mode only.
