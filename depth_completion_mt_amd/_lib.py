@@ -20,6 +20,7 @@ FLAG_FORCE_STAGED = 1
 FLAG_FORCE_FUSED = 2
 FLAG_NORMALIZE = 4
 STAGE_FILL31, STAGE_FILLLOOP, STAGE_MEDIAN5, STAGE_BLUR, STAGE_FINAL = 7, 8, 9, 10, 11
+EVAL_GT, EVAL_BOTH = 0, 1
 
 # every symbol include/dcmt.h declares (tests check the library exports exactly these)
 EXPORTS = (
@@ -29,6 +30,7 @@ EXPORTS = (
     "dcmt_strerror", "dcmt_last_hip_error", "dcmt_version", "dcmt_project_points_dev", "dcmt_set_kernel_timing", "dcmt_last_kernel_times",
     "dcmt_slic_num_centers", "dcmt_slic_labels_dev", "dcmt_default_stereo_params", "dcmt_stereo_refine_dev",
     "dcmt_project_points", "dcmt_slic_labels", "dcmt_stereo_refine", "dcmt_last_path",
+    "dcmt_evaluate_dev", "dcmt_evaluate_u16_dev", "dcmt_evaluate",
 )
 
 
@@ -54,6 +56,12 @@ class StereoParams(ctypes.Structure):
     """Mirror of dcmt_stereo_params (include/dcmt.h)."""
     _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float), ("damp", ctypes.c_float),
                 ("max_depth", ctypes.c_float), ("iterations", ctypes.c_int32)]
+
+
+class EvalFrame(ctypes.Structure):
+    """Mirror of dcmt_eval_frame (include/dcmt.h): one frame's sums against ground truth."""
+    _fields_ = [("n", ctypes.c_double), ("sum_err", ctypes.c_double), ("sum_abs", ctypes.c_double), ("sum_sq", ctypes.c_double),
+                ("n_inv", ctypes.c_double), ("sum_inv_abs", ctypes.c_double), ("sum_inv_sq", ctypes.c_double)]
 
 
 def build(force: bool = False) -> str:
@@ -122,6 +130,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_slic_labels.argtypes = [vp, vp, sz, i, i, i, i, vp, vp]
         L.dcmt_stereo_refine.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, i, i, vp]
         L.dcmt_slic_num_centers.argtypes = [i, i, i]
+        f32 = ctypes.c_float
+        L.dcmt_evaluate_dev.argtypes = [vp, vp, vp, i, i, i, f32, i, vp, vp]
+        L.dcmt_evaluate_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, f32, i, vp, vp]
+        L.dcmt_evaluate.argtypes = [vp, vp, sz, vp, sz, i, i, f32, i, ctypes.POINTER(EvalFrame)]
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

@@ -5,6 +5,9 @@
     interpolate_with_superpixels(labels, sparse, blur_type="gaussian", use_superpixel=1) -> dense
         reference: src/DC_lidar_camera/img_completion_lc.cpp:34-38
 
+    evaluate_performance(gt, pred, preset) -> what the reference's evaluate_performance(s) returns
+        reference: src/DC_lidar_only/main.cpp:16, src/DC_lidar_camera/main_lc.cpp:85, src/DC_stereo_lidar/main_sl.cpp:1031
+
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
 stream (dcmt_complete_f32_dev: asynchronous).  PyTorch is only the owner of device memory
@@ -17,6 +20,20 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
+
+
+EVAL_FIELDS = ("n", "sum_err", "sum_abs", "sum_sq", "n_inv", "sum_inv_abs", "sum_inv_sq")     # dcmt_eval_frame, in order
+# the three reference functions: (mask mode, threshold).  LO main.cpp:19 `int tolerance = 0` over gt only; LC main_lc.cpp:88
+# `int tolerance = 0.1` (truncates to 0) over gt and pred; SL main_sl.cpp:1036 `int tolerance = 2` over gt and pred
+EVAL_PRESETS = {"lidar_only": ("gt", 0.0), "lidar_camera": ("both", 0.0), "stereo_lidar": ("both", 2.0)}
+
+
+def _eval_mode(mode) -> int:
+    if mode == "gt" or (not isinstance(mode, str) and mode == L.EVAL_GT):
+        return L.EVAL_GT
+    if mode == "both" or (not isinstance(mode, str) and mode == L.EVAL_BOTH):
+        return L.EVAL_BOTH
+    raise ValueError("mode must be 'gt' (mask gt > thresh) or 'both' (gt > thresh and pred > thresh)")
 
 
 class DcmtError(RuntimeError):
@@ -225,6 +242,51 @@ class Context:
             raise DcmtError(st, "dcmt_stereo_refine_dev")
         return d_out
 
+    # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
+    def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
+                     stream: int | None = None):
+        """Per-frame sums of the reference's error terms on the device (dcmt_evaluate_dev).  d_gt, d_pred: contiguous CUDA tensors
+        [batch][rows][cols] (or [rows][cols]); d_pred f32; d_gt f32, or a 2-byte type (torch.uint16 / int16 view of the KITTI
+        PNG payload) that goes to dcmt_evaluate_u16_dev with gt = payload * gt_scale.  mode "gt": mask gt > thresh; "both":
+        gt > thresh and pred > thresh.  Returns a float64 CUDA tensor [batch, 7] (EVAL_FIELDS) without synchronising."""
+        import torch
+        assert d_pred.is_cuda and d_pred.dtype == torch.float32 and d_pred.is_contiguous()
+        assert d_gt.is_cuda and d_gt.is_contiguous() and d_gt.shape == d_pred.shape
+        shp = d_pred.shape if d_pred.dim() == 3 else (1,) + tuple(d_pred.shape)
+        b, r, c = shp
+        if d_out is None:
+            d_out = torch.empty((b, 7), dtype=torch.float64, device=d_pred.device)
+        assert d_out.is_cuda and d_out.dtype == torch.float64 and d_out.is_contiguous() and d_out.numel() == 7 * b
+        if stream is None:
+            stream = torch.cuda.current_stream(d_pred.device).cuda_stream
+        m = _eval_mode(mode)
+        if d_gt.element_size() == 2:
+            st = L.lib().dcmt_evaluate_u16_dev(self._h, d_gt.data_ptr(), ctypes.c_float(gt_scale), d_pred.data_ptr(), r, c, b,
+                                               ctypes.c_float(thresh), m, d_out.data_ptr(), ctypes.c_void_p(stream))
+        else:
+            assert d_gt.dtype == torch.float32
+            st = L.lib().dcmt_evaluate_dev(self._h, d_gt.data_ptr(), d_pred.data_ptr(), r, c, b, ctypes.c_float(thresh), m,
+                                           d_out.data_ptr(), ctypes.c_void_p(stream))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_evaluate_dev")
+        return d_out
+
+    def evaluate(self, gt: np.ndarray, pred: np.ndarray, thresh: float = 0.0, mode="both") -> np.ndarray:
+        """One frame of host memory (dcmt_evaluate, synchronous; any row stride): float64 [7] (EVAL_FIELDS)."""
+        g = np.asarray(gt, dtype=np.float32)
+        q = np.asarray(pred, dtype=np.float32)
+        assert g.ndim == 2 and g.shape == q.shape
+        if g.strides[1] != 4:
+            g = np.ascontiguousarray(g)
+        if q.strides[1] != 4:
+            q = np.ascontiguousarray(q)
+        out = L.EvalFrame()
+        st = L.lib().dcmt_evaluate(self._h, g.ctypes.data, g.strides[0], q.ctypes.data, q.strides[0], g.shape[0], g.shape[1],
+                                   ctypes.c_float(thresh), _eval_mode(mode), ctypes.byref(out))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_evaluate")
+        return np.array([getattr(out, f) for f in EVAL_FIELDS], dtype=np.float64)
+
     def last_fill_iters(self, n: int):
         out = (ctypes.c_int * n)()
         st = L.lib().dcmt_last_fill_iters(self._h, out, n)
@@ -289,3 +351,77 @@ def interpolate_with_superpixels(labels: np.ndarray, n_labels: int, sparse_r_img
     b = 1 if a.ndim == 2 else a.shape[0]
     return _ctx_for(a.shape[-2], a.shape[-1], b).complete(a, make_params(blur_type="gaussian", **kw), labels=labels,
                                                           n_labels=n_labels, use_superpixel=use_superpixel)
+
+
+def _sums_array(sums) -> np.ndarray:
+    if hasattr(sums, "detach"):                  # a torch tensor: copying it to the host synchronises with its stream
+        sums = sums.detach().cpu().numpy()
+    return np.asarray(sums, dtype=np.float64).reshape(-1, 7)
+
+
+def _metrics(s: np.ndarray) -> dict:
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n, n_inv = s[:, 0], s[:, 4]
+        return {"me": s[:, 1] / n, "mae": s[:, 2] / n, "rmse": np.sqrt(s[:, 3] / n),
+                "imae": 1000.0 * s[:, 5] / n_inv, "irmse": 1000.0 * np.sqrt(s[:, 6] / n_inv)}
+
+
+def eval_summary(sums) -> dict:
+    """Metrics from evaluate_dev / evaluate sums ([batch, 7] or [7]; numpy or torch).  me (signed mean of gt - pred), mae, rmse in
+    the GT's unit (metres); imae, irmse in 1/km (the KITTI depth-completion table's unit for inverse depth).  f64 throughout.
+      "per_frame":      each metric per frame (arrays), plus the pixel counts n and n_inv; a frame with an empty mask gives NaN;
+      "pixel_weighted": over the batch, every masked pixel weighing the same (the sums of all frames, then one division);
+      "frame_mean":     the mean of the per-frame metrics over the frames whose mask is not empty (NaN if there is none)."""
+    s = _sums_array(sums)
+    per = _metrics(s)
+    pw = {k: float(v[0]) for k, v in _metrics(s.sum(axis=0, keepdims=True)).items()}
+    fm = {}
+    for k, v in per.items():
+        ok = ~np.isnan(v)
+        fm[k] = float(v[ok].mean()) if ok.any() else float("nan")
+    per = dict(per, n=s[:, 0].copy(), n_inv=s[:, 4].copy())
+    return {"per_frame": per, "pixel_weighted": pw, "frame_mean": fm}
+
+
+def reference_performance(sums, preset: str):
+    """The reference function's own results from sums made with the preset's mode and threshold (EVAL_PRESETS), with its final
+    arithmetic in f32: float(sum) / count, then sqrt (the count converted to float as `float / int` does).
+      "lidar_only":   mse (the signed mean error; the name is the reference's)           LO main.cpp:33
+      "lidar_camera": (mse, mae), where mse is the RMSE                                   LC main_lc.cpp:114-115
+      "stereo_lidar": (mae, rmse)                                                         SL main_sl.cpp:1058-1059
+    np.float32 values for a single frame's sums ([7]), arrays of them for [batch, 7].  An empty mask gives NaN (0 / 0)."""
+    if preset not in EVAL_PRESETS:
+        raise ValueError(f"preset must be one of {sorted(EVAL_PRESETS)}")
+    arr = np.asarray(sums.detach().cpu().numpy() if hasattr(sums, "detach") else sums, dtype=np.float64)
+    single = arr.ndim == 1
+    s = arr.reshape(-1, 7)
+    f32 = np.float32
+    cnt = s[:, 0].astype(f32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if preset == "lidar_only":
+            res = (s[:, 1].astype(f32) / cnt,)
+        else:
+            mae = s[:, 2].astype(f32) / cnt
+            rmse = np.sqrt(s[:, 3].astype(f32) / cnt)
+            res = (rmse, mae) if preset == "lidar_camera" else (mae, rmse)
+    res = tuple(r[0] if single else r for r in res)
+    return res[0] if len(res) == 1 else res
+
+
+def evaluate_performance(gt, pred, preset: str = "lidar_only", gt_scale: float = 1.0 / 256.0):
+    """Drop-in for the reference's evaluate_performance(s) (EVAL_PRESETS, reference_performance for what each returns).
+    numpy frames [rows][cols] go through the host entry point (a uint16 GT is converted as payload * gt_scale in f32);
+    CUDA tensors [batch][rows][cols] through the device one (per-frame arrays; the result is copied back, so this synchronises)."""
+    if preset not in EVAL_PRESETS:
+        raise ValueError(f"preset must be one of {sorted(EVAL_PRESETS)}")
+    mode, thresh = EVAL_PRESETS[preset]
+    if hasattr(pred, "is_cuda") and pred.is_cuda:
+        b = 1 if pred.dim() == 2 else pred.shape[0]
+        ctx = _ctx_for(pred.shape[-2], pred.shape[-1], b, pred.device.index or 0)
+        sums = ctx.evaluate_dev(gt, pred, thresh, mode, gt_scale).cpu().numpy()
+        return reference_performance(sums[0] if pred.dim() == 2 else sums, preset)
+    g = np.asarray(gt)
+    if g.dtype == np.uint16:
+        g = g.astype(np.float32) * np.float32(gt_scale)
+    q = np.asarray(pred, dtype=np.float32)
+    return reference_performance(_ctx_for(q.shape[0], q.shape[1], 1).evaluate(g, q, thresh, mode), preset)

@@ -22,6 +22,7 @@
 #include "dcmt_kernels_pair.h"
 #include "dcmt_kernels_fp_q16.h"
 #include "dcmt_kernels_slic.h"
+#include "dcmt_kernels_eval.h"
 
 using namespace dcmt;
 
@@ -88,6 +89,8 @@ struct dcmt_ctx {
     double* slic_centers[2] = {nullptr, nullptr};
     unsigned long long* slic_sums = nullptr;
     size_t slic_center_cap = 0;                 // centres per frame the two buffers above hold
+    double* eval_slab = nullptr;      // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
+                                      // allocated by the first evaluate call
     int label_group = 0;              // LC fast path, two columns per lane: labels side by side per wave (0 = by label size); env DCMT_LABEL_GROUP
     int label_pairs = -1;             // LC fast path: one wave per label pair (1), per label (0), by label size (-1); env DCMT_LABEL_PAIRS
     int min_fused_batch = 3;          // smaller batches use the staged kernels (measured crossover with both streaming kernels in row bands,
@@ -138,11 +141,14 @@ uint32_t k0_bits(const uint8_t k0[25])
     return b;
 }
 
-// the library is built with -ffinite-math-only: test the exponent bits, not the value
+// the library is built with -ffinite-math-only: test the exponent bits, not the value -- and read them through memory, or the
+// compiler, which may assume every float argument finite, folds the test to true
 bool finite_bits(float v)
 {
+    volatile float m = v;
+    const float c = m;
     uint32_t b;
-    std::memcpy(&b, &v, sizeof b);
+    std::memcpy(&b, &c, sizeof b);
     return (b & 0x7f800000u) != 0x7f800000u;
 }
 
@@ -675,6 +681,26 @@ int host_call(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int
     return chain_rc;
 }
 
+// dcmt_evaluate_dev / dcmt_evaluate_u16_dev: checks, the slab on first use, then the two kernels (dcmt_kernels_eval.h)
+template <typename TG>
+int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_pred, int rows, int cols, int batch, float thresh,
+                 int mode, dcmt_eval_frame* d_out, hipStream_t st)
+{
+    if (!ctx || !d_gt || !d_pred || !d_out) return DCMT_E_INVALID;
+    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!finite_bits(thresh) || thresh < 0.0f || !finite_bits(gt_scale)) return DCMT_E_INVALID;
+    if (mode != DCMT_EVAL_GT && mode != DCMT_EVAL_BOTH) return DCMT_E_INVALID;
+    if ((uintptr_t)d_out % 8 != 0) return DCMT_E_INVALID;
+    if (!ctx->eval_slab)     // sized for the largest call the ctx admits (eval_chunks grows with the frame size), before any launch
+        DCMT_HIP(ctx, hipMalloc((void**)&ctx->eval_slab, sizeof(double) * kEvalSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)ctx->max_batch));
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
+    hipLaunchKernelGGL(k_eval_partial<TG>, dim3(chunks, batch), dim3(kEvalThreads), 0, st, d_gt, gt_scale, d_pred, n, thresh,
+                       mode == DCMT_EVAL_BOTH ? 1 : 0, ctx->eval_slab);
+    hipLaunchKernelGGL(k_eval_combine, dim3(batch), dim3(64), 0, st, ctx->eval_slab, chunks, reinterpret_cast<double*>(d_out));
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -806,7 +832,7 @@ void dcmt_destroy(dcmt_ctx* ctx)
     (void)hipFree(ctx->d_in); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_lab);
     (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max); (void)hipFree(ctx->winner);
     (void)hipFree(ctx->slic_cells); (void)hipFree(ctx->slic_centers[0]); (void)hipFree(ctx->slic_centers[1]);
-    (void)hipFree(ctx->slic_sums);
+    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     for (auto e : ctx->tev) if (e) (void)hipEventDestroy(e);
     delete ctx;
@@ -927,6 +953,20 @@ int dcmt_stereo_refine_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d
         hipLaunchKernelGGL(k_stereo_refine<false>, sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+int dcmt_evaluate_dev(dcmt_ctx* ctx, const float* d_gt, const float* d_pred, int rows, int cols, int batch, float thresh, int mode,
+                      dcmt_eval_frame* d_out, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return evaluate_dev(ctx, d_gt, 1.0f, d_pred, rows, cols, batch, thresh, mode, d_out, (hipStream_t)stream);
+}
+
+int dcmt_evaluate_u16_dev(dcmt_ctx* ctx, const uint16_t* d_gt, float gt_scale, const float* d_pred, int rows, int cols, int batch,
+                          float thresh, int mode, dcmt_eval_frame* d_out, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return evaluate_dev(ctx, d_gt, gt_scale, d_pred, rows, cols, batch, thresh, mode, d_out, (hipStream_t)stream);
 }
 
 int dcmt_slic_num_centers(int rows, int cols, int step)
@@ -1084,6 +1124,29 @@ int dcmt_stereo_refine(dcmt_ctx* ctx, const float* depth, size_t drs, const uint
     rc = dcmt_stereo_refine_dev(ctx, (const float*)dd.p, (const uint8_t*)dl.p, (const uint8_t*)dr.p, (float*)dout.p, rows, cols, 1, params, st);
     if (rc != DCMT_OK) return rc;
     DCMT_HIP(ctx, hipMemcpy2DAsync(refined, ors, dout.p, frow, frow, rows, hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return DCMT_OK;
+}
+
+int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred, size_t prs, int rows, int cols, float thresh, int mode,
+                  dcmt_eval_frame* out)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !gt || !pred || !out || rows < 1 || cols < 1) return DCMT_E_INVALID;
+    if (grs < sizeof(float) * (size_t)cols || prs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
+    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    hipStream_t st;
+    int rc = host_stream(ctx, &st);
+    if (rc != DCMT_OK) return rc;
+    DevBuf dg, dp, dout;
+    const size_t frow = sizeof(float) * (size_t)cols;
+    if ((rc = dg.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dp.alloc(ctx, frow * rows)) != DCMT_OK ||
+        (rc = dout.alloc(ctx, sizeof(dcmt_eval_frame))) != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(dg.p, frow, gt, grs, frow, rows, hipMemcpyHostToDevice, st));
+    DCMT_HIP(ctx, hipMemcpy2DAsync(dp.p, frow, pred, prs, frow, rows, hipMemcpyHostToDevice, st));
+    rc = dcmt_evaluate_dev(ctx, (const float*)dg.p, (const float*)dp.p, rows, cols, 1, thresh, mode, (dcmt_eval_frame*)dout.p, st);
+    if (rc != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpyAsync(out, dout.p, sizeof(dcmt_eval_frame), hipMemcpyDeviceToHost, st));
     DCMT_HIP(ctx, hipStreamSynchronize(st));
     return DCMT_OK;
 }

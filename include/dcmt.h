@@ -143,7 +143,8 @@ int dcmt_device_count(void);
 /* Creates a context on `device` able to process up to max_batch frames of up to
  * max_rows x max_cols per call.  Allocates the device scratch every path needs up front (8 B per
  * pixel per frame of max_batch); two buffers only one path uses are allocated by the first call that takes it and kept (the
- * 16-bit plane of large on-grid batches, 2 B per pixel; the column statistics of the small-batch tile kernels), so no call
+ * 16-bit plane of large on-grid batches, 2 B per pixel; the column statistics of the small-batch tile kernels); SLIC scratch and
+ * the partial-sum slab of the evaluate calls are allocated the same way by the first call that needs them, so no call
  * after the first of its kind allocates.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
  * and one offset just below 2^31 is kept free as "nowhere"); max_batch at most 65535. */
 int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx **out);
@@ -264,6 +265,56 @@ void dcmt_default_stereo_params(dcmt_stereo_params *p);
 int dcmt_stereo_refine_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_left, const uint8_t *d_right,
                            float *d_refined, int rows, int cols, int batch, const dcmt_stereo_params *params,
                            void *stream);
+
+/* ---- scoring the path's output against ground truth ---------------------------------- */
+
+/* What every reference main does with the dense depth: evaluate_performance, DC_lidar_only/main.cpp:16-34 (the signed mean
+ * error over gt > 0, returned as `mse`); evaluate_performance, DC_lidar_camera/main_lc.cpp:85-116 (RMSE -- named `mse` -- and
+ * MAE over gt > 0 && pred > 0: its `int tolerance = 0.1;` truncates to 0); evaluate_performances, DC_stereo_lidar/main_sl.cpp:1031-1061
+ * (MAE and RMSE over gt > 2 && pred > 2, run before and after the refinement, :1232 / :1247); plus the inverse-depth terms of the
+ * KITTI depth-completion table that main_lc.cpp:93-98 holds as commented-out lines (iMAE, iRMSE).  The library returns per-frame
+ * SUMS; the divisions (and the reference's f32 final arithmetic) are the caller's -- the Python layer's eval_summary /
+ * evaluate_performance do them.
+ *
+ * Per pixel, exactly the reference's statements: e = gt - pred, d = fabsf(e), d * d are f32 operations (one rounding each, no FMA);
+ * thresh compares as an f32 `>` (what `float > int` is in the reference).  The inverse term |1.0/(double)gt - 1.0/(double)pred| is
+ * f64 and is taken only where pred > 0 too (nothing non-finite enters a library built with -ffinite-math-only).
+ * Sums: f64, in a fixed reduction tree (dcmt_kernels_eval.h): a frame's 7 values depend only on its own pixels and on (rows, cols)
+ * -- not on batch, the frame's position in the batch, the load widths its alignment allows, or the run.  No float atomics.  The
+ * reference's running `float` sum is NOT reproduced: the f64 sum is closer to the exact value (the two agree where every partial
+ * sum is exact in f32).  A frame whose mask is empty gives all zeros. */
+typedef struct {                /* n and n_inv are integer counts stored as doubles (exact: a frame has < 2^29 pixels) */
+    double n;                   /* pixels in the mask                                                                    */
+    double sum_err;             /* sum of e = gt - pred, e an f32 difference             (LO main.cpp:27)                */
+    double sum_abs;             /* sum of d = |e|, d an f32 value                         (LC main_lc.cpp:106, SL :1049)  */
+    double sum_sq;              /* sum of d * d, product rounded to f32, no FMA           (LC :108, SL :1052)             */
+    double n_inv;               /* pixels in the mask with pred > 0 (== n in DCMT_EVAL_BOTH mode)                         */
+    double sum_inv_abs;         /* sum of |1.0/(double)gt - 1.0/(double)pred| over those  (main_lc.cpp:96, f64)           */
+    double sum_inv_sq;          /* sum of its square, f64                                                                 */
+} dcmt_eval_frame;
+
+#define DCMT_EVAL_GT    0       /* mask: gt > thresh                   (DC_lidar_only)                                    */
+#define DCMT_EVAL_BOTH  1       /* mask: gt > thresh && pred > thresh  (DC_lidar_camera, DC_stereo_lidar)                 */
+
+/* DEVICE pointers, stream-ordered: d_gt, d_pred contiguous [batch][rows][cols]; d_out: [batch] dcmt_eval_frame, 8-byte aligned.
+ * Never synchronises.  May be enqueued right behind a completion or refinement call on the same stream (same ordering rule as
+ * every *_dev call on one ctx); it touches none of the state the cascade carries from call to call (the 16-bit flag ring, the
+ * normalisation extrema, the bounding-box tables, the projection's winner plane) and leaves dcmt_last_path and the probes alone.
+ * The first evaluate call on a ctx allocates a partial-sum slab (64 B per 8192 pixels of a max_rows x max_cols frame, times
+ * max_batch) before it enqueues anything; later calls never allocate.
+ * DCMT_E_INVALID: a null pointer, sizes beyond the ctx limits, thresh < 0 (or not finite), mode not DCMT_EVAL_GT / DCMT_EVAL_BOTH,
+ * d_out not 8-byte aligned. */
+int dcmt_evaluate_dev(dcmt_ctx *ctx, const float *d_gt, const float *d_pred, int rows, int cols, int batch,
+                      float thresh, int mode, dcmt_eval_frame *d_out, void *stream);
+/* Ground truth as the KITTI depth PNG payload: gt = __fmul_rn((float)v, gt_scale) (gt_scale 1/256 for KITTI), the conversion of
+ * dcmt_complete_u16_dev and of LO main.cpp:82 / LC main_lc.cpp:180; the same bits as dcmt_evaluate_dev on the converted plane.
+ * (SL passes the raw uint16 Mat to its float reader, main_sl.cpp:1232, :1247 -- a caller bug, not reproduced.) */
+int dcmt_evaluate_u16_dev(dcmt_ctx *ctx, const uint16_t *d_gt, float gt_scale, const float *d_pred,
+                          int rows, int cols, int batch, float thresh, int mode, dcmt_eval_frame *d_out, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); the same bits as dcmt_evaluate_dev on the frame.  Uses the ctx's
+ * slab like the device call, so it must not overlap a device evaluate call on the same ctx that is still in flight. */
+int dcmt_evaluate(dcmt_ctx *ctx, const float *gt, size_t gt_row_stride, const float *pred, size_t pred_row_stride,
+                  int rows, int cols, float thresh, int mode, dcmt_eval_frame *out);
 
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 
