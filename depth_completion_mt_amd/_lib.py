@@ -31,6 +31,7 @@ EXPORTS = (
     "dcmt_slic_num_centers", "dcmt_slic_labels_dev", "dcmt_default_stereo_params", "dcmt_stereo_refine_dev",
     "dcmt_project_points", "dcmt_slic_labels", "dcmt_stereo_refine", "dcmt_last_path",
     "dcmt_evaluate_dev", "dcmt_evaluate_u16_dev", "dcmt_evaluate",
+    "dcmt_colorize_dev", "dcmt_colorize", "dcmt_colormap_jet",
 )
 
 
@@ -134,6 +135,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_evaluate_dev.argtypes = [vp, vp, vp, i, i, i, f32, i, vp, vp]
         L.dcmt_evaluate_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, f32, i, vp, vp]
         L.dcmt_evaluate.argtypes = [vp, vp, sz, vp, sz, i, i, f32, i, ctypes.POINTER(EvalFrame)]
+        L.dcmt_colorize_dev.argtypes = [vp, vp, i, i, i, vp, vp]
+        L.dcmt_colorize.argtypes = [vp, vp, sz, i, i, vp, sz]
+        L.dcmt_colormap_jet.argtypes = [vp]
+        L.dcmt_colormap_jet.restype = None
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

@@ -7,6 +7,8 @@
 
     evaluate_performance(gt, pred, preset) -> what the reference's evaluate_performance(s) returns
         reference: src/DC_lidar_only/main.cpp:16, src/DC_lidar_camera/main_lc.cpp:85, src/DC_stereo_lidar/main_sl.cpp:1031
+    to_color_image(r_img) -> the BGR JET image the reference's toColorImage makes
+        reference: src/DC_lidar_only/main.cpp:6-14
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -287,6 +289,37 @@ class Context:
             raise DcmtError(st, "dcmt_evaluate")
         return np.array([getattr(out, f) for f in EVAL_FIELDS], dtype=np.float64)
 
+    # ---- JET colourisation (dcmt_colorize*) --------------------------------------------
+    def colorize_dev(self, d_src, d_bgr=None, stream: int | None = None):
+        """The reference's toColorImage on the device (dcmt_colorize_dev): per frame min-max to [0, 1], * 255 to u8, JET palette.
+        d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]).  Returns a uint8 CUDA tensor of d_src's shape + (3,),
+        B, G, R per pixel, without synchronising."""
+        import torch
+        assert d_src.is_cuda and d_src.dtype == torch.float32 and d_src.is_contiguous()
+        shp = d_src.shape if d_src.dim() == 3 else (1,) + tuple(d_src.shape)
+        b, r, c = shp
+        if d_bgr is None:
+            d_bgr = torch.empty(tuple(d_src.shape) + (3,), dtype=torch.uint8, device=d_src.device)
+        assert d_bgr.is_cuda and d_bgr.dtype == torch.uint8 and d_bgr.is_contiguous() and d_bgr.numel() == 3 * b * r * c
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        st = L.lib().dcmt_colorize_dev(self._h, d_src.data_ptr(), r, c, b, d_bgr.data_ptr(), ctypes.c_void_p(stream))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_colorize_dev")
+        return d_bgr
+
+    def colorize(self, frame: np.ndarray) -> np.ndarray:
+        """One frame of host memory (dcmt_colorize, synchronous; any row stride): uint8 [rows][cols][3], B, G, R."""
+        a = np.asarray(frame, dtype=np.float32)
+        assert a.ndim == 2
+        if a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        out = np.empty(a.shape + (3,), dtype=np.uint8)
+        st = L.lib().dcmt_colorize(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], out.ctypes.data, out.strides[0])
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_colorize")
+        return out
+
     def last_fill_iters(self, n: int):
         out = (ctypes.c_int * n)()
         st = L.lib().dcmt_last_fill_iters(self._h, out, n)
@@ -351,6 +384,33 @@ def interpolate_with_superpixels(labels: np.ndarray, n_labels: int, sparse_r_img
     b = 1 if a.ndim == 2 else a.shape[0]
     return _ctx_for(a.shape[-2], a.shape[-1], b).complete(a, make_params(blur_type="gaussian", **kw), labels=labels,
                                                           n_labels=n_labels, use_superpixel=use_superpixel)
+
+
+def to_color_image(r_img):
+    """The reference's toColorImage (DC_lidar_only/main.cpp:6-14): a depth plane -> its JET image, uint8 [rows][cols][3] in
+    B, G, R order.  A numpy frame goes through the host entry point; a CUDA tensor ([rows][cols] or [batch][rows][cols]) through
+    the device one, on torch's current stream, and comes back as a CUDA tensor without synchronising."""
+    if hasattr(r_img, "is_cuda") and r_img.is_cuda:
+        b = 1 if r_img.dim() == 2 else r_img.shape[0]
+        return _ctx_for(r_img.shape[-2], r_img.shape[-1], b, r_img.device.index or 0).colorize_dev(r_img)
+    a = np.asarray(r_img, dtype=np.float32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).colorize(a)
+
+
+_jet = None
+
+
+def __getattr__(name):
+    # JET_BGR: the palette the kernels use (dcmt_colormap_jet), (256, 3) uint8, B, G, R; read-only.  Loaded on first use.
+    global _jet
+    if name == "JET_BGR":
+        if _jet is None:
+            buf = (ctypes.c_uint8 * 768)()
+            L.lib().dcmt_colormap_jet(buf)
+            _jet = np.ctypeslib.as_array(buf).reshape(256, 3)
+            _jet.flags.writeable = False
+        return _jet
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _sums_array(sums) -> np.ndarray:

@@ -23,6 +23,7 @@
 #include "dcmt_kernels_fp_q16.h"
 #include "dcmt_kernels_slic.h"
 #include "dcmt_kernels_eval.h"
+#include "dcmt_kernels_color.h"
 
 using namespace dcmt;
 
@@ -91,6 +92,8 @@ struct dcmt_ctx {
     size_t slic_center_cap = 0;                 // centres per frame the two buffers above hold
     double* eval_slab = nullptr;      // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
                                       // allocated by the first evaluate call
+    float* color_slab = nullptr;      // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
+                                      // (allocated by dcmt_create)
     int label_group = 0;              // LC fast path, two columns per lane: labels side by side per wave (0 = by label size); env DCMT_LABEL_GROUP
     int label_pairs = -1;             // LC fast path: one wave per label pair (1), per label (0), by label size (-1); env DCMT_LABEL_PAIRS
     int min_fused_batch = 3;          // smaller batches use the staged kernels (measured crossover with both streaming kernels in row bands,
@@ -701,6 +704,37 @@ int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_p
     return DCMT_OK;
 }
 
+// dcmt_colorize_dev: a min/max pass over the batch's frames, then one map pass over its flat pixel run (dcmt_kernels_color.h).
+// Batches of 2^31 pixels or more go in segments of whole frames, each a pair of its own: a segment holds fewer than 2^31 pixels
+// (32-bit pixel indices) and, where it is not the last, a multiple of 4 frames, so every segment starts as aligned as the batch
+// does.  (Measured, 1024 frames of 352 x 1216: segments of 128 / 64 / 32 frames, whose re-read could come from the Infinity Cache,
+// take 0.90 / 0.91 / 1.03 ms against 0.85 ms for the whole batch in one pair.)
+int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batch, uint8_t* d_bgr, hipStream_t st)
+{
+    if (!ctx || !d_src || !d_bgr) return DCMT_E_INVALID;
+    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if ((uintptr_t)d_src % 4 != 0) return DCMT_E_INVALID;
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
+    const uint32_t cap = (0x80000000u - kColorPxPerWg) / n;                 // frames per segment the 32-bit pixel run allows (>= 3)
+    uint32_t seg = std::min((uint32_t)batch, cap);
+    if (seg >= 4 && seg < (uint32_t)batch) seg &= ~3u;
+    for (uint32_t f0 = 0; f0 < (uint32_t)batch; f0 += seg) {
+        const uint32_t nf = std::min(seg, (uint32_t)batch - f0), total = nf * n;
+        const float* s = d_src + (size_t)f0 * n;
+        uint8_t* o = d_bgr + (size_t)3 * f0 * n;
+        const uint32_t span = std::min(nf, (kColorPxPerWg - 1) / n + 2);   // frames one map workgroup can touch
+        const size_t lds = sizeof(uint32_t) * 256 + sizeof(float) * 2 * span;
+        const dim3 grid((total + kColorPxPerWg - 1) / kColorPxPerWg);
+        hipLaunchKernelGGL(k_color_minmax, dim3(chunks, nf), dim3(kColorThreads), 0, st, s, n, ctx->color_slab);
+        if ((uintptr_t)s % 16 == 0 && (uintptr_t)o % 4 == 0)
+            hipLaunchKernelGGL(k_color_map<true>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
+        else
+            hipLaunchKernelGGL(k_color_map<false>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
+        DCMT_HIP(ctx, hipGetLastError());
+    }
+    return DCMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -814,6 +848,8 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     if (hipMalloc((void**)&ctx->norm_stats, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
     if (hipMemset(ctx->norm_stats, 0, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_HIP);
     if (hipMalloc((void**)&ctx->norm_coef, sizeof(float) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
+    if (hipMalloc((void**)&ctx->color_slab, sizeof(float) * kColorSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)max_batch) != hipSuccess)
+        return fail(DCMT_E_NOMEM);
     if (hipHostMalloc((void**)&ctx->h_counters, sizeof(int) * (size_t)kCntStride * max_batch, hipHostMallocDefault) != hipSuccess)
         return fail(DCMT_E_NOMEM);
     *out = ctx;
@@ -832,7 +868,7 @@ void dcmt_destroy(dcmt_ctx* ctx)
     (void)hipFree(ctx->d_in); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_lab);
     (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max); (void)hipFree(ctx->winner);
     (void)hipFree(ctx->slic_cells); (void)hipFree(ctx->slic_centers[0]); (void)hipFree(ctx->slic_centers[1]);
-    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab);
+    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab); (void)hipFree(ctx->color_slab);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     for (auto e : ctx->tev) if (e) (void)hipEventDestroy(e);
     delete ctx;
@@ -967,6 +1003,23 @@ int dcmt_evaluate_u16_dev(dcmt_ctx* ctx, const uint16_t* d_gt, float gt_scale, c
 {
     DCMT_ON_DEVICE(ctx);
     return evaluate_dev(ctx, d_gt, gt_scale, d_pred, rows, cols, batch, thresh, mode, d_out, (hipStream_t)stream);
+}
+
+int dcmt_colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batch, uint8_t* d_bgr, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return colorize_dev(ctx, d_src, rows, cols, batch, d_bgr, (hipStream_t)stream);
+}
+
+void dcmt_colormap_jet(uint8_t bgr[768])
+{
+    if (!bgr) return;
+    static const uint32_t jet[256] = {DCMT_JET_BGR_PACKED};
+    for (int i = 0; i < 256; ++i) {
+        bgr[3 * i] = (uint8_t)jet[i];
+        bgr[3 * i + 1] = (uint8_t)(jet[i] >> 8);
+        bgr[3 * i + 2] = (uint8_t)(jet[i] >> 16);
+    }
 }
 
 int dcmt_slic_num_centers(int rows, int cols, int step)
@@ -1147,6 +1200,26 @@ int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred,
     rc = dcmt_evaluate_dev(ctx, (const float*)dg.p, (const float*)dp.p, rows, cols, 1, thresh, mode, (dcmt_eval_frame*)dout.p, st);
     if (rc != DCMT_OK) return rc;
     DCMT_HIP(ctx, hipMemcpyAsync(out, dout.p, sizeof(dcmt_eval_frame), hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return DCMT_OK;
+}
+
+int dcmt_colorize(dcmt_ctx* ctx, const float* src, size_t srs, int rows, int cols, uint8_t* bgr, size_t ors)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !src || !bgr || rows < 1 || cols < 1) return DCMT_E_INVALID;
+    if (srs < sizeof(float) * (size_t)cols || ors < 3 * (size_t)cols) return DCMT_E_INVALID;
+    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    hipStream_t st;
+    int rc = host_stream(ctx, &st);
+    if (rc != DCMT_OK) return rc;
+    DevBuf ds, dout;
+    const size_t frow = sizeof(float) * (size_t)cols, brow = 3 * (size_t)cols;
+    if ((rc = ds.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, brow * rows)) != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(ds.p, frow, src, srs, frow, rows, hipMemcpyHostToDevice, st));
+    rc = dcmt_colorize_dev(ctx, (const float*)ds.p, rows, cols, 1, (uint8_t*)dout.p, st);
+    if (rc != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(bgr, ors, dout.p, brow, brow, rows, hipMemcpyDeviceToHost, st));
     DCMT_HIP(ctx, hipStreamSynchronize(st));
     return DCMT_OK;
 }

@@ -145,7 +145,8 @@ int dcmt_device_count(void);
  * pixel per frame of max_batch); two buffers only one path uses are allocated by the first call that takes it and kept (the
  * 16-bit plane of large on-grid batches, 2 B per pixel; the column statistics of the small-batch tile kernels); SLIC scratch and
  * the partial-sum slab of the evaluate calls are allocated the same way by the first call that needs them, so no call
- * after the first of its kind allocates.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
+ * after the first of its kind allocates.  The min/max slab of dcmt_colorize* (8 B per 8192 pixels of a frame, times max_batch)
+ * is allocated here.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
  * and one offset just below 2^31 is kept free as "nowhere"); max_batch at most 65535. */
 int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx **out);
 void dcmt_destroy(dcmt_ctx *ctx);
@@ -315,6 +316,34 @@ int dcmt_evaluate_u16_dev(dcmt_ctx *ctx, const uint16_t *d_gt, float gt_scale, c
  * slab like the device call, so it must not overlap a device evaluate call on the same ctx that is still in flight. */
 int dcmt_evaluate(dcmt_ctx *ctx, const float *gt, size_t gt_row_stride, const float *pred, size_t pred_row_stride,
                   int rows, int cols, float thresh, int mode, dcmt_eval_frame *out);
+
+/* ---- JET colourisation of the path's output ------------------------------------------------------------ */
+
+/* The reference mains' toColorImage (DC_lidar_only/main.cpp:6-14, utils.cpp:6-13, DC_stereo_lidar/main_sl.cpp:42-49), run on
+ * every dense plane after the path:
+ *     cv::normalize(r_img, n, 1.0, 0, cv::NORM_MINMAX);  n.convertTo(u8, CV_8UC1, 255.0);  cv::applyColorMap(u8, out, COLORMAP_JET);
+ * Per frame: smin / smax = its extrema; scale = 1 / (smax - smin) in double (0 when smax - smin <= DBL_EPSILON), rounded to f32;
+ * shift = -(float)(smin * scale); v = x * scale + shift in f32 with two roundings (the arithmetic of DCMT_FLAG_NORMALIZE);
+ * idx = v * 255 rounded half to even and saturated to 0..255; out = the JET palette's entry idx, 3 bytes in B, G, R order.
+ * An AVX2 build of OpenCV fuses x * scale + shift into one FMA: that can move a pixel by one palette index, only in a frame
+ * without a zero pixel and only where v * 255 lies within an ulp of a .5.  A constant frame maps to entry 0.  Inputs must be
+ * finite, as for every entry point of this library (-ffinite-math-only); -0.0 is treated as 0.0. */
+
+/* DEVICE pointers, stream-ordered: d_src contiguous f32 [batch][rows][cols], 4-byte aligned; d_bgr [batch][rows][cols][3] bytes,
+ * any alignment (16-byte d_src and 4-byte d_bgr take the wide loads and stores).  Never synchronises.  May be enqueued right
+ * behind a completion or refinement call on the same stream (same ordering rule as every *_dev call on one ctx); it touches none
+ * of the state the cascade carries from call to call (the 16-bit flag ring, the normalisation extrema, the bounding-box tables,
+ * the projection's winner plane) and leaves dcmt_last_path and the probes alone.  Uses a min/max slab that dcmt_create allocates
+ * (8 B per 8192 pixels of a max_rows x max_cols frame, times max_batch); never allocates.  A frame's bytes depend only on its
+ * own pixels, not on batch or its position in the batch.  No float atomics.
+ * DCMT_E_INVALID: a null pointer, sizes beyond the ctx limits, d_src not 4-byte aligned. */
+int dcmt_colorize_dev(dcmt_ctx *ctx, const float *d_src, int rows, int cols, int batch, uint8_t *d_bgr, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: src_row_stride >= 4 * cols, bgr_row_stride >= 3 * cols); the same
+ * bytes as dcmt_colorize_dev on the frame.  What dcmt_shim::to_color_image calls.  Uses the ctx's slab like the device call, so it
+ * must not overlap a device colorize call on the same ctx that is still in flight. */
+int dcmt_colorize(dcmt_ctx *ctx, const float *src, size_t src_row_stride, int rows, int cols, uint8_t *bgr, size_t bgr_row_stride);
+/* The palette the kernels use: cv::COLORMAP_JET's 256 entries in index order, each B, G, R.  Needs no GPU. */
+void dcmt_colormap_jet(uint8_t bgr[768]);
 
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 

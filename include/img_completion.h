@@ -185,6 +185,19 @@ inline void stereo_refine(const cv::Mat& dense_depth, const cv::Mat& left_gray, 
     optimized_depth = out;
 }
 
+// The mains' toColorImage (DC_lidar_only/main.cpp:6-14): normalize to [0, 1], convertTo CV_8UC1 * 255, applyColorMap JET.
+// CV_32FC1 in, a fresh CV_8UC3 (B, G, R) out.  Not named toColorImage: the reference mains define that function themselves.
+inline void to_color_image(const cv::Mat& r_img, cv::Mat& color_img)
+{
+    if (r_img.type() != CV_32FC1 || r_img.rows < 1 || r_img.cols < 1) throw std::runtime_error("to_color_image: image must be CV_32FC1");
+    const int rows = r_img.rows, cols = r_img.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_8UC3);
+    raise(dcmt_colorize(thread_ctx().get(rows, cols), r_img.ptr<float>(), r_img.step[0], rows, cols, out.ptr<unsigned char>(), out.step[0]),
+          "to_color_image");
+    color_img = out;
+}
+
 }  // namespace dcmt_shim
 
 // reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there.
