@@ -155,6 +155,21 @@ bool finite_bits(float v)
     return (b & 0x7f800000u) != 0x7f800000u;
 }
 
+// [a, a + a_bytes) and [b, b + b_bytes) share a byte: a completion call's input frames and its dst (in place, or overlapping)
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    return (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
+
+// dcmt_last_path of a call whose result went to scratch first and was then copied to its overlapping dst
+constexpr const char* kPathCopy = " + copy to dst";
+
+void path_append(dcmt_ctx* ctx, const char* s)
+{
+    const size_t n = std::strlen(ctx->last_path);
+    std::snprintf(ctx->last_path + n, sizeof ctx->last_path - n, "%s", s);
+}
+
 int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p)
 {
     if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
@@ -287,7 +302,13 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
     }
     // table mode: only the k_fp_s path reads X6 through the per-column table (the probes and the unfused kernels get a fully written X6)
     int* tc = (stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table) ? ctx->tb : nullptr;
-    float* o6 = stop == DCMT_STAGE_EXTEND ? dst : x6;
+    const void* in = src16 ? (const void*)src16 : (const void*)src;    // (cf is nullptr with d_x4 and with src16)
+    // Frames that overlap dst (in place, or shifted; never with d_x4, which is scratch).  The f32 kernels read them only in k_pre, into
+    // scratch, and write dst last.  Two things would break that: the stop_after = EXTEND probe, where k_pre writes dst while other
+    // waves still read their strips and halo columns from the frames -- it goes to X6 (this call's k_pre output anyway) and one copy
+    // moves it to dst; and the 16-bit attempt, whose k_fp_q writes dst BEFORE the gated f32 rerun reads the frames again -- not taken.
+    const bool src_dst_overlap = ranges_overlap(in, (size_t)batch * fe * (src16 ? 2 : 4), dst, (size_t)batch * fe * sizeof(float));
+    float* o6 = stop == DCMT_STAGE_EXTEND && !src_dst_overlap ? dst : x6;
     // LDS-DMA rows need 16-byte aligned sources: cols % 4 == 0 and a 16-byte aligned base
     const bool wide = ctx->wide && cols % 4 == 0 && ((uintptr_t)src % 16 == 0) && !src16;
     // two columns per lane (k_pre_p) wherever a lane's 8-byte accesses are aligned: even width, 8-byte aligned frames
@@ -302,15 +323,11 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
         if (bands > kMaxBands) bands = kMaxBands;
     }
     // 16-bit X6 (k_pre_p<Q16OUT> -> k_fp_q): the whole chain in table mode, two columns per lane, the reference's constants, no
-    // normalisation in front (normalised depths are no multiples of 1/256)
-    // in place (or overlapping) f32 calls never take the 16-bit attempt: k_fp_q writes dst BEFORE the gated f32 rerun would read src again
-    // (the f32 kernels alone are alias-safe: src is only read by k_pre into ctx scratch, dst is written last)
-    const bool src_dst_overlap = !src16 && (uintptr_t)src < (uintptr_t)(dst + (size_t)batch * fe) && (uintptr_t)dst < (uintptr_t)(src + (size_t)batch * fe);
+    // normalisation in front (normalised depths are no multiples of 1/256), no overlap of the frames with dst (above)
     const bool q16 = q16_try && (long long)batch * ((cols + FpQ::VW - 1) / FpQ::VW) >= ctx->q16_min_waves && pair && tc && !cf &&
                      Q16::params_ok(p->max_depth, p->valid_thresh) && (uintptr_t)dst % 8 == 0 && (!src16 || in_scale == 0.00390625f) && !src_dst_overlap;
     if (q16) { const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc; }
 
-    const void* in = src16 ? (const void*)src16 : (const void*)src;    // (cf is nullptr with d_x4 and with src16)
     const float scale = src16 ? in_scale : 1.0f;
     // k_pre_s (one column per lane) into o6
     auto pre_s = [&](auto kind, auto wide_) {
@@ -351,7 +368,13 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
     std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s%s%s", d_x4 ? "k_label_bbox + k_label_stage + " : "",
                   q16 ? (src16 ? "k_pre_p<U16,Q16OUT>" : "k_pre_p<Q16OUT>") : pair ? (d_x4 ? "k_pre_p<START4>" : src16 ? "k_pre_p<U16>" : cf ? "k_pre_p<NORM>" : "k_pre_p") : "k_pre_s",
                   bands > 1 ? " (row bands)" : "");
-    if (stop == DCMT_STAGE_EXTEND) return DCMT_OK;
+    if (stop == DCMT_STAGE_EXTEND) {
+        if (o6 != dst) {
+            DCMT_HIP(ctx, hipMemcpyAsync(dst, o6, sizeof(float) * (size_t)batch * fe, hipMemcpyDeviceToDevice, st));
+            path_append(ctx, kPathCopy);
+        }
+        return DCMT_OK;
+    }
 
     const int fstrips = (cols + FillS::VW - 1) / FillS::VW;
     const dim3 fgrid(((fstrips + 3) / 4) * batch);
@@ -395,8 +418,7 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
                            p->valid_thresh, (const int*)tc, bands, gate, fb_s);
         DCMT_HIP(ctx, hipGetLastError());
         stamp(3);
-        { const size_t n_ = std::strlen(ctx->last_path);
-          std::snprintf(ctx->last_path + n_, sizeof ctx->last_path - n_, " + %s", q16 ? "k_fp_q" : (fb_s > 1 ? "k_fp_s (row bands)" : "k_fp_s")); }
+        path_append(ctx, q16 ? " + k_fp_q" : (fb_s > 1 ? " + k_fp_s (row bands)" : " + k_fp_s"));
         ctx->last_has_loop = 1;
         int rc = DCMT_OK, apps = 0;
         const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
@@ -462,6 +484,12 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
     const int blur = force_gaussian ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
     ctx->tev_valid = 0;
     if (ctx->timing && ctx->tev[0]) (void)hipEventRecord(ctx->tev[0], st);
+    // In place (or overlapping) calls: every kernel that writes d_dst must run behind the last one that reads the input frames.  Where
+    // the kernel that reads them would also write d_dst (the probes below, and stop_after = EXTEND in run_chain_fused), an overlapping
+    // call points its output at scratch the path does not use at that point and copies it to d_dst (kPathCopy in dcmt_last_path).
+    const size_t n_px = (size_t)batch * rows * cols;
+    bool src_dst_overlap = d_src16 ? ranges_overlap(d_src16, n_px * sizeof(uint16_t), d_dst, n_px * sizeof(float))
+                                   : ranges_overlap(d_src, n_px * sizeof(float), d_dst, n_px * sizeof(float));
     const float* coef = nullptr;
     if (p->flags & DCMT_FLAG_NORMALIZE) {
         // N1: one read-only pass for the per-frame extrema, then (a, b) per frame; the first kernel of whichever
@@ -475,8 +503,13 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
         DCMT_HIP(ctx, hipGetLastError());
         coef = ctx->norm_coef;
         if (stop == DCMT_STAGE_NORMALIZE) {
-            hipLaunchKernelGGL(k_norm_write, dim3(2048), dim3(256), 0, st, d_src, d_dst, coef, fe, batch);
+            // k_norm_write is a grid-stride pass: with a shifted overlap it would overwrite frames other threads have yet to read.
+            // Overlapping: into pp[0] (no other kernel of this call) and copied.
+            float* o = src_dst_overlap ? ctx->pp[0] : d_dst;
+            hipLaunchKernelGGL(k_norm_write, dim3(2048), dim3(256), 0, st, d_src, o, coef, fe, batch);
             DCMT_HIP(ctx, hipGetLastError());
+            if (o != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, o, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
+            std::snprintf(ctx->last_path, sizeof ctx->last_path, "k_minmax + k_norm_coef + k_norm_write%s", o != d_dst ? kPathCopy : "");
             ctx->last_stream = st; ctx->last_batch = batch; ctx->last_apps_launched = 0; ctx->last_has_loop = 0;
             return DCMT_OK;
         }
@@ -502,7 +535,10 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
                 DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
                 DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
             }
-            float* x4 = stop == DCMT_STAGE_CLOSE5 ? d_dst : ctx->pp[0];       // (dead before the redo chain writes pp[0]; x5 shares pp[1])
+            // (dead before the redo chain writes pp[0]; x5 shares pp[1]).  The CLOSE5 probe is X4 itself, written straight to d_dst --
+            // unless d_dst overlaps d_src: the label stage's waves read d_src around their label's box (wide boxes in column chunks, a
+            // later chunk reading what an earlier one wrote) while others write X4, so X4 stays in pp[0] and is copied
+            float* x4 = stop == DCMT_STAGE_CLOSE5 && !src_dst_overlap ? d_dst : ctx->pp[0];
             const dim3 bg((cols + 63) / 64, (rows + kBboxRows - 1) / kBboxRows, batch);
             const size_t table = sizeof(int) * 4 * (size_t)n_labels;
             if (table <= 48 * 1024 && !ctx->bbox_global)
@@ -545,6 +581,8 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
 #undef DCMT_LSTAGEP
             DCMT_HIP(ctx, hipGetLastError());
             if (stop == DCMT_STAGE_CLOSE5) {
+                if (x4 != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, x4, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
+                std::snprintf(ctx->last_path, sizeof ctx->last_path, "k_label_bbox + k_label_stage%s", x4 != d_dst ? kPathCopy : "");
                 ctx->last_stream = st; ctx->last_batch = batch; ctx->last_apps_launched = 0; ctx->last_has_loop = 0;
                 return DCMT_OK;
             }
@@ -559,9 +597,9 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
             return run_chain_fused(ctx, kind, d_src, d_dst, rows, cols, batch, &q, st, sync_loop, nullptr, d_src16, in_scale, coef);
         }
         if (d_src16) {   // the staged kernels take f32: convert into scratch that nothing writes before they have read it
-            const size_t n = (size_t)batch * rows * cols;
-            hipLaunchKernelGGL(k_u16_to_f32, dim3(1024), dim3(256), 0, st, d_src16, ctx->pp[0], n, in_scale);
+            hipLaunchKernelGGL(k_u16_to_f32, dim3(1024), dim3(256), 0, st, d_src16, ctx->pp[0], n_px, in_scale);
             d_src = ctx->pp[0];
+            src_dst_overlap = false;
         }
     }
     ctx->last_stream = st;
@@ -572,28 +610,41 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
     { const int erc = ensure_colstat(ctx); if (erc != DCMT_OK) return erc; }
     std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s + k_fill31_v1 + k_post_v1 (staged tile kernels)", (d_labels && use_superpixel) ? "k_pre_labeled_v1" : "k_pre_v1");
     const int dump = stop <= DCMT_STAGE_CLOSE5 ? stop : 0;
+    // Up to FILL7 the kernel that reads the frames writes the probe itself: stages 2..4 as its dump, FILL7 as its X5 output.  Into a
+    // d_dst that overlaps d_src that would race with other workgroups still reading their halo from d_src, so the probe goes to
+    // scratch and is copied: X5 for FILL7 (its own plane), pp[0] for the dumps (first written by the 31x31 fill, which these probes do
+    // not run; the uint16 input converted into pp[0] never overlaps d_dst).
+    float* probe = !src_dst_overlap ? d_dst : stop == DCMT_STAGE_FILL7 ? ctx->x5 : ctx->pp[0];
+    float* x5_out = stop == DCMT_STAGE_FILL7 ? probe : ctx->x5;
+    float* dump_out = dump ? probe : d_dst;        // (not written without a dump stage)
     int stat_rows = (int)grid.y;                   // tile rows of the kernel that writes the column statistics
     if (d_labels && use_superpixel && few) {
         hipLaunchKernelGGL((k_pre_labeled_v1<FTH_FEW, TW>), fgrid, block, 0, st, d_src, d_labels, n_labels,
-                           stop == DCMT_STAGE_FILL7 ? d_dst : ctx->x5, ctx->colstat, ctx->counters, d_dst, rows, cols,
+                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
                            p->max_depth, p->valid_thresh, kb, dump, coef);
         stat_rows = (int)fgrid.y;
     } else if (d_labels && use_superpixel) {
         hipLaunchKernelGGL((k_pre_labeled_v1<TH, TW>), grid, block, 0, st, d_src, d_labels, n_labels,
-                           stop == DCMT_STAGE_FILL7 ? d_dst : ctx->x5, ctx->colstat, ctx->counters, d_dst, rows, cols,
+                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
                            p->max_depth, p->valid_thresh, kb, dump, coef);
     } else if (few) {
         hipLaunchKernelGGL((k_pre_v1<FTH_FEW, TW>), fgrid, block, 0, st, d_src,
-                           stop == DCMT_STAGE_FILL7 ? d_dst : ctx->x5, ctx->colstat, ctx->counters, d_dst, rows, cols,
+                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
                            p->max_depth, p->valid_thresh, kb, dump, coef);
         stat_rows = (int)fgrid.y;
     } else {
         hipLaunchKernelGGL((k_pre_v1<TH, TW>), grid, block, 0, st, d_src,
-                           stop == DCMT_STAGE_FILL7 ? d_dst : ctx->x5, ctx->colstat, ctx->counters, d_dst, rows, cols,
+                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
                            p->max_depth, p->valid_thresh, kb, dump, coef);
     }
     DCMT_HIP(ctx, hipGetLastError());
-    if (stop <= DCMT_STAGE_FILL7) return DCMT_OK;
+    if (stop <= DCMT_STAGE_FILL7) {
+        if (probe != d_dst) {
+            DCMT_HIP(ctx, hipMemcpyAsync(d_dst, probe, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
+            path_append(ctx, kPathCopy);
+        }
+        return DCMT_OK;
+    }
 
     // H6 + H7
     if (stop == DCMT_STAGE_EXTEND) {

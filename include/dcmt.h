@@ -43,8 +43,16 @@
  * arbitrary f32 depths pay one double run in 64 calls.  Depths beyond 119.996 m (inverted values below -20 m: outside the 15-bit code
  * range) count as "not on the grid" as well, also on the uint16 entry point (payloads above 30719).
  *
- * In place: d_dst may be d_src (the reference's function is in place by signature: dense = sparse.clone(), :27), or overlap
- * it; the library then never takes the 16-bit attempt (its f32 kernels read src completely before dst is first written).
+ * In place: on dcmt_complete_f32_dev, dcmt_complete_u16_dev and dcmt_complete_labeled_f32_dev, d_dst may be d_src (the
+ * reference's function is in place by signature: dense = sparse.clone(), :27) or overlap it in any way -- shifted by frames, rows
+ * or single elements; on the uint16 entry point d_src's 2 bytes per pixel anywhere inside or across d_dst's 4 -- at every
+ * stop_after, with the bits of a call into separate memory.  In an overlapping call every kernel that writes d_dst runs after the
+ * last one that reads d_src.  Where the kernel that reads d_src would itself write d_dst (the probes up to DCMT_STAGE_EXTEND, and DCMT_STAGE_NORMALIZE),
+ * an overlapping call writes the result to context scratch and copies it to d_dst: one device-to-device copy more, and
+ * dcmt_last_path ends in "+ copy to dst".  The 16-bit attempt is not made when d_dst overlaps d_src (f32 or uint16): its rerun would
+ * read d_src again after d_dst was written.  The labeled entry point's attempt reads the label stage's output in scratch, so
+ * overlap does not stop it there.  d_labels must not overlap d_dst.  The host entry points stage through device buffers of their
+ * own: src may be dst there too.
  * Empty pixels: the sign of a zero in an output pixel that stays empty (an all-empty frame) is +0.0 where the input held +0.0; an
  * input -0.0 counts as 0.0 (empty) and may come out as either zero.
  */
@@ -165,7 +173,7 @@ void dcmt_k0_diamond(uint8_t k0[25]);
 /* HOST pointers, synchronous: copies in, runs the cascade, copies out.  Backs the cv::Mat
  * shim (replaces the body of img_completion, img_completion.cpp:17-204).
  * src/dst: f32, `batch` frames of rows x cols; row and frame strides in BYTES (cv::Mat::step
- * for a single Mat; frame strides are ignored when batch == 1).  src is never written.
+ * for a single Mat; frame strides are ignored when batch == 1).  src is never written (unless it is dst: in place works).
  * The hole-closure loop runs exactly as many times as the reference would (up to
  * max_fill_iters); returns DCMT_E_NOT_CONVERGED if the cap was hit (dst is still written). */
 int dcmt_complete_f32(dcmt_ctx *ctx,
