@@ -21,6 +21,7 @@
 #include "dcmt_kernels_fused.h"
 #include "dcmt_kernels_pair.h"
 #include "dcmt_kernels_fp_q16.h"
+#include "dcmt_kernels_tail.h"
 #include "dcmt_kernels_slic.h"
 #include "dcmt_kernels_eval.h"
 #include "dcmt_kernels_color.h"
@@ -186,7 +187,8 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
     return DCMT_OK;
 }
 
-// Scratch only one of the paths uses is allocated by the first call that takes that path (never again afterwards): the column
+// Scratch only one of the paths uses is allocated by the first call that takes that path (never again afterwards; run_chain calls
+// these before it enqueues anything): the column
 // statistics of the staged tile kernels, the 16-bit plane of k_pre_p<Q16OUT> -> k_fp_q.
 int ensure_colstat(dcmt_ctx* ctx)
 {
@@ -266,8 +268,9 @@ int fill_loop(dcmt_ctx* ctx, int batch, const dcmt_params* p, hipStream_t st, bo
     return rc;
 }
 
-// Fast path.  Whole chain: k_pre_s -> k_fp_s, then three launches that return at once for every frame
-// k_fp_s finished (k_fill_s redo, k_fill_s loop applications, k_post_s only_if_holes).  stop_after probes:
+// Fast path.  Whole chain: k_pre_s -> k_fp_s -> k_tail, one workgroup per frame that returns at once for every frame k_fp_s
+// finished and runs the hole-closure loop for the others (the host entry points, which read the counters back between
+// applications, launch k_fill_s redo, k_fill_s loop applications, k_post_s only_if_holes instead).  stop_after probes:
 // k_pre_s -> k_fill_s (-> loop) -> k_post_s / copy.  Preconditions are checked by the caller.
 // d_x4 != nullptr: X4 is already there (LC fast path): k_pre_s only runs H5 + H6 on it.
 // src16 != nullptr: uint16 ingest fused into k_pre_s.  cf: N1's (a, b) per frame, applied while k_pre_s loads.
@@ -402,28 +405,39 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
         // frames this kernel leaves with holes are recomputed by the redo chain below whenever that chain is enqueued (always on the host
         // entry points, with spec_fill_iters >= 1 on the device ones): then the kernel may leave out the select that only such frames need
         const bool filled = bl && ctx->assume_filled && (sync_loop || (p->spec_fill_iters >= 1 && p->max_fill_iters >= 1));
-        const int* gate = nullptr;          // k_fp_s below: the path itself, or the f32 rerun behind the 16-bit attempt
+        const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
+        // device entry points: everything behind k_fp_* is k_tail (dcmt_kernels_tail.h), also the second half of the f32 rerun behind
+        // a 16-bit attempt; the host entry points (and spec_fill_iters = 0, where nothing follows) keep k_fp_s as a launch of its own
+        const bool tail = !sync_loop && n_redo > 0;
         if (q16) {
             auto* fpq = filled ? k_fp_q<true, true> : bl ? k_fp_q<true, false> : k_fp_q<false, false>;
             const int qstrips = (cols + FpQ::VW - 1) / FpQ::VW;
             hipLaunchKernelGGL(fpq, wave_grid(qstrips, batch, xm), b256, 0, st, (const void*)ctx->x6q, dst, cnt, rows, cols, qstrips, batch, xm,
                                p->max_depth, p->valid_thresh, (const int*)tc, bands);
-            // frames that are no multiples of 1/256 m: both f32 kernels again, gated on the flag the attempt raised (they return at once otherwise)
+            // frames that are no multiples of 1/256 m: both f32 kernels again, gated on the flag the attempt raised (k_pre_p returns at once
+            // otherwise; k_fp_s is k_tail's first phase, or a gated launch where no k_tail follows)
             // (the uint16 entry point too: a payload beyond 30719 = 119.996 m has no code)
             with_k0(k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, x6, nullptr, qbad, nullptr); });
-            gate = qbad;
         }
-        auto* fps = filled ? k_fp_s<true, true> : bl ? k_fp_s<true> : k_fp_s<false>;
-        hipLaunchKernelGGL(fps, wave_grid(pstrips * fb_s, batch, xm), b256, 0, st, x6, dst, cnt, rows, cols, pstrips, batch, xm, p->max_depth,
-                           p->valid_thresh, (const int*)tc, bands, gate, fb_s);
+        if (!q16 || !tail) {
+            auto* fps = filled ? k_fp_s<true, true> : bl ? k_fp_s<true> : k_fp_s<false>;
+            hipLaunchKernelGGL(fps, wave_grid(pstrips * fb_s, batch, xm), b256, 0, st, x6, dst, cnt, rows, cols, pstrips, batch, xm, p->max_depth,
+                               p->valid_thresh, (const int*)tc, bands, q16 ? (const int*)qbad : (const int*)nullptr, fb_s);
+        }
         DCMT_HIP(ctx, hipGetLastError());
         stamp(3);
         path_append(ctx, q16 ? " + k_fp_q" : (fb_s > 1 ? " + k_fp_s (row bands)" : " + k_fp_s"));
         ctx->last_has_loop = 1;
         int rc = DCMT_OK, apps = 0;
-        const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
-        if (n_redo > 0) {
-            if (sync_loop) {      // host entry points: look before launching anything else
+        if (tail) {
+            auto* kt = filled ? k_tail<true, true> : bl ? k_tail<true, false> : k_tail<false, false>;
+            hipLaunchKernelGGL(kt, dim3(batch), b256, 0, st, (const float*)x6, q16 ? (const unsigned short*)ctx->x6q : (const unsigned short*)nullptr,
+                               q16 ? (const int*)qbad : (const int*)nullptr, pp0, pp1, dst, cnt, n_redo, rows, cols, fstrips, pstrips, p->max_depth,
+                               p->valid_thresh, (const int*)tc, bands);
+            DCMT_HIP(ctx, hipGetLastError());
+            apps = n_redo;
+        } else if (n_redo > 0) {
+            {                     // host entry points: look before launching anything else
                 DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride, hipMemcpyDeviceToHost, st));
                 DCMT_HIP(ctx, hipStreamSynchronize(st));
                 bool any = false;
@@ -483,6 +497,42 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
     const int stop = p->stop_after;
     const int blur = force_gaussian ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
     ctx->tev_valid = 0;
+    // which kernels run.  The streaming kernels give one wave a whole column strip: a handful of frames cannot fill the GPU
+    // with them, there the staged tile kernels (hundreds of small workgroups per frame) win
+    const int kind = k0_preset(kb);
+    const bool labeled = d_labels && use_superpixel;
+    const bool big_enough = batch >= ctx->min_fused_batch || (p->flags & DCMT_FLAG_FORCE_FUSED);
+    const bool streaming = !(p->flags & DCMT_FLAG_FORCE_STAGED) && big_enough && kind >= 0 && rows >= 8 && cols >= 8;
+    const bool lc_fast = streaming && labeled && n_labels > 0 && (stop == DCMT_STAGE_FINAL || stop == DCMT_STAGE_CLOSE5);
+    const bool fused = streaming && !labeled && stop >= DCMT_STAGE_EXTEND;
+    // Scratch that only some paths use is allocated by the first call that takes such a path -- here, before anything of the call is
+    // enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.
+    if (!((p->flags & DCMT_FLAG_NORMALIZE) && stop == DCMT_STAGE_NORMALIZE)) {
+        if (lc_fast || fused) {
+            // (every call that may make a 16-bit attempt; run_chain_fused has the exact conditions)
+            if (ctx->fp_q16 && stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table && ctx->pair && cols % 2 == 0 && !(p->flags & DCMT_FLAG_NORMALIZE) &&
+                (long long)batch * ((cols + FpQ::VW - 1) / FpQ::VW) >= ctx->q16_min_waves && Q16::params_ok(p->max_depth, p->valid_thresh)) {
+                const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc;
+            }
+        } else {
+            const int erc = ensure_colstat(ctx); if (erc != DCMT_OK) return erc;
+        }
+        if (lc_fast) {
+            // LC fast path: per (frame, label) bounding boxes
+            const size_t need = (size_t)batch * n_labels * 2;
+            if (need > ctx->bb_ints) {
+                (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max);
+                ctx->bb_min = ctx->bb_max = nullptr; ctx->bb_ints = 0;
+                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_min, sizeof(int) * need));
+                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_max, sizeof(int) * need));
+                ctx->bb_ints = need;
+                // "no box" everywhere, once: the label stage's waves put every entry they have read back into this state (a fill in front
+                // of every call is two dependent operations with a bubble behind the previous call's last kernel each)
+                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
+                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
+            }
+        }
+    }
     if (ctx->timing && ctx->tev[0]) (void)hipEventRecord(ctx->tev[0], st);
     // In place (or overlapping) calls: every kernel that writes d_dst must run behind the last one that reads the input frames.  Where
     // the kernel that reads them would also write d_dst (the probes below, and stop_after = EXTEND in run_chain_fused), an overlapping
@@ -515,26 +565,8 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
         }
     }
     {
-        const int kind = k0_preset(kb);
-        const bool labeled = d_labels && use_superpixel;
-        // the streaming kernels give one wave a whole column strip: a handful of frames cannot fill the
-        // GPU with them, there the staged tile kernels (hundreds of small workgroups per frame) win
-        const bool big_enough = batch >= ctx->min_fused_batch || (p->flags & DCMT_FLAG_FORCE_FUSED);
-        if (!(p->flags & DCMT_FLAG_FORCE_STAGED) && big_enough && labeled && kind >= 0 && rows >= 8 && cols >= 8 && n_labels > 0 &&
-            (stop == DCMT_STAGE_FINAL || stop == DCMT_STAGE_CLOSE5)) {
+        if (lc_fast) {
             // LC fast path: bounding boxes -> one wave per label (masked H2..H4) -> X4 -> the img_completion kernels
-            const size_t need = (size_t)batch * n_labels * 2;
-            if (need > ctx->bb_ints) {
-                (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max);
-                ctx->bb_min = ctx->bb_max = nullptr; ctx->bb_ints = 0;
-                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_min, sizeof(int) * need));
-                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_max, sizeof(int) * need));
-                ctx->bb_ints = need;
-                // "no box" everywhere, once: the label stage's waves put every entry they have read back into this state (a fill in front
-                // of every call is two dependent operations with a bubble behind the previous call's last kernel each)
-                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
-                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
-            }
             // (dead before the redo chain writes pp[0]; x5 shares pp[1]).  The CLOSE5 probe is X4 itself, written straight to d_dst --
             // unless d_dst overlaps d_src: the label stage's waves read d_src around their label's box (wide boxes in column chunks, a
             // later chunk reading what an earlier one wrote) while others write X4, so X4 stays in pp[0] and is copied
@@ -590,8 +622,7 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
             q.blur = blur;
             return run_chain_fused(ctx, kind, d_src, d_dst, rows, cols, batch, &q, st, sync_loop, x4);
         }
-        if (!(p->flags & DCMT_FLAG_FORCE_STAGED) && big_enough && !labeled && kind >= 0 && rows >= 8 && cols >= 8 &&
-            stop >= DCMT_STAGE_EXTEND) {
+        if (fused) {
             dcmt_params q = *p;
             q.blur = blur;
             return run_chain_fused(ctx, kind, d_src, d_dst, rows, cols, batch, &q, st, sync_loop, nullptr, d_src16, in_scale, coef);
@@ -607,7 +638,6 @@ int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_
     ctx->last_apps_launched = 0;
     ctx->last_has_loop = 0;
 
-    { const int erc = ensure_colstat(ctx); if (erc != DCMT_OK) return erc; }
     std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s + k_fill31_v1 + k_post_v1 (staged tile kernels)", (d_labels && use_superpixel) ? "k_pre_labeled_v1" : "k_pre_v1");
     const int dump = stop <= DCMT_STAGE_CLOSE5 ? stop : 0;
     // Up to FILL7 the kernel that reads the frames writes the probe itself: stages 2..4 as its dump, FILL7 as its X5 output.  Into a

@@ -16,6 +16,8 @@
 //                      Gaussian, the masked select and the final invert in the same step.
 //   k_fill_s / k_post_s  the two halves of k_fp_s as separate kernels: the hole-closure loop
 //                      (H8) for the rare frames that need it, and the stop_after probes.
+//                      Their bodies (fill_strip, post_strip) and k_fp_s's (fp_s_unit) are __device__ functions over
+//                      (frame, strip), which k_tail (dcmt_kernels_tail.h) walks for the frames k_fp_* could not finish.
 //
 // Row indices in comments: i = input row of the current step; stage outputs lag behind.
 #pragma once
@@ -792,30 +794,18 @@ struct PostPipe {
     }
 };
 
-// only_if_holes: recompute pass behind k_fp_s -- frames that needed no loop application are
-// already final and are skipped.
+// H9..H11 of one post strip of one frame: `src` is the frame's X8 plane, `out` its plane of dst.  The body of k_post_s, and of
+// k_tail's last phase (dcmt_kernels_tail.h).
 template <int MODE, bool BLUR>
-__global__ __launch_bounds__(256)
-void k_post_s(const float* __restrict__ pp0, const float* __restrict__ pp1, float* __restrict__ dst,
-              const int* __restrict__ counters, int n_apps_launched, int rows, int cols, int strips,
-              int batch, int xcd_map, float max_depth, float thr, int only_if_holes)
+__device__ __forceinline__ void post_strip(const float* src, float* out, int rows, int cols, int strip, int lane, float max_depth, float thr)
 {
-    const int lane = threadIdx.x & 63;
-    int f, sg;
-    frame_unit(blockIdx.x, (strips + 3) / 4, batch, xcd_map, f, sg);
-    const int strip = sg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: keep it scalar
-    if (strip >= strips) return;
-    const int* cnt = counters + (size_t)f * kCntStride;
-    if (only_if_holes && cnt[1] == 0) return;
-    const int a = apps_done(cnt, n_apps_launched);
-    const size_t fo = (size_t)f * rows * cols;
     const int gx0 = strip * PostS::VW - PostS::H;
     const int gxc = min(max(gx0 + lane, 0), cols - 1);               // BORDER_REPLICATE for the median
     FrameBuf sf;
-    sf.init(((a & 1) ? pp1 : pp0) + fo, (size_t)rows * cols);
+    sf.init(src, (size_t)rows * cols);
     const unsigned sb = 4u * (unsigned)gxc;
     PostPipe<MODE, BLUR> pipe;
-    pipe.init(dst + fo, rows, cols, gx0, lane, max_depth, thr);
+    pipe.init(out, rows, cols, gx0, lane, max_depth, thr);
 
     float PF[8];
     constexpr int PFD = 4;
@@ -834,6 +824,26 @@ void k_post_s(const float* __restrict__ pp0, const float* __restrict__ pp1, floa
             pipe.template step<p>(x, t);
         });
     }
+}
+
+// only_if_holes: recompute pass behind k_fp_s -- frames that needed no loop application are
+// already final and are skipped.
+template <int MODE, bool BLUR>
+__global__ __launch_bounds__(256)
+void k_post_s(const float* __restrict__ pp0, const float* __restrict__ pp1, float* __restrict__ dst,
+              const int* __restrict__ counters, int n_apps_launched, int rows, int cols, int strips,
+              int batch, int xcd_map, float max_depth, float thr, int only_if_holes)
+{
+    const int lane = threadIdx.x & 63;
+    int f, sg;
+    frame_unit(blockIdx.x, (strips + 3) / 4, batch, xcd_map, f, sg);
+    const int strip = sg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: keep it scalar
+    if (strip >= strips) return;
+    const int* cnt = counters + (size_t)f * kCntStride;
+    if (only_if_holes && cnt[1] == 0) return;
+    const int a = apps_done(cnt, n_apps_launched);
+    const size_t fo = (size_t)f * rows * cols;
+    post_strip<MODE, BLUR>(((a & 1) ? pp1 : pp0) + fo, dst + fo, rows, cols, strip, lane, max_depth, thr);
 }
 
 // ---------------------------------------------------------------------------------
@@ -886,28 +896,17 @@ __device__ __forceinline__ void row_scans3(float a, float b, float& pa, float& s
 #undef DCMT_S3
 }
 
-__global__ __launch_bounds__(256)
-void k_fill_s(const float* __restrict__ in, float* __restrict__ out, int* __restrict__ counters,
-              int rows, int cols, int strips, int batch, int xcd_map, float thr, int app, int redo, const int* __restrict__ tb, int tbands,
-              const unsigned short* __restrict__ in16, const int* __restrict__ q16_bad)
+// One fill strip of one frame (the body of k_fill_s, and of k_tail's fill phases): `in` / `out` / `in16` are the frame's planes, cnt
+// its counter block, f its index (for the table).  q16: read the 16-bit codes of in16 instead of `in`.
+__device__ __forceinline__ void fill_strip(const float* in, float* out, int* cnt, int rows, int cols, int f, int strip, int lane, float thr,
+                                           int app, int redo, const int* tb, int tbands, const unsigned short* in16, bool q16)
 {
-    const int lane = threadIdx.x & 63;
-    int f, sg;
-    frame_unit(blockIdx.x, (strips + 3) / 4, batch, xcd_map, f, sg);
-    const int strip = sg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (strip >= strips) return;
-    int* cnt = frame_counters(counters, f);
-    if (app >= 1 && cnt[app] == 0) return;       // holes left by application app-1: none
-    if (redo && cnt[1] == 0) return;             // redo of application 0 behind k_fp_s: only frames that need the loop
     const int gx = strip * FillS::VW - FillS::R + lane;
     const bool outlane = gx >= 0 && gx < cols && lane >= FillS::R && lane < 64 - FillS::R;
-    const size_t fo = (size_t)f * rows * cols;
     const int gxc = min(max(gx, 0), cols - 1);
-    const float* sp = in + fo + gxc;
-    float* op = out + fo + gxc;
-    // in16: X6 was left as 16-bit codes (k_pre_p<Q16OUT>) unless that attempt raised *q16_bad and the f32 kernels reran into `in`
-    const bool q16 = in16 != nullptr && *q16_bad == 0;
-    const unsigned short* sq = in16 ? in16 + fo + gxc : nullptr;
+    const float* sp = in + gxc;
+    float* op = out + gxc;
+    const unsigned short* sq = in16 ? in16 + gxc : nullptr;      // (q16 implies in16)
     auto ld_in = [&](size_t off) -> float { return q16 ? Q16::value(sq[off]) : sp[off]; };
     const int a_lo = ((lane - FillS::R) & 63) * 4, a_hi = ((lane + FillS::R) & 63) * 4;   // bpermute byte addresses
     // tb: `in` is an X6 whose extension zones were never written (k_pre_s / k_pre_p, table mode): the rows above a column's first
@@ -968,6 +967,25 @@ void k_fill_s(const float* __restrict__ in, float* __restrict__ out, int* __rest
     }
 }
 
+__global__ __launch_bounds__(256)
+void k_fill_s(const float* __restrict__ in, float* __restrict__ out, int* __restrict__ counters,
+              int rows, int cols, int strips, int batch, int xcd_map, float thr, int app, int redo, const int* __restrict__ tb, int tbands,
+              const unsigned short* __restrict__ in16, const int* __restrict__ q16_bad)
+{
+    const int lane = threadIdx.x & 63;
+    int f, sg;
+    frame_unit(blockIdx.x, (strips + 3) / 4, batch, xcd_map, f, sg);
+    const int strip = sg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (strip >= strips) return;
+    int* cnt = frame_counters(counters, f);
+    if (app >= 1 && cnt[app] == 0) return;       // holes left by application app-1: none
+    if (redo && cnt[1] == 0) return;             // redo of application 0 behind k_fp_s: only frames that need the loop
+    const size_t fo = (size_t)f * rows * cols;
+    // in16: X6 was left as 16-bit codes (k_pre_p<Q16OUT>) unless that attempt raised *q16_bad and the f32 kernels reran into `in`
+    const bool q16 = in16 != nullptr && *q16_bad == 0;
+    fill_strip(in + fo, out + fo, cnt, rows, cols, f, strip, lane, thr, app, redo, tb, tbands, in16 ? in16 + fo : nullptr, q16);
+}
+
 // ---------------------------------------------------------------------------------
 // k_fp_s : k_fill_s (application 0) and k_post_s in ONE streaming kernel -- X7 never goes to
 // memory.  One wave64 owns the 64 columns of a post strip (56 of them produce output).
@@ -989,30 +1007,21 @@ void k_fill_s(const float* __restrict__ in, float* __restrict__ out, int* __rest
 //
 // Correct only for frames that need no hole-closure loop application (the common case: every
 // hole is filled by H7).  The kernel counts the holes it leaves per frame (cnt[1]); frames with
-// cnt[1] > 0 are recomputed afterwards by k_fill_s / k_post_s (their only_if_holes modes).
+// cnt[1] > 0 are recomputed afterwards: by k_tail (dcmt_kernels_tail.h) on the device entry points, by k_fill_s / k_post_s
+// (their only_if_holes modes) on the host entry points.
 // ---------------------------------------------------------------------------------
 constexpr int kBandHalo = 19;        // rows of X6 an output row needs above and below it: 15 (H7) + 2 (median) + 2 (Gaussian)
 struct FpS {
     static constexpr int LAG = 29;               // post step u = t - LAG: it takes X7 row u - 2 = t - 31, which the fill front end returns in the same step
 };
 
-template <bool BLUR, bool FILLED = false>
-__global__ __launch_bounds__(256)
-void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restrict__ counters,
-            int rows_all, int cols, int strips, int batch, int xcd_map, float max_depth, float thr, const int* __restrict__ tb,
-            int tbands, const int* __restrict__ gate, int fbands)
+// One (strip, band) unit of one frame: the body of k_fp_s, and of k_tail's f32 rerun behind a 16-bit attempt that raised its flag
+// (dcmt_kernels_tail.h).  x6 / dst are the frame's planes, cnt its counter block, f its index (for the table), delay the calling
+// wave's 16 * (64 + 64 + 32) floats of LDS (initialised here: a wave may run one unit after another).
+template <bool BLUR, bool FILLED>
+__device__ __forceinline__ void fp_s_unit(float* delay, const float* x6, float* dst, int* cnt, int rows_all, int cols, int f, int strip, int band,
+                                          int lane, float max_depth, float thr, const int* tb, int tbands, int fbands)
 {
-    if (gate && *gate == 0) return;          // the f32 rerun behind a 16-bit attempt (k_fp_q): only if that attempt raised its flag
-    // per wave, three 15-step delay lines: centre values, A's 16-row maxima (64 lanes each), B's 16-row
-    // maxima (only its 30 halo lanes: packed to 32) -- 10 KiB per wave, 40 KiB per workgroup: 4 fit a CU
-    __shared__ float s_delay[4][16 * (64 + 64 + 32)];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int f, unit;
-    if (!wave_strip(blockIdx.x, wave, strips * fbands, batch, xcd_map, f, unit)) return;
-    const int strip = unit % strips, band = unit / strips;           // fbands > 1: the strip in row bands, one wave each (small batches)
-    int* cnt = frame_counters(counters, f);
-    const size_t fo = (size_t)f * rows_all * cols;
     const int gx0 = strip * PostS::VW - PostS::H;
     const int gxa = gx0 + lane;
     // B: lanes 0..14 = the 15 columns right of the strip (ascending); lanes 49..63 = the 15 columns left of it
@@ -1057,7 +1066,7 @@ void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restri
         if (band == fbands - 1) so1 = rows;
     }
     FrameBuf sf;
-    sf.init(x6 + fo, (size_t)rows_all * cols);
+    sf.init(x6, (size_t)rows_all * cols);
     const unsigned rowb = 4u * (unsigned)cols;
     const unsigned sba = 4u * (unsigned)gxac + (unsigned)V * rowb;   // byte offset of (row V, this lane's column)
     const unsigned sbb = 4u * (unsigned)gxbc + (unsigned)V * rowb;
@@ -1073,13 +1082,13 @@ void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restri
     const bool edge_strip = gx0 < 0 || gx0 + 63 >= cols;
     const int src_lane = min(max(gxa, 0), cols - 1) - gx0;          // BORDER_REPLICATE columns for the median
     const int a_lo = (lane < 15 ? 63 - lane : lane - 15) * 4, a_hi = ((lane + 15) & 63) * 4;   // ds_bpermute byte addresses
-    float (*dl_c)[64] = reinterpret_cast<float (*)[64]>(s_delay[wave]);
-    float (*dl_a)[64] = reinterpret_cast<float (*)[64]>(s_delay[wave] + 16 * 64);
-    float (*dl_b)[32] = reinterpret_cast<float (*)[32]>(s_delay[wave] + 16 * 128);
+    float (*dl_c)[64] = reinterpret_cast<float (*)[64]>(delay);
+    float (*dl_a)[64] = reinterpret_cast<float (*)[64]>(delay + 16 * 64);
+    float (*dl_b)[32] = reinterpret_cast<float (*)[32]>(delay + 16 * 128);
     const int lb = lane <= 14 ? lane : (lane >= 48 ? lane - 32 : 15);   // B's live lanes 0..14, 48..63 -> words 0..14, 16..31; the dead lanes share word 15
 
     PostPipe<11, BLUR, FILLED> pipe;
-    pipe.init(dst + fo + (size_t)V * cols, rows, cols, gx0, lane, max_depth, thr);
+    pipe.init(dst + (size_t)V * cols, rows, cols, gx0, lane, max_depth, thr);
     pipe.so0 = so0; pipe.so1 = so1;
 
     constexpr float NEG = -FLT_MAX;
@@ -1199,7 +1208,7 @@ void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restri
             // u == 6: output row 0 of the shifted frame (image row V) has just been stored; the V rows above it are equal
             if (t0 == 32 && V > 0 && band == 0) {
                 FrameBuf top;
-                top.init(dst + fo, (size_t)V * cols);
+                top.init(dst, (size_t)V * cols);
                 const unsigned tb = pipe.outlane ? pipe.ob : kDropOffset;
                 for (int r = 0; r < V; ++r) top.st(tb, r, cols, pipe.last_out);
             }
@@ -1218,6 +1227,27 @@ void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restri
         if (before) atomicAdd(&cnt[0], before);
         if (after) atomicAdd(&cnt[1], after);
     }
+}
+
+
+template <bool BLUR, bool FILLED = false>
+__global__ __launch_bounds__(256)
+void k_fp_s(const float* __restrict__ x6, float* __restrict__ dst, int* __restrict__ counters,
+            int rows_all, int cols, int strips, int batch, int xcd_map, float max_depth, float thr, const int* __restrict__ tb,
+            int tbands, const int* __restrict__ gate, int fbands)
+{
+    if (gate && *gate == 0) return;
+    // per wave, three 15-step delay lines: centre values, A's 16-row maxima (64 lanes each), B's 16-row
+    // maxima (only its 30 halo lanes: packed to 32) -- 10 KiB per wave, 40 KiB per workgroup: 4 fit a CU
+    __shared__ float s_delay[4][16 * (64 + 64 + 32)];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int f, unit;
+    if (!wave_strip(blockIdx.x, wave, strips * fbands, batch, xcd_map, f, unit)) return;
+    const int strip = unit % strips, band = unit / strips;           // fbands > 1: the strip in row bands, one wave each (small batches)
+    const size_t fo = (size_t)f * rows_all * cols;
+    fp_s_unit<BLUR, FILLED>(s_delay[wave], x6 + fo, dst + fo, frame_counters(counters, f), rows_all, cols, f, strip, band, lane, max_depth, thr,
+                            tb, tbands, fbands);
 }
 
 }  // namespace dcmt

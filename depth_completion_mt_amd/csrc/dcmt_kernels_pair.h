@@ -219,6 +219,9 @@ void k_pre_p(const void* __restrict__ src_, float* __restrict__ x6, int rows, in
     // and the OR of the residues are looked at once, behind the loop
     unsigned chk_max = 0, chk_or = 0;
 
+    constexpr bool LEAN_STORE = Q16OUT && !START4 && !U16;
+    const unsigned st_col = outlane ? (Q16OUT ? qc : oc) : kDropOffset;   // where this lane's stores go, once it has something to store
+    const unsigned long long band_rows = band > 0 ? ~0ull : 0ull;
     const int nsteps = r1 + G::LAT;
     // One row step.  INNER: every row the step touches (i - 6 .. i) lies inside the image, every lane's columns do, and the x5 row
     // it finishes belongs to this wave -- the border selects (one per stage and column) and the row tests are compiled out.  The
@@ -298,13 +301,26 @@ void k_pre_p(const void* __restrict__ src_, float* __restrict__ x6, int rows, in
             tie = __builtin_amdgcn_inverse_ballot_w64(ve & ~seen_e) ? m : tie; tio = __builtin_amdgcn_inverse_ballot_w64(vo & ~seen_o) ? m : tio;
             bie = __builtin_amdgcn_inverse_ballot_w64(ve) ? m : bie; bio = __builtin_amdgcn_inverse_ballot_w64(vo) ? m : bio;
             seen_e |= ve; seen_o |= vo;
+            asm volatile("" : "+v"(tie), "+v"(tio), "+v"(bie), "+v"(bio));   // here, not at the end of the block of eight: deferred, the four
+                                                                            // selects keep the compare masks of all eight steps in SGPRs (30-80 of them spilled, read back by v_readlane in the loops)
         }
         // both columns leave in one 8-byte store once either has had its first valid row (what lands above a column's own first
         // valid row is never read in table mode and rewritten by the epilogue otherwise); the store itself is issued on every
         // step by every lane, aimed past the buffer when there is nothing to write (no branch in the row step)
         // (a band below the first one stores all its rows: the rows between a column's first valid row in an upper band and its
         // first one here are real holes that the reader looks at)
-        const bool real = inrows && outlane && (band > 0 || __builtin_amdgcn_inverse_ballot_w64(seen_e | seen_o));
+        // LEAN_STORE (the raw-f32 16-bit instantiation, the one the large batches run): one select on the lane's precomputed offset st_col.
+        // Written as outlane && ..., the lane test becomes an s_and_saveexec region around the select in every step; the other
+        // instantiations keep that form, because with this one their allocation grows to 144-173 VGPRs (resource usage of `make asm`).
+        unsigned sa;                                                 // byte offset of the lane's column pair, or kDropOffset
+        [[maybe_unused]] bool real = false;
+        if constexpr (LEAN_STORE) {
+            const bool seen_any = __builtin_amdgcn_inverse_ballot_w64(seen_e | seen_o | band_rows);
+            sa = (inrows && seen_any) ? st_col : kDropOffset;
+        } else {
+            real = inrows && outlane && (band > 0 || __builtin_amdgcn_inverse_ballot_w64(seen_e | seen_o));
+            sa = real ? (Q16OUT ? qc : oc) : kDropOffset;
+        }
         if constexpr (Q16OUT) {
             // code = 256 x + OFFSET through the float adder: y = fma(x, 256, OFFSET + 2^23) lies in [2^23, 2^24) for every code, where the
             // low mantissa bits ARE the integer -- no v_cvt; the two low halves leave as one dword (v_perm_b32)
@@ -321,9 +337,9 @@ void k_pre_p(const void* __restrict__ src_, float* __restrict__ x6, int rows, in
                 bad |= real ? diff : 0u;
             }
             const unsigned packed = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, yo), __builtin_bit_cast(unsigned, ye), 0x05040100u);
-            __builtin_amdgcn_raw_buffer_store_b32(packed, ob.rs, real ? qc : kDropOffset, (inrows ? m : 0) * cols * 2, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(packed, ob.rs, sa, (inrows ? m : 0) * cols * 2, 0);
         } else {
-            st2(ob, real ? oc : kDropOffset, inrows ? m : 0, cols, x5);
+            st2(ob, sa, inrows ? m : 0, cols, x5);
         }
     };
     // three loops, not one loop with a choice inside (which costs 40 registers: the allocator then has to agree on every ring slot's
