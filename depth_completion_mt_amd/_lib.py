@@ -32,6 +32,7 @@ EXPORTS = (
     "dcmt_project_points", "dcmt_slic_labels", "dcmt_stereo_refine", "dcmt_last_path",
     "dcmt_evaluate_dev", "dcmt_evaluate_u16_dev", "dcmt_evaluate",
     "dcmt_colorize_dev", "dcmt_colorize", "dcmt_colormap_jet",
+    "dcmt_default_cloud_params", "dcmt_depth_to_cloud_dev", "dcmt_depth_to_cloud", "dcmt_gaussian5_dev", "dcmt_gaussian5",
 )
 
 
@@ -63,6 +64,17 @@ class EvalFrame(ctypes.Structure):
     """Mirror of dcmt_eval_frame (include/dcmt.h): one frame's sums against ground truth."""
     _fields_ = [("n", ctypes.c_double), ("sum_err", ctypes.c_double), ("sum_abs", ctypes.c_double), ("sum_sq", ctypes.c_double),
                 ("n_inv", ctypes.c_double), ("sum_inv_abs", ctypes.c_double), ("sum_inv_sq", ctypes.c_double)]
+
+
+class CloudParams(ctypes.Structure):
+    """Mirror of dcmt_cloud_params (include/dcmt.h): the pinhole intrinsics of the back-projection."""
+    _fields_ = [("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double)]
+
+
+class CloudPoint(ctypes.Structure):
+    """Mirror of dcmt_cloud_point (include/dcmt.h): one 16-byte record."""
+    _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("z", ctypes.c_float),
+                ("b", ctypes.c_uint8), ("g", ctypes.c_uint8), ("r", ctypes.c_uint8), ("a", ctypes.c_uint8)]
 
 
 def build(force: bool = False) -> str:
@@ -139,6 +151,13 @@ def lib() -> ctypes.CDLL:
         L.dcmt_colorize.argtypes = [vp, vp, sz, i, i, vp, sz]
         L.dcmt_colormap_jet.argtypes = [vp]
         L.dcmt_colormap_jet.restype = None
+        i64 = ctypes.c_int64
+        L.dcmt_default_cloud_params.argtypes = [vp]
+        L.dcmt_default_cloud_params.restype = None
+        L.dcmt_depth_to_cloud_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, i64, vp, vp]
+        L.dcmt_depth_to_cloud.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i64, ctypes.POINTER(i64)]
+        L.dcmt_gaussian5_dev.argtypes = [vp, vp, vp, i, i, i, vp]
+        L.dcmt_gaussian5.argtypes = [vp, vp, sz, vp, sz, i, i]
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

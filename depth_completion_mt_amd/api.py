@@ -9,6 +9,8 @@
         reference: src/DC_lidar_only/main.cpp:16, src/DC_lidar_camera/main_lc.cpp:85, src/DC_stereo_lidar/main_sl.cpp:1031
     to_color_image(r_img) -> the BGR JET image the reference's toColorImage makes
         reference: src/DC_lidar_only/main.cpp:6-14
+    reproject_pc_colors(depth, bgr) / reproject_pc(depth) -> the ordered point cloud of a dense plane
+        reference: src/DC_stereo_lidar/main_sl.cpp:924-965, :887-922
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -73,6 +75,20 @@ def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int =
     if normalize is not None:
         p.flags |= L.FLAG_NORMALIZE
         p.norm_lo, p.norm_hi = float(normalize[0]), float(normalize[1])
+    return p
+
+
+# one record of a cloud (dcmt_cloud_point): 16 bytes, the layout PCL's PointXYZRGB has in a binary .pcd
+CLOUD_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])
+
+
+def make_cloud_params(fx: float | None = None, fy: float | None = None, cx: float | None = None, cy: float | None = None) -> L.CloudParams:
+    """dcmt_cloud_params: the reference's intrinsics (SL/main_sl.cpp:927-930) unless given."""
+    p = L.CloudParams()
+    L.lib().dcmt_default_cloud_params(ctypes.byref(p))
+    for k, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy)):
+        if v is not None:
+            setattr(p, k, float(v))
     return p
 
 
@@ -320,6 +336,94 @@ class Context:
             raise DcmtError(st, "dcmt_colorize")
         return out
 
+    # ---- point cloud of a dense plane (dcmt_depth_to_cloud*) and the blur in front of it (dcmt_gaussian5*) -----------
+    def depth_to_cloud_dev(self, d_depth, d_bgr=None, params: L.CloudParams | None = None, d_points=None, d_offsets=None,
+                           capacity: int | None = None, stream: int | None = None):
+        """The reference's reproject_pc_colors / reproject_pc (SL/main_sl.cpp:924-965, :887-922) on the device: one record per pixel
+        with depth > 0, frames in batch order, pixels row-major.  d_depth: contiguous f32 CUDA tensor [batch][rows][cols] (or
+        [rows][cols]: a batch of one); d_bgr: uint8 CUDA tensor of d_depth's shape + (3,) or None (fourth dword 1.0f).
+        Returns (points, offsets): points float32 [capacity, 4] (default capacity batch * rows * cols; the fourth column holds the
+        colour BITS b | g << 8 | r << 16 | 255 << 24: compare and slice it through .view(torch.int32) / .view(torch.uint8)),
+        offsets int32 [batch + 1]; frame f owns points[offsets[f]:offsets[f + 1]].  Rows of points from offsets[batch] on are not
+        written.  No synchronisation."""
+        import torch
+        assert d_depth.is_cuda and d_depth.dtype == torch.float32 and d_depth.is_contiguous()
+        shp = d_depth.shape if d_depth.dim() == 3 else (1,) + tuple(d_depth.shape)
+        b, r, c = shp
+        if d_bgr is not None:
+            assert d_bgr.is_cuda and d_bgr.dtype == torch.uint8 and d_bgr.is_contiguous() and d_bgr.numel() == 3 * b * r * c
+        if capacity is None:
+            capacity = d_points.numel() // 4 if d_points is not None else b * r * c
+        if d_points is None:
+            d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
+        assert d_points.is_cuda and d_points.dtype == torch.float32 and d_points.is_contiguous() and d_points.numel() >= 4 * capacity
+        if d_offsets is None:
+            d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
+        assert d_offsets.is_cuda and d_offsets.dtype == torch.int32 and d_offsets.is_contiguous() and d_offsets.numel() == b + 1
+        p = params or make_cloud_params()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_depth.device).cuda_stream
+        st = L.lib().dcmt_depth_to_cloud_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
+                                             ctypes.byref(p), d_points.data_ptr(), int(capacity), d_offsets.data_ptr(),
+                                             ctypes.c_void_p(stream))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_depth_to_cloud_dev")
+        return d_points, d_offsets
+
+    def depth_to_cloud(self, depth: np.ndarray, bgr: np.ndarray | None = None, params: L.CloudParams | None = None) -> np.ndarray:
+        """One frame of host memory (dcmt_depth_to_cloud, synchronous; any row stride): a structured array (CLOUD_DTYPE: x y z f32,
+        b g r a u8) of the true length."""
+        a = np.asarray(depth, dtype=np.float32)
+        assert a.ndim == 2
+        if a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        rows, cols = a.shape
+        col = None
+        if bgr is not None:
+            col = np.asarray(bgr, dtype=np.uint8)
+            assert col.shape == (rows, cols, 3)
+            if col.strides[1] != 3 or col.strides[2] != 1:
+                col = np.ascontiguousarray(col)
+        out = np.empty(rows * cols, dtype=CLOUD_DTYPE)
+        n = ctypes.c_int64(0)
+        p = params or make_cloud_params()
+        st = L.lib().dcmt_depth_to_cloud(self._h, a.ctypes.data, a.strides[0], col.ctypes.data if col is not None else None,
+                                         col.strides[0] if col is not None else 0, rows, cols, ctypes.byref(p), out.ctypes.data,
+                                         out.size, ctypes.byref(n))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_depth_to_cloud")
+        return out[:n.value].copy()
+
+    def gaussian5_dev(self, d_src, d_dst=None, stream: int | None = None):
+        """cv::GaussianBlur(src, dst, Size(5, 5), 0) on the device (dcmt_gaussian5_dev; SL/main_sl.cpp:1253), without the cascade's
+        masked select.  d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]); d_dst may be d_src (in place).
+        Returns d_dst without synchronising."""
+        import torch
+        assert d_src.is_cuda and d_src.dtype == torch.float32 and d_src.is_contiguous()
+        shp = d_src.shape if d_src.dim() == 3 else (1,) + tuple(d_src.shape)
+        b, r, c = shp
+        if d_dst is None:
+            d_dst = torch.full_like(d_src, float("nan"))
+        assert d_dst.is_cuda and d_dst.dtype == torch.float32 and d_dst.is_contiguous() and d_dst.numel() == d_src.numel()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        st = L.lib().dcmt_gaussian5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, ctypes.c_void_p(stream))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_gaussian5_dev")
+        return d_dst
+
+    def gaussian5(self, frame: np.ndarray) -> np.ndarray:
+        """One frame of host memory (dcmt_gaussian5, synchronous; any row stride): a new f32 array."""
+        a = np.asarray(frame, dtype=np.float32)
+        assert a.ndim == 2
+        if a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        out = np.empty(a.shape, dtype=np.float32)
+        st = L.lib().dcmt_gaussian5(self._h, a.ctypes.data, a.strides[0], out.ctypes.data, out.strides[0], a.shape[0], a.shape[1])
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_gaussian5")
+        return out
+
     def last_fill_iters(self, n: int):
         out = (ctypes.c_int * n)()
         st = L.lib().dcmt_last_fill_iters(self._h, out, n)
@@ -395,6 +499,65 @@ def to_color_image(r_img):
         return _ctx_for(r_img.shape[-2], r_img.shape[-1], b, r_img.device.index or 0).colorize_dev(r_img)
     a = np.asarray(r_img, dtype=np.float32)
     return _ctx_for(a.shape[0], a.shape[1], 1).colorize(a)
+
+
+def reproject_pc_colors(depth, bgr):
+    """The reference's reproject_pc_colors (SL/main_sl.cpp:924-965) on one frame: the ordered coloured cloud of a depth plane.
+    numpy in: a structured array (CLOUD_DTYPE) of the true length, through the host entry point.  CUDA tensors in ([rows][cols]
+    f32 and [rows][cols][3] uint8): a float32 CUDA tensor [n, 4] of the true length (fourth column: the colour bits); reading the
+    count synchronises with torch's current stream."""
+    if hasattr(depth, "is_cuda") and depth.is_cuda:
+        assert depth.dim() == 2
+        pts, off = _ctx_for(depth.shape[0], depth.shape[1], 1, depth.device.index or 0).depth_to_cloud_dev(depth, bgr)
+        return pts[:int(off[1].item())]
+    a = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).depth_to_cloud(a, bgr)
+
+
+def reproject_pc(depth):
+    """The reference's reproject_pc (SL/main_sl.cpp:887-922): as reproject_pc_colors without a colour plane; the fourth dword of
+    every record is 1.0f."""
+    return reproject_pc_colors(depth, None)
+
+
+def write_pcd(path, points) -> None:
+    """Writes a cloud (CLOUD_DTYPE records, or anything of 16 bytes per record such as a float32 [n, 4] array) as the binary
+    .pcd pcl::PCDWriter::writeBinary makes of a PointXYZRGB cloud (SL/main_sl.cpp:962-963): FIELDS x y z rgb, SIZE 4 4 4 4,
+    TYPE F F F F, COUNT 1 1 1 1, WIDTH n, HEIGHT 1, POINTS n, DATA binary, then the records as they are.  The header text is
+    what PCL's file-format page documents; neither PCL nor a file written by it was available to compare with, so it is checked
+    only by the round trip through read_pcd."""
+    rec = np.ascontiguousarray(points)
+    if rec.dtype != CLOUD_DTYPE:
+        rec = rec.view(np.uint8).reshape(-1, 16).view(CLOUD_DTYPE).reshape(-1)
+    n = rec.shape[0]
+    head = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
+            f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_pcd(path) -> np.ndarray:
+    """Reads a binary .pcd of four 4-byte fields per point (what write_pcd writes) back into CLOUD_DTYPE records."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    fields, pos = {}, 0
+    while True:
+        end = blob.index(b"\n", pos)
+        line = blob[pos:end].decode("ascii")
+        pos = end + 1
+        if line.startswith("#") or not line.strip():
+            continue
+        key, _, val = line.partition(" ")
+        fields[key] = val.strip()
+        if key == "DATA":
+            break
+    if fields["DATA"] != "binary" or fields.get("SIZE") != "4 4 4 4" or fields.get("COUNT") != "1 1 1 1":
+        raise ValueError("read_pcd: only binary files of four 4-byte fields per point are supported")
+    n = int(fields["POINTS"])
+    if len(blob) - pos < 16 * n:
+        raise ValueError("read_pcd: file shorter than its POINTS line says")
+    return np.frombuffer(blob, dtype=CLOUD_DTYPE, count=n, offset=pos).copy()
 
 
 _jet = None

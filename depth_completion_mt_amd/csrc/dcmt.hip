@@ -25,6 +25,7 @@
 #include "dcmt_kernels_slic.h"
 #include "dcmt_kernels_eval.h"
 #include "dcmt_kernels_color.h"
+#include "dcmt_cloud.h"
 
 using namespace dcmt;
 
@@ -95,6 +96,8 @@ struct dcmt_ctx {
                                       // allocated by the first evaluate call
     float* color_slab = nullptr;      // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
                                       // (allocated by dcmt_create)
+    uint32_t* cloud_slab = nullptr;   // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
+                                      // color_slab, kCloudWaves entries per chunk (allocated by dcmt_create)
     int label_group = 0;              // LC fast path, two columns per lane: labels side by side per wave (0 = by label size); env DCMT_LABEL_GROUP
     int label_pairs = -1;             // LC fast path: one wave per label pair (1), per label (0), by label size (-1); env DCMT_LABEL_PAIRS
     int min_fused_batch = 3;          // smaller batches use the staged kernels (measured crossover with both streaming kernels in row bands,
@@ -816,6 +819,52 @@ int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batc
     return DCMT_OK;
 }
 
+// as finite_bits, for the f64 intrinsics of dcmt_cloud_params
+bool finite_bits64(double v)
+{
+    volatile double m = v;
+    uint64_t b;
+    double t = m;
+    std::memcpy(&b, &t, sizeof b);
+    return (b & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+
+// dcmt_depth_to_cloud_dev: per-wave counts, their exclusive scan in one workgroup, then the scatter (dcmt_kernels_cloud.h, compiled
+// in dcmt_cloud.hip)
+int depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                       const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, hipStream_t st)
+{
+    if (!ctx || !d_depth || !d_points || !d_offsets || !params) return DCMT_E_INVALID;
+    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
+    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
+    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
+    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
+    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
+    launch_depth_to_cloud(d_depth, d_bgr, n, (uint32_t)cols, chunks, eval_chunk_groups(n), (uint32_t)batch, k, ctx->cloud_slab, d_points,
+                          (uint32_t)std::min<int64_t>(capacity, INT32_MAX), d_offsets, st);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// dcmt_gaussian5_dev: one streaming kernel (k_gauss5, dcmt_kernels_cloud.h); an in-place call writes to pp[0] (scratch every cascade call rewrites before it reads it) and
+// copies the result over the source
+int gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, hipStream_t st)
+{
+    if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
+    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
+    const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
+    const bool in_place = d_dst == d_src;
+    if (!in_place && ranges_overlap(d_src, bytes, d_dst, bytes)) return DCMT_E_INVALID;
+    float* out = in_place ? ctx->pp[0] : d_dst;
+    launch_gauss5(d_src, out, rows, cols, batch, st);
+    DCMT_HIP(ctx, hipGetLastError());
+    if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -931,6 +980,8 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     if (hipMalloc((void**)&ctx->norm_coef, sizeof(float) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
     if (hipMalloc((void**)&ctx->color_slab, sizeof(float) * kColorSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)max_batch) != hipSuccess)
         return fail(DCMT_E_NOMEM);
+    if (hipMalloc((void**)&ctx->cloud_slab, sizeof(uint32_t) * kCloudWaves * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)max_batch) != hipSuccess)
+        return fail(DCMT_E_NOMEM);
     if (hipHostMalloc((void**)&ctx->h_counters, sizeof(int) * (size_t)kCntStride * max_batch, hipHostMallocDefault) != hipSuccess)
         return fail(DCMT_E_NOMEM);
     *out = ctx;
@@ -949,7 +1000,7 @@ void dcmt_destroy(dcmt_ctx* ctx)
     (void)hipFree(ctx->d_in); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_lab);
     (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max); (void)hipFree(ctx->winner);
     (void)hipFree(ctx->slic_cells); (void)hipFree(ctx->slic_centers[0]); (void)hipFree(ctx->slic_centers[1]);
-    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab); (void)hipFree(ctx->color_slab);
+    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab); (void)hipFree(ctx->color_slab); (void)hipFree(ctx->cloud_slab);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     for (auto e : ctx->tev) if (e) (void)hipEventDestroy(e);
     delete ctx;
@@ -1101,6 +1152,28 @@ void dcmt_colormap_jet(uint8_t bgr[768])
         bgr[3 * i + 1] = (uint8_t)(jet[i] >> 8);
         bgr[3 * i + 2] = (uint8_t)(jet[i] >> 16);
     }
+}
+
+void dcmt_default_cloud_params(dcmt_cloud_params* p)
+{
+    if (!p) return;
+    p->fx = 9.597910e+02;   // main_sl.cpp:927-930
+    p->fy = 9.569251e+02;
+    p->cx = 6.960217e+02;
+    p->cy = 2.241806e+02;
+}
+
+int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                            const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return depth_to_cloud_dev(ctx, d_depth, d_bgr, rows, cols, batch, params, d_points, capacity, d_offsets, (hipStream_t)stream);
+}
+
+int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return gaussian5_dev(ctx, d_src, d_dst, rows, cols, batch, (hipStream_t)stream);
 }
 
 int dcmt_slic_num_centers(int rows, int cols, int step)
@@ -1301,6 +1374,55 @@ int dcmt_colorize(dcmt_ctx* ctx, const float* src, size_t srs, int rows, int col
     rc = dcmt_colorize_dev(ctx, (const float*)ds.p, rows, cols, 1, (uint8_t*)dout.p, st);
     if (rc != DCMT_OK) return rc;
     DCMT_HIP(ctx, hipMemcpy2DAsync(bgr, ors, dout.p, brow, brow, rows, hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return DCMT_OK;
+}
+
+int dcmt_depth_to_cloud(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_t* bgr, size_t brs, int rows, int cols,
+                        const dcmt_cloud_params* params, dcmt_cloud_point* points, int64_t capacity, int64_t* n_points)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !points || !n_points || !params || rows < 1 || cols < 1 || capacity < 0) return DCMT_E_INVALID;
+    if (drs < sizeof(float) * (size_t)cols || (bgr && brs < 3 * (size_t)cols)) return DCMT_E_INVALID;
+    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    hipStream_t st;
+    int rc = host_stream(ctx, &st);
+    if (rc != DCMT_OK) return rc;
+    DevBuf dd, dc, dp, doff;
+    const size_t frow = sizeof(float) * (size_t)cols, brow = 3 * (size_t)cols;
+    const int64_t room = std::min<int64_t>(capacity, (int64_t)rows * cols);         // a frame never has more records than pixels
+    if ((rc = dd.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dp.alloc(ctx, sizeof(dcmt_cloud_point) * (size_t)room)) != DCMT_OK ||
+        (rc = doff.alloc(ctx, sizeof(int32_t) * 2)) != DCMT_OK || (bgr && (rc = dc.alloc(ctx, brow * rows)) != DCMT_OK)) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(dd.p, frow, depth, drs, frow, rows, hipMemcpyHostToDevice, st));
+    if (bgr) DCMT_HIP(ctx, hipMemcpy2DAsync(dc.p, brow, bgr, brs, brow, rows, hipMemcpyHostToDevice, st));
+    rc = dcmt_depth_to_cloud_dev(ctx, (const float*)dd.p, bgr ? (const uint8_t*)dc.p : nullptr, rows, cols, 1, params,
+                                 (dcmt_cloud_point*)dp.p, room, (int32_t*)doff.p, st);
+    if (rc != DCMT_OK) return rc;
+    int32_t off[2] = {0, 0};
+    DCMT_HIP(ctx, hipMemcpyAsync(off, doff.p, sizeof(off), hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    const int64_t have = std::min<int64_t>(off[1], room);
+    if (have > 0) DCMT_HIP(ctx, hipMemcpy(points, dp.p, sizeof(dcmt_cloud_point) * (size_t)have, hipMemcpyDeviceToHost));
+    *n_points = off[1];
+    return DCMT_OK;
+}
+
+int dcmt_gaussian5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size_t drs, int rows, int cols)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !src || !dst || rows < 1 || cols < 1) return DCMT_E_INVALID;
+    if (srs < sizeof(float) * (size_t)cols || drs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
+    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    hipStream_t st;
+    int rc = host_stream(ctx, &st);
+    if (rc != DCMT_OK) return rc;
+    DevBuf ds, dout;
+    const size_t frow = sizeof(float) * (size_t)cols;
+    if ((rc = ds.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, frow * rows)) != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(ds.p, frow, src, srs, frow, rows, hipMemcpyHostToDevice, st));
+    rc = dcmt_gaussian5_dev(ctx, (const float*)ds.p, (float*)dout.p, rows, cols, 1, st);
+    if (rc != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(dst, drs, dout.p, frow, frow, rows, hipMemcpyDeviceToHost, st));
     DCMT_HIP(ctx, hipStreamSynchronize(st));
     return DCMT_OK;
 }

@@ -1,0 +1,259 @@
+// dcmt_kernels_cloud.h -- what DC_stereo_lidar/main_sl.cpp does with the refined depth after the path (:1251-1270), batched on
+// the device:
+//     cv::GaussianBlur(optimized_depth, optimized_depth, cv::Size(5, 5), 0);                         (:1253)  k_gauss5
+//     reproject_pc_colors(optimized_depth, colour image, ...)  /  reproject_pc(optimized_depth)      (:924-965, :887-922)
+//
+// Back-projection: every pixel with depth > 0 (an f32 compare) becomes one 16-byte record, frames in batch order, pixels
+// row-major -- the reference's push_back order:
+//     z = depth;  x_ = (float)(((double)x - cx) * (double)z / fx);  y_ = (float)(((double)y - cy) * (double)z / fy);
+// f64 subtraction, product and a true division, one rounding each, then one rounding to f32.  The fourth dword holds
+// b | g << 8 | r << 16 | 255 << 24 from the colour plane (PointXYZRGB), or 1.0f without one (PointXYZ's padding, and the
+// [x y z w] record dcmt_project_points_dev reads).
+//
+// An order-preserving stream compaction with integer counts only; no workgroup waits on another, no atomics:
+//   k_cloud_count    one workgroup per (chunk, frame), the chunking of dcmt_kernels_eval.h.  A frame is a flat run of groups
+//                    of 4 pixels; each of the workgroup's 4 waves owns a contiguous quarter of the chunk's groups and walks it
+//                    64 groups (256 pixels) per step, lane l on group l of the step.  One count per wave to the slab:
+//                    [frame][chunk][wave] uint32;
+//   k_cloud_scan     ONE workgroup: the exclusive scan of the slab in (frame, chunk, wave) order, in place, and d_offsets
+//                    (the base of each frame's first entry, and the total).  Integer sums: the result does not depend on how
+//                    the slab is cut among the workgroup's waves;
+//   k_cloud_scatter  the same runs.  A wave carries a wave-uniform base, advanced by the popcount of each step; inside a step
+//                    the rank of pixel i of lane l = sum_k mbcnt(ballot_k) + the lane's own earlier pixels.  (row, col) from one
+//                    integer division per group and a carry.  The step's records go through a per-wave LDS stage in rank order
+//                    (no workgroup barrier: a wave only reads what it wrote itself), so that lane l of a round computes and
+//                    stores record 64 * round + l: consecutive 16-byte stores, and on a sparse plane one round of f64
+//                    divisions per step with every lane at work instead of four with a few.  64-bit addressing; a record
+//                    whose global index is >= capacity is not stored.
+// Depth loads are 16 bytes at any dword alignment and colour loads 12 bytes at any byte alignment (gfx950's global loads run
+// in unaligned mode, as k_eval_partial / k_color_minmax rely on); the partial last group of a frame (n % 4 pixels) goes pixel
+// by pixel.  A frame's records depend only on its own pixels; only the base depends on what lies in front of it.
+// Bytes per pixel: 4 (count) + 4 (re-read) + 3 (colour) + 16 * (share of pixels with depth > 0).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "dcmt_cloud.h"
+#include "dcmt_gauss.h"
+
+namespace dcmt {
+
+constexpr int kCloudThreads = 64 * kCloudWaves;
+constexpr int kCloudScanThreads = 1024;
+
+// the groups [ws, we) of wave w of chunk c (G groups per chunk: eval_chunk_groups(n)): a contiguous quarter of the chunk
+__device__ __forceinline__ void cloud_wave_run(uint32_t n, uint32_t G, uint32_t c, uint32_t w, uint32_t& ws, uint32_t& we)
+{
+    const uint32_t ng = (n + 3) / 4;
+    const uint32_t g0 = c * G, g1 = min(g0 + G, ng), W = (G + kCloudWaves - 1) / kCloudWaves;
+    ws = min(g0 + w * W, g1);
+    we = min(ws + W, g1);
+}
+
+// the 4 pixels of group g of a frame (0 where the group is beyond the run or the pixel beyond the frame)
+__device__ __forceinline__ void cloud_load4(const float* __restrict__ p, uint32_t g, uint32_t n, bool active, float d[4])
+{
+    if (active && g < n / 4) {
+        float4 t;
+        __builtin_memcpy(&t, p + 4 * (size_t)g, sizeof t);
+        d[0] = t.x; d[1] = t.y; d[2] = t.z; d[3] = t.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t q = 4 * g + i;
+            d[i] = active && q < n ? p[q] : 0.0f;
+        }
+    }
+}
+
+// grid (eval_chunks(n), frames), 256 threads; G = eval_chunk_groups(n).  slab: [frames][chunks][kCloudWaves] counts
+__global__ __launch_bounds__(kCloudThreads)
+void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
+    const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
+    uint32_t ws, we;
+    cloud_wave_run(n, G, blockIdx.x, w, ws, we);
+    uint32_t cnt = 0;
+    for (uint32_t gb = ws; gb < we; gb += 64) {
+        float d[4];
+        cloud_load4(p, gb + l, n, gb + l < we, d);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) cnt += (uint32_t)__popcll(__ballot(d[i] > 0.0f));
+    }
+    if (l == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + w] = cnt;
+}
+
+// one workgroup of 1024 threads.  slab: entries counts in, exclusive bases out; per = entries per frame (chunks * kCloudWaves, a
+// multiple of 4); offsets: [frames + 1].  Each of the 16 waves owns one contiguous sixteenth of the slab and walks it in tiles of
+// 256 entries, 16 bytes per lane: first the wave's total, then -- behind the one barrier, with the totals of the waves in front
+// as the carry -- the scan of its tiles (4 entries in the lane, a shuffle scan over the lanes, a wave-uniform carry).
+__global__ __launch_bounds__(kCloudScanThreads)
+void k_cloud_scan(uint32_t* __restrict__ slab, uint32_t entries, uint32_t per, uint32_t frames, int32_t* __restrict__ offsets)
+{
+    constexpr uint32_t kWaves = kCloudScanThreads / 64;
+    __shared__ uint32_t wsum[kWaves];
+    const uint32_t l = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+    const uint32_t S = ((entries + kWaves - 1) / kWaves + 255) & ~255u;
+    const uint32_t s0 = min(w * S, entries), s1 = min(s0 + S, entries);       // multiples of 4: an access is inside or outside
+    uint4* __restrict__ v = reinterpret_cast<uint4*>(slab);
+    uint32_t s = 0;
+#pragma unroll 4
+    for (uint32_t e = s0 + 4 * l; e < s1; e += 256) { const uint4 a = v[e / 4]; s += a.x + a.y + a.z + a.w; }
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    if (l == 0) wsum[w] = s;
+    __syncthreads();
+    uint32_t run = 0;
+    for (uint32_t j = 0; j < w; ++j) run += wsum[j];
+    if (threadIdx.x == kCloudScanThreads - 1) offsets[frames] = (int32_t)(run + s);
+    for (uint32_t tb = s0; tb < s1; tb += 256) {
+        const uint32_t e = tb + 4 * l;
+        uint4 a = {0u, 0u, 0u, 0u};
+        if (e < s1) a = v[e / 4];
+        const uint32_t t = a.x + a.y + a.z + a.w;
+        uint32_t inc = t;
+        for (int m = 1; m < 64; m <<= 1) { const uint32_t o = __shfl_up(inc, m, 64); if ((int)l >= m) inc += o; }
+        if (e < s1) {
+            uint4 b;
+            b.x = run + inc - t; b.y = b.x + a.x; b.z = b.y + a.y; b.w = b.z + a.z;
+            if (e % per == 0) offsets[e / per] = (int32_t)b.x;                 // per % 4 == 0: a frame starts on an access
+            v[e / 4] = b;
+        }
+        run += __shfl(inc, 63, 64);
+    }
+}
+
+// grid (eval_chunks(n), frames), 256 threads.  slab: the bases k_cloud_scan left.  bgr: [frames][n][3] bytes or null.
+template <bool kColor>
+__global__ __launch_bounds__(kCloudThreads)
+void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict__ bgr, uint32_t n, uint32_t G, uint32_t cols, CloudK k,
+                     const uint32_t* __restrict__ slab, uint4* __restrict__ points, uint32_t capacity)
+{
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
+    const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
+    const uint8_t* __restrict__ cp = kColor ? bgr + 3 * (size_t)blockIdx.y * n : nullptr;
+    uint32_t ws, we;
+    cloud_wave_run(n, G, blockIdx.x, w, ws, we);
+    __shared__ uint4 stage_all[kCloudWaves][256];          // per wave: the records of one step (up to 256), in rank order
+    uint4* stage = stage_all[w];
+    uint32_t base = slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + w];     // wave-uniform
+    if (base >= capacity) return;                         // the whole run lies beyond the caller's room
+    for (uint32_t gb = ws; gb < we; gb += 64) {
+        const uint32_t g = gb + l, q = 4 * g;
+        const bool active = g < we;
+        float d[4];
+        cloud_load4(p, g, n, active, d);
+        uint32_t c[4] = {0x3f800000u, 0x3f800000u, 0x3f800000u, 0x3f800000u};       // 1.0f
+        if (kColor) {
+            if (active && g < n / 4) {
+                uint3 t;
+                __builtin_memcpy(&t, cp + 3 * (size_t)q, sizeof t);
+                c[0] = t.x | 0xff000000u;
+                c[1] = (t.x >> 24) | (t.y << 8) | 0xff000000u;
+                c[2] = (t.y >> 16) | (t.z << 16) | 0xff000000u;
+                c[3] = (t.z >> 8) | 0xff000000u;
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (active && q + i < n) {
+                        const uint8_t* s = cp + 3 * (size_t)(q + i);
+                        c[i] = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | 0xff000000u;
+                    }
+            }
+        }
+        bool v[4];
+        uint32_t lower = 0, step = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[i] = d[i] > 0.0f;
+            const unsigned long long b = __ballot(v[i]);
+            lower += __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+            step += (uint32_t)__popcll(b);
+        }
+        // the step's records in rank order to the wave's LDS stage (pixel, row, column, fourth dword) ...
+        uint32_t r = lower;
+        uint32_t row = q / cols, col = q - row * cols;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i > 0 && ++col == cols) { col = 0; ++row; }
+            if (v[i]) {
+                uint4 e;
+                e.x = __float_as_uint(d[i]); e.y = col; e.z = row; e.w = c[i];
+                stage[r++] = e;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // ... and out again 64 at a time: lane l computes and stores record j + l, so a store instruction writes consecutive
+        // records and every lane of a round divides (one round per step on a sparse plane, four on a dense one)
+        for (uint32_t j = 0; j < step; j += 64) {
+            const uint32_t slot = j + l;
+            if (slot < step && base + slot < capacity) {
+                const uint4 e = stage[slot];
+                const double z = (double)__uint_as_float(e.x);
+                uint4 o;
+                o.x = __float_as_uint((float)__ddiv_rn(__dmul_rn(__dsub_rn((double)e.y, k.cx), z), k.fx));
+                o.y = __float_as_uint((float)__ddiv_rn(__dmul_rn(__dsub_rn((double)e.z, k.cy), z), k.fy));
+                o.z = e.x;
+                o.w = e.w;
+                points[(size_t)(base + slot)] = o;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        base += step;
+    }
+}
+
+// ---- cv::GaussianBlur(src, dst, Size(5, 5), 0) without the cascade's masked select ------------------------------------------
+// [1 4 6 4 1]/16, rows then columns, BORDER_REFLECT_101 (reflect101: 0 for a length of 1, repeated reflection for 2), each pass
+// gauss_taps.  A wave streams down a strip of 64 columns (60 outputs, 2 halo columns either side; lane l holds column
+// x0 - 2 + l, reflected into the frame) over a band of band_rows output rows (kGaussRows; fewer for a handful of frames, so that
+// they still make a few thousand waves): a row is one coalesced load per lane, its
+// neighbours come through lane shuffles, the row pass results of the last 5 rows stay in registers for the column pass.  No LDS,
+// no barrier; the loads of kGaussBatch rows go out together.  src and dst must not overlap (the entry point sends an in-place
+// call through scratch).
+constexpr int kGaussCols = 60, kGaussRows = 32, kGaussBatch = 6;
+
+// grid (ceil(strips * bands / 4), frames), 256 threads: one wave per (strip, band); strips = ceil(cols / kGaussCols),
+// bands = ceil(rows / band_rows)
+__global__ __launch_bounds__(256)
+void k_gauss5(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols, int strips, int bands, int band_rows)
+{
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
+    const int id = blockIdx.x * 4 + w;
+    if (id >= strips * bands) return;
+    const int band = id / strips, strip = id - band * strips;
+    const size_t fo = (size_t)blockIdx.y * rows * cols;
+    const float* __restrict__ s = src + fo;
+    const int gx = strip * kGaussCols - 2 + l;
+    // columns and rows beyond the frame's own reflection zone are clamped to something readable; no output depends on them
+    const int cx = reflect101(min(gx, cols + 1), cols);
+    const bool out_col = l >= 2 && l < 62 && gx < cols;
+    const int y0 = band * band_rows, R = min(band_rows, rows - y0);
+    float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, h3 = 0.0f, h4 = 0.0f;
+    for (int i0 = 0; i0 < R + 4; i0 += kGaussBatch) {          // input row i of the band is frame row y0 + i - 2
+        float v[kGaussBatch];
+#pragma unroll
+        for (int j = 0; j < kGaussBatch; ++j) {
+            const int sy = reflect101(min(y0 + i0 + j - 2, rows + 1), rows);
+            v[j] = s[(size_t)sy * cols + cx];
+        }
+#pragma unroll
+        for (int j = 0; j < kGaussBatch; ++j) {
+            const int i = i0 + j;
+            if (i < R + 4) {                                   // wave-uniform
+                const float l1 = __shfl_up(v[j], 1, 64), r1 = __shfl_down(v[j], 1, 64);
+                const float l2 = __shfl_up(v[j], 2, 64), r2 = __shfl_down(v[j], 2, 64);
+                h0 = h1; h1 = h2; h2 = h3; h3 = h4;
+                h4 = gauss_taps(v[j], __fadd_rn(l1, r1), __fadd_rn(l2, r2));
+                if (i >= 4 && out_col)
+                    dst[fo + (size_t)(y0 + i - 4) * cols + gx] = gauss_taps(h2, __fadd_rn(h1, h3), __fadd_rn(h0, h4));
+            }
+        }
+    }
+}
+
+}  // namespace dcmt

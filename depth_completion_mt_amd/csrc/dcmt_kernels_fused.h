@@ -690,15 +690,7 @@ struct PostS {
     static constexpr int VW = 64 - 2 * H;
 };
 
-// One pass of the [1 4 6 4 1]/16 filter in the reference order  c*k0 + s1*k1 + s2*k2  (s1, s2 = the already rounded
-// sums of the two neighbour pairs; every product rounded, the sum taken left to right).  k1 = 1/4 and k2 = 1/16 are
-// powers of two, so those two products are exact and folding them into fused multiply-adds changes no rounding:
-// round(a + exact(s*k)) is what the unfused sequence computes too.  (The one exception is a product that underflows
-// into a subnormal and loses bits there, |s| < 2^-122 -- forty orders of magnitude below a depth in metres.)
-__device__ __forceinline__ float gauss_taps(float c, float s1, float s2)
-{
-    return __builtin_fmaf(s2, 0.0625f, __builtin_fmaf(s1, 0.25f, __fmul_rn(c, 0.375f)));
-}
+// gauss_taps, one pass of the [1 4 6 4 1]/16 filter in the reference order: dcmt_gauss.h (through dcmt_kernels_v1.h)
 
 // The streaming post pipeline (H9..H11) of one wave: state + one step.  Shared by k_post_s
 // (input rows from global memory) and k_fp_s (input rows straight from the fill stage).

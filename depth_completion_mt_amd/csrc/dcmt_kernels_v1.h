@@ -20,6 +20,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include "dcmt_gauss.h"
 #include <float.h>
 #include <stdint.h>
 
@@ -731,12 +732,7 @@ void k_fill31_v1(const float* __restrict__ in, float* __restrict__ out, const in
 //            the frame after its last fill application.
 // mode: 8 = copy only (probe of H8), 9 = stop after the median, 10 = after the blur, 11 = all
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect101(int p, int len)
-{
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = p < 0 ? -p : 2 * len - 2 - p;
-    return p;
-}
+// reflect101 (BORDER_REFLECT_101): dcmt_gauss.h
 
 // which ping-pong buffer holds frame f after the loop applications that actually ran
 __device__ __forceinline__ int apps_done(const int* cnt, int n_apps_launched)

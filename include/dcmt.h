@@ -154,7 +154,7 @@ int dcmt_device_count(void);
  * 16-bit plane of large on-grid batches, 2 B per pixel; the column statistics of the small-batch tile kernels); SLIC scratch and
  * the partial-sum slab of the evaluate calls are allocated the same way by the first call that needs them, so no call
  * after the first of its kind allocates.  The min/max slab of dcmt_colorize* (8 B per 8192 pixels of a frame, times max_batch)
- * is allocated here.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
+ * and the count slab of dcmt_depth_to_cloud* (16 B per 8192 pixels, times max_batch) are allocated here.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
  * and one offset just below 2^31 is kept free as "nowhere"); max_batch at most 65535. */
 int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx **out);
 void dcmt_destroy(dcmt_ctx *ctx);
@@ -352,6 +352,60 @@ int dcmt_colorize_dev(dcmt_ctx *ctx, const float *d_src, int rows, int cols, int
 int dcmt_colorize(dcmt_ctx *ctx, const float *src, size_t src_row_stride, int rows, int cols, uint8_t *bgr, size_t bgr_row_stride);
 /* The palette the kernels use: cv::COLORMAP_JET's 256 entries in index order, each B, G, R.  Needs no GPU. */
 void dcmt_colormap_jet(uint8_t bgr[768]);
+
+/* ---- the dense plane as an ordered point cloud, and the blur in front of it ------------------------------ */
+
+/* What DC_stereo_lidar/main_sl.cpp does with the refined depth after the path (:1251-1270): an unmasked 5x5 Gaussian (:1253),
+ * toColorImage (:1257, :1259: dcmt_colorize_dev), and reproject_pc_colors (:924-965; its colourless twin reproject_pc :887-922),
+ * which turns the plane into the ordered, coloured point cloud the executable writes as colored_point_cloud.pcd.
+ *
+ * Back-projection: frames in batch order, pixels row-major (y outer, x inner: the reference's push_back order), one record
+ * only where depth > 0 as an f32 compare (so -0.0, 0 and negatives give none), exactly the reference's statements (:934-955):
+ *     z  = depth
+ *     x_ = (float)(((double)x - cx) * (double)z / fx)      f64 subtraction, product and a true IEEE division, one rounding
+ *     y_ = (float)(((double)y - cy) * (double)z / fy)      each, then one rounding to f32
+ *     b, g, r = d_bgr[frame][y][x][0..2], a = 255          (PointXYZRGB sets alpha 255)
+ *     d_bgr == NULL (reproject_pc): the fourth dword is 1.0f (PCL's PointXYZ padding; also the [x y z w] record that
+ *                                   dcmt_project_points_dev reads, so a cloud can go straight back into the projection). */
+typedef struct { double fx, fy, cx, cy; } dcmt_cloud_params;              /* 9.597910e+02, 9.569251e+02, 6.960217e+02, 2.241806e+02: main_sl.cpp:927-930 */
+typedef struct { float x, y, z; uint8_t b, g, r, a; } dcmt_cloud_point;   /* 16 bytes */
+void dcmt_default_cloud_params(dcmt_cloud_params *p);
+
+/* DEVICE pointers, stream-ordered.  d_depth: contiguous f32 [batch][rows][cols], 4-byte aligned; d_bgr: [batch][rows][cols][3]
+ * bytes, any alignment, or NULL -- the layout dcmt_colorize_dev writes, so the colourised depth (the reference's commented line
+ * :943) or a camera image (:944) can be passed.
+ * d_offsets: [batch + 1] int32; frame f owns records [d_offsets[f], d_offsets[f+1]), d_offsets[0] = 0, d_offsets[batch] = the
+ * total: the convention of dcmt_project_points_dev.  The offsets are always the true counts.
+ * d_points: ONE packed run for the whole batch, 16-byte aligned, room for `capacity` records.  A record whose global index is
+ * >= capacity is not written and nothing at or beyond min(total, capacity) records is touched; the call never synchronises, so
+ * the caller sees an overflow as d_offsets[batch] > capacity.  capacity = batch * rows * cols can never overflow.
+ * Never synchronises.  May be enqueued right behind any other *_dev call of the ctx on the same stream (same ordering rule as
+ * every *_dev call on one ctx); it touches none of the state the cascade carries from call to call (the 16-bit flag ring, the
+ * normalisation extrema, the bounding-box tables, the projection's winner plane) and leaves dcmt_last_path and the probes alone.
+ * Uses a count slab that dcmt_create allocates (16 B per 8192 pixels of a max_rows x max_cols frame, times max_batch); never
+ * allocates.  Integer counts and an integer scan in a fixed order: no atomics, no memset.  A frame's records depend only on its
+ * own pixels -- not on batch, its position in the batch, alignment or the run; only its offset depends on the frames before it.
+ * DCMT_E_INVALID: null ctx / d_depth / d_points / d_offsets / params, sizes beyond the ctx limits, capacity < 0,
+ * batch * rows * cols > INT32_MAX, d_depth not 4-byte or d_points not 16-byte aligned, a non-finite intrinsic, fx or fy zero. */
+int dcmt_depth_to_cloud_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_bgr /* or NULL */,
+                            int rows, int cols, int batch, const dcmt_cloud_params *params,
+                            dcmt_cloud_point *d_points, int64_t capacity, int32_t *d_offsets, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES; bgr may be NULL): the same bytes as the device call.  Writes
+ * min(*n_points, capacity) records; *n_points is the true count. */
+int dcmt_depth_to_cloud(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
+                        const uint8_t *bgr /* or NULL */, size_t bgr_row_stride, int rows, int cols,
+                        const dcmt_cloud_params *params, dcmt_cloud_point *points, int64_t capacity, int64_t *n_points);
+
+/* cv::GaussianBlur(src, dst, Size(5, 5), 0) on its own (main_sl.cpp:1253), WITHOUT the masked select of DCMT_STAGE_BLUR: the fixed
+ * table [1 4 6 4 1]/16, rows then columns, BORDER_REFLECT_101, each pass c*k0 + (l1 + r1)*k1 + (l2 + r2)*k2 in f32, every
+ * operation rounded once.  d_src / d_dst: contiguous f32 [batch][rows][cols], 4-byte aligned.  d_dst == d_src is allowed (the
+ * reference's call is in place) and gives the bits of an out-of-place call: the result goes to context scratch (one of the two
+ * planes dcmt_create allocates, which every completion call rewrites before it reads it) and one device-to-device copy moves it
+ * to d_dst.  Any other overlap is DCMT_E_INVALID.  Stream-ordered, never synchronises, never allocates; same standing behind
+ * other *_dev calls as dcmt_depth_to_cloud_dev. */
+int dcmt_gaussian5_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
+int dcmt_gaussian5(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols);
 
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 

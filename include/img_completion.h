@@ -198,6 +198,39 @@ inline void to_color_image(const cv::Mat& r_img, cv::Mat& color_img)
     color_img = out;
 }
 
+// cv::GaussianBlur(src, dst, cv::Size(5, 5), 0) as DC_stereo_lidar/main_sl.cpp:1253 calls it on the refined depth (in place there:
+// src and dst may be the same Mat).  CV_32FC1 in, a fresh CV_32FC1 out.
+inline void gaussian_blur5(const cv::Mat& src, cv::Mat& dst)
+{
+    check_input(src);
+    const int rows = src.rows, cols = src.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    raise(dcmt_gaussian5(thread_ctx().get(rows, cols), src.ptr<float>(), src.step[0], out.ptr<float>(), out.step[0], rows, cols),
+          "gaussian_blur5");
+    dst = out;
+}
+
+// reproject_pc_colors / reproject_pc (DC_stereo_lidar/main_sl.cpp:924-965, :887-922): the records of the ordered point cloud of a
+// CV_32FC1 depth plane, one per pixel with depth > 0, row-major.  bgr: CV_8UC3 of the depth's size, or an empty Mat (then the
+// fourth dword of every record is 1.0f).  params == nullptr: the reference's intrinsics (:927-930).
+inline void depth_to_cloud(const cv::Mat& depth, const cv::Mat& bgr, std::vector<dcmt_cloud_point>& out, const dcmt_cloud_params* params = nullptr)
+{
+    check_input(depth);
+    const int rows = depth.rows, cols = depth.cols;
+    const bool colour = !bgr.empty();
+    if (colour && (bgr.type() != CV_8UC3 || bgr.rows != rows || bgr.cols != cols))
+        throw std::runtime_error("depth_to_cloud: colour image must be CV_8UC3 of the depth's size");
+    dcmt_cloud_params def;
+    dcmt_default_cloud_params(&def);
+    out.resize((size_t)rows * cols);
+    int64_t n = 0;
+    raise(dcmt_depth_to_cloud(thread_ctx().get(rows, cols), depth.ptr<float>(), depth.step[0], colour ? bgr.ptr<unsigned char>() : nullptr,
+                              colour ? bgr.step[0] : 0, rows, cols, params ? params : &def, out.data(), (int64_t)out.size(), &n),
+          "depth_to_cloud");
+    out.resize((size_t)n);
+}
+
 }  // namespace dcmt_shim
 
 // reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there.
