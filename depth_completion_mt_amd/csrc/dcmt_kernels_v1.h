@@ -230,8 +230,11 @@ void k_project_resolve(const float* __restrict__ pts, ProjMats M, const unsigned
 // pixels (rows 1..R-2, cols 1..C-2), 0 on the border (:719-745; byte-valued, so exact in f32).
 // calculateObservationDerivatives (:749-801) as called from optimize_IG: r = i exactly, so r0 = i, dr = 0, dr1 = 1 and
 // the lower row of the bilinear patch carries weight 0 -- only row i matters; c0 = (int)(c + 0.5) (a double sum,
-// truncated), accepted when 0 <= c0 and c0 + 1 <= cols, and `at<>(r0, cols)` for c0 + 1 == cols is the next element in
-// memory, i.e. the first pixel of the next row (past the buffer for the last row: that one pixel is left as it is).
+// truncated), accepted when 0 <= c0 and c0 + 1 <= cols.  For c0 + 1 == cols the reference's `at<EntryType>(r0, cols)` is
+// undefined (48-byte elements addressed in 12-byte steps: bytes inside row r0 that nothing writes); here, as in the oracle,
+// the image is one dense run of pixels and p01 is the first pixel of the next row (the frame's very last pixel is left
+// as it is).  Both derivative entries of such a patch are border entries, so dx = 0 and the disparity keeps its value
+// whichever grey value is read ("The right edge of the stereo patch").
 // f32 arithmetic, one rounding per operation, in the reference's order.
 // ---------------------------------------------------------------------------------
 struct StereoP { float baseline, focal, damp, max_depth; int iterations; };
@@ -246,7 +249,7 @@ __device__ __forceinline__ float grey_dx(const uint8_t* g, int r, int c, int row
 // row, 256 columns at a time (five workgroups per 1242-pixel row, each staging the row, took 1.12 ms instead of 0.91) --
 // or (ceil(cols / 256), rows, batch) without; no index divisions.  Per Gauss-Newton sweep the reference
 // touches six right-image bytes (p00, p01 and the central differences at both); p01 is the neighbour of p00 in memory
-// (e1 = e0 + 1, also across the end of a row, which the reference's at<>() reads too), so the six are four distinct bytes:
+// (e1 = e0 + 1, also across the end of a row, where the reference's own read is undefined, see above), so the six are four distinct bytes:
 // g[e0-1], g[e0], g[e1], g[e1+1].  All arithmetic as in the oracle: one rounding per operation, IEEE divisions where the
 // reference divides (initial disparity, every sweep's step, final depth).
 // LDS_ROW: the workgroup first stages the whole right-image row (and the first pixel of the next one) in LDS: a sweep's

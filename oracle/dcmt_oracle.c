@@ -1,9 +1,10 @@
 /*
  * dcmt_oracle.c -- CPU restatement of the reference's `img_completion` cascade.
  *
- * TEST INFRASTRUCTURE, NOT PRODUCT CODE (see dcmt_oracle.h).  PARITY UNPINNED: OpenCV,
- * which holds the reference's arithmetic, is not available here and the reference has
- * no tests/fixtures for this path; OpenCV's documented semantics are restated below.
+ * TEST INFRASTRUCTURE, NOT PRODUCT CODE (see dcmt_oracle.h).  The reference's own statements
+ * restated here are held bit for bit to a build of its unmodified sources
+ * (tests/test_reference_parity.py); OpenCV, which holds the rest of the arithmetic, is not
+ * available here, and its documented semantics are restated below.
  *
  * Every function cites the reference lines it follows.  LO = src/DC_lidar_only,
  * LC = src/DC_lidar_camera (paths relative to /root/reference).
@@ -631,7 +632,8 @@ void dcmt_oracle_project_points(const float *points, int n, const float T[16], c
  * rounded, no contraction (-ffp-contract=off).  A centre that loses all its pixels becomes NaN in the reference and
  * its window loop never runs again (`k < NaN` is false); here it is flagged dead to the same effect.
  * create_connectivity (:186-259) only fills a local array nothing reads, so it is not part of the path.
- * PARITY UNPINNED, as the rest of this file (never diffed against an executing build of the reference). */
+ * Bit-identical (labels, live centres, NaN positions of dead ones) to slic.cpp compiled unmodified
+ * (tests/test_reference_parity.py). */
 static double slic_dist(const double *c, int x, int y, const uint8_t *px, int nc, int ns)
 {
     const double d0 = c[0] - (double)px[0], d1 = c[1] - (double)px[1], d2 = c[2] - (double)px[2];
@@ -715,12 +717,18 @@ int dcmt_oracle_slic(const uint8_t *lab, int rows, int cols, int step, int nc, i
  *     :749-801 with img_point = (i, pixel_right): r = i, c = pixel_right, r0 = (int)(r+0.5) = i, c0 = (int)(c+0.5)
  *     (double sum, truncated); rejected if c0 < 0 or c0 + 1 > cols (:762-772, with its `>` comparisons);
  *     dr = r - r0 = 0, dr1 = 1: the lower patch row has weight 0 and drops out; value and derivative are the linear
- *     interpolation between entries (i, c0) and (i, c0 + 1) -- for c0 + 1 == cols that `at<>` is the next element in
- *     memory, the first pixel of row i + 1 (past the buffer on the last row: the reference's behaviour is undefined
- *     there, this restatement leaves that pixel unchanged);
+ *     interpolation between entries (i, c0) and (i, c0 + 1).  For c0 + 1 == cols the reference's `at<EntryType>(i, cols)` is
+ *     UNDEFINED: its images are CV_32FC(sizeof(EntryType)) -- 48 bytes per pixel, addressed in 12-byte steps -- so that
+ *     entry lies inside row i's own allocation, in bytes nothing ever writes (and the lower patch row of the last image row,
+ *     weight 0, lies behind the buffer).  This restatement takes the image as one dense run of pixels instead: p01 is the
+ *     first pixel of row i + 1, and the very last pixel of the frame is left unchanged.  Either way the disparity keeps its
+ *     value there as long as the derivative read is 0: both entries of such a patch are border entries with derivative 0,
+ *     so dx = 0 and the step is +-0 ("The right edge of the stereo patch"; the reference build
+ *     of the tests zero-fills its images, and agrees there too);
  *     error = value - left value, clamped to +-255; J = -1; H = (J*dx)^2 + 500; disparity += -(J*dx*error)/H;
  *   retrieve_optimized_depth :863-885: depth = (baseline*focal)/disparity where disparity > 0, capped at 100.
- * f32, one rounding per operation, the reference's order (this file: -ffp-contract=off).  PARITY UNPINNED. */
+ * f32, one rounding per operation, the reference's order (this file: -ffp-contract=off).  Bit-identical to the reference's
+ * own functions compiled against a stand-in Eigen::Vector2f (tests/test_reference_parity.py). */
 static float grey_dx(const uint8_t *g, int r, int c, int rows, int cols)
 {
     if (r < 1 || r >= rows - 1 || c < 1 || c >= cols - 1) return 0.0f;

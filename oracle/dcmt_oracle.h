@@ -5,13 +5,14 @@
  * bench.py's cpu_baseline leg may link or call anything declared here.  The shipped
  * path (depth_completion_mt_amd/, include/dcmt.h) never falls back to it.
  *
- * PARITY UNPINNED: the arithmetic of the reference lives in OpenCV (un-vendored,
- * version un-pinned; cv::dilate / morphologyEx / medianBlur / GaussianBlur), which is
- * not installed in the build image, and the reference ships no tests, fixtures or
- * golden vectors for this path.  This file restates the reference's stage order
- * (/root/reference/src/DC_lidar_only/img_completion.cpp:17-204 and
- * src/DC_lidar_camera/img_completion_lc.cpp:34-203) plus OpenCV's documented
- * semantics; it has never been diffed against an executing OpenCV.
+ * PARITY: the reference's own statements are pinned -- tests/test_reference_parity.py
+ * compares this file bit for bit with a build of the reference's unmodified sources
+ * (oracle/refbuild/, oracle/_ref/).  The arithmetic inside OpenCV (un-vendored, version
+ * un-pinned; cv::dilate / morphologyEx / medianBlur / GaussianBlur) is restated from its
+ * documentation here, in the numpy twin and in that build's stand-in header; OpenCV is not
+ * installed in the build image and none of the three has been diffed against it.
+ * Stage order: the reference's src/DC_lidar_only/img_completion.cpp:17-204 and
+ * src/DC_lidar_camera/img_completion_lc.cpp:34-203.
  */
 #ifndef DCMT_ORACLE_H
 #define DCMT_ORACLE_H

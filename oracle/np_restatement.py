@@ -1,7 +1,7 @@
 """Second, independently written restatement of the reference cascade, in numpy.
 
-TEST INFRASTRUCTURE, NOT PRODUCT CODE.  PARITY UNPINNED (OpenCV absent, the reference
-ships no fixtures).  This file exists to (a) cross-check oracle/dcmt_oracle.c -- two
+TEST INFRASTRUCTURE, NOT PRODUCT CODE.  OpenCV's primitives are restated (OpenCV absent); the
+reference's own logic is held to a build of its sources (tests/test_reference_parity.py).  This file exists to (a) cross-check oracle/dcmt_oracle.c -- two
 restatements written in different styles (whole-array shifted slices here, scalar loops
 there) agreeing bit for bit is the best substitute for executing OpenCV that this image
 allows -- and (b) generate the golden vectors in tests/golden/ (tests/golden/make_golden.py).

@@ -1,8 +1,9 @@
 """ctypes binding of the C oracle (oracle/dcmt_oracle.c).
 
 TEST INFRASTRUCTURE, NOT PRODUCT CODE.  Only tests/, __graft_entry__.smoke() and
-bench.py's cpu_baseline leg may import this module.  PARITY UNPINNED (see
-dcmt_oracle.h): OpenCV is absent and the reference ships no fixtures for this path.
+bench.py's cpu_baseline leg may import this module.  Held bit for bit to a build of the
+reference's own sources (oracle/ref.py, tests/test_reference_parity.py); OpenCV's primitives
+are restated from its documentation (dcmt_oracle.h).
 """
 from __future__ import annotations
 
