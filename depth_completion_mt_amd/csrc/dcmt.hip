@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "dcmt.h"
+#include "dcmt_plan.h"
 #include "dcmt_kernels_v1.h"
 #include "dcmt_kernels_fused.h"
 #include "dcmt_kernels_pair.h"
@@ -57,20 +58,7 @@ struct dcmt_ctx {
     int timing = 0;                   // dcmt_set_kernel_timing: events around the kernel groups of the streaming path
     hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int tev_valid = 0;                // the last call recorded all five
-    int poison = 0;                   // env DCMT_POISON=1: fill the staging output with NaN before every host call
-    int xcd_map = 1;                  // XCD-aware workgroup->frame mapping; env DCMT_XCD_MAP=0 disables
-    int wide = 1;                     // LDS-DMA row loads where alignment allows; env DCMT_WIDE=0 disables
-    int fuse_fp = 1;                  // H7..H11 in one kernel (k_fp_s); env DCMT_FUSE_FP=0 keeps k_fill_s + k_post_s
-    int top_table = 1;                // k_pre leaves the extension zones of X6 unwritten, k_fp_s clamps its rows and starts below the top one; env DCMT_TOP_TABLE=0 disables
-    int pair = 1;                     // two columns per lane in H2..H6 (k_pre_p) where the width is even; env DCMT_PAIR=0 keeps k_pre_s
-    int bands = 0;                    // row bands per strip in k_pre_p (0 = by batch size); env DCMT_BANDS
-    int fbands = 0;                   // row bands per strip in k_fp_s (0 = by batch size); env DCMT_FBANDS
-    int fp_q16 = 1;                   // X6 as 16-bit codes + k_fp_q wherever the frames allow it (multiples of 1/256 m: checked on the device, the f32
-                                      // kernels rerun behind a raised flag); env DCMT_FP_Q16=0 disables
-    int assume_filled = 1;            // k_fp_s / k_fp_q without the median >= thr select where the redo chain follows; env DCMT_ASSUME_FILLED=0 keeps it
-    int q16_min_waves = 2600;         // ... and the batch is large enough: k_fp_q has half as many, longer waves than k_fp_s (3 per SIMD instead of 4), so it
-                                      // only pays from about one round of them on (measured, 352x1216, frames per call, whole step against the f32 kernels:
-                                      // 128 -12 %, 256 +3 %, 512 +4 %, 1024 +5 %; threshold = 236 frames); env DCMT_Q16_MIN_WAVES
+    plan::Knobs knobs;                // the environment knobs (dcmt_plan.h), read by dcmt_create
     unsigned short* x6q = nullptr;    // [max_batch][rows][cols] X6 as 16-bit codes (k_pre_p<Q16OUT> -> k_fp_q)
     int* q16_bad = nullptr;           // a ring of kQ16Flags flags; attempt n uses flag n % kQ16Flags: raised by k_pre_p<Q16OUT> when a value it stored was
                                       // not a code, and cleared one attempt ahead by that kernel too (no memset in the stream)
@@ -85,7 +73,6 @@ struct dcmt_ctx {
     int* bb_min = nullptr;            // LC fast path: per (frame, label) bounding boxes, grown on demand
     int* bb_max = nullptr;
     size_t bb_ints = 0;
-    int bbox_global = 0;              // LC fast path: the bounding-box pass without its per-workgroup LDS table; env DCMT_BBOX_GLOBAL
     // N3 (SLIC) scratch, allocated by the first dcmt_slic_labels_dev call
     int* slic_cells = nullptr;                  // two cell sets: counts [batch][cells] + overflow flags [batch] each, then the index lists [batch][cells][kSlicCellCap] each
     size_t slic_cell_cap = 0;                   // cells per frame that buffer holds
@@ -98,18 +85,29 @@ struct dcmt_ctx {
                                       // (allocated by dcmt_create)
     uint32_t* cloud_slab = nullptr;   // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
                                       // color_slab, kCloudWaves entries per chunk (allocated by dcmt_create)
-    int label_group = 0;              // LC fast path, two columns per lane: labels side by side per wave (0 = by label size); env DCMT_LABEL_GROUP
-    int label_pairs = -1;             // LC fast path: one wave per label pair (1), per label (0), by label size (-1); env DCMT_LABEL_PAIRS
-    int min_fused_batch = 3;          // smaller batches use the staged kernels (measured crossover with both streaming kernels in row bands,
-                                      // tools/batch_sweep.py: 1 frame 20.6 k staged / 17.1 k streaming, 2 frames 34.7 k / 34.0 k, 3 frames 39.5 k / 50.4 k,
-                                      // 4 frames 42.6 k / 65.7 k, 8 frames 52 k / 124 k frames/s); env DCMT_MIN_FUSED_BATCH
 };
 
 namespace {
 
-constexpr int TH = 32, TW = 64;
-constexpr int FTH_FEW = 16;          // tile height of the staged kernels for a handful of frames: twice the workgroups, a shorter
-                                     // critical path (a single frame's 209 tiles of 32 rows leave a fifth of the CUs idle)
+using plan::TH;
+using plan::TW;
+using plan::FTH_FEW;
+
+// dcmt_plan.h restates what the kernel headers and dcmt.h own: every copy is checked here
+static_assert(plan::kK0AsCompiled == K0_AS_COMPILED && plan::kK0Diamond == K0_DIAMOND, "k0 presets");
+static_assert(plan::pre_p_vw(K0_AS_COMPILED, false) == PreP<K0_AS_COMPILED, false>::VW && plan::pre_p_vw(K0_DIAMOND, false) == PreP<K0_DIAMOND, false>::VW &&
+              plan::pre_p_vw(K0_AS_COMPILED, true) == PreP<K0_AS_COMPILED, true>::VW && plan::pre_p_vw(K0_DIAMOND, true) == PreP<K0_DIAMOND, true>::VW, "PreP::VW");
+static_assert(plan::pre_s_vw(K0_AS_COMPILED, false) == PreS<K0_AS_COMPILED, false>::VW && plan::pre_s_vw(K0_AS_COMPILED, true) == PreS<K0_AS_COMPILED, true>::VW &&
+              plan::pre_s_vw(K0_DIAMOND, false) == PreS<K0_DIAMOND, false>::VW && plan::pre_s_vw(K0_DIAMOND, true) == PreS<K0_DIAMOND, true>::VW, "PreS::VW");
+static_assert(plan::kFpQVW == FpQ::VW && plan::kPostSVW == PostS::VW && plan::kFillSVW == FillS::VW, "FpQ / PostS / FillS::VW");
+static_assert(plan::kMaxBands == kMaxBands && plan::kLabelGroupMax == kLabelGroupMax, "kMaxBands, kLabelGroupMax");
+static_assert(plan::kStageNormalize == DCMT_STAGE_NORMALIZE && plan::kStageClose5 == DCMT_STAGE_CLOSE5 && plan::kStageFill7 == DCMT_STAGE_FILL7 &&
+              plan::kStageExtend == DCMT_STAGE_EXTEND && plan::kStageFinal == DCMT_STAGE_FINAL, "dcmt_stage");
+static_assert(plan::kFlagForceStaged == DCMT_FLAG_FORCE_STAGED && plan::kFlagForceFused == DCMT_FLAG_FORCE_FUSED &&
+              plan::kFlagNormalize == DCMT_FLAG_NORMALIZE, "DCMT_FLAG_*");
+static_assert(plan::q16_params_ok(100.0f, 0.1f) && Q16::params_ok(100.0f, 0.1f) && !plan::q16_params_ok(80.0f, 0.1f) && !Q16::params_ok(80.0f, 0.1f) &&
+              !plan::q16_params_ok(100.0f, 0.2f) && !Q16::params_ok(100.0f, 0.2f), "Q16::params_ok");
+static_assert(sizeof(plan::Plan::path) == sizeof(dcmt_ctx::last_path), "dcmt_last_path");
 
 #define DCMT_HIP(ctx, call)                                        \
     do {                                                           \
@@ -159,26 +157,16 @@ bool finite_bits(float v)
     return (b & 0x7f800000u) != 0x7f800000u;
 }
 
-// [a, a + a_bytes) and [b, b + b_bytes) share a byte: a completion call's input frames and its dst (in place, or overlapping)
-bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+// rows x cols x batch is a size the context was created for
+bool dims_ok(const dcmt_ctx* ctx, int rows, int cols, int batch)
 {
-    return (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
-}
-
-// dcmt_last_path of a call whose result went to scratch first and was then copied to its overlapping dst
-constexpr const char* kPathCopy = " + copy to dst";
-
-void path_append(dcmt_ctx* ctx, const char* s)
-{
-    const size_t n = std::strlen(ctx->last_path);
-    std::snprintf(ctx->last_path + n, sizeof ctx->last_path - n, "%s", s);
+    return rows >= 1 && cols >= 1 && batch >= 1 && batch <= ctx->max_batch && rows <= ctx->max_rows && cols <= ctx->max_cols;
 }
 
 int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p)
 {
     if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1) return DCMT_E_INVALID;
-    if (batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
     if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN) return DCMT_E_INVALID;
     if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;
@@ -190,9 +178,9 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
     return DCMT_OK;
 }
 
-// Scratch only one of the paths uses is allocated by the first call that takes that path (never again afterwards; run_chain calls
-// these before it enqueues anything): the column
-// statistics of the staged tile kernels, the 16-bit plane of k_pre_p<Q16OUT> -> k_fp_q.
+// Scratch only one of the paths uses is allocated by the first call whose plan names it (never again afterwards) -- before anything
+// of the call is enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.  The column
+// statistics of the staged tile kernels, the 16-bit plane of k_pre_p<Q16OUT> -> k_fp_q, the label stage's bounding boxes.
 int ensure_colstat(dcmt_ctx* ctx)
 {
     if (!ctx->colstat)
@@ -204,13 +192,32 @@ int ensure_x6q(dcmt_ctx* ctx)
     if (!ctx->x6q) DCMT_HIP(ctx, hipMalloc((void**)&ctx->x6q, sizeof(unsigned short) * ctx->frame_elems * (size_t)ctx->max_batch + 16));
     return DCMT_OK;
 }
+int ensure_bbox(dcmt_ctx* ctx, size_t need, hipStream_t st)     // per (frame, label) bounding boxes, grown on demand
+{
+    if (need <= ctx->bb_ints) return DCMT_OK;
+    (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max);
+    ctx->bb_min = ctx->bb_max = nullptr; ctx->bb_ints = 0;
+    DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_min, sizeof(int) * need));
+    DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_max, sizeof(int) * need));
+    ctx->bb_ints = need;
+    // "no box" everywhere, once: the label stage's waves put every entry they have read back into this state (a fill in front
+    // of every call is two dependent operations with a bubble behind the previous call's last kernel each)
+    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
+    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
+    return DCMT_OK;
+}
 
-// grid of the kernels that deal (frame, strip) pairs to waves in one flat sequence (wave_strip in dcmt_kernels_fused.h)
 constexpr unsigned kQ16Flags = 64;
 
-dim3 wave_grid(int strips, int batch, int xcd_map)
+// The stateful part of the 16-bit dispatch, once per streaming call: a frame that is no multiple of 1/256 m costs the attempt AND the
+// f32 rerun; once a call has raised the flag (seen here at the start of a later call, without synchronising) the next 63 calls go
+// straight to the f32 kernels -- counted whether or not they would otherwise have made the attempt.
+bool q16_allowed_now(dcmt_ctx* ctx)
 {
-    return dim3(xcd_map ? 8 * (((batch / 8) * strips + 3) / 4) : (batch * strips + 3) / 4);
+    if (!ctx->knobs.fp_q16) return false;
+    if (*(volatile int*)ctx->q16_seen) { *(volatile int*)ctx->q16_seen = 0; ctx->q16_skip = 63; }
+    if (ctx->q16_skip > 0) { --ctx->q16_skip; return false; }
+    return true;
 }
 
 dim3 tile_grid(int rows, int cols, int batch) { return dim3((cols + TW - 1) / TW, (rows + TH - 1) / TH, batch); }
@@ -232,6 +239,31 @@ void with_k0(int k0kind, F f)
     if (k0kind == K0_AS_COMPILED) f(std::integral_constant<int, K0_AS_COMPILED>{});
     else f(std::integral_constant<int, K0_DIAMOND>{});
 }
+
+// likewise f(flag) with a bool, f(tile height) with the staged kernels' FTH_FEW or TH
+template <typename F>
+void with_bool(bool b, F f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename F>
+void with_tile_h(bool few, F f)
+{
+    if (few) f(std::integral_constant<int, FTH_FEW>{});
+    else f(std::integral_constant<int, TH>{});
+}
+
+// What a completion call is given: device pointers (src or src16; labels only where they are used) and the batch's shape
+struct Frames {
+    const float* src;
+    const uint16_t* src16;
+    float in_scale;
+    const int32_t* labels;
+    int n_labels;
+    float* dst;
+    int rows, cols, batch;
+};
 
 // The hole-closure loop shared by both paths.  `launch_app(i)` enqueues application i
 // (reads pp[(i-1)&1], writes pp[i&1], skips frames without holes).  Returns the number of
@@ -271,78 +303,51 @@ int fill_loop(dcmt_ctx* ctx, int batch, const dcmt_params* p, hipStream_t st, bo
     return rc;
 }
 
-// Fast path.  Whole chain: k_pre_s -> k_fp_s -> k_tail, one workgroup per frame that returns at once for every frame k_fp_s
-// finished and runs the hole-closure loop for the others (the host entry points, which read the counters back between
-// applications, launch k_fill_s redo, k_fill_s loop applications, k_post_s only_if_holes instead).  stop_after probes:
-// k_pre_s -> k_fill_s (-> loop) -> k_post_s / copy.  Preconditions are checked by the caller.
-// d_x4 != nullptr: X4 is already there (LC fast path): k_pre_s only runs H5 + H6 on it.
-// src16 != nullptr: uint16 ingest fused into k_pre_s.  cf: N1's (a, b) per frame, applied while k_pre_s loads.
-int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, int rows, int cols, int batch,
-                    const dcmt_params* p, hipStream_t st, bool sync_loop, const float* d_x4 = nullptr,
-                    const uint16_t* src16 = nullptr, float in_scale = 1.0f, const float* cf = nullptr)
+// Every completion call starts here, once its scratch is there: the state dcmt_last_* report on, and dcmt_last_path
+void begin_call(dcmt_ctx* ctx, hipStream_t st, int batch, const char* path)
 {
-    const int stop = p->stop_after;
     ctx->last_stream = st;
     ctx->last_batch = batch;
     ctx->last_apps_launched = 0;
     ctx->last_has_loop = 0;
+    std::memcpy(ctx->last_path, path, sizeof ctx->last_path);
+}
+
+// The streaming route of a plan.  Whole chain: k_pre_s -> k_fp_s -> k_tail, one workgroup per frame that returns at once for every
+// frame k_fp_s finished and runs the hole-closure loop for the others (the host entry points, which read the counters back between
+// applications, launch k_fill_s redo, k_fill_s loop applications, k_post_s only_if_holes instead).  stop_after probes:
+// k_pre_s -> k_fill_s (-> loop) -> k_post_s / copy.  fr.labels: X4 is already in pp[0] (LC fast path): k_pre only runs H5 + H6 on it.
+// fr.src16: uint16 ingest fused into k_pre.  pl.norm: N1's (a, b) per frame, applied while k_pre loads.  p: the call's parameters
+// with the effective blur.
+int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, hipStream_t st, bool sync_loop)
+{
+    const int stop = p->stop_after, rows = fr.rows, cols = fr.cols, batch = fr.batch, xm = pl.xcd_map, bands = pl.bands;
+    const bool q16 = pl.q16, filled = pl.filled, bl = p->blur == DCMT_BLUR_GAUSSIAN;
+    float* dst = fr.dst;
     // (the hole counters are cleared by the first kernel of the chain: clear_frame_counters)
     auto stamp = [&](int i) { if (ctx->timing && ctx->tev[i]) (void)hipEventRecord(ctx->tev[i], st); };
     stamp(1);
     const size_t fe = (size_t)rows * cols;
-    const bool bl = p->blur == DCMT_BLUR_GAUSSIAN;
-    const int xm = (ctx->xcd_map && batch % 8 == 0) ? 1 : 0;
     const dim3 b256(256);
-    const float* src = d_x4 ? d_x4 : d_src;
+    const float* d_x4 = fr.labels ? ctx->pp[0] : nullptr;
+    const uint16_t* src16 = fr.src16;
+    const float* cf = pl.norm && !d_x4 ? ctx->norm_coef : nullptr;     // (nullptr with d_x4 and with src16)
     float* x6 = ctx->x5;
     float* pp0 = ctx->pp[0];
     float* pp1 = ctx->pp[1];
     int* cnt = ctx->counters;
-    // 16-bit X6: a frame that is no multiple of 1/256 m costs the attempt AND the f32 rerun; once a call has raised the flag (seen
-    // here at the start of a later call, without synchronising) the next 63 calls go straight to the f32 kernels.  (The uint16 entry
-    // point's depths are multiples of 1/256 m by construction, but a payload beyond 30719 -- 119.996 m -- has no code either.)
-    bool q16_try = ctx->fp_q16 != 0;
-    if (q16_try) {
-        if (*(volatile int*)ctx->q16_seen) { *(volatile int*)ctx->q16_seen = 0; ctx->q16_skip = 63; }
-        if (ctx->q16_skip > 0) { --ctx->q16_skip; q16_try = false; }
-    }
-    // table mode: only the k_fp_s path reads X6 through the per-column table (the probes and the unfused kernels get a fully written X6)
-    int* tc = (stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table) ? ctx->tb : nullptr;
-    const void* in = src16 ? (const void*)src16 : (const void*)src;    // (cf is nullptr with d_x4 and with src16)
-    // Frames that overlap dst (in place, or shifted; never with d_x4, which is scratch).  The f32 kernels read them only in k_pre, into
-    // scratch, and write dst last.  Two things would break that: the stop_after = EXTEND probe, where k_pre writes dst while other
-    // waves still read their strips and halo columns from the frames -- it goes to X6 (this call's k_pre output anyway) and one copy
-    // moves it to dst; and the 16-bit attempt, whose k_fp_q writes dst BEFORE the gated f32 rerun reads the frames again -- not taken.
-    const bool src_dst_overlap = ranges_overlap(in, (size_t)batch * fe * (src16 ? 2 : 4), dst, (size_t)batch * fe * sizeof(float));
-    float* o6 = stop == DCMT_STAGE_EXTEND && !src_dst_overlap ? dst : x6;
-    // LDS-DMA rows need 16-byte aligned sources: cols % 4 == 0 and a 16-byte aligned base
-    const bool wide = ctx->wide && cols % 4 == 0 && ((uintptr_t)src % 16 == 0) && !src16;
-    // two columns per lane (k_pre_p) wherever a lane's 8-byte accesses are aligned: even width, 8-byte aligned frames
-    const bool pair = ctx->pair && cols % 2 == 0 && cols >= 8 && ((uintptr_t)(src16 ? (const void*)src16 : (const void*)src) % (src16 ? 4 : 8) == 0) &&
-                      ((uintptr_t)o6 % 8 == 0);
-    // row bands: full-height strips of a small batch leave most wave slots empty; bands need the (ti, bi) table (one slot per band)
-    int bands = 1;                          // row bands of k_pre_p = table slots per frame
-    if (pair && tc) {
-        const int pstr = (cols + PreP<K0_AS_COMPILED, false>::VW - 1) / PreP<K0_AS_COMPILED, false>::VW;
-        bands = ctx->bands > 0 ? ctx->bands : ((long long)batch * pstr >= 2560 ? 1 : (int)((2560 + (long long)batch * pstr - 1) / ((long long)batch * pstr)));
-        if (bands > rows / 32) bands = rows / 32 > 0 ? rows / 32 : 1;
-        if (bands > kMaxBands) bands = kMaxBands;
-    }
-    // 16-bit X6 (k_pre_p<Q16OUT> -> k_fp_q): the whole chain in table mode, two columns per lane, the reference's constants, no
-    // normalisation in front (normalised depths are no multiples of 1/256), no overlap of the frames with dst (above)
-    const bool q16 = q16_try && (long long)batch * ((cols + FpQ::VW - 1) / FpQ::VW) >= ctx->q16_min_waves && pair && tc && !cf &&
-                     Q16::params_ok(p->max_depth, p->valid_thresh) && (uintptr_t)dst % 8 == 0 && (!src16 || in_scale == 0.00390625f) && !src_dst_overlap;
-    if (q16) { const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc; }
+    int* tc = pl.table ? ctx->tb : nullptr;
+    const void* in = src16 ? (const void*)src16 : d_x4 ? (const void*)d_x4 : (const void*)fr.src;
+    float* o6 = stop == DCMT_STAGE_EXTEND && pl.out == plan::Out::DST ? dst : x6;
 
-    const float scale = src16 ? in_scale : 1.0f;
+    const float scale = src16 ? fr.in_scale : 1.0f;
     // k_pre_s (one column per lane) into o6
     auto pre_s = [&](auto kind, auto wide_) {
         constexpr int KIND = decltype(kind)::value;
         constexpr bool WIDE = decltype(wide_)::value;
         auto* k = d_x4 ? k_pre_s<KIND, WIDE, true, false> : src16 ? k_pre_s<KIND, false, false, true> :
                   cf ? k_pre_s<KIND, WIDE, false, false, true> : k_pre_s<KIND, WIDE, false, false>;
-        const int strips = (cols + PreS<KIND, WIDE>::VW - 1) / PreS<KIND, WIDE>::VW;
-        hipLaunchKernelGGL(k, wave_grid(strips, batch, xm), b256, 0, st, in, o6, rows, cols, strips, batch, xm, p->max_depth, p->valid_thresh,
+        hipLaunchKernelGGL(k, dim3(pl.pre_grid), b256, 0, st, in, o6, rows, cols, pl.pre_strips, batch, xm, p->max_depth, p->valid_thresh,
                            scale, cf, tc, cnt);
     };
     // k_pre_p (two columns per lane) into o: X6 in f32, or as 16-bit codes (QOUT) that raise *qbad where a value has none and clear
@@ -352,9 +357,7 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
         constexpr bool QOUT = decltype(qout)::value;
         auto* k = d_x4 ? k_pre_p<KIND, true, false, false, QOUT> : src16 ? k_pre_p<KIND, false, true, false, QOUT> :
                   cf ? k_pre_p<KIND, false, false, true> : k_pre_p<KIND, false, false, false, QOUT>;
-        const int vw = d_x4 ? PreP<KIND, true>::VW : PreP<KIND, false>::VW;
-        const int strips = (cols + vw - 1) / vw;
-        hipLaunchKernelGGL(k, wave_grid(strips * bands, batch, xm), b256, 0, st, in, o, rows, cols, strips, bands, batch, xm, p->max_depth,
+        hipLaunchKernelGGL(k, dim3(pl.pre_grid), b256, 0, st, in, o, rows, cols, pl.pre_strips, bands, batch, xm, p->max_depth,
                            p->valid_thresh, scale, cf, tc, cnt, qbad, gate, ctx->q16_seen_dev, qclr);
     };
     int* qbad = ctx->q16_bad;               // the flag of this call's 16-bit attempt
@@ -363,27 +366,21 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
         qbad = ctx->q16_bad + ctx->q16_attempts % kQ16Flags;
         int* qnext = ctx->q16_bad + (ctx->q16_attempts + 1) % kQ16Flags;
         ++ctx->q16_attempts;
-        with_k0(k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q), qbad, nullptr, qnext); });
-    } else if (pair) {
-        with_k0(k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, o6, nullptr, nullptr, nullptr); });
+        with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q), qbad, nullptr, qnext); });
+    } else if (pl.pair) {
+        with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, o6, nullptr, nullptr, nullptr); });
     } else {
-        with_k0(k0kind, [&](auto kind) { if (wide) pre_s(kind, std::true_type{}); else pre_s(kind, std::false_type{}); });
+        with_k0(pl.k0kind, [&](auto kind) { if (pl.wide) pre_s(kind, std::true_type{}); else pre_s(kind, std::false_type{}); });
     }
     DCMT_HIP(ctx, hipGetLastError());
     stamp(2);
-    std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s%s%s", d_x4 ? "k_label_bbox + k_label_stage + " : "",
-                  q16 ? (src16 ? "k_pre_p<U16,Q16OUT>" : "k_pre_p<Q16OUT>") : pair ? (d_x4 ? "k_pre_p<START4>" : src16 ? "k_pre_p<U16>" : cf ? "k_pre_p<NORM>" : "k_pre_p") : "k_pre_s",
-                  bands > 1 ? " (row bands)" : "");
     if (stop == DCMT_STAGE_EXTEND) {
-        if (o6 != dst) {
-            DCMT_HIP(ctx, hipMemcpyAsync(dst, o6, sizeof(float) * (size_t)batch * fe, hipMemcpyDeviceToDevice, st));
-            path_append(ctx, kPathCopy);
-        }
+        if (o6 != dst) DCMT_HIP(ctx, hipMemcpyAsync(dst, o6, sizeof(float) * (size_t)batch * fe, hipMemcpyDeviceToDevice, st));
         return DCMT_OK;
     }
 
-    const int fstrips = (cols + FillS::VW - 1) / FillS::VW;
-    const dim3 fgrid(((fstrips + 3) / 4) * batch);
+    const int fstrips = pl.fill_strips, pstrips = pl.post_strips;
+    const dim3 fgrid(pl.fill_grid);
     // the hole-closure loop's applications 1, 2, ... (pp[0] <-> pp[1])
     auto fill_apps = [&](int* apps) {
         return fill_loop(ctx, batch, p, st, sync_loop, [&](int i) {
@@ -391,48 +388,29 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
                                fstrips, batch, xm, p->valid_thresh, i, 0, (const int*)nullptr, 1, (const unsigned short*)nullptr, (const int*)nullptr);
         }, apps);
     };
-    if (stop == DCMT_STAGE_FINAL && ctx->fuse_fp) {
-        // one kernel for H7..H11; frames it leaves with holes are redone by the unfused kernels below
-        const int pstrips = (cols + PostS::VW - 1) / PostS::VW;
-        // k_fp_s deals (frame, strip) pairs to waves in one flat sequence (per XCD with the XCD map): no half-empty workgroups
-        // row bands for k_fp_s: a batch whose strips are fewer than two waves per SIMD runs every strip as fb_s bands, about one
-        // round of three waves per SIMD in all (a band pays 19 + 19 rows of halo and 19 steps of pipeline: only worth it while the
-        // GPU is not full -- from ~100 frames of 1216 columns on there is one band)
-        int fb_s = 1;
-        if (tc) {
-            const long long w1 = (long long)batch * pstrips;
-            fb_s = ctx->fbands > 0 ? ctx->fbands : (w1 >= 2048 ? 1 : (int)((3072 + w1 / 2) / w1));
-            if (fb_s > rows / 32) fb_s = rows / 32 > 0 ? rows / 32 : 1;
-            if (fb_s < 1) fb_s = 1;
-        }
-        // frames this kernel leaves with holes are recomputed by the redo chain below whenever that chain is enqueued (always on the host
-        // entry points, with spec_fill_iters >= 1 on the device ones): then the kernel may leave out the select that only such frames need
-        const bool filled = bl && ctx->assume_filled && (sync_loop || (p->spec_fill_iters >= 1 && p->max_fill_iters >= 1));
-        const int n_redo = sync_loop ? p->max_fill_iters : (p->spec_fill_iters < p->max_fill_iters ? p->spec_fill_iters : p->max_fill_iters);
-        // device entry points: everything behind k_fp_* is k_tail (dcmt_kernels_tail.h), also the second half of the f32 rerun behind
-        // a 16-bit attempt; the host entry points (and spec_fill_iters = 0, where nothing follows) keep k_fp_s as a launch of its own
-        const bool tail = !sync_loop && n_redo > 0;
+    if (pl.fuse_fp) {
+        // one kernel for H7..H11 (k_fp_s deals (frame, strip, band) units to waves in one flat sequence, per XCD with the XCD map: no
+        // half-empty workgroups); frames it leaves with holes are redone by the unfused kernels below
+        const int n_redo = pl.n_redo;
         if (q16) {
             auto* fpq = filled ? k_fp_q<true, true> : bl ? k_fp_q<true, false> : k_fp_q<false, false>;
-            const int qstrips = (cols + FpQ::VW - 1) / FpQ::VW;
-            hipLaunchKernelGGL(fpq, wave_grid(qstrips, batch, xm), b256, 0, st, (const void*)ctx->x6q, dst, cnt, rows, cols, qstrips, batch, xm,
+            hipLaunchKernelGGL(fpq, dim3(pl.fp_q_grid), b256, 0, st, (const void*)ctx->x6q, dst, cnt, rows, cols, pl.q_strips, batch, xm,
                                p->max_depth, p->valid_thresh, (const int*)tc, bands);
             // frames that are no multiples of 1/256 m: both f32 kernels again, gated on the flag the attempt raised (k_pre_p returns at once
             // otherwise; k_fp_s is k_tail's first phase, or a gated launch where no k_tail follows)
             // (the uint16 entry point too: a payload beyond 30719 = 119.996 m has no code)
-            with_k0(k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, x6, nullptr, qbad, nullptr); });
+            with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, x6, nullptr, qbad, nullptr); });
         }
-        if (!q16 || !tail) {
+        if (pl.fp_s_launch) {
             auto* fps = filled ? k_fp_s<true, true> : bl ? k_fp_s<true> : k_fp_s<false>;
-            hipLaunchKernelGGL(fps, wave_grid(pstrips * fb_s, batch, xm), b256, 0, st, x6, dst, cnt, rows, cols, pstrips, batch, xm, p->max_depth,
-                               p->valid_thresh, (const int*)tc, bands, q16 ? (const int*)qbad : (const int*)nullptr, fb_s);
+            hipLaunchKernelGGL(fps, dim3(pl.fp_s_grid), b256, 0, st, x6, dst, cnt, rows, cols, pstrips, batch, xm, p->max_depth,
+                               p->valid_thresh, (const int*)tc, bands, q16 ? (const int*)qbad : (const int*)nullptr, pl.fb_s);
         }
         DCMT_HIP(ctx, hipGetLastError());
         stamp(3);
-        path_append(ctx, q16 ? " + k_fp_q" : (fb_s > 1 ? " + k_fp_s (row bands)" : " + k_fp_s"));
         ctx->last_has_loop = 1;
         int rc = DCMT_OK, apps = 0;
-        if (tail) {
+        if (pl.tail) {
             auto* kt = filled ? k_tail<true, true> : bl ? k_tail<true, false> : k_tail<false, false>;
             hipLaunchKernelGGL(kt, dim3(batch), b256, 0, st, (const float*)x6, q16 ? (const unsigned short*)ctx->x6q : (const unsigned short*)nullptr,
                                q16 ? (const int*)qbad : (const int*)nullptr, pp0, pp1, dst, cnt, n_redo, rows, cols, fstrips, pstrips, p->max_depth,
@@ -451,7 +429,7 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
                                q16 ? (const unsigned short*)ctx->x6q : (const unsigned short*)nullptr, (const int*)qbad);
             rc = fill_apps(&apps);
             if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
-            hipLaunchKernelGGL((bl ? k_post_s<11, true> : k_post_s<11, false>), dim3(((pstrips + 3) / 4) * batch), b256, 0, st, pp0, pp1, dst, cnt, apps,
+            hipLaunchKernelGGL((bl ? k_post_s<11, true> : k_post_s<11, false>), dim3(pl.post_grid), b256, 0, st, pp0, pp1, dst, cnt, apps,
                                rows, cols, pstrips, batch, xm, p->max_depth, p->valid_thresh, 1);
             DCMT_HIP(ctx, hipGetLastError());
         }
@@ -475,8 +453,7 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
     } else {
         auto* post = stop == DCMT_STAGE_MEDIAN5 ? k_post_s<9, false> : stop == DCMT_STAGE_BLUR ? (bl ? k_post_s<10, true> : k_post_s<10, false>) :
                      (bl ? k_post_s<11, true> : k_post_s<11, false>);
-        const int strips = (cols + PostS::VW - 1) / PostS::VW;
-        hipLaunchKernelGGL(post, dim3(((strips + 3) / 4) * batch), b256, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, strips, batch, xm,
+        hipLaunchKernelGGL(post, dim3(pl.post_grid), b256, 0, st, pp0, pp1, dst, cnt, apps, rows, cols, pstrips, batch, xm,
                            p->max_depth, p->valid_thresh, 0);
     }
     DCMT_HIP(ctx, hipGetLastError());
@@ -484,228 +461,152 @@ int run_chain_fused(dcmt_ctx* ctx, int k0kind, const float* d_src, float* dst, i
     return rc;
 }
 
-// Enqueues the cascade on `st`.  sync_loop: run the hole-closure loop exactly as the
-// reference would, reading the hole counters back between applications (host entry
-// points); otherwise enqueue p->spec_fill_iters applications speculatively.
-int run_chain(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_labels, int use_superpixel,
-              float* d_dst, int rows, int cols, int batch, const dcmt_params* p, bool force_gaussian,
-              hipStream_t st, bool sync_loop, const uint16_t* d_src16 = nullptr, float in_scale = 1.0f)
+// the scratch plane (or dst) a plan points the output of the kernel that reads the frames at
+float* out_plane(const dcmt_ctx* ctx, plan::Out o, float* dst) { return o == plan::Out::DST ? dst : o == plan::Out::X5 ? ctx->x5 : ctx->pp[0]; }
+
+// Plans the call (dcmt_plan.h), allocates what the plan names, then enqueues the cascade on `st`.  sync_loop: run the hole-closure
+// loop exactly as the reference would, reading the hole counters back between applications (host entry points); otherwise enqueue
+// p->spec_fill_iters applications speculatively.
+int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_gaussian, hipStream_t st, bool sync_loop)
 {
-    const dim3 grid = tile_grid(rows, cols, batch), block(kThreads);
-    const bool few = batch < 12;                    // measured up to 8 frames (tools/batch_sweep.py): +15 % at 3 and 6, +7 % at 8
-    const dim3 fgrid((cols + TW - 1) / TW, few ? (rows + FTH_FEW - 1) / FTH_FEW : (rows + TH - 1) / TH, batch);
-#define DCMT_FILL31(...) { if (few) hipLaunchKernelGGL((k_fill31_v1<FTH_FEW, TW>), fgrid, block, 0, st, __VA_ARGS__); \
-                           else hipLaunchKernelGGL((k_fill31_v1<TH, TW>), fgrid, block, 0, st, __VA_ARGS__); }
+    const int rows = fr.rows, cols = fr.cols, batch = fr.batch, stop = p->stop_after;
     const uint32_t kb = k0_bits(p->k0);
-    const int stop = p->stop_after;
     const int blur = force_gaussian ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
     ctx->tev_valid = 0;
-    // which kernels run.  The streaming kernels give one wave a whole column strip: a handful of frames cannot fill the GPU
-    // with them, there the staged tile kernels (hundreds of small workgroups per frame) win
-    const int kind = k0_preset(kb);
-    const bool labeled = d_labels && use_superpixel;
-    const bool big_enough = batch >= ctx->min_fused_batch || (p->flags & DCMT_FLAG_FORCE_FUSED);
-    const bool streaming = !(p->flags & DCMT_FLAG_FORCE_STAGED) && big_enough && kind >= 0 && rows >= 8 && cols >= 8;
-    const bool lc_fast = streaming && labeled && n_labels > 0 && (stop == DCMT_STAGE_FINAL || stop == DCMT_STAGE_CLOSE5);
-    const bool fused = streaming && !labeled && stop >= DCMT_STAGE_EXTEND;
-    // Scratch that only some paths use is allocated by the first call that takes such a path -- here, before anything of the call is
-    // enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.
-    if (!((p->flags & DCMT_FLAG_NORMALIZE) && stop == DCMT_STAGE_NORMALIZE)) {
-        if (lc_fast || fused) {
-            // (every call that may make a 16-bit attempt; run_chain_fused has the exact conditions)
-            if (ctx->fp_q16 && stop == DCMT_STAGE_FINAL && ctx->fuse_fp && ctx->top_table && ctx->pair && cols % 2 == 0 && !(p->flags & DCMT_FLAG_NORMALIZE) &&
-                (long long)batch * ((cols + FpQ::VW - 1) / FpQ::VW) >= ctx->q16_min_waves && Q16::params_ok(p->max_depth, p->valid_thresh)) {
-                const int erc = ensure_x6q(ctx); if (erc != DCMT_OK) return erc;
-            }
-        } else {
-            const int erc = ensure_colstat(ctx); if (erc != DCMT_OK) return erc;
-        }
-        if (lc_fast) {
-            // LC fast path: per (frame, label) bounding boxes
-            const size_t need = (size_t)batch * n_labels * 2;
-            if (need > ctx->bb_ints) {
-                (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max);
-                ctx->bb_min = ctx->bb_max = nullptr; ctx->bb_ints = 0;
-                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_min, sizeof(int) * need));
-                DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_max, sizeof(int) * need));
-                ctx->bb_ints = need;
-                // "no box" everywhere, once: the label stage's waves put every entry they have read back into this state (a fill in front
-                // of every call is two dependent operations with a bubble behind the previous call's last kernel each)
-                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
-                DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
-            }
-        }
-    }
+    if ((p->flags & DCMT_FLAG_NORMALIZE) && fr.src16) return DCMT_E_UNSUPPORTED;
+    plan::Call c;
+    c.rows = rows; c.cols = cols; c.batch = batch;
+    c.input = fr.labels ? plan::Input::LABELED : fr.src16 ? plan::Input::U16 : plan::Input::F32;
+    c.n_labels = fr.n_labels;
+    c.src = fr.src16 ? (uintptr_t)fr.src16 : (uintptr_t)fr.src; c.dst = (uintptr_t)fr.dst; c.labels = (uintptr_t)fr.labels;
+    c.in_scale = fr.in_scale;
+    c.max_depth = p->max_depth; c.valid_thresh = p->valid_thresh;
+    c.k0kind = k0_preset(kb);
+    c.gaussian = blur == DCMT_BLUR_GAUSSIAN;
+    c.max_fill_iters = p->max_fill_iters; c.spec_fill_iters = p->spec_fill_iters; c.stop_after = stop; c.flags = p->flags;
+    c.sync_loop = sync_loop;
+    c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && q16_allowed_now(ctx);
+    const plan::Plan pl = plan::plan_call(ctx->knobs, c);
+
+    int erc = DCMT_OK;
+    if (pl.needs_x6q && (erc = ensure_x6q(ctx)) != DCMT_OK) return erc;
+    if (pl.needs_colstat && (erc = ensure_colstat(ctx)) != DCMT_OK) return erc;
+    if (pl.needs_bbox && (erc = ensure_bbox(ctx, (size_t)batch * fr.n_labels * 2, st)) != DCMT_OK) return erc;
+    begin_call(ctx, st, batch, pl.path);
     if (ctx->timing && ctx->tev[0]) (void)hipEventRecord(ctx->tev[0], st);
-    // In place (or overlapping) calls: every kernel that writes d_dst must run behind the last one that reads the input frames.  Where
-    // the kernel that reads them would also write d_dst (the probes below, and stop_after = EXTEND in run_chain_fused), an overlapping
-    // call points its output at scratch the path does not use at that point and copies it to d_dst (kPathCopy in dcmt_last_path).
+
     const size_t n_px = (size_t)batch * rows * cols;
-    bool src_dst_overlap = d_src16 ? ranges_overlap(d_src16, n_px * sizeof(uint16_t), d_dst, n_px * sizeof(float))
-                                   : ranges_overlap(d_src, n_px * sizeof(float), d_dst, n_px * sizeof(float));
+    const float* d_src = fr.src;
+    float* d_dst = fr.dst;
+    float* out = out_plane(ctx, pl.out, d_dst);     // an overlapping call's probe: scratch, then one copy (the plan says why that plane is free)
     const float* coef = nullptr;
-    if (p->flags & DCMT_FLAG_NORMALIZE) {
+    if (pl.norm) {
         // N1: one read-only pass for the per-frame extrema, then (a, b) per frame; the first kernel of whichever
         // path runs below applies them while it loads
-        if (d_src16) return DCMT_E_UNSUPPORTED;
         const size_t fe = (size_t)rows * cols;
         // (norm_stats is all zero here: dcmt_create cleared it, k_norm_coef clears what it has read)
-        hipLaunchKernelGGL(k_minmax, dim3(kMinmaxUnits * batch), dim3(256), 0, st, d_src, ctx->norm_stats, fe, batch,
-                           (ctx->xcd_map && batch % 8 == 0) ? 1 : 0);
+        hipLaunchKernelGGL(k_minmax, dim3(kMinmaxUnits * batch), dim3(256), 0, st, d_src, ctx->norm_stats, fe, batch, pl.xcd_map);
         hipLaunchKernelGGL(k_norm_coef, dim3((batch + 63) / 64), dim3(64), 0, st, ctx->norm_stats, ctx->norm_coef, batch, p->norm_lo, p->norm_hi);
         DCMT_HIP(ctx, hipGetLastError());
         coef = ctx->norm_coef;
-        if (stop == DCMT_STAGE_NORMALIZE) {
-            // k_norm_write is a grid-stride pass: with a shifted overlap it would overwrite frames other threads have yet to read.
-            // Overlapping: into pp[0] (no other kernel of this call) and copied.
-            float* o = src_dst_overlap ? ctx->pp[0] : d_dst;
-            hipLaunchKernelGGL(k_norm_write, dim3(2048), dim3(256), 0, st, d_src, o, coef, fe, batch);
+        if (pl.route == plan::Route::NORMALIZE_ONLY) {
+            hipLaunchKernelGGL(k_norm_write, dim3(2048), dim3(256), 0, st, d_src, out, coef, fe, batch);
             DCMT_HIP(ctx, hipGetLastError());
-            if (o != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, o, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
-            std::snprintf(ctx->last_path, sizeof ctx->last_path, "k_minmax + k_norm_coef + k_norm_write%s", o != d_dst ? kPathCopy : "");
-            ctx->last_stream = st; ctx->last_batch = batch; ctx->last_apps_launched = 0; ctx->last_has_loop = 0;
+            if (out != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
             return DCMT_OK;
         }
     }
-    {
-        if (lc_fast) {
-            // LC fast path: bounding boxes -> one wave per label (masked H2..H4) -> X4 -> the img_completion kernels
-            // (dead before the redo chain writes pp[0]; x5 shares pp[1]).  The CLOSE5 probe is X4 itself, written straight to d_dst --
-            // unless d_dst overlaps d_src: the label stage's waves read d_src around their label's box (wide boxes in column chunks, a
-            // later chunk reading what an earlier one wrote) while others write X4, so X4 stays in pp[0] and is copied
-            float* x4 = stop == DCMT_STAGE_CLOSE5 && !src_dst_overlap ? d_dst : ctx->pp[0];
-            const dim3 bg((cols + 63) / 64, (rows + kBboxRows - 1) / kBboxRows, batch);
-            const size_t table = sizeof(int) * 4 * (size_t)n_labels;
-            if (table <= 48 * 1024 && !ctx->bbox_global)
-                hipLaunchKernelGGL(k_label_bbox<true>, bg, dim3(256), table, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
-                                   rows, cols, p->max_depth, p->valid_thresh, coef);
-            else
-                hipLaunchKernelGGL(k_label_bbox<false>, bg, dim3(256), 0, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
-                                   rows, cols, p->max_depth, p->valid_thresh, coef);
-            // two columns per lane (k_label_stage_p) where a lane's 8-byte accesses are aligned; G labels side by side per wave, from the
-            // mean label area (a grown box of w + 10 columns takes (w + 10) / 2 + 1 lanes; SLIC-like labels are a few columns wider
-            // than the square root of their area)
-            const bool lpair = ctx->pair && cols % 2 == 0 && cols >= 8 && (uintptr_t)d_src % 8 == 0 && (uintptr_t)d_labels % 8 == 0 && (uintptr_t)x4 % 8 == 0;
-            int G = 1;
-            {
-                const double w = std::sqrt((double)rows * cols / n_labels) + 4.0;
-                const int lanes = (int)((w + 10.0) / 2.0) + 1;
-                G = (64 + lanes / 4) / (lanes > 0 ? lanes : 1);        // as many as fit side by side, rounded up when they nearly do (the rest gets a pass of its own)
-                if (G < 1) G = 1;
-                if (G > kLabelGroupMax) G = kLabelGroupMax;
-                if (ctx->label_group >= 1 && ctx->label_group <= kLabelGroupMax) G = ctx->label_group;
-            }
-            const int lwaves = (n_labels + G - 1) / G;
-            const dim3 lgp((lwaves + 3) / 4, batch);
-#define DCMT_LSTAGEP(KIND, NORM) hipLaunchKernelGGL((k_label_stage_p<KIND, NORM>), lgp, dim3(256), 0, st, d_src, d_labels, n_labels, G, \
-                                                   ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef)
-            // labels of about 22 columns or less (the mean box of an even partition, with SLIC-like slack) can share a
-            // wave: one wave per label PAIR; few large labels: one wave per label (see k_label_stage_s)
-            const bool pairs = ctx->label_pairs >= 0 ? ctx->label_pairs != 0 : (double)rows * cols / n_labels <= 22.0 * 22.0;
-            const dim3 lg(pairs ? (n_labels + 7) / 8 : (n_labels + 3) / 4, batch);
-#define DCMT_LSTAGE(KIND, NORM) { if (pairs) hipLaunchKernelGGL((k_label_stage_s<KIND, NORM, true>), lg, dim3(256), 0, st, d_src, d_labels, n_labels, \
-                                                   ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef); \
-                                  else hipLaunchKernelGGL((k_label_stage_s<KIND, NORM, false>), lg, dim3(256), 0, st, d_src, d_labels, n_labels, \
-                                                   ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef); }
-            if (lpair) {
-                if (kind == K0_AS_COMPILED) { if (coef) DCMT_LSTAGEP(K0_AS_COMPILED, true); else DCMT_LSTAGEP(K0_AS_COMPILED, false); }
-                else { if (coef) DCMT_LSTAGEP(K0_DIAMOND, true); else DCMT_LSTAGEP(K0_DIAMOND, false); }
-            } else if (kind == K0_AS_COMPILED) { if (coef) DCMT_LSTAGE(K0_AS_COMPILED, true) else DCMT_LSTAGE(K0_AS_COMPILED, false) }
-            else { if (coef) DCMT_LSTAGE(K0_DIAMOND, true) else DCMT_LSTAGE(K0_DIAMOND, false) }
-#undef DCMT_LSTAGE
-#undef DCMT_LSTAGEP
-            DCMT_HIP(ctx, hipGetLastError());
-            if (stop == DCMT_STAGE_CLOSE5) {
-                if (x4 != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, x4, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
-                std::snprintf(ctx->last_path, sizeof ctx->last_path, "k_label_bbox + k_label_stage%s", x4 != d_dst ? kPathCopy : "");
-                ctx->last_stream = st; ctx->last_batch = batch; ctx->last_apps_launched = 0; ctx->last_has_loop = 0;
-                return DCMT_OK;
-            }
-            dcmt_params q = *p;
-            q.blur = blur;
-            return run_chain_fused(ctx, kind, d_src, d_dst, rows, cols, batch, &q, st, sync_loop, x4);
-        }
-        if (fused) {
-            dcmt_params q = *p;
-            q.blur = blur;
-            return run_chain_fused(ctx, kind, d_src, d_dst, rows, cols, batch, &q, st, sync_loop, nullptr, d_src16, in_scale, coef);
-        }
-        if (d_src16) {   // the staged kernels take f32: convert into scratch that nothing writes before they have read it
-            hipLaunchKernelGGL(k_u16_to_f32, dim3(1024), dim3(256), 0, st, d_src16, ctx->pp[0], n_px, in_scale);
-            d_src = ctx->pp[0];
-            src_dst_overlap = false;
+    if (pl.needs_bbox) {
+        // LC fast path: bounding boxes -> the label stage -> X4 (in pp[0]; the CLOSE5 probe: the plan's plane)
+        const int32_t* d_labels = fr.labels;
+        const int n_labels = fr.n_labels;
+        float* x4 = pl.route == plan::Route::LABEL_PROBE ? out : ctx->pp[0];
+        const dim3 bg((cols + 63) / 64, (rows + kBboxRows - 1) / kBboxRows, batch);
+        if (pl.bbox_lds)
+            hipLaunchKernelGGL(k_label_bbox<true>, bg, dim3(256), sizeof(int) * 4 * (size_t)n_labels, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
+                               rows, cols, p->max_depth, p->valid_thresh, coef);
+        else
+            hipLaunchKernelGGL(k_label_bbox<false>, bg, dim3(256), 0, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
+                               rows, cols, p->max_depth, p->valid_thresh, coef);
+        const dim3 lg(pl.label_grid_x, batch);
+        if (pl.lpair)
+            with_k0(pl.k0kind, [&](auto kind) { with_bool(coef != nullptr, [&](auto norm) {
+                hipLaunchKernelGGL((k_label_stage_p<decltype(kind)::value, decltype(norm)::value>), lg, dim3(256), 0, st, d_src, d_labels, n_labels,
+                                   pl.label_group, ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef);
+            }); });
+        else
+            with_k0(pl.k0kind, [&](auto kind) { with_bool(coef != nullptr, [&](auto norm) { with_bool(pl.label_pairs, [&](auto pairs) {
+                hipLaunchKernelGGL((k_label_stage_s<decltype(kind)::value, decltype(norm)::value, decltype(pairs)::value>), lg, dim3(256), 0, st, d_src,
+                                   d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef);
+            }); }); });
+        DCMT_HIP(ctx, hipGetLastError());
+        if (pl.route == plan::Route::LABEL_PROBE) {
+            if (x4 != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, x4, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
+            return DCMT_OK;
         }
     }
-    ctx->last_stream = st;
-    ctx->last_batch = batch;
-    ctx->last_apps_launched = 0;
-    ctx->last_has_loop = 0;
+    if (pl.route == plan::Route::STREAMING) {
+        dcmt_params q = *p;
+        q.blur = blur;
+        return launch_streaming(ctx, pl, fr, &q, st, sync_loop);
+    }
+    if (pl.u16_convert) {   // the staged kernels take f32: convert into scratch that nothing writes before they have read it
+        hipLaunchKernelGGL(k_u16_to_f32, dim3(1024), dim3(256), 0, st, fr.src16, ctx->pp[0], n_px, fr.in_scale);
+        d_src = ctx->pp[0];
+    }
 
-    std::snprintf(ctx->last_path, sizeof ctx->last_path, "%s + k_fill31_v1 + k_post_v1 (staged tile kernels)", (d_labels && use_superpixel) ? "k_pre_labeled_v1" : "k_pre_v1");
-    const int dump = stop <= DCMT_STAGE_CLOSE5 ? stop : 0;
-    // Up to FILL7 the kernel that reads the frames writes the probe itself: stages 2..4 as its dump, FILL7 as its X5 output.  Into a
-    // d_dst that overlaps d_src that would race with other workgroups still reading their halo from d_src, so the probe goes to
-    // scratch and is copied: X5 for FILL7 (its own plane), pp[0] for the dumps (first written by the 31x31 fill, which these probes do
-    // not run; the uint16 input converted into pp[0] never overlaps d_dst).
-    float* probe = !src_dst_overlap ? d_dst : stop == DCMT_STAGE_FILL7 ? ctx->x5 : ctx->pp[0];
-    float* x5_out = stop == DCMT_STAGE_FILL7 ? probe : ctx->x5;
-    float* dump_out = dump ? probe : d_dst;        // (not written without a dump stage)
-    int stat_rows = (int)grid.y;                   // tile rows of the kernel that writes the column statistics
-    if (d_labels && use_superpixel && few) {
-        hipLaunchKernelGGL((k_pre_labeled_v1<FTH_FEW, TW>), fgrid, block, 0, st, d_src, d_labels, n_labels,
-                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
-                           p->max_depth, p->valid_thresh, kb, dump, coef);
-        stat_rows = (int)fgrid.y;
-    } else if (d_labels && use_superpixel) {
-        hipLaunchKernelGGL((k_pre_labeled_v1<TH, TW>), grid, block, 0, st, d_src, d_labels, n_labels,
-                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
-                           p->max_depth, p->valid_thresh, kb, dump, coef);
-    } else if (few) {
-        hipLaunchKernelGGL((k_pre_v1<FTH_FEW, TW>), fgrid, block, 0, st, d_src,
-                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
-                           p->max_depth, p->valid_thresh, kb, dump, coef);
-        stat_rows = (int)fgrid.y;
-    } else {
-        hipLaunchKernelGGL((k_pre_v1<TH, TW>), grid, block, 0, st, d_src,
-                           x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
-                           p->max_depth, p->valid_thresh, kb, dump, coef);
-    }
+    // staged tile kernels.  Up to FILL7 the kernel that reads the frames writes the probe itself: stages 2..4 as its dump, FILL7 as
+    // its X5 output
+    const dim3 grid(pl.tiles_x, pl.tiles_y, batch), block(kThreads);
+    const int stat_rows = pl.tiles_y;              // tile rows of the kernel that writes the column statistics
+    float* x5_out = stop == DCMT_STAGE_FILL7 ? out : ctx->x5;
+    float* dump_out = pl.dump ? out : d_dst;       // (not written without a dump stage)
+    if (fr.labels)
+        with_tile_h(pl.few, [&](auto th) {
+            hipLaunchKernelGGL((k_pre_labeled_v1<decltype(th)::value, TW>), grid, block, 0, st, d_src, fr.labels, fr.n_labels, x5_out, ctx->colstat,
+                               ctx->counters, dump_out, rows, cols, p->max_depth, p->valid_thresh, kb, pl.dump, coef);
+        });
+    else
+        with_tile_h(pl.few, [&](auto th) {
+            hipLaunchKernelGGL((k_pre_v1<decltype(th)::value, TW>), grid, block, 0, st, d_src, x5_out, ctx->colstat, ctx->counters, dump_out, rows, cols,
+                               p->max_depth, p->valid_thresh, kb, pl.dump, coef);
+        });
     DCMT_HIP(ctx, hipGetLastError());
     if (stop <= DCMT_STAGE_FILL7) {
-        if (probe != d_dst) {
-            DCMT_HIP(ctx, hipMemcpyAsync(d_dst, probe, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
-            path_append(ctx, kPathCopy);
-        }
+        if (out != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
         return DCMT_OK;
     }
 
-    // H6 + H7
+    // H6 + H7 (extend_only: the EXTEND probe), and the loop's applications
+    auto fill31 = [&](const float* in, float* o, int app, int extend_only) {
+        with_tile_h(pl.few, [&](auto th) {
+            hipLaunchKernelGGL((k_fill31_v1<decltype(th)::value, TW>), grid, block, 0, st, in, o, ctx->colstat, ctx->counters, rows, cols, p->valid_thresh,
+                               app, extend_only, stat_rows);
+        });
+    };
     if (stop == DCMT_STAGE_EXTEND) {
-        DCMT_FILL31(ctx->x5, d_dst, ctx->colstat, ctx->counters, rows, cols, p->valid_thresh, 0, 1, stat_rows)
+        fill31(ctx->x5, d_dst, 0, 1);
         DCMT_HIP(ctx, hipGetLastError());
         return DCMT_OK;
     }
-    DCMT_FILL31(ctx->x5, stop == DCMT_STAGE_FILL31 ? d_dst : ctx->pp[0], ctx->colstat, ctx->counters, rows, cols, p->valid_thresh, 0, 0, stat_rows)
+    fill31(ctx->x5, stop == DCMT_STAGE_FILL31 ? d_dst : ctx->pp[0], 0, 0);
     DCMT_HIP(ctx, hipGetLastError());
     if (stop == DCMT_STAGE_FILL31) return DCMT_OK;
 
     // H8
     ctx->last_has_loop = 1;
     int apps = 0;
-    const int rc = fill_loop(ctx, batch, p, st, sync_loop, [&](int i) {
-        DCMT_FILL31(ctx->pp[(i - 1) & 1], ctx->pp[i & 1], ctx->colstat, ctx->counters, rows, cols, p->valid_thresh, i, 0, stat_rows)
-    }, &apps);
+    const int rc = fill_loop(ctx, batch, p, st, sync_loop, [&](int i) { fill31(ctx->pp[(i - 1) & 1], ctx->pp[i & 1], i, 0); }, &apps);
     if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
     ctx->last_apps_launched = apps;
 
     const int mode = stop <= DCMT_STAGE_FILLLOOP ? 8 : stop;
-    if (few) hipLaunchKernelGGL((k_post_v1<FTH_FEW, TW>), fgrid, block, 0, st, ctx->pp[0], ctx->pp[1], d_dst, ctx->counters, apps,
-                                rows, cols, p->max_depth, p->valid_thresh, blur, mode);
-    else hipLaunchKernelGGL((k_post_v1<TH, TW>), grid, block, 0, st, ctx->pp[0], ctx->pp[1], d_dst, ctx->counters, apps,
-                            rows, cols, p->max_depth, p->valid_thresh, blur, mode);
+    with_tile_h(pl.few, [&](auto th) {
+        hipLaunchKernelGGL((k_post_v1<decltype(th)::value, TW>), grid, block, 0, st, ctx->pp[0], ctx->pp[1], d_dst, ctx->counters, apps,
+                           rows, cols, p->max_depth, p->valid_thresh, blur, mode);
+    });
     DCMT_HIP(ctx, hipGetLastError());
     return rc;
-#undef DCMT_FILL31
 }
 
 int ensure_host_staging(dcmt_ctx* ctx, bool labels)
@@ -752,10 +653,10 @@ int host_call(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int
             DCMT_HIP(ctx, hipMemcpy2DAsync((char*)ctx->d_lab + f * frame_b, row_b, (const char*)labels + f * lfs, lrs, row_b,
                                            rows, hipMemcpyHostToDevice, st));
     }
-    if (ctx->poison)   // DCMT_POISON=1: stale output can never pass for fresh output (tests)
+    if (ctx->knobs.poison)   // DCMT_POISON=1: stale output can never pass for fresh output (tests)
         DCMT_HIP(ctx, hipMemsetAsync(ctx->d_out, 0xFF, frame_b * (size_t)batch, st));
-    const int chain_rc = run_chain(ctx, ctx->d_in, labels ? ctx->d_lab : nullptr, n_labels, use_superpixel, ctx->d_out,
-                                   rows, cols, batch, p, force_gaussian, st, true);
+    const Frames fr = {ctx->d_in, nullptr, 1.0f, labels && use_superpixel ? ctx->d_lab : nullptr, n_labels, ctx->d_out, rows, cols, batch};
+    const int chain_rc = run_chain(ctx, fr, p, force_gaussian, st, true);
     if (chain_rc != DCMT_OK && chain_rc != DCMT_E_NOT_CONVERGED) return chain_rc;
     for (int f = 0; f < batch; ++f) {
         if (drs == row_b)
@@ -774,7 +675,7 @@ int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_p
                  int mode, dcmt_eval_frame* d_out, hipStream_t st)
 {
     if (!ctx || !d_gt || !d_pred || !d_out) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (!finite_bits(thresh) || thresh < 0.0f || !finite_bits(gt_scale)) return DCMT_E_INVALID;
     if (mode != DCMT_EVAL_GT && mode != DCMT_EVAL_BOTH) return DCMT_E_INVALID;
     if ((uintptr_t)d_out % 8 != 0) return DCMT_E_INVALID;
@@ -796,7 +697,7 @@ int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_p
 int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batch, uint8_t* d_bgr, hipStream_t st)
 {
     if (!ctx || !d_src || !d_bgr) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if ((uintptr_t)d_src % 4 != 0) return DCMT_E_INVALID;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
     const uint32_t cap = (0x80000000u - kColorPxPerWg) / n;                 // frames per segment the 32-bit pixel run allows (>= 3)
@@ -835,7 +736,7 @@ int depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr
                        const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, hipStream_t st)
 {
     if (!ctx || !d_depth || !d_points || !d_offsets || !params) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
     if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
     if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
@@ -853,11 +754,11 @@ int depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr
 int gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, hipStream_t st)
 {
     if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
     const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
     const bool in_place = d_dst == d_src;
-    if (!in_place && ranges_overlap(d_src, bytes, d_dst, bytes)) return DCMT_E_INVALID;
+    if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
     float* out = in_place ? ctx->pp[0] : d_dst;
     launch_gauss5(d_src, out, rows, cols, batch, st);
     DCMT_HIP(ctx, hipGetLastError());
@@ -940,21 +841,7 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     ctx->device = device;
     ctx->max_rows = max_rows; ctx->max_cols = max_cols; ctx->max_batch = max_batch;
     ctx->frame_elems = (size_t)max_rows * max_cols;
-    { const char* e = std::getenv("DCMT_POISON"); ctx->poison = e && e[0] == '1'; }
-    { const char* e = std::getenv("DCMT_XCD_MAP"); if (e) ctx->xcd_map = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_WIDE"); if (e) ctx->wide = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_FUSE_FP"); if (e) ctx->fuse_fp = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_FP_Q16"); if (e) ctx->fp_q16 = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_Q16_MIN_WAVES"); if (e) ctx->q16_min_waves = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_ASSUME_FILLED"); if (e) ctx->assume_filled = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_TOP_TABLE"); if (e) ctx->top_table = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_PAIR"); if (e) ctx->pair = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_BANDS"); if (e) ctx->bands = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_FBANDS"); if (e) ctx->fbands = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_MIN_FUSED_BATCH"); if (e) ctx->min_fused_batch = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_LABEL_PAIRS"); if (e) ctx->label_pairs = std::atoi(e); }
-    { const char* e = std::getenv("DCMT_LABEL_GROUP"); if (e) ctx->label_group = std::atoi(e); }
-    ctx->bbox_global = std::getenv("DCMT_BBOX_GLOBAL") != nullptr;
+    ctx->knobs = plan::knobs_from_env();
     DeviceGuard dev_guard_(ctx);                    // allocate on the context's device, leave the caller's current device as it was
     auto fail = [&](int rc) { dcmt_destroy(ctx); return rc; };
     if (dev_guard_.rc != DCMT_OK) return fail(dev_guard_.rc);
@@ -972,8 +859,8 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     *ctx->q16_seen = 0;
     if (hipHostGetDevicePointer((void**)&ctx->q16_seen_dev, ctx->q16_seen, 0) != hipSuccess) return fail(DCMT_E_HIP);
     // (first, last) table: one slot per frame and row band.  Bands are only chosen while frames x strips x bands stays near one
-    // round of waves (run_chain_fused), so frames x bands <= max_batch + 2560; an explicit DCMT_BANDS may go up to kMaxBands each.
-    const size_t tb_slots = ctx->bands > 0 ? (size_t)max_batch * kMaxBands : std::min<size_t>((size_t)max_batch * kMaxBands, (size_t)max_batch + 2560);
+    // round of waves (plan_call), so frames x bands <= max_batch + kPreBandWaves; an explicit DCMT_BANDS may go up to kMaxBands each.
+    const size_t tb_slots = ctx->knobs.bands > 0 ? (size_t)max_batch * kMaxBands : std::min<size_t>((size_t)max_batch * kMaxBands, (size_t)max_batch + plan::kPreBandWaves);
     if (hipMalloc((void**)&ctx->tb, sizeof(int) * 2 * (size_t)max_cols * tb_slots) != hipSuccess) return fail(DCMT_E_NOMEM);
     if (hipMalloc((void**)&ctx->norm_stats, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
     if (hipMemset(ctx->norm_stats, 0, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_HIP);
@@ -1029,7 +916,7 @@ int dcmt_complete_f32_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int r
     DCMT_ON_DEVICE(ctx);
     int rc = check_params(ctx, d_src, d_dst, rows, cols, batch, params);
     if (rc != DCMT_OK) return rc;
-    return run_chain(ctx, d_src, nullptr, 0, 0, d_dst, rows, cols, batch, params, false, (hipStream_t)stream, false);
+    return run_chain(ctx, Frames{d_src, nullptr, 1.0f, nullptr, 0, d_dst, rows, cols, batch}, params, false, (hipStream_t)stream, false);
 }
 
 int dcmt_complete_u16_dev(dcmt_ctx* ctx, const uint16_t* d_src, float scale, float* d_dst, int rows, int cols, int batch,
@@ -1038,7 +925,7 @@ int dcmt_complete_u16_dev(dcmt_ctx* ctx, const uint16_t* d_src, float scale, flo
     DCMT_ON_DEVICE(ctx);
     int rc = check_params(ctx, d_src, d_dst, rows, cols, batch, params);
     if (rc != DCMT_OK) return rc;
-    return run_chain(ctx, nullptr, nullptr, 0, 0, d_dst, rows, cols, batch, params, false, (hipStream_t)stream, false, d_src, scale);
+    return run_chain(ctx, Frames{nullptr, d_src, scale, nullptr, 0, d_dst, rows, cols, batch}, params, false, (hipStream_t)stream, false);
 }
 
 int dcmt_complete_labeled_f32_dev(dcmt_ctx* ctx, const float* d_src, const int32_t* d_labels, int n_labels, float* d_dst,
@@ -1048,7 +935,7 @@ int dcmt_complete_labeled_f32_dev(dcmt_ctx* ctx, const float* d_src, const int32
     int rc = check_params(ctx, d_src, d_dst, rows, cols, batch, params);
     if (rc != DCMT_OK) return rc;
     if (!d_labels) return DCMT_E_INVALID;
-    return run_chain(ctx, d_src, d_labels, n_labels, use_superpixel, d_dst, rows, cols, batch, params, true,
+    return run_chain(ctx, Frames{d_src, nullptr, 1.0f, use_superpixel ? d_labels : nullptr, n_labels, d_dst, rows, cols, batch}, params, true,
                      (hipStream_t)stream, false);
 }
 
@@ -1058,7 +945,7 @@ int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t*
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !d_offsets || !T || !P || !d_sparse || n_points < 0 || (n_points > 0 && !d_points)) return DCMT_E_INVALID;
     if ((uintptr_t)d_points % 16 != 0) return DCMT_E_INVALID;           // the 16-byte point records are read whole
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     ProjMats M;
     std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
@@ -1110,7 +997,7 @@ int dcmt_stereo_refine_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !d_depth || !d_left || !d_right || !d_refined || !params) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (params->iterations > 1000) return DCMT_E_INVALID;
     StereoP P{params->baseline, params->focal, params->damp, params->max_depth, params->iterations < 0 ? 4 : params->iterations};
     if (rows > 65535 || batch > 65535) return DCMT_E_INVALID;                  // grid dimensions y, z
@@ -1190,7 +1077,7 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !d_lab || !d_labels) return DCMT_E_INVALID;
-    if (rows < 1 || cols < 1 || batch < 1 || batch > ctx->max_batch || rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (step < 6 || nc < 1) return DCMT_E_INVALID;
     const int n = dcmt_slic_num_centers(rows, cols, step);
     hipStream_t st = (hipStream_t)stream;

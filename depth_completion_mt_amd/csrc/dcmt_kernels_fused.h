@@ -95,7 +95,7 @@ struct Q16 {
     static constexpr unsigned HOLE_MAX_HI = (HOLE_MAX << 16) | 0xffffu;   // the same test on the high half of a packed pair
     __device__ static __forceinline__ unsigned code(float x) { return (unsigned)((int)__fmul_rn(x, 256.0f) + OFFSET); }
     __device__ static __forceinline__ float value(unsigned c) { return __builtin_fmaf((float)c, 0.00390625f, -23.99609375f); }   // (c - 6143) / 256, exact
-    __host__ __device__ static bool params_ok(float max_depth, float thr) { return max_depth == 100.0f && thr == 0.1f; }
+    __host__ __device__ static constexpr bool params_ok(float max_depth, float thr) { return max_depth == 100.0f && thr == 0.1f; }
 };
 
 __device__ __forceinline__ int wave_max_i(int v)
