@@ -27,7 +27,7 @@
 // Lane layout: a wave owns 128 columns, lane l the columns c0 + 2l ("E", low half) and c0 + 2l + 1 ("O", high half), 120 of them output
 // (2 + 2 per side go to the median and the Gaussian).  The 15 + 15 halo columns of the 31-wide maximum ride in a second register B, one
 // column per lane, unpacked: even columns of the right halo in lanes 0..7, odd ones in 8..15, even columns of the left halo in lanes
-// 56..63, odd ones in 48..55; lanes 16..47 are dead.  137..144 VGPRs: 3 waves per SIMD.
+// 56..63, odd ones in 48..55; lanes 16..47 are dead.  144..152 VGPRs: 3 waves per SIMD.
 // Fill: the vertical 31-maximum runs packed; the horizontal one, on rows that have a hole, works on the unpacked halves (unsigned
 // integers: 0 is the neutral element).  tests/test_lane_schemes.py restates this index arithmetic in numpy and checks it lane by lane
 // against the definition.  m = max(E, O) per lane; PX / SX = EXCLUSIVE prefix / suffix maxima of m inside each 16-lane DPP row (the
@@ -224,8 +224,13 @@ struct PostPipeP {
         for (int q = 0; q < 8; ++q) { G1[q] = {0.f, 0.f}; MR[q] = {0.f, 0.f}; }
     }
 
+    // MODE: what the caller knows about the step at compile time.  BORDER: nothing -- every row-range test runs.  INNER: the output
+    // row u - 6 lies in [2, rows - 3] -- no row test, the Gaussian's plain rows.  (edge_strip stays a wave-uniform branch in both:
+    // a second instantiation of the interior body for edge strips costs 70 VGPRs, k_fp_q's main loop has the figures.)
+    enum { BORDER = 0, INNER = 1 };
+
     // everything behind the median of image row u - 4 (me, mo = its two columns) in f32: H10, H11, the store of output row u - 6
-    template <int PP>
+    template <int PP, int MODE = BORDER>
     __device__ __forceinline__ void after_median(float me, float mo, int u)
     {
         MR[(PP + 4) & 7] = {me, mo};
@@ -242,7 +247,7 @@ struct PostPipeP {
         }
         // ---- vertical pass + select + invert for output row o = u - 6
         const int o = u - 6;
-        if ((unsigned)o < (unsigned)rows) {
+        if (MODE != BORDER || (unsigned)o < (unsigned)rows) {
             const F2 mo_ = MR[(PP + 2) & 7];
             auto finish = [&](F2 u1, F2 u2, F2 d1, F2 d2) {
                 F2 val = mo_;
@@ -258,7 +263,7 @@ struct PostPipeP {
                 last_out = val;
             };
             const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
-            if (BLUR && (o < 2 || o + 2 >= rows)) {                      // reflect-101 rows (rows >= 8 guaranteed)
+            if (BLUR && MODE == BORDER && (o < 2 || o + 2 >= rows)) {    // reflect-101 rows (rows >= 8 guaranteed)
                 finish(o >= 1 ? g_m1 : g_p1,
                        o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),
                        o + 1 < rows ? g_p1 : g_m1,
@@ -279,7 +284,7 @@ struct PostPipeP {
     // Horizontal, two columns per lane, four lane shifts (each folded into an add):  S1 = O[l-1] + O,  S2 = E + E[l+1],
     //     G_E = 4 (E + S1) + (S2[l-1] + S2) = 6 E + 4 (O[l-1] + O) + E[l-1] + E[l+1],   G_O = 4 (O + S2) + (S1 + S1[l+1]):
     // 2 conversions + 8 + 2 * 4 + 2 instructions per row step instead of 4 + 14 + 10 + 2.
-    template <int PP>
+    template <int PP, int MODE = BORDER>
     __device__ __forceinline__ void after_median_codes(unsigned m, int u)
     {
         static_assert(BLUR, "exact only on grid values; the select of LO :184 is not in here");
@@ -292,7 +297,7 @@ struct PostPipeP {
         const float ue = __fadd_rn(from_left(s2), s2), wo = __fadd_rn(from_right(s1), s1);
         G1[(PP + 4) & 7] = {__builtin_fmaf(__fadd_rn(ce, s1), 4.0f, ue), __builtin_fmaf(__fadd_rn(co, s2), 4.0f, wo)};
         const int o = u - 6;
-        if ((unsigned)o < (unsigned)rows) {
+        if (MODE != BORDER || (unsigned)o < (unsigned)rows) {
             const float top = __fadd_rn(max_depth, (float)Q16::OFFSET * 0.00390625f);     // 100 + 6143 / 256: exact
             auto finish = [&](F2 u1, F2 u2, F2 d1, F2 d2) {
                 const F2 g0 = G1[(PP + 2) & 7];
@@ -303,7 +308,7 @@ struct PostPipeP {
                 last_out = val;
             };
             const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
-            if (o < 2 || o + 2 >= rows) {                                // reflect-101 rows, as above
+            if (MODE == BORDER && (o < 2 || o + 2 >= rows)) {            // reflect-101 rows, as above
                 finish(o >= 1 ? g_m1 : g_p1,
                        o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),
                        o + 1 < rows ? g_p1 : g_m1,
@@ -363,13 +368,14 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     const unsigned flb = EB * (unsigned)gxbc + (unsigned)max(tib, V) * rowb, ceb = EB * (unsigned)gxbc + (unsigned)max(bib, V) * rowb;
     auto clamp3 = [](unsigned a, unsigned lo, unsigned hi) -> unsigned { unsigned r; asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(lo), "v"(hi)); return r; };
     // one column's code at a (clamped) byte offset
-    auto ld_code = [&](unsigned off) -> unsigned { return (unsigned)(unsigned short)__builtin_amdgcn_raw_buffer_load_b16(sf.rs, off, 0, 0); };
-    struct Raw { unsigned e, o, b; };
+    // (what the load instruction returned, 16 bits: widening and packing are arithmetic on the result and belong to the step that consumes it)
+    auto ld_code = [&](unsigned off) -> unsigned short { return (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(sf.rs, off, 0, 0); };
+    struct Raw { unsigned short e, o, b; };
     auto ld_row = [&](int row) -> Raw {                              // row relative to V, already clamped to [0, rows)
         return Raw{ld_code(clamp3(sbe + (unsigned)row * rowb, fle, cee)), ld_code(clamp3(sbo + (unsigned)row * rowb, flo, ceo)),
                    ld_code(clamp3(sbb + (unsigned)row * rowb, flb, ceb))};
     };
-    auto pack = [](unsigned e, unsigned o) -> unsigned { return e | (o << 16); };
+    auto pack = [](unsigned short e, unsigned short o) -> unsigned { return (unsigned)e | ((unsigned)o << 16); };
     const bool outside = gxe < 0 || gxe >= cols;
     const bool own = !outside && 2 * lane >= FpQ::H && 2 * lane < 128 - FpQ::H;
     const unsigned long long own_mask = __ballot(own);
@@ -391,16 +397,22 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     const bool warm = V > 0;
     unsigned xa0 = 0, xb0 = 0;                                       // cold start: 0 is the neutral element
     if (warm) { const Raw r = ld_row(0); xa0 = pack(r.e, r.o); xb0 = r.b; }
-    unsigned PFA[16], PFB[16], W2A[16], W6A[16], W2B[16], W6B[16];
+    // The prefetch rings, slot = step mod 16, PFD of them in flight.  They are carried round the loops as the load instructions left
+    // them -- a value COMPUTED from a load result and carried over a back edge makes the compiler wait there for every load in flight
+    // (one drain of the whole lookahead per 16 row steps).  The border body loads three 16-bit codes per row
+    // (PFE, PFO, PFB), the interior body one dword for the (E, O) pair (PFA) and PFB; the two formats meet only where the main
+    // loop changes bodies (twice per wave).
+    unsigned short PFE[16], PFO[16], PFB[16];
+    unsigned PFA[16], W2A[16], W6A[16], W2B[16], W6B[16];
 #pragma unroll
-    for (int q = 0; q < 16; ++q) { PFA[q] = PFB[q] = 0; W2A[q] = W6A[q] = xa0; W2B[q] = W6B[q] = xb0; }
+    for (int q = 0; q < 16; ++q) { PFE[q] = PFO[q] = PFB[q] = 0; PFA[q] = 0; W2A[q] = W6A[q] = xa0; W2B[q] = W6B[q] = xb0; }
 #pragma unroll
     for (int q = 0; q < 16; ++q) { dl_c[q][lane] = xa0; dl_a[q][lane] = xa0; dl_b[q][lb] = xb0; }
     constexpr int PFD = DCMT_FPQ_PFD;        // rows of load lookahead
 #pragma unroll
     for (int q = 0; q < PFD; ++q) {
         const Raw r = ld_row(min(max(q + (warm ? 16 : 0) - 15, 0), rows - 1));
-        PFA[q] = pack(r.e, r.o); PFB[q] = r.b;
+        PFE[q] = r.e; PFO[q] = r.o; PFB[q] = r.b;
     }
     unsigned vpa = xa0, vpb = xb0, x7_prev = xa0;
     int before = 0, after = 0;
@@ -408,13 +420,25 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     unsigned long long pend_hme = 0, pend_hmo = 0;
     unsigned nxt_c = xa0, nxt_a = xa0, nxt_b = xb0;
 
-    // the fill front end of step t: returns X7 (packed codes) of image row t - 31
-    auto fill_step = [&](auto P_, int t) -> unsigned {
+    using Pipe = PostPipeP<BLUR>;
+    using BorderMode = std::integral_constant<int, Pipe::BORDER>;
+    // the fill front end of step t: returns X7 (packed codes) of image row t - 31.  M_: Pipe::BORDER, or Pipe::INNER -- the caller
+    // vouches that row t + PFD - 15 is a row of the stream no column clamps (one aligned dword holds E and O, the row offset is
+    // wave-uniform) and that X7 row t - 31 is a row of the frame
+    auto fill_step = [&](auto P_, auto M_, int t) -> unsigned {
         constexpr int p = decltype(P_)::value;
-        const unsigned xa = PFA[p], xb = PFB[p];
-        {
+        constexpr int MODE = decltype(M_)::value;
+        unsigned xa;
+        const unsigned xb = PFB[p];
+        if constexpr (MODE == Pipe::BORDER) {
+            xa = pack(PFE[p], PFO[p]);
             const Raw r = ld_row(min(max(t + PFD - 15, 0), rows - 1));
-            PFA[(p + PFD) & 15] = pack(r.e, r.o); PFB[(p + PFD) & 15] = r.b;
+            PFE[(p + PFD) & 15] = r.e; PFO[(p + PFD) & 15] = r.o; PFB[(p + PFD) & 15] = r.b;
+        } else {
+            xa = PFA[p];
+            const unsigned srow = (unsigned)(t + PFD - 15) * rowb;   // wave-uniform: an SGPR offset
+            PFA[(p + PFD) & 15] = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(sf.rs, sbe, srow, 0);
+            PFB[(p + PFD) & 15] = (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(sf.rs, sbb, srow, 0);
         }
         const int o = t - 31;
         unsigned x7 = pend_v;
@@ -423,7 +447,7 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
             const bool he = __builtin_amdgcn_inverse_ballot_w64(pend_hme), ho = __builtin_amdgcn_inverse_ballot_w64(pend_hmo);
             const unsigned m = (he ? 0xffffu : 0u) | (ho ? 0xffff0000u : 0u);
             x7 = (d & m) | (pend_v & ~m);
-            if ((unsigned)o < (unsigned)rows) {
+            if (MODE != Pipe::BORDER || (unsigned)o < (unsigned)rows) {
                 before += __builtin_popcountll(pend_hme & own_mask) + __builtin_popcountll(pend_hmo & own_mask);
                 after += __builtin_popcountll(__builtin_amdgcn_ballot_w64((x7 << 16) <= Q16::HOLE_MAX_HI) & own_mask) +
                          __builtin_popcountll(__builtin_amdgcn_ballot_w64(x7 <= Q16::HOLE_MAX_HI) & own_mask);
@@ -434,7 +458,7 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
             if (gxe < 0) x7 = (l0 & 0xffffu) | (l0 << 16);
             if (gxe >= cols) x7 = (r0 >> 16) | (r0 & 0xffff0000u);
         }
-        if (o >= rows) { asm volatile("" ::); x7 = x7_prev; }
+        if (MODE == Pipe::BORDER && o >= rows) { asm volatile("" ::); x7 = x7_prev; }
         x7_prev = x7;
         // vertical 31-max: A packed (two-input instructions), B unpacked
         const unsigned w2a = hmax2(xa, vpa);
@@ -484,14 +508,15 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
         return x7;
     };
     // post step u: the median of image row u - 4 on packed pairs, then PostPipeP's f32 tail
-    auto post_step = [&](auto PP_, unsigned x, int u) {
+    auto post_step = [&](auto PP_, auto M_, unsigned x, int u) {
         constexpr int PP = decltype(PP_)::value;
+        constexpr int MODE = decltype(M_)::value;
         const unsigned rl = u_left(x), rr = u_right(x);              // columns 2l-2, 2l-1 | 2l+2, 2l+3
         unsigned s[5] = {rl, __builtin_amdgcn_alignbit(x, rl, 16), x, __builtin_amdgcn_alignbit(rr, x, 16), rr};
         q_sort5(s);
         const unsigned m = mc.template step<PP>(s);
-        if constexpr (BLUR && FILLED) pipe.template after_median_codes<PP>(m, u);       // codes all the way: exact (PostPipeP)
-        else pipe.template after_median<PP>(Q16::value(m & 0xffffu), Q16::value(m >> 16), u);
+        if constexpr (BLUR && FILLED) pipe.template after_median_codes<PP, MODE>(m, u);       // codes all the way: exact (PostPipeP)
+        else pipe.template after_median<PP, MODE>(Q16::value(m & 0xffffu), Q16::value(m >> 16), u);
     };
 
     // steps 0..31 (16..31 after a warm start): fill only.  The last of them returns X7 row 0, which the post pipeline takes three times
@@ -499,12 +524,12 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     for (int t0 = warm ? 16 : 0; t0 < 32; t0 += 16) {
         static_for<0, 16>([&](auto P_) {
             constexpr int p = decltype(P_)::value;
-            const unsigned x7 = fill_step(P_, t0 + p);
+            const unsigned x7 = fill_step(P_, BorderMode{}, t0 + p);
             if constexpr (p == 15) {
                 if (t0 == 16) {
-                    post_step(std::integral_constant<int, 0>{}, x7, 0);
-                    post_step(std::integral_constant<int, 1>{}, x7, 1);
-                    post_step(std::integral_constant<int, 2>{}, x7, 2);
+                    post_step(std::integral_constant<int, 0>{}, BorderMode{}, x7, 0);
+                    post_step(std::integral_constant<int, 1>{}, BorderMode{}, x7, 1);
+                    post_step(std::integral_constant<int, 2>{}, BorderMode{}, x7, 2);
                 }
             }
         });
@@ -515,8 +540,8 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     auto main_step = [&](auto P_) {
         constexpr int p = decltype(P_)::value;
         const int t = t0 + p, u = t - 29;
-        const unsigned x7 = fill_step(P_, t);
-        post_step(std::integral_constant<int, ((p + 3) & 7)>{}, x7, u);
+        const unsigned x7 = fill_step(P_, BorderMode{}, t);
+        post_step(std::integral_constant<int, ((p + 3) & 7)>{}, BorderMode{}, x7, u);
         if constexpr (p == 3) {
             // u == 6: output row 0 of the shifted frame (image row V) has just been stored; the V rows above it are equal
             if (t0 == 32 && V > 0) {
@@ -529,7 +554,40 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     };
     // (the sixteen steps of a block in four quarters with a way out behind each: the last block of a wave is 7.5 steps too long on
     // average otherwise -- 3 % of its row steps)
+    //
+    // Interior blocks.  A block of 16 steps t0 .. t0 + 15 loads the stream rows t0 + PFD - 15 .. t0 + PFD, returns the X7 rows
+    // t0 - 31 .. t0 - 16 and stores the output rows t0 - 35 .. t0 - 20.  Where every one of those load rows lies inside the frame AND
+    // inside [first, last] valid row of every column the wave reads, ld_row's clamps are the identity; where the output rows lie in
+    // [2, rows - 3] (t0 >= 48 for the first, the load rows' bound covers the last), every row-range test of the step has one known
+    // answer.  Such blocks are one contiguous run of t0; they take a body without the clamps, the tests and the selects, with one
+    // dword load for (E, O).  Everything else -- the first and the last blocks, ragged tops and bottoms -- takes the border body
+    // above, which also keeps the quarter exits and the V top rows.
+    // edge_strip is a wave-uniform branch in both bodies.  As a compile-time property of the interior body (two loops chosen per
+    // wave, or one loop with the choice per block) it took k_fp_q<true, true> from 148 to 216..221 VGPRs -- the register allocator
+    // keeps the state of both instantiations apart -- and to 58..70 spilled VGPRs with three waves per SIMD asked for.
+    const int r_first = max(__builtin_amdgcn_readfirstlane(wave_max_i(max(max(tie, tio), tib))) - V, 0);
+    const int r_last = min(__builtin_amdgcn_readfirstlane(wave_min_i(min(min(bie, bio), bib))) - V, rows - 1);
+    auto interior = [&](int t) -> bool { return t >= 48 && t + PFD - 15 >= r_first && t + PFD <= r_last; };
+    using InnerMode = std::integral_constant<int, Pipe::INNER>;
     for (; t0 < nsteps; t0 += 16) {
+        if (interior(t0)) {
+            // the rows in flight change format: the only places that wait for the whole lookahead, twice per wave
+#pragma unroll
+            for (int q = 0; q < PFD; ++q) PFA[q] = pack(PFE[q], PFO[q]);
+            do {
+                static_for<0, 16>([&](auto P_) {
+                    constexpr int p = decltype(P_)::value;
+                    int t = t0 + p;
+                    asm volatile("" : "+s"(t));      // (the row offsets from t, step by step: left to itself the compiler keeps 30 multiples of the row pitch in SGPRs and spills)
+                    const unsigned x7 = fill_step(P_, InnerMode{}, t);
+                    post_step(std::integral_constant<int, ((p + 3) & 7)>{}, InnerMode{}, x7, t - 29);
+                });
+                t0 += 16;
+            } while (interior(t0));
+#pragma unroll
+            for (int q = 0; q < PFD; ++q) { PFE[q] = (unsigned short)PFA[q]; PFO[q] = (unsigned short)(PFA[q] >> 16); }
+            // (the block behind an interior run exists and is no interior one: t0 + PFD > r_last and t0 - 16 + PFD <= rows - 1 < nsteps - 16)
+        }
         static_for<0, 4>(main_step);
         if (t0 + 4 >= nsteps) break;
         static_for<4, 8>(main_step);
