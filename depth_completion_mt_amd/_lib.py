@@ -33,6 +33,7 @@ EXPORTS = (
     "dcmt_evaluate_dev", "dcmt_evaluate_u16_dev", "dcmt_evaluate",
     "dcmt_colorize_dev", "dcmt_colorize", "dcmt_colormap_jet",
     "dcmt_default_cloud_params", "dcmt_depth_to_cloud_dev", "dcmt_depth_to_cloud", "dcmt_gaussian5_dev", "dcmt_gaussian5",
+    "dcmt_default_reproject_params", "dcmt_reproject_depth_dev", "dcmt_reproject_depth",
 )
 
 
@@ -75,6 +76,13 @@ class CloudPoint(ctypes.Structure):
     """Mirror of dcmt_cloud_point (include/dcmt.h): one 16-byte record."""
     _fields_ = [("x", ctypes.c_float), ("y", ctypes.c_float), ("z", ctypes.c_float),
                 ("b", ctypes.c_uint8), ("g", ctypes.c_uint8), ("r", ctypes.c_uint8), ("a", ctypes.c_uint8)]
+
+
+class ReprojectParams(ctypes.Structure):
+    """Mirror of dcmt_reproject_params (include/dcmt.h): the source camera's intrinsics, the 4x4 transform that is applied and the
+    destination camera's 3x3 matrix, both row-major."""
+    _fields_ = [("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+                ("M", ctypes.c_float * 16), ("K", ctypes.c_float * 9)]
 
 
 def build(force: bool = False) -> str:
@@ -158,6 +166,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_depth_to_cloud.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i64, ctypes.POINTER(i64)]
         L.dcmt_gaussian5_dev.argtypes = [vp, vp, vp, i, i, i, vp]
         L.dcmt_gaussian5.argtypes = [vp, vp, sz, vp, sz, i, i]
+        L.dcmt_default_reproject_params.argtypes = [vp]
+        L.dcmt_default_reproject_params.restype = None
+        L.dcmt_reproject_depth_dev.argtypes = [vp, vp, i, i, i, vp, vp, i, i, vp]
+        L.dcmt_reproject_depth.argtypes = [vp, vp, sz, i, i, vp, vp, sz, i, i]
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

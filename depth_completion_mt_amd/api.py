@@ -11,6 +11,8 @@
         reference: src/DC_lidar_only/main.cpp:6-14
     reproject_pc_colors(depth, bgr) / reproject_pc(depth) -> the ordered point cloud of a dense plane
         reference: src/DC_stereo_lidar/main_sl.cpp:924-965, :887-922
+    unrectify_sol(depth_pre_optim, out_shape, R_rect) -> the plane forward-warped into the un-rectified camera's frame
+        reference: src/DC_stereo_lidar/main_sl.cpp:967-1028 (its data, not its drawing and printing)
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -90,6 +92,28 @@ def make_cloud_params(fx: float | None = None, fy: float | None = None, cx: floa
         if v is not None:
             setattr(p, k, float(v))
     return p
+
+
+def make_reproject_params(M=None, K=None, fx: float | None = None, fy: float | None = None, cx: float | None = None,
+                          cy: float | None = None) -> L.ReprojectParams:
+    """dcmt_reproject_params: the reference's intrinsics and camera_mat (SL/main_sl.cpp:969-976) and M = identity unless given.
+    M: 4x4 (the matrix that is APPLIED: pass the inverse of R_rect; its 4th row is ignored), K: 3x3, both row-major, rounded to f32."""
+    p = L.ReprojectParams()
+    L.lib().dcmt_default_reproject_params(ctypes.byref(p))
+    for k, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy)):
+        if v is not None:
+            setattr(p, k, float(v))
+    if M is not None:
+        p.M[:] = np.asarray(M, dtype=np.float32).reshape(16).tolist()
+    if K is not None:
+        p.K[:] = np.asarray(K, dtype=np.float32).reshape(9).tolist()
+    return p
+
+
+def inverse_f32(R_rect) -> np.ndarray:
+    """What unrectify_sol passes as M: the inverse of the 4x4 R_rect computed in f64 (numpy.linalg.inv) and rounded once to f32.
+    This inverse is OURS: the reference calls Eigen's f32 Matrix4f::inverse() inside its loop, whose bits are not reproduced."""
+    return np.linalg.inv(np.asarray(R_rect, dtype=np.float64).reshape(4, 4)).astype(np.float32)
 
 
 class Context:
@@ -424,6 +448,44 @@ class Context:
             raise DcmtError(st, "dcmt_gaussian5")
         return out
 
+    # ---- a plane seen by one camera -> the plane another camera sees (dcmt_reproject_depth*) ------------------------------
+    def reproject_depth_dev(self, d_depth, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None, d_out=None,
+                            stream: int | None = None):
+        """The data part of the reference's unrectify_sol (SL/main_sl.cpp:967-1028) on the device: every source pixel is un-projected
+        with the intrinsics, moved by M, projected with K and, where it lands inside [out_rows][out_cols], stores its new depth; the
+        last source pixel in row-major order wins a destination pixel, pixels nothing lands on are 0.  d_depth: contiguous f32 CUDA
+        tensor [batch][rows][cols] (or [rows][cols]: a batch of one).  Returns d_out, f32 [batch][out_rows][out_cols] (or
+        [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation."""
+        import torch
+        assert d_depth.is_cuda and d_depth.dtype == torch.float32 and d_depth.is_contiguous()
+        shp = d_depth.shape if d_depth.dim() == 3 else (1,) + tuple(d_depth.shape)
+        b, r, c = shp
+        if d_out is None:
+            d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
+        assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.is_contiguous() and d_out.numel() == b * out_rows * out_cols
+        p = params or make_reproject_params()
+        if stream is None:
+            stream = torch.cuda.current_stream(d_depth.device).cuda_stream
+        st = L.lib().dcmt_reproject_depth_dev(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
+                                              int(out_cols), ctypes.c_void_p(stream))
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_reproject_depth_dev")
+        return d_out
+
+    def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None) -> np.ndarray:
+        """One frame of host memory (dcmt_reproject_depth, synchronous; any row stride): a new f32 array [out_rows][out_cols]."""
+        a = np.asarray(depth, dtype=np.float32)
+        assert a.ndim == 2
+        if a.strides[1] != 4:
+            a = np.ascontiguousarray(a)
+        out = np.empty((int(out_rows), int(out_cols)), dtype=np.float32)
+        p = params or make_reproject_params()
+        st = L.lib().dcmt_reproject_depth(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], ctypes.byref(p), out.ctypes.data,
+                                          out.strides[0], out.shape[0], out.shape[1])
+        if st != L.OK:
+            raise DcmtError(st, "dcmt_reproject_depth")
+        return out
+
     def last_fill_iters(self, n: int):
         out = (ctypes.c_int * n)()
         st = L.lib().dcmt_last_fill_iters(self._h, out, n)
@@ -518,6 +580,17 @@ def reproject_pc(depth):
     """The reference's reproject_pc (SL/main_sl.cpp:887-922): as reproject_pc_colors without a colour plane; the fourth dword of
     every record is 1.0f."""
     return reproject_pc_colors(depth, None)
+
+
+def unrectify_sol(depth_pre_optim, out_shape, R_rect) -> np.ndarray:
+    """The reference's unrectify_sol (SL/main_sl.cpp:967-1028, called at :1228) on one host frame, without its drawing and printing:
+    depth_pre_optim forward-warped into the un-rectified camera's frame, a new f32 array of out_shape = (rows, cols) that is 0 where
+    nothing lands.  R_rect: the 4x4 matrix the reference passes (R_rect_02).  The matrix that is applied is inverse_f32(R_rect): the
+    inverse computed in f64 and rounded to f32 -- ours, not the bits of Eigen's f32 inverse()."""
+    a = np.asarray(depth_pre_optim, dtype=np.float32)
+    rows, cols = int(out_shape[0]), int(out_shape[1])
+    ctx = _ctx_for(max(a.shape[0], rows), max(a.shape[1], cols), 1)
+    return ctx.reproject_depth(a, rows, cols, make_reproject_params(M=inverse_f32(R_rect)))
 
 
 def write_pcd(path, points) -> None:

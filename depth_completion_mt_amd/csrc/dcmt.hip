@@ -66,7 +66,8 @@ struct dcmt_ctx {
     int* q16_seen = nullptr;          // pinned host word (and its device address) the same kernel sets: the NEXT calls skip the 16-bit attempt
     int* q16_seen_dev = nullptr;
     int q16_skip = 0;                 // calls left without an attempt (after a raised flag: 63, then one more try)
-    unsigned* winner = nullptr;       // N2: the winner plane of dcmt_project_points_dev (tags: generation | point index), allocated by its first call
+    unsigned* winner = nullptr;       // the winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev (tags: generation | index; winner_generation),
+                                      // allocated by the first call of either
     size_t winner_elems = 0;
     int winner_bits = 0;              // index bits of the plane's tag layout
     unsigned winner_gen = 0;          // generation of the last call (0: the plane is all zeros and nothing has been written)
@@ -766,6 +767,59 @@ int gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int
     return DCMT_OK;
 }
 
+// The winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev: tags of generation g = (g << idx_bits) | index, g >= 1
+// (0 = the cleared plane); the index is N2's global point index or the reprojection's frame-local source pixel index.  A call only
+// looks at tags of its own generation, so the plane is not cleared between calls, whichever of the two they are.  It is cleared when
+// it is (re)allocated, when a call needs more index bits than its layout has, and when the generations run out.  n_px: entries
+// this call needs; n_index: it stores indices below n_index (N2 keeps its bound of <= n_index).  Any allocation happens here, before
+// the call has enqueued anything.  Returns the call's generation, shifted into place.
+int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag)
+{
+    int need_bits = 1;
+    while (need_bits < 31 && ((size_t)1 << need_bits) <= n_index) ++need_bits;
+    if (need_bits > 30) return DCMT_E_INVALID;
+    if (n_px > ctx->winner_elems) {
+        (void)hipFree(ctx->winner); ctx->winner = nullptr; ctx->winner_elems = 0;
+        DCMT_HIP(ctx, hipMalloc((void**)&ctx->winner, sizeof(unsigned) * n_px));
+        ctx->winner_elems = n_px; ctx->winner_bits = 0; ctx->winner_gen = 0;
+    }
+    const bool relayout = need_bits > ctx->winner_bits;
+    if (relayout) ctx->winner_bits = need_bits < 24 ? 24 : need_bits;       // (room for 16 M indices per call before the next re-layout)
+    const unsigned gen_max = (1u << (32 - ctx->winner_bits)) - 1u;
+    if (relayout || ctx->winner_gen == 0 || ctx->winner_gen >= gen_max) {
+        DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner_elems, st));
+        ctx->winner_gen = 0;
+    }
+    *gen_tag = ++ctx->winner_gen << ctx->winner_bits;
+    return DCMT_OK;
+}
+
+// dcmt_reproject_depth_dev: k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h, compiled in dcmt_cloud.hip) on the
+// winner plane above
+int reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                        float* d_out, int out_rows, int out_cols, hipStream_t st)
+{
+    if (!ctx || !d_depth || !d_out || !params) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
+    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
+    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
+    for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
+    const size_t src_px = (size_t)rows * cols, dst_px = (size_t)out_rows * out_cols;
+    if (plan::ranges_overlap((uintptr_t)d_depth, sizeof(float) * src_px * batch, (uintptr_t)d_out, sizeof(float) * dst_px * batch)) return DCMT_E_INVALID;
+    ReprojK k;
+    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
+    std::memcpy(k.M, params->M, sizeof k.M);
+    std::memcpy(k.K, params->K, sizeof k.K);
+    unsigned gen_tag = 0;
+    const int rc = winner_generation(ctx, dst_px * batch, src_px, st, &gen_tag);
+    if (rc != DCMT_OK) return rc;
+    launch_reproject(d_depth, rows, cols, batch, k, ctx->winner, gen_tag, ctx->winner_bits, d_out, out_rows, out_cols, st);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -950,25 +1004,10 @@ int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t*
     ProjMats M;
     std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
     std::memcpy(M.P, P, sizeof(float) * 12);
-    // the winner plane: tags of generation g = (g << idx_bits) | point index, g >= 1 (0 = the cleared plane).  It is cleared when it
-    // is (re)allocated, when a call needs more index bits than its layout has, and when the generations run out.
     const size_t n_px = (size_t)batch * rows * cols;
-    int need_bits = 1;
-    while (need_bits < 31 && ((size_t)1 << need_bits) <= (size_t)n_points) ++need_bits;
-    if (need_bits > 30) return DCMT_E_INVALID;                             // (2^30 points per call: 16 GiB of records)
-    if (n_px > ctx->winner_elems) {
-        (void)hipFree(ctx->winner); ctx->winner = nullptr; ctx->winner_elems = 0;
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->winner, sizeof(unsigned) * n_px));
-        ctx->winner_elems = n_px; ctx->winner_bits = 0; ctx->winner_gen = 0;
-    }
-    const bool relayout = need_bits > ctx->winner_bits;
-    if (relayout) ctx->winner_bits = need_bits < 24 ? 24 : need_bits;       // (room for 16 M points per call before the next re-layout)
-    const unsigned gen_max = (1u << (32 - ctx->winner_bits)) - 1u;
-    if (relayout || ctx->winner_gen == 0 || ctx->winner_gen >= gen_max) {
-        DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner_elems, st));
-        ctx->winner_gen = 0;
-    }
-    const unsigned gen_tag = ++ctx->winner_gen << ctx->winner_bits;
+    unsigned gen_tag = 0;
+    const int rc = winner_generation(ctx, n_px, (size_t)n_points, st, &gen_tag);      // (2^30 points per call: 16 GiB of records)
+    if (rc != DCMT_OK) return rc;
     unsigned* winner = ctx->winner;
     if (n_points > 0)
         hipLaunchKernelGGL(k_project_scatter, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, M,
@@ -1061,6 +1100,27 @@ int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows
 {
     DCMT_ON_DEVICE(ctx);
     return gaussian5_dev(ctx, d_src, d_dst, rows, cols, batch, (hipStream_t)stream);
+}
+
+void dcmt_default_reproject_params(dcmt_reproject_params* p)
+{
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->fx = 9.597910e+02;   // main_sl.cpp:969-972
+    p->fy = 9.569251e+02;
+    p->cx = 6.960217e+02;
+    p->cy = 2.241806e+02;
+    p->M[0] = p->M[5] = p->M[10] = p->M[15] = 1.0f;
+    p->K[0] = 9.597910e+02f; p->K[2] = 6.960217e+02f;     // camera_mat, :974-976
+    p->K[4] = 9.569251e+02f; p->K[5] = 2.241806e+02f;
+    p->K[8] = 1.0f;
+}
+
+int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                             float* d_out, int out_rows, int out_cols, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    return reproject_depth_dev(ctx, d_depth, rows, cols, batch, params, d_out, out_rows, out_cols, (hipStream_t)stream);
 }
 
 int dcmt_slic_num_centers(int rows, int cols, int step)
@@ -1310,6 +1370,27 @@ int dcmt_gaussian5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size
     rc = dcmt_gaussian5_dev(ctx, (const float*)ds.p, (float*)dout.p, rows, cols, 1, st);
     if (rc != DCMT_OK) return rc;
     DCMT_HIP(ctx, hipMemcpy2DAsync(dst, drs, dout.p, frow, frow, rows, hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return DCMT_OK;
+}
+
+int dcmt_reproject_depth(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_reproject_params* params,
+                         float* out, size_t ors, int out_rows, int out_cols)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !out || !params || rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1) return DCMT_E_INVALID;
+    if (drs < sizeof(float) * (size_t)cols || ors < sizeof(float) * (size_t)out_cols) return DCMT_E_INVALID;
+    if (rows > ctx->max_rows || cols > ctx->max_cols || out_rows > ctx->max_rows || out_cols > ctx->max_cols) return DCMT_E_INVALID;
+    hipStream_t st;
+    int rc = host_stream(ctx, &st);
+    if (rc != DCMT_OK) return rc;
+    DevBuf dd, dout;
+    const size_t srow = sizeof(float) * (size_t)cols, orow = sizeof(float) * (size_t)out_cols;
+    if ((rc = dd.alloc(ctx, srow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, orow * out_rows)) != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(dd.p, srow, depth, drs, srow, rows, hipMemcpyHostToDevice, st));
+    rc = dcmt_reproject_depth_dev(ctx, (const float*)dd.p, rows, cols, 1, params, (float*)dout.p, out_rows, out_cols, st);
+    if (rc != DCMT_OK) return rc;
+    DCMT_HIP(ctx, hipMemcpy2DAsync(out, ors, dout.p, orow, orow, out_rows, hipMemcpyDeviceToHost, st));
     DCMT_HIP(ctx, hipStreamSynchronize(st));
     return DCMT_OK;
 }

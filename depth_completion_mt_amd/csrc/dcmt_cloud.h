@@ -18,4 +18,12 @@ void launch_depth_to_cloud(const float* depth, const uint8_t* bgr, uint32_t n, u
 // k_gauss5 on st; src and dst must not overlap
 void launch_gauss5(const float* src, float* dst, int rows, int cols, int batch, hipStream_t st);
 
+// dcmt_reproject_params as the kernels of dcmt_kernels_reproject.h take it: the three rows of M that are used, the two rows of K
+struct ReprojK { double fx, fy, cx, cy; float M[12]; float K[6]; };
+
+// k_reproject_scatter -> k_reproject_resolve on st.  winner: the context's winner plane (batch * out_rows * out_cols tags at least);
+// gen_tag, idx_bits: this call's generation and the plane's tag layout; depth and out must not overlap.
+void launch_reproject(const float* depth, int rows, int cols, int batch, const ReprojK& k, unsigned* winner, unsigned gen_tag, int idx_bits,
+                      float* out, int out_rows, int out_cols, hipStream_t st);
+
 }  // namespace dcmt

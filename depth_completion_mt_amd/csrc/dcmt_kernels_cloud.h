@@ -41,6 +41,14 @@ namespace dcmt {
 constexpr int kCloudThreads = 64 * kCloudWaves;
 constexpr int kCloudScanThreads = 1024;
 
+// (float)(((double)i - c) * (double)z / f): the x_ (i = column, c = cx, f = fx) or y_ (row, cy, fy) of a pixel of depth z.  f64
+// subtraction, product and a true division, one rounding each, then one rounding to f32 (k_cloud_scatter, and the kernels of
+// dcmt_kernels_reproject.h)
+__device__ __forceinline__ float unproject_axis(uint32_t i, double c, double z, double f)
+{
+    return (float)__ddiv_rn(__dmul_rn(__dsub_rn((double)i, c), z), f);
+}
+
 // the groups [ws, we) of wave w of chunk c (G groups per chunk: eval_chunk_groups(n)): a contiguous quarter of the chunk
 __device__ __forceinline__ void cloud_wave_run(uint32_t n, uint32_t G, uint32_t c, uint32_t w, uint32_t& ws, uint32_t& we)
 {
@@ -193,8 +201,8 @@ void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict_
                 const uint4 e = stage[slot];
                 const double z = (double)__uint_as_float(e.x);
                 uint4 o;
-                o.x = __float_as_uint((float)__ddiv_rn(__dmul_rn(__dsub_rn((double)e.y, k.cx), z), k.fx));
-                o.y = __float_as_uint((float)__ddiv_rn(__dmul_rn(__dsub_rn((double)e.z, k.cy), z), k.fy));
+                o.x = __float_as_uint(unproject_axis(e.y, k.cx, z, k.fx));
+                o.y = __float_as_uint(unproject_axis(e.z, k.cy, z, k.fy));
                 o.z = e.x;
                 o.w = e.w;
                 points[(size_t)(base + slot)] = o;

@@ -21,6 +21,7 @@
 
 #include <hip/hip_runtime.h>
 #include "dcmt_gauss.h"
+#include "dcmt_dot_rn.h"
 #include <float.h>
 #include <stdint.h>
 
@@ -140,10 +141,7 @@ void k_norm_write(const float* __restrict__ src, float* __restrict__ dst, const 
 // ---------------------------------------------------------------------------------
 struct ProjMats { float T[12]; float P[12]; };   // the three rows of T that are used; P
 
-__device__ __forceinline__ float dot4_rn(const float* m, float x, float y, float z)
-{
-    return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(m[0], x), __fmul_rn(m[1], y)), __fmul_rn(m[2], z)), m[3]);
-}
+// dot4_rn: dcmt_dot_rn.h
 
 // returns false if the point is dropped; otherwise pixel (u, v) and its depth
 __device__ __forceinline__ bool project_point(const ProjMats& M, float x, float y, float z, int rows, int cols, int& u, int& v, float& depth)

@@ -229,7 +229,8 @@ int dcmt_complete_labeled_f32_dev(dcmt_ctx *ctx, const float *d_src, const int32
  * operation, sums left to right -- the order of the reference's hand-written transform; Eigen's evaluation order for
  * `P * p.homogeneous()` is not pinned, so against a real build a point whose uf or vf sits
  * within an ulp of an integer may land in the neighbouring pixel.  Stream-ordered, never synchronises; uses ctx
- * scratch, so do not overlap it with another call on the same ctx. */
+ * scratch (the winner plane, shared with dcmt_reproject_depth_dev: see there), so do not overlap it with another call
+ * on the same ctx. */
 int dcmt_project_points_dev(dcmt_ctx *ctx, const float *d_points, const int32_t *d_offsets, int n_points,
                             int batch, const float T[16], const float P[12], float *d_sparse,
                             int rows, int cols, void *stream);
@@ -406,6 +407,55 @@ int dcmt_depth_to_cloud(dcmt_ctx *ctx, const float *depth, size_t depth_row_stri
 int dcmt_gaussian5_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, void *stream);
 /* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
 int dcmt_gaussian5(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols);
+
+/* ---- a dense plane seen by one camera -> the plane another camera sees --------------------------------- */
+
+/* The data part of unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228 on the pre-refinement depth so that "MAE
+ * pre" can be scored against ground truth, which lives in the un-rectified frame, :1225-1234); its cv::circle / imshow / std::cout
+ * lines are display and are not reproduced.  A forward warp: per source pixel (row y, column x), exactly the reference's statements
+ *     z  = depth                                                                            (:986-988)
+ *     x_ = (float)(((double)x - cx) * (double)z / fx)      f64 subtraction, product and a true IEEE division, one rounding
+ *     y_ = (float)(((double)y - cy) * (double)z / fy)      each, then one rounding to f32    (:989-990)
+ *     t  = M * (x_, y_, z, 1)                              rows 0..2                         (:993)
+ *     skip unless t.z > 0          -- the only validity test: there is NO depth > 0 filter   (:999)
+ *     c  = K * (t.x, t.y, t.z);  uf = c.x / t.z,  vf = c.y / t.z                             (:1000-1001)
+ *     if 0 <= uf < out_cols and 0 <= vf < out_rows:  out(int(vf), int(uf)) = t.z             (:1008-1015)
+ * in row-major source order, so a later source pixel overwrites an earlier one that fell into the same destination pixel (with
+ * KITTI's R_rect_02 some 800 destination pixels of a 352x1216 plane are decided that way).  d_out is written completely, 0 where
+ * nothing lands (the reference starts from Mat::zeros, :1227).
+ * M: 4x4, K: 3x3, both ROW-major (Eigen's default storage is column-major: pass the transposes' data()); M's 4th row and K's 3rd
+ * row are ignored.  M is the matrix that is APPLIED: the reference computes R_rect.inverse() with Eigen inside the loop; Eigen's
+ * f32 inverse is not reproduced, the caller passes the inverse.  All arithmetic behind x_, y_ is f32, one rounding per operation,
+ * sums left to right -- the order of the reference's hand-written transform in N2; Eigen's evaluation order for the
+ * `Matrix4f * Vector4f` and `Matrix3f * Vector3f` products is not pinned, so against a real build a pixel
+ * whose uf or vf sits within an ulp of an integer may land in the neighbouring pixel. */
+typedef struct { double fx, fy, cx, cy; float M[16]; float K[9]; } dcmt_reproject_params;   /* row-major; M's 4th row is ignored */
+/* fx, fy, cx, cy and K = camera_mat of :969-976; M = identity */
+void dcmt_default_reproject_params(dcmt_reproject_params *p);
+
+/* DEVICE pointers, stream-ordered.  d_depth: contiguous f32 [batch][rows][cols]; d_out: contiguous f32 [batch][out_rows][out_cols];
+ * both 4-byte aligned (16-byte d_out with batch * out_rows * out_cols a multiple of 4 takes the widest stores).  Finite inputs, as
+ * for every entry point of this library.  Never synchronises once it has allocated what it needs.  May be enqueued right behind any
+ * other *_dev call of the ctx on the same stream (same ordering rule as every *_dev call on one ctx); of the state the cascade
+ * carries from call to call it touches only the winner plane it SHARES with dcmt_project_points_dev: batch * out_rows * out_cols
+ * uint32 tags (generation | frame-local source pixel index, at least 24 index bits: one layout for both calls).  A call of either
+ * kind looks only at tags of its own generation, so the two may follow each other in any order; the plane is (re)allocated -- a
+ * synchronising hipMalloc, before the call enqueues anything -- only when a call needs more entries than any call before it, and
+ * cleared only then, when the generations run out (every 255 calls at 24 bits) or when a call needs more index bits.  The
+ * layout never shrinks: once a dcmt_project_points_dev call with more than 2^24 points has raised the index bits to b, every later
+ * call of either kind on that ctx runs out of generations after 2^(32-b) - 1 calls (7 at 29 bits), each time at the cost of
+ * one clear of the whole plane; a caller to whom that matters gives the two kinds a ctx each.  Integer
+ * atomicMax decides the winner: the result does not depend on arrival order, the batch size, a frame's position in the batch,
+ * alignment or the run.  d_depth is not written.
+ * DCMT_E_INVALID: a null pointer, rows x cols or out_rows x out_cols beyond the ctx limits, batch beyond max_batch, a non-finite
+ * intrinsic or matrix entry (of the rows that are read), fx or fy zero, a pointer not 4-byte aligned, d_out overlapping d_depth in
+ * any way (the reference's planes are distinct: there is no in-place form). */
+int dcmt_reproject_depth_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch,
+                             const dcmt_reproject_params *params, float *d_out, int out_rows, int out_cols, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); the same bits as the device call on the frame.  Uses the ctx's
+ * winner plane like the device call. */
+int dcmt_reproject_depth(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, int rows, int cols,
+                         const dcmt_reproject_params *params, float *out, size_t out_row_stride, int out_rows, int out_cols);
 
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 

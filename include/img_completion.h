@@ -231,6 +231,25 @@ inline void depth_to_cloud(const cv::Mat& depth, const cv::Mat& bgr, std::vector
     out.resize((size_t)n);
 }
 
+// unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
+// takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
+// overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
+// reference passes (it calls Eigen's R_rect.inverse() inside its loop; that f32 inverse is not reproduced here, pass your own).
+// Intrinsics and camera matrix: the reference's (:969-976).
+inline void unrectify_sol(const cv::Mat& depth, cv::Mat& depth_unrect, const float Minv[16])
+{
+    check_input(depth);
+    if (depth_unrect.type() != CV_32FC1 || depth_unrect.rows < 1 || depth_unrect.cols < 1)
+        throw std::runtime_error("unrectify_sol: the destination must be a pre-sized CV_32FC1 image");
+    const int rows = depth.rows, cols = depth.cols, orows = depth_unrect.rows, ocols = depth_unrect.cols;
+    dcmt_reproject_params p;
+    dcmt_default_reproject_params(&p);
+    for (int i = 0; i < 16; ++i) p.M[i] = Minv[i];
+    raise(dcmt_reproject_depth(thread_ctx().get(rows > orows ? rows : orows, cols > ocols ? cols : ocols), depth.ptr<float>(), depth.step[0],
+                               rows, cols, &p, depth_unrect.ptr<float>(), depth_unrect.step[0], orows, ocols),
+          "unrectify_sol");
+}
+
 }  // namespace dcmt_shim
 
 // reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there.
