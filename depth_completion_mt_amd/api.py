@@ -48,6 +48,38 @@ class DcmtError(RuntimeError):
         self.status = status
 
 
+def _check(st: int, what: str) -> None:
+    if st != L.OK:
+        raise DcmtError(st, what)
+
+
+def _is_dev(t, dtype=None) -> bool:
+    """A contiguous CUDA tensor (of that dtype)."""
+    return t.is_cuda and t.is_contiguous() and (dtype is None or t.dtype == dtype)
+
+
+def _brc(t, trailing: int = 0):
+    """(batch, rows, cols) of a [batch][rows][cols] or [rows][cols] tensor, `trailing` more dimensions behind them."""
+    shp = tuple(t.shape)[:t.dim() - trailing]
+    b, r, c = shp if len(shp) == 3 else (1,) + shp
+    return b, r, c
+
+
+def _stream(stream, t) -> ctypes.c_void_p:
+    """The hipStream_t a *_dev call enqueues on: the one given (as int), by default torch's current stream on t's device."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+    return ctypes.c_void_p(stream)
+
+
+def _frame_f32(a) -> np.ndarray:
+    """One host frame as the single-frame entry points take it: f32 [rows][cols] with unit column stride, any row stride."""
+    a = np.asarray(a, dtype=np.float32)
+    assert a.ndim == 2
+    return a if a.strides[1] == 4 else np.ascontiguousarray(a)
+
+
 def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int = L.STAGE_FINAL,
                 max_fill_iters: int = 64, spec_fill_iters: int = 1, verbose: bool = False,
                 max_depth: float = 100.0, valid_thresh: float = 0.1, force_staged: bool = False, force_fused: bool = False,
@@ -123,8 +155,7 @@ class Context:
         self._h = ctypes.c_void_p()
         self.device, self.max_rows, self.max_cols, self.max_batch = device, max_rows, max_cols, max_batch
         st = L.lib().dcmt_create(device, max_rows, max_cols, max_batch, ctypes.byref(self._h))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_create")
+        _check(st, "dcmt_create")
 
     def close(self):
         if self._h:
@@ -178,24 +209,20 @@ class Context:
         and returns immediately."""
         import torch
         p = params or make_params()
-        assert d_src.is_cuda and d_src.dtype == torch.float32 and d_src.is_contiguous()
+        assert _is_dev(d_src, torch.float32)
         if d_dst is None:
             d_dst = torch.full_like(d_src, float("nan"))     # never mistake stale memory for output
-        assert d_dst.is_cuda and d_dst.dtype == torch.float32 and d_dst.is_contiguous() and d_dst.shape == d_src.shape
-        shp = d_src.shape if d_src.dim() == 3 else (1,) + tuple(d_src.shape)
-        b, r, c = shp
-        if stream is None:
-            stream = torch.cuda.current_stream(d_src.device).cuda_stream
+        assert _is_dev(d_dst, torch.float32) and d_dst.shape == d_src.shape
+        b, r, c = _brc(d_src)
         if d_labels is None:
             st = L.lib().dcmt_complete_f32_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, ctypes.byref(p),
-                                               ctypes.c_void_p(stream))
+                                               _stream(stream, d_src))
         else:
-            assert d_labels.is_cuda and d_labels.dtype == torch.int32 and d_labels.is_contiguous()
+            assert _is_dev(d_labels, torch.int32)
             st = L.lib().dcmt_complete_labeled_f32_dev(self._h, d_src.data_ptr(), d_labels.data_ptr(), int(n_labels),
                                                        d_dst.data_ptr(), r, c, b, ctypes.byref(p), int(use_superpixel),
-                                                       ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_complete_f32_dev")
+                                                       _stream(stream, d_src))
+        _check(st, "dcmt_complete_f32_dev")
         return d_dst
 
     def complete_u16_dev(self, d_src16, scale: float = 1.0 / 256.0, d_dst=None, params: L.Params | None = None,
@@ -204,17 +231,13 @@ class Context:
         the reference's imread + convertTo(CV_32F, 1/256) (src/DC_lidar_only/main.cpp:75-82) fused into the first kernel."""
         import torch
         p = params or make_params()
-        assert d_src16.is_cuda and d_src16.element_size() == 2 and d_src16.is_contiguous()
-        shp = d_src16.shape if d_src16.dim() == 3 else (1,) + tuple(d_src16.shape)
-        b, r, c = shp
+        assert _is_dev(d_src16) and d_src16.element_size() == 2
+        b, r, c = _brc(d_src16)
         if d_dst is None:
             d_dst = torch.full(tuple(d_src16.shape), float("nan"), dtype=torch.float32, device=d_src16.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_src16.device).cuda_stream
         st = L.lib().dcmt_complete_u16_dev(self._h, d_src16.data_ptr(), ctypes.c_float(scale), d_dst.data_ptr(), r, c, b,
-                                           ctypes.byref(p), ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_complete_u16_dev")
+                                           ctypes.byref(p), _stream(stream, d_src16))
+        _check(st, "dcmt_complete_u16_dev")
         return d_dst
 
     def project_points_dev(self, d_points, d_offsets, T, P, rows: int, cols: int, d_sparse=None, stream: int | None = None):
@@ -222,52 +245,44 @@ class Context:
         [n][4] (x, y, z, reflectance); d_offsets: int32 CUDA tensor [batch + 1], frame f owns points
         [offsets[f], offsets[f+1]); T 4x4, P 3x4 row-major.  Returns [batch][rows][cols] f32, 0 = no point."""
         import torch
-        assert d_points.is_cuda and d_points.dtype == torch.float32 and d_points.is_contiguous() and d_points.shape[-1] == 4
-        assert d_offsets.is_cuda and d_offsets.dtype == torch.int32 and d_offsets.is_contiguous()
+        assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
+        assert _is_dev(d_offsets, torch.int32)
         batch = d_offsets.numel() - 1
         n = d_points.numel() // 4
         if d_sparse is None:
             d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
-        assert d_sparse.is_cuda and d_sparse.dtype == torch.float32 and d_sparse.is_contiguous() and tuple(d_sparse.shape) == (batch, rows, cols)
+        assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
         t = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
         p = np.ascontiguousarray(P, dtype=np.float32).reshape(12)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_points.device).cuda_stream
         st = L.lib().dcmt_project_points_dev(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch, t.ctypes.data, p.ctypes.data,
-                                             d_sparse.data_ptr(), rows, cols, ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_project_points_dev")
+                                             d_sparse.data_ptr(), rows, cols, _stream(stream, d_points))
+        _check(st, "dcmt_project_points_dev")
         return d_sparse
 
     def slic_labels_dev(self, d_lab, step: int, nc: int, d_labels=None, return_centers: bool = False, stream: int | None = None):
         """N3, Slic::generate_superpixels (LC/slic.cpp:101-182) on the device.  d_lab: uint8 CUDA tensor [batch][rows][cols][3]
         (or [rows][cols][3]).  Returns (labels int32 [batch][rows][cols], n_centers[, centers float64 [batch][n][5]])."""
         import torch
-        assert d_lab.is_cuda and d_lab.dtype == torch.uint8 and d_lab.is_contiguous() and d_lab.shape[-1] == 3
-        shp = d_lab.shape if d_lab.dim() == 4 else (1,) + tuple(d_lab.shape)
-        b, r, c = shp[0], shp[1], shp[2]
+        assert _is_dev(d_lab, torch.uint8) and d_lab.shape[-1] == 3
+        b, r, c = _brc(d_lab, 1)
         n = L.lib().dcmt_slic_num_centers(r, c, int(step))
         if d_labels is None:
             d_labels = torch.full((b, r, c), -7, dtype=torch.int32, device=d_lab.device)
-        assert d_labels.is_cuda and d_labels.dtype == torch.int32 and d_labels.is_contiguous() and tuple(d_labels.shape) == (b, r, c)
+        assert _is_dev(d_labels, torch.int32) and tuple(d_labels.shape) == (b, r, c)
         d_cent = torch.empty((b, max(n, 1), 5), dtype=torch.float64, device=d_lab.device) if return_centers else None
-        if stream is None:
-            stream = torch.cuda.current_stream(d_lab.device).cuda_stream
         st = L.lib().dcmt_slic_labels_dev(self._h, d_lab.data_ptr(), r, c, b, int(step), int(nc), d_labels.data_ptr(),
-                                          d_cent.data_ptr() if return_centers else None, ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_slic_labels_dev")
+                                          d_cent.data_ptr() if return_centers else None, _stream(stream, d_lab))
+        _check(st, "dcmt_slic_labels_dev")
         return (d_labels, n, d_cent[:, :n]) if return_centers else (d_labels, n)
 
     def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
         """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
         kw: baseline, focal, damp, max_depth override the reference's constants."""
         import torch
-        assert d_depth.is_cuda and d_depth.dtype == torch.float32 and d_depth.is_contiguous()
+        assert _is_dev(d_depth, torch.float32)
         for t in (d_left, d_right):
-            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.shape == d_depth.shape
-        shp = d_depth.shape if d_depth.dim() == 3 else (1,) + tuple(d_depth.shape)
-        b, r, c = shp
+            assert _is_dev(t, torch.uint8) and t.shape == d_depth.shape
+        b, r, c = _brc(d_depth)
         if d_out is None:
             d_out = torch.full_like(d_depth, float("nan"))
         sp = L.StereoParams()
@@ -276,12 +291,9 @@ class Context:
             setattr(sp, k, float(v))
         if iterations is not None:
             sp.iterations = int(iterations)
-        if stream is None:
-            stream = torch.cuda.current_stream(d_depth.device).cuda_stream
         st = L.lib().dcmt_stereo_refine_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(),
-                                            r, c, b, ctypes.byref(sp), ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_stereo_refine_dev")
+                                            r, c, b, ctypes.byref(sp), _stream(stream, d_depth))
+        _check(st, "dcmt_stereo_refine_dev")
         return d_out
 
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
@@ -292,41 +304,31 @@ class Context:
         PNG payload) that goes to dcmt_evaluate_u16_dev with gt = payload * gt_scale.  mode "gt": mask gt > thresh; "both":
         gt > thresh and pred > thresh.  Returns a float64 CUDA tensor [batch, 7] (EVAL_FIELDS) without synchronising."""
         import torch
-        assert d_pred.is_cuda and d_pred.dtype == torch.float32 and d_pred.is_contiguous()
-        assert d_gt.is_cuda and d_gt.is_contiguous() and d_gt.shape == d_pred.shape
-        shp = d_pred.shape if d_pred.dim() == 3 else (1,) + tuple(d_pred.shape)
-        b, r, c = shp
+        assert _is_dev(d_pred, torch.float32)
+        assert _is_dev(d_gt) and d_gt.shape == d_pred.shape
+        b, r, c = _brc(d_pred)
         if d_out is None:
             d_out = torch.empty((b, 7), dtype=torch.float64, device=d_pred.device)
-        assert d_out.is_cuda and d_out.dtype == torch.float64 and d_out.is_contiguous() and d_out.numel() == 7 * b
-        if stream is None:
-            stream = torch.cuda.current_stream(d_pred.device).cuda_stream
+        assert _is_dev(d_out, torch.float64) and d_out.numel() == 7 * b
         m = _eval_mode(mode)
         if d_gt.element_size() == 2:
             st = L.lib().dcmt_evaluate_u16_dev(self._h, d_gt.data_ptr(), ctypes.c_float(gt_scale), d_pred.data_ptr(), r, c, b,
-                                               ctypes.c_float(thresh), m, d_out.data_ptr(), ctypes.c_void_p(stream))
+                                               ctypes.c_float(thresh), m, d_out.data_ptr(), _stream(stream, d_pred))
         else:
             assert d_gt.dtype == torch.float32
             st = L.lib().dcmt_evaluate_dev(self._h, d_gt.data_ptr(), d_pred.data_ptr(), r, c, b, ctypes.c_float(thresh), m,
-                                           d_out.data_ptr(), ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_evaluate_dev")
+                                           d_out.data_ptr(), _stream(stream, d_pred))
+        _check(st, "dcmt_evaluate_dev")
         return d_out
 
     def evaluate(self, gt: np.ndarray, pred: np.ndarray, thresh: float = 0.0, mode="both") -> np.ndarray:
         """One frame of host memory (dcmt_evaluate, synchronous; any row stride): float64 [7] (EVAL_FIELDS)."""
-        g = np.asarray(gt, dtype=np.float32)
-        q = np.asarray(pred, dtype=np.float32)
-        assert g.ndim == 2 and g.shape == q.shape
-        if g.strides[1] != 4:
-            g = np.ascontiguousarray(g)
-        if q.strides[1] != 4:
-            q = np.ascontiguousarray(q)
+        g, q = _frame_f32(gt), _frame_f32(pred)
+        assert g.shape == q.shape
         out = L.EvalFrame()
         st = L.lib().dcmt_evaluate(self._h, g.ctypes.data, g.strides[0], q.ctypes.data, q.strides[0], g.shape[0], g.shape[1],
                                    ctypes.c_float(thresh), _eval_mode(mode), ctypes.byref(out))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_evaluate")
+        _check(st, "dcmt_evaluate")
         return np.array([getattr(out, f) for f in EVAL_FIELDS], dtype=np.float64)
 
     # ---- JET colourisation (dcmt_colorize*) --------------------------------------------
@@ -335,29 +337,21 @@ class Context:
         d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]).  Returns a uint8 CUDA tensor of d_src's shape + (3,),
         B, G, R per pixel, without synchronising."""
         import torch
-        assert d_src.is_cuda and d_src.dtype == torch.float32 and d_src.is_contiguous()
-        shp = d_src.shape if d_src.dim() == 3 else (1,) + tuple(d_src.shape)
-        b, r, c = shp
+        assert _is_dev(d_src, torch.float32)
+        b, r, c = _brc(d_src)
         if d_bgr is None:
             d_bgr = torch.empty(tuple(d_src.shape) + (3,), dtype=torch.uint8, device=d_src.device)
-        assert d_bgr.is_cuda and d_bgr.dtype == torch.uint8 and d_bgr.is_contiguous() and d_bgr.numel() == 3 * b * r * c
-        if stream is None:
-            stream = torch.cuda.current_stream(d_src.device).cuda_stream
-        st = L.lib().dcmt_colorize_dev(self._h, d_src.data_ptr(), r, c, b, d_bgr.data_ptr(), ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_colorize_dev")
+        assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
+        st = L.lib().dcmt_colorize_dev(self._h, d_src.data_ptr(), r, c, b, d_bgr.data_ptr(), _stream(stream, d_src))
+        _check(st, "dcmt_colorize_dev")
         return d_bgr
 
     def colorize(self, frame: np.ndarray) -> np.ndarray:
         """One frame of host memory (dcmt_colorize, synchronous; any row stride): uint8 [rows][cols][3], B, G, R."""
-        a = np.asarray(frame, dtype=np.float32)
-        assert a.ndim == 2
-        if a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
+        a = _frame_f32(frame)
         out = np.empty(a.shape + (3,), dtype=np.uint8)
         st = L.lib().dcmt_colorize(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], out.ctypes.data, out.strides[0])
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_colorize")
+        _check(st, "dcmt_colorize")
         return out
 
     # ---- point cloud of a dense plane (dcmt_depth_to_cloud*) and the blur in front of it (dcmt_gaussian5*) -----------
@@ -371,36 +365,29 @@ class Context:
         offsets int32 [batch + 1]; frame f owns points[offsets[f]:offsets[f + 1]].  Rows of points from offsets[batch] on are not
         written.  No synchronisation."""
         import torch
-        assert d_depth.is_cuda and d_depth.dtype == torch.float32 and d_depth.is_contiguous()
-        shp = d_depth.shape if d_depth.dim() == 3 else (1,) + tuple(d_depth.shape)
-        b, r, c = shp
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
         if d_bgr is not None:
-            assert d_bgr.is_cuda and d_bgr.dtype == torch.uint8 and d_bgr.is_contiguous() and d_bgr.numel() == 3 * b * r * c
+            assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
         if capacity is None:
             capacity = d_points.numel() // 4 if d_points is not None else b * r * c
         if d_points is None:
             d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
-        assert d_points.is_cuda and d_points.dtype == torch.float32 and d_points.is_contiguous() and d_points.numel() >= 4 * capacity
+        assert _is_dev(d_points, torch.float32) and d_points.numel() >= 4 * capacity
         if d_offsets is None:
             d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
-        assert d_offsets.is_cuda and d_offsets.dtype == torch.int32 and d_offsets.is_contiguous() and d_offsets.numel() == b + 1
+        assert _is_dev(d_offsets, torch.int32) and d_offsets.numel() == b + 1
         p = params or make_cloud_params()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_depth.device).cuda_stream
         st = L.lib().dcmt_depth_to_cloud_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
                                              ctypes.byref(p), d_points.data_ptr(), int(capacity), d_offsets.data_ptr(),
-                                             ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_depth_to_cloud_dev")
+                                             _stream(stream, d_depth))
+        _check(st, "dcmt_depth_to_cloud_dev")
         return d_points, d_offsets
 
     def depth_to_cloud(self, depth: np.ndarray, bgr: np.ndarray | None = None, params: L.CloudParams | None = None) -> np.ndarray:
         """One frame of host memory (dcmt_depth_to_cloud, synchronous; any row stride): a structured array (CLOUD_DTYPE: x y z f32,
         b g r a u8) of the true length."""
-        a = np.asarray(depth, dtype=np.float32)
-        assert a.ndim == 2
-        if a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
+        a = _frame_f32(depth)
         rows, cols = a.shape
         col = None
         if bgr is not None:
@@ -414,8 +401,7 @@ class Context:
         st = L.lib().dcmt_depth_to_cloud(self._h, a.ctypes.data, a.strides[0], col.ctypes.data if col is not None else None,
                                          col.strides[0] if col is not None else 0, rows, cols, ctypes.byref(p), out.ctypes.data,
                                          out.size, ctypes.byref(n))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_depth_to_cloud")
+        _check(st, "dcmt_depth_to_cloud")
         return out[:n.value].copy()
 
     def gaussian5_dev(self, d_src, d_dst=None, stream: int | None = None):
@@ -423,29 +409,21 @@ class Context:
         masked select.  d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]); d_dst may be d_src (in place).
         Returns d_dst without synchronising."""
         import torch
-        assert d_src.is_cuda and d_src.dtype == torch.float32 and d_src.is_contiguous()
-        shp = d_src.shape if d_src.dim() == 3 else (1,) + tuple(d_src.shape)
-        b, r, c = shp
+        assert _is_dev(d_src, torch.float32)
+        b, r, c = _brc(d_src)
         if d_dst is None:
             d_dst = torch.full_like(d_src, float("nan"))
-        assert d_dst.is_cuda and d_dst.dtype == torch.float32 and d_dst.is_contiguous() and d_dst.numel() == d_src.numel()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_src.device).cuda_stream
-        st = L.lib().dcmt_gaussian5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_gaussian5_dev")
+        assert _is_dev(d_dst, torch.float32) and d_dst.numel() == d_src.numel()
+        st = L.lib().dcmt_gaussian5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, _stream(stream, d_src))
+        _check(st, "dcmt_gaussian5_dev")
         return d_dst
 
     def gaussian5(self, frame: np.ndarray) -> np.ndarray:
         """One frame of host memory (dcmt_gaussian5, synchronous; any row stride): a new f32 array."""
-        a = np.asarray(frame, dtype=np.float32)
-        assert a.ndim == 2
-        if a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
+        a = _frame_f32(frame)
         out = np.empty(a.shape, dtype=np.float32)
         st = L.lib().dcmt_gaussian5(self._h, a.ctypes.data, a.strides[0], out.ctypes.data, out.strides[0], a.shape[0], a.shape[1])
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_gaussian5")
+        _check(st, "dcmt_gaussian5")
         return out
 
     # ---- a plane seen by one camera -> the plane another camera sees (dcmt_reproject_depth*) ------------------------------
@@ -457,33 +435,25 @@ class Context:
         tensor [batch][rows][cols] (or [rows][cols]: a batch of one).  Returns d_out, f32 [batch][out_rows][out_cols] (or
         [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation."""
         import torch
-        assert d_depth.is_cuda and d_depth.dtype == torch.float32 and d_depth.is_contiguous()
-        shp = d_depth.shape if d_depth.dim() == 3 else (1,) + tuple(d_depth.shape)
-        b, r, c = shp
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
         if d_out is None:
             d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
-        assert d_out.is_cuda and d_out.dtype == torch.float32 and d_out.is_contiguous() and d_out.numel() == b * out_rows * out_cols
+        assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
         p = params or make_reproject_params()
-        if stream is None:
-            stream = torch.cuda.current_stream(d_depth.device).cuda_stream
         st = L.lib().dcmt_reproject_depth_dev(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
-                                              int(out_cols), ctypes.c_void_p(stream))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_reproject_depth_dev")
+                                              int(out_cols), _stream(stream, d_depth))
+        _check(st, "dcmt_reproject_depth_dev")
         return d_out
 
     def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None) -> np.ndarray:
         """One frame of host memory (dcmt_reproject_depth, synchronous; any row stride): a new f32 array [out_rows][out_cols]."""
-        a = np.asarray(depth, dtype=np.float32)
-        assert a.ndim == 2
-        if a.strides[1] != 4:
-            a = np.ascontiguousarray(a)
+        a = _frame_f32(depth)
         out = np.empty((int(out_rows), int(out_cols)), dtype=np.float32)
         p = params or make_reproject_params()
         st = L.lib().dcmt_reproject_depth(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], ctypes.byref(p), out.ctypes.data,
                                           out.strides[0], out.shape[0], out.shape[1])
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_reproject_depth")
+        _check(st, "dcmt_reproject_depth")
         return out
 
     def last_fill_iters(self, n: int):
@@ -496,15 +466,13 @@ class Context:
     def set_kernel_timing(self, on: bool = True):
         """Measurement aid: HIP events around the kernel groups of the streaming path of every following *_dev call."""
         st = L.lib().dcmt_set_kernel_timing(self._h, int(bool(on)))
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_set_kernel_timing")
+        _check(st, "dcmt_set_kernel_timing")
 
     def last_kernel_times(self) -> dict:
         """Milliseconds of the last *_dev call's kernel groups (synchronises with its stream)."""
         ms = (ctypes.c_float * 4)()
         st = L.lib().dcmt_last_kernel_times(self._h, ms)
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_last_kernel_times")
+        _check(st, "dcmt_last_kernel_times")
         return {"front": ms[0], "k_pre": ms[1], "k_fp": ms[2], "k_fp_s": ms[2], "behind": ms[3]}
 
     def last_path(self) -> str:
@@ -514,8 +482,7 @@ class Context:
     def last_holes_after_extend(self, n: int):
         out = (ctypes.c_int * n)()
         st = L.lib().dcmt_last_holes_after_extend(self._h, out, n)
-        if st != L.OK:
-            raise DcmtError(st, "dcmt_last_holes_after_extend")
+        _check(st, "dcmt_last_holes_after_extend")
         return list(out)
 
 

@@ -4,6 +4,11 @@
 // the kernels in dcmt_kernels_v1.h / dcmt_kernels_fused.h, and the host<->device copies of
 // the cv::Mat entry point.  No PyTorch, no OpenCV, no CPU fallback: if there is no gfx950
 // device every entry point fails with DCMT_E_NO_DEVICE / DCMT_E_HIP.
+//
+// The rest of the ABI is in two more translation units over dcmt_ctx.h (the context and the checks every entry point starts with):
+// dcmt_cloud.hip (point cloud, unmasked Gaussian, reprojection: kernels and *_dev entry points) and dcmt_host.hip (the synchronous
+// single-frame host variants of the *_dev calls).  Host code may move between them; a kernel and the function that launches it stay
+// where they are, in their order: both decide what the compiler emits for every other kernel of the code object.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +23,7 @@
 
 #include "dcmt.h"
 #include "dcmt_plan.h"
+#include "dcmt_ctx.h"
 #include "dcmt_kernels_v1.h"
 #include "dcmt_kernels_fused.h"
 #include "dcmt_kernels_pair.h"
@@ -30,63 +36,6 @@
 
 using namespace dcmt;
 
-struct dcmt_ctx {
-    int device = 0;
-    int max_rows = 0, max_cols = 0, max_batch = 0;
-    size_t frame_elems = 0;           // max_rows * max_cols
-    // device scratch
-    float* x5 = nullptr;              // [max_batch][rows][cols] : cascade after the small fill (= pp[1], see dcmt_create)
-    float* pp[2] = {nullptr, nullptr};// ping-pong of the large-fill applications
-    int* colstat = nullptr;           // [max_batch][tile rows][2][cols]  (staged path)
-    int* counters = nullptr;          // [max_batch][kCntStride]
-    int* tb = nullptr;                // [max_batch][2][max_cols]: first / last valid row of every X6 column (k_pre table mode -> k_fp_s)
-    uint32_t* norm_stats = nullptr;   // [max_batch][2]  N1: order-preserving keys of each frame's max and (inverted) min
-    float* norm_coef = nullptr;       // [max_batch][2]  N1: dst = src * a + b
-    // host-entry staging (allocated on first use)
-    float* d_in = nullptr;
-    float* d_out = nullptr;
-    int32_t* d_lab = nullptr;
-    int* h_counters = nullptr;        // pinned
-    hipStream_t own_stream = nullptr;
-    // state of the last call
-    hipStream_t last_stream = nullptr;
-    int last_batch = 0;
-    int last_apps_launched = 0;       // loop applications (app >= 1) enqueued
-    int last_has_loop = 0;            // the call went at least through H8
-    int last_hip_error = 0;
-    char last_path[160] = "";         // dcmt_last_path: the kernels the last call dispatched
-    int timing = 0;                   // dcmt_set_kernel_timing: events around the kernel groups of the streaming path
-    hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int tev_valid = 0;                // the last call recorded all five
-    plan::Knobs knobs;                // the environment knobs (dcmt_plan.h), read by dcmt_create
-    unsigned short* x6q = nullptr;    // [max_batch][rows][cols] X6 as 16-bit codes (k_pre_p<Q16OUT> -> k_fp_q)
-    int* q16_bad = nullptr;           // a ring of kQ16Flags flags; attempt n uses flag n % kQ16Flags: raised by k_pre_p<Q16OUT> when a value it stored was
-                                      // not a code, and cleared one attempt ahead by that kernel too (no memset in the stream)
-    unsigned q16_attempts = 0;
-    int* q16_seen = nullptr;          // pinned host word (and its device address) the same kernel sets: the NEXT calls skip the 16-bit attempt
-    int* q16_seen_dev = nullptr;
-    int q16_skip = 0;                 // calls left without an attempt (after a raised flag: 63, then one more try)
-    unsigned* winner = nullptr;       // the winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev (tags: generation | index; winner_generation),
-                                      // allocated by the first call of either
-    size_t winner_elems = 0;
-    int winner_bits = 0;              // index bits of the plane's tag layout
-    unsigned winner_gen = 0;          // generation of the last call (0: the plane is all zeros and nothing has been written)
-    int* bb_min = nullptr;            // LC fast path: per (frame, label) bounding boxes, grown on demand
-    int* bb_max = nullptr;
-    size_t bb_ints = 0;
-    // N3 (SLIC) scratch, allocated by the first dcmt_slic_labels_dev call
-    int* slic_cells = nullptr;                  // two cell sets: counts [batch][cells] + overflow flags [batch] each, then the index lists [batch][cells][kSlicCellCap] each
-    size_t slic_cell_cap = 0;                   // cells per frame that buffer holds
-    double* slic_centers[2] = {nullptr, nullptr};
-    unsigned long long* slic_sums = nullptr;
-    size_t slic_center_cap = 0;                 // centres per frame the two buffers above hold
-    double* eval_slab = nullptr;      // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
-                                      // allocated by the first evaluate call
-    float* color_slab = nullptr;      // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
-                                      // (allocated by dcmt_create)
-    uint32_t* cloud_slab = nullptr;   // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
-                                      // color_slab, kCloudWaves entries per chunk (allocated by dcmt_create)
-};
 
 namespace {
 
@@ -110,58 +59,11 @@ static_assert(plan::q16_params_ok(100.0f, 0.1f) && Q16::params_ok(100.0f, 0.1f) 
               !plan::q16_params_ok(100.0f, 0.2f) && !Q16::params_ok(100.0f, 0.2f), "Q16::params_ok");
 static_assert(sizeof(plan::Plan::path) == sizeof(dcmt_ctx::last_path), "dcmt_last_path");
 
-#define DCMT_HIP(ctx, call)                                        \
-    do {                                                           \
-        hipError_t e_ = (call);                                    \
-        if (e_ != hipSuccess) {                                    \
-            if (ctx) (ctx)->last_hip_error = (int)e_;              \
-            return e_ == hipErrorOutOfMemory ? DCMT_E_NOMEM : DCMT_E_HIP; \
-        }                                                          \
-    } while (0)
-
-
-// Every entry point that takes a context runs with that context's device current and puts the caller's current device back
-// before it returns: one process may drive several GPUs, one host thread + one dcmt_ctx + one stream per GPU (HIP's current
-// device is per thread), and a library that is shared with a framework (torch) must not move that framework's device.
-struct DeviceGuard {
-    int prev = -1, rc = DCMT_OK;
-    explicit DeviceGuard(dcmt_ctx* ctx)
-    {
-        if (!ctx) return;                                   // the entry point reports DCMT_E_INVALID itself
-        if (hipGetDevice(&prev) != hipSuccess) { prev = -1; rc = DCMT_E_HIP; return; }
-        if (prev != ctx->device) {
-            const hipError_t e = hipSetDevice(ctx->device);
-            if (e != hipSuccess) { ctx->last_hip_error = (int)e; rc = DCMT_E_HIP; prev = -1; }
-        } else prev = -1;                                   // nothing to restore
-    }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-};
-#define DCMT_ON_DEVICE(ctx) DeviceGuard dev_guard_(ctx); if (dev_guard_.rc != DCMT_OK) return dev_guard_.rc
-
 uint32_t k0_bits(const uint8_t k0[25])
 {
     uint32_t b = 0;
     for (int i = 0; i < 25; ++i) if (k0[i]) b |= 1u << i;
     return b;
-}
-
-// the library is built with -ffinite-math-only: test the exponent bits, not the value -- and read them through memory, or the
-// compiler, which may assume every float argument finite, folds the test to true
-bool finite_bits(float v)
-{
-    volatile float m = v;
-    const float c = m;
-    uint32_t b;
-    std::memcpy(&b, &c, sizeof b);
-    return (b & 0x7f800000u) != 0x7f800000u;
-}
-
-// rows x cols x batch is a size the context was created for
-bool dims_ok(const dcmt_ctx* ctx, int rows, int cols, int batch)
-{
-    return rows >= 1 && cols >= 1 && batch >= 1 && batch <= ctx->max_batch && rows <= ctx->max_rows && cols <= ctx->max_cols;
 }
 
 int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p)
@@ -721,58 +623,11 @@ int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batc
     return DCMT_OK;
 }
 
-// as finite_bits, for the f64 intrinsics of dcmt_cloud_params
-bool finite_bits64(double v)
-{
-    volatile double m = v;
-    uint64_t b;
-    double t = m;
-    std::memcpy(&b, &t, sizeof b);
-    return (b & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
+}  // namespace
 
-// dcmt_depth_to_cloud_dev: per-wave counts, their exclusive scan in one workgroup, then the scatter (dcmt_kernels_cloud.h, compiled
-// in dcmt_cloud.hip)
-int depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
-                       const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, hipStream_t st)
-{
-    if (!ctx || !d_depth || !d_points || !d_offsets || !params) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
-    if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
-    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
-    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
-    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
-    const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
-    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
-    launch_depth_to_cloud(d_depth, d_bgr, n, (uint32_t)cols, chunks, eval_chunk_groups(n), (uint32_t)batch, k, ctx->cloud_slab, d_points,
-                          (uint32_t)std::min<int64_t>(capacity, INT32_MAX), d_offsets, st);
-    DCMT_HIP(ctx, hipGetLastError());
-    return DCMT_OK;
-}
+namespace dcmt {
 
-// dcmt_gaussian5_dev: one streaming kernel (k_gauss5, dcmt_kernels_cloud.h); an in-place call writes to pp[0] (scratch every cascade call rewrites before it reads it) and
-// copies the result over the source
-int gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, hipStream_t st)
-{
-    if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
-    if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
-    const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
-    const bool in_place = d_dst == d_src;
-    if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
-    float* out = in_place ? ctx->pp[0] : d_dst;
-    launch_gauss5(d_src, out, rows, cols, batch, st);
-    DCMT_HIP(ctx, hipGetLastError());
-    if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
-    return DCMT_OK;
-}
-
-// The winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev: tags of generation g = (g << idx_bits) | index, g >= 1
-// (0 = the cleared plane); the index is N2's global point index or the reprojection's frame-local source pixel index.  A call only
-// looks at tags of its own generation, so the plane is not cleared between calls, whichever of the two they are.  It is cleared when
-// it is (re)allocated, when a call needs more index bits than its layout has, and when the generations run out.  n_px: entries
-// this call needs; n_index: it stores indices below n_index (N2 keeps its bound of <= n_index).  Any allocation happens here, before
-// the call has enqueued anything.  Returns the call's generation, shifted into place.
+// (dcmt_ctx.h)
 int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag)
 {
     int need_bits = 1;
@@ -794,33 +649,13 @@ int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st
     return DCMT_OK;
 }
 
-// dcmt_reproject_depth_dev: k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h, compiled in dcmt_cloud.hip) on the
-// winner plane above
-int reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
-                        float* d_out, int out_rows, int out_cols, hipStream_t st)
+void frame_chunks(uint32_t n, uint32_t* chunks, uint32_t* groups)
 {
-    if (!ctx || !d_depth || !d_out || !params) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
-    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
-    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
-    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
-    for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
-    for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
-    const size_t src_px = (size_t)rows * cols, dst_px = (size_t)out_rows * out_cols;
-    if (plan::ranges_overlap((uintptr_t)d_depth, sizeof(float) * src_px * batch, (uintptr_t)d_out, sizeof(float) * dst_px * batch)) return DCMT_E_INVALID;
-    ReprojK k;
-    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
-    std::memcpy(k.M, params->M, sizeof k.M);
-    std::memcpy(k.K, params->K, sizeof k.K);
-    unsigned gen_tag = 0;
-    const int rc = winner_generation(ctx, dst_px * batch, src_px, st, &gen_tag);
-    if (rc != DCMT_OK) return rc;
-    launch_reproject(d_depth, rows, cols, batch, k, ctx->winner, gen_tag, ctx->winner_bits, d_out, out_rows, out_cols, st);
-    DCMT_HIP(ctx, hipGetLastError());
-    return DCMT_OK;
+    *chunks = eval_chunks(n);
+    *groups = eval_chunk_groups(n);
 }
 
-}  // namespace
+}  // namespace dcmt
 
 extern "C" {
 
@@ -1080,49 +915,6 @@ void dcmt_colormap_jet(uint8_t bgr[768])
     }
 }
 
-void dcmt_default_cloud_params(dcmt_cloud_params* p)
-{
-    if (!p) return;
-    p->fx = 9.597910e+02;   // main_sl.cpp:927-930
-    p->fy = 9.569251e+02;
-    p->cx = 6.960217e+02;
-    p->cy = 2.241806e+02;
-}
-
-int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
-                            const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
-{
-    DCMT_ON_DEVICE(ctx);
-    return depth_to_cloud_dev(ctx, d_depth, d_bgr, rows, cols, batch, params, d_points, capacity, d_offsets, (hipStream_t)stream);
-}
-
-int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, void* stream)
-{
-    DCMT_ON_DEVICE(ctx);
-    return gaussian5_dev(ctx, d_src, d_dst, rows, cols, batch, (hipStream_t)stream);
-}
-
-void dcmt_default_reproject_params(dcmt_reproject_params* p)
-{
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->fx = 9.597910e+02;   // main_sl.cpp:969-972
-    p->fy = 9.569251e+02;
-    p->cx = 6.960217e+02;
-    p->cy = 2.241806e+02;
-    p->M[0] = p->M[5] = p->M[10] = p->M[15] = 1.0f;
-    p->K[0] = 9.597910e+02f; p->K[2] = 6.960217e+02f;     // camera_mat, :974-976
-    p->K[4] = 9.569251e+02f; p->K[5] = 2.241806e+02f;
-    p->K[8] = 1.0f;
-}
-
-int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
-                             float* d_out, int out_rows, int out_cols, void* stream)
-{
-    DCMT_ON_DEVICE(ctx);
-    return reproject_depth_dev(ctx, d_depth, rows, cols, batch, params, d_out, out_rows, out_cols, (hipStream_t)stream);
-}
-
 int dcmt_slic_num_centers(int rows, int cols, int step)
 {
     if (rows < 1 || cols < 1 || step < 1) return 0;
@@ -1197,201 +989,6 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
     }
     if (d_centers)       // ten iterations: the final centres are back in buffer 0
         DCMT_HIP(ctx, hipMemcpyAsync(d_centers, ctx->slic_centers[0], sizeof(double) * 5 * (size_t)n * batch, hipMemcpyDeviceToDevice, st));
-    return DCMT_OK;
-}
-
-// ---- host variants of N2 / N3 / N4: temporary device buffers, synchronous ----------------------------------------
-namespace {
-struct DevBuf {                                    // freed when the call returns, whatever path it takes
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(dcmt_ctx* ctx, size_t bytes) { DCMT_HIP(ctx, hipMalloc(&p, bytes ? bytes : 1)); return DCMT_OK; }
-};
-int host_stream(dcmt_ctx* ctx, hipStream_t* st)
-{
-    if (!ctx->own_stream) DCMT_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
-    *st = ctx->own_stream;
-    return DCMT_OK;
-}
-}  // namespace
-
-int dcmt_project_points(dcmt_ctx* ctx, const float* points, int n_points, const float T[16], const float P[12],
-                        float* sparse, size_t srs, int rows, int cols)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !sparse || !T || !P || n_points < 0 || (n_points > 0 && !points) || rows < 1 || cols < 1) return DCMT_E_INVALID;
-    if (srs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf dp, doff, dout;
-    const size_t row_b = sizeof(float) * (size_t)cols;
-    if ((rc = dp.alloc(ctx, sizeof(float) * 4 * (size_t)n_points)) != DCMT_OK || (rc = doff.alloc(ctx, sizeof(int32_t) * 2)) != DCMT_OK ||
-        (rc = dout.alloc(ctx, row_b * rows)) != DCMT_OK) return rc;
-    const int32_t off[2] = {0, n_points};
-    if (n_points) DCMT_HIP(ctx, hipMemcpyAsync(dp.p, points, sizeof(float) * 4 * (size_t)n_points, hipMemcpyHostToDevice, st));
-    DCMT_HIP(ctx, hipMemcpyAsync(doff.p, off, sizeof(off), hipMemcpyHostToDevice, st));
-    rc = dcmt_project_points_dev(ctx, (const float*)dp.p, (const int32_t*)doff.p, n_points, 1, T, P, (float*)dout.p, rows, cols, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(sparse, srs, dout.p, row_b, row_b, rows, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_slic_labels(dcmt_ctx* ctx, const uint8_t* lab, size_t lrs, int rows, int cols, int step, int nc, int32_t* labels, double* centers)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !lab || !labels || rows < 1 || cols < 1 || lrs < 3 * (size_t)cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    const int n = dcmt_slic_num_centers(rows, cols, step);
-    DevBuf dl, dlab, dc;
-    const size_t row_b = 3 * (size_t)cols, px = (size_t)rows * cols;
-    if ((rc = dl.alloc(ctx, row_b * rows)) != DCMT_OK || (rc = dlab.alloc(ctx, sizeof(int32_t) * px)) != DCMT_OK ||
-        (rc = dc.alloc(ctx, sizeof(double) * 5 * (size_t)(n > 0 ? n : 1))) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dl.p, row_b, lab, lrs, row_b, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_slic_labels_dev(ctx, (const uint8_t*)dl.p, rows, cols, 1, step, nc, (int32_t*)dlab.p, centers ? (double*)dc.p : nullptr, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpyAsync(labels, dlab.p, sizeof(int32_t) * px, hipMemcpyDeviceToHost, st));
-    if (centers && n > 0) DCMT_HIP(ctx, hipMemcpyAsync(centers, dc.p, sizeof(double) * 5 * (size_t)n, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_stereo_refine(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs,
-                       float* refined, size_t ors, int rows, int cols, const dcmt_stereo_params* params)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !depth || !left || !right || !refined || !params || rows < 1 || cols < 1) return DCMT_E_INVALID;
-    if (drs < sizeof(float) * (size_t)cols || ors < sizeof(float) * (size_t)cols || lrs < (size_t)cols || rrs < (size_t)cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf dd, dl, dr, dout;
-    const size_t frow = sizeof(float) * (size_t)cols, brow = (size_t)cols;
-    if ((rc = dd.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dl.alloc(ctx, brow * rows)) != DCMT_OK || (rc = dr.alloc(ctx, brow * rows)) != DCMT_OK ||
-        (rc = dout.alloc(ctx, frow * rows)) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dd.p, frow, depth, drs, frow, rows, hipMemcpyHostToDevice, st));
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dl.p, brow, left, lrs, brow, rows, hipMemcpyHostToDevice, st));
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dr.p, brow, right, rrs, brow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_stereo_refine_dev(ctx, (const float*)dd.p, (const uint8_t*)dl.p, (const uint8_t*)dr.p, (float*)dout.p, rows, cols, 1, params, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(refined, ors, dout.p, frow, frow, rows, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred, size_t prs, int rows, int cols, float thresh, int mode,
-                  dcmt_eval_frame* out)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !gt || !pred || !out || rows < 1 || cols < 1) return DCMT_E_INVALID;
-    if (grs < sizeof(float) * (size_t)cols || prs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
-    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf dg, dp, dout;
-    const size_t frow = sizeof(float) * (size_t)cols;
-    if ((rc = dg.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dp.alloc(ctx, frow * rows)) != DCMT_OK ||
-        (rc = dout.alloc(ctx, sizeof(dcmt_eval_frame))) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dg.p, frow, gt, grs, frow, rows, hipMemcpyHostToDevice, st));
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dp.p, frow, pred, prs, frow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_evaluate_dev(ctx, (const float*)dg.p, (const float*)dp.p, rows, cols, 1, thresh, mode, (dcmt_eval_frame*)dout.p, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpyAsync(out, dout.p, sizeof(dcmt_eval_frame), hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_colorize(dcmt_ctx* ctx, const float* src, size_t srs, int rows, int cols, uint8_t* bgr, size_t ors)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !src || !bgr || rows < 1 || cols < 1) return DCMT_E_INVALID;
-    if (srs < sizeof(float) * (size_t)cols || ors < 3 * (size_t)cols) return DCMT_E_INVALID;
-    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf ds, dout;
-    const size_t frow = sizeof(float) * (size_t)cols, brow = 3 * (size_t)cols;
-    if ((rc = ds.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, brow * rows)) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(ds.p, frow, src, srs, frow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_colorize_dev(ctx, (const float*)ds.p, rows, cols, 1, (uint8_t*)dout.p, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(bgr, ors, dout.p, brow, brow, rows, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_depth_to_cloud(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_t* bgr, size_t brs, int rows, int cols,
-                        const dcmt_cloud_params* params, dcmt_cloud_point* points, int64_t capacity, int64_t* n_points)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !depth || !points || !n_points || !params || rows < 1 || cols < 1 || capacity < 0) return DCMT_E_INVALID;
-    if (drs < sizeof(float) * (size_t)cols || (bgr && brs < 3 * (size_t)cols)) return DCMT_E_INVALID;
-    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf dd, dc, dp, doff;
-    const size_t frow = sizeof(float) * (size_t)cols, brow = 3 * (size_t)cols;
-    const int64_t room = std::min<int64_t>(capacity, (int64_t)rows * cols);         // a frame never has more records than pixels
-    if ((rc = dd.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dp.alloc(ctx, sizeof(dcmt_cloud_point) * (size_t)room)) != DCMT_OK ||
-        (rc = doff.alloc(ctx, sizeof(int32_t) * 2)) != DCMT_OK || (bgr && (rc = dc.alloc(ctx, brow * rows)) != DCMT_OK)) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dd.p, frow, depth, drs, frow, rows, hipMemcpyHostToDevice, st));
-    if (bgr) DCMT_HIP(ctx, hipMemcpy2DAsync(dc.p, brow, bgr, brs, brow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_depth_to_cloud_dev(ctx, (const float*)dd.p, bgr ? (const uint8_t*)dc.p : nullptr, rows, cols, 1, params,
-                                 (dcmt_cloud_point*)dp.p, room, (int32_t*)doff.p, st);
-    if (rc != DCMT_OK) return rc;
-    int32_t off[2] = {0, 0};
-    DCMT_HIP(ctx, hipMemcpyAsync(off, doff.p, sizeof(off), hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    const int64_t have = std::min<int64_t>(off[1], room);
-    if (have > 0) DCMT_HIP(ctx, hipMemcpy(points, dp.p, sizeof(dcmt_cloud_point) * (size_t)have, hipMemcpyDeviceToHost));
-    *n_points = off[1];
-    return DCMT_OK;
-}
-
-int dcmt_gaussian5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size_t drs, int rows, int cols)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !src || !dst || rows < 1 || cols < 1) return DCMT_E_INVALID;
-    if (srs < sizeof(float) * (size_t)cols || drs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
-    if (rows > ctx->max_rows || cols > ctx->max_cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf ds, dout;
-    const size_t frow = sizeof(float) * (size_t)cols;
-    if ((rc = ds.alloc(ctx, frow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, frow * rows)) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(ds.p, frow, src, srs, frow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_gaussian5_dev(ctx, (const float*)ds.p, (float*)dout.p, rows, cols, 1, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dst, drs, dout.p, frow, frow, rows, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return DCMT_OK;
-}
-
-int dcmt_reproject_depth(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_reproject_params* params,
-                         float* out, size_t ors, int out_rows, int out_cols)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !depth || !out || !params || rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1) return DCMT_E_INVALID;
-    if (drs < sizeof(float) * (size_t)cols || ors < sizeof(float) * (size_t)out_cols) return DCMT_E_INVALID;
-    if (rows > ctx->max_rows || cols > ctx->max_cols || out_rows > ctx->max_rows || out_cols > ctx->max_cols) return DCMT_E_INVALID;
-    hipStream_t st;
-    int rc = host_stream(ctx, &st);
-    if (rc != DCMT_OK) return rc;
-    DevBuf dd, dout;
-    const size_t srow = sizeof(float) * (size_t)cols, orow = sizeof(float) * (size_t)out_cols;
-    if ((rc = dd.alloc(ctx, srow * rows)) != DCMT_OK || (rc = dout.alloc(ctx, orow * out_rows)) != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(dd.p, srow, depth, drs, srow, rows, hipMemcpyHostToDevice, st));
-    rc = dcmt_reproject_depth_dev(ctx, (const float*)dd.p, rows, cols, 1, params, (float*)dout.p, out_rows, out_cols, st);
-    if (rc != DCMT_OK) return rc;
-    DCMT_HIP(ctx, hipMemcpy2DAsync(out, ors, dout.p, orow, orow, out_rows, hipMemcpyDeviceToHost, st));
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
     return DCMT_OK;
 }
 

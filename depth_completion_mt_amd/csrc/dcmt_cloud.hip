@@ -1,52 +1,129 @@
-// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h and dcmt_kernels_reproject.h and their launchers (dcmt_cloud.h); the entry
-// points that call them, dcmt_depth_to_cloud*, dcmt_gaussian5* and dcmt_reproject_depth*, are in dcmt.hip with every other entry point.
+// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h and dcmt_kernels_reproject.h, a code object of their own, and the entry
+// points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev and the defaults of their
+// parameter structs.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// are in dcmt_host.hip.
+#include <algorithm>
+
+#include "dcmt_ctx.h"
 #include "dcmt_kernels_cloud.h"
 #include "dcmt_kernels_reproject.h"
 
-namespace dcmt {
+using namespace dcmt;
 
-void launch_depth_to_cloud(const float* depth, const uint8_t* bgr, uint32_t n, uint32_t cols, uint32_t chunks, uint32_t groups,
-                           uint32_t batch, const CloudK& k, uint32_t* slab, void* points, uint32_t capacity, int32_t* offsets,
-                           hipStream_t st)
+extern "C" {
+
+void dcmt_default_cloud_params(dcmt_cloud_params* p)
 {
-    const dim3 grid(chunks, batch);
-    const uint32_t per = chunks * kCloudWaves;
-    hipLaunchKernelGGL(k_cloud_count, grid, dim3(kCloudThreads), 0, st, depth, n, groups, slab);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, slab, per * batch, per, batch, offsets);
-    if (bgr)
-        hipLaunchKernelGGL(k_cloud_scatter<true>, grid, dim3(kCloudThreads), 0, st, depth, bgr, n, groups, cols, k, slab,
-                           reinterpret_cast<uint4*>(points), capacity);
-    else
-        hipLaunchKernelGGL(k_cloud_scatter<false>, grid, dim3(kCloudThreads), 0, st, depth, bgr, n, groups, cols, k, slab,
-                           reinterpret_cast<uint4*>(points), capacity);
+    if (!p) return;
+    p->fx = 9.597910e+02;   // main_sl.cpp:927-930
+    p->fy = 9.569251e+02;
+    p->cx = 6.960217e+02;
+    p->cy = 2.241806e+02;
 }
 
-void launch_gauss5(const float* src, float* dst, int rows, int cols, int batch, hipStream_t st)
+// per-wave counts, their exclusive scan in one workgroup, then the scatter (dcmt_kernels_cloud.h)
+int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                            const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
 {
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_depth || !d_points || !d_offsets || !params) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
+    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
+    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
+    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols, room = (uint32_t)std::min<int64_t>(capacity, INT32_MAX);
+    uint32_t chunks, groups;
+    frame_chunks(n, &chunks, &groups);
+    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
+    const dim3 grid(chunks, batch);
+    const uint32_t per = chunks * kCloudWaves;      // slab: [batch][chunks][kCloudWaves] uint32
+    uint4* points = reinterpret_cast<uint4*>(d_points);
+    hipLaunchKernelGGL(k_cloud_count, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, ctx->cloud_slab);
+    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, ctx->cloud_slab, per * (uint32_t)batch, per, (uint32_t)batch, d_offsets);
+    if (d_bgr)
+        hipLaunchKernelGGL(k_cloud_scatter<true>, grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, k, ctx->cloud_slab, points, room);
+    else
+        hipLaunchKernelGGL(k_cloud_scatter<false>, grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, k, ctx->cloud_slab, points, room);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// one streaming kernel (k_gauss5, dcmt_kernels_cloud.h), whose src and dst must not overlap: an in-place call writes to pp[0]
+// (scratch every cascade call rewrites before it reads it) and copies the result over the source
+int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
+    const bool in_place = d_dst == d_src;
+    if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
+    float* out = in_place ? ctx->pp[0] : d_dst;
     const int strips = (cols + kGaussCols - 1) / kGaussCols;
     int band_rows = kGaussRows;                      // shorter bands while the call makes fewer than ~2 waves per SIMD
     while (band_rows > 8 && (size_t)strips * ((rows + band_rows - 1) / band_rows) * batch < 2048) band_rows /= 2;
     const int bands = (rows + band_rows - 1) / band_rows;
-    hipLaunchKernelGGL(k_gauss5, dim3((unsigned)(((size_t)strips * bands + 3) / 4), batch), dim3(256), 0, st, src, dst, rows, cols, strips, bands,
+    hipLaunchKernelGGL(k_gauss5, dim3((unsigned)(((size_t)strips * bands + 3) / 4), batch), dim3(256), 0, st, d_src, out, rows, cols, strips, bands,
                        band_rows);
+    DCMT_HIP(ctx, hipGetLastError());
+    if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
 }
 
-void launch_reproject(const float* depth, int rows, int cols, int batch, const ReprojK& k, unsigned* winner, unsigned gen_tag, int idx_bits,
-                      float* out, int out_rows, int out_cols, hipStream_t st)
+void dcmt_default_reproject_params(dcmt_reproject_params* p)
 {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->fx = 9.597910e+02;   // main_sl.cpp:969-972
+    p->fy = 9.569251e+02;
+    p->cx = 6.960217e+02;
+    p->cy = 2.241806e+02;
+    p->M[0] = p->M[5] = p->M[10] = p->M[15] = 1.0f;
+    p->K[0] = 9.597910e+02f; p->K[2] = 6.960217e+02f;     // camera_mat, :974-976
+    p->K[4] = 9.569251e+02f; p->K[5] = 2.241806e+02f;
+    p->K[8] = 1.0f;
+}
+
+// k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h) on the context's winner plane (winner_generation, dcmt_ctx.h)
+int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                             float* d_out, int out_rows, int out_cols, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_depth || !d_out || !params) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
+    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
+    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
+    for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, dst_n = (uint32_t)out_rows * (uint32_t)out_cols;
     const size_t n_px = (size_t)batch * dst_n;
-    hipLaunchKernelGGL(k_reproject_scatter, dim3((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch), dim3(256), 0, st, depth, n,
-                       (uint32_t)cols, k, winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
-    if (n_px % 4 == 0 && (uintptr_t)out % 16 == 0)
-        hipLaunchKernelGGL(k_reproject_resolve<4>, dim3((unsigned)((n_px / 4 + 255) / 256)), dim3(256), 0, st, depth, n, (uint32_t)cols, k, winner,
-                           out, dst_n, n_px, gen_tag, idx_bits);
-    else if (n_px % 2 == 0 && (uintptr_t)out % 8 == 0)
-        hipLaunchKernelGGL(k_reproject_resolve<2>, dim3((unsigned)((n_px / 2 + 255) / 256)), dim3(256), 0, st, depth, n, (uint32_t)cols, k, winner,
-                           out, dst_n, n_px, gen_tag, idx_bits);
+    if (plan::ranges_overlap((uintptr_t)d_depth, sizeof(float) * n * batch, (uintptr_t)d_out, sizeof(float) * n_px)) return DCMT_E_INVALID;
+    ReprojK k;
+    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
+    std::memcpy(k.M, params->M, sizeof k.M);
+    std::memcpy(k.K, params->K, sizeof k.K);
+    unsigned gen_tag = 0;
+    const int rc = winner_generation(ctx, n_px, n, st, &gen_tag);
+    if (rc != DCMT_OK) return rc;
+    hipLaunchKernelGGL(k_reproject_scatter, dim3((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch), dim3(256), 0, st, d_depth, n,
+                       (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
+    if (n_px % 4 == 0 && (uintptr_t)d_out % 16 == 0)
+        hipLaunchKernelGGL(k_reproject_resolve<4>, dim3((unsigned)((n_px / 4 + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
+                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+    else if (n_px % 2 == 0 && (uintptr_t)d_out % 8 == 0)
+        hipLaunchKernelGGL(k_reproject_resolve<2>, dim3((unsigned)((n_px / 2 + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
+                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
     else
-        hipLaunchKernelGGL(k_reproject_resolve<1>, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, depth, n, (uint32_t)cols, k, winner,
-                           out, dst_n, n_px, gen_tag, idx_bits);
+        hipLaunchKernelGGL(k_reproject_resolve<1>, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
+                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
 }
 
-}  // namespace dcmt
+}  // extern "C"
