@@ -1,13 +1,12 @@
 // dcmt.hip -- implementation of the C ABI in include/dcmt.h on gfx950 (MI355X).
 //
-// Host side of the hot path: context (device scratch owned per GPU), launch sequencing of
-// the kernels in dcmt_kernels_v1.h / dcmt_kernels_fused.h, and the host<->device copies of
-// the cv::Mat entry point.  No PyTorch, no OpenCV, no CPU fallback: if there is no gfx950
+// Host side of the hot path: context (device scratch owned per GPU) and launch sequencing of
+// the kernels in dcmt_kernels_v1.h / dcmt_kernels_fused.h.  No PyTorch, no OpenCV, no CPU fallback: if there is no gfx950
 // device every entry point fails with DCMT_E_NO_DEVICE / DCMT_E_HIP.
 //
 // The rest of the ABI is in two more translation units over dcmt_ctx.h (the context and the checks every entry point starts with):
-// dcmt_cloud.hip (point cloud, unmasked Gaussian, reprojection: kernels and *_dev entry points) and dcmt_host.hip (the synchronous
-// single-frame host variants of the *_dev calls).  Host code may move between them; a kernel and the function that launches it stay
+// dcmt_cloud.hip (point cloud, unmasked Gaussian, reprojection: kernels and *_dev entry points) and dcmt_host.hip (every synchronous
+// host entry point: the host<->device copies around a device call).  Host code may move between them; a kernel and the function that launches it stay
 // where they are, in their order: both decide what the compiler emits for every other kernel of the code object.
 #include <hip/hip_runtime.h>
 
@@ -66,47 +65,17 @@ uint32_t k0_bits(const uint8_t k0[25])
     return b;
 }
 
-int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p)
+// The label stage's bounding boxes, per (frame, label): two tables, grown on demand and together
+int ensure_bbox(dcmt_ctx* ctx, size_t need, hipStream_t st)
 {
-    if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
-    if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
-    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN) return DCMT_E_INVALID;
-    if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;
-    if (p->spec_fill_iters < 0 || p->spec_fill_iters > kMaxIters) return DCMT_E_INVALID;
-    const bool norm = (p->flags & DCMT_FLAG_NORMALIZE) != 0;
-    if (p->stop_after < (norm ? DCMT_STAGE_NORMALIZE : DCMT_STAGE_INVERT) || p->stop_after > DCMT_STAGE_FINAL) return DCMT_E_INVALID;
-    if (norm && !(finite_bits(p->norm_lo) && finite_bits(p->norm_hi))) return DCMT_E_INVALID;
-    if (k0_bits(p->k0) == 0) return DCMT_E_INVALID;
-    return DCMT_OK;
-}
-
-// Scratch only one of the paths uses is allocated by the first call whose plan names it (never again afterwards) -- before anything
-// of the call is enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.  The column
-// statistics of the staged tile kernels, the 16-bit plane of k_pre_p<Q16OUT> -> k_fp_q, the label stage's bounding boxes.
-int ensure_colstat(dcmt_ctx* ctx)
-{
-    if (!ctx->colstat)
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->colstat, sizeof(int) * 2 * (size_t)ctx->max_cols * ((ctx->max_rows + FTH_FEW - 1) / FTH_FEW) * ctx->max_batch));
-    return DCMT_OK;
-}
-int ensure_x6q(dcmt_ctx* ctx)
-{
-    if (!ctx->x6q) DCMT_HIP(ctx, hipMalloc((void**)&ctx->x6q, sizeof(unsigned short) * ctx->frame_elems * (size_t)ctx->max_batch + 16));
-    return DCMT_OK;
-}
-int ensure_bbox(dcmt_ctx* ctx, size_t need, hipStream_t st)     // per (frame, label) bounding boxes, grown on demand
-{
-    if (need <= ctx->bb_ints) return DCMT_OK;
-    (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max);
-    ctx->bb_min = ctx->bb_max = nullptr; ctx->bb_ints = 0;
-    DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_min, sizeof(int) * need));
-    DCMT_HIP(ctx, hipMalloc((void**)&ctx->bb_max, sizeof(int) * need));
-    ctx->bb_ints = need;
+    bool fresh = false;
+    DCMT_TRY(ctx->bb_min.reserve(ctx, need, &fresh));
+    DCMT_TRY(ctx->bb_max.reserve(ctx, need, &fresh));
+    if (!fresh) return DCMT_OK;
     // "no box" everywhere, once: the label stage's waves put every entry they have read back into this state (a fill in front
     // of every call is two dependent operations with a bubble behind the previous call's last kernel each)
-    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * need, st));
-    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * need, st));
+    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_min, 0x7f, sizeof(int) * ctx->bb_min.n, st));
+    DCMT_HIP(ctx, hipMemsetAsync(ctx->bb_max, 0xff, sizeof(int) * ctx->bb_max.n, st));
     return DCMT_OK;
 }
 
@@ -135,38 +104,19 @@ int k0_preset(uint32_t kb)
     return -1;
 }
 
-// f(kind) with the k0 preset (a k0_preset result >= 0) as a compile-time constant
-template <typename F>
-void with_k0(int k0kind, F f)
-{
-    if (k0kind == K0_AS_COMPILED) f(std::integral_constant<int, K0_AS_COMPILED>{});
-    else f(std::integral_constant<int, K0_DIAMOND>{});
-}
+// with_value (dcmt_ctx.h): f(kind) with the k0 preset (a k0_preset result >= 0) as a compile-time constant, f(flag) with a bool,
+// f(tile height) with the staged kernels' FTH_FEW or TH
+template <typename F> void with_k0(int k0kind, F f) { with_value<(int)K0_AS_COMPILED, (int)K0_DIAMOND>(k0kind, f); }
+template <typename F> void with_bool(bool b, F f) { with_value<true, false>(b, f); }
+template <typename F> void with_tile_h(bool few, F f) { with_value<FTH_FEW, TH>(few ? FTH_FEW : TH, f); }
 
-// likewise f(flag) with a bool, f(tile height) with the staged kernels' FTH_FEW or TH
-template <typename F>
-void with_bool(bool b, F f)
+// The hole counters of the first `batch` frames, as they are once `st` has run dry, in ctx->h_counters
+int read_counters(dcmt_ctx* ctx, hipStream_t st, int batch)
 {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
+    DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride, hipMemcpyDeviceToHost, st));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return DCMT_OK;
 }
-template <typename F>
-void with_tile_h(bool few, F f)
-{
-    if (few) f(std::integral_constant<int, FTH_FEW>{});
-    else f(std::integral_constant<int, TH>{});
-}
-
-// What a completion call is given: device pointers (src or src16; labels only where they are used) and the batch's shape
-struct Frames {
-    const float* src;
-    const uint16_t* src16;
-    float in_scale;
-    const int32_t* labels;
-    int n_labels;
-    float* dst;
-    int rows, cols, batch;
-};
 
 // The hole-closure loop shared by both paths.  `launch_app(i)` enqueues application i
 // (reads pp[(i-1)&1], writes pp[i&1], skips frames without holes).  Returns the number of
@@ -180,9 +130,7 @@ int fill_loop(dcmt_ctx* ctx, int batch, const dcmt_params* p, hipStream_t st, bo
         // i-1, fills them (application i: a no-op when there are none) and stops when it saw
         // none; the cap bounds i.
         for (int i = 1;; ++i) {
-            DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride,
-                                         hipMemcpyDeviceToHost, st));
-            DCMT_HIP(ctx, hipStreamSynchronize(st));
+            DCMT_TRY(read_counters(ctx, st, batch));
             bool any = false;
             for (int f = 0; f < batch; ++f) {
                 const int n_i = ctx->h_counters[(size_t)f * kCntStride + i];   // [1 + (i-1)]
@@ -269,7 +217,7 @@ int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, cons
         qbad = ctx->q16_bad + ctx->q16_attempts % kQ16Flags;
         int* qnext = ctx->q16_bad + (ctx->q16_attempts + 1) % kQ16Flags;
         ++ctx->q16_attempts;
-        with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q), qbad, nullptr, qnext); });
+        with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q.p), qbad, nullptr, qnext); });
     } else if (pl.pair) {
         with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::false_type{}, o6, nullptr, nullptr, nullptr); });
     } else {
@@ -322,8 +270,7 @@ int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, cons
             apps = n_redo;
         } else if (n_redo > 0) {
             {                     // host entry points: look before launching anything else
-                DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)batch * kCntStride, hipMemcpyDeviceToHost, st));
-                DCMT_HIP(ctx, hipStreamSynchronize(st));
+                DCMT_TRY(read_counters(ctx, st, batch));
                 bool any = false;
                 for (int f = 0; f < batch; ++f) any |= ctx->h_counters[(size_t)f * kCntStride + 1] > 0;
                 if (!any) { if (p->verbose) for (int f = 0; f < batch; ++f) std::printf("0\n"); return DCMT_OK; }
@@ -391,10 +338,13 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && q16_allowed_now(ctx);
     const plan::Plan pl = plan::plan_call(ctx->knobs, c);
 
-    int erc = DCMT_OK;
-    if (pl.needs_x6q && (erc = ensure_x6q(ctx)) != DCMT_OK) return erc;
-    if (pl.needs_colstat && (erc = ensure_colstat(ctx)) != DCMT_OK) return erc;
-    if (pl.needs_bbox && (erc = ensure_bbox(ctx, (size_t)batch * fr.n_labels * 2, st)) != DCMT_OK) return erc;
+    // Scratch only one of the paths uses is allocated by the first call whose plan names it (never again afterwards) -- before anything
+    // of the call is enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.  The 16-bit
+    // plane of k_pre_p<Q16OUT> -> k_fp_q (and 16 bytes of slack), the column statistics of the staged tile kernels, the label stage's
+    // bounding boxes.
+    if (pl.needs_x6q) DCMT_TRY(ctx->x6q.reserve(ctx, ctx->frame_elems * (size_t)ctx->max_batch + 16 / sizeof(unsigned short)));
+    if (pl.needs_colstat) DCMT_TRY(ctx->colstat.reserve(ctx, 2 * (size_t)ctx->max_cols * ((ctx->max_rows + FTH_FEW - 1) / FTH_FEW) * ctx->max_batch));
+    if (pl.needs_bbox) DCMT_TRY(ensure_bbox(ctx, (size_t)batch * fr.n_labels * 2, st));
     begin_call(ctx, st, batch, pl.path);
     if (ctx->timing && ctx->tev[0]) (void)hipEventRecord(ctx->tev[0], st);
 
@@ -425,12 +375,10 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
         const int n_labels = fr.n_labels;
         float* x4 = pl.route == plan::Route::LABEL_PROBE ? out : ctx->pp[0];
         const dim3 bg((cols + 63) / 64, (rows + kBboxRows - 1) / kBboxRows, batch);
-        if (pl.bbox_lds)
-            hipLaunchKernelGGL(k_label_bbox<true>, bg, dim3(256), sizeof(int) * 4 * (size_t)n_labels, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
-                               rows, cols, p->max_depth, p->valid_thresh, coef);
-        else
-            hipLaunchKernelGGL(k_label_bbox<false>, bg, dim3(256), 0, st, d_src, d_labels, n_labels, ctx->bb_min, ctx->bb_max, x4,
-                               rows, cols, p->max_depth, p->valid_thresh, coef);
+        with_bool(pl.bbox_lds, [&](auto lds) {
+            hipLaunchKernelGGL(k_label_bbox<decltype(lds)::value>, bg, dim3(256), lds ? sizeof(int) * 4 * (size_t)n_labels : 0, st, d_src, d_labels, n_labels,
+                               ctx->bb_min, ctx->bb_max, x4, rows, cols, p->max_depth, p->valid_thresh, coef);
+        });
         const dim3 lg(pl.label_grid_x, batch);
         if (pl.lpair)
             with_k0(pl.k0kind, [&](auto kind) { with_bool(coef != nullptr, [&](auto norm) {
@@ -512,66 +460,6 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     return rc;
 }
 
-int ensure_host_staging(dcmt_ctx* ctx, bool labels)
-{
-    const size_t bytes = sizeof(float) * ctx->frame_elems * (size_t)ctx->max_batch;
-    if (!ctx->d_in) DCMT_HIP(ctx, hipMalloc((void**)&ctx->d_in, bytes));
-    if (!ctx->d_out) DCMT_HIP(ctx, hipMalloc((void**)&ctx->d_out, bytes));
-    if (labels && !ctx->d_lab) DCMT_HIP(ctx, hipMalloc((void**)&ctx->d_lab, bytes));
-    if (!ctx->own_stream) DCMT_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
-    return DCMT_OK;
-}
-
-int host_call(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int32_t* labels, size_t lrs, size_t lfs,
-              int n_labels, int use_superpixel, float* dst, size_t drs, size_t dfs, int rows, int cols, int batch,
-              const dcmt_params* p, bool force_gaussian)
-{
-    int rc = check_params(ctx, src, dst, rows, cols, batch, p);
-    if (rc != DCMT_OK) return rc;
-    if (srs < sizeof(float) * (size_t)cols || drs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
-    if (labels && lrs < sizeof(int32_t) * (size_t)cols) return DCMT_E_INVALID;
-    rc = ensure_host_staging(ctx, labels != nullptr);
-    if (rc != DCMT_OK) return rc;
-    hipStream_t st = ctx->own_stream;
-    const size_t row_b = sizeof(float) * (size_t)cols, frame_b = row_b * rows;
-    if (p->verbose == 1) {
-        // what img_completion prints before it starts (LO :29, :41-50): the dimensions and the largest input value (start value 0.0, :22)
-        std::printf("NUMERO ROWS, COLS: %d %d\n", rows, cols);
-        for (int f = 0; f < batch; ++f) {
-            float mx = 0.0f;
-            for (int r = 0; r < rows; ++r) {
-                const float* row = reinterpret_cast<const float*>(reinterpret_cast<const char*>(src) + f * sfs + r * srs);
-                for (int c = 0; c < cols; ++c) mx = row[c] > mx ? row[c] : mx;
-            }
-            std::printf("max range is%g\n", (double)mx);               // operator<<(float): six significant digits, as %g
-        }
-    }
-    for (int f = 0; f < batch; ++f) {
-        if (srs == row_b)      // contiguous rows (the usual cv::Mat): one linear copy instead of a pitched one
-            DCMT_HIP(ctx, hipMemcpyAsync((char*)ctx->d_in + f * frame_b, (const char*)src + f * sfs, frame_b, hipMemcpyHostToDevice, st));
-        else
-        DCMT_HIP(ctx, hipMemcpy2DAsync((char*)ctx->d_in + f * frame_b, row_b, (const char*)src + f * sfs, srs, row_b, rows,
-                                       hipMemcpyHostToDevice, st));
-        if (labels)
-            DCMT_HIP(ctx, hipMemcpy2DAsync((char*)ctx->d_lab + f * frame_b, row_b, (const char*)labels + f * lfs, lrs, row_b,
-                                           rows, hipMemcpyHostToDevice, st));
-    }
-    if (ctx->knobs.poison)   // DCMT_POISON=1: stale output can never pass for fresh output (tests)
-        DCMT_HIP(ctx, hipMemsetAsync(ctx->d_out, 0xFF, frame_b * (size_t)batch, st));
-    const Frames fr = {ctx->d_in, nullptr, 1.0f, labels && use_superpixel ? ctx->d_lab : nullptr, n_labels, ctx->d_out, rows, cols, batch};
-    const int chain_rc = run_chain(ctx, fr, p, force_gaussian, st, true);
-    if (chain_rc != DCMT_OK && chain_rc != DCMT_E_NOT_CONVERGED) return chain_rc;
-    for (int f = 0; f < batch; ++f) {
-        if (drs == row_b)
-            DCMT_HIP(ctx, hipMemcpyAsync((char*)dst + f * dfs, (const char*)ctx->d_out + f * frame_b, frame_b, hipMemcpyDeviceToHost, st));
-        else
-            DCMT_HIP(ctx, hipMemcpy2DAsync((char*)dst + f * dfs, drs, (const char*)ctx->d_out + f * frame_b, row_b, row_b, rows,
-                                           hipMemcpyDeviceToHost, st));
-    }
-    DCMT_HIP(ctx, hipStreamSynchronize(st));
-    return chain_rc;
-}
-
 // dcmt_evaluate_dev / dcmt_evaluate_u16_dev: checks, the slab on first use, then the two kernels (dcmt_kernels_eval.h)
 template <typename TG>
 int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_pred, int rows, int cols, int batch, float thresh,
@@ -582,8 +470,8 @@ int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_p
     if (!finite_bits(thresh) || thresh < 0.0f || !finite_bits(gt_scale)) return DCMT_E_INVALID;
     if (mode != DCMT_EVAL_GT && mode != DCMT_EVAL_BOTH) return DCMT_E_INVALID;
     if ((uintptr_t)d_out % 8 != 0) return DCMT_E_INVALID;
-    if (!ctx->eval_slab)     // sized for the largest call the ctx admits (eval_chunks grows with the frame size), before any launch
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->eval_slab, sizeof(double) * kEvalSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)ctx->max_batch));
+    // first use: sized for the largest call the ctx admits (eval_chunks grows with the frame size), before any launch
+    DCMT_TRY(ctx->eval_slab.reserve(ctx, (size_t)kEvalSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * ctx->max_batch));
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
     hipLaunchKernelGGL(k_eval_partial<TG>, dim3(chunks, batch), dim3(kEvalThreads), 0, st, d_gt, gt_scale, d_pred, n, thresh,
                        mode == DCMT_EVAL_BOTH ? 1 : 0, ctx->eval_slab);
@@ -614,10 +502,9 @@ int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batc
         const size_t lds = sizeof(uint32_t) * 256 + sizeof(float) * 2 * span;
         const dim3 grid((total + kColorPxPerWg - 1) / kColorPxPerWg);
         hipLaunchKernelGGL(k_color_minmax, dim3(chunks, nf), dim3(kColorThreads), 0, st, s, n, ctx->color_slab);
-        if ((uintptr_t)s % 16 == 0 && (uintptr_t)o % 4 == 0)
-            hipLaunchKernelGGL(k_color_map<true>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
-        else
-            hipLaunchKernelGGL(k_color_map<false>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
+        with_bool((uintptr_t)s % 16 == 0 && (uintptr_t)o % 4 == 0, [&](auto aligned) {
+            hipLaunchKernelGGL(k_color_map<decltype(aligned)::value>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
+        });
         DCMT_HIP(ctx, hipGetLastError());
     }
     return DCMT_OK;
@@ -628,21 +515,39 @@ int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batc
 namespace dcmt {
 
 // (dcmt_ctx.h)
+int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p)
+{
+    if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
+    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN) return DCMT_E_INVALID;
+    if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;
+    if (p->spec_fill_iters < 0 || p->spec_fill_iters > kMaxIters) return DCMT_E_INVALID;
+    const bool norm = (p->flags & DCMT_FLAG_NORMALIZE) != 0;
+    if (p->stop_after < (norm ? DCMT_STAGE_NORMALIZE : DCMT_STAGE_INVERT) || p->stop_after > DCMT_STAGE_FINAL) return DCMT_E_INVALID;
+    if (norm && !(finite_bits(p->norm_lo) && finite_bits(p->norm_hi))) return DCMT_E_INVALID;
+    if (k0_bits(p->k0) == 0) return DCMT_E_INVALID;
+    return DCMT_OK;
+}
+
+int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_gaussian, hipStream_t st)
+{
+    return run_chain(ctx, fr, p, force_gaussian, st, true);
+}
+
 int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag)
 {
     int need_bits = 1;
     while (need_bits < 31 && ((size_t)1 << need_bits) <= n_index) ++need_bits;
     if (need_bits > 30) return DCMT_E_INVALID;
-    if (n_px > ctx->winner_elems) {
-        (void)hipFree(ctx->winner); ctx->winner = nullptr; ctx->winner_elems = 0;
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->winner, sizeof(unsigned) * n_px));
-        ctx->winner_elems = n_px; ctx->winner_bits = 0; ctx->winner_gen = 0;
-    }
+    bool fresh = false;
+    DCMT_TRY(ctx->winner.reserve(ctx, n_px, &fresh));
+    if (fresh) { ctx->winner_bits = 0; ctx->winner_gen = 0; }
     const bool relayout = need_bits > ctx->winner_bits;
     if (relayout) ctx->winner_bits = need_bits < 24 ? 24 : need_bits;       // (room for 16 M indices per call before the next re-layout)
     const unsigned gen_max = (1u << (32 - ctx->winner_bits)) - 1u;
     if (relayout || ctx->winner_gen == 0 || ctx->winner_gen >= gen_max) {
-        DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner_elems, st));
+        DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner.n, st));
         ctx->winner_gen = 0;
     }
     *gen_tag = ++ctx->winner_gen << ctx->winner_bits;
@@ -734,31 +639,26 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     DeviceGuard dev_guard_(ctx);                    // allocate on the context's device, leave the caller's current device as it was
     auto fail = [&](int rc) { dcmt_destroy(ctx); return rc; };
     if (dev_guard_.rc != DCMT_OK) return fail(dev_guard_.rc);
-    const size_t plane = sizeof(float) * ctx->frame_elems * (size_t)max_batch;
+    const size_t plane = ctx->frame_elems * (size_t)max_batch;      // elements
     // two planes: X6 (x5) is dead once the first fill application of the hole-closure loop has read it, and that application writes pp[0], so
     // x5 shares pp[1] (the second application's output); X4 of the label-masked stage and the staged kernels' uint16 conversion live in
     // pp[0], which nothing writes before they have been read
-    if (hipMalloc((void**)&ctx->pp[0], plane) != hipSuccess) return fail(DCMT_E_NOMEM);
-    if (hipMalloc((void**)&ctx->pp[1], plane) != hipSuccess) return fail(DCMT_E_NOMEM);
+    auto mem = [&](auto& buf, size_t count) { return buf.reserve(ctx, count) == DCMT_OK; };     // (whatever HIP calls the failure: DCMT_E_NOMEM)
+    const size_t mb = (size_t)max_batch, chunks = eval_chunks((uint32_t)ctx->frame_elems);
+    if (!mem(ctx->pp[0], plane) || !mem(ctx->pp[1], plane)) return fail(DCMT_E_NOMEM);
     ctx->x5 = ctx->pp[1];
-    if (hipMalloc((void**)&ctx->counters, sizeof(int) * (size_t)kCntStride * max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
-    if (hipMalloc((void**)&ctx->q16_bad, sizeof(int) * kQ16Flags) != hipSuccess) return fail(DCMT_E_NOMEM);
+    if (!mem(ctx->counters, kCntStride * mb) || !mem(ctx->q16_bad, kQ16Flags)) return fail(DCMT_E_NOMEM);
     if (hipMemset(ctx->q16_bad, 0, sizeof(int) * kQ16Flags) != hipSuccess) return fail(DCMT_E_HIP);
-    if (hipHostMalloc((void**)&ctx->q16_seen, 64, hipHostMallocMapped) != hipSuccess) return fail(DCMT_E_NOMEM);
+    if (!mem(ctx->q16_seen, 64 / sizeof(int))) return fail(DCMT_E_NOMEM);
     *ctx->q16_seen = 0;
     if (hipHostGetDevicePointer((void**)&ctx->q16_seen_dev, ctx->q16_seen, 0) != hipSuccess) return fail(DCMT_E_HIP);
     // (first, last) table: one slot per frame and row band.  Bands are only chosen while frames x strips x bands stays near one
     // round of waves (plan_call), so frames x bands <= max_batch + kPreBandWaves; an explicit DCMT_BANDS may go up to kMaxBands each.
-    const size_t tb_slots = ctx->knobs.bands > 0 ? (size_t)max_batch * kMaxBands : std::min<size_t>((size_t)max_batch * kMaxBands, (size_t)max_batch + plan::kPreBandWaves);
-    if (hipMalloc((void**)&ctx->tb, sizeof(int) * 2 * (size_t)max_cols * tb_slots) != hipSuccess) return fail(DCMT_E_NOMEM);
-    if (hipMalloc((void**)&ctx->norm_stats, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
-    if (hipMemset(ctx->norm_stats, 0, sizeof(uint32_t) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_HIP);
-    if (hipMalloc((void**)&ctx->norm_coef, sizeof(float) * 2 * (size_t)max_batch) != hipSuccess) return fail(DCMT_E_NOMEM);
-    if (hipMalloc((void**)&ctx->color_slab, sizeof(float) * kColorSlabStride * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)max_batch) != hipSuccess)
-        return fail(DCMT_E_NOMEM);
-    if (hipMalloc((void**)&ctx->cloud_slab, sizeof(uint32_t) * kCloudWaves * eval_chunks((uint32_t)ctx->frame_elems) * (size_t)max_batch) != hipSuccess)
-        return fail(DCMT_E_NOMEM);
-    if (hipHostMalloc((void**)&ctx->h_counters, sizeof(int) * (size_t)kCntStride * max_batch, hipHostMallocDefault) != hipSuccess)
+    const size_t tb_slots = ctx->knobs.bands > 0 ? mb * kMaxBands : std::min<size_t>(mb * kMaxBands, mb + plan::kPreBandWaves);
+    if (!mem(ctx->tb, 2 * (size_t)max_cols * tb_slots) || !mem(ctx->norm_stats, 2 * mb)) return fail(DCMT_E_NOMEM);
+    if (hipMemset(ctx->norm_stats, 0, sizeof(uint32_t) * 2 * mb) != hipSuccess) return fail(DCMT_E_HIP);
+    if (!mem(ctx->norm_coef, 2 * mb) || !mem(ctx->color_slab, kColorSlabStride * chunks * mb) || !mem(ctx->cloud_slab, kCloudWaves * chunks * mb) ||
+        !mem(ctx->h_counters, kCntStride * mb))
         return fail(DCMT_E_NOMEM);
     *out = ctx;
     return DCMT_OK;
@@ -769,34 +669,8 @@ void dcmt_destroy(dcmt_ctx* ctx)
     if (!ctx) return;
     DeviceGuard dev_guard_(ctx);
     if (ctx->own_stream) { (void)hipStreamSynchronize(ctx->own_stream); (void)hipStreamDestroy(ctx->own_stream); }
-    (void)hipFree(ctx->pp[0]); (void)hipFree(ctx->pp[1]);
-    (void)hipFree(ctx->colstat); (void)hipFree(ctx->counters); (void)hipFree(ctx->tb);
-    (void)hipFree(ctx->x6q); (void)hipFree(ctx->q16_bad); if (ctx->q16_seen) (void)hipHostFree(ctx->q16_seen);
-    (void)hipFree(ctx->norm_stats); (void)hipFree(ctx->norm_coef);
-    (void)hipFree(ctx->d_in); (void)hipFree(ctx->d_out); (void)hipFree(ctx->d_lab);
-    (void)hipFree(ctx->bb_min); (void)hipFree(ctx->bb_max); (void)hipFree(ctx->winner);
-    (void)hipFree(ctx->slic_cells); (void)hipFree(ctx->slic_centers[0]); (void)hipFree(ctx->slic_centers[1]);
-    (void)hipFree(ctx->slic_sums); (void)hipFree(ctx->eval_slab); (void)hipFree(ctx->color_slab); (void)hipFree(ctx->cloud_slab);
-    if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     for (auto e : ctx->tev) if (e) (void)hipEventDestroy(e);
-    delete ctx;
-}
-
-int dcmt_complete_f32(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, float* dst, size_t drs, size_t dfs,
-                      int rows, int cols, int batch, const dcmt_params* params)
-{
-    DCMT_ON_DEVICE(ctx);
-    return host_call(ctx, src, srs, sfs, nullptr, 0, 0, 0, 0, dst, drs, dfs, rows, cols, batch, params, false);
-}
-
-int dcmt_complete_labeled_f32(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int32_t* labels, size_t lrs,
-                              size_t lfs, int n_labels, float* dst, size_t drs, size_t dfs, int rows, int cols, int batch,
-                              const dcmt_params* params, int use_superpixel)
-{
-    DCMT_ON_DEVICE(ctx);
-    if (!labels) return DCMT_E_INVALID;
-    return host_call(ctx, src, srs, sfs, labels, lrs, lfs, n_labels, use_superpixel, dst, drs, dfs, rows, cols, batch,
-                     params, true);
+    delete ctx;                                     // every buffer frees itself, on the context's device: the guard outlives them
 }
 
 int dcmt_complete_f32_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch,
@@ -847,12 +721,11 @@ int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t*
     if (n_points > 0)
         hipLaunchKernelGGL(k_project_scatter, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, M,
                            winner, rows, cols, gen_tag);
-    if (n_px % 4 == 0 && (uintptr_t)d_sparse % 16 == 0)
-        hipLaunchKernelGGL(k_project_resolve<4>, dim3((unsigned)((n_px / 4 + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px, gen_tag, ctx->winner_bits);
-    else if (n_px % 2 == 0 && (uintptr_t)d_sparse % 8 == 0)
-        hipLaunchKernelGGL(k_project_resolve<2>, dim3((unsigned)((n_px / 2 + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px, gen_tag, ctx->winner_bits);
-    else
-        hipLaunchKernelGGL(k_project_resolve<1>, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px, gen_tag, ctx->winner_bits);
+    const int vec = n_px % 4 == 0 && (uintptr_t)d_sparse % 16 == 0 ? 4 : n_px % 2 == 0 && (uintptr_t)d_sparse % 8 == 0 ? 2 : 1;     // pixels per thread
+    with_value<4, 2, 1>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_project_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px,
+                           gen_tag, ctx->winner_bits);
+    });
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
@@ -941,24 +814,15 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
     const size_t cells = (size_t)gx * gy;
     // two cell sets (the assignment reads one while the next centres are binned into the other); per set [batch][cells] counts
     // with the [batch] overflow flags right behind, and [batch][cells][kSlicCellCap] centre indices
-    if (cells > ctx->slic_cell_cap) {
-        (void)hipFree(ctx->slic_cells); ctx->slic_cells = nullptr; ctx->slic_cell_cap = 0;
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->slic_cells, 2 * sizeof(int) * ((size_t)ctx->max_batch * cells * (1 + kSlicCellCap) + ctx->max_batch)));
-        ctx->slic_cell_cap = cells;
-    }
+    DCMT_TRY(ctx->slic_cells.reserve(ctx, 2 * ((size_t)ctx->max_batch * cells * (1 + kSlicCellCap) + ctx->max_batch)));
     const size_t n_cnt = (size_t)batch * cells + batch;
     int* set_cnt[2] = {ctx->slic_cells, ctx->slic_cells + n_cnt};
     int* set_ovf[2] = {set_cnt[0] + (size_t)batch * cells, set_cnt[1] + (size_t)batch * cells};
     int* set_list[2] = {ctx->slic_cells + 2 * n_cnt, ctx->slic_cells + 2 * n_cnt + (size_t)batch * cells * kSlicCellCap};
-    if ((size_t)n > ctx->slic_center_cap) {
-        (void)hipFree(ctx->slic_centers[0]); (void)hipFree(ctx->slic_centers[1]); (void)hipFree(ctx->slic_sums);
-        ctx->slic_centers[0] = ctx->slic_centers[1] = nullptr; ctx->slic_sums = nullptr; ctx->slic_center_cap = 0;
-        const size_t cn = (size_t)n * ctx->max_batch;
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->slic_centers[0], sizeof(double) * 5 * cn));
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->slic_centers[1], sizeof(double) * 5 * cn));
-        DCMT_HIP(ctx, hipMalloc((void**)&ctx->slic_sums, sizeof(unsigned long long) * 6 * cn));
-        ctx->slic_center_cap = (size_t)n;
-    }
+    const size_t cn = (size_t)n * ctx->max_batch;                          // the three centre buffers grow together
+    DCMT_TRY(ctx->slic_centers[0].reserve(ctx, 5 * cn));
+    DCMT_TRY(ctx->slic_centers[1].reserve(ctx, 5 * cn));
+    DCMT_TRY(ctx->slic_sums.reserve(ctx, 6 * cn));
     DCMT_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, sizeof(int32_t) * px, st));                    // clusters = -1 (slic.cpp:24)
     DCMT_HIP(ctx, hipMemsetAsync(set_cnt[0], 0, sizeof(int) * 2 * n_cnt, st));                  // both cell sets' counts and flags
     DCMT_HIP(ctx, hipMemsetAsync(ctx->slic_sums, 0, sizeof(unsigned long long) * 6 * (size_t)n * batch, st));   // every iteration leaves them zeroed
@@ -974,15 +838,10 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
         double* cur = ctx->slic_centers[it & 1];
         double* nxt = ctx->slic_centers[(it + 1) & 1];
         const int a = it & 1, b = a ^ 1;
-        if (th == 64)
-            hipLaunchKernelGGL(k_slic_assign<64>, dim3((cols + kSlicTW - 1) / kSlicTW, (rows + 63) / 64, batch), dim3(256), 0, st, d_lab, cur,
+        with_value<64, 32, 16>(th, [&](auto h) {
+            hipLaunchKernelGGL(k_slic_assign<decltype(h)::value>, dim3((cols + kSlicTW - 1) / kSlicTW, (rows + h - 1) / h, batch), dim3(256), 0, st, d_lab, cur,
                                set_cnt[a], set_list[a], set_ovf[a], d_labels, ctx->slic_sums, rows, cols, step, nc, n, gx, gy, cell_px);
-        else if (th == 32)
-            hipLaunchKernelGGL(k_slic_assign<32>, dim3((cols + kSlicTW - 1) / kSlicTW, (rows + 31) / 32, batch), dim3(256), 0, st, d_lab, cur,
-                               set_cnt[a], set_list[a], set_ovf[a], d_labels, ctx->slic_sums, rows, cols, step, nc, n, gx, gy, cell_px);
-        else
-            hipLaunchKernelGGL(k_slic_assign<16>, dim3((cols + kSlicTW - 1) / kSlicTW, (rows + 15) / 16, batch), dim3(256), 0, st, d_lab, cur,
-                               set_cnt[a], set_list[a], set_ovf[a], d_labels, ctx->slic_sums, rows, cols, step, nc, n, gx, gy, cell_px);
+        });
         hipLaunchKernelGGL(k_slic_norm_bin, dim3((unsigned)((nb_threads + 255) / 256)), dim3(256), 0, st, ctx->slic_sums, nxt, n, batch,
                            set_cnt[b], set_list[b], set_ovf[b], set_cnt[a], (int)n_cnt, cell_px, gx, gy);
         DCMT_HIP(ctx, hipGetLastError());
@@ -992,20 +851,12 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
     return DCMT_OK;
 }
 
-static int read_counters(dcmt_ctx* ctx)
-{
-    DCMT_HIP(ctx, hipMemcpyAsync(ctx->h_counters, ctx->counters, sizeof(int) * (size_t)ctx->last_batch * kCntStride,
-                                 hipMemcpyDeviceToHost, ctx->last_stream));
-    DCMT_HIP(ctx, hipStreamSynchronize(ctx->last_stream));
-    return DCMT_OK;
-}
-
 int dcmt_last_fill_iters(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
     if (!ctx->last_has_loop) return DCMT_E_INVALID;
-    int rc = read_counters(ctx);
+    int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
     if (rc != DCMT_OK) return rc;
     for (int f = 0; f < n; ++f) {
         const int* c = ctx->h_counters + (size_t)f * kCntStride;
@@ -1021,7 +872,7 @@ int dcmt_last_holes_after_extend(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
-    int rc = read_counters(ctx);
+    int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
     if (rc != DCMT_OK) return rc;
     for (int f = 0; f < n; ++f) out[f] = ctx->h_counters[(size_t)f * kCntStride];
     return DCMT_OK;

@@ -113,15 +113,11 @@ int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int 
     if (rc != DCMT_OK) return rc;
     hipLaunchKernelGGL(k_reproject_scatter, dim3((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch), dim3(256), 0, st, d_depth, n,
                        (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
-    if (n_px % 4 == 0 && (uintptr_t)d_out % 16 == 0)
-        hipLaunchKernelGGL(k_reproject_resolve<4>, dim3((unsigned)((n_px / 4 + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
-                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
-    else if (n_px % 2 == 0 && (uintptr_t)d_out % 8 == 0)
-        hipLaunchKernelGGL(k_reproject_resolve<2>, dim3((unsigned)((n_px / 2 + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
-                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
-    else
-        hipLaunchKernelGGL(k_reproject_resolve<1>, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, ctx->winner,
-                           d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+    const int vec = n_px % 4 == 0 && (uintptr_t)d_out % 16 == 0 ? 4 : n_px % 2 == 0 && (uintptr_t)d_out % 8 == 0 ? 2 : 1;       // pixels per thread
+    with_value<4, 2, 1>(vec, [&](auto v) {
+        hipLaunchKernelGGL(k_reproject_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k,
+                           ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+    });
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

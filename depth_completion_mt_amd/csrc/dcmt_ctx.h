@@ -7,28 +7,65 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "dcmt.h"
 #include "dcmt_plan.h"
 
+struct dcmt_ctx;
+
+namespace dcmt {
+
+// One allocation of the context and its element count: device memory, or host memory that is pinned (h_counters) or pinned and
+// mapped (q16_seen).  Frees itself with the context; reads as a plain T* wherever one is expected (launch arguments, arithmetic).
+// DCMT_LOCAL keeps an internal name out of libdcmt_hip.so's dynamic symbol table
+#define DCMT_LOCAL __attribute__((visibility("hidden")))
+enum class Mem { DEVICE, PINNED, MAPPED };
+template <typename T, Mem M = Mem::DEVICE>
+struct DCMT_LOCAL Buf {
+    T* p = nullptr;
+    size_t n = 0;                     // elements allocated
+    Buf() = default;
+    Buf(const Buf&) = delete;
+    Buf& operator=(const Buf&) = delete;
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    void release()
+    {
+        if (p) (void)(M == Mem::DEVICE ? hipFree(p) : hipHostFree(p));
+        p = nullptr; n = 0;
+    }
+    // Room for `count` elements: nothing when they fit, otherwise free and allocate (the contents are lost; *reallocated is set, and
+    // left alone otherwise, so one flag can watch several buffers).  A failure leaves the buffer empty and is reported as DCMT_HIP
+    // reports it.  An allocation synchronises the device: callers reserve before they enqueue anything of a call.
+    int reserve(dcmt_ctx* ctx, size_t count, bool* reallocated = nullptr);
+};
+
+}  // namespace dcmt
+
+// Who allocates what: dcmt_create unless the comment names a first user; what a first user allocates is sized for the context's
+// maxima and never again, what is "grown on demand" is reallocated by a call that needs more than any before it.
 struct dcmt_ctx {
+    template <typename T> using Dev = dcmt::Buf<T>;
+    DCMT_LOCAL ~dcmt_ctx() = default;
     int device = 0;
     int max_rows = 0, max_cols = 0, max_batch = 0;
     size_t frame_elems = 0;           // max_rows * max_cols
     // device scratch
-    float* x5 = nullptr;              // [max_batch][rows][cols] : cascade after the small fill (= pp[1], see dcmt_create)
-    float* pp[2] = {nullptr, nullptr};// ping-pong of the large-fill applications
-    int* colstat = nullptr;           // [max_batch][tile rows][2][cols]  (staged path)
-    int* counters = nullptr;          // [max_batch][kCntStride]
-    int* tb = nullptr;                // [max_batch][2][max_cols]: first / last valid row of every X6 column (k_pre table mode -> k_fp_s)
-    uint32_t* norm_stats = nullptr;   // [max_batch][2]  N1: order-preserving keys of each frame's max and (inverted) min
-    float* norm_coef = nullptr;       // [max_batch][2]  N1: dst = src * a + b
-    // host-entry staging (allocated on first use)
-    float* d_in = nullptr;
-    float* d_out = nullptr;
-    int32_t* d_lab = nullptr;
-    int* h_counters = nullptr;        // pinned
-    hipStream_t own_stream = nullptr;
+    Dev<float> pp[2];                 // [max_batch][rows][cols] each: ping-pong of the large-fill applications
+    float* x5 = nullptr;              // cascade after the small fill: an alias of pp[1], owns nothing (see dcmt_create)
+    Dev<int> colstat;                 // [max_batch][tile rows][2][cols]  (staged path; the first call whose plan names it)
+    Dev<int> counters;                // [max_batch][kCntStride]
+    Dev<int> tb;                      // [max_batch][2][max_cols]: first / last valid row of every X6 column (k_pre table mode -> k_fp_s)
+    Dev<uint32_t> norm_stats;         // [max_batch][2]  N1: order-preserving keys of each frame's max and (inverted) min
+    Dev<float> norm_coef;             // [max_batch][2]  N1: dst = src * a + b
+    // staging of dcmt_complete_f32 / dcmt_complete_labeled_f32 (dcmt_host.hip), [max_batch][rows][cols] each: allocated by the first
+    // such call (d_lab: the first labeled one) and kept, because these are called once per frame in a loop
+    Dev<float> d_in;
+    Dev<float> d_out;
+    Dev<int32_t> d_lab;
+    dcmt::Buf<int, dcmt::Mem::PINNED> h_counters;   // [max_batch][kCntStride]: where read_counters puts the hole counters
+    hipStream_t own_stream = nullptr; // the host entry points' stream, created by the first of them
     // state of the last call
     hipStream_t last_stream = nullptr;
     int last_batch = 0;
@@ -40,45 +77,64 @@ struct dcmt_ctx {
     hipEvent_t tev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int tev_valid = 0;                // the last call recorded all five
     dcmt::plan::Knobs knobs;                // the environment knobs (dcmt_plan.h), read by dcmt_create
-    unsigned short* x6q = nullptr;    // [max_batch][rows][cols] X6 as 16-bit codes (k_pre_p<Q16OUT> -> k_fp_q)
-    int* q16_bad = nullptr;           // a ring of kQ16Flags flags; attempt n uses flag n % kQ16Flags: raised by k_pre_p<Q16OUT> when a value it stored was
+    Dev<unsigned short> x6q;          // [max_batch][rows][cols] X6 as 16-bit codes (k_pre_p<Q16OUT> -> k_fp_q) and 16 bytes of slack; the first
+                                      // call whose plan names it
+    Dev<int> q16_bad;                 // a ring of kQ16Flags flags; attempt n uses flag n % kQ16Flags: raised by k_pre_p<Q16OUT> when a value it stored was
                                       // not a code, and cleared one attempt ahead by that kernel too (no memset in the stream)
     unsigned q16_attempts = 0;
-    int* q16_seen = nullptr;          // pinned host word (and its device address) the same kernel sets: the NEXT calls skip the 16-bit attempt
-    int* q16_seen_dev = nullptr;
+    dcmt::Buf<int, dcmt::Mem::MAPPED> q16_seen;     // pinned host word (and its device address) the same kernel sets: the NEXT calls skip the 16-bit attempt
+    int* q16_seen_dev = nullptr;      // (an alias, owns nothing)
     int q16_skip = 0;                 // calls left without an attempt (after a raised flag: 63, then one more try)
-    unsigned* winner = nullptr;       // the winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev (tags: generation | index; winner_generation),
-                                      // allocated by the first call of either
-    size_t winner_elems = 0;
+    Dev<unsigned> winner;             // the winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev (tags: generation | index; winner_generation),
+                                      // allocated by the first call of either, grown on demand
     int winner_bits = 0;              // index bits of the plane's tag layout
     unsigned winner_gen = 0;          // generation of the last call (0: the plane is all zeros and nothing has been written)
-    int* bb_min = nullptr;            // LC fast path: per (frame, label) bounding boxes, grown on demand
-    int* bb_max = nullptr;
-    size_t bb_ints = 0;
-    // N3 (SLIC) scratch, allocated by the first dcmt_slic_labels_dev call
-    int* slic_cells = nullptr;                  // two cell sets: counts [batch][cells] + overflow flags [batch] each, then the index lists [batch][cells][kSlicCellCap] each
-    size_t slic_cell_cap = 0;                   // cells per frame that buffer holds
-    double* slic_centers[2] = {nullptr, nullptr};
-    unsigned long long* slic_sums = nullptr;
-    size_t slic_center_cap = 0;                 // centres per frame the two buffers above hold
-    double* eval_slab = nullptr;      // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
+    Dev<int> bb_min;                  // LC fast path: per (frame, label) bounding boxes, grown on demand (ensure_bbox), both together
+    Dev<int> bb_max;
+    // N3 (SLIC) scratch, allocated by the first dcmt_slic_labels_dev call and grown on demand.  All four hold max_batch frames, so
+    // their counts grow with the cells / centres per frame and no per-frame capacity is kept beside them.
+    Dev<int> slic_cells;              // two cell sets: counts [batch][cells] + overflow flags [batch] each, then the index lists [batch][cells][kSlicCellCap] each
+    Dev<double> slic_centers[2];      // the three centre buffers grow together
+    Dev<unsigned long long> slic_sums;
+    Dev<double> eval_slab;            // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
                                       // allocated by the first evaluate call
-    float* color_slab = nullptr;      // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
-                                      // (allocated by dcmt_create)
-    uint32_t* cloud_slab = nullptr;   // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
-                                      // color_slab, kCloudWaves entries per chunk (allocated by dcmt_create)
+    Dev<float> color_slab;            // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
+    Dev<uint32_t> cloud_slab;         // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
+                                      // color_slab, kCloudWaves entries per chunk
 };
 
 namespace dcmt {
 
+// A HIP error becomes the call's status and dcmt_last_hip_error, and stops being the thread's last HIP error: left there, it would be
+// what this library's next launch check reports, or that of a framework sharing the runtime (a refused allocation, say)
 #define DCMT_HIP(ctx, call)                                        \
     do {                                                           \
         hipError_t e_ = (call);                                    \
         if (e_ != hipSuccess) {                                    \
+            (void)hipGetLastError();                               \
             if (ctx) (ctx)->last_hip_error = (int)e_;              \
             return e_ == hipErrorOutOfMemory ? DCMT_E_NOMEM : DCMT_E_HIP; \
         }                                                          \
     } while (0)
+
+// the same for a call that returns a dcmt_status
+#define DCMT_TRY(call)                                             \
+    do {                                                           \
+        const int rc_ = (call);                                    \
+        if (rc_ != DCMT_OK) return rc_;                            \
+    } while (0)
+
+template <typename T, Mem M>
+int Buf<T, M>::reserve(dcmt_ctx* ctx, size_t count, bool* reallocated)
+{
+    if (count <= n) return DCMT_OK;
+    release();
+    if (reallocated) *reallocated = true;
+    void* q = nullptr;
+    DCMT_HIP(ctx, M == Mem::DEVICE ? hipMalloc(&q, sizeof(T) * count) : hipHostMalloc(&q, sizeof(T) * count, M == Mem::MAPPED ? hipHostMallocMapped : hipHostMallocDefault));
+    p = static_cast<T*>(q); n = count;
+    return DCMT_OK;
+}
 
 // Every entry point that takes a context runs with that context's device current and puts the caller's current device back
 // before it returns: one process may drive several GPUs, one host thread + one dcmt_ctx + one stream per GPU (HIP's current
@@ -111,6 +167,16 @@ inline bool finite_bits(float v)
     return (b & 0x7f800000u) != 0x7f800000u;
 }
 
+// f(std::integral_constant<_, V>{}) with the first of the listed values that equals v, the last one where none does: a runtime
+// value as a template argument, out of that list
+template <auto V, auto... Rest, typename T, typename F>
+void with_value(T v, F f)
+{
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<decltype(V), V>{});
+    else if (v == V) f(std::integral_constant<decltype(V), V>{});
+    else with_value<Rest...>(v, f);
+}
+
 // rows x cols x batch is a size the context was created for
 inline bool dims_ok(const dcmt_ctx* ctx, int rows, int cols, int batch)
 {
@@ -138,5 +204,24 @@ int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st
 // eval_chunks(n) and eval_chunk_groups(n) of dcmt_kernels_eval.h, for a translation unit that must not compile that header's
 // kernels (dcmt_cloud.hip, whose kernels walk a frame in the same chunks).  Defined in dcmt.hip.
 void frame_chunks(uint32_t n, uint32_t* chunks, uint32_t* groups);
+
+// What a completion call is given: device pointers (src or src16; labels only where they are used) and the batch's shape
+struct Frames {
+    const float* src;
+    const uint16_t* src16;
+    float in_scale;
+    const int32_t* labels;
+    int n_labels;
+    float* dst;
+    int rows, cols, batch;
+};
+
+// What dcmt_complete_f32 and dcmt_complete_labeled_f32 (dcmt_host.hip) need of the cascade, which the *_dev ABI does not offer.
+// check_params: the checks every dcmt_complete_* entry point starts with (a, b: its source and destination).  complete_sync: the
+// cascade on the device planes of `fr`, enqueued on `st`, with the hole-closure loop run exactly as the reference runs it -- the hole
+// counters are read back between applications, so the call synchronises with `st` -- and DCMT_E_NOT_CONVERGED where the loop hit
+// p->max_fill_iters (dst is written all the same).  Both defined in dcmt.hip.
+DCMT_LOCAL int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p);
+DCMT_LOCAL int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_gaussian, hipStream_t st);
 
 }  // namespace dcmt

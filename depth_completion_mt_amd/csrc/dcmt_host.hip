@@ -1,7 +1,11 @@
-// dcmt_host.hip -- the synchronous single-frame host variants of the *_dev entry points: stage the caller's planes in temporary
-// device buffers, run the public *_dev function with batch = 1 on the context's own stream, fetch the results, synchronise.
-// Nothing but dcmt.h's ABI is called here and no kernel is compiled: this translation unit emits no device code.
+// dcmt_host.hip -- the synchronous host entry points: copy the caller's planes to the device, run the device call on the context's
+// own stream, copy the results back, synchronise.  The single-frame variants of the *_dev entry points stage in temporary buffers
+// and call dcmt.h's public *_dev function with batch = 1.  dcmt_complete_f32 and dcmt_complete_labeled_f32 (the cv::Mat entry
+// points, called once per frame in a loop) stage batches in buffers the context keeps, and reach the cascade through the two
+// internal declarations of dcmt_ctx.h -- check_params and complete_sync -- because they run the hole-closure loop with the counters
+// read back, which the public ABI does not offer.  No kernel is compiled: this translation unit emits no device code.
 #include <algorithm>
+#include <cstdio>
 #include <initializer_list>
 
 #include "dcmt.h"
@@ -26,6 +30,16 @@ struct Plane {
 };
 using Planes = std::initializer_list<Plane*>;
 
+// One plane between host rows `pitch` bytes apart and its packed device copy, enqueued on the context's own stream: a linear copy
+// where the host rows are packed too (the usual cv::Mat), a pitched one otherwise.
+int copy_plane(dcmt_ctx* ctx, void* dev, void* host, size_t pitch, size_t row_bytes, size_t rows, hipMemcpyKind kind)
+{
+    const bool up = kind == hipMemcpyHostToDevice;
+    if (pitch == row_bytes || rows == 1) DCMT_HIP(ctx, hipMemcpyAsync(up ? dev : host, up ? host : dev, row_bytes * rows, kind, ctx->own_stream));
+    else DCMT_HIP(ctx, hipMemcpy2DAsync(up ? dev : host, up ? row_bytes : pitch, up ? host : dev, up ? pitch : row_bytes, row_bytes, rows, kind, ctx->own_stream));
+    return DCMT_OK;
+}
+
 // Checks the pitches, gets the context's own stream (created on first use), allocates every plane and only then enqueues the
 // uploads of `ins`: an allocation that fails leaves nothing of the call in the stream.
 int stage(dcmt_ctx* ctx, Planes ins, Planes outs)
@@ -35,31 +49,84 @@ int stage(dcmt_ctx* ctx, Planes ins, Planes outs)
     if (!ctx->own_stream) DCMT_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     for (Planes l : {ins, outs})
         for (Plane* p : l) if (p->host) DCMT_HIP(ctx, hipMalloc(&p->dev, std::max<size_t>(p->row_bytes * p->rows, 1)));
-    for (Plane* p : ins) {
-        if (!p->host || !p->row_bytes) continue;
-        if (p->rows == 1) DCMT_HIP(ctx, hipMemcpyAsync(p->dev, p->host, p->row_bytes, hipMemcpyHostToDevice, ctx->own_stream));
-        else DCMT_HIP(ctx, hipMemcpy2DAsync(p->dev, p->row_bytes, p->host, p->pitch, p->row_bytes, p->rows, hipMemcpyHostToDevice, ctx->own_stream));
-    }
+    for (Plane* p : ins)
+        if (p->host && p->row_bytes) DCMT_TRY(copy_plane(ctx, p->dev, p->host, p->pitch, p->row_bytes, p->rows, hipMemcpyHostToDevice));
     return DCMT_OK;
 }
 
 // Copies `outs` back behind whatever the call enqueued and waits for it all.
 int fetch(dcmt_ctx* ctx, Planes outs)
 {
-    for (Plane* p : outs) {
-        if (!p->host || !p->row_bytes) continue;
-        if (p->rows == 1) DCMT_HIP(ctx, hipMemcpyAsync(p->host, p->dev, p->row_bytes, hipMemcpyDeviceToHost, ctx->own_stream));
-        else DCMT_HIP(ctx, hipMemcpy2DAsync(p->host, p->pitch, p->dev, p->row_bytes, p->row_bytes, p->rows, hipMemcpyDeviceToHost, ctx->own_stream));
-    }
+    for (Plane* p : outs)
+        if (p->host && p->row_bytes) DCMT_TRY(copy_plane(ctx, p->dev, p->host, p->pitch, p->row_bytes, p->rows, hipMemcpyDeviceToHost));
     DCMT_HIP(ctx, hipStreamSynchronize(ctx->own_stream));
     return DCMT_OK;
 }
 
+// dcmt_complete_f32 / dcmt_complete_labeled_f32: frame f of a plane starts f * its frame stride (sfs / lfs / dfs) bytes behind the
+// pointer.  The staging buffers are the context's, sized for its maxima by the first call and kept (d_lab by the first labeled call).
+int host_call(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int32_t* labels, size_t lrs, size_t lfs,
+              int n_labels, int use_superpixel, float* dst, size_t drs, size_t dfs, int rows, int cols, int batch,
+              const dcmt_params* p, bool force_gaussian)
+{
+    DCMT_TRY(check_params(ctx, src, dst, rows, cols, batch, p));
+    if (srs < sizeof(float) * (size_t)cols || drs < sizeof(float) * (size_t)cols) return DCMT_E_INVALID;
+    if (labels && lrs < sizeof(int32_t) * (size_t)cols) return DCMT_E_INVALID;
+    const size_t staged = ctx->frame_elems * (size_t)ctx->max_batch;
+    DCMT_TRY(ctx->d_in.reserve(ctx, staged));
+    DCMT_TRY(ctx->d_out.reserve(ctx, staged));
+    if (labels) DCMT_TRY(ctx->d_lab.reserve(ctx, staged));
+    if (!ctx->own_stream) DCMT_HIP(ctx, hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    hipStream_t st = ctx->own_stream;
+    const size_t fe = (size_t)rows * cols, row_b = sizeof(float) * (size_t)cols;
+    if (p->verbose == 1) {
+        // what img_completion prints before it starts (LO :29, :41-50): the dimensions and the largest input value (start value 0.0, :22)
+        std::printf("NUMERO ROWS, COLS: %d %d\n", rows, cols);
+        for (int f = 0; f < batch; ++f) {
+            float mx = 0.0f;
+            for (int r = 0; r < rows; ++r) {
+                const float* row = reinterpret_cast<const float*>(reinterpret_cast<const char*>(src) + f * sfs + r * srs);
+                for (int c = 0; c < cols; ++c) mx = row[c] > mx ? row[c] : mx;
+            }
+            std::printf("max range is%g\n", (double)mx);               // operator<<(float): six significant digits, as %g
+        }
+    }
+    for (int f = 0; f < batch; ++f) {
+        DCMT_TRY(copy_plane(ctx, ctx->d_in + f * fe, (char*)src + f * sfs, srs, row_b, rows, hipMemcpyHostToDevice));
+        if (labels) DCMT_TRY(copy_plane(ctx, ctx->d_lab + f * fe, (char*)labels + f * lfs, lrs, row_b, rows, hipMemcpyHostToDevice));
+    }
+    if (ctx->knobs.poison)   // DCMT_POISON=1: stale output can never pass for fresh output (tests)
+        DCMT_HIP(ctx, hipMemsetAsync(ctx->d_out, 0xFF, sizeof(float) * fe * batch, st));
+    const Frames fr = {ctx->d_in, nullptr, 1.0f, labels && use_superpixel ? ctx->d_lab.p : nullptr, n_labels, ctx->d_out, rows, cols, batch};
+    const int chain_rc = complete_sync(ctx, fr, p, force_gaussian, st);
+    if (chain_rc != DCMT_OK && chain_rc != DCMT_E_NOT_CONVERGED) return chain_rc;
+    for (int f = 0; f < batch; ++f) DCMT_TRY(copy_plane(ctx, ctx->d_out + f * fe, (char*)dst + f * dfs, drs, row_b, rows, hipMemcpyDeviceToHost));
+    DCMT_HIP(ctx, hipStreamSynchronize(st));
+    return chain_rc;
+}
+
 }  // namespace
 
-// Every variant: its own null checks and the frame against the context's maxima (before anything is allocated), stage, the
+// Every single-frame variant: its own null checks and the frame against the context's maxima (before anything is allocated), stage, the
 // *_dev call -- which reports what only it can detect (a NaN matrix, step < 6) --, fetch.
 extern "C" {
+
+int dcmt_complete_f32(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, float* dst, size_t drs, size_t dfs,
+                      int rows, int cols, int batch, const dcmt_params* params)
+{
+    DCMT_ON_DEVICE(ctx);
+    return host_call(ctx, src, srs, sfs, nullptr, 0, 0, 0, 0, dst, drs, dfs, rows, cols, batch, params, false);
+}
+
+int dcmt_complete_labeled_f32(dcmt_ctx* ctx, const float* src, size_t srs, size_t sfs, const int32_t* labels, size_t lrs,
+                              size_t lfs, int n_labels, float* dst, size_t drs, size_t dfs, int rows, int cols, int batch,
+                              const dcmt_params* params, int use_superpixel)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!labels) return DCMT_E_INVALID;
+    return host_call(ctx, src, srs, sfs, labels, lrs, lfs, n_labels, use_superpixel, dst, drs, dfs, rows, cols, batch,
+                     params, true);
+}
 
 int dcmt_project_points(dcmt_ctx* ctx, const float* points, int n_points, const float T[16], const float P[12],
                         float* sparse, size_t srs, int rows, int cols)

@@ -1,7 +1,9 @@
 """The three oldest single-frame host entry points -- dcmt_project_points, dcmt_slic_labels, dcmt_stereo_refine -- called through
 ctypes with rows that are NOT packed: every plane lives in a wider parent array, so row bytes != pitch (and 3 bytes per pixel for
 the Lab image, two differently pitched inputs in one stereo call).  24 x 40 is the smallest frame at which that arithmetic can go
-wrong; the results are bit-equal to the oracle and the parents' padding, pre-filled with a sentinel, is untouched."""
+wrong; the results are bit-equal to the oracle and the parents' padding, pre-filled with a sentinel, is untouched.  Likewise the two
+batched cv::Mat entry points, dcmt_complete_f32 and dcmt_complete_labeled_f32: two frames in one 24 x 56 parent whose frame stride
+is larger than a frame."""
 import ctypes
 
 import numpy as np
@@ -141,3 +143,86 @@ def test_frames_wider_than_the_context_and_short_pitches_are_invalid(ctx):
         assert stereo(**short) == L.E_INVALID, short
     # a packed frame (pitch == row bytes) is the limit that passes
     assert _project(ctx, pts, out, 4 * COLS) == L.OK and slic(3 * COLS) == L.OK and stereo(4 * COLS, COLS, COLS, 4 * COLS) == L.OK
+
+
+# ---- dcmt_complete_f32 / dcmt_complete_labeled_f32: batch 2, 24 x 40 inside 24 x 56, three parent rows between the frames
+
+BATCH, WIDE, GAP = 2, 56, 3
+
+
+@pytest.fixture(scope="module")
+def ctx2():
+    with Context(0, ROWS, COLS, BATCH) as c:
+        yield c
+
+
+def _batch_parent(cols=WIDE, dtype=np.float32):
+    """[BATCH][ROWS + GAP][cols] full of the sentinel: frame f is its [f, :ROWS, :COLS]"""
+    return np.full((BATCH, ROWS + GAP, cols), SENTINEL, dtype=np.uint32).view(dtype)
+
+
+def _only_the_frames_written(par):
+    mask = np.ones(par.shape, bool)
+    mask[:, :ROWS, :COLS] = False
+    return bool((par.view(np.uint32)[mask] == SENTINEL).all())
+
+
+def _complete(ctx, src, dst, lab=None, n_labels=0, *, rows=ROWS, cols=COLS, srs=None, drs=None, lrs=None, sfs=None, dfs=None):
+    """the entry point on the frames at the start of the parents src / dst / lab; row and frame strides are the parents' unless given"""
+    from depth_completion_mt_amd import make_params
+    p = ctypes.byref(make_params())
+    srs, sfs, drs, dfs = srs or src.strides[1], sfs or src.strides[0], drs or dst.strides[1], dfs or dst.strides[0]
+    if lab is None:
+        return L.lib().dcmt_complete_f32(ctx._h, src.ctypes.data, srs, sfs, dst.ctypes.data, drs, dfs, rows, cols, BATCH, p)
+    return L.lib().dcmt_complete_labeled_f32(ctx._h, src.ctypes.data, srs, sfs, lab.ctypes.data, lrs or lab.strides[1], lab.strides[0], n_labels,
+                                             dst.ctypes.data, drs, dfs, rows, cols, BATCH, p, 1)
+
+
+def _batch_inputs():
+    frames = synth.synth_batch(BATCH, ROWS, COLS, 11)
+    labels, n_labels = synth.synth_labels(ROWS, COLS, 12, 3)
+    src, lab = _batch_parent(), _batch_parent(PARENT, np.int32)         # the label planes' pitch differs from the frames'
+    src[:, :ROWS, :COLS] = frames
+    lab[:, :ROWS, :COLS] = labels
+    return frames, labels.astype(np.int32), n_labels, src, lab
+
+
+def test_complete_f32_of_a_pitched_batch(ctx2):
+    frames, _, _, src, _ = _batch_inputs()
+    dst = _batch_parent()
+    assert (src.strides[1], src.strides[0]) == (4 * WIDE, 4 * WIDE * (ROWS + GAP)) and src.strides[0] > 4 * WIDE * ROWS
+    assert _complete(ctx2, src, dst) == L.OK
+    for f in range(BATCH):
+        assert_bit_equal(dst[f, :ROWS, :COLS], O.img_completion(frames[f]), f"dcmt_complete_f32, pitched, frame {f}")
+    assert _only_the_frames_written(dst)
+
+
+def test_complete_labeled_f32_of_a_pitched_batch(ctx2):
+    frames, labels, n_labels, src, lab = _batch_inputs()
+    dst = _batch_parent(COLS + 1)                                        # a third pitch, one element more than a row
+    assert lab.strides[1] == 4 * PARENT != src.strides[1] and dst.strides[1] == 4 * COLS + 4
+    assert _complete(ctx2, src, dst, lab, n_labels) == L.OK
+    for f in range(BATCH):
+        assert_bit_equal(dst[f, :ROWS, :COLS], O.interpolate_with_superpixels(frames[f], labels, n_labels),
+                         f"dcmt_complete_labeled_f32, pitched, frame {f}")
+    assert _only_the_frames_written(dst)
+
+
+def test_complete_short_pitches_and_oversized_frames_are_invalid(ctx2):
+    frames, labels, n_labels, src, lab = _batch_inputs()
+    row = 4 * COLS
+    # the limit that passes: packed frames, pitch == row bytes ...
+    packed, packed_lab, out = np.ascontiguousarray(frames), np.ascontiguousarray(np.stack([labels] * BATCH)), np.empty_like(frames)
+    assert packed.strides[1] == packed_lab.strides[1] == out.strides[1] == row
+    assert _complete(ctx2, packed, out) == L.OK and _complete(ctx2, packed, out, packed_lab, n_labels) == L.OK
+    # ... one byte less does not, in any of the planes ...
+    dst = _batch_parent()
+    for short in ({"srs": row - 1}, {"drs": row - 1}):
+        assert _complete(ctx2, src, dst, **short) == L.E_INVALID, short
+    for short in ({"srs": row - 1}, {"drs": row - 1}, {"lrs": row - 1}):
+        assert _complete(ctx2, src, dst, lab, n_labels, **short) == L.E_INVALID, short
+    # ... and neither does a frame of 24 x 41 or 25 x 40 in the 24 x 40 context (the parents have the room)
+    for big in ({"cols": COLS + 1}, {"rows": ROWS + 1}):
+        assert _complete(ctx2, src, dst, **big) == L.E_INVALID, big
+        assert _complete(ctx2, src, dst, lab, n_labels, **big) == L.E_INVALID, big
+    assert (dst.view(np.uint32) == SENTINEL).all(), "a refused call writes nothing"
