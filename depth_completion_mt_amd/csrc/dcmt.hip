@@ -22,6 +22,7 @@
 
 #include "dcmt.h"
 #include "dcmt_plan.h"
+#include "dcmt_plan_side.h"
 #include "dcmt_ctx.h"
 #include "dcmt_kernels_v1.h"
 #include "dcmt_kernels_fused.h"
@@ -57,6 +58,7 @@ static_assert(plan::kFlagForceStaged == DCMT_FLAG_FORCE_STAGED && plan::kFlagFor
 static_assert(plan::q16_params_ok(100.0f, 0.1f) && Q16::params_ok(100.0f, 0.1f) && !plan::q16_params_ok(80.0f, 0.1f) && !Q16::params_ok(80.0f, 0.1f) &&
               !plan::q16_params_ok(100.0f, 0.2f) && !Q16::params_ok(100.0f, 0.2f), "Q16::params_ok");
 static_assert(sizeof(plan::Plan::path) == sizeof(dcmt_ctx::last_path), "dcmt_last_path");
+static_assert(plan::kOk == DCMT_OK && plan::kInvalid == DCMT_E_INVALID, "dcmt_status");
 
 uint32_t k0_bits(const uint8_t k0[25])
 {
@@ -480,30 +482,22 @@ int evaluate_dev(dcmt_ctx* ctx, const TG* d_gt, float gt_scale, const float* d_p
     return DCMT_OK;
 }
 
-// dcmt_colorize_dev: a min/max pass over the batch's frames, then one map pass over its flat pixel run (dcmt_kernels_color.h).
-// Batches of 2^31 pixels or more go in segments of whole frames, each a pair of its own: a segment holds fewer than 2^31 pixels
-// (32-bit pixel indices) and, where it is not the last, a multiple of 4 frames, so every segment starts as aligned as the batch
-// does.  (Measured, 1024 frames of 352 x 1216: segments of 128 / 64 / 32 frames, whose re-read could come from the Infinity Cache,
-// take 0.90 / 0.91 / 1.03 ms against 0.85 ms for the whole batch in one pair.)
+// dcmt_colorize_dev: per segment of frames (plan_colorize: one segment unless the batch has 2^31 pixels or more) a min/max pass over
+// its frames, then one map pass over its flat pixel run (dcmt_kernels_color.h)
 int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batch, uint8_t* d_bgr, hipStream_t st)
 {
     if (!ctx || !d_src || !d_bgr) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if ((uintptr_t)d_src % 4 != 0) return DCMT_E_INVALID;
-    const uint32_t n = (uint32_t)rows * (uint32_t)cols, chunks = eval_chunks(n);
-    const uint32_t cap = (0x80000000u - kColorPxPerWg) / n;                 // frames per segment the 32-bit pixel run allows (>= 3)
-    uint32_t seg = std::min((uint32_t)batch, cap);
-    if (seg >= 4 && seg < (uint32_t)batch) seg &= ~3u;
-    for (uint32_t f0 = 0; f0 < (uint32_t)batch; f0 += seg) {
-        const uint32_t nf = std::min(seg, (uint32_t)batch - f0), total = nf * n;
-        const float* s = d_src + (size_t)f0 * n;
-        uint8_t* o = d_bgr + (size_t)3 * f0 * n;
-        const uint32_t span = std::min(nf, (kColorPxPerWg - 1) / n + 2);   // frames one map workgroup can touch
-        const size_t lds = sizeof(uint32_t) * 256 + sizeof(float) * 2 * span;
-        const dim3 grid((total + kColorPxPerWg - 1) / kColorPxPerWg);
-        hipLaunchKernelGGL(k_color_minmax, dim3(chunks, nf), dim3(kColorThreads), 0, st, s, n, ctx->color_slab);
-        with_bool((uintptr_t)s % 16 == 0 && (uintptr_t)o % 4 == 0, [&](auto aligned) {
-            hipLaunchKernelGGL(k_color_map<decltype(aligned)::value>, grid, dim3(kColorThreads), lds, st, s, n, total, ctx->color_slab, chunks, o);
+    const plan::ColorPlan pl = plan::plan_colorize((uint32_t)rows * (uint32_t)cols, batch, (uintptr_t)d_src, (uintptr_t)d_bgr);
+    for (uint32_t i = 0; i < pl.count; ++i) {
+        const plan::ColorSegment sg = pl.segment(i);
+        const float* s = d_src + (size_t)sg.first * pl.n;
+        uint8_t* o = d_bgr + (size_t)3 * sg.first * pl.n;
+        hipLaunchKernelGGL(k_color_minmax, dim3(sg.minmax_x, sg.minmax_y), dim3(kColorThreads), 0, st, s, pl.n, ctx->color_slab);
+        with_bool(sg.aligned, [&](auto aligned) {
+            hipLaunchKernelGGL(k_color_map<decltype(aligned)::value>, dim3(sg.map_grid), dim3(kColorThreads), sg.lds, st, s, pl.n, sg.total, ctx->color_slab,
+                               pl.chunks, o);
         });
         DCMT_HIP(ctx, hipGetLastError());
     }
@@ -537,27 +531,18 @@ int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool fo
 
 int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag)
 {
-    int need_bits = 1;
-    while (need_bits < 31 && ((size_t)1 << need_bits) <= n_index) ++need_bits;
-    if (need_bits > 30) return DCMT_E_INVALID;
-    bool fresh = false;
-    DCMT_TRY(ctx->winner.reserve(ctx, n_px, &fresh));
-    if (fresh) { ctx->winner_bits = 0; ctx->winner_gen = 0; }
-    const bool relayout = need_bits > ctx->winner_bits;
-    if (relayout) ctx->winner_bits = need_bits < 24 ? 24 : need_bits;       // (room for 16 M indices per call before the next re-layout)
-    const unsigned gen_max = (1u << (32 - ctx->winner_bits)) - 1u;
-    if (relayout || ctx->winner_gen == 0 || ctx->winner_gen >= gen_max) {
+    const bool fresh = n_px > ctx->winner.n;                // what reserve is about to replace
+    const plan::Winner w = plan::winner_next(ctx->winner_bits, ctx->winner_gen, fresh, n_index);
+    if (w.status != DCMT_OK) return w.status;
+    DCMT_TRY(ctx->winner.reserve(ctx, n_px));
+    if (w.clear) {
+        ctx->winner_gen = 0;                                // (a clear that fails is tried again by the next call)
         DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner.n, st));
-        ctx->winner_gen = 0;
     }
-    *gen_tag = ++ctx->winner_gen << ctx->winner_bits;
+    ctx->winner_bits = w.bits;
+    ctx->winner_gen = w.gen;
+    *gen_tag = w.tag;
     return DCMT_OK;
-}
-
-void frame_chunks(uint32_t n, uint32_t* chunks, uint32_t* groups)
-{
-    *chunks = eval_chunks(n);
-    *groups = eval_chunk_groups(n);
 }
 
 }  // namespace dcmt
@@ -721,8 +706,7 @@ int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t*
     if (n_points > 0)
         hipLaunchKernelGGL(k_project_scatter, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, M,
                            winner, rows, cols, gen_tag);
-    const int vec = n_px % 4 == 0 && (uintptr_t)d_sparse % 16 == 0 ? 4 : n_px % 2 == 0 && (uintptr_t)d_sparse % 8 == 0 ? 2 : 1;     // pixels per thread
-    with_value<4, 2, 1>(vec, [&](auto v) {
+    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_sparse), [&](auto v) {
         hipLaunchKernelGGL(k_project_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px,
                            gen_tag, ctx->winner_bits);
     });
@@ -747,10 +731,11 @@ int dcmt_stereo_refine_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (params->iterations > 1000) return DCMT_E_INVALID;
     StereoP P{params->baseline, params->focal, params->damp, params->max_depth, params->iterations < 0 ? 4 : params->iterations};
-    if (rows > 65535 || batch > 65535) return DCMT_E_INVALID;                  // grid dimensions y, z
-    const dim3 sg((cols + 255) / 256, rows, batch), sg1(1, rows, batch);
-    if (cols + 4 <= 48 * 1024)      // the right-image row fits the workgroup's LDS: one workgroup stages it and walks the whole row
-        hipLaunchKernelGGL(k_stereo_refine<true>, sg1, dim3(256), (size_t)cols + 4, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
+    const plan::StereoPlan pl = plan::plan_stereo(rows, cols, batch);
+    if (pl.status != DCMT_OK) return pl.status;
+    const dim3 sg(pl.gx, pl.gy, pl.gz);
+    if (pl.lds_row)
+        hipLaunchKernelGGL(k_stereo_refine<true>, sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
     else
         hipLaunchKernelGGL(k_stereo_refine<false>, sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
     DCMT_HIP(ctx, hipGetLastError());
@@ -788,14 +773,7 @@ void dcmt_colormap_jet(uint8_t bgr[768])
     }
 }
 
-int dcmt_slic_num_centers(int rows, int cols, int step)
-{
-    if (rows < 1 || cols < 1 || step < 1) return 0;
-    int nx = 0, ny = 0;
-    for (int i = step; i < cols - step / 2; i += step) ++nx;     // slic.cpp:33-34
-    for (int j = step; j < rows - step / 2; j += step) ++ny;
-    return nx * ny;
-}
+int dcmt_slic_num_centers(int rows, int cols, int step) { return plan::slic_num_centers(rows, cols, step); }
 
 int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols, int batch, int step, int nc,
                          int32_t* d_labels, double* d_centers, void* stream)
@@ -804,46 +782,35 @@ int dcmt_slic_labels_dev(dcmt_ctx* ctx, const uint8_t* d_lab, int rows, int cols
     if (!ctx || !d_lab || !d_labels) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (step < 6 || nc < 1) return DCMT_E_INVALID;
-    const int n = dcmt_slic_num_centers(rows, cols, step);
     hipStream_t st = (hipStream_t)stream;
-    const size_t px = (size_t)batch * rows * cols;
-    if (n == 0) { DCMT_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, sizeof(int32_t) * px, st)); return DCMT_OK; }
-    int cell_px = step;                                                    // cells of step x step pixels
-    { const char* e = std::getenv("DCMT_SLIC_CELL_SCALE"); if (e && std::atoi(e) > 1) cell_px = step * std::atoi(e); }   // tests: crowded cells
-    const int gx = (cols - 1) / cell_px + 1, gy = (rows - 1) / cell_px + 1;
-    const size_t cells = (size_t)gx * gy;
-    // two cell sets (the assignment reads one while the next centres are binned into the other); per set [batch][cells] counts
-    // with the [batch] overflow flags right behind, and [batch][cells][kSlicCellCap] centre indices
-    DCMT_TRY(ctx->slic_cells.reserve(ctx, 2 * ((size_t)ctx->max_batch * cells * (1 + kSlicCellCap) + ctx->max_batch)));
-    const size_t n_cnt = (size_t)batch * cells + batch;
-    int* set_cnt[2] = {ctx->slic_cells, ctx->slic_cells + n_cnt};
-    int* set_ovf[2] = {set_cnt[0] + (size_t)batch * cells, set_cnt[1] + (size_t)batch * cells};
-    int* set_list[2] = {ctx->slic_cells + 2 * n_cnt, ctx->slic_cells + 2 * n_cnt + (size_t)batch * cells * kSlicCellCap};
-    const size_t cn = (size_t)n * ctx->max_batch;                          // the three centre buffers grow together
-    DCMT_TRY(ctx->slic_centers[0].reserve(ctx, 5 * cn));
-    DCMT_TRY(ctx->slic_centers[1].reserve(ctx, 5 * cn));
-    DCMT_TRY(ctx->slic_sums.reserve(ctx, 6 * cn));
-    DCMT_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, sizeof(int32_t) * px, st));                    // clusters = -1 (slic.cpp:24)
-    DCMT_HIP(ctx, hipMemsetAsync(set_cnt[0], 0, sizeof(int) * 2 * n_cnt, st));                  // both cell sets' counts and flags
-    DCMT_HIP(ctx, hipMemsetAsync(ctx->slic_sums, 0, sizeof(unsigned long long) * 6 * (size_t)n * batch, st));   // every iteration leaves them zeroed
-    hipLaunchKernelGGL(k_slic_init, dim3((n + 63) / 64, batch), dim3(64), 0, st, d_lab, ctx->slic_centers[0], rows, cols, step, n,
+    const char* e_scale = std::getenv("DCMT_SLIC_CELL_SCALE");
+    const char* e_th = std::getenv("DCMT_SLIC_TH");
+    const plan::SlicPlan pl = plan::plan_slic(rows, cols, batch, ctx->max_batch, step, e_scale ? std::atoi(e_scale) : 0, e_th ? std::atoi(e_th) : 0);
+    const int n = pl.n, cell_px = pl.cell_px, gx = pl.gx, gy = pl.gy;
+    if (n == 0) { DCMT_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, sizeof(int32_t) * pl.clear_labels, st)); return DCMT_OK; }
+    DCMT_TRY(ctx->slic_cells.reserve(ctx, pl.reserve_cells));
+    DCMT_TRY(ctx->slic_centers[0].reserve(ctx, pl.reserve_centers));
+    DCMT_TRY(ctx->slic_centers[1].reserve(ctx, pl.reserve_centers));
+    DCMT_TRY(ctx->slic_sums.reserve(ctx, pl.reserve_sums));
+    int* const cells = ctx->slic_cells;
+    int* set_cnt[2] = {cells + pl.cnt[0], cells + pl.cnt[1]};
+    int* set_ovf[2] = {cells + pl.ovf[0], cells + pl.ovf[1]};
+    int* set_list[2] = {cells + pl.list[0], cells + pl.list[1]};
+    DCMT_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, sizeof(int32_t) * pl.clear_labels, st));                  // clusters = -1 (slic.cpp:24)
+    DCMT_HIP(ctx, hipMemsetAsync(set_cnt[0], 0, sizeof(int) * pl.clear_cnt, st));                          // both cell sets' counts and flags
+    DCMT_HIP(ctx, hipMemsetAsync(ctx->slic_sums, 0, sizeof(unsigned long long) * pl.clear_sums, st));      // every iteration leaves them zeroed
+    hipLaunchKernelGGL(k_slic_init, dim3(pl.init_x, batch), dim3(64), 0, st, d_lab, ctx->slic_centers[0], rows, cols, step, n,
                        set_cnt[0], set_list[0], set_ovf[0], cell_px, gx, gy);
-    const size_t nb_threads = std::max((size_t)n * batch, n_cnt);
-    // tile height: the tallest the step allows, unless that leaves the GPU short of workgroups (a caller streaming single frames:
-    // 114 tiles of 64 x 64 per 1216 x 352 image for 256 CUs) -- then shorter tiles, more of them, shorter columns per thread
-    int th = slic_tile_rows(cell_px);
-    { const char* e = std::getenv("DCMT_SLIC_TH"); if (e && (std::atoi(e) == 16 || std::atoi(e) == 32 || std::atoi(e) == 64) && std::atoi(e) <= th) th = std::atoi(e);
-      else while (th > 16 && (size_t)((cols + kSlicTW - 1) / kSlicTW) * ((rows + th - 1) / th) * batch < 1024) th /= 2; }
     for (int it = 0; it < 10; ++it) {                                                           // NR_ITERATIONS (slic.h:20)
         double* cur = ctx->slic_centers[it & 1];
         double* nxt = ctx->slic_centers[(it + 1) & 1];
         const int a = it & 1, b = a ^ 1;
-        with_value<64, 32, 16>(th, [&](auto h) {
-            hipLaunchKernelGGL(k_slic_assign<decltype(h)::value>, dim3((cols + kSlicTW - 1) / kSlicTW, (rows + h - 1) / h, batch), dim3(256), 0, st, d_lab, cur,
+        with_value<64, 32, 16>(pl.th, [&](auto h) {
+            hipLaunchKernelGGL(k_slic_assign<decltype(h)::value>, dim3(pl.tiles_x, pl.tiles_y, batch), dim3(256), 0, st, d_lab, cur,
                                set_cnt[a], set_list[a], set_ovf[a], d_labels, ctx->slic_sums, rows, cols, step, nc, n, gx, gy, cell_px);
         });
-        hipLaunchKernelGGL(k_slic_norm_bin, dim3((unsigned)((nb_threads + 255) / 256)), dim3(256), 0, st, ctx->slic_sums, nxt, n, batch,
-                           set_cnt[b], set_list[b], set_ovf[b], set_cnt[a], (int)n_cnt, cell_px, gx, gy);
+        hipLaunchKernelGGL(k_slic_norm_bin, dim3(pl.bin_x), dim3(256), 0, st, ctx->slic_sums, nxt, n, batch,
+                           set_cnt[b], set_list[b], set_ovf[b], set_cnt[a], (int)pl.n_cnt, cell_px, gx, gy);
         DCMT_HIP(ctx, hipGetLastError());
     }
     if (d_centers)       // ten iterations: the final centres are back in buffer 0

@@ -1,10 +1,12 @@
 // dcmt_cloud.h -- what the kernels of dcmt_kernels_cloud.h / dcmt_kernels_reproject.h (compiled in dcmt_cloud.hip, a code object of
-// their own) share with the host code that sizes their scratch and fills their arguments.
+// their own) share with the host code that sizes their scratch and grids (dcmt_plan_side.h) and fills their arguments.  No HIP.
 #pragma once
 
 namespace dcmt {
 
 constexpr int kCloudWaves = 4;                  // waves per workgroup of k_cloud_count / k_cloud_scatter = slab entries per (frame, chunk)
+constexpr int kGaussCols = 60, kGaussRows = 32; // k_gauss5: output columns of a wave's strip, output rows of its band at most
+constexpr int kReprojectPxPerWg = 1024;         // k_reproject_scatter: 256 threads x 4 source pixels
 
 struct CloudK { double fx, fy, cx, cy; };
 

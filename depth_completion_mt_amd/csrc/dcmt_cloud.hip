@@ -4,6 +4,8 @@
 // are in dcmt_host.hip.
 #include <algorithm>
 
+#include "dcmt_chunks.h"
+#include "dcmt_plan_side.h"
 #include "dcmt_ctx.h"
 #include "dcmt_kernels_cloud.h"
 #include "dcmt_kernels_reproject.h"
@@ -30,12 +32,10 @@ int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* 
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
     if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
-    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
-    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, room = (uint32_t)std::min<int64_t>(capacity, INT32_MAX);
-    uint32_t chunks, groups;
-    frame_chunks(n, &chunks, &groups);
+    const uint32_t chunks = eval_chunks(n), groups = eval_chunk_groups(n);
     const CloudK k = {params->fx, params->fy, params->cx, params->cy};
     const dim3 grid(chunks, batch);
     const uint32_t per = chunks * kCloudWaves;      // slab: [batch][chunks][kCloudWaves] uint32
@@ -63,12 +63,8 @@ int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows
     const bool in_place = d_dst == d_src;
     if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
     float* out = in_place ? ctx->pp[0] : d_dst;
-    const int strips = (cols + kGaussCols - 1) / kGaussCols;
-    int band_rows = kGaussRows;                      // shorter bands while the call makes fewer than ~2 waves per SIMD
-    while (band_rows > 8 && (size_t)strips * ((rows + band_rows - 1) / band_rows) * batch < 2048) band_rows /= 2;
-    const int bands = (rows + band_rows - 1) / band_rows;
-    hipLaunchKernelGGL(k_gauss5, dim3((unsigned)(((size_t)strips * bands + 3) / 4), batch), dim3(256), 0, st, d_src, out, rows, cols, strips, bands,
-                       band_rows);
+    const plan::GaussPlan pl = plan::plan_gauss5(rows, cols, batch);
+    hipLaunchKernelGGL(k_gauss5, dim3(pl.grid_x, batch), dim3(256), 0, st, d_src, out, rows, cols, pl.strips, pl.bands, pl.band_rows);
     DCMT_HIP(ctx, hipGetLastError());
     if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
     return DCMT_OK;
@@ -96,8 +92,7 @@ int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int 
     if (!ctx || !d_depth || !d_out || !params) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
     if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
-    if (!finite_bits64(params->fx) || !finite_bits64(params->fy) || !finite_bits64(params->cx) || !finite_bits64(params->cy)) return DCMT_E_INVALID;
-    if (params->fx == 0.0 || params->fy == 0.0) return DCMT_E_INVALID;
+    if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
     for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
     for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
@@ -113,8 +108,7 @@ int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int 
     if (rc != DCMT_OK) return rc;
     hipLaunchKernelGGL(k_reproject_scatter, dim3((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch), dim3(256), 0, st, d_depth, n,
                        (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
-    const int vec = n_px % 4 == 0 && (uintptr_t)d_out % 16 == 0 ? 4 : n_px % 2 == 0 && (uintptr_t)d_out % 8 == 0 ? 2 : 1;       // pixels per thread
-    with_value<4, 2, 1>(vec, [&](auto v) {
+    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
         hipLaunchKernelGGL(k_reproject_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k,
                            ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
     });

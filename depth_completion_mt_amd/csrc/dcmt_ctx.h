@@ -193,17 +193,20 @@ inline bool finite_bits64(double v)
     return (b & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }
 
+// pinhole intrinsics the point cloud and the reprojection can divide by
+DCMT_LOCAL inline bool intrinsics_ok(double fx, double fy, double cx, double cy)
+{
+    return finite_bits64(fx) && finite_bits64(fy) && finite_bits64(cx) && finite_bits64(cy) && fx != 0.0 && fy != 0.0;
+}
+
 // The winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev: tags of generation g = (g << idx_bits) | index, g >= 1
 // (0 = the cleared plane); the index is N2's global point index or the reprojection's frame-local source pixel index.  A call only
 // looks at tags of its own generation, so the plane is not cleared between calls, whichever of the two they are.  It is cleared when
 // it is (re)allocated, when a call needs more index bits than its layout has, and when the generations run out.  n_px: entries
 // this call needs; n_index: it stores indices below n_index (N2 keeps its bound of <= n_index).  Any allocation happens here, before
-// the call has enqueued anything.  Returns the call's generation, shifted into place.  Defined in dcmt.hip.
+// the call has enqueued anything.  Returns the call's generation, shifted into place.  The state's step is plan::winner_next
+// (dcmt_plan_side.h); this function, defined in dcmt.hip, reserves and clears as it says.
 int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag);
-
-// eval_chunks(n) and eval_chunk_groups(n) of dcmt_kernels_eval.h, for a translation unit that must not compile that header's
-// kernels (dcmt_cloud.hip, whose kernels walk a frame in the same chunks).  Defined in dcmt.hip.
-void frame_chunks(uint32_t n, uint32_t* chunks, uint32_t* groups);
 
 // What a completion call is given: device pointers (src or src16; labels only where they are used) and the batch's shape
 struct Frames {

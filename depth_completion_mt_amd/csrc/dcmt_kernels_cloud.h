@@ -223,7 +223,7 @@ void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict_
 // neighbours come through lane shuffles, the row pass results of the last 5 rows stay in registers for the column pass.  No LDS,
 // no barrier; the loads of kGaussBatch rows go out together.  src and dst must not overlap (the entry point sends an in-place
 // call through scratch).
-constexpr int kGaussCols = 60, kGaussRows = 32, kGaussBatch = 6;
+constexpr int kGaussBatch = 6;      // (kGaussCols, kGaussRows: dcmt_cloud.h)
 
 // grid (ceil(strips * bands / 4), frames), 256 threads: one wave per (strip, band); strips = ceil(cols / kGaussCols),
 // bands = ceil(rows / band_rows)

@@ -37,13 +37,9 @@
 #include <stdint.h>
 
 #include "dcmt_kernels_eval.h"
+#include "dcmt_tiles.h"        // kColorThreads, kColorGroupsPerLane, kColorPxPerWg, kColorSlabStride
 
 namespace dcmt {
-
-constexpr int kColorThreads = 256;
-constexpr int kColorGroupsPerLane = 4;
-constexpr uint32_t kColorPxPerWg = 4u * kColorGroupsPerLane * kColorThreads;    // 4096 pixels per map workgroup
-constexpr int kColorSlabStride = 2;                                            // floats per slab entry: min, max
 
 // cv::COLORMAP_JET, index order, packed b | g << 8 | r << 16 (tests/golden/jet_lut.json, which stores [B, G, R] triples)
 #define DCMT_JET_BGR_PACKED \

@@ -17,24 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "dcmt_chunks.h"
+
 namespace dcmt {
 
-constexpr int kEvalThreads = 256;
-constexpr uint32_t kEvalGroupsPerChunk = 2048;       // 8192 pixels per workgroup: 53 chunks for a 352 x 1216 frame
-constexpr uint32_t kEvalMaxChunks = 1024;
 constexpr int kEvalSlabStride = 8;                  // doubles per slab entry (7 used): 64-byte entries
-
-__host__ __device__ inline uint32_t eval_chunks(uint32_t n)
-{
-    const uint32_t ng = (n + 3) / 4;
-    const uint32_t c = (ng + kEvalGroupsPerChunk - 1) / kEvalGroupsPerChunk;
-    return c < kEvalMaxChunks ? c : kEvalMaxChunks;
-}
-__host__ __device__ inline uint32_t eval_chunk_groups(uint32_t n)
-{
-    const uint32_t ng = (n + 3) / 4, c = eval_chunks(n);
-    return (ng + c - 1) / c;
-}
 
 struct EvalAcc {
     int n = 0, n_inv = 0;

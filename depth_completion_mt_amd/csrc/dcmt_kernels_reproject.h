@@ -31,8 +31,6 @@
 
 namespace dcmt {
 
-constexpr int kReprojectPxPerWg = 1024;        // 256 threads x 4 source pixels
-
 // t_2 of a source pixel: what the scatter stores the index of and the resolve writes
 __device__ __forceinline__ float reproject_t2(const ReprojK& k, uint32_t x, uint32_t y, float z, float& x_, float& y_)
 {

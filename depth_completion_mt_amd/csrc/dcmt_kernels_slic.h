@@ -20,10 +20,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "dcmt_tiles.h"        // kSlicCellCap, kSlicTW, slic_tile_rows
+
 namespace dcmt {
 
 constexpr unsigned long long kSlicDead = 0x7ff8000000000000ull;     // bit pattern of a dead centre's x (a NaN)
-constexpr int kSlicCellCap = 4;                                     // centre indices a cell's list holds
 
 __device__ __forceinline__ double slic_dist(const double* c, int x, int y, const uint8_t* px, double nc, double ns)
 {
@@ -122,11 +123,8 @@ __device__ __forceinline__ bool slic_window(const double* C, int step, int rows,
 // atomics of one instruction are served one lane after the other (measured: a quarter of the kernel at 18-pixel
 // superpixels, half of it at 68).  So a thread works down a column (TH / 4 rows), sums the run of equal winners in
 // registers and adds a run to the table when it ends.  (Several copies of the table, lane & 3: slower -- LDS, occupancy.)
-// Tile height (template parameter TH): as tall as the tile's cells fit -- the staging is paid once per tile and a thread's
-// runs get longer -- 64 rows = 16 per thread for steps from 16 up (at most 7 x 7 staged cells), 32 for steps 11 to 15
-// (9 x 6), 16 for the steps below (6: at most 14 x 6 = 84 of the 128 cells a tile may stage).
-constexpr int kSlicTW = 64, kSlicMaxCells = 128;
-__host__ __device__ constexpr int slic_tile_rows(int step) { return step >= 16 ? 64 : (step >= 11 ? 32 : 16); }
+// Tile height (template parameter TH): slic_tile_rows (dcmt_tiles.h) is the tallest a step allows.
+constexpr int kSlicMaxCells = 128;
 constexpr int kSlicEntries = 128;                                // staged centres per tile, numbered densely (more: slow walk)
 constexpr int kSlicListCap = 9 * kSlicCellCap;
 constexpr int kSlicMaskBits = 32;

@@ -1,0 +1,203 @@
+// dcmt_plan_side.h -- the launch geometry and scratch layout of the entry points beside the cascade, as values: one pure function
+// per entry point that has something to decide; dcmt.hip and dcmt_cloud.hip check, plan, reserve, and then launch what the plan
+// says.  Plain C++17, no HIP, like dcmt_plan.h: tested on a CPU (tests/plan_test.cpp).  The kernels' constants come from the
+// HIP-free headers their kernel headers include; only the two status values are restated (dcmt.hip checks them).
+#ifndef DCMT_PLAN_SIDE_H
+#define DCMT_PLAN_SIDE_H
+
+#include <cstddef>
+#include <cstdint>
+
+#include "dcmt_chunks.h"
+#include "dcmt_cloud.h"
+#include "dcmt_tiles.h"
+
+#pragma GCC visibility push(hidden)       // internal names: none of them in libdcmt_hip.so's dynamic symbol table
+namespace dcmt {
+namespace plan {
+
+constexpr int kOk = 0, kInvalid = -1;        // dcmt.h: DCMT_OK, DCMT_E_INVALID
+
+// ---- dcmt_colorize_dev --------------------------------------------------------------------------------------------------
+// A min/max pass over the frames, then one map pass over their flat pixel run (dcmt_kernels_color.h).  Batches of 2^31 pixels or
+// more go in segments of whole frames, each a pair of launches of its own: a segment holds at most 2^31 - kColorPxPerWg pixels
+// (32-bit pixel indices, the last workgroup's overhang included).  All segments but the last have `seg` frames, a multiple of 4
+// where the cap allows 4, so that they start as aligned as the batch does; frames above ~2^29 pixels have a cap of 3, and there a
+// later segment may be less aligned than the first -- `aligned` is decided per segment, from its own addresses.  (Measured, 1024
+// frames of 352 x 1216: segments of 128 / 64 / 32 frames, whose re-read could come from the Infinity Cache, take 0.90 / 0.91 /
+// 1.03 ms against 0.85 ms for the whole batch in one pair.)
+struct ColorSegment {
+    uint32_t first, frames;          // frames [first, first + frames) of the batch
+    uint32_t total;                  // its pixels
+    uint32_t span;                   // frames one map workgroup can touch
+    size_t lds;                      // k_color_map's dynamic LDS: the palette, then (scale, shift) for `span` frames
+    unsigned map_grid;               // k_color_map
+    unsigned minmax_x, minmax_y;     // k_color_minmax: (chunks, frames)
+    bool aligned;                    // k_color_map<true>: source 16-byte, output 4-byte aligned
+};
+
+struct ColorPlan {
+    uint32_t n, batch, chunks;       // pixels per frame, frames, eval_chunks(n)
+    uint32_t seg, count;             // frames per segment (the last one: what is left), segments
+    uintptr_t src, bgr;
+    ColorSegment segment(uint32_t i) const
+    {
+        ColorSegment s;
+        s.first = i * seg;
+        s.frames = batch - s.first < seg ? batch - s.first : seg;
+        s.total = s.frames * n;
+        const uint32_t reach = (kColorPxPerWg - 1) / n + 2;
+        s.span = s.frames < reach ? s.frames : reach;
+        s.lds = sizeof(uint32_t) * 256 + sizeof(float) * 2 * s.span;
+        s.map_grid = (s.total + kColorPxPerWg - 1) / kColorPxPerWg;
+        s.minmax_x = chunks;
+        s.minmax_y = s.frames;
+        s.aligned = (src + sizeof(float) * (size_t)s.first * n) % 16 == 0 && (bgr + (size_t)3 * s.first * n) % 4 == 0;
+        return s;
+    }
+};
+
+// n = rows * cols >= 1 (at most 0x1ffffff0: dcmt_create), batch >= 1
+inline ColorPlan plan_colorize(uint32_t n, int batch, uintptr_t src_addr, uintptr_t bgr_addr)
+{
+    ColorPlan p;
+    p.n = n; p.batch = (uint32_t)batch; p.chunks = eval_chunks(n);
+    p.src = src_addr; p.bgr = bgr_addr;
+    const uint32_t cap = (0x80000000u - kColorPxPerWg) / n;                 // frames per segment the 32-bit pixel run allows (>= 3)
+    p.seg = p.batch < cap ? p.batch : cap;
+    if (p.seg >= 4 && p.seg < p.batch) p.seg &= ~3u;
+    p.count = (p.batch + p.seg - 1) / p.seg;
+    return p;
+}
+
+// ---- the winner plane of dcmt_project_points_dev and dcmt_reproject_depth_dev (winner_generation, dcmt_ctx.h) -----------
+// One call's step of the plane's state: (bits, gen) = the index bits of the tag layout and the last call's generation, fresh = the
+// plane has just been (re)allocated, n_index = the call stores indices below n_index.  The plane is cleared when it is fresh,
+// when the call needs more index bits than the layout has, and when the generations have run out.
+struct Winner {
+    int status;                      // kInvalid: 2^30 indices or more (nothing else is meaningful then)
+    int bits;
+    unsigned gen;
+    bool clear;                      // zero the plane before the call's kernels
+    unsigned tag;                    // gen << bits
+};
+
+inline Winner winner_next(int bits, unsigned gen, bool fresh, size_t n_index)
+{
+    int need_bits = 1;
+    while (need_bits < 31 && ((size_t)1 << need_bits) <= n_index) ++need_bits;
+    if (need_bits > 30) return {kInvalid, bits, gen, false, 0};
+    if (fresh) { bits = 0; gen = 0; }
+    const bool relayout = need_bits > bits;
+    if (relayout) bits = need_bits < 24 ? 24 : need_bits;                  // (room for 16 M indices per call before the next re-layout)
+    const unsigned gen_max = (1u << (32 - bits)) - 1u;
+    const bool clear = relayout || gen == 0 || gen >= gen_max;
+    gen = clear ? 1 : gen + 1;
+    return {kOk, bits, gen, clear, gen << bits};
+}
+
+// k_project_resolve / k_reproject_resolve: pixels per thread, as wide as the pixel count and the output's address allow
+inline int resolve_vec(size_t n_px, uintptr_t addr)
+{
+    return n_px % 4 == 0 && addr % 16 == 0 ? 4 : n_px % 2 == 0 && addr % 8 == 0 ? 2 : 1;
+}
+
+// ---- dcmt_slic_labels_dev -----------------------------------------------------------------------------------------------
+inline int slic_num_centers(int rows, int cols, int step)
+{
+    if (rows < 1 || cols < 1 || step < 1) return 0;
+    int nx = 0, ny = 0;
+    for (int i = step; i < cols - step / 2; i += step) ++nx;     // slic.cpp:33-34
+    for (int j = step; j < rows - step / 2; j += step) ++ny;
+    return nx * ny;
+}
+
+// slic_cells holds two cell sets (the assignment reads one while the next centres are binned into the other), laid out for this
+// call's batch: set 0's counts [batch][cells] with its [batch] overflow flags right behind, set 1's the same, then set 0's and
+// set 1's centre indices [batch][cells][kSlicCellCap].  All four buffers are reserved for max_batch frames, so they grow only with
+// the cells / centres per frame.
+struct SlicPlan {
+    int n;                           // centres per frame (0: the call only sets the labels to -1)
+    int cell_px, gx, gy;             // cells of cell_px x cell_px pixels, gx x gy of them
+    size_t cells;
+    size_t cnt[2], ovf[2], list[2];  // element offsets into slic_cells
+    size_t n_cnt;                    // one set's counts and flags (k_slic_norm_bin clears the set it has read)
+    size_t reserve_cells, reserve_centers, reserve_sums;   // slic_cells; slic_centers[0] and [1] each; slic_sums
+    size_t clear_labels, clear_cnt, clear_sums;            // elements the three memsets cover: d_labels; both sets' counts and flags, from cnt[0]; slic_sums
+    int th;                          // tile height of k_slic_assign: 64, 32 or 16
+    unsigned tiles_x, tiles_y;       // k_slic_assign: (tiles_x, tiles_y, batch)
+    unsigned init_x;                 // k_slic_init: (init_x, batch), 64 threads
+    size_t nb_threads;               // k_slic_norm_bin: one thread per centre and per count / flag
+    unsigned bin_x;
+};
+
+// cell_scale > 1: cells of cell_scale x step pixels (crowded cells, for tests); th_override: 16, 32 or 64 where the step allows it
+// (the DCMT_SLIC_CELL_SCALE / DCMT_SLIC_TH values of the call, 0 where unset)
+inline SlicPlan plan_slic(int rows, int cols, int batch, int max_batch, int step, int cell_scale, int th_override)
+{
+    SlicPlan p;
+    const size_t b = (size_t)batch, mb = (size_t)max_batch;
+    p.n = slic_num_centers(rows, cols, step);
+    p.cell_px = cell_scale > 1 ? step * cell_scale : step;
+    p.gx = (cols - 1) / p.cell_px + 1; p.gy = (rows - 1) / p.cell_px + 1;
+    p.cells = (size_t)p.gx * p.gy;
+    p.n_cnt = b * p.cells + b;
+    p.cnt[0] = 0; p.cnt[1] = p.n_cnt;
+    p.ovf[0] = p.cnt[0] + b * p.cells; p.ovf[1] = p.cnt[1] + b * p.cells;
+    p.list[0] = 2 * p.n_cnt; p.list[1] = p.list[0] + b * p.cells * kSlicCellCap;
+    p.reserve_cells = 2 * (mb * p.cells * (1 + kSlicCellCap) + mb);
+    p.reserve_centers = 5 * (size_t)p.n * mb;                              // the three centre buffers grow together
+    p.reserve_sums = 6 * (size_t)p.n * mb;
+    p.clear_labels = b * rows * cols;
+    p.clear_cnt = 2 * p.n_cnt;
+    p.clear_sums = 6 * (size_t)p.n * b;
+    // tile height: the tallest the step allows, unless that leaves the GPU short of workgroups (a caller streaming single frames:
+    // 114 tiles of 64 x 64 per 1216 x 352 image for 256 CUs) -- then shorter tiles, more of them, shorter columns per thread
+    p.tiles_x = (unsigned)((cols + kSlicTW - 1) / kSlicTW);
+    p.th = slic_tile_rows(p.cell_px);
+    if ((th_override == 16 || th_override == 32 || th_override == 64) && th_override <= p.th) p.th = th_override;
+    else while (p.th > 16 && (size_t)p.tiles_x * ((rows + p.th - 1) / p.th) * b < 1024) p.th /= 2;
+    p.tiles_y = (unsigned)((rows + p.th - 1) / p.th);
+    p.init_x = (unsigned)((p.n + 63) / 64);
+    p.nb_threads = (size_t)p.n * b > p.n_cnt ? (size_t)p.n * b : p.n_cnt;
+    p.bin_x = (unsigned)((p.nb_threads + 255) / 256);
+    return p;
+}
+
+// ---- dcmt_gaussian5_dev -------------------------------------------------------------------------------------------------
+struct GaussPlan {
+    int strips, band_rows, bands;    // one wave per (strip of kGaussCols columns, band of band_rows rows)
+    unsigned grid_x;                 // k_gauss5: (grid_x, batch), four waves per workgroup
+};
+
+inline GaussPlan plan_gauss5(int rows, int cols, int batch)
+{
+    GaussPlan p;
+    p.strips = (cols + kGaussCols - 1) / kGaussCols;
+    p.band_rows = kGaussRows;                        // shorter bands while the call makes fewer than ~2 waves per SIMD
+    while (p.band_rows > 8 && (size_t)p.strips * ((rows + p.band_rows - 1) / p.band_rows) * batch < 2048) p.band_rows /= 2;
+    p.bands = (rows + p.band_rows - 1) / p.band_rows;
+    p.grid_x = (unsigned)(((size_t)p.strips * p.bands + 3) / 4);
+    return p;
+}
+
+// ---- dcmt_stereo_refine_dev ---------------------------------------------------------------------------------------------
+struct StereoPlan {
+    int status;                      // kInvalid: rows or batch beyond a grid's y / z dimension
+    bool lds_row;                    // k_stereo_refine<true>: the right-image row fits the workgroup's LDS, one workgroup stages it and walks the whole row
+    size_t lds;                      // its dynamic LDS (0 for the global variant)
+    unsigned gx, gy, gz;
+};
+
+inline StereoPlan plan_stereo(int rows, int cols, int batch)
+{
+    if (rows > 65535 || batch > 65535) return {kInvalid, false, 0, 0, 0, 0};
+    const bool lds_row = cols + 4 <= 48 * 1024;
+    return {kOk, lds_row, lds_row ? (size_t)cols + 4 : 0, lds_row ? 1u : (unsigned)((cols + 255) / 256), (unsigned)rows, (unsigned)batch};
+}
+
+}  // namespace plan
+}  // namespace dcmt
+#pragma GCC visibility pop
+
+#endif
