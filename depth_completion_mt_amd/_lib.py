@@ -34,6 +34,7 @@ EXPORTS = (
     "dcmt_colorize_dev", "dcmt_colorize", "dcmt_colormap_jet",
     "dcmt_default_cloud_params", "dcmt_depth_to_cloud_dev", "dcmt_depth_to_cloud", "dcmt_gaussian5_dev", "dcmt_gaussian5",
     "dcmt_default_reproject_params", "dcmt_reproject_depth_dev", "dcmt_reproject_depth",
+    "dcmt_bgr_convert_dev", "dcmt_bgr_convert", "dcmt_lab_tables",
 )
 
 
@@ -170,6 +171,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_default_reproject_params.restype = None
         L.dcmt_reproject_depth_dev.argtypes = [vp, vp, i, i, i, vp, vp, i, i, vp]
         L.dcmt_reproject_depth.argtypes = [vp, vp, sz, i, i, vp, vp, sz, i, i]
+        L.dcmt_bgr_convert_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_bgr_convert.argtypes = [vp, vp, sz, i, i, vp, sz, vp, sz]
+        L.dcmt_lab_tables.argtypes = [vp, vp, vp]
+        L.dcmt_lab_tables.restype = None
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

@@ -9,6 +9,8 @@
         reference: src/DC_lidar_only/main.cpp:16, src/DC_lidar_camera/main_lc.cpp:85, src/DC_stereo_lidar/main_sl.cpp:1031
     to_color_image(r_img) -> the BGR JET image the reference's toColorImage makes
         reference: src/DC_lidar_only/main.cpp:6-14
+    bgr_to_lab(img) / bgr_to_gray(img) -> the 8-bit Lab / grey image cv::cvtColor makes of a camera frame
+        reference: src/DC_lidar_camera/main_lc.cpp:183, src/DC_stereo_lidar/main_sl.cpp:439, :1167, :1171
     reproject_pc_colors(depth, bgr) / reproject_pc(depth) -> the ordered point cloud of a dense plane
         reference: src/DC_stereo_lidar/main_sl.cpp:924-965, :887-922
     unrectify_sol(depth_pre_optim, out_shape, R_rect) -> the plane forward-warped into the un-rectified camera's frame
@@ -354,6 +356,43 @@ class Context:
         _check(st, "dcmt_colorize")
         return out
 
+    # ---- camera BGR bytes -> 8-bit Lab and grey planes (dcmt_bgr_convert*) ---------------------------------------
+    def bgr_convert_dev(self, d_bgr, lab: bool = True, gray: bool = False, d_lab=None, d_gray=None, stream: int | None = None):
+        """cv::cvtColor(BGR2Lab) and / or cv::cvtColor(BGR2GRAY) on the device (dcmt_bgr_convert_dev; LC/main_lc.cpp:183,
+        SL/main_sl.cpp:439, :1167, :1171), one read of the image for both.  d_bgr: contiguous uint8 CUDA tensor
+        [batch][rows][cols][3] (or [rows][cols][3]), B, G, R.  Returns the Lab tensor (d_bgr's shape: what slic_labels_dev takes),
+        the grey tensor (d_bgr's shape without the 3: what stereo_refine_dev takes), or (lab, grey) where both are wanted, without
+        synchronising.  A d_lab / d_gray that is given is written and wanted; d_lab may be d_bgr (in place)."""
+        import torch
+        assert _is_dev(d_bgr, torch.uint8) and d_bgr.shape[-1] == 3
+        b, r, c = _brc(d_bgr, 1)
+        lab, gray = lab or d_lab is not None, gray or d_gray is not None
+        if lab and d_lab is None:
+            d_lab = torch.empty_like(d_bgr)
+        if gray and d_gray is None:
+            d_gray = torch.empty(tuple(d_bgr.shape[:-1]), dtype=torch.uint8, device=d_bgr.device)
+        assert d_lab is None or (_is_dev(d_lab, torch.uint8) and d_lab.numel() == 3 * b * r * c)
+        assert d_gray is None or (_is_dev(d_gray, torch.uint8) and d_gray.numel() == b * r * c)
+        st = L.lib().dcmt_bgr_convert_dev(self._h, d_bgr.data_ptr(), r, c, b, d_lab.data_ptr() if lab else None,
+                                          d_gray.data_ptr() if gray else None, _stream(stream, d_bgr))
+        _check(st, "dcmt_bgr_convert_dev")
+        return (d_lab, d_gray) if lab and gray else d_lab if lab else d_gray
+
+    def bgr_convert(self, frame: np.ndarray, lab: bool = True, gray: bool = False):
+        """One frame of host memory (dcmt_bgr_convert, synchronous; any row stride): uint8 [rows][cols][3] B, G, R -> the Lab
+        frame, the grey frame [rows][cols], or (lab, grey)."""
+        a = np.asarray(frame, dtype=np.uint8)
+        assert a.ndim == 3 and a.shape[2] == 3 and (lab or gray)
+        if a.strides[1] != 3 or a.strides[2] != 1:
+            a = np.ascontiguousarray(a)
+        o_lab = np.empty(a.shape, dtype=np.uint8) if lab else None
+        o_gray = np.empty(a.shape[:2], dtype=np.uint8) if gray else None
+        st = L.lib().dcmt_bgr_convert(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1],
+                                      o_lab.ctypes.data if lab else None, o_lab.strides[0] if lab else 0,
+                                      o_gray.ctypes.data if gray else None, o_gray.strides[0] if gray else 0)
+        _check(st, "dcmt_bgr_convert")
+        return (o_lab, o_gray) if lab and gray else o_lab if lab else o_gray
+
     # ---- point cloud of a dense plane (dcmt_depth_to_cloud*) and the blur in front of it (dcmt_gaussian5*) -----------
     def depth_to_cloud_dev(self, d_depth, d_bgr=None, params: L.CloudParams | None = None, d_points=None, d_offsets=None,
                            capacity: int | None = None, stream: int | None = None):
@@ -528,6 +567,27 @@ def to_color_image(r_img):
         return _ctx_for(r_img.shape[-2], r_img.shape[-1], b, r_img.device.index or 0).colorize_dev(r_img)
     a = np.asarray(r_img, dtype=np.float32)
     return _ctx_for(a.shape[0], a.shape[1], 1).colorize(a)
+
+
+def _bgr_convert(img, lab: bool):
+    if hasattr(img, "is_cuda") and img.is_cuda:
+        b = 1 if img.dim() == 3 else img.shape[0]
+        return _ctx_for(img.shape[-3], img.shape[-2], b, img.device.index or 0).bgr_convert_dev(img, lab=lab, gray=not lab)
+    a = np.asarray(img, dtype=np.uint8)
+    return _ctx_for(a.shape[0], a.shape[1], 1).bgr_convert(a, lab=lab, gray=not lab)
+
+
+def bgr_to_lab(img):
+    """cv::cvtColor(img, lab, cv::COLOR_BGR2Lab) on 8-bit pixels (LC/main_lc.cpp:183, SL/main_sl.cpp:439): uint8 [rows][cols][3]
+    B, G, R -> L * 255 / 100, a + 128, b + 128.  A numpy frame goes through the host entry point; a CUDA tensor ([rows][cols][3] or
+    [batch][rows][cols][3]) through the device one, on torch's current stream, and comes back as a CUDA tensor without synchronising."""
+    return _bgr_convert(img, True)
+
+
+def bgr_to_gray(img):
+    """cv::cvtColor(img, gray, cv::COLOR_BGR2GRAY) on 8-bit pixels (SL/main_sl.cpp:1167, :1171): uint8 [...][rows][cols][3] ->
+    [...][rows][cols]; numpy or CUDA tensor, as bgr_to_lab."""
+    return _bgr_convert(img, False)
 
 
 def reproject_pc_colors(depth, bgr):

@@ -1,12 +1,13 @@
-// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h and dcmt_kernels_reproject.h, a code object of their own, and the entry
-// points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev and the defaults of their
-// parameter structs.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h and dcmt_kernels_bgr.h, a code object of their
+// own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
+// dcmt_bgr_convert_dev, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
 #include "dcmt_chunks.h"
 #include "dcmt_plan_side.h"
 #include "dcmt_ctx.h"
+#include "dcmt_kernels_bgr.h"
 #include "dcmt_kernels_cloud.h"
 #include "dcmt_kernels_reproject.h"
 
@@ -114,6 +115,38 @@ int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int 
     });
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+// k_bgr_convert (dcmt_kernels_bgr.h) over the batch as one flat run of pixels, a launch per segment (plan_bgr_convert)
+int dcmt_bgr_convert_dev(dcmt_ctx* ctx, const uint8_t* d_bgr, int rows, int cols, int batch, uint8_t* d_lab, uint8_t* d_gray, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_bgr || (!d_lab && !d_gray)) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const plan::BgrPlan pl = plan::plan_bgr_convert((size_t)batch * rows * cols, (uintptr_t)d_bgr, (uintptr_t)d_lab, (uintptr_t)d_gray);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    for (size_t i = 0; i < pl.count; ++i) {
+        const plan::BgrSegment sg = pl.segment(i);
+        const uint8_t* src = d_bgr + 3 * sg.first;
+        uint8_t* lab = d_lab ? d_lab + 3 * sg.first : nullptr;
+        uint8_t* gray = d_gray ? d_gray + sg.first : nullptr;
+        with_value<7, 6, 5, 3, 2, 1>((d_lab ? 1 : 0) | (d_gray ? 2 : 0) | (pl.aligned ? 4 : 0), [&](auto v) {
+            constexpr int m = decltype(v)::value;
+            hipLaunchKernelGGL((k_bgr_convert<(m & 1) != 0, (m & 2) != 0, (m & 4) != 0>), dim3(sg.grid), dim3(kBgrThreads), 0, st, src, sg.total, pl.passes, lab, gray);
+        });
+        DCMT_HIP(ctx, hipGetLastError());
+    }
+    return DCMT_OK;
+}
+
+void dcmt_lab_tables(uint16_t gamma[256], uint16_t cbrt[3072], int32_t coef[9])
+{
+    static const LabTables t = {{DCMT_LAB_GAMMA}, {DCMT_LAB_CBRT}};
+    static const int32_t c[9] = {DCMT_LAB_COEF};
+    if (gamma) std::memcpy(gamma, t.gamma, sizeof t.gamma);
+    if (cbrt) std::memcpy(cbrt, t.cbrt, sizeof t.cbrt);
+    if (coef) std::memcpy(coef, c, sizeof c);
 }
 
 }  // extern "C"

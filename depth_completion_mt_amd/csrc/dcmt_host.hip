@@ -231,4 +231,14 @@ int dcmt_reproject_depth(dcmt_ctx* ctx, const float* depth, size_t drs, int rows
     return rc == DCMT_OK ? fetch(ctx, {&warped}) : rc;
 }
 
+int dcmt_bgr_convert(dcmt_ctx* ctx, const uint8_t* bgr, size_t brs, int rows, int cols, uint8_t* lab, size_t lrs, uint8_t* gray, size_t grs)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !bgr || (!lab && !gray) || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    Plane in(bgr, brs, 3 * (size_t)cols, rows), l(lab, lrs, 3 * (size_t)cols, rows), g(gray, grs, cols, rows);
+    int rc = stage(ctx, {&in}, {&l, &g});
+    if (rc == DCMT_OK) rc = dcmt_bgr_convert_dev(ctx, (const uint8_t*)in.dev, rows, cols, 1, (uint8_t*)l.dev, (uint8_t*)g.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&l, &g}) : rc;
+}
+
 }  // extern "C"

@@ -10,6 +10,7 @@
 
 #include "dcmt_chunks.h"
 #include "dcmt_cloud.h"
+#include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_tiles.h"
 
 #pragma GCC visibility push(hidden)       // internal names: none of them in libdcmt_hip.so's dynamic symbol table
@@ -178,6 +179,53 @@ inline GaussPlan plan_gauss5(int rows, int cols, int batch)
     while (p.band_rows > 8 && (size_t)p.strips * ((rows + p.band_rows - 1) / p.band_rows) * batch < 2048) p.band_rows /= 2;
     p.bands = (rows + p.band_rows - 1) / p.band_rows;
     p.grid_x = (unsigned)(((size_t)p.strips * p.bands + 3) / 4);
+    return p;
+}
+
+// ---- dcmt_bgr_convert_dev ----------------------------------------------------------------------------------------------
+// One kernel over the batch as ONE flat run of pixels (dcmt_kernels_bgr.h): nothing in it depends on where a frame ends.  Runs of
+// more than kBgrSegPx pixels go in segments of kBgrSegPx, a launch each; kBgrSegPx is a multiple of 4, so every segment's three
+// base pointers are as aligned as the call's and `aligned` is decided once.  A workgroup takes `passes` passes of kBgrPxPerPass
+// pixels: kBgrMaxPasses, so that the copy of the Lab tables to LDS (6.5 KiB) is small against its pixels (48 KiB read), halved
+// while the run makes fewer than two workgroups per CU.
+// The checks on the three buffers are here as well, so that they are tested without a device: at least one output; lab may BE bgr
+// (in place: every lane has read its pixels before it writes them, and no other lane reads them); any other overlap is refused.
+struct BgrSegment {
+    size_t first;                    // the segment's first pixel in the run
+    uint32_t total;                  // its pixels
+    unsigned grid;                   // k_bgr_convert: workgroups
+};
+
+struct BgrPlan {
+    int status;                      // kInvalid: no output, or buffers that overlap (nothing else is meaningful then)
+    size_t px;                       // pixels of the run
+    size_t count;                    // segments
+    uint32_t passes;                 // per workgroup
+    bool aligned;                    // k_bgr_convert<.., .., true>: bgr and every output wanted are 4-byte aligned
+    uint32_t share() const { return passes * kBgrPxPerPass; }        // pixels per workgroup
+    BgrSegment segment(size_t i) const
+    {
+        BgrSegment s;
+        s.first = i * (size_t)kBgrSegPx;
+        s.total = px - s.first < kBgrSegPx ? (uint32_t)(px - s.first) : kBgrSegPx;
+        s.grid = (unsigned)((s.total + share() - 1) / share());
+        return s;
+    }
+};
+
+// px = batch * rows * cols >= 1; lab_addr / gray_addr: 0 = that output is not wanted
+inline BgrPlan plan_bgr_convert(size_t px, uintptr_t bgr_addr, uintptr_t lab_addr, uintptr_t gray_addr)
+{
+    BgrPlan p = {kInvalid, px, 0, 0, false};
+    if (!bgr_addr || (!lab_addr && !gray_addr) || px < 1) return p;
+    if (lab_addr && lab_addr != bgr_addr && ranges_overlap(bgr_addr, 3 * px, lab_addr, 3 * px)) return p;
+    if (gray_addr && ranges_overlap(bgr_addr, 3 * px, gray_addr, px)) return p;
+    if (lab_addr && gray_addr && ranges_overlap(lab_addr, 3 * px, gray_addr, px)) return p;
+    p.status = kOk;
+    p.count = (px + kBgrSegPx - 1) / kBgrSegPx;
+    p.passes = kBgrMaxPasses;
+    while (p.passes > 1 && px / p.share() < 512) p.passes /= 2;
+    p.aligned = bgr_addr % 4 == 0 && lab_addr % 4 == 0 && gray_addr % 4 == 0;
     return p;
 }
 

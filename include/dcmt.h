@@ -242,7 +242,7 @@ int dcmt_project_points_dev(dcmt_ctx *ctx, const float *d_points, const int32_t 
  * (init_data :19-57), then NR_ITERATIONS = 10 rounds of "every pixel of a centre's [c - step, c + step) window takes the
  * centre with the smallest distance (compute_dist :59-68, f64), the lowest index on ties" and "every centre becomes the
  * mean of its pixels".  d_lab: [batch][rows][cols][3] uint8 -- the image the reference passes (its cv::cvtColor(BGR2Lab)
- * output); step, nc: the reference's int arguments (step = (int)sqrt(w*h / n_superpixels), nc = 50 / 40).
+ * output: what dcmt_bgr_convert_dev writes from the camera's BGR bytes, on the same stream); step, nc: the reference's int arguments (step = (int)sqrt(w*h / n_superpixels), nc = 50 / 40).
  * d_labels: [batch][rows][cols] int32, row-major (the reference's clusters[col][row]), -1 = never reached: exactly what
  * dcmt_complete_labeled_f32_dev takes, with n_labels = dcmt_slic_num_centers(rows, cols, step).
  * d_centers (may be NULL): [batch][n][5] f64 = L, a, b, x, y after the last iteration.
@@ -261,7 +261,7 @@ int dcmt_slic_labels_dev(dcmt_ctx *ctx, const uint8_t *d_lab, int rows, int cols
  * derivatives calculateMeasuementDerivatives :715-747 made), disparity -> depth clamped to max_depth
  * (retrieve_optimized_depth :863-885).  Every pixel only ever touches its own disparity, so the sweeps are independent
  * per pixel.  d_left / d_right: [batch][rows][cols] uint8 grey images (the reference's cv::cvtColor(BGR2GRAY) outputs,
- * :1167-1171); d_depth: the path's output; d_refined: [batch][rows][cols] f32, 0 where the disparity ends up <= 0.
+ * :1167-1171: what dcmt_bgr_convert_dev writes from the cameras' BGR bytes, on the same stream); d_depth: the path's output; d_refined: [batch][rows][cols] f32, 0 where the disparity ends up <= 0.
  * iterations < 0 selects the reference's 4; iterations == 0 is the pure depth -> disparity -> depth round trip
  * (its `depth_pre_optim`, :1225-1226). */
 typedef struct {
@@ -456,6 +456,40 @@ int dcmt_reproject_depth_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int 
  * winner plane like the device call. */
 int dcmt_reproject_depth(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, int rows, int cols,
                          const dcmt_reproject_params *params, float *out, size_t out_row_stride, int out_rows, int out_cols);
+
+/* ---- producer of the image inputs: camera BGR bytes -> 8-bit Lab and grey planes ----------------------- */
+
+/* What the reference mains do with every camera frame before anything else: cv::cvtColor(image, lab_image, cv::COLOR_BGR2Lab)
+ * (DC_lidar_camera/main_lc.cpp:183, DC_stereo_lidar/main_sl.cpp:439: the input of Slic::generate_superpixels) and
+ * cv::cvtColor(..., cv::COLOR_BGR2GRAY) (main_sl.cpp:1167, :1171: the inputs of the stereo refinement), on CV_8UC3 pixels B, G, R.
+ * Both are integer-only per pixel, in the fixed-point scheme OpenCV uses for 8-bit images -- restated from memory of its sources,
+ * never run against an OpenCV: the definition is OURS and bit-exact from there on.
+ *     grey  Y = (B * 3735 + G * 19235 + R * 9798 + 16384) >> 15
+ *     Lab   R' = gamma[R], G' = gamma[G], B' = gamma[B]             gamma[i] = floor(2040 * lin(i / 255) + 0.5), the sRGB curve
+ *           fX = cbrt[D(R' * C00 + G' * C01 + B' * C02, 12)]        cbrt[i] = floor(32768 * f(i / 2040) + 0.5), f = t^(1/3), or
+ *           fY, fZ: rows 1 and 2 of C                               7.787 t + 16/116 below 0.008856; C = rint(4096 * M / white), D65
+ *           L = D(296 * fY - 1336934, 15),  a = D(500 * (fX - fY) + 128 * 32768, 15),  b = D(200 * (fY - fZ) + 128 * 32768, 15)
+ *     with D(v, n) = (v + (1 << (n - 1))) >> n.  L = L* * 255 / 100, a = a* + 128, b = b* + 128, as cv::cvtColor stores them in bytes.
+ * Against the documented f64 formulas rounded to nearest, over all 2^24 colours: grey within 1 level, L within 2, a within 3, b
+ * within 2 (DESIGN.md section 15 has the counts).
+ *
+ * DEVICE pointers, stream-ordered.  d_bgr, d_lab: [batch][rows][cols][3] bytes; d_gray: [batch][rows][cols] bytes; any byte
+ * alignment (4-byte aligned pointers take the wide loads and stores).  d_lab or d_gray may be NULL, not both: one read of the image
+ * serves both outputs (the left image of DC_stereo_lidar needs both, the right one grey only).  d_lab == d_bgr is allowed (in place)
+ * and gives the bytes of an out-of-place call; any other overlap among the three buffers is DCMT_E_INVALID.  Never synchronises,
+ * never allocates, uses no ctx scratch and carries no state from call to call; may be enqueued in front of or behind any other
+ * *_dev call of the ctx on the same stream.  A pixel's bytes depend on that pixel alone.
+ * DCMT_E_INVALID: a null ctx or d_bgr, both outputs NULL, sizes beyond the ctx limits, overlapping buffers. */
+int dcmt_bgr_convert_dev(dcmt_ctx *ctx, const uint8_t *d_bgr, int rows, int cols, int batch,
+                         uint8_t *d_lab /* or NULL */, uint8_t *d_gray /* or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: bgr and lab >= 3 * cols, gray >= cols; the stride of a NULL
+ * output is ignored); the same bytes as the device call.  What dcmt_shim::bgr_to_lab / bgr_to_gray call. */
+int dcmt_bgr_convert(dcmt_ctx *ctx, const uint8_t *bgr, size_t bgr_row_stride, int rows, int cols,
+                     uint8_t *lab /* or NULL */, size_t lab_row_stride,
+                     uint8_t *gray /* or NULL */, size_t gray_row_stride);
+/* The constants the kernel uses: the two tables and C, row-major (rows X, Y, Z over columns R, G, B).  Any pointer may be NULL.
+ * Needs no GPU. */
+void dcmt_lab_tables(uint16_t gamma[256], uint16_t cbrt[3072], int32_t coef[9]);
 
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 

@@ -198,6 +198,33 @@ inline void to_color_image(const cv::Mat& r_img, cv::Mat& color_img)
     color_img = out;
 }
 
+// cv::cvtColor(image, lab_image, cv::COLOR_BGR2Lab) on a camera frame (DC_lidar_camera/main_lc.cpp:183, DC_stereo_lidar/
+// main_sl.cpp:439): CV_8UC3 (B, G, R) in, a fresh CV_8UC3 (L, a, b) out -- the image slic_labels takes.  The arithmetic is the
+// library's statement of OpenCV's 8-bit fixed-point scheme (dcmt.h), not a call into OpenCV.
+inline void bgr_to_lab(const cv::Mat& image, cv::Mat& lab_image)
+{
+    if (image.type() != CV_8UC3 || image.rows < 1 || image.cols < 1) throw std::runtime_error("bgr_to_lab: image must be CV_8UC3");
+    const int rows = image.rows, cols = image.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_8UC3);
+    raise(dcmt_bgr_convert(thread_ctx().get(rows, cols), image.ptr<unsigned char>(), image.step[0], rows, cols, out.ptr<unsigned char>(),
+                           out.step[0], nullptr, 0), "bgr_to_lab");
+    lab_image = out;
+}
+
+// cv::cvtColor(image, gray, cv::COLOR_BGR2GRAY) (main_sl.cpp:1167, :1171): CV_8UC3 in, a fresh CV_8UC1 out -- the images
+// stereo_refine takes.
+inline void bgr_to_gray(const cv::Mat& image, cv::Mat& gray)
+{
+    if (image.type() != CV_8UC3 || image.rows < 1 || image.cols < 1) throw std::runtime_error("bgr_to_gray: image must be CV_8UC3");
+    const int rows = image.rows, cols = image.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_8UC1);
+    raise(dcmt_bgr_convert(thread_ctx().get(rows, cols), image.ptr<unsigned char>(), image.step[0], rows, cols, nullptr, 0,
+                           out.ptr<unsigned char>(), out.step[0]), "bgr_to_gray");
+    gray = out;
+}
+
 // cv::GaussianBlur(src, dst, cv::Size(5, 5), 0) as DC_stereo_lidar/main_sl.cpp:1253 calls it on the refined depth (in place there:
 // src and dst may be the same Mat).  CV_32FC1 in, a fresh CV_32FC1 out.
 inline void gaussian_blur5(const cv::Mat& src, cv::Mat& dst)
