@@ -23,6 +23,7 @@ here.  All arithmetic happens in csrc/ (HIP); there is no CPU path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
@@ -73,6 +74,15 @@ def _stream(stream, t) -> ctypes.c_void_p:
         import torch
         stream = torch.cuda.current_stream(t.device).cuda_stream
     return ctypes.c_void_p(stream)
+
+
+def _on_stream(stream, t):
+    """What a wrapper creates its default outputs under: torch's current stream is the stream the call enqueues on, so the
+    caching allocator ties the block to that stream and a fill is ordered in front of the kernels."""
+    if stream is None:
+        return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(torch.cuda.ExternalStream(stream, device=t.device) if stream else torch.cuda.default_stream(t.device))
 
 
 def _frame_f32(a) -> np.ndarray:
@@ -208,12 +218,14 @@ class Context:
                      use_superpixel: int = 1, stream: int | None = None):
         """d_src/d_dst: contiguous f32 CUDA tensors [batch][rows][cols] (or [rows][cols]) on this
         context's GPU.  Enqueues on `stream` (a hipStream_t as int; default torch's current stream)
-        and returns immediately."""
+        and returns immediately.  An output that is not given is allocated (and, where it has a fill, filled) on
+        that same stream."""
         import torch
         p = params or make_params()
         assert _is_dev(d_src, torch.float32)
         if d_dst is None:
-            d_dst = torch.full_like(d_src, float("nan"))     # never mistake stale memory for output
+            with _on_stream(stream, d_src):
+                d_dst = torch.full_like(d_src, float("nan"))     # never mistake stale memory for output
         assert _is_dev(d_dst, torch.float32) and d_dst.shape == d_src.shape
         b, r, c = _brc(d_src)
         if d_labels is None:
@@ -230,13 +242,15 @@ class Context:
     def complete_u16_dev(self, d_src16, scale: float = 1.0 / 256.0, d_dst=None, params: L.Params | None = None,
                          stream: int | None = None):
         """KITTI uint16 depth payload in (torch.uint16 or int16-viewed CUDA tensor [batch][rows][cols]), metres out:
-        the reference's imread + convertTo(CV_32F, 1/256) (src/DC_lidar_only/main.cpp:75-82) fused into the first kernel."""
+        the reference's imread + convertTo(CV_32F, 1/256) (src/DC_lidar_only/main.cpp:75-82) fused into the first kernel.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         p = params or make_params()
         assert _is_dev(d_src16) and d_src16.element_size() == 2
         b, r, c = _brc(d_src16)
         if d_dst is None:
-            d_dst = torch.full(tuple(d_src16.shape), float("nan"), dtype=torch.float32, device=d_src16.device)
+            with _on_stream(stream, d_src16):
+                d_dst = torch.full(tuple(d_src16.shape), float("nan"), dtype=torch.float32, device=d_src16.device)
         st = L.lib().dcmt_complete_u16_dev(self._h, d_src16.data_ptr(), ctypes.c_float(scale), d_dst.data_ptr(), r, c, b,
                                            ctypes.byref(p), _stream(stream, d_src16))
         _check(st, "dcmt_complete_u16_dev")
@@ -245,14 +259,16 @@ class Context:
     def project_points_dev(self, d_points, d_offsets, T, P, rows: int, cols: int, d_sparse=None, stream: int | None = None):
         """N2 (SL/main_sl.cpp:478-520): velodyne points -> sparse depth images on the device.  d_points: f32 CUDA tensor
         [n][4] (x, y, z, reflectance); d_offsets: int32 CUDA tensor [batch + 1], frame f owns points
-        [offsets[f], offsets[f+1]); T 4x4, P 3x4 row-major.  Returns [batch][rows][cols] f32, 0 = no point."""
+        [offsets[f], offsets[f+1]); T 4x4, P 3x4 row-major.  Returns [batch][rows][cols] f32, 0 = no point.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
         assert _is_dev(d_offsets, torch.int32)
         batch = d_offsets.numel() - 1
         n = d_points.numel() // 4
         if d_sparse is None:
-            d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
+            with _on_stream(stream, d_points):
+                d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
         assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
         t = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
         p = np.ascontiguousarray(P, dtype=np.float32).reshape(12)
@@ -263,15 +279,17 @@ class Context:
 
     def slic_labels_dev(self, d_lab, step: int, nc: int, d_labels=None, return_centers: bool = False, stream: int | None = None):
         """N3, Slic::generate_superpixels (LC/slic.cpp:101-182) on the device.  d_lab: uint8 CUDA tensor [batch][rows][cols][3]
-        (or [rows][cols][3]).  Returns (labels int32 [batch][rows][cols], n_centers[, centers float64 [batch][n][5]])."""
+        (or [rows][cols][3]).  Returns (labels int32 [batch][rows][cols], n_centers[, centers float64 [batch][n][5]]).
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_lab, torch.uint8) and d_lab.shape[-1] == 3
         b, r, c = _brc(d_lab, 1)
         n = L.lib().dcmt_slic_num_centers(r, c, int(step))
-        if d_labels is None:
-            d_labels = torch.full((b, r, c), -7, dtype=torch.int32, device=d_lab.device)
+        with _on_stream(stream, d_lab):
+            if d_labels is None:
+                d_labels = torch.full((b, r, c), -7, dtype=torch.int32, device=d_lab.device)
+            d_cent = torch.empty((b, max(n, 1), 5), dtype=torch.float64, device=d_lab.device) if return_centers else None
         assert _is_dev(d_labels, torch.int32) and tuple(d_labels.shape) == (b, r, c)
-        d_cent = torch.empty((b, max(n, 1), 5), dtype=torch.float64, device=d_lab.device) if return_centers else None
         st = L.lib().dcmt_slic_labels_dev(self._h, d_lab.data_ptr(), r, c, b, int(step), int(nc), d_labels.data_ptr(),
                                           d_cent.data_ptr() if return_centers else None, _stream(stream, d_lab))
         _check(st, "dcmt_slic_labels_dev")
@@ -279,14 +297,16 @@ class Context:
 
     def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
         """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
-        kw: baseline, focal, damp, max_depth override the reference's constants."""
+        kw: baseline, focal, damp, max_depth override the reference's constants.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_depth, torch.float32)
         for t in (d_left, d_right):
             assert _is_dev(t, torch.uint8) and t.shape == d_depth.shape
         b, r, c = _brc(d_depth)
         if d_out is None:
-            d_out = torch.full_like(d_depth, float("nan"))
+            with _on_stream(stream, d_depth):
+                d_out = torch.full_like(d_depth, float("nan"))
         sp = L.StereoParams()
         L.lib().dcmt_default_stereo_params(ctypes.byref(sp))
         for k, v in kw.items():
@@ -304,13 +324,15 @@ class Context:
         """Per-frame sums of the reference's error terms on the device (dcmt_evaluate_dev).  d_gt, d_pred: contiguous CUDA tensors
         [batch][rows][cols] (or [rows][cols]); d_pred f32; d_gt f32, or a 2-byte type (torch.uint16 / int16 view of the KITTI
         PNG payload) that goes to dcmt_evaluate_u16_dev with gt = payload * gt_scale.  mode "gt": mask gt > thresh; "both":
-        gt > thresh and pred > thresh.  Returns a float64 CUDA tensor [batch, 7] (EVAL_FIELDS) without synchronising."""
+        gt > thresh and pred > thresh.  Returns a float64 CUDA tensor [batch, 7] (EVAL_FIELDS) without synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_pred, torch.float32)
         assert _is_dev(d_gt) and d_gt.shape == d_pred.shape
         b, r, c = _brc(d_pred)
         if d_out is None:
-            d_out = torch.empty((b, 7), dtype=torch.float64, device=d_pred.device)
+            with _on_stream(stream, d_pred):
+                d_out = torch.empty((b, 7), dtype=torch.float64, device=d_pred.device)
         assert _is_dev(d_out, torch.float64) and d_out.numel() == 7 * b
         m = _eval_mode(mode)
         if d_gt.element_size() == 2:
@@ -337,12 +359,14 @@ class Context:
     def colorize_dev(self, d_src, d_bgr=None, stream: int | None = None):
         """The reference's toColorImage on the device (dcmt_colorize_dev): per frame min-max to [0, 1], * 255 to u8, JET palette.
         d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]).  Returns a uint8 CUDA tensor of d_src's shape + (3,),
-        B, G, R per pixel, without synchronising."""
+        B, G, R per pixel, without synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_src, torch.float32)
         b, r, c = _brc(d_src)
         if d_bgr is None:
-            d_bgr = torch.empty(tuple(d_src.shape) + (3,), dtype=torch.uint8, device=d_src.device)
+            with _on_stream(stream, d_src):
+                d_bgr = torch.empty(tuple(d_src.shape) + (3,), dtype=torch.uint8, device=d_src.device)
         assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
         st = L.lib().dcmt_colorize_dev(self._h, d_src.data_ptr(), r, c, b, d_bgr.data_ptr(), _stream(stream, d_src))
         _check(st, "dcmt_colorize_dev")
@@ -362,15 +386,17 @@ class Context:
         SL/main_sl.cpp:439, :1167, :1171), one read of the image for both.  d_bgr: contiguous uint8 CUDA tensor
         [batch][rows][cols][3] (or [rows][cols][3]), B, G, R.  Returns the Lab tensor (d_bgr's shape: what slic_labels_dev takes),
         the grey tensor (d_bgr's shape without the 3: what stereo_refine_dev takes), or (lab, grey) where both are wanted, without
-        synchronising.  A d_lab / d_gray that is given is written and wanted; d_lab may be d_bgr (in place)."""
+        synchronising.  A d_lab / d_gray that is given is written and wanted; d_lab may be d_bgr (in place).
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_bgr, torch.uint8) and d_bgr.shape[-1] == 3
         b, r, c = _brc(d_bgr, 1)
         lab, gray = lab or d_lab is not None, gray or d_gray is not None
-        if lab and d_lab is None:
-            d_lab = torch.empty_like(d_bgr)
-        if gray and d_gray is None:
-            d_gray = torch.empty(tuple(d_bgr.shape[:-1]), dtype=torch.uint8, device=d_bgr.device)
+        with _on_stream(stream, d_bgr):
+            if lab and d_lab is None:
+                d_lab = torch.empty_like(d_bgr)
+            if gray and d_gray is None:
+                d_gray = torch.empty(tuple(d_bgr.shape[:-1]), dtype=torch.uint8, device=d_bgr.device)
         assert d_lab is None or (_is_dev(d_lab, torch.uint8) and d_lab.numel() == 3 * b * r * c)
         assert d_gray is None or (_is_dev(d_gray, torch.uint8) and d_gray.numel() == b * r * c)
         st = L.lib().dcmt_bgr_convert_dev(self._h, d_bgr.data_ptr(), r, c, b, d_lab.data_ptr() if lab else None,
@@ -402,7 +428,8 @@ class Context:
         Returns (points, offsets): points float32 [capacity, 4] (default capacity batch * rows * cols; the fourth column holds the
         colour BITS b | g << 8 | r << 16 | 255 << 24: compare and slice it through .view(torch.int32) / .view(torch.uint8)),
         offsets int32 [batch + 1]; frame f owns points[offsets[f]:offsets[f + 1]].  Rows of points from offsets[batch] on are not
-        written.  No synchronisation."""
+        written.  No synchronisation.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_depth, torch.float32)
         b, r, c = _brc(d_depth)
@@ -410,11 +437,12 @@ class Context:
             assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
         if capacity is None:
             capacity = d_points.numel() // 4 if d_points is not None else b * r * c
-        if d_points is None:
-            d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
+        with _on_stream(stream, d_depth):
+            if d_points is None:
+                d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
+            if d_offsets is None:
+                d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
         assert _is_dev(d_points, torch.float32) and d_points.numel() >= 4 * capacity
-        if d_offsets is None:
-            d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
         assert _is_dev(d_offsets, torch.int32) and d_offsets.numel() == b + 1
         p = params or make_cloud_params()
         st = L.lib().dcmt_depth_to_cloud_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
@@ -446,12 +474,14 @@ class Context:
     def gaussian5_dev(self, d_src, d_dst=None, stream: int | None = None):
         """cv::GaussianBlur(src, dst, Size(5, 5), 0) on the device (dcmt_gaussian5_dev; SL/main_sl.cpp:1253), without the cascade's
         masked select.  d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]); d_dst may be d_src (in place).
-        Returns d_dst without synchronising."""
+        Returns d_dst without synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_src, torch.float32)
         b, r, c = _brc(d_src)
         if d_dst is None:
-            d_dst = torch.full_like(d_src, float("nan"))
+            with _on_stream(stream, d_src):
+                d_dst = torch.full_like(d_src, float("nan"))
         assert _is_dev(d_dst, torch.float32) and d_dst.numel() == d_src.numel()
         st = L.lib().dcmt_gaussian5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, _stream(stream, d_src))
         _check(st, "dcmt_gaussian5_dev")
@@ -472,12 +502,14 @@ class Context:
         with the intrinsics, moved by M, projected with K and, where it lands inside [out_rows][out_cols], stores its new depth; the
         last source pixel in row-major order wins a destination pixel, pixels nothing lands on are 0.  d_depth: contiguous f32 CUDA
         tensor [batch][rows][cols] (or [rows][cols]: a batch of one).  Returns d_out, f32 [batch][out_rows][out_cols] (or
-        [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation."""
+        [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_depth, torch.float32)
         b, r, c = _brc(d_depth)
         if d_out is None:
-            d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
+            with _on_stream(stream, d_depth):
+                d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
         assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
         p = params or make_reproject_params()
         st = L.lib().dcmt_reproject_depth_dev(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
