@@ -35,6 +35,7 @@ EXPORTS = (
     "dcmt_default_cloud_params", "dcmt_depth_to_cloud_dev", "dcmt_depth_to_cloud", "dcmt_gaussian5_dev", "dcmt_gaussian5",
     "dcmt_default_reproject_params", "dcmt_reproject_depth_dev", "dcmt_reproject_depth",
     "dcmt_bgr_convert_dev", "dcmt_bgr_convert", "dcmt_lab_tables",
+    "dcmt_project_points_calib_dev", "dcmt_depth_to_cloud_calib_dev", "dcmt_reproject_depth_calib_dev", "dcmt_stereo_refine_calib_dev",
 )
 
 
@@ -84,6 +85,16 @@ class ReprojectParams(ctypes.Structure):
     destination camera's 3x3 matrix, both row-major."""
     _fields_ = [("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
                 ("M", ctypes.c_float * 16), ("K", ctypes.c_float * 9)]
+
+
+class ProjectCalib(ctypes.Structure):
+    """Mirror of dcmt_project_calib (include/dcmt.h): one frame's record of dcmt_project_points_calib_dev, rows 0..2 of T, then P."""
+    _fields_ = [("T", ctypes.c_float * 12), ("P", ctypes.c_float * 12)]
+
+
+class StereoCalib(ctypes.Structure):
+    """Mirror of dcmt_stereo_calib (include/dcmt.h): one frame's record of dcmt_stereo_refine_calib_dev."""
+    _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float)]
 
 
 def build(force: bool = False) -> str:
@@ -175,6 +186,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_bgr_convert.argtypes = [vp, vp, sz, i, i, vp, sz, vp, sz]
         L.dcmt_lab_tables.argtypes = [vp, vp, vp]
         L.dcmt_lab_tables.restype = None
+        L.dcmt_project_points_calib_dev.argtypes = [vp, vp, vp, i, i, vp, vp, i, i, vp]
+        L.dcmt_depth_to_cloud_calib_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, i64, vp, vp]
+        L.dcmt_reproject_depth_calib_dev.argtypes = [vp, vp, i, i, i, vp, vp, i, i, vp]
+        L.dcmt_stereo_refine_calib_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

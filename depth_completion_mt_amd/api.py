@@ -154,6 +154,108 @@ def make_reproject_params(M=None, K=None, fx: float | None = None, fy: float | N
     return p
 
 
+# ---- per-frame calibration tables of the *_calib_dev calls (include/dcmt.h): structured arrays of exactly the C layouts ----------
+PROJECT_CALIB_DTYPE = np.dtype([("T", "<f4", (12,)), ("P", "<f4", (12,))])                                   # dcmt_project_calib, 96 B
+CLOUD_CALIB_DTYPE = np.dtype([("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8")])                    # dcmt_cloud_params, 32 B
+REPROJECT_CALIB_DTYPE = np.dtype({"names": ["fx", "fy", "cx", "cy", "M", "K"], "formats": ["<f8", "<f8", "<f8", "<f8", ("<f4", (16,)), ("<f4", (9,))],
+                                  "offsets": [0, 8, 16, 24, 32, 96], "itemsize": 136})                      # dcmt_reproject_params
+STEREO_CALIB_DTYPE = np.dtype([("baseline", "<f4"), ("focal", "<f4")])                                       # dcmt_stereo_calib, 8 B
+
+
+def _finite_or_raise(what: str, a) -> None:
+    bad = ~np.isfinite(np.asarray(a, dtype=np.float64))
+    if bad.any():
+        raise ValueError(f"{what}: a non-finite entry in record {int(np.argwhere(bad)[0][0])}")
+
+
+def _nonzero_or_raise(what: str, a) -> None:
+    bad = np.asarray(a) == 0
+    if bad.any():
+        raise ValueError(f"{what} is zero in record {int(np.argwhere(bad)[0][0])}")
+
+
+def _batch_of(**arrays) -> int:
+    """The number of records a make_*_calib call describes: its arguments are arrays of [b] or scalars, at least one an array."""
+    shapes = {k: np.shape(v) for k, v in arrays.items()}
+    try:
+        shp = np.broadcast_shapes(*shapes.values())
+    except ValueError:
+        shp = None
+    if shp is None or len(shp) != 1:
+        raise ValueError(f"per-frame values must be scalars or arrays of one common length [b], at least one an array; got shapes {shapes}")
+    return int(shp[0])
+
+
+def _intrinsics(out, b, fx, fy, cx, cy) -> None:
+    for k, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy)):
+        out[k] = np.broadcast_to(np.asarray(v, dtype=np.float64), (b,))
+        _finite_or_raise(k, out[k])
+    _nonzero_or_raise("fx", out["fx"])
+    _nonzero_or_raise("fy", out["fy"])
+
+
+def make_project_calib(T, P) -> np.ndarray:
+    """The table of Context.project_points_calib_dev: T [b][4][4] (or [b][3][4]: the bottom row is never used), P [b][3][4], both
+    row-major, rounded to f32.  Raises ValueError on a non-finite entry -- a record the device call would answer with an empty
+    frame.  Upload it once, outside the hot loop (calib_to_device)."""
+    T, P = np.asarray(T, dtype=np.float32), np.asarray(P, dtype=np.float32)
+    b = T.shape[0]
+    assert T.shape in ((b, 4, 4), (b, 3, 4)) and P.shape == (b, 3, 4), (T.shape, P.shape)
+    out = np.zeros(b, PROJECT_CALIB_DTYPE)
+    out["T"], out["P"] = T[:, :3].reshape(b, 12), P.reshape(b, 12)
+    _finite_or_raise("T", out["T"])
+    _finite_or_raise("P", out["P"])
+    return out
+
+
+def make_cloud_calib(fx, fy, cx, cy) -> np.ndarray:
+    """The table of Context.depth_to_cloud_calib_dev: per-frame intrinsics, arrays of [b] (a scalar is repeated; at least one
+    must be an array).  Raises ValueError on a non-finite entry and on fx or fy zero, what dcmt_depth_to_cloud_dev refuses."""
+    out = np.zeros(_batch_of(fx=fx, fy=fy, cx=cx, cy=cy), CLOUD_CALIB_DTYPE)
+    _intrinsics(out, len(out), fx, fy, cx, cy)
+    return out
+
+
+def make_reproject_calib(M, K, fx, fy, cx, cy) -> np.ndarray:
+    """The table of Context.reproject_depth_calib_dev: M [b][4][4] (the matrix that is APPLIED; its 4th row is ignored), K [b][3][3]
+    (its 3rd row is ignored), row-major, rounded to f32; fx, fy, cx, cy arrays of [b] or scalars.  Raises ValueError on what
+    dcmt_reproject_depth_dev refuses: a non-finite intrinsic or entry of the rows that are read, fx or fy zero."""
+    M, K = np.asarray(M, dtype=np.float32), np.asarray(K, dtype=np.float32)
+    b = M.shape[0]
+    assert M.shape == (b, 4, 4) and K.shape == (b, 3, 3), (M.shape, K.shape)
+    out = np.zeros(b, REPROJECT_CALIB_DTYPE)
+    _intrinsics(out, b, fx, fy, cx, cy)
+    out["M"], out["K"] = M.reshape(b, 16), K.reshape(b, 9)
+    _finite_or_raise("M", out["M"][:, :12])
+    _finite_or_raise("K", out["K"][:, :6])
+    return out
+
+
+def make_stereo_calib(baseline, focal) -> np.ndarray:
+    """The table of Context.stereo_refine_calib_dev: per-frame baseline and focal length, arrays of [b] (a scalar is repeated; at
+    least one must be an array).  Raises ValueError on a non-finite entry and on focal zero."""
+    out = np.zeros(_batch_of(baseline=baseline, focal=focal), STEREO_CALIB_DTYPE)
+    for k, v in (("baseline", baseline), ("focal", focal)):
+        out[k] = np.broadcast_to(np.asarray(v, dtype=np.float32), (len(out),))
+        _finite_or_raise(k, out[k])
+    _nonzero_or_raise("focal", out["focal"])
+    return out
+
+
+def calib_to_device(table: np.ndarray, device="cuda"):
+    """A make_*_calib array as the CUDA tensor the *_calib_dev wrappers take: uint8 [b][record bytes] (torch has no structured
+    dtype).  One synchronous upload: do it outside the hot loop."""
+    import torch
+    t = np.ascontiguousarray(table)
+    return torch.from_numpy(t.view(np.uint8).reshape(len(t), t.dtype.itemsize)).to(device)
+
+
+def _table_ptr(d_table, batch: int, rec: int) -> int:
+    """The device address of a calibration table: a contiguous CUDA tensor of any dtype that holds exactly batch records."""
+    assert _is_dev(d_table) and d_table.numel() * d_table.element_size() == batch * rec, (tuple(d_table.shape), d_table.dtype, batch, rec)
+    return d_table.data_ptr()
+
+
 def inverse_f32(R_rect) -> np.ndarray:
     """What unrectify_sol passes as M: the inverse of the 4x4 R_rect computed in f64 (numpy.linalg.inv) and rounded once to f32.
     This inverse is OURS: the reference calls Eigen's f32 Matrix4f::inverse() inside its loop, whose bits are not reproduced."""
@@ -277,6 +379,26 @@ class Context:
         _check(st, "dcmt_project_points_dev")
         return d_sparse
 
+    def project_points_calib_dev(self, d_points, d_offsets, d_calib, rows: int, cols: int, d_sparse=None, stream: int | None = None):
+        """project_points_dev with the matrices of each sweep's own drive (dcmt_project_points_calib_dev): d_calib is a CUDA tensor
+        holding [batch] dcmt_project_calib records (make_project_calib, calib_to_device), read on the stream the call enqueues on.
+        A sweep whose record has a non-finite entry gives a zero plane.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
+        assert _is_dev(d_offsets, torch.int32)
+        batch = d_offsets.numel() - 1
+        n = d_points.numel() // 4
+        if d_sparse is None:
+            with _on_stream(stream, d_points):
+                d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
+        assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
+        st = L.lib().dcmt_project_points_calib_dev(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch,
+                                                   _table_ptr(d_calib, batch, PROJECT_CALIB_DTYPE.itemsize), d_sparse.data_ptr(), rows, cols,
+                                                   _stream(stream, d_points))
+        _check(st, "dcmt_project_points_calib_dev")
+        return d_sparse
+
     def slic_labels_dev(self, d_lab, step: int, nc: int, d_labels=None, return_centers: bool = False, stream: int | None = None):
         """N3, Slic::generate_superpixels (LC/slic.cpp:101-182) on the device.  d_lab: uint8 CUDA tensor [batch][rows][cols][3]
         (or [rows][cols][3]).  Returns (labels int32 [batch][rows][cols], n_centers[, centers float64 [batch][n][5]]).
@@ -316,6 +438,32 @@ class Context:
         st = L.lib().dcmt_stereo_refine_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(),
                                             r, c, b, ctypes.byref(sp), _stream(stream, d_depth))
         _check(st, "dcmt_stereo_refine_dev")
+        return d_out
+
+    def stereo_refine_calib_dev(self, d_depth, d_left, d_right, d_calib, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
+        """stereo_refine_dev with each frame's own baseline and focal length (dcmt_stereo_refine_calib_dev): d_calib is a CUDA tensor
+        holding [batch] dcmt_stereo_calib records (make_stereo_calib, calib_to_device), read on the stream the call enqueues on.
+        kw: damp, max_depth.  A frame whose record has a non-finite entry or focal zero gives a zero plane.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        for t in (d_left, d_right):
+            assert _is_dev(t, torch.uint8) and t.shape == d_depth.shape
+        b, r, c = _brc(d_depth)
+        if d_out is None:
+            with _on_stream(stream, d_depth):
+                d_out = torch.full_like(d_depth, float("nan"))
+        sp = L.StereoParams()
+        L.lib().dcmt_default_stereo_params(ctypes.byref(sp))
+        for k, v in kw.items():
+            assert k in ("damp", "max_depth"), k
+            setattr(sp, k, float(v))
+        if iterations is not None:
+            sp.iterations = int(iterations)
+        st = L.lib().dcmt_stereo_refine_calib_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(),
+                                                  r, c, b, ctypes.byref(sp), _table_ptr(d_calib, b, STEREO_CALIB_DTYPE.itemsize),
+                                                  _stream(stream, d_depth))
+        _check(st, "dcmt_stereo_refine_calib_dev")
         return d_out
 
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
@@ -451,6 +599,32 @@ class Context:
         _check(st, "dcmt_depth_to_cloud_dev")
         return d_points, d_offsets
 
+    def depth_to_cloud_calib_dev(self, d_depth, d_calib, d_bgr=None, d_points=None, d_offsets=None, capacity: int | None = None,
+                                 stream: int | None = None):
+        """depth_to_cloud_dev with each frame's own intrinsics (dcmt_depth_to_cloud_calib_dev): d_calib is a CUDA tensor holding
+        [batch] dcmt_cloud_params records (make_cloud_calib, calib_to_device), read on the stream the call enqueues on.  A frame
+        whose record has a non-finite entry or fx or fy zero gives no records: offsets[f + 1] == offsets[f].
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
+        if d_bgr is not None:
+            assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
+        if capacity is None:
+            capacity = d_points.numel() // 4 if d_points is not None else b * r * c
+        with _on_stream(stream, d_depth):
+            if d_points is None:
+                d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
+            if d_offsets is None:
+                d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
+        assert _is_dev(d_points, torch.float32) and d_points.numel() >= 4 * capacity
+        assert _is_dev(d_offsets, torch.int32) and d_offsets.numel() == b + 1
+        st = L.lib().dcmt_depth_to_cloud_calib_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
+                                                   _table_ptr(d_calib, b, CLOUD_CALIB_DTYPE.itemsize), d_points.data_ptr(), int(capacity),
+                                                   d_offsets.data_ptr(), _stream(stream, d_depth))
+        _check(st, "dcmt_depth_to_cloud_calib_dev")
+        return d_points, d_offsets
+
     def depth_to_cloud(self, depth: np.ndarray, bgr: np.ndarray | None = None, params: L.CloudParams | None = None) -> np.ndarray:
         """One frame of host memory (dcmt_depth_to_cloud, synchronous; any row stride): a structured array (CLOUD_DTYPE: x y z f32,
         b g r a u8) of the true length."""
@@ -515,6 +689,23 @@ class Context:
         st = L.lib().dcmt_reproject_depth_dev(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
                                               int(out_cols), _stream(stream, d_depth))
         _check(st, "dcmt_reproject_depth_dev")
+        return d_out
+
+    def reproject_depth_calib_dev(self, d_depth, out_rows: int, out_cols: int, d_calib, d_out=None, stream: int | None = None):
+        """reproject_depth_dev with each frame's own intrinsics, M and K (dcmt_reproject_depth_calib_dev): d_calib is a CUDA tensor
+        holding [batch] dcmt_reproject_params records (make_reproject_calib, calib_to_device), read on the stream the call enqueues
+        on.  A frame whose record the uniform call would refuse gives a zero plane.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
+        if d_out is None:
+            with _on_stream(stream, d_depth):
+                d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
+        assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
+        st = L.lib().dcmt_reproject_depth_calib_dev(self._h, d_depth.data_ptr(), r, c, b, _table_ptr(d_calib, b, REPROJECT_CALIB_DTYPE.itemsize),
+                                                    d_out.data_ptr(), int(out_rows), int(out_cols), _stream(stream, d_depth))
+        _check(st, "dcmt_reproject_depth_calib_dev")
         return d_out
 
     def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None) -> np.ndarray:

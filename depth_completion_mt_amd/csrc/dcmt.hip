@@ -687,22 +687,38 @@ int dcmt_complete_labeled_f32_dev(dcmt_ctx* ctx, const float* d_src, const int32
                      (hipStream_t)stream, false);
 }
 
-int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
-                            const float T[16], const float P[12], float* d_sparse, int rows, int cols, void* stream)
+}  // extern "C"
+
+// T, P: the host's one pair of matrices (dcmt_project_points_dev), or null with d_table, the device's [batch] records
+// (dcmt_project_points_calib_dev)
+static int project_points(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
+                          const float* T, const float* P, const dcmt_project_calib* d_table, float* d_sparse, int rows, int cols, void* stream)
 {
     DCMT_ON_DEVICE(ctx);
-    if (!ctx || !d_offsets || !T || !P || !d_sparse || n_points < 0 || (n_points > 0 && !d_points)) return DCMT_E_INVALID;
+    if (!ctx || !d_offsets || (!d_table && (!T || !P)) || !d_sparse || n_points < 0 || (n_points > 0 && !d_points)) return DCMT_E_INVALID;
     if ((uintptr_t)d_points % 16 != 0) return DCMT_E_INVALID;           // the 16-byte point records are read whole
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    ProjMats M;
-    std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
-    std::memcpy(M.P, P, sizeof(float) * 12);
     const size_t n_px = (size_t)batch * rows * cols;
+    if (d_table && (!plan::calib_table_aligned((uintptr_t)d_table, 16) || !plan::calib_table_clear_of((uintptr_t)d_table, sizeof *d_table, batch, (uintptr_t)d_sparse, sizeof(float) * n_px))) return DCMT_E_INVALID;
     unsigned gen_tag = 0;
     const int rc = winner_generation(ctx, n_px, (size_t)n_points, st, &gen_tag);      // (2^30 points per call: 16 GiB of records)
     if (rc != DCMT_OK) return rc;
     unsigned* winner = ctx->winner;
+    if (d_table) {
+        if (n_points > 0)
+            hipLaunchKernelGGL(k_project_scatter_calib, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, d_table,
+                               winner, rows, cols, gen_tag);
+        with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_sparse), [&](auto v) {
+            hipLaunchKernelGGL(k_project_resolve_calib<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, d_table, winner,
+                               d_sparse, (uint32_t)rows * (uint32_t)cols, n_px, gen_tag, ctx->winner_bits);
+        });
+        DCMT_HIP(ctx, hipGetLastError());
+        return DCMT_OK;
+    }
+    ProjMats M;
+    std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
+    std::memcpy(M.P, P, sizeof(float) * 12);
     if (n_points > 0)
         hipLaunchKernelGGL(k_project_scatter, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, M,
                            winner, rows, cols, gen_tag);
@@ -712,6 +728,50 @@ int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t*
     });
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+// d_table: null (dcmt_stereo_refine_dev: baseline and focal from params) or the device's [batch] records (dcmt_stereo_refine_calib_dev)
+static int stereo_refine(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, float* d_refined,
+                         int rows, int cols, int batch, const dcmt_stereo_params* params, const dcmt_stereo_calib* d_table, bool table, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_depth || !d_left || !d_right || !d_refined || !params) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if (params->iterations > 1000) return DCMT_E_INVALID;
+    if (table && (!plan::calib_table_aligned((uintptr_t)d_table, 8) || !plan::calib_table_clear_of((uintptr_t)d_table, sizeof *d_table, batch, (uintptr_t)d_refined, sizeof(float) * (size_t)batch * rows * cols)))
+        return DCMT_E_INVALID;
+    StereoP P{params->baseline, params->focal, params->damp, params->max_depth, params->iterations < 0 ? 4 : params->iterations};
+    const plan::StereoPlan pl = plan::plan_stereo(rows, cols, batch);
+    if (pl.status != DCMT_OK) return pl.status;
+    const dim3 sg(pl.gx, pl.gy, pl.gz);
+    if (table) {
+        const StereoTable PT{d_table, P.damp, P.max_depth, P.iterations};
+        if (pl.lds_row)
+            hipLaunchKernelGGL((k_stereo_refine<true, StereoTable>), sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, PT);
+        else
+            hipLaunchKernelGGL((k_stereo_refine<false, StereoTable>), sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, PT);
+    } else if (pl.lds_row)
+        hipLaunchKernelGGL(k_stereo_refine<true>, sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
+    else
+        hipLaunchKernelGGL(k_stereo_refine<false>, sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+int dcmt_project_points_dev(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
+                            const float T[16], const float P[12], float* d_sparse, int rows, int cols, void* stream)
+{
+    if (!T || !P) return DCMT_E_INVALID;
+    return project_points(ctx, d_points, d_offsets, n_points, batch, T, P, nullptr, d_sparse, rows, cols, stream);
+}
+
+int dcmt_project_points_calib_dev(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
+                                  const dcmt_project_calib* d_calib, float* d_sparse, int rows, int cols, void* stream)
+{
+    if (!d_calib) return DCMT_E_INVALID;
+    return project_points(ctx, d_points, d_offsets, n_points, batch, nullptr, nullptr, d_calib, d_sparse, rows, cols, stream);
 }
 
 void dcmt_default_stereo_params(dcmt_stereo_params* p)
@@ -726,20 +786,13 @@ void dcmt_default_stereo_params(dcmt_stereo_params* p)
 int dcmt_stereo_refine_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, float* d_refined,
                            int rows, int cols, int batch, const dcmt_stereo_params* params, void* stream)
 {
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !d_depth || !d_left || !d_right || !d_refined || !params) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
-    if (params->iterations > 1000) return DCMT_E_INVALID;
-    StereoP P{params->baseline, params->focal, params->damp, params->max_depth, params->iterations < 0 ? 4 : params->iterations};
-    const plan::StereoPlan pl = plan::plan_stereo(rows, cols, batch);
-    if (pl.status != DCMT_OK) return pl.status;
-    const dim3 sg(pl.gx, pl.gy, pl.gz);
-    if (pl.lds_row)
-        hipLaunchKernelGGL(k_stereo_refine<true>, sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
-    else
-        hipLaunchKernelGGL(k_stereo_refine<false>, sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
-    DCMT_HIP(ctx, hipGetLastError());
-    return DCMT_OK;
+    return stereo_refine(ctx, d_depth, d_left, d_right, d_refined, rows, cols, batch, params, nullptr, false, stream);
+}
+
+int dcmt_stereo_refine_calib_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, float* d_refined,
+                                 int rows, int cols, int batch, const dcmt_stereo_params* params, const dcmt_stereo_calib* d_calib, void* stream)
+{
+    return stereo_refine(ctx, d_depth, d_left, d_right, d_refined, rows, cols, batch, params, d_calib, true, stream);
 }
 
 int dcmt_evaluate_dev(dcmt_ctx* ctx, const float* d_gt, const float* d_pred, int rows, int cols, int batch, float thresh, int mode,

@@ -1,6 +1,6 @@
 // dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h and dcmt_kernels_bgr.h, a code object of their
 // own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
-// dcmt_bgr_convert_dev, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_bgr_convert_dev, the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -24,23 +24,41 @@ void dcmt_default_cloud_params(dcmt_cloud_params* p)
     p->cy = 2.241806e+02;
 }
 
-// per-wave counts, their exclusive scan in one workgroup, then the scatter (dcmt_kernels_cloud.h)
-int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
-                            const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
+}  // extern "C"
+
+// per-wave counts, their exclusive scan in one workgroup, then the scatter (dcmt_kernels_cloud.h).  params: the host's one set of
+// intrinsics (dcmt_depth_to_cloud_dev) or null with d_table, the device's [batch] (dcmt_depth_to_cloud_calib_dev)
+static int depth_to_cloud(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                          const dcmt_cloud_params* params, const dcmt_cloud_params* d_table, dcmt_cloud_point* d_points, int64_t capacity,
+                          int32_t* d_offsets, void* stream)
 {
     DCMT_ON_DEVICE(ctx);
-    if (!ctx || !d_depth || !d_points || !d_offsets || !params) return DCMT_E_INVALID;
+    if (!ctx || !d_depth || !d_points || !d_offsets || (!params && !d_table)) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (capacity < 0 || (int64_t)batch * rows * cols > (int64_t)INT32_MAX) return DCMT_E_INVALID;
     if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_points % 16 != 0 || (uintptr_t)d_offsets % 4 != 0) return DCMT_E_INVALID;
-    if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
+    if (params && !intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, room = (uint32_t)std::min<int64_t>(capacity, INT32_MAX);
+    if (d_table && (!plan::calib_table_aligned((uintptr_t)d_table, 8) || !plan::calib_table_clear_of((uintptr_t)d_table, sizeof *d_table, batch, (uintptr_t)d_points, sizeof(dcmt_cloud_point) * (size_t)room) ||
+                    !plan::calib_table_clear_of((uintptr_t)d_table, sizeof *d_table, batch, (uintptr_t)d_offsets, sizeof(int32_t) * ((size_t)batch + 1))))
+        return DCMT_E_INVALID;
     const uint32_t chunks = eval_chunks(n), groups = eval_chunk_groups(n);
-    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
     const dim3 grid(chunks, batch);
     const uint32_t per = chunks * kCloudWaves;      // slab: [batch][chunks][kCloudWaves] uint32
     uint4* points = reinterpret_cast<uint4*>(d_points);
+    if (d_table) {
+        hipLaunchKernelGGL(k_cloud_count_calib, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, d_table, ctx->cloud_slab);
+        hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, ctx->cloud_slab, per * (uint32_t)batch, per, (uint32_t)batch, d_offsets);
+        const CloudTable kt{d_table};
+        if (d_bgr)
+            hipLaunchKernelGGL((k_cloud_scatter<true, CloudTable>), grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, kt, ctx->cloud_slab, points, room);
+        else
+            hipLaunchKernelGGL((k_cloud_scatter<false, CloudTable>), grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, kt, ctx->cloud_slab, points, room);
+        DCMT_HIP(ctx, hipGetLastError());
+        return DCMT_OK;
+    }
+    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
     hipLaunchKernelGGL(k_cloud_count, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, ctx->cloud_slab);
     hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, ctx->cloud_slab, per * (uint32_t)batch, per, (uint32_t)batch, d_offsets);
     if (d_bgr)
@@ -49,6 +67,70 @@ int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* 
         hipLaunchKernelGGL(k_cloud_scatter<false>, grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, k, ctx->cloud_slab, points, room);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+// k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h) on the context's winner plane (winner_generation, dcmt_ctx.h);
+// params / d_table as for depth_to_cloud
+static int reproject_depth(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                           const dcmt_reproject_params* d_table, float* d_out, int out_rows, int out_cols, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_depth || !d_out || (!params && !d_table)) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
+    if (params) {
+        if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
+        for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
+        for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols, dst_n = (uint32_t)out_rows * (uint32_t)out_cols;
+    const size_t n_px = (size_t)batch * dst_n;
+    if (plan::ranges_overlap((uintptr_t)d_depth, sizeof(float) * n * batch, (uintptr_t)d_out, sizeof(float) * n_px)) return DCMT_E_INVALID;
+    if (d_table && (!plan::calib_table_aligned((uintptr_t)d_table, 8) || !plan::calib_table_clear_of((uintptr_t)d_table, sizeof *d_table, batch, (uintptr_t)d_out, sizeof(float) * n_px)))
+        return DCMT_E_INVALID;
+    unsigned gen_tag = 0;
+    const int rc = winner_generation(ctx, n_px, n, st, &gen_tag);
+    if (rc != DCMT_OK) return rc;
+    const dim3 scatter_grid((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch);
+    if (d_table) {
+        hipLaunchKernelGGL(k_reproject_scatter_calib, scatter_grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, d_table, ctx->winner,
+                           (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
+        with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
+            hipLaunchKernelGGL(k_reproject_resolve_calib<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols,
+                               d_table, ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+        });
+        DCMT_HIP(ctx, hipGetLastError());
+        return DCMT_OK;
+    }
+    ReprojK k;
+    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
+    std::memcpy(k.M, params->M, sizeof k.M);
+    std::memcpy(k.K, params->K, sizeof k.K);
+    hipLaunchKernelGGL(k_reproject_scatter, scatter_grid, dim3(256), 0, st, d_depth, n,
+                       (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
+    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
+        hipLaunchKernelGGL(k_reproject_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k,
+                           ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+    });
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+int dcmt_depth_to_cloud_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                            const dcmt_cloud_params* params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
+{
+    if (!params) return DCMT_E_INVALID;
+    return depth_to_cloud(ctx, d_depth, d_bgr, rows, cols, batch, params, nullptr, d_points, capacity, d_offsets, stream);
+}
+
+int dcmt_depth_to_cloud_calib_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_bgr, int rows, int cols, int batch,
+                                  const dcmt_cloud_params* d_params, dcmt_cloud_point* d_points, int64_t capacity, int32_t* d_offsets, void* stream)
+{
+    if (!d_params) return DCMT_E_INVALID;
+    return depth_to_cloud(ctx, d_depth, d_bgr, rows, cols, batch, nullptr, d_params, d_points, capacity, d_offsets, stream);
 }
 
 // one streaming kernel (k_gauss5, dcmt_kernels_cloud.h), whose src and dst must not overlap: an in-place call writes to pp[0]
@@ -85,36 +167,18 @@ void dcmt_default_reproject_params(dcmt_reproject_params* p)
     p->K[8] = 1.0f;
 }
 
-// k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h) on the context's winner plane (winner_generation, dcmt_ctx.h)
 int dcmt_reproject_depth_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
                              float* d_out, int out_rows, int out_cols, void* stream)
 {
-    DCMT_ON_DEVICE(ctx);
-    if (!ctx || !d_depth || !d_out || !params) return DCMT_E_INVALID;
-    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
-    if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
-    if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
-    for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
-    for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const uint32_t n = (uint32_t)rows * (uint32_t)cols, dst_n = (uint32_t)out_rows * (uint32_t)out_cols;
-    const size_t n_px = (size_t)batch * dst_n;
-    if (plan::ranges_overlap((uintptr_t)d_depth, sizeof(float) * n * batch, (uintptr_t)d_out, sizeof(float) * n_px)) return DCMT_E_INVALID;
-    ReprojK k;
-    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
-    std::memcpy(k.M, params->M, sizeof k.M);
-    std::memcpy(k.K, params->K, sizeof k.K);
-    unsigned gen_tag = 0;
-    const int rc = winner_generation(ctx, n_px, n, st, &gen_tag);
-    if (rc != DCMT_OK) return rc;
-    hipLaunchKernelGGL(k_reproject_scatter, dim3((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch), dim3(256), 0, st, d_depth, n,
-                       (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
-    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
-        hipLaunchKernelGGL(k_reproject_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k,
-                           ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
-    });
-    DCMT_HIP(ctx, hipGetLastError());
-    return DCMT_OK;
+    if (!params) return DCMT_E_INVALID;
+    return reproject_depth(ctx, d_depth, rows, cols, batch, params, nullptr, d_out, out_rows, out_cols, stream);
+}
+
+int dcmt_reproject_depth_calib_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* d_params,
+                                   float* d_out, int out_rows, int out_cols, void* stream)
+{
+    if (!d_params) return DCMT_E_INVALID;
+    return reproject_depth(ctx, d_depth, rows, cols, batch, nullptr, d_params, d_out, out_rows, out_cols, stream);
 }
 
 // k_bgr_convert (dcmt_kernels_bgr.h) over the batch as one flat run of pixels, a launch per segment (plan_bgr_convert)

@@ -33,6 +33,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+#include "dcmt_calib.h"
 #include "dcmt_cloud.h"
 #include "dcmt_gauss.h"
 
@@ -74,9 +77,8 @@ __device__ __forceinline__ void cloud_load4(const float* __restrict__ p, uint32_
     }
 }
 
-// grid (eval_chunks(n), frames), 256 threads; G = eval_chunk_groups(n).  slab: [frames][chunks][kCloudWaves] counts
-__global__ __launch_bounds__(kCloudThreads)
-void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
+// the counting of one workgroup (k_cloud_count, k_cloud_count_calib)
+__device__ __forceinline__ void cloud_count_run(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
 {
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
     const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
@@ -90,6 +92,27 @@ void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint
         for (int i = 0; i < 4; ++i) cnt += (uint32_t)__popcll(__ballot(d[i] > 0.0f));
     }
     if (l == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + w] = cnt;
+}
+
+// grid (eval_chunks(n), frames), 256 threads; G = eval_chunk_groups(n).  slab: [frames][chunks][kCloudWaves] counts
+__global__ __launch_bounds__(kCloudThreads)
+void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
+{
+    cloud_count_run(depth, n, G, slab);
+}
+
+// the same with a table of per-frame intrinsics (dcmt_calib.h): a frame whose record is bad counts nothing, so the scan's offsets
+// stay true and k_cloud_scatter<.., CloudTable>, which skips the frame, leaves no gap
+__global__ __launch_bounds__(kCloudThreads)
+void k_cloud_count_calib(const float* __restrict__ depth, uint32_t n, uint32_t G, const dcmt_cloud_params* __restrict__ table,
+                         uint32_t* __restrict__ slab)
+{
+    CloudK k;
+    if (!load_cloud_record(table, blockIdx.y, k)) {                 // wave-uniform: one scalar load per wave
+        if ((threadIdx.x & 63) == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + threadIdx.x / 64] = 0u;
+        return;
+    }
+    cloud_count_run(depth, n, G, slab);
 }
 
 // one workgroup of 1024 threads.  slab: entries counts in, exclusive bases out; per = entries per frame (chunks * kCloudWaves, a
@@ -131,12 +154,24 @@ void k_cloud_scan(uint32_t* __restrict__ slab, uint32_t entries, uint32_t per, u
     }
 }
 
+// The intrinsics as k_cloud_scatter's argument `geo`: CloudK itself, by value (dcmt_depth_to_cloud_dev), or a table of per-frame
+// records (dcmt_depth_to_cloud_calib_dev, dcmt_calib.h), of which the workgroup takes record blockIdx.y -- loaded once per wave
+// through the scalar cache in front of the pixel loop, into the SGPRs where the by-value argument lies.  A frame whose record is bad
+// was counted as empty (k_cloud_count_calib) and is skipped
+struct CloudTable { const dcmt_cloud_params* __restrict__ records; };
+__device__ __forceinline__ const CloudK& cloud_k(const CloudK& arg, const CloudK&) { return arg; }
+__device__ __forceinline__ const CloudK& cloud_k(const CloudTable&, const CloudK& rec) { return rec; }
+
 // grid (eval_chunks(n), frames), 256 threads.  slab: the bases k_cloud_scan left.  bgr: [frames][n][3] bytes or null.
-template <bool kColor>
+template <bool kColor, typename KSrc = CloudK>
 __global__ __launch_bounds__(kCloudThreads)
-void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict__ bgr, uint32_t n, uint32_t G, uint32_t cols, CloudK k,
+void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict__ bgr, uint32_t n, uint32_t G, uint32_t cols, KSrc geo,
                      const uint32_t* __restrict__ slab, uint4* __restrict__ points, uint32_t capacity)
 {
+    [[maybe_unused]] CloudK rec;
+    if constexpr (std::is_same_v<KSrc, CloudTable>)
+        if (!load_cloud_record(geo.records, blockIdx.y, rec)) return;
+    const CloudK& k = cloud_k(geo, rec);
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
     const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
     const uint8_t* __restrict__ cp = kColor ? bgr + 3 * (size_t)blockIdx.y * n : nullptr;

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dcmt_calib.h"
 #include "dcmt_cloud.h"
 #include "dcmt_dot_rn.h"
 #include "dcmt_kernels_cloud.h"
@@ -43,9 +44,8 @@ __device__ __forceinline__ float reproject_t2(const ReprojK& k, uint32_t x, uint
 // thread t takes pixels t, t + 256, t + 512, t + 768 of them: four independent coalesced dword loads in flight per thread (the
 // pattern of k_minmax), and the 64 atomics of a wave instruction start from 64 consecutive source pixels, so under a near-identity
 // warp they hit runs of consecutive dwords of the winner plane.
-__global__ __launch_bounds__(256)
-void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, unsigned* __restrict__ winner,
-                         uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
+__device__ __forceinline__ void reproject_scatter_run(const float* __restrict__ depth, uint32_t n, uint32_t cols, const ReprojK& k, unsigned* __restrict__ winner,
+                                                      uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
 {
     const uint32_t q0 = blockIdx.x * (uint32_t)kReprojectPxPerWg + threadIdx.x;
     const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
@@ -69,6 +69,25 @@ void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t c
         if ((unsigned)u < dst_cols && (unsigned)v < dst_rows)
             atomicMax(&win[(size_t)v * dst_cols + (unsigned)u], gen_tag | q);
     }
+}
+
+__global__ __launch_bounds__(256)
+void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, unsigned* __restrict__ winner,
+                         uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
+{
+    reproject_scatter_run(depth, n, cols, k, winner, dst_rows, dst_cols, gen_tag);
+}
+
+// the same with the frame's own record: record blockIdx.y of the table (dcmt_calib.h), loaded once per wave through the scalar cache
+// in front of the pixel loop.  A frame with a bad record scatters nothing: its part of the winner plane keeps no tag of this
+// generation and k_reproject_resolve_calib writes zeros there
+__global__ __launch_bounds__(256)
+void k_reproject_scatter_calib(const float* __restrict__ depth, uint32_t n, uint32_t cols, const dcmt_reproject_params* __restrict__ table,
+                               unsigned* __restrict__ winner, uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
+{
+    ReprojK k;
+    if (!load_reproject_record(table, blockIdx.y, k)) return;
+    reproject_scatter_run(depth, n, cols, k, winner, dst_rows, dst_cols, gen_tag);
 }
 
 // One thread per PW neighbouring destination pixels of the whole batch (a thread's pixels may lie in two frames): 8- / 16-byte
@@ -96,6 +115,52 @@ void k_reproject_resolve(const float* __restrict__ depth, uint32_t n, uint32_t c
         const uint32_t q = w[j] & mask;
         if ((w[j] & ~mask) == gen_tag && q < n) {             // (q < n holds for every tag this call's scatter wrote)
             const float z = depth[f * n + q];
+            const uint32_t y = q / cols, x = q - y * cols;
+            float x_, y_;
+            o[j] = reproject_t2(k, x, y, z, x_, y_);
+        }
+    }
+    if constexpr (PW == 4) *reinterpret_cast<float4*>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
+    else if constexpr (PW == 2) *reinterpret_cast<float2*>(out + i) = make_float2(o[0], o[1]);
+    else out[i] = o[0];
+}
+
+// k_reproject_resolve with the record of each pixel's OWN frame, the scheme of k_project_resolve_calib (dcmt_kernels_v1.h): the frame
+// of the wave's first pixel and that pixel's place in it from one division per wave on the scalar unit; where the wave's 64 * PW
+// pixels end inside that frame -- almost always -- its record comes through the scalar cache once per wave, as the by-value
+// argument of the uniform kernel does, and no lane divides.  Otherwise each lane finds the frame of its first pixel and each pixel
+// that holds a winner gathers the 48 bytes reproject_t2 reads from its own frame's record.  Either way the arithmetic is
+// reproject_t2's.
+template <int PW>
+__global__ __launch_bounds__(256)
+void k_reproject_resolve_calib(const float* __restrict__ depth, uint32_t n, uint32_t cols, const dcmt_reproject_params* __restrict__ table,
+                               const unsigned* __restrict__ winner, float* __restrict__ out, uint32_t dst_n, size_t n_px, unsigned gen_tag, int idx_bits)
+{
+    const uint32_t l = threadIdx.x & 63;
+    const size_t i_wave = (blockIdx.x * (size_t)256 + __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u)) * PW;     // the wave's first pixel
+    const size_t i = i_wave + (size_t)l * PW;
+    if (i >= n_px) return;
+    unsigned w[PW];
+    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
+    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
+    else w[0] = winner[i];
+    const unsigned mask = (1u << idx_bits) - 1u;
+    const uint32_t f_wave = (uint32_t)(i_wave / dst_n);                           // i_wave < n_px here, so f_wave < frames
+    const uint32_t r_wave = (uint32_t)(i_wave - (size_t)f_wave * dst_n);
+    const bool one_frame = r_wave + 64u * PW <= dst_n;                            // (a frame has < 2^29 pixels: no overflow)
+    uint32_t f = f_wave, r = r_wave + l * PW;                                     // r < dst_n + 256
+    ReprojK k;
+    if (one_frame) load_reproject_t2_record(table, f_wave, k);
+    else { const uint32_t df = r / dst_n; f += df; r -= df * dst_n; }             // i < n_px, so f < frames, and so is every frame below:
+    float o[PW];                                                                  // i + PW <= n_px (the pixel count is a multiple of PW)
+#pragma unroll
+    for (int j = 0; j < PW; ++j) {
+        if (!one_frame && j > 0 && ++r == dst_n) { r = 0; ++f; }
+        o[j] = 0.0f;
+        const uint32_t q = w[j] & mask;
+        if ((w[j] & ~mask) == gen_tag && q < n) {             // (q < n holds for every tag this call's scatter wrote)
+            if (!one_frame) load_reproject_t2_record(table, f, k);
+            const float z = depth[(size_t)f * n + q];
             const uint32_t y = q / cols, x = q - y * cols;
             float x_, y_;
             o[j] = reproject_t2(k, x, y, z, x_, y_);

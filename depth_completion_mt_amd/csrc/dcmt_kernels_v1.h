@@ -20,10 +20,12 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include "dcmt_calib.h"
 #include "dcmt_gauss.h"
 #include "dcmt_dot_rn.h"
 #include <float.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "dcmt_median.h"
 
@@ -221,6 +223,150 @@ void k_project_resolve(const float* __restrict__ pts, ProjMats M, const unsigned
     else sparse[i] = o[0];
 }
 
+// ---- N2 with a table of per-frame matrices (dcmt_project_calib, dcmt_calib.h) -------------------------------------------------
+// A record as ProjMats; `ok`: every one of its 24 entries is finite, tested on the bits
+__device__ __forceinline__ bool load_project_record(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
+{
+    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) { const uint32_t b = w[i]; ok = ok && bits_finite32(b); M.T[i] = __uint_as_float(b); }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) { const uint32_t b = w[12 + i]; ok = ok && bits_finite32(b); M.P[i] = __uint_as_float(b); }
+    return ok;
+}
+
+// the same test by 24 lanes of a wave at once, a word each, and one ballot (on the scalar unit it takes some seventy instructions
+// per wave, in a kernel that has about as many per wave in all).  EVERY lane of the wave must be active.
+__device__ __forceinline__ bool project_record_ok_wave(const dcmt_project_calib* __restrict__ table, uint32_t f)
+{
+    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
+    const uint32_t l = threadIdx.x & 63;
+    return __ballot(l < kProjRecWords && !bits_finite32(w[l < kProjRecWords ? l : 0])) == 0;
+}
+
+// the whole record, untested
+__device__ __forceinline__ void load_project_record_untested(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
+{
+    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) M.T[i] = __uint_as_float(w[i]);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) M.P[i] = __uint_as_float(w[12 + i]);
+}
+
+// what point_depth reads (T rows 0..2, P row 2), untested: a pixel with a tag of the call's generation lies in a frame whose record
+// the scatter has accepted
+__device__ __forceinline__ void load_project_depth_record(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
+{
+    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) M.T[i] = __uint_as_float(w[i]);
+#pragma unroll
+    for (int i = 8; i < 12; ++i) M.P[i] = __uint_as_float(w[12 + i]);
+}
+
+// k_project_scatter with the record of each point's OWN frame.  A workgroup's 256 points span a sweep boundary wherever d_offsets
+// says so (empty sweeps included), so the frame is the lane's.  The common case -- a sweep has some 120 000 points -- is a wave
+// whose points all lie in the frame of the workgroup's first point: that frame's record is requested through the scalar cache as
+// soon as the workgroup's search has found it, while the lanes' own offsets loads are in flight (the kernel is a chain of dependent
+// loads), and tested by 24 lanes and one ballot; a second ballot asks whether every active lane of the wave stayed in that frame.
+// If so the wave runs the instruction stream of the uniform kernel on SGPRs.  Otherwise (a wave behind a sweep boundary) each lane
+// gathers and tests its own frame's 96 bytes.  Measured 13 % behind the uniform call, all of it here.  A frame with a bad record scatters nothing: its part of the winner
+// plane keeps no tag of this generation and the resolve writes zeros there.
+__global__ __launch_bounds__(256)
+void k_project_scatter_calib(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
+                             const dcmt_project_calib* __restrict__ table, unsigned* __restrict__ winner, int rows, int cols, unsigned gen_tag)
+{
+    __shared__ int s_lo;
+    const int i0 = blockIdx.x * 256;
+    if (threadIdx.x == 0) {
+        int lo = 0, hi = batch;
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= i0) lo = mid; else hi = mid; }
+        s_lo = lo;
+    }
+    __syncthreads();
+    const int lo_wg = __builtin_amdgcn_readfirstlane(s_lo);         // 0 <= lo_wg < batch whatever the offsets hold
+    const bool ok_wg = project_record_ok_wave(table, (uint32_t)lo_wg);            // (every lane is still active here)
+    const int i = i0 + threadIdx.x;
+    if (i >= n_points) return;
+    ProjMats M_wg;
+    load_project_record_untested(table, (uint32_t)lo_wg, M_wg);
+    int lo = lo_wg;
+    while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;            // lo_wg <= lo < batch
+    const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
+    const auto scatter = [&](const ProjMats& M) {
+        int u, v; float d;
+        if (!project_point(M, p.x, p.y, p.z, rows, cols, u, v, d)) return;
+        // project_point's bounds are float compares, which -ffinite-math-only lets the compiler treat as if uf and vf were finite; a
+        // record that is finite but huge makes them NaN.  The address is formed only after the bound has held in the integer domain
+        if ((unsigned)u < (unsigned)cols && (unsigned)v < (unsigned)rows)
+            atomicMax(&winner[((size_t)lo * rows + (unsigned)v) * cols + (unsigned)u], gen_tag | (unsigned)i);
+    };
+    if (__ballot(lo != lo_wg) == 0) {                               // (over the active lanes)
+        if (ok_wg) scatter(M_wg);
+    } else {
+        ProjMats M;
+        if (load_project_record(table, (uint32_t)lo, M)) scatter(M);
+    }
+}
+
+// k_project_resolve with the record of each pixel's OWN frame: the winning point's frame is the frame of the pixel it won.  A
+// wave's 64 * PW consecutive pixels lie in one frame almost always (a frame of 352 x 1216 has 1672 such runs, one of which holds its
+// end): the frame of the wave's first pixel and that pixel's place in it are wave-uniform -- one division per wave, on the scalar
+// unit -- and where the run ends inside the frame, that frame's record comes through the scalar cache once per wave and no lane
+// divides.  Otherwise each lane finds the frame of its first pixel (a 32-bit division) and each pixel that holds a winner gathers
+// the 64 bytes point_depth reads from its own frame's record.  frame_px = rows * cols.
+template <int PW>
+__global__ __launch_bounds__(256)
+void k_project_resolve_calib(const float* __restrict__ pts, const dcmt_project_calib* __restrict__ table, const unsigned* __restrict__ winner,
+                             float* __restrict__ sparse, uint32_t frame_px, size_t n_px, unsigned gen_tag, int idx_bits)
+{
+    const uint32_t l = threadIdx.x & 63;
+    const size_t i_wave = (blockIdx.x * (size_t)256 + __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u)) * PW;     // the wave's first pixel
+    const size_t i = i_wave + (size_t)l * PW;
+    if (i >= n_px) return;
+    unsigned w[PW];
+    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
+    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
+    else w[0] = winner[i];
+    const unsigned mask = (1u << idx_bits) - 1u;
+    const uint32_t f_wave = (uint32_t)(i_wave / frame_px);                        // i_wave < n_px here, so f_wave < batch
+    const uint32_t r_wave = (uint32_t)(i_wave - (size_t)f_wave * frame_px);
+    float o[PW];
+    if (r_wave + 64u * PW <= frame_px) {                                          // (a frame has < 2^29 pixels: no overflow)
+        ProjMats M;
+        load_project_depth_record(table, f_wave, M);
+#pragma unroll
+        for (int k = 0; k < PW; ++k) {
+            o[k] = 0.0f;
+            if ((w[k] & ~mask) == gen_tag) {
+                const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)(w[k] & mask));
+                o[k] = point_depth(M, p.x, p.y, p.z);
+            }
+        }
+    } else {
+        uint32_t r = r_wave + l * PW;                                             // < frame_px + 256
+        const uint32_t df = r / frame_px;
+        uint32_t f = f_wave + df;                                                 // i < n_px, so f < batch, and so is every frame below:
+        r -= df * frame_px;                                                       // i + PW <= n_px (the pixel count is a multiple of PW)
+#pragma unroll
+        for (int k = 0; k < PW; ++k) {
+            if (k > 0 && ++r == frame_px) { r = 0; ++f; }
+            o[k] = 0.0f;
+            if ((w[k] & ~mask) == gen_tag) {
+                ProjMats M;
+                load_project_depth_record(table, f, M);
+                const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)(w[k] & mask));
+                o[k] = point_depth(M, p.x, p.y, p.z);
+            }
+        }
+    }
+    if constexpr (PW == 4) *reinterpret_cast<float4*>(sparse + i) = make_float4(o[0], o[1], o[2], o[3]);
+    else if constexpr (PW == 2) *reinterpret_cast<float2*>(sparse + i) = make_float2(o[0], o[1]);
+    else sparse[i] = o[0];
+}
+
 // ---------------------------------------------------------------------------------
 // N4: the stereo photometric refinement behind the path (SL/main_sl.cpp:715-885, driven from :1165-1246).  One thread
 // per pixel runs all sweeps for its own disparity; the images are read as bytes and the EntryType fields (value,
@@ -236,6 +382,9 @@ void k_project_resolve(const float* __restrict__ pts, ProjMats M, const unsigned
 // f32 arithmetic, one rounding per operation, in the reference's order.
 // ---------------------------------------------------------------------------------
 struct StereoP { float baseline, focal, damp, max_depth; int iterations; };
+struct StereoTable { const dcmt_stereo_calib* __restrict__ records; float damp, max_depth; int iterations; };
+__device__ __forceinline__ const StereoP& stereo_p(const StereoP& arg, const StereoP&) { return arg; }
+__device__ __forceinline__ const StereoP& stereo_p(const StereoTable&, const StereoP& rec) { return rec; }
 
 __device__ __forceinline__ float grey_dx(const uint8_t* g, int r, int c, int rows, int cols)
 {
@@ -254,11 +403,27 @@ __device__ __forceinline__ float grey_dx(const uint8_t* g, int r, int c, int row
 // bytes then come from ds_read_u8 instead of four byte gathers through the texture path, which is what bound the first
 // version (1.42 ms per 256 pairs of 1242x375 with ~250 VALU instructions per pixel: the CU's address unit takes a 64-lane byte
 // load at a few lanes per cycle).  Dynamic LDS: cols + 4 bytes.
-template <bool LDS_ROW>
+// P_arg: StereoP itself, by value (dcmt_stereo_refine_dev), or StereoTable (dcmt_stereo_refine_calib_dev): damp, max_depth and
+// iterations with a table of per-frame baselines and focal lengths (dcmt_calib.h), of which the workgroup takes record blockIdx.z --
+// two dwords loaded once per wave through the scalar cache in front of the column loop.  A frame whose record is bad (a non-finite
+// entry, focal zero) is written as zeros
+template <bool LDS_ROW, typename G = StereoP>
 __global__ __launch_bounds__(256)
 void k_stereo_refine(const float* __restrict__ depth, const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                     float* __restrict__ out, int rows, int cols, int batch, StereoP P)
+                     float* __restrict__ out, int rows, int cols, int batch, G P_arg)
 {
+    [[maybe_unused]] StereoP P_rec;
+    if constexpr (std::is_same_v<G, StereoTable>) {
+        const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(P_arg.records) + 2 * (size_t)blockIdx.z;
+        const uint32_t bb = w[0], fb = w[1];
+        if (!(bits_finite32(bb) && bits_finite32(fb) && (fb << 1) != 0)) {
+            float* __restrict__ o = out + ((size_t)blockIdx.z * rows + blockIdx.y) * cols;
+            for (int j = blockIdx.x * 256 + threadIdx.x; j < cols; j += gridDim.x * 256) o[j] = 0.0f;
+            return;
+        }
+        P_rec = StereoP{__uint_as_float(bb), __uint_as_float(fb), P_arg.damp, P_arg.max_depth, P_arg.iterations};
+    }
+    const StereoP& P = stereo_p(P_arg, P_rec);
     extern __shared__ uint8_t s_row[];             // LDS_ROW: [0] pad, [1 .. n] the row (and the next row's first pixel), two pads
     const int j0 = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
     if constexpr (LDS_ROW) {

@@ -103,6 +103,15 @@ inline int resolve_vec(size_t n_px, uintptr_t addr)
     return n_px % 4 == 0 && addr % 16 == 0 ? 4 : n_px % 2 == 0 && addr % 8 == 0 ? 2 : 1;
 }
 
+// ---- the per-frame calibration tables of the *_calib_dev calls ----------------------------------------------------------------
+// A table of `batch` records of `rec` bytes at address `table`: present and aligned to `align` ...
+inline bool calib_table_aligned(uintptr_t table, size_t align) { return table != 0 && table % align == 0; }
+// ... and clear of an output buffer of the same call (`out_bytes` bytes at `out`)
+inline bool calib_table_clear_of(uintptr_t table, size_t rec, int batch, uintptr_t out, size_t out_bytes)
+{
+    return !ranges_overlap(table, rec * (size_t)batch, out, out_bytes);
+}
+
 // ---- dcmt_slic_labels_dev -----------------------------------------------------------------------------------------------
 inline int slic_num_centers(int rows, int cols, int step)
 {

@@ -457,6 +457,53 @@ int dcmt_reproject_depth_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int 
 int dcmt_reproject_depth(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, int rows, int cols,
                          const dcmt_reproject_params *params, float *out, size_t out_row_stride, int out_rows, int out_cols);
 
+/* ---- per-frame calibration tables for the four geometric *_dev calls ----------------------------------- */
+
+/* dcmt_project_points_dev, dcmt_depth_to_cloud_dev, dcmt_reproject_depth_dev and dcmt_stereo_refine_dev take ONE camera geometry for
+ * the whole batch (the reference runs one frame of one drive).  A real batch is mixed -- the KITTI depth-completion validation and
+ * selection sets draw their frames from five recording days, each with its own P_rect, R_rect, Tr_velo_to_cam, focal length and
+ * baseline -- so each of the four has a twin that takes a DEVICE table of [batch] records instead, record f for frame f:
+ *     call                              record                  bytes   table alignment
+ *     dcmt_project_points_calib_dev     dcmt_project_calib      96      16    T rows 0..2 at byte 0, P at byte 48, row-major
+ *     dcmt_depth_to_cloud_calib_dev     dcmt_cloud_params       32      8     fx, fy, cx, cy at bytes 0, 8, 16, 24
+ *     dcmt_reproject_depth_calib_dev    dcmt_reproject_params   136     8     fx fy cx cy at 0, M at 32, K at 96, 4 bytes of padding
+ *     dcmt_stereo_refine_calib_dev      dcmt_stereo_calib       8       8     baseline at byte 0, focal at byte 4
+ * The table is read by the kernels, on the caller's stream: it may be written by earlier work on that stream, and it must stay
+ * unchanged until the call's kernels have run.  It is only read.  Typically it is uploaded once, outside the hot loop.
+ * Everything else is as for the uniform twin -- the arithmetic operation by operation, the winner plane and its generations, the
+ * packed cloud layout and its true offsets, the in-place and overlap rules, the load widths alignment allows, every argument
+ * check that needs no table; the calls never synchronise and allocate nothing their twins do not.  Frame f of a table call is,
+ * bit for bit, what the uniform call returns for frame f alone with record f.
+ * DCMT_E_INVALID in addition: a null table, a table not aligned as listed, a table that overlaps an output buffer (d_sparse;
+ * d_points or d_offsets; d_out; d_refined).
+ *
+ * BAD RECORDS.  The host cannot look into a device table without synchronising, so what the uniform calls refuse on the host is
+ * tested per frame on the device: a non-finite entry (of the entries that are read: T rows 0..2 and P; the intrinsics; M rows
+ * 0..2 and K rows 0..1; baseline and focal), fx or fy zero, focal zero.  A frame whose record fails gives the EMPTY result -- a zero
+ * plane from the projection, the reprojection and the refinement; no records from the cloud, in its count pass too, so that
+ * d_offsets[f + 1] == d_offsets[f] and every other frame's offsets stay true -- and the other frames are what they would be
+ * with a good record there.  The library is built with -ffinite-math-only: the kernels test the BIT PATTERN of a record (its
+ * exponent field, read as an integer), never a float compare the compiler may remove.  A record that is finite can still overflow
+ * the arithmetic (Inf - Inf); its frame is then whatever that arithmetic gives, but every address that depends on a record's values
+ * is formed only after an integer-domain bound has held ((unsigned)u < cols && (unsigned)v < rows in both scatter kernels), so the
+ * calls are memory-safe on any table contents and no other frame is touched. */
+typedef struct { float T[12]; float P[12]; } dcmt_project_calib;   /* rows 0..2 of T, then P; row-major; 96 B */
+typedef struct { float baseline, focal; }    dcmt_stereo_calib;    /* 8 B */
+
+int dcmt_project_points_calib_dev(dcmt_ctx *ctx, const float *d_points, const int32_t *d_offsets, int n_points, int batch,
+                                  const dcmt_project_calib *d_calib /* [batch], 16-byte aligned */,
+                                  float *d_sparse, int rows, int cols, void *stream);
+int dcmt_depth_to_cloud_calib_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_bgr /* or NULL */,
+                                  int rows, int cols, int batch, const dcmt_cloud_params *d_params /* [batch], 8-byte aligned */,
+                                  dcmt_cloud_point *d_points, int64_t capacity, int32_t *d_offsets, void *stream);
+int dcmt_reproject_depth_calib_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch,
+                                   const dcmt_reproject_params *d_params /* [batch], 8-byte aligned */,
+                                   float *d_out, int out_rows, int out_cols, void *stream);
+/* params: HOST, as for dcmt_stereo_refine_dev: damp, max_depth and iterations are used, its baseline and focal are ignored */
+int dcmt_stereo_refine_calib_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_left, const uint8_t *d_right,
+                                 float *d_refined, int rows, int cols, int batch, const dcmt_stereo_params *params,
+                                 const dcmt_stereo_calib *d_calib /* [batch], 8-byte aligned */, void *stream);
+
 /* ---- producer of the image inputs: camera BGR bytes -> 8-bit Lab and grey planes ----------------------- */
 
 /* What the reference mains do with every camera frame before anything else: cv::cvtColor(image, lab_image, cv::COLOR_BGR2Lab)
