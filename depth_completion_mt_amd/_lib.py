@@ -36,6 +36,7 @@ EXPORTS = (
     "dcmt_default_reproject_params", "dcmt_reproject_depth_dev", "dcmt_reproject_depth",
     "dcmt_bgr_convert_dev", "dcmt_bgr_convert", "dcmt_lab_tables",
     "dcmt_project_points_calib_dev", "dcmt_depth_to_cloud_calib_dev", "dcmt_reproject_depth_calib_dev", "dcmt_stereo_refine_calib_dev",
+    "dcmt_crop_frames_dev", "dcmt_depth_to_u16_dev", "dcmt_depth_to_u16",
 )
 
 
@@ -95,6 +96,12 @@ class ProjectCalib(ctypes.Structure):
 class StereoCalib(ctypes.Structure):
     """Mirror of dcmt_stereo_calib (include/dcmt.h): one frame's record of dcmt_stereo_refine_calib_dev."""
     _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float)]
+
+
+class CropSrc(ctypes.Structure):
+    """Mirror of dcmt_crop_src (include/dcmt.h): one frame's record of dcmt_crop_frames_dev, 32 bytes."""
+    _fields_ = [("offset", ctypes.c_uint64), ("row_stride", ctypes.c_uint32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+                ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
 
 
 def build(force: bool = False) -> str:
@@ -190,6 +197,9 @@ def lib() -> ctypes.CDLL:
         L.dcmt_depth_to_cloud_calib_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, i64, vp, vp]
         L.dcmt_reproject_depth_calib_dev.argtypes = [vp, vp, i, i, i, vp, vp, i, i, vp]
         L.dcmt_stereo_refine_calib_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_crop_frames_dev.argtypes = [vp, vp, sz, vp, i, vp, i, i, i, vp]
+        L.dcmt_depth_to_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, vp]
+        L.dcmt_depth_to_u16.argtypes = [vp, vp, sz, f32, vp, sz, i, i]
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

@@ -242,6 +242,70 @@ def make_stereo_calib(baseline, focal) -> np.ndarray:
     return out
 
 
+CROP_SRC_DTYPE = np.dtype([("offset", "<u8"), ("row_stride", "<u4"), ("rows", "<i4"), ("cols", "<i4"), ("x0", "<i4"), ("y0", "<i4"),
+                           ("reserved", "<u4")])                                                              # dcmt_crop_src, 32 B
+
+
+def kitti_crop_origin(rows: int, cols: int, out_rows: int = 352, out_cols: int = 1216):
+    """(y0, x0) of the bottom-centre out_rows x out_cols window of a rows x cols frame, the cut the KITTI depth benchmark's cropped
+    sets are made with AS THIS PROJECT STATES IT: y0 = rows - out_rows, x0 = (cols - out_cols) // 2.  What a crop table holds is
+    explicit origins; this is only their default."""
+    return rows - out_rows, (cols - out_cols) // 2
+
+
+def pack_ragged(frames):
+    """Frames of several sizes, [rows][cols] or [rows][cols][3] arrays of one dtype, packed back to back into one flat uint8 array:
+    (bytes, shapes [(rows, cols)], offsets in bytes) -- what make_crop_table's defaults describe."""
+    frames = [np.ascontiguousarray(f) for f in frames]
+    assert frames and all(f.ndim in (2, 3) and f.dtype == frames[0].dtype and f.shape[2:] == frames[0].shape[2:] for f in frames)
+    sizes = [f.nbytes for f in frames]
+    offsets = [int(v) for v in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
+    flat = np.concatenate([f.reshape(-1).view(np.uint8) for f in frames])
+    return flat, [tuple(f.shape[:2]) for f in frames], offsets
+
+
+def make_crop_table(shapes, out_shape, elem_bytes: int, offsets=None, row_strides=None, origins=None, src_bytes: int | None = None) -> np.ndarray:
+    """The table of Context.crop_frames_dev: one dcmt_crop_src record per frame.  shapes: [(rows, cols)] of the source frames;
+    out_shape: (out_rows, out_cols) of the window; elem_bytes: 1..4.  Defaults: frames packed back to back from byte 0 (offsets),
+    tight rows (row_strides = cols * elem_bytes), origins [(y0, x0)] from kitti_crop_origin.  Raises ValueError on what the device
+    call would answer with a zero frame: a size below 1, a negative origin, a window that leaves its frame, a stride shorter than a
+    row and -- where src_bytes, the size of the source buffer, is given -- a frame that leaves the buffer.  Upload it with
+    calib_to_device."""
+    out_rows, out_cols = (int(v) for v in out_shape)
+    if elem_bytes not in (1, 2, 3, 4) or out_rows < 1 or out_cols < 1:
+        raise ValueError(f"elem_bytes must be 1..4 and the window at least 1 x 1; got {elem_bytes}, {out_rows} x {out_cols}")
+    shapes = [(int(r), int(c)) for r, c in shapes]
+    b = len(shapes)
+    if row_strides is None:
+        row_strides = [c * elem_bytes for _, c in shapes]
+    if offsets is None:
+        offsets, at = [], 0
+        for (r, _), st in zip(shapes, row_strides):
+            offsets.append(at)
+            at += max(r, 0) * int(st)
+    if origins is None:
+        origins = [kitti_crop_origin(r, c, out_rows, out_cols) for r, c in shapes]
+    if not (len(offsets) == len(row_strides) == len(origins) == b):
+        raise ValueError("shapes, offsets, row_strides and origins must have one entry per frame")
+    out = np.zeros(b, CROP_SRC_DTYPE)
+    for f, ((r, c), off, st, (y0, x0)) in enumerate(zip(shapes, offsets, row_strides, origins)):
+        off, st, y0, x0 = int(off), int(st), int(y0), int(x0)
+        if r < 1 or c < 1 or r > 0x7fffffff or c > 0x7fffffff:
+            raise ValueError(f"frame {f}: rows and cols must be 1 .. 2^31 - 1; got {r} x {c}")
+        if x0 < 0 or y0 < 0:
+            raise ValueError(f"frame {f}: a negative origin ({y0}, {x0})")
+        if x0 + out_cols > c or y0 + out_rows > r:
+            raise ValueError(f"frame {f}: the {out_rows} x {out_cols} window at ({y0}, {x0}) leaves the {r} x {c} frame")
+        if st < c * elem_bytes or st > 0xffffffff:
+            raise ValueError(f"frame {f}: row_stride {st} is not in {c * elem_bytes} .. 2^32 - 1")
+        if off < 0 or off >= 1 << 64:
+            raise ValueError(f"frame {f}: offset {off}")
+        if src_bytes is not None and off + (r - 1) * st + c * elem_bytes > src_bytes:
+            raise ValueError(f"frame {f}: ends at byte {off + (r - 1) * st + c * elem_bytes} of a source of {src_bytes}")
+        out[f] = (off, st, r, c, x0, y0, 0)
+    return out
+
+
 def calib_to_device(table: np.ndarray, device="cuda"):
     """A make_*_calib array as the CUDA tensor the *_calib_dev wrappers take: uint8 [b][record bytes] (torch has no structured
     dtype).  One synchronous upload: do it outside the hot loop."""
@@ -552,6 +616,64 @@ class Context:
         _check(st, "dcmt_bgr_convert_dev")
         return (d_lab, d_gray) if lab and gray else d_lab if lab else d_gray
 
+    # ---- ragged frames in, the uint16 payload out (dcmt_crop_frames_dev, dcmt_depth_to_u16*) -----------------------------
+    def crop_frames_dev(self, d_src, d_table, out_rows: int, out_cols: int, elem_bytes: int | None = None, dtype=None, d_dst=None,
+                        stream: int | None = None):
+        """One window out of each frame of a ragged batch, into one uniform batch, in one launch (dcmt_crop_frames_dev).  d_src: a
+        flat uint8 CUDA tensor or any contiguous one -- all its bytes are the source buffer; d_table: a CUDA tensor holding [batch]
+        dcmt_crop_src records (make_crop_table, calib_to_device), read on the stream the call enqueues on.  The element is
+        elem_bytes bytes, or dtype's, or d_src's.  Returns [batch][out_rows][out_cols] of dtype (by default uint8, uint16, uint8
+        [...][3] or float32 for 1, 2, 3, 4 bytes), without synchronising; a frame whose record is bad is all zero.  d_dst: any
+        contiguous CUDA tensor of exactly the output's bytes, at any byte alignment.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_src) and _is_dev(d_table)
+        if dtype is None and elem_bytes is None:
+            dtype = d_src.dtype
+        if elem_bytes is None:
+            elem_bytes = torch.empty(0, dtype=dtype).element_size()
+        if dtype is None:
+            dtype = {1: torch.uint8, 2: torch.uint16, 3: torch.uint8, 4: torch.float32}[elem_bytes]
+        item = torch.empty(0, dtype=dtype).element_size()
+        assert elem_bytes in (1, 2, 3, 4) and elem_bytes % item == 0, (elem_bytes, dtype)
+        batch, rem = divmod(d_table.numel() * d_table.element_size(), CROP_SRC_DTYPE.itemsize)
+        assert batch >= 1 and rem == 0, tuple(d_table.shape)
+        if d_dst is None:
+            shape = (batch, out_rows, out_cols) + ((elem_bytes // item,) if elem_bytes != item else ())
+            with _on_stream(stream, d_src):
+                d_dst = torch.empty(shape, dtype=dtype, device=d_src.device)
+        assert _is_dev(d_dst) and d_dst.numel() * d_dst.element_size() == batch * out_rows * out_cols * elem_bytes
+        st = L.lib().dcmt_crop_frames_dev(self._h, d_src.data_ptr(), d_src.numel() * d_src.element_size(), d_table.data_ptr(), elem_bytes,
+                                          d_dst.data_ptr(), out_rows, out_cols, batch, _stream(stream, d_src))
+        _check(st, "dcmt_crop_frames_dev")
+        return d_dst
+
+    def depth_to_u16_dev(self, d_depth, scale: float = 256.0, d_out=None, stream: int | None = None):
+        """A dense plane as the KITTI payload (dcmt_depth_to_u16_dev): round-to-nearest-even of depth * scale, saturated to
+        0..65535 -- cv::Mat::convertTo(CV_16U, scale), the inverse of complete_u16_dev's ingest.  d_depth: contiguous f32 CUDA tensor
+        [batch][rows][cols] (or [rows][cols]).  Returns a torch.uint16 CUDA tensor of its shape (d_out: any 2-byte dtype), without
+        synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
+        if d_out is None:
+            with _on_stream(stream, d_depth):
+                d_out = torch.empty(tuple(d_depth.shape), dtype=torch.uint16, device=d_depth.device)
+        assert _is_dev(d_out) and d_out.element_size() == 2 and d_out.numel() == b * r * c
+        st = L.lib().dcmt_depth_to_u16_dev(self._h, d_depth.data_ptr(), ctypes.c_float(scale), d_out.data_ptr(), r, c, b, _stream(stream, d_depth))
+        _check(st, "dcmt_depth_to_u16_dev")
+        return d_out
+
+    def depth_to_u16(self, frame: np.ndarray, scale: float = 256.0) -> np.ndarray:
+        """One frame of host memory (dcmt_depth_to_u16, synchronous; any row stride): uint16 [rows][cols]."""
+        a = _frame_f32(frame)
+        out = np.empty(a.shape, dtype=np.uint16)
+        st = L.lib().dcmt_depth_to_u16(self._h, a.ctypes.data, a.strides[0], ctypes.c_float(scale), out.ctypes.data, out.strides[0],
+                                       a.shape[0], a.shape[1])
+        _check(st, "dcmt_depth_to_u16")
+        return out
+
     def bgr_convert(self, frame: np.ndarray, lab: bool = True, gray: bool = False):
         """One frame of host memory (dcmt_bgr_convert, synchronous; any row stride): uint8 [rows][cols][3] B, G, R -> the Lab
         frame, the grey frame [rows][cols], or (lab, grey)."""
@@ -811,6 +933,17 @@ def bgr_to_gray(img):
     """cv::cvtColor(img, gray, cv::COLOR_BGR2GRAY) on 8-bit pixels (SL/main_sl.cpp:1167, :1171): uint8 [...][rows][cols][3] ->
     [...][rows][cols]; numpy or CUDA tensor, as bgr_to_lab."""
     return _bgr_convert(img, False)
+
+
+def depth_to_u16(depth, scale: float = 256.0):
+    """A depth plane in metres as KITTI stores it: uint16 round(depth * scale), ties to even, saturated (what the reference's
+    commented imwrite lines intend, LC/main_lc.cpp:233-234).  A numpy frame goes through the host entry point; a CUDA tensor
+    ([rows][cols] or [batch][rows][cols]) through the device one, on torch's current stream, without synchronising."""
+    if hasattr(depth, "is_cuda") and depth.is_cuda:
+        b = 1 if depth.dim() == 2 else depth.shape[0]
+        return _ctx_for(depth.shape[-2], depth.shape[-1], b, depth.device.index or 0).depth_to_u16_dev(depth, scale)
+    a = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).depth_to_u16(a, scale)
 
 
 def reproject_pc_colors(depth, bgr):

@@ -1,6 +1,6 @@
-// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h and dcmt_kernels_bgr.h, a code object of their
-// own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
-// dcmt_bgr_convert_dev, the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h, dcmt_kernels_bgr.h and dcmt_kernels_crop.h, a code
+// object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
+// dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -9,6 +9,7 @@
 #include "dcmt_ctx.h"
 #include "dcmt_kernels_bgr.h"
 #include "dcmt_kernels_cloud.h"
+#include "dcmt_kernels_crop.h"
 #include "dcmt_kernels_reproject.h"
 
 using namespace dcmt;
@@ -199,6 +200,44 @@ int dcmt_bgr_convert_dev(dcmt_ctx* ctx, const uint8_t* d_bgr, int rows, int cols
             constexpr int m = decltype(v)::value;
             hipLaunchKernelGGL((k_bgr_convert<(m & 1) != 0, (m & 2) != 0, (m & 4) != 0>), dim3(sg.grid), dim3(kBgrThreads), 0, st, src, sg.total, pl.passes, lab, gray);
         });
+        DCMT_HIP(ctx, hipGetLastError());
+    }
+    return DCMT_OK;
+}
+
+// k_crop_frames (dcmt_kernels_crop.h): one launch, the frame's record read and tested by the kernel (plan_crop)
+int dcmt_crop_frames_dev(dcmt_ctx* ctx, const void* d_src, size_t src_bytes, const dcmt_crop_src* d_table, int elem_bytes, void* d_dst,
+                         int out_rows, int out_cols, int batch, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_src || !d_table || !d_dst) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
+    const plan::CropPlan pl = plan::plan_crop(out_rows, out_cols, batch, elem_bytes, (uintptr_t)d_src, src_bytes, (uintptr_t)d_table, (uintptr_t)d_dst);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipLaunchKernelGGL(k_crop_frames, dim3(pl.grid_x, pl.grid_y), dim3(kCropThreads), 0, (hipStream_t)stream, (const uint8_t*)d_src, (uint64_t)src_bytes,
+                       d_table, (uint32_t)elem_bytes, (uint8_t*)d_dst, (uint32_t)out_rows, (uint32_t)out_cols, pl.band);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// k_depth_to_u16 (dcmt_kernels_crop.h) over the batch as one flat run of pixels, a launch per segment (plan_depth_to_u16)
+int dcmt_depth_to_u16_dev(dcmt_ctx* ctx, const float* d_depth, float scale, uint16_t* d_out, int rows, int cols, int batch, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_depth || !d_out) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    volatile float sv = scale;                       // on the bits, read through memory (finite_bits): finite, sign clear, not zero
+    const float sc = sv;
+    uint32_t sb;
+    std::memcpy(&sb, &sc, sizeof sb);
+    if (!finite_bits(scale) || (sb >> 31) != 0 || (sb << 1) == 0) return DCMT_E_INVALID;
+    const plan::U16Plan pl = plan::plan_depth_to_u16((size_t)batch * rows * cols, (uintptr_t)d_depth, (uintptr_t)d_out);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    for (size_t i = 0; i < pl.count; ++i) {
+        const plan::U16Segment sg = pl.segment(i);
+        if (pl.aligned) hipLaunchKernelGGL(k_depth_to_u16<true>, dim3(sg.grid), dim3(kU16Threads), 0, st, d_depth + sg.first, sg.total, scale, d_out + sg.first);
+        else hipLaunchKernelGGL(k_depth_to_u16<false>, dim3(sg.grid), dim3(kU16Threads), 0, st, d_depth + sg.first, sg.total, scale, d_out + sg.first);
         DCMT_HIP(ctx, hipGetLastError());
     }
     return DCMT_OK;

@@ -241,4 +241,14 @@ int dcmt_bgr_convert(dcmt_ctx* ctx, const uint8_t* bgr, size_t brs, int rows, in
     return rc == DCMT_OK ? fetch(ctx, {&l, &g}) : rc;
 }
 
+int dcmt_depth_to_u16(dcmt_ctx* ctx, const float* depth, size_t drs, float scale, uint16_t* out, size_t ors, int rows, int cols)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !out || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    Plane in(depth, drs, sizeof(float) * (size_t)cols, rows), o(out, ors, sizeof(uint16_t) * (size_t)cols, rows);
+    int rc = stage(ctx, {&in}, {&o});
+    if (rc == DCMT_OK) rc = dcmt_depth_to_u16_dev(ctx, (const float*)in.dev, scale, (uint16_t*)o.dev, rows, cols, 1, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o}) : rc;
+}
+
 }  // extern "C"

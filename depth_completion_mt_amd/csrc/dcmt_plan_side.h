@@ -10,6 +10,7 @@
 
 #include "dcmt_chunks.h"
 #include "dcmt_cloud.h"
+#include "dcmt_crop.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_tiles.h"
 
@@ -235,6 +236,71 @@ inline BgrPlan plan_bgr_convert(size_t px, uintptr_t bgr_addr, uintptr_t lab_add
     p.passes = kBgrMaxPasses;
     while (p.passes > 1 && px / p.share() < 512) p.passes /= 2;
     p.aligned = bgr_addr % 4 == 0 && lab_addr % 4 == 0 && gray_addr % 4 == 0;
+    return p;
+}
+
+// ---- dcmt_crop_frames_dev ----------------------------------------------------------------------------------------------
+// One launch for the whole ragged batch (dcmt_kernels_crop.h): grid (bands, frames) -- the frame is blockIdx.y, so nothing is
+// multiplied up to a flat index and 65535 frames are 65535 rows of the grid.  A workgroup takes a band of `band` destination rows,
+// its four waves a row at a time: kCropBandRows, so that a wave reads its frame's record once for four rows, halved while the call
+// makes fewer than 1024 workgroups, and doubled while a frame has more than 2^20 bands (a grid's x dimension times the workgroup
+// size stays below 2^32 for the tallest frame dcmt_create admits).  The checks on the buffers are here as well, tested without a device.
+struct CropPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, elem outside 1..4, no source bytes, overlapping buffers
+    uint32_t band;                   // destination rows per workgroup
+    unsigned grid_x, grid_y;         // k_crop_frames: (bands, frames), kCropThreads threads
+    size_t dst_bytes;
+};
+
+// out_rows, out_cols, batch >= 1 and within the context's limits (out_rows * out_cols <= 0x1ffffff0, batch <= 65535)
+inline CropPlan plan_crop(int out_rows, int out_cols, int batch, int elem, uintptr_t src, size_t src_bytes, uintptr_t table, uintptr_t dst)
+{
+    CropPlan p = {kInvalid, 0, 0, 0, 0};
+    if (!src || !table || !dst || elem < 1 || elem > 4 || src_bytes == 0 || table % 8 != 0) return p;
+    p.dst_bytes = (size_t)batch * (size_t)out_rows * (size_t)out_cols * (size_t)elem;
+    if (ranges_overlap(dst, p.dst_bytes, src, src_bytes) || ranges_overlap(dst, p.dst_bytes, table, (size_t)32 * (size_t)batch)) return p;
+    p.status = kOk;
+    p.band = kCropBandRows;
+    const auto bands = [&] { return ((uint32_t)out_rows + p.band - 1) / p.band; };
+    while (p.band > (uint32_t)kCropWaves && (size_t)bands() * (size_t)batch < 1024) p.band /= 2;
+    while (bands() > (1u << 20)) p.band *= 2;
+    p.grid_x = bands();
+    p.grid_y = (unsigned)batch;
+    return p;
+}
+
+// ---- dcmt_depth_to_u16_dev ---------------------------------------------------------------------------------------------
+// One kernel over the batch as one flat run of pixels, in segments of kU16SegPx like the BGR ingest; `aligned` (eight pixels per
+// access) is decided once: a segment starts 4 * kU16SegPx and 2 * kU16SegPx bytes behind the last, multiples of 16.
+struct U16Segment {
+    size_t first;
+    uint32_t total;
+    unsigned grid;
+};
+
+struct U16Plan {
+    int status;                      // kInvalid: a null or misaligned pointer, buffers that overlap
+    size_t px, count;
+    bool aligned;                    // k_depth_to_u16<true>: both pointers 16-byte aligned
+    U16Segment segment(size_t i) const
+    {
+        U16Segment s;
+        s.first = i * (size_t)kU16SegPx;
+        s.total = px - s.first < kU16SegPx ? (uint32_t)(px - s.first) : kU16SegPx;
+        s.grid = (unsigned)((s.total + kU16PxPerWg - 1) / kU16PxPerWg);
+        return s;
+    }
+};
+
+// px = batch * rows * cols >= 1
+inline U16Plan plan_depth_to_u16(size_t px, uintptr_t depth, uintptr_t out)
+{
+    U16Plan p = {kInvalid, px, 0, false};
+    if (!depth || !out || px < 1 || depth % 4 != 0 || out % 2 != 0) return p;
+    if (ranges_overlap(depth, 4 * px, out, 2 * px)) return p;
+    p.status = kOk;
+    p.count = (px + kU16SegPx - 1) / kU16SegPx;
+    p.aligned = depth % 16 == 0 && out % 16 == 0;
     return p;
 }
 

@@ -538,6 +538,62 @@ int dcmt_bgr_convert(dcmt_ctx *ctx, const uint8_t *bgr, size_t bgr_row_stride, i
  * Needs no GPU. */
 void dcmt_lab_tables(uint16_t gamma[256], uint16_t cbrt[3072], int32_t coef[9]);
 
+/* ---- the library's two ends: ragged frames in, the uint16 payload out ---------------------------------- */
+
+/* Every *_dev entry point takes [batch][rows][cols] with ONE rows x cols for the call, but the frames of a real batch have several
+ * sizes: the five KITTI recording days deliver 375x1242, 370x1224, 374x1238, 370x1226 and 376x1241, the reference's
+ * DC_stereo_lidar main reads such raw frames (image_02 / image_03 and the full-size velodyne projection) and scores them against
+ * the 352x1216 val_selection_cropped ground truth.  dcmt_crop_frames_dev cuts one window out of each frame of such a ragged
+ * batch into one uniform batch, in ONE launch: frame f of d_dst is rows y0 .. y0 + out_rows - 1 and columns x0 .. x0 + out_cols - 1
+ * of source frame f, byte for byte -- numpy's src[y0:y0 + out_rows, x0:x0 + out_cols].  An element is elem_bytes OPAQUE bytes: grey
+ * 1, uint16 depth or ground truth 2, BGR 3, f32 4.
+ * A source frame lies anywhere inside [d_src, d_src + src_bytes) and may be pitched (a packed ragged buffer, a padded batch,
+ * cv::Mat::step): record f of the device table says where.  d_src + offset and d_dst may have ANY byte alignment; the aligned part of
+ * every destination row is written with 16-byte stores, assembled from naturally aligned 16-byte source loads (a byte shift that is
+ * uniform per row), the row's ends with byte accesses; nothing rests on unaligned hardware accesses.  The same bytes either way.
+ * The table is read by the kernel on the caller's stream, once per wave, with the rules of the calibration tables above: earlier
+ * work on the stream may have written it, it stays unchanged until the kernel has run, it is only read.
+ * BAD RECORDS are tested per frame on the device, in the integer domain, in 64-bit arithmetic that cannot wrap.  A record is good if
+ *     rows >= 1, cols >= 1, x0 >= 0, y0 >= 0, x0 + out_cols <= cols, y0 + out_rows <= rows, row_stride >= cols * elem_bytes,
+ *     offset <= src_bytes, (rows - 1) * row_stride + cols * elem_bytes <= src_bytes - offset
+ * all hold.  A frame whose record fails is all ZERO bytes and no other frame is touched (the convention of the *_calib_dev calls).
+ * For any table contents the call reads no byte outside [d_src, d_src + src_bytes) and writes none outside d_dst's
+ * batch * out_rows * out_cols * elem_bytes bytes.
+ * Never synchronises, never allocates, uses no ctx scratch and carries no state from call to call; may be enqueued in front of or
+ * behind any other *_dev call of the ctx on the same stream.
+ * DCMT_E_INVALID: a null pointer, elem_bytes outside 1..4, out_rows x out_cols or batch beyond the ctx limits (the SOURCE frames may
+ * be larger), src_bytes == 0, a table that is not 8-byte aligned, d_dst overlapping [d_src, d_src + src_bytes) or the table. */
+typedef struct {
+    uint64_t offset;      /* bytes from d_src to element (0,0) of the frame                */
+    uint32_t row_stride;  /* bytes between its rows; >= cols * elem_bytes                  */
+    int32_t  rows, cols;  /* the frame's own size, in elements                             */
+    int32_t  x0, y0;      /* column / row of the window's first element inside the frame   */
+    uint32_t reserved;    /* ignored                                                       */
+} dcmt_crop_src;          /* 32 bytes; table 8-byte aligned                                */
+
+int dcmt_crop_frames_dev(dcmt_ctx *ctx, const void *d_src, size_t src_bytes,
+                         const dcmt_crop_src *d_table /* [batch], device */, int elem_bytes /* 1, 2, 3 or 4 */,
+                         void *d_dst /* [batch][out_rows][out_cols] elements, contiguous */,
+                         int out_rows, int out_cols, int batch, void *stream);
+
+/* A dense f32 plane as KITTI stores depth: uint16, round(metres * 256) -- what the benchmark takes, what the reference's commented
+ * imwrite lines intend (DC_lidar_camera/main_lc.cpp:233-234), and the inverse of the ingest of dcmt_complete_u16_dev and
+ * dcmt_evaluate_u16_dev: a dense batch leaves at 2 B/px.  Per pixel
+ *     t = x * scale, one f32 rounding;  r = t rounded to nearest, ties to even;  out = r saturated to 0..65535
+ * which is cv::Mat::convertTo(CV_16U, scale) on a CV_32F plane.  Negatives and both zeros give 0.  The saturation is taken on t's BIT
+ * PATTERN (t may be +Inf for a finite x, and the library is built with -ffinite-math-only): a set sign bit gives 0, bits at or above
+ * those of 65535.0f, as integers, give 65535.  Every payload v = 0..65535 survives v * (1/256) and back.
+ * DEVICE pointers, stream-ordered: d_depth contiguous f32 [batch][rows][cols], 4-byte aligned; d_out uint16 of the same shape,
+ * 2-byte aligned (both 16-byte aligned: eight pixels per access; the same bytes either way).  Never synchronises, never allocates,
+ * keeps no state; same standing among other *_dev calls as dcmt_crop_frames_dev.
+ * DCMT_E_INVALID: a null pointer, sizes beyond the ctx limits, a scale that is not finite and > 0, d_depth not 4-byte or d_out not
+ * 2-byte aligned, any overlap of the two buffers. */
+int dcmt_depth_to_u16_dev(dcmt_ctx *ctx, const float *d_depth, float scale /* 256 for KITTI */, uint16_t *d_out,
+                          int rows, int cols, int batch, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); the same bytes as the device call. */
+int dcmt_depth_to_u16(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, float scale,
+                      uint16_t *out, size_t out_row_stride, int rows, int cols);
+
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 
 /* Each copies its inputs to the device, runs the device entry point above and copies the result back; device buffers
