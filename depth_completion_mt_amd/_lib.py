@@ -37,6 +37,8 @@ EXPORTS = (
     "dcmt_bgr_convert_dev", "dcmt_bgr_convert", "dcmt_lab_tables",
     "dcmt_project_points_calib_dev", "dcmt_depth_to_cloud_calib_dev", "dcmt_reproject_depth_calib_dev", "dcmt_stereo_refine_calib_dev",
     "dcmt_crop_frames_dev", "dcmt_depth_to_u16_dev", "dcmt_depth_to_u16",
+    "dcmt_project_points_nearest_dev", "dcmt_project_points_nearest_calib_dev", "dcmt_reproject_depth_nearest_dev",
+    "dcmt_reproject_depth_nearest_calib_dev", "dcmt_project_points_nearest", "dcmt_reproject_depth_nearest",
 )
 
 
@@ -102,6 +104,15 @@ class CropSrc(ctypes.Structure):
     """Mirror of dcmt_crop_src (include/dcmt.h): one frame's record of dcmt_crop_frames_dev, 32 bytes."""
     _fields_ = [("offset", ctypes.c_uint64), ("row_stride", ctypes.c_uint32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
                 ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+def nearest_name(twin: str) -> str:
+    """The nearest-wins form of a last-wins scatter entry point: dcmt_project_points[_calib]_dev -> dcmt_project_points_nearest[_calib]_dev,
+    likewise dcmt_reproject_depth*; the host forms gain the suffix."""
+    for stem in ("dcmt_project_points", "dcmt_reproject_depth"):
+        if twin.startswith(stem):
+            return stem + "_nearest" + twin[len(stem):]
+    raise ValueError(twin)
 
 
 def build(force: bool = False) -> str:
@@ -200,6 +211,9 @@ def lib() -> ctypes.CDLL:
         L.dcmt_crop_frames_dev.argtypes = [vp, vp, sz, vp, i, vp, i, i, i, vp]
         L.dcmt_depth_to_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, vp]
         L.dcmt_depth_to_u16.argtypes = [vp, vp, sz, f32, vp, sz, i, i]
+        for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
+                     "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
+            getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes
         L.dcmt_slic_labels_dev.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp]
         L.dcmt_last_fill_iters.argtypes = [vp, ip, i]
         L.dcmt_last_holes_after_extend.argtypes = [vp, ip, i]

@@ -56,6 +56,11 @@ def _check(st: int, what: str) -> None:
         raise DcmtError(st, what)
 
 
+def _rule(twin: str, nearest: bool) -> str:
+    """The entry point of a scatter call under either collision rule: the reference's (the last wins) or nearest wins."""
+    return L.nearest_name(twin) if nearest else twin
+
+
 def _is_dev(t, dtype=None) -> bool:
     """A contiguous CUDA tensor (of that dtype)."""
     return t.is_cuda and t.is_contiguous() and (dtype is None or t.dtype == dtype)
@@ -422,10 +427,13 @@ class Context:
         _check(st, "dcmt_complete_u16_dev")
         return d_dst
 
-    def project_points_dev(self, d_points, d_offsets, T, P, rows: int, cols: int, d_sparse=None, stream: int | None = None):
+    def project_points_dev(self, d_points, d_offsets, T, P, rows: int, cols: int, d_sparse=None, stream: int | None = None,
+                           nearest: bool = False):
         """N2 (SL/main_sl.cpp:478-520): velodyne points -> sparse depth images on the device.  d_points: f32 CUDA tensor
         [n][4] (x, y, z, reflectance); d_offsets: int32 CUDA tensor [batch + 1], frame f owns points
         [offsets[f], offsets[f+1]); T 4x4, P 3x4 row-major.  Returns [batch][rows][cols] f32, 0 = no point.
+        A pixel several points land on keeps the last in file order (the reference's rule) or, with nearest=True, the closest: the
+        smallest p.z (dcmt_project_points_nearest_dev; d_sparse must then overlap none of the inputs).
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
@@ -438,15 +446,17 @@ class Context:
         assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
         t = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
         p = np.ascontiguousarray(P, dtype=np.float32).reshape(12)
-        st = L.lib().dcmt_project_points_dev(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch, t.ctypes.data, p.ctypes.data,
-                                             d_sparse.data_ptr(), rows, cols, _stream(stream, d_points))
-        _check(st, "dcmt_project_points_dev")
+        name = _rule("dcmt_project_points_dev", nearest)
+        st = getattr(L.lib(), name)(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch, t.ctypes.data, p.ctypes.data,
+                                    d_sparse.data_ptr(), rows, cols, _stream(stream, d_points))
+        _check(st, name)
         return d_sparse
 
-    def project_points_calib_dev(self, d_points, d_offsets, d_calib, rows: int, cols: int, d_sparse=None, stream: int | None = None):
+    def project_points_calib_dev(self, d_points, d_offsets, d_calib, rows: int, cols: int, d_sparse=None, stream: int | None = None,
+                                 nearest: bool = False):
         """project_points_dev with the matrices of each sweep's own drive (dcmt_project_points_calib_dev): d_calib is a CUDA tensor
         holding [batch] dcmt_project_calib records (make_project_calib, calib_to_device), read on the stream the call enqueues on.
-        A sweep whose record has a non-finite entry gives a zero plane.
+        A sweep whose record has a non-finite entry gives a zero plane.  nearest: as for project_points_dev.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
@@ -457,10 +467,11 @@ class Context:
             with _on_stream(stream, d_points):
                 d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
         assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
-        st = L.lib().dcmt_project_points_calib_dev(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch,
-                                                   _table_ptr(d_calib, batch, PROJECT_CALIB_DTYPE.itemsize), d_sparse.data_ptr(), rows, cols,
-                                                   _stream(stream, d_points))
-        _check(st, "dcmt_project_points_calib_dev")
+        name = _rule("dcmt_project_points_calib_dev", nearest)
+        st = getattr(L.lib(), name)(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch,
+                                    _table_ptr(d_calib, batch, PROJECT_CALIB_DTYPE.itemsize), d_sparse.data_ptr(), rows, cols,
+                                    _stream(stream, d_points))
+        _check(st, name)
         return d_sparse
 
     def slic_labels_dev(self, d_lab, step: int, nc: int, d_labels=None, return_centers: bool = False, stream: int | None = None):
@@ -793,12 +804,13 @@ class Context:
 
     # ---- a plane seen by one camera -> the plane another camera sees (dcmt_reproject_depth*) ------------------------------
     def reproject_depth_dev(self, d_depth, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None, d_out=None,
-                            stream: int | None = None):
+                            stream: int | None = None, nearest: bool = False):
         """The data part of the reference's unrectify_sol (SL/main_sl.cpp:967-1028) on the device: every source pixel is un-projected
         with the intrinsics, moved by M, projected with K and, where it lands inside [out_rows][out_cols], stores its new depth; the
         last source pixel in row-major order wins a destination pixel, pixels nothing lands on are 0.  d_depth: contiguous f32 CUDA
         tensor [batch][rows][cols] (or [rows][cols]: a batch of one).  Returns d_out, f32 [batch][out_rows][out_cols] (or
-        [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation.
+        [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation.  nearest=True: a z-buffer -- a destination pixel
+        keeps the smallest new depth that lands on it instead of the last (dcmt_reproject_depth_nearest_dev).
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_depth, torch.float32)
@@ -808,15 +820,17 @@ class Context:
                 d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
         assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
         p = params or make_reproject_params()
-        st = L.lib().dcmt_reproject_depth_dev(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
-                                              int(out_cols), _stream(stream, d_depth))
-        _check(st, "dcmt_reproject_depth_dev")
+        name = _rule("dcmt_reproject_depth_dev", nearest)
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
+                                    int(out_cols), _stream(stream, d_depth))
+        _check(st, name)
         return d_out
 
-    def reproject_depth_calib_dev(self, d_depth, out_rows: int, out_cols: int, d_calib, d_out=None, stream: int | None = None):
+    def reproject_depth_calib_dev(self, d_depth, out_rows: int, out_cols: int, d_calib, d_out=None, stream: int | None = None,
+                                  nearest: bool = False):
         """reproject_depth_dev with each frame's own intrinsics, M and K (dcmt_reproject_depth_calib_dev): d_calib is a CUDA tensor
         holding [batch] dcmt_reproject_params records (make_reproject_calib, calib_to_device), read on the stream the call enqueues
-        on.  A frame whose record the uniform call would refuse gives a zero plane.
+        on.  A frame whose record the uniform call would refuse gives a zero plane.  nearest: as for reproject_depth_dev.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_depth, torch.float32)
@@ -825,19 +839,23 @@ class Context:
             with _on_stream(stream, d_depth):
                 d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
         assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
-        st = L.lib().dcmt_reproject_depth_calib_dev(self._h, d_depth.data_ptr(), r, c, b, _table_ptr(d_calib, b, REPROJECT_CALIB_DTYPE.itemsize),
-                                                    d_out.data_ptr(), int(out_rows), int(out_cols), _stream(stream, d_depth))
-        _check(st, "dcmt_reproject_depth_calib_dev")
+        name = _rule("dcmt_reproject_depth_calib_dev", nearest)
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, _table_ptr(d_calib, b, REPROJECT_CALIB_DTYPE.itemsize),
+                                    d_out.data_ptr(), int(out_rows), int(out_cols), _stream(stream, d_depth))
+        _check(st, name)
         return d_out
 
-    def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None) -> np.ndarray:
-        """One frame of host memory (dcmt_reproject_depth, synchronous; any row stride): a new f32 array [out_rows][out_cols]."""
+    def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None,
+                        nearest: bool = False) -> np.ndarray:
+        """One frame of host memory (dcmt_reproject_depth, synchronous; any row stride): a new f32 array [out_rows][out_cols].
+        nearest=True: dcmt_reproject_depth_nearest, the z-buffer of reproject_depth_dev."""
         a = _frame_f32(depth)
         out = np.empty((int(out_rows), int(out_cols)), dtype=np.float32)
         p = params or make_reproject_params()
-        st = L.lib().dcmt_reproject_depth(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], ctypes.byref(p), out.ctypes.data,
-                                          out.strides[0], out.shape[0], out.shape[1])
-        _check(st, "dcmt_reproject_depth")
+        name = _rule("dcmt_reproject_depth", nearest)
+        st = getattr(L.lib(), name)(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], ctypes.byref(p), out.ctypes.data,
+                                    out.strides[0], out.shape[0], out.shape[1])
+        _check(st, name)
         return out
 
     def last_fill_iters(self, n: int):
@@ -965,15 +983,16 @@ def reproject_pc(depth):
     return reproject_pc_colors(depth, None)
 
 
-def unrectify_sol(depth_pre_optim, out_shape, R_rect) -> np.ndarray:
+def unrectify_sol(depth_pre_optim, out_shape, R_rect, nearest: bool = False) -> np.ndarray:
     """The reference's unrectify_sol (SL/main_sl.cpp:967-1028, called at :1228) on one host frame, without its drawing and printing:
     depth_pre_optim forward-warped into the un-rectified camera's frame, a new f32 array of out_shape = (rows, cols) that is 0 where
     nothing lands.  R_rect: the 4x4 matrix the reference passes (R_rect_02).  The matrix that is applied is inverse_f32(R_rect): the
-    inverse computed in f64 and rounded to f32 -- ours, not the bits of Eigen's f32 inverse()."""
+    inverse computed in f64 and rounded to f32 -- ours, not the bits of Eigen's f32 inverse().  nearest=True: the warp as a z-buffer
+    (Context.reproject_depth)."""
     a = np.asarray(depth_pre_optim, dtype=np.float32)
     rows, cols = int(out_shape[0]), int(out_shape[1])
     ctx = _ctx_for(max(a.shape[0], rows), max(a.shape[1], cols), 1)
-    return ctx.reproject_depth(a, rows, cols, make_reproject_params(M=inverse_f32(R_rect)))
+    return ctx.reproject_depth(a, rows, cols, make_reproject_params(M=inverse_f32(R_rect)), nearest=nearest)
 
 
 def write_pcd(path, points) -> None:

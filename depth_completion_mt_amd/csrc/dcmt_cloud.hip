@@ -1,5 +1,6 @@
-// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h, dcmt_kernels_bgr.h and dcmt_kernels_crop.h, a code
+// dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h, dcmt_kernels_nearest.h, dcmt_kernels_bgr.h and dcmt_kernels_crop.h, a code
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
+// the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include "dcmt_kernels_bgr.h"
 #include "dcmt_kernels_cloud.h"
 #include "dcmt_kernels_crop.h"
+#include "dcmt_kernels_nearest.h"
 #include "dcmt_kernels_reproject.h"
 
 using namespace dcmt;
@@ -70,6 +72,26 @@ static int depth_to_cloud(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_
     return DCMT_OK;
 }
 
+// what the uniform reprojection calls refuse in their host record: a non-finite intrinsic or matrix entry (of the rows that are read),
+// fx or fy zero
+static bool reproject_params_ok(const dcmt_reproject_params* params)
+{
+    if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return false;
+    for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return false;         // (M's 4th row and K's 3rd are never read)
+    for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return false;
+    return true;
+}
+
+// ... and the record as the kernels take it
+static ReprojK reproject_k(const dcmt_reproject_params* params)
+{
+    ReprojK k;
+    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
+    std::memcpy(k.M, params->M, sizeof k.M);
+    std::memcpy(k.K, params->K, sizeof k.K);
+    return k;
+}
+
 // k_reproject_scatter, k_reproject_resolve (dcmt_kernels_reproject.h) on the context's winner plane (winner_generation, dcmt_ctx.h);
 // params / d_table as for depth_to_cloud
 static int reproject_depth(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
@@ -79,11 +101,7 @@ static int reproject_depth(dcmt_ctx* ctx, const float* d_depth, int rows, int co
     if (!ctx || !d_depth || !d_out || (!params && !d_table)) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
     if ((uintptr_t)d_depth % 4 != 0 || (uintptr_t)d_out % 4 != 0) return DCMT_E_INVALID;
-    if (params) {
-        if (!intrinsics_ok(params->fx, params->fy, params->cx, params->cy)) return DCMT_E_INVALID;
-        for (int i = 0; i < 12; ++i) if (!finite_bits(params->M[i])) return DCMT_E_INVALID;         // (M's 4th row and K's 3rd are never read)
-        for (int i = 0; i < 6; ++i) if (!finite_bits(params->K[i])) return DCMT_E_INVALID;
-    }
+    if (params && !reproject_params_ok(params)) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols, dst_n = (uint32_t)out_rows * (uint32_t)out_cols;
     const size_t n_px = (size_t)batch * dst_n;
@@ -104,10 +122,7 @@ static int reproject_depth(dcmt_ctx* ctx, const float* d_depth, int rows, int co
         DCMT_HIP(ctx, hipGetLastError());
         return DCMT_OK;
     }
-    ReprojK k;
-    k.fx = params->fx; k.fy = params->fy; k.cx = params->cx; k.cy = params->cy;
-    std::memcpy(k.M, params->M, sizeof k.M);
-    std::memcpy(k.K, params->K, sizeof k.K);
+    const ReprojK k = reproject_k(params);
     hipLaunchKernelGGL(k_reproject_scatter, scatter_grid, dim3(256), 0, st, d_depth, n,
                        (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
     with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
@@ -180,6 +195,100 @@ int dcmt_reproject_depth_calib_dev(dcmt_ctx* ctx, const float* d_depth, int rows
 {
     if (!d_params) return DCMT_E_INVALID;
     return reproject_depth(ctx, d_depth, rows, cols, batch, nullptr, d_params, d_out, out_rows, out_cols, stream);
+}
+
+}  // extern "C"
+
+// The nearest-wins calls (dcmt_kernels_nearest.h): clear the output, scatter keys into it, fix it up in place -- what the plan says
+// (plan_project_nearest / plan_reproject_nearest, which also hold the checks on the buffers).  Nothing of the context is read or
+// written but its device and its limits: no scratch, no state, no allocation.
+template <typename Scatter>
+static int nearest_launch(dcmt_ctx* ctx, const plan::NearestPlan& pl, float* d_out, hipStream_t st, Scatter scatter)
+{
+    unsigned* keys = reinterpret_cast<unsigned*>(d_out);
+    DCMT_HIP(ctx, hipMemsetAsync(d_out, 0, pl.clear_bytes, st));
+    if (pl.scatter_x > 0) scatter(dim3(pl.scatter_x, pl.scatter_y), keys);
+    with_value<4, 2, 1>(pl.vec, [&](auto v) {
+        hipLaunchKernelGGL(k_nearest_fixup<decltype(v)::value>, dim3(pl.fixup_x), dim3(256), 0, st, keys, pl.n_px);
+    });
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// T, P / d_table as for dcmt.hip's project_points
+static int project_points_nearest(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch, const float* T,
+                                  const float* P, const dcmt_project_calib* d_table, float* d_sparse, int rows, int cols, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || (!d_table && (!T || !P))) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const plan::NearestPlan pl = plan::plan_project_nearest(rows, cols, batch, n_points, (uintptr_t)d_points, (uintptr_t)d_offsets, d_table != nullptr,
+                                                            (uintptr_t)d_table, (uintptr_t)d_sparse);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_table)
+        return nearest_launch(ctx, pl, d_sparse, st, [&](dim3 grid, unsigned* keys) {
+            hipLaunchKernelGGL(k_project_nearest_scatter_calib, grid, dim3(256), 0, st, d_points, d_offsets, n_points, batch, d_table, keys, rows, cols);
+        });
+    ProjMats M;
+    std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
+    std::memcpy(M.P, P, sizeof(float) * 12);
+    return nearest_launch(ctx, pl, d_sparse, st, [&](dim3 grid, unsigned* keys) {
+        hipLaunchKernelGGL(k_project_nearest_scatter, grid, dim3(256), 0, st, d_points, d_offsets, n_points, batch, M, keys, rows, cols);
+    });
+}
+
+// params / d_table as for reproject_depth
+static int reproject_depth_nearest(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                                   const dcmt_reproject_params* d_table, float* d_out, int out_rows, int out_cols, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || (!params && !d_table)) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch) || !dims_ok(ctx, out_rows, out_cols, batch)) return DCMT_E_INVALID;
+    if (params && !reproject_params_ok(params)) return DCMT_E_INVALID;
+    const plan::NearestPlan pl = plan::plan_reproject_nearest(rows, cols, out_rows, out_cols, batch, (uintptr_t)d_depth, d_table != nullptr,
+                                                              (uintptr_t)d_table, (uintptr_t)d_out);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t n = (uint32_t)rows * (uint32_t)cols;
+    if (d_table)
+        return nearest_launch(ctx, pl, d_out, st, [&](dim3 grid, unsigned* keys) {
+            hipLaunchKernelGGL(k_reproject_nearest_scatter_calib, grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, d_table, keys, (uint32_t)out_rows, (uint32_t)out_cols);
+        });
+    const ReprojK k = reproject_k(params);
+    return nearest_launch(ctx, pl, d_out, st, [&](dim3 grid, unsigned* keys) {
+        hipLaunchKernelGGL(k_reproject_nearest_scatter, grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, keys, (uint32_t)out_rows, (uint32_t)out_cols);
+    });
+}
+
+extern "C" {
+
+int dcmt_project_points_nearest_dev(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
+                                    const float T[16], const float P[12], float* d_sparse, int rows, int cols, void* stream)
+{
+    if (!T || !P) return DCMT_E_INVALID;
+    return project_points_nearest(ctx, d_points, d_offsets, n_points, batch, T, P, nullptr, d_sparse, rows, cols, stream);
+}
+
+int dcmt_project_points_nearest_calib_dev(dcmt_ctx* ctx, const float* d_points, const int32_t* d_offsets, int n_points, int batch,
+                                          const dcmt_project_calib* d_calib, float* d_sparse, int rows, int cols, void* stream)
+{
+    if (!d_calib) return DCMT_E_INVALID;
+    return project_points_nearest(ctx, d_points, d_offsets, n_points, batch, nullptr, nullptr, d_calib, d_sparse, rows, cols, stream);
+}
+
+int dcmt_reproject_depth_nearest_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* params,
+                                     float* d_out, int out_rows, int out_cols, void* stream)
+{
+    if (!params) return DCMT_E_INVALID;
+    return reproject_depth_nearest(ctx, d_depth, rows, cols, batch, params, nullptr, d_out, out_rows, out_cols, stream);
+}
+
+int dcmt_reproject_depth_nearest_calib_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_reproject_params* d_params,
+                                           float* d_out, int out_rows, int out_cols, void* stream)
+{
+    if (!d_params) return DCMT_E_INVALID;
+    return reproject_depth_nearest(ctx, d_depth, rows, cols, batch, nullptr, d_params, d_out, out_rows, out_cols, stream);
 }
 
 // k_bgr_convert (dcmt_kernels_bgr.h) over the batch as one flat run of pixels, a launch per segment (plan_bgr_convert)

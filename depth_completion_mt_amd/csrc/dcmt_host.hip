@@ -128,8 +128,9 @@ int dcmt_complete_labeled_f32(dcmt_ctx* ctx, const float* src, size_t srs, size_
                      params, true);
 }
 
-int dcmt_project_points(dcmt_ctx* ctx, const float* points, int n_points, const float T[16], const float P[12],
-                        float* sparse, size_t srs, int rows, int cols)
+// dcmt_project_points and dcmt_project_points_nearest: the same staging around dev_call, the *_dev entry point of either rule
+static int project_points_host(decltype(&dcmt_project_points_dev) dev_call, dcmt_ctx* ctx, const float* points, int n_points, const float T[16],
+                               const float P[12], float* sparse, size_t srs, int rows, int cols)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !sparse || !T || !P || n_points < 0 || (n_points > 0 && !points) || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
@@ -137,8 +138,20 @@ int dcmt_project_points(dcmt_ctx* ctx, const float* points, int n_points, const 
     Plane pts(points, sizeof(float) * 4 * (size_t)n_points), off(offsets, sizeof offsets), out(sparse, srs, sizeof(float) * (size_t)cols, rows);
     int rc = stage(ctx, {&pts, &off}, {&out});
     if (rc == DCMT_OK)
-        rc = dcmt_project_points_dev(ctx, (const float*)pts.dev, (const int32_t*)off.dev, n_points, 1, T, P, (float*)out.dev, rows, cols, ctx->own_stream);
+        rc = dev_call(ctx, (const float*)pts.dev, (const int32_t*)off.dev, n_points, 1, T, P, (float*)out.dev, rows, cols, ctx->own_stream);
     return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
+}
+
+int dcmt_project_points(dcmt_ctx* ctx, const float* points, int n_points, const float T[16], const float P[12],
+                        float* sparse, size_t srs, int rows, int cols)
+{
+    return project_points_host(dcmt_project_points_dev, ctx, points, n_points, T, P, sparse, srs, rows, cols);
+}
+
+int dcmt_project_points_nearest(dcmt_ctx* ctx, const float* points, int n_points, const float T[16], const float P[12],
+                                float* sparse, size_t srs, int rows, int cols)
+{
+    return project_points_host(dcmt_project_points_nearest_dev, ctx, points, n_points, T, P, sparse, srs, rows, cols);
 }
 
 int dcmt_slic_labels(dcmt_ctx* ctx, const uint8_t* lab, size_t lrs, int rows, int cols, int step, int nc, int32_t* labels, double* centers)
@@ -219,16 +232,29 @@ int dcmt_gaussian5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size
     return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
 }
 
-int dcmt_reproject_depth(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_reproject_params* params,
-                         float* out, size_t ors, int out_rows, int out_cols)
+// dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
+static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
+                                const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !depth || !out || !params || !dims_ok(ctx, rows, cols, 1) || !dims_ok(ctx, out_rows, out_cols, 1)) return DCMT_E_INVALID;
     Plane in(depth, drs, sizeof(float) * (size_t)cols, rows), warped(out, ors, sizeof(float) * (size_t)out_cols, out_rows);
     int rc = stage(ctx, {&in}, {&warped});
     if (rc == DCMT_OK)
-        rc = dcmt_reproject_depth_dev(ctx, (const float*)in.dev, rows, cols, 1, params, (float*)warped.dev, out_rows, out_cols, ctx->own_stream);
+        rc = dev_call(ctx, (const float*)in.dev, rows, cols, 1, params, (float*)warped.dev, out_rows, out_cols, ctx->own_stream);
     return rc == DCMT_OK ? fetch(ctx, {&warped}) : rc;
+}
+
+int dcmt_reproject_depth(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_reproject_params* params,
+                         float* out, size_t ors, int out_rows, int out_cols)
+{
+    return reproject_depth_host(dcmt_reproject_depth_dev, ctx, depth, drs, rows, cols, params, out, ors, out_rows, out_cols);
+}
+
+int dcmt_reproject_depth_nearest(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_reproject_params* params,
+                                 float* out, size_t ors, int out_rows, int out_cols)
+{
+    return reproject_depth_host(dcmt_reproject_depth_nearest_dev, ctx, depth, drs, rows, cols, params, out, ors, out_rows, out_cols);
 }
 
 int dcmt_bgr_convert(dcmt_ctx* ctx, const uint8_t* bgr, size_t brs, int rows, int cols, uint8_t* lab, size_t lrs, uint8_t* gray, size_t grs)

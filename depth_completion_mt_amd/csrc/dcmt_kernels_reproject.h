@@ -43,13 +43,14 @@ __device__ __forceinline__ float reproject_t2(const ReprojK& k, uint32_t x, uint
 // grid (ceil(n / 1024), frames), 256 threads; n = src_rows * src_cols.  A workgroup owns 1024 consecutive pixels of its frame and
 // thread t takes pixels t, t + 256, t + 512, t + 768 of them: four independent coalesced dword loads in flight per thread (the
 // pattern of k_minmax), and the 64 atomics of a wave instruction start from 64 consecutive source pixels, so under a near-identity
-// warp they hit runs of consecutive dwords of the winner plane.
-__device__ __forceinline__ void reproject_scatter_run(const float* __restrict__ depth, uint32_t n, uint32_t cols, const ReprojK& k, unsigned* __restrict__ winner,
-                                                      uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
+// warp they hit runs of consecutive dwords of the winner plane.  store(pixel, q, t_2): what is done at the landing pixel (its index in
+// the frame's destination plane) -- the tag here, the depth's key in the nearest-wins kernels (dcmt_kernels_nearest.h).
+template <typename Store>
+__device__ __forceinline__ void reproject_scatter_run(const float* __restrict__ depth, uint32_t n, uint32_t cols, const ReprojK& k,
+                                                      uint32_t dst_rows, uint32_t dst_cols, Store store)
 {
     const uint32_t q0 = blockIdx.x * (uint32_t)kReprojectPxPerWg + threadIdx.x;
     const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
-    unsigned* __restrict__ win = winner + (size_t)blockIdx.y * dst_rows * dst_cols;
     float zr[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) zr[r] = q0 + 256u * r < n ? p[q0 + 256u * r] : 0.0f;
@@ -67,15 +68,22 @@ __device__ __forceinline__ void reproject_scatter_run(const float* __restrict__ 
         if (!(uf >= 0.0f && uf < (float)dst_cols && vf >= 0.0f && vf < (float)dst_rows)) continue;   // :1008-1009
         const int u = (int)uf, v = (int)vf;
         if ((unsigned)u < dst_cols && (unsigned)v < dst_rows)
-            atomicMax(&win[(size_t)v * dst_cols + (unsigned)u], gen_tag | q);
+            store((size_t)v * dst_cols + (unsigned)u, q, t2);
     }
+}
+
+// the store of the last-wins kernels: the tag of the call's generation and the source pixel's index
+__device__ __forceinline__ auto reproject_tag_store(unsigned* __restrict__ winner, uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
+{
+    unsigned* __restrict__ win = winner + (size_t)blockIdx.y * dst_rows * dst_cols;
+    return [=](size_t px, uint32_t q, float) { atomicMax(&win[px], gen_tag | q); };
 }
 
 __global__ __launch_bounds__(256)
 void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, unsigned* __restrict__ winner,
                          uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
 {
-    reproject_scatter_run(depth, n, cols, k, winner, dst_rows, dst_cols, gen_tag);
+    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_tag_store(winner, dst_rows, dst_cols, gen_tag));
 }
 
 // the same with the frame's own record: record blockIdx.y of the table (dcmt_calib.h), loaded once per wave through the scalar cache
@@ -87,7 +95,7 @@ void k_reproject_scatter_calib(const float* __restrict__ depth, uint32_t n, uint
 {
     ReprojK k;
     if (!load_reproject_record(table, blockIdx.y, k)) return;
-    reproject_scatter_run(depth, n, cols, k, winner, dst_rows, dst_cols, gen_tag);
+    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_tag_store(winner, dst_rows, dst_cols, gen_tag));
 }
 
 // One thread per PW neighbouring destination pixels of the whole batch (a thread's pixels may lie in two frames): 8- / 16-byte

@@ -23,6 +23,7 @@
 #include "dcmt_calib.h"
 #include "dcmt_gauss.h"
 #include "dcmt_dot_rn.h"
+#include "dcmt_project.h"
 #include <float.h>
 #include <stdint.h>
 #include <type_traits>
@@ -141,29 +142,7 @@ void k_norm_write(const float* __restrict__ src, float* __restrict__ dst, const 
 // thread per pixel recomputes the winning point's depth (the same deterministic arithmetic) or writes 0.
 // Every product and sum is rounded separately (__fmul_rn / __fadd_rn: no FMA contraction), sums left to right.
 // ---------------------------------------------------------------------------------
-struct ProjMats { float T[12]; float P[12]; };   // the three rows of T that are used; P
-
-// dot4_rn: dcmt_dot_rn.h
-
-// returns false if the point is dropped; otherwise pixel (u, v) and its depth
-__device__ __forceinline__ bool project_point(const ProjMats& M, float x, float y, float z, int rows, int cols, int& u, int& v, float& depth)
-{
-    const float tx = dot4_rn(M.T, x, y, z), ty = dot4_rn(M.T + 4, x, y, z), tz = dot4_rn(M.T + 8, x, y, z);
-    if (!(tz > 0.0f)) return false;                                   // SL :487
-    const float px = dot4_rn(M.P, tx, ty, tz), py = dot4_rn(M.P + 4, tx, ty, tz), pz = dot4_rn(M.P + 8, tx, ty, tz);
-    if (pz == 0.0f) return false;                                     // x/0 is +-inf or NaN: fails every bound below
-    const float uf = __fdiv_rn(px, pz), vf = __fdiv_rn(py, pz);       // SL :502-503
-    if (!(uf >= 0.0f && uf < (float)cols && vf >= 0.0f && vf < (float)rows)) return false;   // SL :506-507
-    u = (int)uf; v = (int)vf; depth = pz;
-    return true;
-}
-
-// depth of a point the first pass has already accepted: p.z of project_point, the same operations in the same order
-__device__ __forceinline__ float point_depth(const ProjMats& M, float x, float y, float z)
-{
-    const float tx = dot4_rn(M.T, x, y, z), ty = dot4_rn(M.T + 4, x, y, z), tz = dot4_rn(M.T + 8, x, y, z);
-    return dot4_rn(M.P + 8, tx, ty, tz);
-}
+// ProjMats, project_point, point_depth, project_wg_frame: dcmt_project.h (shared with the nearest-wins kernels of dcmt_kernels_nearest.h)
 
 // The winner plane holds TAGS: (generation << idx_bits) | global point index.  A call only looks at tags of its own generation, so
 // the plane is not cleared between calls (one 0.48 GB memset per 256 sweeps less); the host clears it when the generations run out
@@ -173,19 +152,11 @@ __global__ __launch_bounds__(256)
 void k_project_scatter(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
                        ProjMats M, unsigned* __restrict__ winner, int rows, int cols, unsigned gen_tag)
 {
-    // frame of the workgroup's first point: one search per workgroup (offsets[f] <= i < offsets[f+1]); a thread's own frame is
-    // that one or, where sweeps end inside the workgroup's 256 points, a later one
-    __shared__ int s_lo;
     const int i0 = blockIdx.x * 256;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = batch;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= i0) lo = mid; else hi = mid; }
-        s_lo = lo;
-    }
-    __syncthreads();
+    const int lo_wg = project_wg_frame(offsets, batch, i0);
     const int i = i0 + threadIdx.x;
     if (i >= n_points) return;
-    int lo = s_lo;
+    int lo = lo_wg;
     while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;
     const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
     int u, v; float d;
@@ -223,92 +194,16 @@ void k_project_resolve(const float* __restrict__ pts, ProjMats M, const unsigned
     else sparse[i] = o[0];
 }
 
-// ---- N2 with a table of per-frame matrices (dcmt_project_calib, dcmt_calib.h) -------------------------------------------------
-// A record as ProjMats; `ok`: every one of its 24 entries is finite, tested on the bits
-__device__ __forceinline__ bool load_project_record(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
-{
-    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { const uint32_t b = w[i]; ok = ok && bits_finite32(b); M.T[i] = __uint_as_float(b); }
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { const uint32_t b = w[12 + i]; ok = ok && bits_finite32(b); M.P[i] = __uint_as_float(b); }
-    return ok;
-}
-
-// the same test by 24 lanes of a wave at once, a word each, and one ballot (on the scalar unit it takes some seventy instructions
-// per wave, in a kernel that has about as many per wave in all).  EVERY lane of the wave must be active.
-__device__ __forceinline__ bool project_record_ok_wave(const dcmt_project_calib* __restrict__ table, uint32_t f)
-{
-    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
-    const uint32_t l = threadIdx.x & 63;
-    return __ballot(l < kProjRecWords && !bits_finite32(w[l < kProjRecWords ? l : 0])) == 0;
-}
-
-// the whole record, untested
-__device__ __forceinline__ void load_project_record_untested(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
-{
-    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) M.T[i] = __uint_as_float(w[i]);
-#pragma unroll
-    for (int i = 0; i < 12; ++i) M.P[i] = __uint_as_float(w[12 + i]);
-}
-
-// what point_depth reads (T rows 0..2, P row 2), untested: a pixel with a tag of the call's generation lies in a frame whose record
-// the scatter has accepted
-__device__ __forceinline__ void load_project_depth_record(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
-{
-    const uint32_t* __restrict__ w = reinterpret_cast<const uint32_t*>(table) + kProjRecWords * (size_t)f;
-#pragma unroll
-    for (int i = 0; i < 12; ++i) M.T[i] = __uint_as_float(w[i]);
-#pragma unroll
-    for (int i = 8; i < 12; ++i) M.P[i] = __uint_as_float(w[12 + i]);
-}
-
-// k_project_scatter with the record of each point's OWN frame.  A workgroup's 256 points span a sweep boundary wherever d_offsets
-// says so (empty sweeps included), so the frame is the lane's.  The common case -- a sweep has some 120 000 points -- is a wave
-// whose points all lie in the frame of the workgroup's first point: that frame's record is requested through the scalar cache as
-// soon as the workgroup's search has found it, while the lanes' own offsets loads are in flight (the kernel is a chain of dependent
-// loads), and tested by 24 lanes and one ballot; a second ballot asks whether every active lane of the wave stayed in that frame.
-// If so the wave runs the instruction stream of the uniform kernel on SGPRs.  Otherwise (a wave behind a sweep boundary) each lane
-// gathers and tests its own frame's 96 bytes.  Measured 13 % behind the uniform call, all of it here.  A frame with a bad record scatters nothing: its part of the winner
-// plane keeps no tag of this generation and the resolve writes zeros there.
+// ---- N2 with a table of per-frame matrices (dcmt_project_calib, dcmt_calib.h; the record loaders: dcmt_project.h) --------------
+// k_project_scatter with the record of each point's OWN frame: project_scatter_calib_run (dcmt_project.h) storing the tag.  Measured
+// 13 % behind the uniform call, all of it here.  A frame with a bad record scatters nothing: its part of the
+// winner plane keeps no tag of this generation and the resolve writes zeros there.
 __global__ __launch_bounds__(256)
 void k_project_scatter_calib(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
                              const dcmt_project_calib* __restrict__ table, unsigned* __restrict__ winner, int rows, int cols, unsigned gen_tag)
 {
-    __shared__ int s_lo;
-    const int i0 = blockIdx.x * 256;
-    if (threadIdx.x == 0) {
-        int lo = 0, hi = batch;
-        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (offsets[mid] <= i0) lo = mid; else hi = mid; }
-        s_lo = lo;
-    }
-    __syncthreads();
-    const int lo_wg = __builtin_amdgcn_readfirstlane(s_lo);         // 0 <= lo_wg < batch whatever the offsets hold
-    const bool ok_wg = project_record_ok_wave(table, (uint32_t)lo_wg);            // (every lane is still active here)
-    const int i = i0 + threadIdx.x;
-    if (i >= n_points) return;
-    ProjMats M_wg;
-    load_project_record_untested(table, (uint32_t)lo_wg, M_wg);
-    int lo = lo_wg;
-    while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;            // lo_wg <= lo < batch
-    const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
-    const auto scatter = [&](const ProjMats& M) {
-        int u, v; float d;
-        if (!project_point(M, p.x, p.y, p.z, rows, cols, u, v, d)) return;
-        // project_point's bounds are float compares, which -ffinite-math-only lets the compiler treat as if uf and vf were finite; a
-        // record that is finite but huge makes them NaN.  The address is formed only after the bound has held in the integer domain
-        if ((unsigned)u < (unsigned)cols && (unsigned)v < (unsigned)rows)
-            atomicMax(&winner[((size_t)lo * rows + (unsigned)v) * cols + (unsigned)u], gen_tag | (unsigned)i);
-    };
-    if (__ballot(lo != lo_wg) == 0) {                               // (over the active lanes)
-        if (ok_wg) scatter(M_wg);
-    } else {
-        ProjMats M;
-        if (load_project_record(table, (uint32_t)lo, M)) scatter(M);
-    }
+    project_scatter_calib_run(pts, offsets, n_points, batch, table, rows, cols,
+                              [&](size_t px, unsigned i, float) { atomicMax(&winner[px], gen_tag | i); });
 }
 
 // k_project_resolve with the record of each pixel's OWN frame: the winning point's frame is the frame of the pixel it won.  A

@@ -113,6 +113,60 @@ inline bool calib_table_clear_of(uintptr_t table, size_t rec, int batch, uintptr
     return !ranges_overlap(table, rec * (size_t)batch, out, out_bytes);
 }
 
+// ---- dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev ----------------------------------------------------
+// A clear of the output plane, a scatter of keys into it, one fix-up pass over it in place (dcmt_kernels_nearest.h).  The output is
+// cleared before the inputs are read, so it must be clear of every input, the table included; the checks on the buffers are here,
+// tested without a device.  Nothing of the context is touched: no scratch, no state.
+struct NearestPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, 2^30 points or more, an output that overlaps an input
+    size_t n_px;                     // pixels of the output plane, the whole batch
+    size_t clear_bytes;              // hipMemsetAsync of the output
+    unsigned scatter_x, scatter_y;   // the scatter kernel's grid, 256 threads; scatter_x == 0: nothing to scatter, no launch
+    int vec;                         // k_nearest_fixup<vec>
+    unsigned fixup_x;                // its grid, 256 threads
+};
+
+inline NearestPlan nearest_plane(size_t n_px, uintptr_t out)
+{
+    NearestPlan p = {kOk, n_px, sizeof(float) * n_px, 0, 1, resolve_vec(n_px, out), 0};
+    p.fixup_x = (unsigned)((n_px / (size_t)p.vec + 255) / 256);
+    return p;
+}
+
+// rows, cols, batch >= 1 and within the context's limits; table: 0 for the uniform call (table_call says which call it is)
+inline NearestPlan plan_project_nearest(int rows, int cols, int batch, int n_points, uintptr_t points, uintptr_t offsets, bool table_call,
+                                        uintptr_t table, uintptr_t out)
+{
+    const NearestPlan bad = {kInvalid, 0, 0, 0, 0, 0, 0};
+    if (!offsets || !out || n_points < 0 || n_points >= (1 << 30) || (n_points > 0 && !points)) return bad;
+    if (points % 16 != 0 || offsets % 4 != 0 || out % 4 != 0) return bad;      // whole 16-byte records; integer atomics on the plane
+    if (table_call && !calib_table_aligned(table, 16)) return bad;
+    NearestPlan p = nearest_plane((size_t)batch * (size_t)rows * (size_t)cols, out);
+    if (ranges_overlap(out, p.clear_bytes, points, (size_t)16 * (size_t)n_points) ||
+        ranges_overlap(out, p.clear_bytes, offsets, sizeof(int32_t) * ((size_t)batch + 1)) ||
+        (table_call && !calib_table_clear_of(table, 96, batch, out, p.clear_bytes)))
+        return bad;
+    p.scatter_x = (unsigned)((n_points + 255) / 256);
+    return p;
+}
+
+// both shapes and batch >= 1 and within the context's limits
+inline NearestPlan plan_reproject_nearest(int rows, int cols, int out_rows, int out_cols, int batch, uintptr_t depth, bool table_call,
+                                          uintptr_t table, uintptr_t out)
+{
+    const NearestPlan bad = {kInvalid, 0, 0, 0, 0, 0, 0};
+    if (!depth || !out || depth % 4 != 0 || out % 4 != 0) return bad;
+    if (table_call && !calib_table_aligned(table, 8)) return bad;
+    const size_t n = (size_t)rows * (size_t)cols;
+    NearestPlan p = nearest_plane((size_t)batch * (size_t)out_rows * (size_t)out_cols, out);
+    if (ranges_overlap(out, p.clear_bytes, depth, sizeof(float) * n * (size_t)batch) ||
+        (table_call && !calib_table_clear_of(table, 136, batch, out, p.clear_bytes)))
+        return bad;
+    p.scatter_x = (unsigned)((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg);
+    p.scatter_y = (unsigned)batch;
+    return p;
+}
+
 // ---- dcmt_slic_labels_dev -----------------------------------------------------------------------------------------------
 inline int slic_num_centers(int rows, int cols, int step)
 {

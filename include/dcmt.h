@@ -230,7 +230,7 @@ int dcmt_complete_labeled_f32_dev(dcmt_ctx *ctx, const float *d_src, const int32
  * `P * p.homogeneous()` is not pinned, so against a real build a point whose uf or vf sits
  * within an ulp of an integer may land in the neighbouring pixel.  Stream-ordered, never synchronises; uses ctx
  * scratch (the winner plane, shared with dcmt_reproject_depth_dev: see there), so do not overlap it with another call
- * on the same ctx. */
+ * on the same ctx.  The closest point instead of the last: dcmt_project_points_nearest_dev, below. */
 int dcmt_project_points_dev(dcmt_ctx *ctx, const float *d_points, const int32_t *d_offsets, int n_points,
                             int batch, const float T[16], const float P[12], float *d_sparse,
                             int rows, int cols, void *stream);
@@ -449,7 +449,8 @@ void dcmt_default_reproject_params(dcmt_reproject_params *p);
  * alignment or the run.  d_depth is not written.
  * DCMT_E_INVALID: a null pointer, rows x cols or out_rows x out_cols beyond the ctx limits, batch beyond max_batch, a non-finite
  * intrinsic or matrix entry (of the rows that are read), fx or fy zero, a pointer not 4-byte aligned, d_out overlapping d_depth in
- * any way (the reference's planes are distinct: there is no in-place form). */
+ * any way (the reference's planes are distinct: there is no in-place form).  The warp as a z-buffer (the smallest t_2 instead of the
+ * last): dcmt_reproject_depth_nearest_dev, below. */
 int dcmt_reproject_depth_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch,
                              const dcmt_reproject_params *params, float *d_out, int out_rows, int out_cols, void *stream);
 /* HOST pointers, one frame, synchronous (row strides in BYTES); the same bits as the device call on the frame.  Uses the ctx's
@@ -503,6 +504,53 @@ int dcmt_reproject_depth_calib_dev(dcmt_ctx *ctx, const float *d_depth, int rows
 int dcmt_stereo_refine_calib_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_left, const uint8_t *d_right,
                                  float *d_refined, int rows, int cols, int batch, const dcmt_stereo_params *params,
                                  const dcmt_stereo_calib *d_calib /* [batch], 8-byte aligned */, void *stream);
+
+/* ---- nearest wins: the two scatter calls as a z-buffer ------------------------------------------------ */
+
+/* dcmt_project_points_dev and dcmt_reproject_depth_dev resolve a pixel that several points (source pixels) land on the way the
+ * reference does: the LAST in file (row-major) order stays.  That is an accident of the order -- a KITTI sweep is ordered by laser
+ * and azimuth, not by depth, and the velodyne sits behind and above the cameras, so along every object edge foreground and
+ * background returns share pixels -- and it is not what producers of sparse depth do: the KITTI devkit's depth maps and the
+ * velodyne_raw images dcmt_complete_u16_dev is fed with keep the CLOSEST return, and a forward warp is a z-buffer.  The reference
+ * rule stays the default, bit-exact; each of the four geometric scatter calls (uniform and per-frame-table twins) has a
+ * *_nearest* form with the SAME arguments:
+ *   - a point / source pixel is transformed, accepted and rejected with exactly the statements and roundings of its twin, so the
+ *     set of occupied output pixels is identical;
+ *   - among all values the twin's rule would have stored into one output pixel (p.z for the projection -- P's third row carries a
+ *     translation, so it need not be positive --, t_2 > 0 for the reprojection) the output holds the SMALLEST, in the usual total
+ *     order on finite f32 with -0 below +0.  Equal values tie harmlessly: the output is the value itself;
+ *   - everything else is the twin's: the output is written completely, 0 where nothing lands; a bad record of a table empties that
+ *     frame only; memory-safe on any table contents; frame f of a table call is, bit for bit, the uniform call on frame f alone with
+ *     record f; finite inputs only.
+ * Mechanism (csrc/dcmt_kernels_nearest.h): hipMemsetAsync zeroes the output; a scatter kernel does one integer atomicMax per
+ * landing point of an order-preserving key of the value INTO THE OUTPUT PLANE (key = ~ord, ord the sign-flip map of f32 bits to
+ * unsigned order; never 0 for a finite value, so 0 is "nothing landed"); one pass over the plane, in place, turns keys back into
+ * values.  No float atomics: the result is bit-reproducible and does not depend on arrival order, the batch size, a frame's position
+ * in the batch, alignment or the run.
+ * The nearest calls touch NONE of the state a ctx carries from call to call -- not the winner plane, not a generation, not an
+ * allocation -- so they never allocate and never synchronise, and they may be mixed with the last-wins calls (and every other call)
+ * on one ctx and stream in any order.
+ * Because the output is cleared BEFORE the inputs are read, it must not overlap any input: DCMT_E_INVALID where d_sparse overlaps
+ * d_points, d_offsets or the table, or d_out overlaps d_depth or the table.  Otherwise the argument checks are the twins'; in
+ * addition d_sparse / d_out and d_offsets must be 4-byte aligned (the plane takes integer atomics), and n_points stays below 2^30.
+ * 16-byte aligned outputs with batch * rows * cols a multiple of 4 take the widest accesses in the last pass. */
+int dcmt_project_points_nearest_dev(dcmt_ctx *ctx, const float *d_points, const int32_t *d_offsets, int n_points,
+                                    int batch, const float T[16], const float P[12], float *d_sparse,
+                                    int rows, int cols, void *stream);
+int dcmt_project_points_nearest_calib_dev(dcmt_ctx *ctx, const float *d_points, const int32_t *d_offsets, int n_points, int batch,
+                                          const dcmt_project_calib *d_calib /* [batch], 16-byte aligned */,
+                                          float *d_sparse, int rows, int cols, void *stream);
+int dcmt_reproject_depth_nearest_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch,
+                                     const dcmt_reproject_params *params, float *d_out, int out_rows, int out_cols, void *stream);
+int dcmt_reproject_depth_nearest_calib_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch,
+                                           const dcmt_reproject_params *d_params /* [batch], 8-byte aligned */,
+                                           float *d_out, int out_rows, int out_cols, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES), staged like their last-wins twins; the same bits as the device
+ * call on the frame. */
+int dcmt_project_points_nearest(dcmt_ctx *ctx, const float *points, int n_points, const float T[16], const float P[12],
+                                float *sparse, size_t sparse_row_stride, int rows, int cols);
+int dcmt_reproject_depth_nearest(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, int rows, int cols,
+                                 const dcmt_reproject_params *params, float *out, size_t out_row_stride, int out_rows, int out_cols);
 
 /* ---- producer of the image inputs: camera BGR bytes -> 8-bit Lab and grey planes ----------------------- */
 

@@ -263,18 +263,30 @@ inline void depth_to_cloud(const cv::Mat& depth, const cv::Mat& bgr, std::vector
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
 // reference passes (it calls Eigen's R_rect.inverse() inside its loop; that f32 inverse is not reproduced here, pass your own).
 // Intrinsics and camera matrix: the reference's (:969-976).
-inline void unrectify_sol(const cv::Mat& depth, cv::Mat& depth_unrect, const float Minv[16])
+inline void unrectify_sol_with(decltype(&dcmt_reproject_depth) call, const char* what, const cv::Mat& depth, cv::Mat& depth_unrect, const float Minv[16])
 {
     check_input(depth);
     if (depth_unrect.type() != CV_32FC1 || depth_unrect.rows < 1 || depth_unrect.cols < 1)
-        throw std::runtime_error("unrectify_sol: the destination must be a pre-sized CV_32FC1 image");
+        throw std::runtime_error(std::string(what) + ": the destination must be a pre-sized CV_32FC1 image");
     const int rows = depth.rows, cols = depth.cols, orows = depth_unrect.rows, ocols = depth_unrect.cols;
     dcmt_reproject_params p;
     dcmt_default_reproject_params(&p);
     for (int i = 0; i < 16; ++i) p.M[i] = Minv[i];
-    raise(dcmt_reproject_depth(thread_ctx().get(rows > orows ? rows : orows, cols > ocols ? cols : ocols), depth.ptr<float>(), depth.step[0],
-                               rows, cols, &p, depth_unrect.ptr<float>(), depth_unrect.step[0], orows, ocols),
-          "unrectify_sol");
+    raise(call(thread_ctx().get(rows > orows ? rows : orows, cols > ocols ? cols : ocols), depth.ptr<float>(), depth.step[0],
+               rows, cols, &p, depth_unrect.ptr<float>(), depth_unrect.step[0], orows, ocols),
+          what);
+}
+
+inline void unrectify_sol(const cv::Mat& depth, cv::Mat& depth_unrect, const float Minv[16])
+{
+    unrectify_sol_with(dcmt_reproject_depth, "unrectify_sol", depth, depth_unrect, Minv);
+}
+
+// The same warp as a z-buffer: a destination pixel several source pixels land on keeps the smallest new depth instead of the last in
+// row-major order (dcmt_reproject_depth_nearest); the occupied pixels are the same.
+inline void unrectify_sol_nearest(const cv::Mat& depth, cv::Mat& depth_unrect, const float Minv[16])
+{
+    unrectify_sol_with(dcmt_reproject_depth_nearest, "unrectify_sol_nearest", depth, depth_unrect, Minv);
 }
 
 }  // namespace dcmt_shim
