@@ -13,7 +13,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libdcmt_hip.so")
 
 OK, E_INVALID, E_UNSUPPORTED, E_NOMEM, E_HIP, E_NOT_CONVERGED, E_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6
-BLUR_NONE, BLUR_GAUSSIAN, BLUR_BILATERAL = 0, 1, 2
+BLUR_NONE, BLUR_GAUSSIAN, BLUR_BILATERAL, BLUR_BILATERAL_CLONE = 0, 1, 2, 3
 STAGE_NORMALIZE = 1
 STAGE_INVERT, STAGE_DILATE_K, STAGE_CLOSE5, STAGE_FILL7, STAGE_EXTEND = 2, 3, 4, 5, 6
 FLAG_FORCE_STAGED = 1
@@ -39,6 +39,7 @@ EXPORTS = (
     "dcmt_crop_frames_dev", "dcmt_depth_to_u16_dev", "dcmt_depth_to_u16",
     "dcmt_project_points_nearest_dev", "dcmt_project_points_nearest_calib_dev", "dcmt_reproject_depth_nearest_dev",
     "dcmt_reproject_depth_nearest_calib_dev", "dcmt_project_points_nearest", "dcmt_reproject_depth_nearest",
+    "dcmt_bilateral5_dev", "dcmt_bilateral5",
 )
 
 
@@ -196,6 +197,8 @@ def lib() -> ctypes.CDLL:
         L.dcmt_depth_to_cloud.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i64, ctypes.POINTER(i64)]
         L.dcmt_gaussian5_dev.argtypes = [vp, vp, vp, i, i, i, vp]
         L.dcmt_gaussian5.argtypes = [vp, vp, sz, vp, sz, i, i]
+        L.dcmt_bilateral5_dev.argtypes = [vp, vp, vp, i, i, i, f32, f32, vp]
+        L.dcmt_bilateral5.argtypes = [vp, vp, sz, vp, sz, i, i, f32, f32]
         L.dcmt_default_reproject_params.argtypes = [vp]
         L.dcmt_default_reproject_params.restype = None
         L.dcmt_reproject_depth_dev.argtypes = [vp, vp, i, i, i, vp, vp, i, i, vp]

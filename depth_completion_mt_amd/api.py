@@ -114,8 +114,9 @@ def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int =
         arr = np.asarray(k0, dtype=np.uint8).reshape(25)
         for i in range(25):
             p.k0[i] = int(arr[i])
-    # the reference compares strings: "bilateral" / "gaussian" / anything else = no blur
-    p.blur = {"gaussian": L.BLUR_GAUSSIAN, "bilateral": L.BLUR_BILATERAL}.get(blur_type, L.BLUR_NONE)
+    # the reference compares strings: "bilateral" / "gaussian" / anything else = no blur; "bilateral_clone" is this project's opt-in:
+    # what the reference's in-place bilateral call computes when it is given a copy (DCMT_BLUR_BILATERAL_CLONE)
+    p.blur = {"gaussian": L.BLUR_GAUSSIAN, "bilateral": L.BLUR_BILATERAL, "bilateral_clone": L.BLUR_BILATERAL_CLONE}.get(blur_type, L.BLUR_NONE)
     p.stop_after = int(stop_after)
     p.max_fill_iters = int(max_fill_iters)
     p.spec_fill_iters = int(spec_fill_iters)
@@ -802,6 +803,31 @@ class Context:
         _check(st, "dcmt_gaussian5")
         return out
 
+    def bilateral5_dev(self, d_src, d_dst=None, sigma_color: float = 1.5, sigma_space: float = 2.0, stream: int | None = None):
+        """cv::bilateralFilter(src, dst, 5, sigma_color, sigma_space) on the device as include/dcmt.h states it (dcmt_bilateral5_dev):
+        the edge-preserving alternative to gaussian5_dev, and the filter of blur_type="bilateral_clone".  Arguments, in-place use
+        and the return value as gaussian5_dev."""
+        import torch
+        assert _is_dev(d_src, torch.float32)
+        b, r, c = _brc(d_src)
+        if d_dst is None:
+            with _on_stream(stream, d_src):
+                d_dst = torch.full_like(d_src, float("nan"))
+        assert _is_dev(d_dst, torch.float32) and d_dst.numel() == d_src.numel()
+        st = L.lib().dcmt_bilateral5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, float(sigma_color), float(sigma_space),
+                                         _stream(stream, d_src))
+        _check(st, "dcmt_bilateral5_dev")
+        return d_dst
+
+    def bilateral5(self, frame: np.ndarray, sigma_color: float = 1.5, sigma_space: float = 2.0) -> np.ndarray:
+        """One frame of host memory (dcmt_bilateral5, synchronous; any row stride): a new f32 array."""
+        a = _frame_f32(frame)
+        out = np.empty(a.shape, dtype=np.float32)
+        st = L.lib().dcmt_bilateral5(self._h, a.ctypes.data, a.strides[0], out.ctypes.data, out.strides[0], a.shape[0], a.shape[1],
+                                     float(sigma_color), float(sigma_space))
+        _check(st, "dcmt_bilateral5")
+        return out
+
     # ---- a plane seen by one camera -> the plane another camera sees (dcmt_reproject_depth*) ------------------------------
     def reproject_depth_dev(self, d_depth, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None, d_out=None,
                             stream: int | None = None, nearest: bool = False):
@@ -962,6 +988,13 @@ def depth_to_u16(depth, scale: float = 256.0):
         return _ctx_for(depth.shape[-2], depth.shape[-1], b, depth.device.index or 0).depth_to_u16_dev(depth, scale)
     a = np.asarray(depth, dtype=np.float32)
     return _ctx_for(a.shape[0], a.shape[1], 1).depth_to_u16(a, scale)
+
+
+def bilateral_filter5(frame, sigma_color: float = 1.5, sigma_space: float = 2.0) -> np.ndarray:
+    """cv::bilateralFilter(frame, out, 5, sigma_color, sigma_space) on one host frame, as include/dcmt.h states it
+    (Context.bilateral5): a new f32 array.  The defaults are the cascade's literals (LO/img_completion.cpp:174)."""
+    a = np.asarray(frame, dtype=np.float32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).bilateral5(a, sigma_color, sigma_space)
 
 
 def reproject_pc_colors(depth, bgr):

@@ -52,7 +52,8 @@ static_assert(plan::pre_s_vw(K0_AS_COMPILED, false) == PreS<K0_AS_COMPILED, fals
 static_assert(plan::kFpQVW == FpQ::VW && plan::kPostSVW == PostS::VW && plan::kFillSVW == FillS::VW, "FpQ / PostS / FillS::VW");
 static_assert(plan::kMaxBands == kMaxBands && plan::kLabelGroupMax == kLabelGroupMax, "kMaxBands, kLabelGroupMax");
 static_assert(plan::kStageNormalize == DCMT_STAGE_NORMALIZE && plan::kStageClose5 == DCMT_STAGE_CLOSE5 && plan::kStageFill7 == DCMT_STAGE_FILL7 &&
-              plan::kStageExtend == DCMT_STAGE_EXTEND && plan::kStageFinal == DCMT_STAGE_FINAL, "dcmt_stage");
+              plan::kStageExtend == DCMT_STAGE_EXTEND && plan::kStageMedian5 == DCMT_STAGE_MEDIAN5 && plan::kStageBlur == DCMT_STAGE_BLUR &&
+              plan::kStageFinal == DCMT_STAGE_FINAL, "dcmt_stage");
 static_assert(plan::kFlagForceStaged == DCMT_FLAG_FORCE_STAGED && plan::kFlagForceFused == DCMT_FLAG_FORCE_FUSED &&
               plan::kFlagNormalize == DCMT_FLAG_NORMALIZE, "DCMT_FLAG_*");
 static_assert(plan::q16_params_ok(100.0f, 0.1f) && Q16::params_ok(100.0f, 0.1f) && !plan::q16_params_ok(80.0f, 0.1f) && !Q16::params_ok(80.0f, 0.1f) &&
@@ -316,6 +317,11 @@ int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, cons
 // the scratch plane (or dst) a plan points the output of the kernel that reads the frames at
 float* out_plane(const dcmt_ctx* ctx, plan::Out o, float* dst) { return o == plan::Out::DST ? dst : o == plan::Out::X5 ? ctx->x5 : ctx->pp[0]; }
 
+int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, int blur, hipStream_t st, bool sync_loop);
+
+// the cascade's literals of the bilateral finish (img_completion.cpp:174); fixed: dcmt_params has no room for them
+constexpr float kBilateralSigmaColor = 1.5f, kBilateralSigmaSpace = 2.0f;
+
 // Plans the call (dcmt_plan.h), allocates what the plan names, then enqueues the cascade on `st`.  sync_loop: run the hole-closure
 // loop exactly as the reference would, reading the hole counters back between applications (host entry points); otherwise enqueue
 // p->spec_fill_iters applications speculatively.
@@ -335,10 +341,32 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     c.max_depth = p->max_depth; c.valid_thresh = p->valid_thresh;
     c.k0kind = k0_preset(kb);
     c.gaussian = blur == DCMT_BLUR_GAUSSIAN;
+    c.bilateral = blur == DCMT_BLUR_BILATERAL_CLONE;
     c.max_fill_iters = p->max_fill_iters; c.spec_fill_iters = p->spec_fill_iters; c.stop_after = stop; c.flags = p->flags;
     c.sync_loop = sync_loop;
     c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && q16_allowed_now(ctx);
     const plan::Plan pl = plan::plan_call(ctx->knobs, c);
+    if (!pl.bilateral) return run_plan(ctx, pl, fr, p, blur, st, sync_loop);
+
+    // The bilateral finish: the plan's chain up to the median into the context's median plane (allocated by the first such call,
+    // before anything is enqueued), then k_bilateral5 from there into dst.  A loop that hit max_fill_iters is filtered like any other.
+    DCMT_TRY(ctx->median.reserve(ctx, ctx->frame_elems * (size_t)ctx->max_batch));
+    Frames fm = fr;
+    fm.dst = ctx->median;
+    dcmt_params q = *p;
+    q.stop_after = DCMT_STAGE_MEDIAN5;
+    const int rc = run_plan(ctx, pl, fm, &q, DCMT_BLUR_NONE, st, sync_loop);
+    if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
+    DCMT_TRY(bilateral5_enqueue(ctx, ctx->median, fr.dst, rows, cols, batch, kBilateralSigmaColor, kBilateralSigmaSpace, pl.bilateral_invert,
+                                p->max_depth, p->valid_thresh, st));
+    return rc;
+}
+
+// The rest of run_chain: allocates what the plan names, then enqueues its kernels.  blur: the effective one.
+int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, int blur, hipStream_t st, bool sync_loop)
+{
+    const int rows = fr.rows, cols = fr.cols, batch = fr.batch, stop = p->stop_after;
+    const uint32_t kb = k0_bits(p->k0);
 
     // Scratch only one of the paths uses is allocated by the first call whose plan names it (never again afterwards) -- before anything
     // of the call is enqueued: an allocation synchronises, and one that fails must not leave half a call in the stream.  The 16-bit
@@ -514,7 +542,7 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
     if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
-    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN) return DCMT_E_INVALID;
+    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN && p->blur != DCMT_BLUR_BILATERAL_CLONE) return DCMT_E_INVALID;
     if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;
     if (p->spec_fill_iters < 0 || p->spec_fill_iters > kMaxIters) return DCMT_E_INVALID;
     const bool norm = (p->flags & DCMT_FLAG_NORMALIZE) != 0;

@@ -1,7 +1,7 @@
 // dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h, dcmt_kernels_nearest.h, dcmt_kernels_bgr.h and dcmt_kernels_crop.h, a code
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
-// dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -13,6 +13,7 @@
 #include "dcmt_kernels_crop.h"
 #include "dcmt_kernels_nearest.h"
 #include "dcmt_kernels_reproject.h"
+#include "dcmt_kernels_bilateral.h"
 
 using namespace dcmt;
 
@@ -359,6 +360,65 @@ void dcmt_lab_tables(uint16_t gamma[256], uint16_t cbrt[3072], int32_t coef[9])
     if (gamma) std::memcpy(gamma, t.gamma, sizeof t.gamma);
     if (cbrt) std::memcpy(cbrt, t.cbrt, sizeof t.cbrt);
     if (coef) std::memcpy(coef, c, sizeof c);
+}
+
+}  // extern "C"
+
+// ---- the bilateral finish (dcmt_kernels_bilateral.h) ---------------------------------------------------------------------------
+namespace dcmt {
+
+// the kernel's constants of (sigma_color, sigma_space); false for a sigma that is not finite and positive, or whose square leaves
+// no finite f32 factor gc
+static bool bilateral_k(float sigma_color, float sigma_space, BilK* k)
+{
+    if (!finite_bits(sigma_color) || !finite_bits(sigma_space) || !(sigma_color > 0.0f) || !(sigma_space > 0.0f)) return false;
+    const float sc2 = sigma_color * sigma_color;
+    if (!finite_bits(sc2) || !(sc2 > 0.0f)) return false;
+    k->gc = -0.5f / sc2;
+    if (!finite_bits(k->gc)) return false;
+    const double gs = -0.5 / ((double)sigma_space * (double)sigma_space);
+    k->ws1 = (float)std::exp(gs);
+    k->ws2 = (float)std::exp(2.0 * gs);
+    k->ws4 = (float)std::exp(4.0 * gs);
+    return true;
+}
+
+// (dcmt_ctx.h)
+int bilateral5_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float sigma_color, float sigma_space,
+                       bool invert, float max_depth, float thr, hipStream_t st)
+{
+    BilK k;
+    if (!bilateral_k(sigma_color, sigma_space, &k)) return DCMT_E_INVALID;
+    const plan::GaussPlan pl = plan::plan_bilateral5(rows, cols, batch);
+    const dim3 grid(pl.grid_x, batch);
+    if (invert)
+        hipLaunchKernelGGL(k_bilateral5<true>, grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, k, max_depth, thr);
+    else
+        hipLaunchKernelGGL(k_bilateral5<false>, grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, k, max_depth, thr);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+}  // namespace dcmt
+
+extern "C" {
+
+// as dcmt_gaussian5_dev: an in-place call writes to pp[0] and copies the result over the source
+int dcmt_bilateral5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float sigma_color, float sigma_space,
+                        void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
+    const bool in_place = d_dst == d_src;
+    if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
+    float* out = in_place ? ctx->pp[0] : d_dst;
+    DCMT_TRY(bilateral5_enqueue(ctx, d_src, out, rows, cols, batch, sigma_color, sigma_space, false, 0.0f, 0.0f, st));
+    if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
 }
 
 }  // extern "C"

@@ -99,6 +99,8 @@ struct dcmt_ctx {
     Dev<double> eval_slab;            // dcmt_evaluate*_dev: per (frame, chunk) partial sums, sized for max_batch frames of max_rows x max_cols,
                                       // allocated by the first evaluate call
     Dev<float> color_slab;            // dcmt_colorize_dev: per (frame, chunk) min and max, sized for max_batch frames of max_rows x max_cols
+    Dev<float> median;                // [max_batch][rows][cols] the cascade's bilateral finish: the median plane k_bilateral5 reads (pp[0] and pp[1] both
+                                      // hold frames' loop results then); the first call with DCMT_BLUR_BILATERAL_CLONE
     Dev<uint32_t> cloud_slab;         // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
                                       // color_slab, kCloudWaves entries per chunk
 };
@@ -226,5 +228,11 @@ struct Frames {
 // p->max_fill_iters (dst is written all the same).  Both defined in dcmt.hip.
 DCMT_LOCAL int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, int cols, int batch, const dcmt_params* p);
 DCMT_LOCAL int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_gaussian, hipStream_t st);
+
+// k_bilateral5 (dcmt_kernels_bilateral.h) enqueued on `st`, for dcmt_bilateral5_dev and the cascade's bilateral finish: d_src and
+// d_dst must not overlap; invert: the cascade's final invert with (max_depth, thr) in the store.  DCMT_E_INVALID for a sigma that is
+// not finite and positive.  Defined in dcmt_cloud.hip, where the kernel is compiled.
+DCMT_LOCAL int bilateral5_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float sigma_color,
+                                  float sigma_space, bool invert, float max_depth, float thr, hipStream_t st);
 
 }  // namespace dcmt

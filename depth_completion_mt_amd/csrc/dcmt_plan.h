@@ -83,7 +83,7 @@ constexpr int kFpSOneBandWaves = 2048, kFpSBandWaves = 3072;   // k_fp_s: one ba
 // Q16::params_ok: the 16-bit codes are built on the reference's constants
 constexpr bool q16_params_ok(float max_depth, float thr) { return max_depth == 100.0f && thr == 0.1f; }
 // dcmt.h: dcmt_stage and the DCMT_FLAG_* bits
-constexpr int kStageNormalize = 1, kStageClose5 = 4, kStageFill7 = 5, kStageExtend = 6, kStageFinal = 11;
+constexpr int kStageNormalize = 1, kStageClose5 = 4, kStageFill7 = 5, kStageExtend = 6, kStageMedian5 = 9, kStageBlur = 10, kStageFinal = 11;
 constexpr int kFlagForceStaged = 1, kFlagForceFused = 2, kFlagNormalize = 4;
 // dcmt_last_path of a call whose result went to scratch first and was then copied to its overlapping dst
 constexpr const char* kPathCopy = " + copy to dst";
@@ -101,6 +101,7 @@ struct Call {
     float max_depth = 100.0f, valid_thresh = 0.1f;
     int k0kind = kK0AsCompiled;
     bool gaussian = true;
+    bool bilateral = false;                  // DCMT_BLUR_BILATERAL_CLONE (never with gaussian)
     int max_fill_iters = 64, spec_fill_iters = 1, stop_after = kStageFinal, flags = 0;
     bool sync_loop = false;                  // host entry points: the hole counters are read back between applications
     bool q16_allowed = false;                // a 16-bit attempt is allowed now (the context's skip state, dcmt.hip: q16_allowed_now)
@@ -133,6 +134,9 @@ struct Plan {
     bool fuse_fp = false;            // H7..H11 in k_fp_* (the whole chain only)
     bool filled = false, tail = false, fp_s_launch = false;
     int n_redo = 0;
+    // the bilateral finish: everything above is the plan of the same call with stop_after = MEDIAN5 and the context's median plane as
+    // its dst; k_bilateral5 then reads that plane and writes dst, with the final invert for stop_after = FINAL
+    bool bilateral = false, bilateral_invert = false;
     char path[160] = "";             // dcmt_last_path
 };
 
@@ -171,6 +175,20 @@ inline Route route_of(const Knobs& k, const Call& c)
 // Context scratch (X5 / X6, pp[0], pp[1]) is 256-byte aligned; address 0 below stands for it.
 inline Plan plan_call(const Knobs& k, const Call& c)
 {
+    if (c.bilateral && c.stop_after >= kStageBlur) {
+        // The chain as for stop_after = MEDIAN5 on whatever route that takes, into the context's median plane (neither pp[0] nor
+        // pp[1] is free: a frame's loop result lies in either, by the number of applications it needed), then one more kernel, the
+        // call's only writer of dst -- behind every kernel that reads the frames, so an overlapping dst needs no copy.
+        Call m = c;
+        m.bilateral = false; m.gaussian = false;
+        m.stop_after = kStageMedian5;
+        m.dst = 0;
+        Plan p = plan_call(k, m);
+        p.bilateral = true;
+        p.bilateral_invert = c.stop_after == kStageFinal;
+        path_append(p.path, " + bilateral5");
+        return p;
+    }
     Plan p;
     const int stop = c.stop_after, rows = c.rows, cols = c.cols, batch = c.batch;
     const size_t n_px = (size_t)batch * rows * cols;

@@ -246,6 +246,19 @@ inline GaussPlan plan_gauss5(int rows, int cols, int batch)
     return p;
 }
 
+// ---- dcmt_bilateral5_dev, and the cascade's bilateral finish ------------------------------------------------------------------
+// k_bilateral5 takes k_gauss5's shape, and its plan the same short-band rule
+inline GaussPlan plan_bilateral5(int rows, int cols, int batch)
+{
+    GaussPlan p;
+    p.strips = (cols + kBilCols - 1) / kBilCols;
+    p.band_rows = kBilRows;
+    while (p.band_rows > 8 && (size_t)p.strips * ((rows + p.band_rows - 1) / p.band_rows) * batch < 2048) p.band_rows /= 2;
+    p.bands = (rows + p.band_rows - 1) / p.band_rows;
+    p.grid_x = (unsigned)(((size_t)p.strips * p.bands + 3) / 4);
+    return p;
+}
+
 // ---- dcmt_bgr_convert_dev ----------------------------------------------------------------------------------------------
 // One kernel over the batch as ONE flat run of pixels (dcmt_kernels_bgr.h): nothing in it depends on where a frame ends.  Runs of
 // more than kBgrSegPx pixels go in segments of kBgrSegPx, a launch each; kBgrSegPx is a multiple of 4, so every segment's three

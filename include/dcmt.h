@@ -83,7 +83,15 @@ typedef enum {
 typedef enum {
     DCMT_BLUR_NONE      = 0, /* any blur_type string other than the two below */
     DCMT_BLUR_GAUSSIAN  = 1, /* "gaussian": GaussianBlur 5x5 sigma 0 + masked select (img_completion.cpp:176-189) */
-    DCMT_BLUR_BILATERAL = 2  /* "bilateral": rejected with DCMT_E_UNSUPPORTED */
+    DCMT_BLUR_BILATERAL = 2, /* "bilateral": rejected with DCMT_E_UNSUPPORTED */
+    /* "bilateral_clone": what img_completion.cpp:174 computes when it is given a copy (an opt-in of this project; the reference's own
+     * in-place call throws): after the 5x5 median, cv::bilateralFilter(clone, dense, 5, 1.5, 2.0) over the WHOLE plane (:174 has no
+     * masked select, unlike the Gaussian's :184), as dcmt_bilateral5_dev states it, then the unchanged final invert.  With
+     * stop_after >= DCMT_STAGE_BLUR the chain runs as for stop_after = DCMT_STAGE_MEDIAN5 on every route (the median plane goes to a
+     * context plane that the first such call allocates, never to d_dst), then one more kernel writes d_dst, as the call's only and
+     * last writer: every promise of the "In place" paragraph above holds.  dcmt_last_path ends in "+ bilateral5".  stop_after <=
+     * DCMT_STAGE_MEDIAN5 ignores the blur, as with every value.  The labeled entry points force the Gaussian whatever this is. */
+    DCMT_BLUR_BILATERAL_CLONE = 3
 } dcmt_blur;
 
 /* Stages of the cascade, for `stop_after` (parity probes; 11 = the whole chain). */
@@ -98,7 +106,7 @@ typedef enum {
     DCMT_STAGE_FILL31   = 7,  /* :131-144 31x31 large-hole fill */
     DCMT_STAGE_FILLLOOP = 8,  /* :146-166 repeat until no holes */
     DCMT_STAGE_MEDIAN5  = 9,  /* :170     5x5 median */
-    DCMT_STAGE_BLUR     = 10, /* :172-189 blur + masked select */
+    DCMT_STAGE_BLUR     = 10, /* :172-189 blur + masked select (DCMT_BLUR_BILATERAL_CLONE: the filter, no select) */
     DCMT_STAGE_FINAL    = 11  /* :191-202 invert back to metres */
 } dcmt_stage;
 
@@ -407,6 +415,24 @@ int dcmt_depth_to_cloud(dcmt_ctx *ctx, const float *depth, size_t depth_row_stri
 int dcmt_gaussian5_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, void *stream);
 /* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
 int dcmt_gaussian5(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols);
+
+/* cv::bilateralFilter(src, dst, 5, sigma_color, sigma_space) for CV_32FC1 with BORDER_DEFAULT, as this project states it (OpenCV is
+ * never executed, and its 4096-bin interpolated exp table is not restated: DESIGN.md section 19): the edge-preserving alternative to
+ * dcmt_gaussian5_dev in front of the point cloud, and the kernel behind DCMT_BLUR_BILATERAL_CLONE.
+ *   taps     the 13 offsets (dy, dx) with dy*dy + dx*dx <= 4, BORDER_REFLECT_101 on both axes (also for 1 or 2 rows or columns)
+ *   weights  ws(dy, dx) = (float)exp(-(dy*dy + dx*dx) / (2 sigma_space^2)), evaluated in double on the host;
+ *            wc = exp(gc * d * d) with d = v(tap) - v(centre) and gc = -0.5f / sigma_color^2, in f32 (the device's exp)
+ *   output   y = c + (sum ws wc d) / (sum ws wc), every operation in f32 and rounded once, both sums in tap order (row-major);
+ *            the centre tap adds d = 0, w = 1.  A constant plane comes back bit for bit.
+ * A pixel's bits do not depend on batch, its frame's position in the batch or the launch geometry.  Buffers, alignment, d_dst ==
+ * d_src (through context scratch and one copy), any other overlap (DCMT_E_INVALID) and the standing behind other *_dev calls: as
+ * dcmt_gaussian5_dev.  Also DCMT_E_INVALID: a sigma that is not finite and > 0, or a sigma_color whose square has no finite f32
+ * reciprocal.  Stream-ordered, never synchronises, never allocates. */
+int dcmt_bilateral5_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, float sigma_color,
+                        float sigma_space, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
+int dcmt_bilateral5(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols,
+                    float sigma_color, float sigma_space);
 
 /* ---- a dense plane seen by one camera -> the plane another camera sees --------------------------------- */
 

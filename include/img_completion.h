@@ -74,6 +74,7 @@ inline int blur_from_string(const std::string& blur_type)
 {
     if (blur_type == "gaussian") return DCMT_BLUR_GAUSSIAN;   // img_completion.cpp:176
     if (blur_type == "bilateral") return DCMT_BLUR_BILATERAL; // :172 -- cv::bilateralFilter in place throws; so do we
+    if (blur_type == "bilateral_clone") return DCMT_BLUR_BILATERAL_CLONE;   // this project's opt-in: :174 given a copy (dcmt.h)
     return DCMT_BLUR_NONE;                                    // any other string: no blur
 }
 
@@ -235,6 +236,21 @@ inline void gaussian_blur5(const cv::Mat& src, cv::Mat& dst)
     out.create(rows, cols, CV_32FC1);
     raise(dcmt_gaussian5(thread_ctx().get(rows, cols), src.ptr<float>(), src.step[0], out.ptr<float>(), out.step[0], rows, cols),
           "gaussian_blur5");
+    dst = out;
+}
+
+// cv::bilateralFilter(src, dst, 5, sigma_color, sigma_space) as dcmt.h states it (dcmt_bilateral5): the edge-preserving alternative to
+// gaussian_blur5; the defaults are the cascade's literals (img_completion.cpp:174).  src and dst may be the same Mat.  CV_32FC1 in,
+// a fresh CV_32FC1 out.
+inline void bilateral_filter5(const cv::Mat& src, cv::Mat& dst, float sigma_color = 1.5f, float sigma_space = 2.0f)
+{
+    check_input(src);
+    const int rows = src.rows, cols = src.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    raise(dcmt_bilateral5(thread_ctx().get(rows, cols), src.ptr<float>(), src.step[0], out.ptr<float>(), out.step[0], rows, cols, sigma_color,
+                          sigma_space),
+          "bilateral_filter5");
     dst = out;
 }
 
