@@ -7,7 +7,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   interpolate_with_superpixels, make_cloud_params, make_params, make_reproject_params, read_pcd, reference_performance,
                   reproject_pc, reproject_pc_colors, to_color_image, unrectify_sol, write_pcd,
                   calib_to_device, make_cloud_calib, make_project_calib, make_reproject_calib, make_stereo_calib,
-                  depth_to_u16, kitti_crop_origin, make_crop_table, pack_ragged, bilateral_filter5)
+                  depth_to_u16, kitti_crop_origin, make_crop_table, pack_ragged, bilateral_filter5,
+                  slic_connectivity_max_labels, slic_enforce_connectivity)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -15,7 +16,7 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "reproject_pc_colors", "reproject_pc", "write_pcd", "read_pcd", "make_reproject_params", "unrectify_sol",
            "bgr_to_lab", "bgr_to_gray", "make_project_calib", "make_cloud_calib", "make_reproject_calib", "make_stereo_calib",
            "calib_to_device", "depth_to_u16", "kitti_crop_origin", "make_crop_table", "pack_ragged",
-           "bilateral_filter5"]
+           "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity"]
 
 
 def __getattr__(name):

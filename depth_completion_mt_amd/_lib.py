@@ -40,6 +40,7 @@ EXPORTS = (
     "dcmt_project_points_nearest_dev", "dcmt_project_points_nearest_calib_dev", "dcmt_reproject_depth_nearest_dev",
     "dcmt_reproject_depth_nearest_calib_dev", "dcmt_project_points_nearest", "dcmt_reproject_depth_nearest",
     "dcmt_bilateral5_dev", "dcmt_bilateral5",
+    "dcmt_slic_connectivity_max_labels", "dcmt_slic_connectivity_dev", "dcmt_slic_connectivity",
 )
 
 
@@ -182,6 +183,9 @@ def lib() -> ctypes.CDLL:
         L.dcmt_slic_labels.argtypes = [vp, vp, sz, i, i, i, i, vp, vp]
         L.dcmt_stereo_refine.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, i, i, vp]
         L.dcmt_slic_num_centers.argtypes = [i, i, i]
+        L.dcmt_slic_connectivity_max_labels.argtypes = [i, i, i]
+        L.dcmt_slic_connectivity_dev.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
+        L.dcmt_slic_connectivity.argtypes = [vp, vp, sz, i, i, i, vp, sz, vp]
         f32 = ctypes.c_float
         L.dcmt_evaluate_dev.argtypes = [vp, vp, vp, i, i, i, f32, i, vp, vp]
         L.dcmt_evaluate_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, f32, i, vp, vp]

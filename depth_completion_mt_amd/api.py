@@ -493,6 +493,40 @@ class Context:
         _check(st, "dcmt_slic_labels_dev")
         return (d_labels, n, d_cent[:, :n]) if return_centers else (d_labels, n)
 
+    def slic_connectivity_dev(self, d_labels, n_centers: int, d_out=None, d_counts=None, stream: int | None = None):
+        """Slic::create_connectivity (LC/slic.cpp:186-254) on the device as include/dcmt.h states it (dcmt_slic_connectivity_dev):
+        every label one 4-connected region, fragments below a quarter of a superpixel merged into a neighbour.  d_labels: int32
+        CUDA tensor [batch][rows][cols] (or [rows][cols]), what slic_labels_dev returns; n_centers: its second return value.
+        d_out may be d_labels (in place).  Returns (d_out, max_labels, d_counts) without synchronising: max_labels bounds every
+        frame's label count and is the n_labels complete_dev takes, d_counts int32 [batch] holds the counts themselves.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_labels, torch.int32)
+        b, r, c = _brc(d_labels)
+        with _on_stream(stream, d_labels):
+            if d_out is None:
+                d_out = torch.full_like(d_labels, -7)
+            if d_counts is None:
+                d_counts = torch.full((b,), -7, dtype=torch.int32, device=d_labels.device)
+        assert _is_dev(d_out, torch.int32) and d_out.numel() == d_labels.numel()
+        assert _is_dev(d_counts, torch.int32) and d_counts.numel() == b
+        st = L.lib().dcmt_slic_connectivity_dev(self._h, d_labels.data_ptr(), r, c, b, int(n_centers), d_out.data_ptr(), d_counts.data_ptr(),
+                                                _stream(stream, d_labels))
+        _check(st, "dcmt_slic_connectivity_dev")
+        return d_out, slic_connectivity_max_labels(r, c, n_centers), d_counts
+
+    def slic_connectivity(self, labels: np.ndarray, n_centers: int):
+        """One frame of host memory (dcmt_slic_connectivity, synchronous; any row stride): (a new int32 array, its label count)."""
+        a = np.asarray(labels, dtype=np.int32)
+        assert a.ndim == 2
+        a = a if a.strides[1] == 4 else np.ascontiguousarray(a)
+        out = np.empty(a.shape, dtype=np.int32)
+        count = ctypes.c_int32(-1)
+        st = L.lib().dcmt_slic_connectivity(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], int(n_centers), out.ctypes.data,
+                                            out.strides[0], ctypes.byref(count))
+        _check(st, "dcmt_slic_connectivity")
+        return out, count.value
+
     def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
         """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
         kw: baseline, focal, damp, max_depth override the reference's constants.
@@ -995,6 +1029,22 @@ def bilateral_filter5(frame, sigma_color: float = 1.5, sigma_space: float = 2.0)
     (Context.bilateral5): a new f32 array.  The defaults are the cascade's literals (LO/img_completion.cpp:174)."""
     a = np.asarray(frame, dtype=np.float32)
     return _ctx_for(a.shape[0], a.shape[1], 1).bilateral5(a, sigma_color, sigma_space)
+
+
+def slic_connectivity_max_labels(rows: int, cols: int, n_centers: int) -> int:
+    """The bound on a frame's label count behind the connectivity pass (dcmt_slic_connectivity_max_labels; needs no GPU): what
+    complete_dev takes as n_labels.  ValueError for a shape the pass refuses (n_centers < 1, fewer than 4 pixels per centre)."""
+    m = L.lib().dcmt_slic_connectivity_max_labels(int(rows), int(cols), int(n_centers))
+    if m < 1:
+        raise ValueError(f"slic_connectivity_max_labels({rows}, {cols}, {n_centers}): (rows * cols) / n_centers must be at least 4")
+    return m
+
+
+def slic_enforce_connectivity(labels, n_centers: int):
+    """The reference's slic.create_connectivity(lab_image) (LC/main_lc.cpp:202) on one host frame, with its result kept
+    (Context.slic_connectivity): labels int32 [rows][cols] (clusters.T), n_centers = slic.centers.size() -> (labels, count)."""
+    a = np.asarray(labels, dtype=np.int32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).slic_connectivity(a, n_centers)
 
 
 def reproject_pc_colors(depth, bgr):

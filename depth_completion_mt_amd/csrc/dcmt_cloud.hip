@@ -1,7 +1,8 @@
 // dcmt_cloud.hip -- the kernels of dcmt_kernels_cloud.h, dcmt_kernels_reproject.h, dcmt_kernels_nearest.h, dcmt_kernels_bgr.h and dcmt_kernels_crop.h, a code
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
-// dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -14,6 +15,7 @@
 #include "dcmt_kernels_nearest.h"
 #include "dcmt_kernels_reproject.h"
 #include "dcmt_kernels_bilateral.h"
+#include "dcmt_kernels_connect.h"
 
 using namespace dcmt;
 
@@ -418,6 +420,43 @@ int dcmt_bilateral5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int row
     float* out = in_place ? ctx->pp[0] : d_dst;
     DCMT_TRY(bilateral5_enqueue(ctx, d_src, out, rows, cols, batch, sigma_color, sigma_space, false, 0.0f, 0.0f, st));
     if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- Slic::create_connectivity (dcmt_kernels_connect.h) -------------------------------------------------------------------------
+extern "C" {
+
+int dcmt_slic_connectivity_max_labels(int rows, int cols, int n_centers)
+{
+    const int bound = plan::connectivity_max_labels(rows, cols, n_centers);
+    return bound == plan::kInvalid ? DCMT_E_INVALID : bound;
+}
+
+// The launches plan_connectivity names, on pp[0] and pp[1] (scratch every completion call rewrites before it reads it) and the
+// context's strip slab, which the first call of this kind allocates for the context's maxima before it enqueues anything.  None of
+// the context's carried state is read or written.
+int dcmt_slic_connectivity_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows, int cols, int batch, int n_centers, int32_t* d_out,
+                               int32_t* d_counts, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const plan::ConnPlan pl = plan::plan_connectivity(rows, cols, batch, n_centers, (uintptr_t)d_labels, (uintptr_t)d_out, (uintptr_t)d_counts);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    DCMT_TRY(ctx->conn_slab.reserve(ctx, plan::connectivity_slab_words(ctx->max_cols, ctx->max_batch)));
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* A = reinterpret_cast<uint32_t*>(ctx->pp[0].p);
+    uint32_t* B = reinterpret_cast<uint32_t*>(ctx->pp[1].p);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols;
+    hipLaunchKernelGGL(k_conn_local, dim3(pl.local_x, batch), dim3(256), 0, st, d_labels, r, c, pl.tiles_x, pl.kbits, A, B);
+    if (pl.border_x > 0) hipLaunchKernelGGL(k_conn_border, dim3(pl.border_x, batch), dim3(256), 0, st, d_labels, r, c, pl.pairs_v, pl.pairs, pl.kbits, A);
+    hipLaunchKernelGGL(k_conn_flatten, dim3(pl.px_x, batch), dim3(256), 0, st, pl.n, c, pl.kbits, A, B);
+    hipLaunchKernelGGL(k_conn_seed, dim3(pl.strips, batch), dim3(256), 0, st, A, B, r, c, pl.kbits, pl.band_rows, pl.lim4, ctx->conn_slab.p);
+    hipLaunchKernelGGL(k_conn_scan, dim3(batch), dim3(256), 0, st, ctx->conn_slab.p, pl.strips, d_counts);
+    hipLaunchKernelGGL(k_conn_rank, dim3(pl.strips, batch), dim3(256), 0, st, B, r, c, pl.band_rows, ctx->conn_slab.p);
+    hipLaunchKernelGGL(k_conn_relabel, dim3(pl.px_x, batch), dim3(256), 0, st, A, B, pl.n, c, pl.kbits, d_out);
+    DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
 

@@ -103,6 +103,8 @@ struct dcmt_ctx {
                                       // hold frames' loop results then); the first call with DCMT_BLUR_BILATERAL_CLONE
     Dev<uint32_t> cloud_slab;         // dcmt_depth_to_cloud_dev: per (frame, chunk, wave) record counts, then their exclusive bases; sized like
                                       // color_slab, kCloudWaves entries per chunk
+    Dev<uint32_t> conn_slab;          // dcmt_slic_connectivity_dev: per (frame, strip of 64 columns) counts of non-small seeds, then their exclusive
+                                      // bases; max_batch x ceil(max_cols / 64) words, allocated by the first such call
 };
 
 namespace dcmt {

@@ -243,6 +243,18 @@ int dcmt_bilateral5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, siz
     return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
 }
 
+int dcmt_slic_connectivity(dcmt_ctx* ctx, const int32_t* labels, size_t lrs, int rows, int cols, int n_centers, int32_t* out, size_t ors,
+                           int32_t* count)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !labels || !out || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t row = sizeof(int32_t) * (size_t)cols;
+    Plane in(labels, lrs, row, rows), o(out, ors, row, rows), n(count, sizeof(int32_t));
+    int rc = stage(ctx, {&in}, {&o, &n});
+    if (rc == DCMT_OK) rc = dcmt_slic_connectivity_dev(ctx, (const int32_t*)in.dev, rows, cols, 1, n_centers, (int32_t*)o.dev, (int32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -10,6 +10,7 @@
 
 #include "dcmt_chunks.h"
 #include "dcmt_cloud.h"
+#include "dcmt_connect.h"
 #include "dcmt_crop.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_tiles.h"
@@ -226,6 +227,79 @@ inline SlicPlan plan_slic(int rows, int cols, int batch, int max_batch, int step
     p.init_x = (unsigned)((p.n + 63) / 64);
     p.nb_threads = (size_t)p.n * b > p.n_cnt ? (size_t)p.n * b : p.n_cnt;
     p.bin_x = (unsigned)((p.nb_threads + 255) / 256);
+    return p;
+}
+
+// ---- dcmt_slic_connectivity_dev ------------------------------------------------------------------------------------------
+// Connected-component labelling of the label plane and the reference's relabelling of it (dcmt_kernels_connect.h): seven launches
+// whose grids depend on the shape alone (the border merge is left out where a frame is one tile), on the context's two 4 B/px
+// planes and a slab of one word per (frame, strip of kConnStripCols columns).  The checks on the arguments are here as well, tested
+// without a device: out may BE labels (the last kernel is the only writer of out and reads no labels), any other overlap among
+// labels, out and counts is refused.
+inline int connectivity_lims(int rows, int cols, int n_centers)      // slic.cpp:188; 0 where it cannot be formed
+{
+    if (rows < 1 || cols < 1 || n_centers < 1 || (int64_t)rows * cols > 0x1ffffff0) return 0;
+    return (rows * cols) / n_centers;
+}
+
+// the bound on a frame's label count, kInvalid where the call refuses the shape: every non-small component holds more than
+// lims >> 2 pixels
+inline int connectivity_max_labels(int rows, int cols, int n_centers)
+{
+    const int lims = connectivity_lims(rows, cols, n_centers);
+    if (lims < 4) return kInvalid;
+    const int m = (rows * cols) / ((lims >> 2) + 1);
+    return m < 1 ? 1 : m;
+}
+
+struct ConnPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, n_centers < 1, lims < 4, buffers that overlap
+    uint32_t n;                      // pixels per frame
+    uint32_t kbits;                  // conn_key_bits(rows)
+    uint32_t lim4;                   // lims >> 2: a component is small iff size + (size >= 2) <= lim4
+    int max_labels;
+    uint32_t tiles_x, tiles_y;
+    unsigned local_x;                // k_conn_local: (tiles_x * tiles_y, batch)
+    uint32_t pairs_v, pairs;         // pixel pairs across vertical tile edges, across all tile edges
+    unsigned border_x;               // k_conn_border: (border_x, batch); 0: one tile, no launch
+    unsigned px_x;                   // k_conn_flatten, k_conn_relabel: (px_x, batch), one thread per pixel
+    uint32_t strips, band_rows;      // k_conn_seed, k_conn_rank: (strips, batch); k_conn_scan: (batch)
+    size_t slab;                     // words of the slab this call uses: [batch][strips]
+};
+
+// the slab a context keeps for its largest call
+inline size_t connectivity_slab_words(int max_cols, int max_batch)
+{
+    return (size_t)max_batch * (size_t)((max_cols + kConnStripCols - 1) / kConnStripCols);
+}
+
+// rows, cols, batch >= 1 and within the context's limits
+inline ConnPlan plan_connectivity(int rows, int cols, int batch, int n_centers, uintptr_t labels, uintptr_t out, uintptr_t counts)
+{
+    ConnPlan p = {};
+    p.status = kInvalid;
+    if (!labels || !out || labels % 4 != 0 || out % 4 != 0 || counts % 4 != 0) return p;
+    p.max_labels = connectivity_max_labels(rows, cols, n_centers);
+    if (p.max_labels == kInvalid) return p;
+    const size_t bytes = sizeof(int32_t) * (size_t)batch * (size_t)rows * (size_t)cols;
+    if (out != labels && ranges_overlap(labels, bytes, out, bytes)) return p;
+    if (counts && (ranges_overlap(counts, sizeof(int32_t) * (size_t)batch, labels, bytes) ||
+                   ranges_overlap(counts, sizeof(int32_t) * (size_t)batch, out, bytes)))
+        return p;
+    p.status = kOk;
+    p.n = (uint32_t)rows * (uint32_t)cols;
+    p.kbits = (uint32_t)conn_key_bits(rows);
+    p.lim4 = (uint32_t)(connectivity_lims(rows, cols, n_centers) >> 2);
+    p.tiles_x = ((uint32_t)cols + kConnTW - 1) / kConnTW;
+    p.tiles_y = ((uint32_t)rows + kConnTH - 1) / kConnTH;
+    p.local_x = p.tiles_x * p.tiles_y;
+    p.pairs_v = (p.tiles_x - 1) * (uint32_t)rows;
+    p.pairs = p.pairs_v + (p.tiles_y - 1) * (uint32_t)cols;
+    p.border_x = (p.pairs + 255) / 256;
+    p.px_x = (p.n + 255) / 256;
+    p.strips = ((uint32_t)cols + kConnStripCols - 1) / kConnStripCols;
+    p.band_rows = ((uint32_t)rows + kConnWaves - 1) / kConnWaves;
+    p.slab = (size_t)batch * p.strips;
     return p;
 }
 

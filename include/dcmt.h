@@ -162,7 +162,8 @@ int dcmt_device_count(void);
  * 16-bit plane of large on-grid batches, 2 B per pixel; the column statistics of the small-batch tile kernels); SLIC scratch and
  * the partial-sum slab of the evaluate calls are allocated the same way by the first call that needs them, so no call
  * after the first of its kind allocates.  The min/max slab of dcmt_colorize* (8 B per 8192 pixels of a frame, times max_batch)
- * and the count slab of dcmt_depth_to_cloud* (16 B per 8192 pixels, times max_batch) are allocated here.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
+ * and the count slab of dcmt_depth_to_cloud* (16 B per 8192 pixels, times max_batch) are allocated here; the strip slab of
+ * dcmt_slic_connectivity_dev (4 B per 64 columns of max_cols, times max_batch) by the first call of it.  A frame may hold at most 2^29 - 16 pixels (it is addressed with 32-bit byte offsets
  * and one offset just below 2^31 is kept free as "nowhere"); max_batch at most 65535. */
 int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx **out);
 void dcmt_destroy(dcmt_ctx *ctx);
@@ -260,6 +261,52 @@ int dcmt_project_points_dev(dcmt_ctx *ctx, const float *d_points, const int32_t 
 int dcmt_slic_num_centers(int rows, int cols, int step);
 int dcmt_slic_labels_dev(dcmt_ctx *ctx, const uint8_t *d_lab, int rows, int cols, int batch, int step, int nc,
                          int32_t *d_labels, double *d_centers, void *stream);
+
+/* Slic::create_connectivity (DC_lidar_camera/slic.cpp:186-254; called at main_lc.cpp:202 between generate_superpixels and
+ * interpolate_with_superpixels) on the device: the connectivity pass of SLIC.  The label plane is relabelled so that every label is
+ * one 4-connected region, and fragments smaller than a quarter of a superpixel take the label of a neighbour.  An OPT-IN: the
+ * reference computes this relabelling into a local (new_clusters) that nothing reads, so its own results are those of the raw
+ * k-means labels; call this between dcmt_slic_labels_dev and dcmt_complete_labeled_f32_dev to get what was intended.
+ * The reference's sequential, order-dependent statements, as the data-parallel definition that gives the same labels.  A frame is
+ * labels[rows][cols] int32 row-major (the reference's clusters[col][row]); x is the column, y the row, s(x, y) = x * rows + y the
+ * reference's scan order (column outer, row inner):
+ *   components  a component is a maximal 4-connected set of pixels with equal input label; any int32 compares, -1 ("never
+ *               reached") and values >= n_centers included (:227 compares with == and nothing else)
+ *   seed        a component's pixel with the smallest s
+ *   count       size + (size >= 2 ? 1 : 0): the reference never marks the seed, reaches it again and counts it twice (:207, :227-230)
+ *   threshold   lims = (rows * cols) / n_centers (integer division; n_centers is the reference's centers.size(), what
+ *               dcmt_slic_num_centers returns); a component is SMALL iff count <= lims >> 2 (:238).  lims >= 4 is required (below
+ *               that a one-pixel component is not small and the reference leaves -1 in it)
+ *   non-small   its label is the number of non-small components whose seed has a smaller s (the reference's running `label`)
+ *   small       of the seed's neighbours (x-1, y), (x, y-1), (x+1, y), (x, y+1), in this order, those inside the frame whose
+ *               component's seed has a smaller s than this seed (the pixels already labelled when the scan arrives) are kept; the
+ *               LAST of them is the neighbour (:210-219), and the component takes the FINAL label of that neighbour's component
+ *               (chains of small components follow links to strictly smaller seeds until they reach a non-small one).  With no
+ *               such neighbour -- only the component of pixel (0, 0) -- it takes label 0, the reference's initial adjlabel
+ *   d_counts    [batch] or NULL: the number of non-small components of each frame.  Every output label lies in
+ *               [0, max(1, count)), and count <= max(1, (rows * cols) / ((lims >> 2) + 1)) because a non-small component holds
+ *               more than lims >> 2 pixels: dcmt_slic_connectivity_max_labels returns this bound (it needs no GPU; DCMT_E_INVALID
+ *               where the call refuses the shape), and the caller passes it as n_labels to dcmt_complete_labeled_f32_dev with no
+ *               host round trip.  Where the component of (0, 0) is small, label 0 can be shared by two regions: the reference's quirk.
+ * Two places where this leaves the reference's text: :226 bounds y by image.cols, which on a landscape image indexes
+ * new_clusters[x] past its end (undefined behaviour) -- y is bounded by rows here, as :213 does; and the result is stored.
+ * Integer arithmetic throughout: the result is bit-exact and does not depend on the batch size, the frame's position in the batch,
+ * alignment, the launch geometry or the run.
+ * d_labels / d_out: [batch][rows][cols] int32, 4-byte aligned.  d_out == d_labels is allowed and gives the bits of an out-of-place
+ * call (the last kernel is the only writer of d_out and reads no labels); any other overlap among d_labels, d_out and d_counts is
+ * DCMT_E_INVALID, as are null pointers, sizes beyond the context's limits, n_centers < 1, lims < 4 and misaligned pointers.
+ * Stream-ordered, never synchronises, a fixed number of launches (seven; six for a frame of at most 64 x 16 pixels): nothing the host
+ * does depends on the data.  Scratch: the two planes dcmt_create allocates (8 B per pixel; the ones the in-place dcmt_gaussian5_dev
+ * borrows, which every completion call rewrites before it reads them) and a slab of 4 B per 64 columns of max_cols, times
+ * max_batch, which the first call of this kind allocates before it enqueues anything.  Of the context's carried state it touches
+ * none: no flag ring, no winner plane, no bounding-box tables, no dcmt_last_path or probe.  Same standing behind other *_dev calls
+ * as dcmt_depth_to_cloud_dev. */
+int dcmt_slic_connectivity_max_labels(int rows, int cols, int n_centers);
+int dcmt_slic_connectivity_dev(dcmt_ctx *ctx, const int32_t *d_labels, int rows, int cols, int batch, int n_centers,
+                               int32_t *d_out, int32_t *d_counts /* [batch] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); labels may be out. */
+int dcmt_slic_connectivity(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, int rows, int cols, int n_centers,
+                           int32_t *out, size_t out_row_stride, int32_t *count /* or NULL */);
 
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 

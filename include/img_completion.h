@@ -168,6 +168,28 @@ inline int slic_labels(const cv::Mat& lab_image, int step, int nc, std::vector<s
     return dcmt_slic_num_centers(rows, cols, step);
 }
 
+// slic.create_connectivity(lab_image) (DC_lidar_camera/main_lc.cpp:202, slic.cpp:186-254) with its result KEPT, as dcmt.h states it
+// (dcmt_slic_connectivity): `clusters` ([col][row], as Slic::clusters) is relabelled in place so that every label is one 4-connected
+// region, fragments below a quarter of a superpixel merged into a neighbour.  n_centers = slic.centers.size() (what slic_labels
+// returns).  Returns the number of labels; every label is below max(1, that).  An opt-in: the reference drops this relabelling.
+inline int slic_enforce_connectivity(std::vector<std::vector<int> >& clusters, int n_centers)
+{
+    const int cols = (int)clusters.size(), rows = cols > 0 ? (int)clusters[0].size() : 0;
+    if (rows < 1) throw std::runtime_error("slic_enforce_connectivity: empty clusters");
+    std::vector<int32_t> lab((size_t)rows * cols);
+    for (int j = 0; j < cols; ++j) {
+        if ((int)clusters[j].size() != rows) throw std::runtime_error("slic_enforce_connectivity: clusters is not rectangular");
+        for (int i = 0; i < rows; ++i) lab[(size_t)i * cols + j] = clusters[j][i];   // [col][row] -> row-major
+    }
+    int32_t count = 0;
+    const size_t row = sizeof(int32_t) * (size_t)cols;
+    raise(dcmt_slic_connectivity(thread_ctx().get(rows, cols), lab.data(), row, rows, cols, n_centers, lab.data(), row, &count),
+          "slic_enforce_connectivity");
+    for (int j = 0; j < cols; ++j)
+        for (int i = 0; i < rows; ++i) clusters[j][i] = lab[(size_t)i * cols + j];
+    return (int)count;
+}
+
 // DC_stereo_lidar/main_sl.cpp:1165-1246: get_initial_disparity + calculateMeasuementDerivatives + optimize_IG +
 // retrieve_optimized_depth on the dense depth (CV_32FC1) and the two grey images (CV_8UC1).
 inline void stereo_refine(const cv::Mat& dense_depth, const cv::Mat& left_gray, const cv::Mat& right_gray, cv::Mat& optimized_depth)
