@@ -8,7 +8,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   reproject_pc, reproject_pc_colors, to_color_image, unrectify_sol, write_pcd,
                   calib_to_device, make_cloud_calib, make_project_calib, make_reproject_calib, make_stereo_calib,
                   depth_to_u16, kitti_crop_origin, make_crop_table, pack_ragged, bilateral_filter5,
-                  slic_connectivity_max_labels, slic_enforce_connectivity)
+                  slic_connectivity_max_labels, slic_enforce_connectivity, slic_display_contours,
+                  slic_colour_with_cluster_means)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -16,7 +17,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "reproject_pc_colors", "reproject_pc", "write_pcd", "read_pcd", "make_reproject_params", "unrectify_sol",
            "bgr_to_lab", "bgr_to_gray", "make_project_calib", "make_cloud_calib", "make_reproject_calib", "make_stereo_calib",
            "calib_to_device", "depth_to_u16", "kitti_crop_origin", "make_crop_table", "pack_ragged",
-           "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity"]
+           "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity",
+           "slic_display_contours", "slic_colour_with_cluster_means"]
 
 
 def __getattr__(name):

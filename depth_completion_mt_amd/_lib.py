@@ -41,6 +41,7 @@ EXPORTS = (
     "dcmt_reproject_depth_nearest_calib_dev", "dcmt_project_points_nearest", "dcmt_reproject_depth_nearest",
     "dcmt_bilateral5_dev", "dcmt_bilateral5",
     "dcmt_slic_connectivity_max_labels", "dcmt_slic_connectivity_dev", "dcmt_slic_connectivity",
+    "dcmt_slic_contours_dev", "dcmt_slic_cluster_means_dev", "dcmt_slic_contours", "dcmt_slic_cluster_means",
 )
 
 
@@ -186,6 +187,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_slic_connectivity_max_labels.argtypes = [i, i, i]
         L.dcmt_slic_connectivity_dev.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
         L.dcmt_slic_connectivity.argtypes = [vp, vp, sz, i, i, i, vp, sz, vp]
+        L.dcmt_slic_contours_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp]
+        L.dcmt_slic_cluster_means_dev.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
+        L.dcmt_slic_contours.argtypes = [vp, vp, sz, i, i, vp, sz, vp, vp, sz]
+        L.dcmt_slic_cluster_means.argtypes = [vp, vp, sz, i, i, i, vp, sz, vp]
         f32 = ctypes.c_float
         L.dcmt_evaluate_dev.argtypes = [vp, vp, vp, i, i, i, f32, i, vp, vp]
         L.dcmt_evaluate_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, f32, i, vp, vp]

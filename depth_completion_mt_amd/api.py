@@ -527,6 +527,75 @@ class Context:
         _check(st, "dcmt_slic_connectivity")
         return out, count.value
 
+    def slic_contours_dev(self, d_labels, d_bgr=None, colour=(0, 0, 200), d_mask=None, stream: int | None = None):
+        """Slic::display_contours (LC/slic.cpp:337-384; main_lc.cpp:214) on the device as include/dcmt.h states it
+        (dcmt_slic_contours_dev).  d_labels: int32 CUDA tensor [batch][rows][cols] (or [rows][cols]).  d_bgr: uint8 CUDA tensor of
+        d_labels' shape + (3,), painted IN PLACE with `colour` (B, G, R; the default is the reference's CV_RGB(200,0,0)) where a pixel
+        is taken; d_mask: uint8 of d_labels' shape, 255 taken / 0 not.  With neither given the mask is created.  Returns
+        (d_bgr, d_mask), None for the one that was not asked for, without synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_labels, torch.int32)
+        b, r, c = _brc(d_labels)
+        if d_bgr is None and d_mask is None:
+            with _on_stream(stream, d_labels):
+                d_mask = torch.full(tuple(d_labels.shape), 0xA5, dtype=torch.uint8, device=d_labels.device)
+        assert d_bgr is None or (_is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c)
+        assert d_mask is None or (_is_dev(d_mask, torch.uint8) and d_mask.numel() == b * r * c)
+        col = (ctypes.c_uint8 * 3)(*[int(v) & 0xFF for v in colour])
+        st = L.lib().dcmt_slic_contours_dev(self._h, d_labels.data_ptr(), r, c, b, None if d_bgr is None else d_bgr.data_ptr(), col,
+                                            None if d_mask is None else d_mask.data_ptr(), _stream(stream, d_labels))
+        _check(st, "dcmt_slic_contours_dev")
+        return d_bgr, d_mask
+
+    def slic_cluster_means_dev(self, d_labels, n_labels: int, d_bgr, d_sums=None, stream: int | None = None):
+        """Slic::colour_with_cluster_means (LC/slic.cpp:392-433) on the device as include/dcmt.h states it
+        (dcmt_slic_cluster_means_dev): every pixel of d_bgr (uint8, d_labels' shape + (3,), IN PLACE) whose label is in [0, n_labels)
+        becomes its label's mean colour, integer division.  d_sums: int32 CUDA tensor [batch][n_labels][4] = sumB, sumG, sumR, count;
+        None: not wanted; True: created.  Returns (d_bgr, d_sums) without synchronising.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_labels, torch.int32)
+        b, r, c = _brc(d_labels)
+        assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
+        if d_sums is True:
+            with _on_stream(stream, d_labels):
+                d_sums = torch.full((b, int(n_labels), 4), -7, dtype=torch.int32, device=d_labels.device)
+        assert d_sums is None or (_is_dev(d_sums, torch.int32) and d_sums.numel() == 4 * b * int(n_labels))
+        st = L.lib().dcmt_slic_cluster_means_dev(self._h, d_labels.data_ptr(), r, c, b, int(n_labels), d_bgr.data_ptr(),
+                                                 None if d_sums is None else d_sums.data_ptr(), _stream(stream, d_labels))
+        _check(st, "dcmt_slic_cluster_means_dev")
+        return d_bgr, d_sums
+
+    def slic_contours(self, labels: np.ndarray, image=None, colour=(0, 0, 200)):
+        """One frame of host memory (dcmt_slic_contours, synchronous; any row stride): (a painted copy of `image` -- uint8
+        [rows][cols][3] -- or None where no image is given, the uint8 [rows][cols] mask)."""
+        a = np.asarray(labels, dtype=np.int32)
+        assert a.ndim == 2
+        a = a if a.strides[1] == 4 else np.ascontiguousarray(a)
+        img = None if image is None else np.array(image, dtype=np.uint8, order="C")
+        assert img is None or img.shape == a.shape + (3,)
+        mask = np.empty(a.shape, dtype=np.uint8)
+        col = (ctypes.c_uint8 * 3)(*[int(v) & 0xFF for v in colour])
+        st = L.lib().dcmt_slic_contours(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], None if img is None else img.ctypes.data,
+                                        0 if img is None else img.strides[0], col, mask.ctypes.data, mask.strides[0])
+        _check(st, "dcmt_slic_contours")
+        return img, mask
+
+    def slic_cluster_means(self, labels: np.ndarray, image, n_labels: int):
+        """One frame of host memory (dcmt_slic_cluster_means, synchronous): (the mean-coloured copy of `image`, int32
+        [n_labels][4] = sumB, sumG, sumR, count)."""
+        a = np.asarray(labels, dtype=np.int32)
+        assert a.ndim == 2
+        a = a if a.strides[1] == 4 else np.ascontiguousarray(a)
+        img = np.array(image, dtype=np.uint8, order="C")
+        assert img.shape == a.shape + (3,)
+        sums = np.empty((max(int(n_labels), 0), 4), dtype=np.int32)
+        st = L.lib().dcmt_slic_cluster_means(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], int(n_labels), img.ctypes.data,
+                                             img.strides[0], sums.ctypes.data)
+        _check(st, "dcmt_slic_cluster_means")
+        return img, sums
+
     def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
         """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
         kw: baseline, focal, damp, max_depth override the reference's constants.
@@ -1045,6 +1114,20 @@ def slic_enforce_connectivity(labels, n_centers: int):
     (Context.slic_connectivity): labels int32 [rows][cols] (clusters.T), n_centers = slic.centers.size() -> (labels, count)."""
     a = np.asarray(labels, dtype=np.int32)
     return _ctx_for(a.shape[0], a.shape[1], 1).slic_connectivity(a, n_centers)
+
+
+def slic_display_contours(labels, image, colour=(0, 0, 200)):
+    """The reference's slic.display_contours(image, CV_RGB(200,0,0)) (LC/main_lc.cpp:214) on one host frame (Context.slic_contours):
+    labels int32 [rows][cols] (clusters.T), image uint8 [rows][cols][3] B, G, R, colour B, G, R -> the painted copy of the image."""
+    a = np.asarray(labels, dtype=np.int32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).slic_contours(a, image, colour)[0]
+
+
+def slic_colour_with_cluster_means(labels, image, n_labels: int):
+    """The reference's slic.colour_with_cluster_means(image) (LC/slic.cpp:392-433) on one host frame (Context.slic_cluster_means):
+    n_labels = slic.centers.size() -> the copy of the image with every superpixel in its mean colour."""
+    a = np.asarray(labels, dtype=np.int32)
+    return _ctx_for(a.shape[0], a.shape[1], 1).slic_cluster_means(a, image, n_labels)[0]
 
 
 def reproject_pc_colors(depth, bgr):

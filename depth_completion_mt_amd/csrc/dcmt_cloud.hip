@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -16,6 +16,7 @@
 #include "dcmt_kernels_reproject.h"
 #include "dcmt_kernels_bilateral.h"
 #include "dcmt_kernels_connect.h"
+#include "dcmt_kernels_contour.h"
 
 using namespace dcmt;
 
@@ -456,6 +457,51 @@ int dcmt_slic_connectivity_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows,
     hipLaunchKernelGGL(k_conn_scan, dim3(batch), dim3(256), 0, st, ctx->conn_slab.p, pl.strips, d_counts);
     hipLaunchKernelGGL(k_conn_rank, dim3(pl.strips, batch), dim3(256), 0, st, B, r, c, pl.band_rows, ctx->conn_slab.p);
     hipLaunchKernelGGL(k_conn_relabel, dim3(pl.px_x, batch), dim3(256), 0, st, A, B, pl.n, c, pl.kbits, d_out);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- Slic::display_contours, Slic::colour_with_cluster_means (dcmt_kernels_contour.h) ---------------------------------------------
+extern "C" {
+
+// The launches plan_contours names, on pp[0] (code bytes) and pp[1] (taken bytes): scratch every completion call rewrites before it
+// reads it.  None of the context's carried state is read or written, and nothing is allocated.
+int dcmt_slic_contours_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows, int cols, int batch, uint8_t* d_bgr, const uint8_t colour_bgr[3],
+                           uint8_t* d_mask, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const plan::ContourPlan pl = plan::plan_contours(rows, cols, batch, (uintptr_t)d_labels, (uintptr_t)d_bgr, (uintptr_t)d_mask, (uintptr_t)colour_bgr);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* codes = reinterpret_cast<uint8_t*>(ctx->pp[0].p);
+    uint8_t* taken = reinterpret_cast<uint8_t*>(ctx->pp[1].p);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols;
+    hipLaunchKernelGGL(k_cont_classify, dim3(pl.tile_grid, batch), dim3(256), 0, st, d_labels, r, c, pl.tiles_x, codes);
+    hipLaunchKernelGGL(k_cont_walk, dim3(batch), dim3(64), pl.walk_lds, st, codes, taken, r, c, pl.chunks);
+    hipLaunchKernelGGL(k_cont_paint, dim3(pl.tile_grid, batch), dim3(256), 0, st, taken, r, c, pl.tiles_x, d_mask, d_bgr, (uint32_t)colour_bgr[0],
+                       (uint32_t)colour_bgr[1], (uint32_t)colour_bgr[2]);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// The launches plan_cluster_means names; the sums are the caller's d_sums or, without one, the head of pp[0].
+int dcmt_slic_cluster_means_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows, int cols, int batch, int n_labels, uint8_t* d_bgr,
+                                int32_t* d_sums, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const size_t plane_bytes = sizeof(float) * ctx->frame_elems * (size_t)ctx->max_batch;
+    const plan::MeansPlan pl = plan::plan_cluster_means(rows, cols, batch, n_labels, plane_bytes, (uintptr_t)d_labels, (uintptr_t)d_bgr, (uintptr_t)d_sums);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* sums = d_sums ? reinterpret_cast<uint32_t*>(d_sums) : reinterpret_cast<uint32_t*>(ctx->pp[0].p);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, nl = (uint32_t)n_labels;
+    hipLaunchKernelGGL(k_means_clear, dim3(pl.clear_grid), dim3(256), 0, st, sums, pl.words);
+    hipLaunchKernelGGL(k_means_sum, dim3(pl.sum_grid, batch), dim3(256), 0, st, d_labels, d_bgr, r, c, pl.tiles_x, nl, sums);
+    hipLaunchKernelGGL(k_means_paint, dim3(pl.px_x, batch), dim3(256), 0, st, d_labels, pl.n, nl, sums, d_bgr);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

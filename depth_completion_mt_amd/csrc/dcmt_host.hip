@@ -255,6 +255,29 @@ int dcmt_slic_connectivity(dcmt_ctx* ctx, const int32_t* labels, size_t lrs, int
     return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
 }
 
+int dcmt_slic_contours(dcmt_ctx* ctx, const int32_t* labels, size_t lrs, int rows, int cols, uint8_t* bgr, size_t brs, const uint8_t colour_bgr[3],
+                       uint8_t* mask, size_t mrs)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !labels || (!bgr && !mask) || !colour_bgr || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    Plane in(labels, lrs, sizeof(int32_t) * (size_t)cols, rows), img(bgr, brs, 3 * (size_t)cols, rows), m(mask, mrs, (size_t)cols, rows);
+    int rc = stage(ctx, {&in, &img}, {&m});
+    if (rc == DCMT_OK) rc = dcmt_slic_contours_dev(ctx, (const int32_t*)in.dev, rows, cols, 1, (uint8_t*)img.dev, colour_bgr, (uint8_t*)m.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&img, &m}) : rc;
+}
+
+int dcmt_slic_cluster_means(dcmt_ctx* ctx, const int32_t* labels, size_t lrs, int rows, int cols, int n_labels, uint8_t* bgr, size_t brs,
+                            int32_t* sums)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !labels || !bgr || n_labels < 1 || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    if ((size_t)n_labels > sizeof(float) * ctx->frame_elems * (size_t)ctx->max_batch / 16) return DCMT_E_INVALID;   // the *_dev call's bound, before anything is staged
+    Plane in(labels, lrs, sizeof(int32_t) * (size_t)cols, rows), img(bgr, brs, 3 * (size_t)cols, rows), s(sums, sizeof(int32_t) * 4 * (size_t)n_labels);
+    int rc = stage(ctx, {&in, &img}, {&s});
+    if (rc == DCMT_OK) rc = dcmt_slic_cluster_means_dev(ctx, (const int32_t*)in.dev, rows, cols, 1, n_labels, (uint8_t*)img.dev, (int32_t*)s.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&img, &s}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -11,6 +11,7 @@
 #include "dcmt_chunks.h"
 #include "dcmt_cloud.h"
 #include "dcmt_connect.h"
+#include "dcmt_contour.h"
 #include "dcmt_crop.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_tiles.h"
@@ -300,6 +301,86 @@ inline ConnPlan plan_connectivity(int rows, int cols, int batch, int n_centers, 
     p.strips = ((uint32_t)cols + kConnStripCols - 1) / kConnStripCols;
     p.band_rows = ((uint32_t)rows + kConnWaves - 1) / kConnWaves;
     p.slab = (size_t)batch * p.strips;
+    return p;
+}
+
+// ---- dcmt_slic_contours_dev, dcmt_slic_cluster_means_dev ------------------------------------------------------------------
+// The two pixel renderings of SLIC (dcmt_kernels_contour.h), three launches each whose grids depend on the shape alone.  The
+// contours borrow pp[0] for the code bytes and pp[1] for the taken bytes, 1 B/px each, both [batch][cols][rows]; the means borrow
+// pp[0] for the sums where the caller passes none.  The checks on the arguments are here as well, tested without a device: every
+// overlap among the device buffers of a call is refused.
+struct ContourPlan {
+    int status;                      // kInvalid: no labels, neither output, no colour, a misaligned label plane, more than
+                                     // 64 * kContMaxChunks rows, buffers that overlap
+    uint32_t chunks;                 // ceil(rows / 64): the steps of a column in k_cont_walk, the tile rows of the other two
+    uint32_t tiles_x;
+    unsigned tile_grid;              // k_cont_classify, k_cont_paint: (tile_grid, batch)
+    uint32_t steps;                  // k_cont_walk: (batch) waves of cols * chunks steps
+    size_t walk_lds;                 // ... its dynamic LDS: one 64-bit mask per chunk
+    size_t scratch;                  // bytes of each of the two borrowed planes this call uses
+};
+
+// rows, cols, batch >= 1 and within the context's limits (a frame of at most 2^29 - 16 pixels)
+inline ContourPlan plan_contours(int rows, int cols, int batch, uintptr_t labels, uintptr_t bgr, uintptr_t mask, uintptr_t colour)
+{
+    ContourPlan p = {};
+    p.status = kInvalid;
+    if (!labels || labels % 4 != 0 || (!bgr && !mask) || !colour) return p;
+    const uint32_t chunks = ((uint32_t)rows + kContTile - 1) / kContTile;
+    if (chunks > (uint32_t)kContMaxChunks) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    if (bgr && ranges_overlap(labels, 4 * px, bgr, 3 * px)) return p;
+    if (mask && ranges_overlap(labels, 4 * px, mask, px)) return p;
+    if (bgr && mask && ranges_overlap(bgr, 3 * px, mask, px)) return p;
+    p.status = kOk;
+    p.chunks = chunks;
+    p.tiles_x = ((uint32_t)cols + kContTile - 1) / kContTile;
+    p.tile_grid = p.tiles_x * p.chunks;
+    p.steps = (uint32_t)cols * p.chunks;                 // < 2^29 / 64 + 2^29
+    p.walk_lds = sizeof(uint64_t) * p.chunks;
+    p.scratch = px;
+    return p;
+}
+
+// the largest n_labels a call with `batch` frames may name: batch * n_labels * 16 bytes of sums fit in one borrowed plane of
+// plane_bytes (4 * max_batch * max_rows * max_cols), and a frame's sums are addressed with 32-bit words
+inline int cluster_means_max_labels(size_t plane_bytes, int batch)
+{
+    const size_t m = plane_bytes / 16 / (size_t)(batch < 1 ? 1 : batch);
+    return m > 0x0fffffff ? 0x0fffffff : (int)m;
+}
+
+struct MeansPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, n_labels < 1 or beyond cluster_means_max_labels, a frame
+                                     // whose sums could pass 2^32 (255 * rows * cols), buffers that overlap
+    uint32_t n;                      // pixels per frame
+    uint32_t tiles_x, tiles_y;
+    unsigned sum_grid;               // k_means_sum: (sum_grid, batch)
+    unsigned px_x;                   // k_means_paint: (px_x, batch)
+    size_t words;                    // the sums: batch * n_labels * 4
+    unsigned clear_grid;             // k_means_clear
+};
+
+inline MeansPlan plan_cluster_means(int rows, int cols, int batch, int n_labels, size_t plane_bytes, uintptr_t labels, uintptr_t bgr,
+                                    uintptr_t sums)
+{
+    MeansPlan p = {};
+    p.status = kInvalid;
+    if (!labels || !bgr || labels % 4 != 0 || sums % 4 != 0) return p;
+    if (n_labels < 1 || n_labels > cluster_means_max_labels(plane_bytes, batch)) return p;
+    if ((uint64_t)rows * (uint64_t)cols * 255u > 0xffffffffull) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    p.words = (size_t)batch * (size_t)n_labels * 4;
+    if (ranges_overlap(labels, 4 * px, bgr, 3 * px)) return p;
+    if (sums && (ranges_overlap(sums, 4 * p.words, labels, 4 * px) || ranges_overlap(sums, 4 * p.words, bgr, 3 * px))) return p;
+    p.status = kOk;
+    p.n = (uint32_t)rows * (uint32_t)cols;
+    p.tiles_x = ((uint32_t)cols + kContTile - 1) / kContTile;
+    p.tiles_y = ((uint32_t)rows + kContTile - 1) / kContTile;
+    p.sum_grid = p.tiles_x * p.tiles_y;
+    p.px_x = (p.n + 255) / 256;
+    const size_t blocks = (p.words + 255) / 256;
+    p.clear_grid = blocks > 4096 ? 4096u : (unsigned)blocks;
     return p;
 }
 

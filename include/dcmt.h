@@ -308,6 +308,58 @@ int dcmt_slic_connectivity_dev(dcmt_ctx *ctx, const int32_t *d_labels, int rows,
 int dcmt_slic_connectivity(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, int rows, int cols, int n_centers,
                            int32_t *out, size_t out_row_stride, int32_t *count /* or NULL */);
 
+/* Slic::display_contours (DC_lidar_camera/slic.cpp:337-384; slic.display_contours(image, CV_RGB(200,0,0)) at main_lc.cpp:214, the
+ * first image the reference shows) and Slic::colour_with_cluster_means (slic.cpp:392-433; its call at main_lc.cpp:249 is commented
+ * out) on the device: the two pixel renderings of a label plane.  Slic::display_center_grid (cv::circle) is not reproduced.
+ * A frame is labels[rows][cols] int32 row-major (the reference's clusters[col][row]); x is the column, y the row.
+ *
+ * CONTOURS.  The reference scans x outer, y inner and keeps a matrix istaken; a pixel is TAKEN iff at least 2 of its 8 neighbours
+ * are inside the frame, have a different label and are not taken yet (:357-372).  Any int32 compares, -1 and values >= n_centers
+ * included (:363 uses != and nothing else).  Its sequential, order-dependent statements, as the definition that gives the same
+ * bits.  The scan has visited four of the neighbours, the EARLIER ones (x-1, y-1), (x-1, y), (x-1, y+1), (x, y-1); the LATER ones
+ * (x+1, y-1), (x+1, y), (x+1, y+1), (x, y+1) are never taken yet.  Per pixel:
+ *   A      the number of in-frame later neighbours with a different label
+ *   c      A + the number of in-frame pixels among (x-1, y-1), (x-1, y), (x-1, y+1) with a different label that are NOT taken
+ *   taken  where (x, y-1) is outside the frame or has the same label: c >= 2.  Otherwise: c >= 2 -> taken; c == 0 -> not taken;
+ *          c == 1 -> !taken(x, y-1).
+ * So taken(x, y-1) -> taken(x, y) is a constant or a negation, never the identity: inside a column a maximal run of c == 1 pixels
+ * under differing upper pixels alternates, taken(y) = taken(base) XOR ((y - base) & 1) with base the pixel just above the run, and
+ * column x needs three bits per pixel of column x - 1.  Taken pixels of d_bgr get the bytes colour_bgr[0..2] = B, G, R
+ * ((uchar)colour[0..2], :380-381; CV_RGB(200,0,0) is {0, 0, 200}); no other byte of d_bgr is written.  d_mask gets 255 where taken, 0
+ * elsewhere.  At least one of d_bgr, d_mask must be given; colour_bgr is a HOST pointer, read before the call returns.
+ *
+ * CLUSTER MEANS.  For each label k in [0, n_labels): the sums of B, G and R over the frame's pixels with label k and their count (on the
+ * raw k-means labels the count is what the reference's center_counts[k] holds, :142-163); every such pixel becomes sum / count per
+ * channel.  The reference divides doubles and converts to uchar implicitly, with no saturate_cast: for a quotient in [0, 255] that
+ * is truncation, so this is INTEGER DIVISION.  A pixel whose label is outside [0, n_labels) indexes `colours` out of bounds in the
+ * reference (undefined behaviour): here it keeps its bytes and is not counted.  d_sums, [batch][n_labels][4] = sumB, sumG, sumR,
+ * count as 32-bit words (labels that own no pixel: zeros), or NULL.  In place on d_bgr: the sums are complete before a byte is written.
+ *
+ * Both: integer arithmetic throughout, so the result is bit-exact and does not depend on the batch size, the frame's position in
+ * the batch, the launch geometry or the run.  d_labels 4-byte aligned, d_sums 4-byte aligned.  DCMT_E_INVALID: null inputs (labels;
+ * both outputs of the contours; the colour; d_bgr of the means), sizes beyond the context's limits, misaligned pointers, ANY overlap
+ * among d_labels, d_bgr, d_mask / d_sums, and
+ *   contours  rows > 262144 (the column pass keeps one 64-bit mask per 64 rows of a column in 32 KiB of LDS)
+ *   means     n_labels < 1; batch * n_labels * 16 bytes more than ONE of the two scratch planes holds, that is
+ *             n_labels > (max_rows * max_cols * max_batch) / (4 * batch) of dcmt_create's arguments -- with d_sums given as well,
+ *             so that a call's validity does not depend on it; rows * cols * 255 >= 2^32 (the sums are 32-bit)
+ * Stream-ordered, never synchronise, never allocate, three launches each whatever the data.  Scratch: the two planes dcmt_create
+ * allocates (the ones dcmt_slic_connectivity_dev borrows, which every completion call rewrites before it reads them): 1 B per pixel
+ * of code bytes in one and 1 B per pixel of taken bytes in the other for the contours, the sums in the first where d_sums is NULL
+ * for the means.  Of the context's carried state they touch none.  Same standing behind other *_dev calls as
+ * dcmt_slic_connectivity_dev. */
+int dcmt_slic_contours_dev(dcmt_ctx *ctx, const int32_t *d_labels, int rows, int cols, int batch,
+                           uint8_t *d_bgr /* [batch][rows][cols][3], painted in place, or NULL */, const uint8_t colour_bgr[3],
+                           uint8_t *d_mask /* [batch][rows][cols], 255 taken / 0 not, or NULL */, void *stream);
+int dcmt_slic_cluster_means_dev(dcmt_ctx *ctx, const int32_t *d_labels, int rows, int cols, int batch, int n_labels,
+                                uint8_t *d_bgr /* [batch][rows][cols][3], in place */,
+                                int32_t *d_sums /* [batch][n_labels][4] = sumB, sumG, sumR, count; or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES).  bgr (or NULL) is painted in place, mask (or NULL) written. */
+int dcmt_slic_contours(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, int rows, int cols, uint8_t *bgr, size_t bgr_row_stride,
+                       const uint8_t colour_bgr[3], uint8_t *mask, size_t mask_row_stride);
+int dcmt_slic_cluster_means(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, int rows, int cols, int n_labels, uint8_t *bgr,
+                            size_t bgr_row_stride, int32_t *sums /* [n_labels][4] or NULL */);
+
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 
 /* What DC_stereo_lidar/main_sl.cpp does with the dense depth (:1165-1246): depth -> disparity (get_initial_disparity

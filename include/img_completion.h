@@ -190,6 +190,42 @@ inline int slic_enforce_connectivity(std::vector<std::vector<int> >& clusters, i
     return (int)count;
 }
 
+// `clusters` ([col][row], as Slic::clusters) as the row-major int32 plane the C ABI takes, checked against the image it belongs to
+inline std::vector<int32_t> clusters_row_major(const std::vector<std::vector<int> >& clusters, const cv::Mat& image, const char* what)
+{
+    const int rows = image.rows, cols = image.cols;
+    if (image.type() != CV_8UC3 || rows < 1 || cols < 1) throw std::runtime_error(std::string(what) + ": image must be CV_8UC3");
+    if ((int)clusters.size() != cols) throw std::runtime_error(std::string(what) + ": clusters does not have the image's size");
+    std::vector<int32_t> lab((size_t)rows * cols);
+    for (int j = 0; j < cols; ++j) {
+        if ((int)clusters[j].size() != rows) throw std::runtime_error(std::string(what) + ": clusters does not have the image's size");
+        for (int i = 0; i < rows; ++i) lab[(size_t)i * cols + j] = clusters[j][i];
+    }
+    return lab;
+}
+
+// slic.display_contours(image, CV_RGB(200,0,0)) (DC_lidar_camera/main_lc.cpp:214, slic.cpp:337-384) as dcmt.h states it
+// (dcmt_slic_contours): the contour pixels of `clusters` painted into `image` (CV_8UC3, in place) with (uchar)colour[0..2] = B, G, R.
+// `colour` is anything indexable: cv::Scalar, cv::Vec3b, an array.
+template <typename Colour>
+inline void slic_display_contours(const std::vector<std::vector<int> >& clusters, cv::Mat& image, const Colour& colour)
+{
+    const std::vector<int32_t> lab = clusters_row_major(clusters, image, "slic_display_contours");
+    const uint8_t bgr[3] = {(uint8_t)colour[0], (uint8_t)colour[1], (uint8_t)colour[2]};
+    raise(dcmt_slic_contours(thread_ctx().get(image.rows, image.cols), lab.data(), sizeof(int32_t) * (size_t)image.cols, image.rows, image.cols,
+                             image.ptr<unsigned char>(), image.step[0], bgr, nullptr, 0), "slic_display_contours");
+}
+
+// slic.colour_with_cluster_means(image) (slic.cpp:392-433) as dcmt.h states it (dcmt_slic_cluster_means): every pixel of `image`
+// (CV_8UC3, in place) becomes the mean colour of its superpixel.  n_labels = slic.centers.size() (what slic_labels returns), or the
+// count slic_enforce_connectivity returns for clusters that went through it; a label outside [0, n_labels) keeps its pixels.
+inline void slic_colour_with_cluster_means(const std::vector<std::vector<int> >& clusters, cv::Mat& image, int n_labels)
+{
+    const std::vector<int32_t> lab = clusters_row_major(clusters, image, "slic_colour_with_cluster_means");
+    raise(dcmt_slic_cluster_means(thread_ctx().get(image.rows, image.cols), lab.data(), sizeof(int32_t) * (size_t)image.cols, image.rows, image.cols,
+                                  n_labels, image.ptr<unsigned char>(), image.step[0], nullptr), "slic_colour_with_cluster_means");
+}
+
 // DC_stereo_lidar/main_sl.cpp:1165-1246: get_initial_disparity + calculateMeasuementDerivatives + optimize_IG +
 // retrieve_optimized_depth on the dense depth (CV_32FC1) and the two grey images (CV_8UC1).
 inline void stereo_refine(const cv::Mat& dense_depth, const cv::Mat& left_gray, const cv::Mat& right_gray, cv::Mat& optimized_depth)
