@@ -19,6 +19,7 @@ STAGE_INVERT, STAGE_DILATE_K, STAGE_CLOSE5, STAGE_FILL7, STAGE_EXTEND = 2, 3, 4,
 FLAG_FORCE_STAGED = 1
 FLAG_FORCE_FUSED = 2
 FLAG_NORMALIZE = 4
+FLAG_NO_EXTRAPOLATE = 8
 STAGE_FILL31, STAGE_FILLLOOP, STAGE_MEDIAN5, STAGE_BLUR, STAGE_FINAL = 7, 8, 9, 10, 11
 EVAL_GT, EVAL_BOTH = 0, 1
 

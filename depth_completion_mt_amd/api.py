@@ -100,9 +100,12 @@ def _frame_f32(a) -> np.ndarray:
 def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int = L.STAGE_FINAL,
                 max_fill_iters: int = 64, spec_fill_iters: int = 1, verbose: bool = False,
                 max_depth: float = 100.0, valid_thresh: float = 0.1, force_staged: bool = False, force_fused: bool = False,
-                normalize=None) -> L.Params:
+                normalize=None, extrapolate: bool = True) -> L.Params:
     """normalize=(lo, hi): min-max normalise every frame first, as cv::normalize(src, dst, lo, hi, NORM_MINMAX)
-    in front of the path does in the stereo-lidar executables (SL/main_sl.cpp:370, :523)."""
+    in front of the path does in the stereo-lidar executables (SL/main_sl.cpp:370, :523).
+    extrapolate=False: DCMT_FLAG_NO_EXTRAPOLATE -- no column extension and no large fills (stages 6..8 do not exist: stop_after 6..8
+    is refused); the median, the blur and the final invert run on the plane the 7x7 fill left, so nothing is invented far from a
+    measurement (include/dcmt.h has the definition)."""
     p = L.Params()
     L.lib().dcmt_default_params(ctypes.byref(p))
     if isinstance(k0, str):
@@ -127,6 +130,8 @@ def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int =
     if normalize is not None:
         p.flags |= L.FLAG_NORMALIZE
         p.norm_lo, p.norm_hi = float(normalize[0]), float(normalize[1])
+    if not extrapolate:
+        p.flags |= L.FLAG_NO_EXTRAPOLATE
     return p
 
 
@@ -1033,7 +1038,8 @@ def _ctx_for(rows: int, cols: int, batch: int, device: int = 0) -> Context:
 
 def img_completion(sparse_r_img: np.ndarray, extr: bool = False, blur_type: str = "gaussian", **kw) -> np.ndarray:
     """Drop-in for the reference's img_completion (LO/img_completion.cpp:17): returns dense_r_img.
-    `extr` is accepted and ignored, as in the reference (:19, never read)."""
+    `extr` is accepted and ignored, as in the reference (:19, never read); the cascade without its extrapolation is the keyword
+    `extrapolate=False` (make_params)."""
     a = np.asarray(sparse_r_img, dtype=np.float32)
     b = 1 if a.ndim == 2 else a.shape[0]
     return _ctx_for(a.shape[-2], a.shape[-1], b).complete(a, make_params(blur_type=blur_type, **kw))

@@ -1,7 +1,7 @@
 // dcmt.hip -- implementation of the C ABI in include/dcmt.h on gfx950 (MI355X).
 //
 // Host side of the hot path: context (device scratch owned per GPU) and launch sequencing of
-// the kernels in dcmt_kernels_v1.h / dcmt_kernels_fused.h.  No PyTorch, no OpenCV, no CPU fallback: if there is no gfx950
+// the kernels in dcmt_kernels_v1.h / dcmt_kernels_fused.h (and dcmt_kernels_local.h: the cascade without its extrapolation).  No PyTorch, no OpenCV, no CPU fallback: if there is no gfx950
 // device every entry point fails with DCMT_E_NO_DEVICE / DCMT_E_HIP.
 //
 // The rest of the ABI is in two more translation units over dcmt_ctx.h (the context and the checks every entry point starts with):
@@ -29,6 +29,7 @@
 #include "dcmt_kernels_pair.h"
 #include "dcmt_kernels_fp_q16.h"
 #include "dcmt_kernels_tail.h"
+#include "dcmt_kernels_local.h"
 #include "dcmt_kernels_slic.h"
 #include "dcmt_kernels_eval.h"
 #include "dcmt_kernels_color.h"
@@ -55,7 +56,9 @@ static_assert(plan::kStageNormalize == DCMT_STAGE_NORMALIZE && plan::kStageClose
               plan::kStageExtend == DCMT_STAGE_EXTEND && plan::kStageMedian5 == DCMT_STAGE_MEDIAN5 && plan::kStageBlur == DCMT_STAGE_BLUR &&
               plan::kStageFinal == DCMT_STAGE_FINAL, "dcmt_stage");
 static_assert(plan::kFlagForceStaged == DCMT_FLAG_FORCE_STAGED && plan::kFlagForceFused == DCMT_FLAG_FORCE_FUSED &&
-              plan::kFlagNormalize == DCMT_FLAG_NORMALIZE, "DCMT_FLAG_*");
+              plan::kFlagNormalize == DCMT_FLAG_NORMALIZE && plan::kFlagNoExtrapolate == DCMT_FLAG_NO_EXTRAPOLATE, "DCMT_FLAG_*");
+static_assert(plan::local_vw(K0_AS_COMPILED) == LocalS<K0_AS_COMPILED>::VW && plan::local_vw(K0_DIAMOND) == LocalS<K0_DIAMOND>::VW &&
+              plan::kLocalReach == LocalS<K0_AS_COMPILED>::REACH && plan::kLocalReach == LocalS<K0_DIAMOND>::REACH, "LocalS");
 static_assert(plan::q16_params_ok(100.0f, 0.1f) && Q16::params_ok(100.0f, 0.1f) && !plan::q16_params_ok(80.0f, 0.1f) && !Q16::params_ok(80.0f, 0.1f) &&
               !plan::q16_params_ok(100.0f, 0.2f) && !Q16::params_ok(100.0f, 0.2f), "Q16::params_ok");
 static_assert(sizeof(plan::Plan::path) == sizeof(dcmt_ctx::last_path), "dcmt_last_path");
@@ -164,6 +167,7 @@ void begin_call(dcmt_ctx* ctx, hipStream_t st, int batch, const char* path)
     ctx->last_batch = batch;
     ctx->last_apps_launched = 0;
     ctx->last_has_loop = 0;
+    ctx->last_no_extrapolate = 0;
     std::memcpy(ctx->last_path, path, sizeof ctx->last_path);
 }
 
@@ -318,6 +322,7 @@ int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, cons
 float* out_plane(const dcmt_ctx* ctx, plan::Out o, float* dst) { return o == plan::Out::DST ? dst : o == plan::Out::X5 ? ctx->x5 : ctx->pp[0]; }
 
 int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, int blur, hipStream_t st, bool sync_loop);
+int launch_local(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, int blur, hipStream_t st);
 
 // the cascade's literals of the bilateral finish (img_completion.cpp:174); fixed: dcmt_params has no room for them
 constexpr float kBilateralSigmaColor = 1.5f, kBilateralSigmaSpace = 2.0f;
@@ -376,6 +381,7 @@ int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_p
     if (pl.needs_colstat) DCMT_TRY(ctx->colstat.reserve(ctx, 2 * (size_t)ctx->max_cols * ((ctx->max_rows + FTH_FEW - 1) / FTH_FEW) * ctx->max_batch));
     if (pl.needs_bbox) DCMT_TRY(ensure_bbox(ctx, (size_t)batch * fr.n_labels * 2, st));
     begin_call(ctx, st, batch, pl.path);
+    ctx->last_no_extrapolate = pl.no_extrapolate;
     if (ctx->timing && ctx->tev[0]) (void)hipEventRecord(ctx->tev[0], st);
 
     const size_t n_px = (size_t)batch * rows * cols;
@@ -431,6 +437,7 @@ int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_p
         q.blur = blur;
         return launch_streaming(ctx, pl, fr, &q, st, sync_loop);
     }
+    if (pl.route == plan::Route::LOCAL) return launch_local(ctx, pl, fr, p, blur, st);
     if (pl.u16_convert) {   // the staged kernels take f32: convert into scratch that nothing writes before they have read it
         hipLaunchKernelGGL(k_u16_to_f32, dim3(1024), dim3(256), 0, st, fr.src16, ctx->pp[0], n_px, fr.in_scale);
         d_src = ctx->pp[0];
@@ -455,6 +462,15 @@ int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_p
     DCMT_HIP(ctx, hipGetLastError());
     if (stop <= DCMT_STAGE_FILL7) {
         if (out != d_dst) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, sizeof(float) * n_px, hipMemcpyDeviceToDevice, st));
+        return DCMT_OK;
+    }
+    if (pl.no_extrapolate) {
+        // H9..H11 on X5 itself: with no application launched k_post_v1 reads its first plane and never looks at the counters
+        with_tile_h(pl.few, [&](auto th) {
+            hipLaunchKernelGGL((k_post_v1<decltype(th)::value, TW>), grid, block, 0, st, ctx->x5, ctx->x5, d_dst, ctx->counters, 0,
+                               rows, cols, p->max_depth, p->valid_thresh, blur, stop);
+        });
+        DCMT_HIP(ctx, hipGetLastError());
         return DCMT_OK;
     }
 
@@ -532,6 +548,29 @@ int colorize_dev(dcmt_ctx* ctx, const float* d_src, int rows, int cols, int batc
     return DCMT_OK;
 }
 
+// Route::LOCAL of a plan (DCMT_FLAG_NO_EXTRAPOLATE): k_local from the frames -- or from X4 in pp[0], which the label stage has left
+// there -- to the plan's output plane, and the copy of an overlapping call.  blur: the effective one.
+int launch_local(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_params* p, int blur, hipStream_t st)
+{
+    const int rows = fr.rows, cols = fr.cols, batch = fr.batch;
+    const bool labeled = fr.labels != nullptr;
+    const float* cf = pl.norm && !labeled ? ctx->norm_coef : nullptr;
+    const void* in = labeled ? (const void*)ctx->pp[0] : fr.src16 ? (const void*)fr.src16 : (const void*)fr.src;
+    const int input = labeled ? LOCAL_START4 : fr.src16 ? LOCAL_U16 : cf ? LOCAL_NORM : LOCAL_F32;
+    const float scale = fr.src16 ? fr.in_scale : 1.0f;
+    float* out = out_plane(ctx, pl.out, fr.dst);
+    // bit 0: the Gaussian runs, bit 1: the final invert runs (stop_after = MEDIAN5 is PostPipe<10, false>: dcmt_kernels_local.h)
+    const int variant = (blur == DCMT_BLUR_GAUSSIAN && p->stop_after >= DCMT_STAGE_BLUR ? 1 : 0) | (p->stop_after == DCMT_STAGE_FINAL ? 2 : 0);
+    with_k0(pl.k0kind, [&](auto kind) { with_value<0, 1, 2, 3>(input, [&](auto in_) { with_value<0, 1, 2, 3>(variant, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        hipLaunchKernelGGL((k_local<decltype(kind)::value, decltype(in_)::value, (V & 2) ? 11 : 10, (V & 1) != 0>), dim3(pl.local_grid), dim3(256), 0, st,
+                           in, out, rows, cols, pl.local_strips, pl.local_bands, batch, pl.xcd_map, p->max_depth, p->valid_thresh, scale, cf);
+    }); }); });
+    DCMT_HIP(ctx, hipGetLastError());
+    if (out != fr.dst) DCMT_HIP(ctx, hipMemcpyAsync(fr.dst, out, sizeof(float) * (size_t)batch * rows * cols, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
+}
+
 }  // namespace
 
 namespace dcmt {
@@ -547,6 +586,8 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
     if (p->spec_fill_iters < 0 || p->spec_fill_iters > kMaxIters) return DCMT_E_INVALID;
     const bool norm = (p->flags & DCMT_FLAG_NORMALIZE) != 0;
     if (p->stop_after < (norm ? DCMT_STAGE_NORMALIZE : DCMT_STAGE_INVERT) || p->stop_after > DCMT_STAGE_FINAL) return DCMT_E_INVALID;
+    // stages 6..8 do not exist without the extrapolation (up to FILL7 the flag is ignored)
+    if ((p->flags & DCMT_FLAG_NO_EXTRAPOLATE) && p->stop_after >= DCMT_STAGE_EXTEND && p->stop_after <= DCMT_STAGE_FILLLOOP) return DCMT_E_UNSUPPORTED;
     if (norm && !(finite_bits(p->norm_lo) && finite_bits(p->norm_hi))) return DCMT_E_INVALID;
     if (k0_bits(p->k0) == 0) return DCMT_E_INVALID;
     return DCMT_OK;
@@ -591,7 +632,7 @@ const char* dcmt_strerror(int s)
     switch (s) {
         case DCMT_OK: return "ok";
         case DCMT_E_INVALID: return "invalid argument";
-        case DCMT_E_UNSUPPORTED: return "unsupported (bilateral blur: the reference's in-place cv::bilateralFilter call throws)";
+        case DCMT_E_UNSUPPORTED: return "unsupported (bilateral blur: the reference's in-place cv::bilateralFilter call throws; or stop_after 6..8 without the extrapolation)";
         case DCMT_E_NOMEM: return "out of memory";
         case DCMT_E_HIP: return "HIP runtime error";
         case DCMT_E_NOT_CONVERGED: return "hole-closure loop hit max_fill_iters with holes left";
@@ -903,6 +944,7 @@ int dcmt_last_fill_iters(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
+    if (ctx->last_no_extrapolate) { std::fill(out, out + n, 0); return DCMT_OK; }      // no loop ran
     if (!ctx->last_has_loop) return DCMT_E_INVALID;
     int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
     if (rc != DCMT_OK) return rc;
@@ -920,6 +962,7 @@ int dcmt_last_holes_after_extend(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
+    if (ctx->last_no_extrapolate) { std::fill(out, out + n, 0); return DCMT_OK; }      // no extension ran
     int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
     if (rc != DCMT_OK) return rc;
     for (int f = 0; f < n; ++f) out[f] = ctx->h_counters[(size_t)f * kCntStride];

@@ -71,6 +71,7 @@ struct dcmt_ctx {
     int last_batch = 0;
     int last_apps_launched = 0;       // loop applications (app >= 1) enqueued
     int last_has_loop = 0;            // the call went at least through H8
+    int last_no_extrapolate = 0;      // the call ran without H6..H8 (DCMT_FLAG_NO_EXTRAPOLATE): dcmt_last_fill_iters and dcmt_last_holes_after_extend report zeros
     int last_hip_error = 0;
     char last_path[160] = "";         // dcmt_last_path: the kernels the last call dispatched
     int timing = 0;                   // dcmt_set_kernel_timing: events around the kernel groups of the streaming path

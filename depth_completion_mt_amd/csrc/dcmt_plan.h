@@ -34,6 +34,7 @@ struct Knobs {
     int min_fused_batch = 3;          // smaller batches use the staged kernels (measured crossover with both streaming kernels in row bands,
                                       // tools/batch_sweep.py: 1 frame 20.6 k staged / 17.1 k streaming, 2 frames 34.7 k / 34.0 k, 3 frames 39.5 k / 50.4 k,
                                       // 4 frames 42.6 k / 65.7 k, 8 frames 52 k / 124 k frames/s); DCMT_MIN_FUSED_BATCH
+    int local_bands = 0;              // row bands per strip in k_local (0 = by batch size); DCMT_LOCAL_BANDS
 };
 
 // how a variable's text becomes the member: 'i' its integer value, '1' whether it starts with '1', 'p' whether it is set at all
@@ -54,6 +55,7 @@ constexpr KnobEnv kKnobEnv[] = {
     {"DCMT_LABEL_GROUP", &Knobs::label_group, 'i'},
     {"DCMT_LABEL_PAIRS", &Knobs::label_pairs, 'i'},
     {"DCMT_MIN_FUSED_BATCH", &Knobs::min_fused_batch, 'i'},
+    {"DCMT_LOCAL_BANDS", &Knobs::local_bands, 'i'},
 };
 
 inline Knobs knobs_from_env()
@@ -76,6 +78,12 @@ constexpr int kK0AsCompiled = 0, kK0Diamond = 1;
 constexpr int pre_p_vw(int k0kind, bool start4) { return start4 ? 120 : k0kind == kK0AsCompiled ? 108 : 104; }
 constexpr int pre_s_vw(int k0kind, bool wide) { return k0kind == kK0AsCompiled ? (wide ? 44 : 48) : (wide ? 40 : 46); }
 constexpr int kFpQVW = 120, kPostSVW = 56, kFillSVW = 34;
+constexpr int local_vw(int k0kind) { return k0kind == kK0AsCompiled ? 40 : 38; }   // LocalS::VW (k_local, dcmt_kernels_local.h)
+constexpr int kLocalReach = 13;      // LocalS::REACH: input rows an output row of k_local needs above and below it
+// k_local runs in row bands up to about kLocalBandWaves waves, in bands of at least kLocalMinBandRows rows (a band streams up to
+// 20 + 14 rows beside its own) and at most kLocalMaxBands of them (measured, tools/time_no_extrapolate.py --bands, 352x1216: one
+// frame 1 / 4 / 11 / 22 / 32 / 44 bands 146 / 47 / 26 / 20 / 19 / 20 us, eight frames 1 / 4 / 9 / 11 / 32 bands 148 / 48 / 46 / 40 / 60 us)
+constexpr int kLocalBandWaves = 2560, kLocalMinBandRows = 16, kLocalMaxBands = 32;
 constexpr int kMaxBands = 8;         // row bands per strip of k_pre_p (table slots per frame)
 constexpr int kLabelGroupMax = 4;    // labels one wave of k_label_stage_p may be given
 constexpr int kPreBandWaves = 2560;  // k_pre_p runs in row bands up to about this many waves (also sizes the band table in dcmt_create)
@@ -84,7 +92,7 @@ constexpr int kFpSOneBandWaves = 2048, kFpSBandWaves = 3072;   // k_fp_s: one ba
 constexpr bool q16_params_ok(float max_depth, float thr) { return max_depth == 100.0f && thr == 0.1f; }
 // dcmt.h: dcmt_stage and the DCMT_FLAG_* bits
 constexpr int kStageNormalize = 1, kStageClose5 = 4, kStageFill7 = 5, kStageExtend = 6, kStageMedian5 = 9, kStageBlur = 10, kStageFinal = 11;
-constexpr int kFlagForceStaged = 1, kFlagForceFused = 2, kFlagNormalize = 4;
+constexpr int kFlagForceStaged = 1, kFlagForceFused = 2, kFlagNormalize = 4, kFlagNoExtrapolate = 8;
 // dcmt_last_path of a call whose result went to scratch first and was then copied to its overlapping dst
 constexpr const char* kPathCopy = " + copy to dst";
 
@@ -107,7 +115,7 @@ struct Call {
     bool q16_allowed = false;                // a 16-bit attempt is allowed now (the context's skip state, dcmt.hip: q16_allowed_now)
 };
 
-enum class Route { NORMALIZE_ONLY, STAGED, LABEL_PROBE, STREAMING };
+enum class Route { NORMALIZE_ONLY, STAGED, LABEL_PROBE, STREAMING, LOCAL };     // LOCAL: k_local (DCMT_FLAG_NO_EXTRAPOLATE)
 enum class Out { DST, X5, PP0 };             // where the kernel that reads the frames writes what is (so far) the call's result
 
 struct Plan {
@@ -137,6 +145,11 @@ struct Plan {
     // the bilateral finish: everything above is the plan of the same call with stop_after = MEDIAN5 and the context's median plane as
     // its dst; k_bilateral5 then reads that plane and writes dst, with the final invert for stop_after = FINAL
     bool bilateral = false, bilateral_invert = false;
+    // DCMT_FLAG_NO_EXTRAPOLATE from stop_after = MEDIAN5 on: H6..H8 do not run.  Route::LOCAL: k_local, every strip in local_bands row
+    // bands; Route::STAGED: k_pre*_v1 into X5, k_post_v1 from there
+    bool no_extrapolate = false;
+    int local_bands = 1, local_strips = 0;
+    unsigned local_grid = 0;
     char path[160] = "";             // dcmt_last_path
 };
 
@@ -159,9 +172,20 @@ inline void path_append(char (&path)[160], const char* s)
 
 // Which kernels run.  The streaming kernels give one wave a whole column strip: a handful of frames cannot fill the GPU
 // with them, there the staged tile kernels (hundreds of small workgroups per frame) win
+// DCMT_FLAG_NO_EXTRAPOLATE takes effect from stop_after = MEDIAN5 on (up to FILL7 the call is the same with and without it; the
+// stages between do not exist with it and are refused before a call is planned)
+inline bool no_extrapolate(const Call& c) { return (c.flags & kFlagNoExtrapolate) && c.stop_after >= kStageMedian5; }
+
 inline Route route_of(const Knobs& k, const Call& c)
 {
     if ((c.flags & kFlagNormalize) && c.stop_after == kStageNormalize) return Route::NORMALIZE_ONLY;
+    if (no_extrapolate(c)) {
+        // k_local wherever the streaming kernels' other conditions hold, at every batch size: its row bands need no table, so a
+        // single frame fills the GPU with them
+        const bool local = !(c.flags & kFlagForceStaged) && c.k0kind >= 0 && c.rows >= 8 && c.cols >= 8 &&
+                           (c.input != Input::LABELED || c.n_labels > 0);
+        return local ? Route::LOCAL : Route::STAGED;
+    }
     const bool big_enough = c.batch >= k.min_fused_batch || (c.flags & kFlagForceFused);
     const bool streaming = !(c.flags & kFlagForceStaged) && big_enough && c.k0kind >= 0 && c.rows >= 8 && c.cols >= 8;
     if (!streaming) return Route::STAGED;
@@ -242,6 +266,32 @@ inline Plan plan_call(const Knobs& k, const Call& c)
             return p;
         }
         overlap = false;         // the streaming kernels read X4 in pp[0]
+    }
+
+    if (p.route == Route::LOCAL) {
+        // One kernel from the frames (uint16 ingest and N1 applied while it loads; labeled: from X4 in pp[0]) to dst.  It writes
+        // dst while other waves still read their halo rows and columns from the frames: an overlapping call writes pp[0] -- free,
+        // because no fill runs -- and one copy follows (labeled: the kernel reads X4, not the frames, and needs none)
+        p.no_extrapolate = true;
+        p.out = overlap ? Out::PP0 : Out::DST;
+        const int vw = local_vw(c.k0kind);
+        p.local_strips = (cols + vw - 1) / vw;
+        // row bands, from the batch size: a band recomputes kLocalReach rows of halo above and below its own
+        const long long w1 = (long long)batch * p.local_strips;
+        int bands = k.local_bands > 0 ? k.local_bands : (w1 >= kLocalBandWaves ? 1 : (int)((kLocalBandWaves + w1 - 1) / w1));
+        if (k.local_bands <= 0) {
+            if (bands > rows / kLocalMinBandRows) bands = rows / kLocalMinBandRows;
+            if (bands > kLocalMaxBands) bands = kLocalMaxBands;
+        }
+        if (bands > rows) bands = rows;
+        if (bands < 1) bands = 1;
+        p.local_bands = bands;
+        p.local_grid = wave_grid(p.local_strips * bands, batch, p.xcd_map);
+        if (labeled) path_append(p.path, "k_label_bbox + k_label_stage + ");
+        path_append(p.path, labeled ? "k_local<START4>" : u16 ? "k_local<U16>" : p.norm ? "k_local<NORM>" : "k_local");
+        if (bands > 1) path_append(p.path, " (row bands)");
+        if (p.out != Out::DST) path_append(p.path, kPathCopy);
+        return p;
     }
 
     if (p.route == Route::STREAMING) {
@@ -333,7 +383,9 @@ inline Plan plan_call(const Knobs& k, const Call& c)
     // not run; the uint16 input converted into pp[0] never overlaps dst).
     p.out = stop <= kStageFill7 && overlap ? (stop == kStageFill7 ? Out::X5 : Out::PP0) : Out::DST;
     path_append(p.path, labeled ? "k_pre_labeled_v1" : "k_pre_v1");
-    path_append(p.path, " + k_fill31_v1 + k_post_v1 (staged tile kernels)");
+    // (no extrapolation: k_post_v1 reads X5, behind the only kernel that reads the frames -- an overlapping dst needs no copy)
+    p.no_extrapolate = no_extrapolate(c);
+    path_append(p.path, p.no_extrapolate ? " + k_post_v1 (staged tile kernels)" : " + k_fill31_v1 + k_post_v1 (staged tile kernels)");
     if (p.out != Out::DST) path_append(p.path, kPathCopy);
     return p;
 }

@@ -51,7 +51,10 @@
  * an overlapping call writes the result to context scratch and copies it to d_dst: one device-to-device copy more, and
  * dcmt_last_path ends in "+ copy to dst".  The 16-bit attempt is not made when d_dst overlaps d_src (f32 or uint16): its rerun would
  * read d_src again after d_dst was written.  The labeled entry point's attempt reads the label stage's output in scratch, so
- * overlap does not stop it there.  d_labels must not overlap d_dst.  The host entry points stage through device buffers of their
+ * overlap does not stop it there.  All of this holds with DCMT_FLAG_NO_EXTRAPOLATE: there the one kernel that reads d_src
+ * (k_local) would write d_dst while other waves still read their halos, so an overlapping call writes to scratch that is free
+ * because no fill runs, one copy follows and dcmt_last_path ends in "+ copy to dst"; the labeled entry point's kernel reads the
+ * label stage's output and needs no copy, nor do the staged kernels or the bilateral finish.  d_labels must not overlap d_dst.  The host entry points stage through device buffers of their
  * own: src may be dst there too.
  * Empty pixels: the sign of a zero in an output pixel that stays empty (an all-empty frame) is +0.0 where the input held +0.0; an
  * input -0.0 counts as 0.0 (empty) and may come out as either zero.
@@ -73,7 +76,8 @@ typedef struct dcmt_ctx dcmt_ctx;
 typedef enum {
     DCMT_OK              = 0,
     DCMT_E_INVALID       = -1, /* bad argument (null pointer, size beyond the ctx limits, empty k0) */
-    DCMT_E_UNSUPPORTED   = -2, /* blur == DCMT_BLUR_BILATERAL: the reference's call throws too (img_completion.cpp:174) */
+    DCMT_E_UNSUPPORTED   = -2, /* blur == DCMT_BLUR_BILATERAL: the reference's call throws too (img_completion.cpp:174);
+                                  stop_after = 6..8 with DCMT_FLAG_NO_EXTRAPOLATE: those stages do not exist then */
     DCMT_E_NOMEM         = -3, /* device or host allocation failed */
     DCMT_E_HIP           = -4, /* a HIP runtime call failed; dcmt_last_hip_error() has the code */
     DCMT_E_NOT_CONVERGED = -5, /* the hole-closure loop (img_completion.cpp:146-166) hit max_fill_iters with holes left */
@@ -150,6 +154,33 @@ typedef struct {
  * (dcmt_complete_u16_dev returns DCMT_E_UNSUPPORTED: the reference never combines the two ingests).
  * A frame whose values are all equal normalises to min(norm_lo, norm_hi) everywhere, as in OpenCV. */
 #define DCMT_FLAG_NORMALIZE 4
+
+/* The cascade without its extrapolation (an opt-in of this project).  The reference's signature has `const bool& extr` and never
+ * reads it: the column extension and both large fills (img_completion.cpp:103-166, img_completion_lc.cpp:119-180) run under
+ * `int densify = true;`.  Without the flag nothing changes, and the drop-in interfaces' `extr` argument stays ignored, as the
+ * reference ignores it.  With the flag stages 6..8 do not exist: with X5 the plane after DCMT_STAGE_FILL7 exactly as without the
+ * flag (the labeled entry point's label-masked stage, the uint16 ingest, DCMT_FLAG_NORMALIZE, either k0 preset or a custom k0
+ * included), thr = valid_thresh and "valid" x >= thr,
+ *     X9  = medianBlur5(X5)                                  (:170, replicated border)
+ *     X10 = DCMT_BLUR_GAUSSIAN:        X9 >= thr ? GaussianBlur5(X9) : X9   (:178-188, reflect-101; forced by the labeled entry points)
+ *           DCMT_BLUR_NONE:            X9
+ *           DCMT_BLUR_BILATERAL_CLONE: bilateral5(X9) over the whole plane, as dcmt_bilateral5_dev states it
+ *           DCMT_BLUR_BILATERAL:       DCMT_E_UNSUPPORTED, as always
+ *     X11 = X10 >= thr ? max_depth - X10 : X10               (:191-202)
+ * A pixel whose median is valid but whose blurred value falls below thr is not inverted: those are the reference's statements.
+ * stop_after <= DCMT_STAGE_FILL7: the call without the flag, bit for bit (the flag is ignored).  DCMT_STAGE_EXTEND, _FILL31 and
+ * _FILLLOOP: DCMT_E_UNSUPPORTED before anything is enqueued.  DCMT_STAGE_MEDIAN5, _BLUR, _FINAL: X9, X10, X11.
+ * max_fill_iters and spec_fill_iters are ignored; dcmt_last_fill_iters and dcmt_last_holes_after_extend report 0 for every frame,
+ * with DCMT_OK; verbose = 1 prints the reference's two header lines and no hole counts, verbose = 2 nothing.
+ * Two consequences: an all-zero frame stays all zero (nothing is invented far from a measurement: no column-top values above the
+ * highest lidar ring), and a frame whose X5 has no hole gives the bits of the call without the flag (there the extension and both
+ * fills change nothing).
+ * The cascade is then a local stencil (13 rows either way, 11 columns to the left, 13 to the right): wherever the streaming
+ * kernels' other conditions hold (a k0 preset, rows and cols >= 8, no DCMT_FLAG_FORCE_STAGED) one kernel, k_local, reads the
+ * frames once and writes d_dst once, at every batch size; otherwise the staged kernels run without the fill.  The 16-bit form is
+ * never taken.  Every route gives the same bits; the call never synchronises and allocates nothing the call without the flag
+ * would not. */
+#define DCMT_FLAG_NO_EXTRAPOLATE 8
 
 /* ---- lifetime --------------------------------------------------------------------- */
 

@@ -89,7 +89,8 @@ inline void raise(int st, const char* what)
 inline void interpolate_with_labels(const std::vector<std::vector<int> >& clusters, int n_labels,
                                     const cv::Mat& sparse_r_img, cv::Mat& dense_r_img,
                                     const std::string& /*blur_type: unused by the reference, img_completion_lc.cpp:183*/,
-                                    int use_superpixel, const double* normalize_range = nullptr /* {alpha, beta}: see below */)
+                                    int use_superpixel, const double* normalize_range = nullptr /* {alpha, beta}: see below */,
+                                    int flags = 0 /* more DCMT_FLAG_* bits */)
 {
     check_input(sparse_r_img);
     const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
@@ -105,6 +106,7 @@ inline void interpolate_with_labels(const std::vector<std::vector<int> >& cluste
     out.create(rows, cols, CV_32FC1);
     dcmt_params p;
     dcmt_default_params(&p);
+    p.flags |= flags;
     if (normalize_range) { p.flags |= DCMT_FLAG_NORMALIZE; p.norm_lo = (float)normalize_range[0]; p.norm_hi = (float)normalize_range[1]; }
     p.verbose = quiet() ? 0 : 2;                             // img_completion_lc.cpp:173
     const int st = dcmt_complete_labeled_f32(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], 0,
@@ -137,6 +139,35 @@ inline void img_completion_normalized(const cv::Mat& projected, cv::Mat& dense_r
                                      out.ptr<float>(), out.step[0], 0, rows, cols, 1, &p);
     raise(st, "img_completion_normalized");
     dense_r_img = out;
+}
+
+// The cascade without its extrapolation (DCMT_FLAG_NO_EXTRAPOLATE, dcmt.h: no column extension, no large fills -- the median, the
+// blur and the final invert run on the plane the 7x7 fill left, and nothing is invented far from a measurement).  An opt-in of
+// this project under a name of its own: the reference's `extr` argument is never read there, so img_completion() below keeps
+// ignoring it.  Prints the reference's two header lines and no hole counts.
+inline void img_completion_no_extrapolate(const cv::Mat& sparse_r_img, cv::Mat& dense_r_img, const std::string& blur_type)
+{
+    check_input(sparse_r_img);
+    const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    dcmt_params p;
+    dcmt_default_params(&p);
+    p.blur = blur_from_string(blur_type);
+    p.flags |= DCMT_FLAG_NO_EXTRAPOLATE;
+    p.verbose = quiet() ? 0 : 1;
+    const int st = dcmt_complete_f32(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], 0,
+                                     out.ptr<float>(), out.step[0], 0, rows, cols, 1, &p);
+    raise(st, "img_completion_no_extrapolate");
+    dense_r_img = out;
+}
+
+// ... and its labeled twin: interpolate_with_labels without the extrapolation (prints nothing)
+inline void interpolate_with_labels_no_extrapolate(const std::vector<std::vector<int> >& clusters, int n_labels,
+                                                   const cv::Mat& sparse_r_img, cv::Mat& dense_r_img, const std::string& blur_type,
+                                                   int use_superpixel, const double* normalize_range = nullptr)
+{
+    interpolate_with_labels(clusters, n_labels, sparse_r_img, dense_r_img, blur_type, use_superpixel, normalize_range, DCMT_FLAG_NO_EXTRAPOLATE);
 }
 
 // ---- the steps either side of the path, on cv::Mat / std::vector like the reference's own code -----------------------
@@ -365,7 +396,8 @@ inline void unrectify_sol_nearest(const cv::Mat& depth, cv::Mat& depth_unrect, c
 
 }  // namespace dcmt_shim
 
-// reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there.
+// reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there (the cascade without its
+// extrapolation is dcmt_shim::img_completion_no_extrapolate).
 inline void img_completion(const cv::Mat& sparse_r_img, cv::Mat& dense_r_img, const bool& /*extr*/, const std::string& blur_type)
 {
     dcmt_shim::check_input(sparse_r_img);
