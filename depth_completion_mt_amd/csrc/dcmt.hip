@@ -580,6 +580,14 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
 {
     if (!ctx || !a || !b || !p) return DCMT_E_INVALID;
     if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    // max_depth and valid_thresh on their bits, read from the struct's memory (the library is built with -ffinite-math-only: a float
+    // compare against NaN or Inf may be folded): both finite, valid_thresh > 0 -- sign clear (-0.0 has it set) and not zero.  At
+    // valid_thresh <= 0 the "0 = empty" convention of every producer and of the label stage would mean nothing.
+    uint32_t mb, tb;
+    std::memcpy(&mb, &p->max_depth, sizeof mb);
+    std::memcpy(&tb, &p->valid_thresh, sizeof tb);
+    if ((mb & 0x7f800000u) == 0x7f800000u || (tb & 0x7f800000u) == 0x7f800000u) return DCMT_E_INVALID;
+    if ((tb >> 31) != 0 || (tb << 1) == 0) return DCMT_E_INVALID;
     if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
     if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN && p->blur != DCMT_BLUR_BILATERAL_CLONE) return DCMT_E_INVALID;
     if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;

@@ -114,7 +114,15 @@ typedef enum {
     DCMT_STAGE_FINAL    = 11  /* :191-202 invert back to metres */
 } dcmt_stage;
 
-/* All literals of the reference in one POD (SURVEY.md section 5 "Config / flags"). */
+/* All literals of the reference in one POD (SURVEY.md section 5 "Config / flags").
+ * Domain of the two numeric fields: max_depth finite; valid_thresh finite and > 0 (0, -0.0 and negative values are refused:
+ * every producer writes 0 for "no point" and the label stage writes 0 outside a label, which only means "empty" below a positive
+ * threshold).  Every dcmt_complete_* entry point returns DCMT_E_INVALID otherwise, tested on the bit patterns, before anything
+ * is allocated or enqueued.
+ * The column extension's fill values for a column without a valid pixel, 100 and -1 (img_completion.cpp:109-110), are literals
+ * of the reference, not its max_depth: they do not follow max_depth.
+ * The 16-bit form of the streaming kernels (k_pre_p<Q16OUT> -> k_fp_q) is built on the reference's constants and is attempted
+ * only at max_depth == 100 and valid_thresh == 0.1f; every other pair takes the f32 kernels. */
 typedef struct {
     float   max_depth;       /* 100.0f                    img_completion.cpp:23 */
     float   valid_thresh;    /* 0.1f: valid <=> x >= valid_thresh, hole <=> x < valid_thresh.

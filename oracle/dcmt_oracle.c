@@ -24,10 +24,13 @@
 /* ---- thresholds -----------------------------------------------------------------
  * The reference compares a float against the *double* literal 0.1
  * (LO/img_completion.cpp:59,96,113,117,140,154,184,194): the float is promoted.
- * (double)0.1f > 0.1, so "valid" is x >= 0.1f and "hole" is x < 0.1f; written here
- * exactly as the reference writes it. */
-static inline int gt_thresh(float x) { return (double)x > 0.1; }
-static inline int lt_thresh(float x) { return (double)x < 0.1; }
+ * (double)0.1f > 0.1, and no f32 lies between 0.1 and 0.1f, so `(double)x > 0.1` is
+ * x >= 0.1f and `(double)x < 0.1` is x < 0.1f (tests/test_oracle_params.py checks the
+ * 2^16 floats on either side of 0.1f).  That f32 form is the one include/dcmt.h states for
+ * dcmt_params.valid_thresh, and the one written here so that the threshold can be a
+ * parameter: valid <=> x >= thr, hole <=> x < thr, both f32 compares. */
+static inline int gt_thresh(float x, float thr) { return x >= thr; }
+static inline int lt_thresh(float x, float thr) { return x < thr; }
 
 /* OpenCV std::max/std::min on floats: max(a,b) = (a < b) ? b : a. */
 static inline float fmax_cv(float a, float b) { return a < b ? b : a; }
@@ -54,13 +57,14 @@ void dcmt_oracle_default_params(dcmt_oracle_params *p)
     p->blur = DCMT_O_BLUR_GAUSSIAN;        /* every caller passes "gaussian" (LO/main.cpp:93) */
     p->max_fill_iters = 64;
     p->stop_after = DCMT_O_STAGE_FINAL;
+    p->valid_thresh = 0.1f;                /* the reference's literal 0.1 (see the thresholds above) */
 }
 
 /* ---- H2 / H11: invert (LO/img_completion.cpp:55-67, 191-202) --------------------- */
-static void invert_valid(float *x, long n, float max_depth)
+static void invert_valid(float *x, long n, float max_depth, float thr)
 {
     for (long i = 0; i < n; ++i)
-        if (gt_thresh(x[i])) x[i] = max_depth - x[i];
+        if (gt_thresh(x[i], thr)) x[i] = max_depth - x[i];
 }
 
 /* ---- cv::dilate with an arbitrary 5x5 element (LO/img_completion.cpp:80) ---------
@@ -149,24 +153,27 @@ void dcmt_oracle_erode_rect(const float *s, float *d, int rows, int cols, int k)
 
 /* ---- fill holes from a dilated copy (LO/img_completion.cpp:88-100, 131-144, 147-159)
  * s = dilate(clone(x), ones(k,k)); x = (x < 0.1) ? s : x.  Returns #holes seen. */
-static int fill_from_dilate(float *x, float *scratch, int rows, int cols, int ksize)
+static int fill_from_dilate(float *x, float *scratch, int rows, int cols, int ksize, float thr)
 {
     int holes = 0;
     dcmt_oracle_dilate_rect(x, scratch, rows, cols, ksize);
     for (long i = 0, n = (long)rows * cols; i < n; ++i)
-        if (lt_thresh(x[i])) { x[i] = scratch[i]; ++holes; }
+        if (lt_thresh(x[i], thr)) { x[i] = scratch[i]; ++holes; }
     return holes;
 }
 
-/* ---- H6: column extension (LO/img_completion.cpp:103-129) -------------------------- */
-void dcmt_oracle_extend_columns(float *x, int rows, int cols)
+/* ---- H6: column extension (LO/img_completion.cpp:103-129) --------------------------
+ * max_val = -1 (:109) and min_val = 100 (:110) are literals of the reference: they are NOT its
+ * max_depth (:23) and do not follow the max_depth parameter.  Only the two scans' compares
+ * (:113, :117) take the threshold. */
+void dcmt_oracle_extend_columns(float *x, int rows, int cols, float thr)
 {
     for (int j = 0; j < cols; ++j) {
         int max_index = 0;         float max_val = -1;     /* :108-109 */
         float min_val = 100;       int min_index = rows - 1; /* :110-111 */
         for (int i = 0; i < rows; ++i) {
-            if (gt_thresh(x[(long)i * cols + j])) { max_index = i; max_val = x[(long)i * cols + j]; }
-            if (gt_thresh(x[(long)(rows - 1 - i) * cols + j])) {
+            if (gt_thresh(x[(long)i * cols + j], thr)) { max_index = i; max_val = x[(long)i * cols + j]; }
+            if (gt_thresh(x[(long)(rows - 1 - i) * cols + j], thr)) {
                 min_index = rows - 1 - i; min_val = x[(long)(rows - 1 - i) * cols + j];
             }
         }
@@ -325,25 +332,26 @@ static int chain_tail(float *x, float *scratch, int rows, int cols, const dcmt_o
                       int blur, int *fill_iters, int *holes_after_extend)
 {
     const long n = (long)rows * cols;
+    const float thr = p->valid_thresh;
     int rc = 0, iters = 0;
     if (fill_iters) *fill_iters = 0;
     if (holes_after_extend) *holes_after_extend = 0;
 
     /* H5 small fill, 7x7 (LO :88-100) */
-    fill_from_dilate(x, scratch, rows, cols, 7);
+    fill_from_dilate(x, scratch, rows, cols, 7, thr);
     if (p->stop_after <= DCMT_O_STAGE_FILL7) return 0;
     /* H6 column extension (LO :103-129), `densify` is the constant true */
-    dcmt_oracle_extend_columns(x, rows, cols);
+    dcmt_oracle_extend_columns(x, rows, cols, thr);
     if (p->stop_after <= DCMT_O_STAGE_EXTEND) return 0;
     /* H7 large fill, 31x31 (LO :131-144) */
     {
-        int h = fill_from_dilate(x, scratch, rows, cols, 31);
+        int h = fill_from_dilate(x, scratch, rows, cols, 31, thr);
         if (holes_after_extend) *holes_after_extend = h;
     }
     if (p->stop_after <= DCMT_O_STAGE_FILL31) return 0;
     /* H8 while(true){ dilate31; count; fill; if(count==0) break; } (LO :146-166) */
     for (;;) {
-        int holes = fill_from_dilate(x, scratch, rows, cols, 31);
+        int holes = fill_from_dilate(x, scratch, rows, cols, 31, thr);
         ++iters;
         if (holes == 0) break;
         if (iters >= p->max_fill_iters) { rc = -1; break; }
@@ -359,11 +367,11 @@ static int chain_tail(float *x, float *scratch, int rows, int cols, const dcmt_o
      * (in-place bilateralFilter) and no caller uses it: not restated. */
     if (blur == DCMT_O_BLUR_GAUSSIAN) {
         dcmt_oracle_gaussian5(x, scratch, rows, cols);
-        for (long i = 0; i < n; ++i) if (gt_thresh(x[i])) x[i] = scratch[i];
+        for (long i = 0; i < n; ++i) if (gt_thresh(x[i], thr)) x[i] = scratch[i];
     }
     if (p->stop_after <= DCMT_O_STAGE_BLUR) return rc;
     /* H11 invert back (LO :191-202) */
-    invert_valid(x, n, p->max_depth);
+    invert_valid(x, n, p->max_depth, thr);
     return rc;
 }
 
@@ -377,7 +385,7 @@ int dcmt_oracle_img_completion(const float *src, float *dst, int rows, int cols,
     if (holes_after_extend) *holes_after_extend = 0;
     memcpy(dst, src, sizeof(float) * n);                       /* H0 clone (LO :27) */
     /* H1 max scan (LO :41-50) only feeds a print: not restated. */
-    invert_valid(dst, n, p->max_depth);                        /* H2 */
+    invert_valid(dst, n, p->max_depth, p->valid_thresh);                        /* H2 */
     if (p->stop_after <= DCMT_O_STAGE_INVERT) goto done;
     dcmt_oracle_dilate_mask5(dst, scratch, rows, cols, p->k0); /* H3 (in-place call == out of place) */
     memcpy(dst, scratch, sizeof(float) * n);
@@ -505,7 +513,7 @@ static int lc_chain(const float *src, const int32_t *labels, int n_labels, float
     int rc = 0;
     if (fill_iters) *fill_iters = 0;
     memcpy(dst, src, sizeof(float) * n);                         /* LC :43 */
-    invert_valid(dst, n, p->max_depth);                          /* LC :45-52 */
+    invert_valid(dst, n, p->max_depth, p->valid_thresh);                          /* LC :45-52 */
     if (p->stop_after <= DCMT_O_STAGE_INVERT) goto done;
     if (use_superpixel == 0) {                                   /* LC :59-64 */
         dcmt_oracle_dilate_mask5(dst, scratch, rows, cols, p->k0);

@@ -45,6 +45,7 @@ typedef struct {
     int     blur;             /* DCMT_O_BLUR_* ("gaussian" is what every caller passes) */
     int     max_fill_iters;   /* cap on the H8 while-loop (reference: unbounded) */
     int     stop_after;       /* DCMT_O_STAGE_*; DCMT_O_STAGE_FINAL for the whole chain */
+    float   valid_thresh;     /* 0.1f: valid <=> x >= valid_thresh, hole <=> x < valid_thresh (f32 compares) */
 } dcmt_oracle_params;
 
 /* Fills defaults: as-compiled 2-tap k0, gaussian, 64 iterations, whole chain. */
@@ -93,7 +94,8 @@ void dcmt_oracle_median5_simple(const float *src, float *dst, int rows, int cols
 /* the chain entry points use the definition instead of the networks (process-wide switch; tests) */
 void dcmt_oracle_use_definitional_median(int on);
 void dcmt_oracle_gaussian5(const float *src, float *dst, int rows, int cols);
-void dcmt_oracle_extend_columns(float *x, int rows, int cols);
+/* thr: the validity threshold of the two scans; the fill values 100 / -1 are the reference's literals */
+void dcmt_oracle_extend_columns(float *x, int rows, int cols, float thr);
 
 /* N1: cv::normalize(src, dst, a, b, NORM_MINMAX) for CV_32F, the pre-step of the stereo-lidar callers
  * (DC_stereo_lidar/main_sl.cpp:370, :523). */

@@ -24,17 +24,24 @@ K0_DIAMOND = np.array([0, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1, 1, 1, 1, 1, 0, 1, 1, 1, 
                       dtype=np.uint8).reshape(5, 5)
 
 
-def _valid(x):   # `depth > 0.1`: float promoted to double against the double literal
-    return x.astype(np.float64) > 0.1
+# The reference writes `depth > 0.1` / `depth < 0.1`: the float promoted to double against the double literal.  No f32 lies
+# between 0.1 and 0.1f = (float)0.1 > 0.1, so those are the f32 compares x >= 0.1f / x < 0.1f -- the form include/dcmt.h
+# states for dcmt_params.valid_thresh and the one that takes a threshold (tests/test_oracle_params.py checks the equivalence).
+DEFAULT_MAX_DEPTH = F32(100.0)      # LO :23
+DEFAULT_VALID_THRESH = F32(0.1)
 
 
-def _hole(x):    # `depth < 0.1`
-    return x.astype(np.float64) < 0.1
+def _valid(x, valid_thresh=DEFAULT_VALID_THRESH):
+    return np.asarray(x, dtype=F32) >= F32(valid_thresh)
 
 
-def invert(x, max_depth=F32(100.0)):
+def _hole(x, valid_thresh=DEFAULT_VALID_THRESH):
+    return np.asarray(x, dtype=F32) < F32(valid_thresh)
+
+
+def invert(x, max_depth=DEFAULT_MAX_DEPTH, valid_thresh=DEFAULT_VALID_THRESH):
     """LO :55-67 / :191-202."""
-    return np.where(_valid(x), F32(max_depth) - x, x).astype(F32)
+    return np.where(_valid(x, valid_thresh), F32(max_depth) - x, x).astype(F32)
 
 
 def _shifted(x, dr, dc, fill):
@@ -79,18 +86,18 @@ def dilate_rect_fast(x, k):
     return dilate(dilate(x, np.ones((1, k), np.uint8)), np.ones((k, 1), np.uint8))
 
 
-def fill(x, k):
+def fill(x, k, valid_thresh=DEFAULT_VALID_THRESH):
     """s = dilate(clone(x), ones(k,k)); x = x<0.1 ? s : x (LO :88-100, :131-144)."""
     s = dilate_rect_fast(x, k)
-    h = _hole(x)
+    h = _hole(x, valid_thresh)
     return np.where(h, s, x).astype(F32), int(h.sum())
 
 
-def extend_columns(x):
-    """LO :103-129."""
+def extend_columns(x, valid_thresh=DEFAULT_VALID_THRESH):
+    """LO :103-129.  The 100 below is the literal of :110, not max_depth (:23): it does not follow the parameter."""
     x = x.copy()
     R, C = x.shape
-    v = _valid(x)
+    v = _valid(x, valid_thresh)
     for j in range(C):
         idx = np.flatnonzero(v[:, j])
         if idx.size == 0:
@@ -270,20 +277,20 @@ def gaussian5(x):
     return o
 
 
-def _tail(x, stop_after, blur, max_fill_iters, info):
-    x, _ = fill(x, 7)                                   # H5
+def _tail(x, stop_after, blur, max_fill_iters, info, max_depth=DEFAULT_MAX_DEPTH, valid_thresh=DEFAULT_VALID_THRESH):
+    x, _ = fill(x, 7, valid_thresh)                     # H5
     if stop_after <= 5:
         return x
-    x = extend_columns(x)                               # H6
+    x = extend_columns(x, valid_thresh)                 # H6
     if stop_after <= 6:
         return x
-    x, n = fill(x, 31)                                  # H7
+    x, n = fill(x, 31, valid_thresh)                    # H7
     info["holes_after_extend"] = n
     if stop_after <= 7:
         return x
     iters = 0
     while True:                                         # H8
-        x, n = fill(x, 31)
+        x, n = fill(x, 31, valid_thresh)
         iters += 1
         if n == 0 or iters >= max_fill_iters:
             break
@@ -295,16 +302,16 @@ def _tail(x, stop_after, blur, max_fill_iters, info):
         return x
     if blur == "gaussian":                              # H10
         g = gaussian5(x)
-        x = np.where(_valid(x), g, x).astype(F32)
+        x = np.where(_valid(x, valid_thresh), g, x).astype(F32)
     if stop_after <= 10:
         return x
-    return invert(x)                                    # H11
+    return invert(x, max_depth, valid_thresh)           # H11
 
 
 def img_completion(sparse, k0=K0_AS_COMPILED, blur="gaussian", stop_after=11, max_fill_iters=64,
-                   info=None):
+                   info=None, max_depth=DEFAULT_MAX_DEPTH, valid_thresh=DEFAULT_VALID_THRESH):
     info = {} if info is None else info
-    x = invert(np.asarray(sparse, dtype=F32))           # H0, H2
+    x = invert(np.asarray(sparse, dtype=F32), max_depth, valid_thresh)   # H0, H2
     if stop_after <= 2:
         return x
     x = dilate(x, k0)                                   # H3
@@ -313,14 +320,15 @@ def img_completion(sparse, k0=K0_AS_COMPILED, blur="gaussian", stop_after=11, ma
     x = erode(dilate(x, _ones(5)), _ones(5))            # H4
     if stop_after <= 4:
         return x
-    return _tail(x, stop_after, blur, max_fill_iters, info)
+    return _tail(x, stop_after, blur, max_fill_iters, info, max_depth, valid_thresh)
 
 
 def interpolate_with_superpixels(sparse, labels, n_labels, k0=K0_AS_COMPILED, use_superpixel=1,
-                                 stop_after=11, max_fill_iters=64, info=None):
+                                 stop_after=11, max_fill_iters=64, info=None,
+                                 max_depth=DEFAULT_MAX_DEPTH, valid_thresh=DEFAULT_VALID_THRESH):
     """LC :34-203 (one whole-image pass per label, literally)."""
     info = {} if info is None else info
-    x = invert(np.asarray(sparse, dtype=F32))
+    x = invert(np.asarray(sparse, dtype=F32), max_depth, valid_thresh)
     if stop_after <= 2:
         return x
     if use_superpixel == 0:
@@ -337,4 +345,4 @@ def interpolate_with_superpixels(sparse, labels, n_labels, k0=K0_AS_COMPILED, us
             x = np.where(m, region, x).astype(F32)
     if stop_after <= 4:
         return x
-    return _tail(x, stop_after, "gaussian", max_fill_iters, info)
+    return _tail(x, stop_after, "gaussian", max_fill_iters, info, max_depth, valid_thresh)

@@ -27,6 +27,7 @@ class Params(ctypes.Structure):
         ("blur", ctypes.c_int),
         ("max_fill_iters", ctypes.c_int),
         ("stop_after", ctypes.c_int),
+        ("valid_thresh", ctypes.c_float),
     ]
 
 
@@ -81,7 +82,7 @@ def lib(native: bool = False) -> ctypes.CDLL:
             getattr(L, n).restype = None
         L.dcmt_oracle_use_definitional_median.argtypes = [ctypes.c_int]
         L.dcmt_oracle_use_definitional_median.restype = None
-        L.dcmt_oracle_extend_columns.argtypes = [fp, ctypes.c_int, ctypes.c_int]
+        L.dcmt_oracle_extend_columns.argtypes = [fp, ctypes.c_int, ctypes.c_int, ctypes.c_float]
         L.dcmt_oracle_extend_columns.restype = None
         L.dcmt_oracle_normalize_minmax.argtypes = [fp, fp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float]
         L.dcmt_oracle_normalize_minmax.restype = None
@@ -126,18 +127,20 @@ def _c32(a) -> np.ndarray:
 
 
 def default_params(k0: str = "as_compiled", blur: str = "gaussian", stop_after: int = STAGE_FINAL,
-                   max_fill_iters: int = 64) -> Params:
+                   max_fill_iters: int = 64, max_depth: float = 100.0, valid_thresh: float = 0.1) -> Params:
     p = Params()
     lib().dcmt_oracle_default_params(ctypes.byref(p))
-    if k0 == "diamond":
+    if isinstance(k0, str) and k0 == "diamond":
         lib().dcmt_oracle_k0_diamond(p.k0)
-    elif k0 != "as_compiled":
+    elif not (isinstance(k0, str) and k0 == "as_compiled"):
         arr = np.asarray(k0, dtype=np.uint8).reshape(25)
         for i in range(25):
             p.k0[i] = int(arr[i])
     p.blur = BLUR_GAUSSIAN if blur == "gaussian" else BLUR_NONE
     p.stop_after = stop_after
     p.max_fill_iters = max_fill_iters
+    p.max_depth = max_depth          # rounded to f32 by the field, as dcmt_params does
+    p.valid_thresh = valid_thresh
     return p
 
 
@@ -223,9 +226,9 @@ def gaussian5(a):
     return _unary("dcmt_oracle_gaussian5", a)
 
 
-def extend_columns(a):
+def extend_columns(a, valid_thresh: float = 0.1):
     x = _c32(a).copy()
-    lib().dcmt_oracle_extend_columns(_fp(x), x.shape[0], x.shape[1])
+    lib().dcmt_oracle_extend_columns(_fp(x), x.shape[0], x.shape[1], ctypes.c_float(valid_thresh))
     return x
 
 

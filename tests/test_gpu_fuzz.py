@@ -1,5 +1,6 @@
 """Differential fuzz of the HIP path against the oracle: random image sizes, densities, value ranges, structuring
-elements, stages, batch sizes (both dispatch paths), label planes, the normalise flag -- every case seeded, every
+elements, stages, batch sizes (both dispatch paths), label planes, the normalise flag, and in half the cases a non-default
+(max_depth, valid_thresh) from the grid of tests/param_cases.py -- every case seeded, every
 result compared bit for bit (through the C ABI, like all parity tests)."""
 import numpy as np
 import pytest
@@ -11,13 +12,22 @@ from depth_completion_mt_amd import api
 pytestmark = pytest.mark.gpu
 
 
-def _frame(g, rows, cols):
+DEFAULT_MT = (100.0, 0.1)
+
+
+def _frame(g, rows, cols, mt=DEFAULT_MT):
+    """mt: the call's (max_depth, valid_thresh); the draws from g do not depend on it"""
     kind = g.integers(0, 5)
     density = (0.0, 0.01, 0.05, 0.3, 1.0)[g.integers(0, 5)]
     x = np.where(g.random((rows, cols)) < density, g.uniform(0.2, 85.0, (rows, cols)), 0.0).astype(np.float32)
     if kind == 1:                                   # values around the threshold and around max_depth
         m = g.random((rows, cols)) < 0.02
-        x[m] = g.choice(np.array([0.05, 0.1, 0.099999994, 99.9, 99.95, 100.0, 100.5, 130.0], np.float32), int(m.sum()))
+        vals = np.array([0.05, 0.1, 0.099999994, 99.9, 99.95, 100.0, 100.5, 130.0], np.float32)
+        if mt != DEFAULT_MT:                        # the same eight, relative to the call's (M, t): t/2, t, t-, M - t, M - t/2, M, M + 1/2, 1.3 M
+            M, t = np.float32(mt[0]), np.float32(mt[1])
+            h = np.float32(0.5)
+            vals = np.array([t * h, t, np.nextafter(t, np.float32(0)), M - t, M - t * h, M, M + h, M * np.float32(1.3)], np.float32)
+        x[m] = g.choice(vals, int(m.sum()))
     elif kind == 2:                                 # empty columns / rows, a filled block
         x[:, g.integers(0, cols):] = 0
         x[: g.integers(0, rows)] = 0
@@ -48,9 +58,13 @@ def _labels(g, rows, cols):
 @pytest.mark.parametrize("seed", range(12))
 def test_fuzz_against_oracle(seed, monkeypatch):
     from oracle import oracle as O
+    from param_cases import GRID
     g = np.random.Generator(np.random.PCG64(1000 + seed))
     gb = np.random.Generator(np.random.PCG64(7000 + seed))       # row bands of k_fp_s (read by dcmt_create): 0 = by batch size
+    gp = np.random.Generator(np.random.PCG64(9000 + seed))       # (max_depth, valid_thresh): a generator of its own, so that the cases
+    nondefault = gp.permutation(10) < 5                          # that keep the defaults are the cases (and frames) they always were
     for case in range(10):
+        mt = GRID[int(gp.integers(0, len(GRID)))] if nondefault[case] else DEFAULT_MT
         monkeypatch.setenv("DCMT_FBANDS", str(int(gb.integers(0, 7))))
         rows, cols = int(g.integers(8, 180)), int(g.integers(8, 400))
         batch = int(g.choice([1, 2, 13]))
@@ -59,12 +73,12 @@ def test_fuzz_against_oracle(seed, monkeypatch):
         stop = int(g.choice([11, 11, 11, 9, 7, 6, 4, 2]))
         norm = (None, (0, 80), (0, 100))[g.integers(0, 3)]
         labeled = g.random() < 0.4
-        frames = np.stack([_frame(g, rows, cols) for _ in range(batch)])
-        what = f"seed {seed} case {case}: {rows}x{cols} b{batch} {k0} {blur} stop{stop} norm{norm} labeled{labeled}"
-        kw = dict(k0=k0, blur_type=blur, stop_after=stop, max_fill_iters=6, force_fused=bool(g.integers(0, 2)))
+        frames = np.stack([_frame(g, rows, cols, mt) for _ in range(batch)])
+        what = f"seed {seed} case {case}: {rows}x{cols} b{batch} {k0} {blur} stop{stop} norm{norm} labeled{labeled} (max_depth, valid_thresh) {mt}"
+        kw = dict(k0=k0, blur_type=blur, stop_after=stop, max_fill_iters=6, force_fused=bool(g.integers(0, 2)), max_depth=mt[0], valid_thresh=mt[1])
         if norm is not None:
             kw["normalize"] = norm
-        op = O.default_params(k0=k0, blur=blur, stop_after=stop, max_fill_iters=6)
+        op = O.default_params(k0=k0, blur=blur, stop_after=stop, max_fill_iters=6, max_depth=mt[0], valid_thresh=mt[1])
         with api.Context(0, rows, cols, batch) as c:
             if labeled:
                 if stop in (2, 6, 7, 9):            # per-stage dumps of the labeled variant: stage 4 and the whole chain only
