@@ -242,9 +242,55 @@ static void test_chunks()
         CHECK((uint64_t)eval_chunks(n) * eval_chunk_groups(n) >= (n + 3) / 4 && (uint64_t)(eval_chunks(n) - 1) * eval_chunk_groups(n) < (n + 3) / 4);
 }
 
+// ---- geometry C of tests/large_batch_cases.py: 65535 frames of 128 x 260 ------------------------------------------------
+// 2,181,004,800 pixels: more than 2^31 and more than the segments' 0x7fff0000, so each of the three segmented entry points runs
+// exactly two segments; the launch loops in dcmt.hip and dcmt_cloud.hip advance their pointers by `first`.
+static void test_geometry_c()
+{
+    constexpr uint32_t n = 128u * 260u;
+    constexpr int batch = 65535;
+    constexpr uint64_t px = (uint64_t)n * batch;
+    static_assert(px == 2181004800ull && px > k2p31 && px > kBgrSegPx && px > kU16SegPx && px < 2ull * kBgrSegPx, "geometry C");
+    constexpr uintptr_t kLab = 0xC00000000ull, kGray = 0xE00000000ull, kOut = 0x400000000ull;     // clear of kSrc + 4 px and kBgr + 3 px
+
+    // the colourisation: whole frames, a multiple of 4 of them in all segments but the last
+    const ColorPlan c = checked_color(n, batch, kSrc, kBgr, true);
+    CHECK(c.count == 2 && c.seg == 64524 && c.seg % 4 == 0);
+    const ColorSegment c0 = c.segment(0), c1 = c.segment(1);
+    CHECK(c0.first == 0 && c0.frames == 64524 && c0.total == 64524u * n && c0.minmax_y == 64524);
+    CHECK(c1.first == 64524 && c1.frames == 1011 && c1.total == 1011u * n && c1.minmax_y == 1011);
+    CHECK((uint64_t)c0.total + c1.total == px && (uint64_t)(c0.frames + 4) * n > k2p31 - kColorPxPerWg);     // (the next multiple of 4 would not fit)
+    CHECK(c0.aligned && c1.aligned);                       // `aligned` follows each segment's own addresses:
+    CHECK(!plan_colorize(n, batch, kSrc + 4, kBgr).segment(0).aligned && !plan_colorize(n, batch, kSrc + 4, kBgr).segment(1).aligned);
+    CHECK(!plan_colorize(n, batch, kSrc, kBgr + 2).segment(0).aligned && !plan_colorize(n, batch, kSrc, kBgr + 2).segment(1).aligned);
+    CHECK(plan_colorize(n, batch, kSrc + 16, kBgr + 4).segment(1).aligned);
+
+    // the BGR ingest: a flat run cut at kBgrSegPx, wherever that falls in a frame (here inside frame 64525)
+    const BgrPlan b = plan_bgr_convert(px, kBgr, kLab, kGray);
+    CHECK(b.status == kOk && b.px == px && b.count == 2 && b.passes == kBgrMaxPasses && b.aligned);
+    const BgrSegment b0 = b.segment(0), b1 = b.segment(1);
+    CHECK(b0.first == 0 && b0.total == kBgrSegPx && b0.grid == (kBgrSegPx + b.share() - 1) / b.share());
+    CHECK(b1.first == kBgrSegPx && b1.total == (uint32_t)(px - kBgrSegPx) && b1.total == 33586688u && b1.grid == (b1.total + b.share() - 1) / b.share());
+    CHECK(b1.first / n == 64525 && b1.first % n != 0 && b1.first % 4 == 0);
+    CHECK(!plan_bgr_convert(px, kBgr, kLab + 1, kGray).aligned && !plan_bgr_convert(px, kBgr + 2, kLab, kGray).aligned &&
+          !plan_bgr_convert(px, kBgr, kLab, kGray + 3).aligned && plan_bgr_convert(px, kBgr, kLab, 0).aligned);
+    CHECK(plan_bgr_convert(px, kBgr, kBgr, kGray).status == kOk && plan_bgr_convert(px, kBgr, kBgr + 3 * px - 1, 0).status == kInvalid);
+
+    // the uint16 export
+    const U16Plan u = plan_depth_to_u16(px, kSrc, kOut);
+    CHECK(u.status == kOk && u.px == px && u.count == 2 && u.aligned);
+    const U16Segment u0 = u.segment(0), u1 = u.segment(1);
+    CHECK(u0.first == 0 && u0.total == kU16SegPx && u0.grid == kU16SegPx / kU16PxPerWg);
+    CHECK(u1.first == kU16SegPx && u1.total == (uint32_t)(px - kU16SegPx) && u1.grid == (u1.total + kU16PxPerWg - 1) / kU16PxPerWg);
+    CHECK((4 * u1.first) % 16 == 0 && (2 * u1.first) % 16 == 0);
+    CHECK(!plan_depth_to_u16(px, kSrc + 4, kOut).aligned && !plan_depth_to_u16(px, kSrc, kOut + 2).aligned);
+    CHECK(plan_depth_to_u16(px, kSrc, kSrc + 4 * px - 2).status == kInvalid);
+}
+
 int main()
 {
     test_colorize();
+    test_geometry_c();
     test_winner();
     test_slic();
     test_gauss_stereo_vec();

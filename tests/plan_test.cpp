@@ -199,6 +199,77 @@ static void test_table()
     }
 }
 
+// The geometries of tests/large_batch_cases.py whose batches the cascade takes: 65535 frames of 96 x 176 (the largest batch: the
+// frame is a grid's z or y dimension in the staged and the label kernels) and 2512 frames of 352 x 1216 (f32 planes beyond 2^32 bytes).
+// Every grid of every plan fits in 31 bits, and on-grid input gets the 16-bit attempt.
+static bool grids_fit(const Plan& p, int batch)
+{
+    for (unsigned g : {p.pre_grid, p.fill_grid, p.post_grid, p.fp_s_grid, p.fp_q_grid, p.local_grid})
+        if (g > 0x7fffffffu) return false;
+    return p.tiles_x >= 0 && p.tiles_y >= 0 && p.tiles_y <= 65535 && p.label_grid_x >= 0 && p.label_grid_x <= 0x7fffffff && batch <= 65535;
+}
+
+static void test_large_batches()
+{
+    const struct { int rows, cols, batch; } geo[] = {{96, 176, 65535}, {352, 1216, 2512}};
+    for (const auto& g : geo) {
+        Call c = call(g.batch);
+        c.rows = g.rows; c.cols = g.cols;
+        CHECK((uint64_t)g.batch * g.rows * g.cols * 4 > 0x100000000ull && kSrc + (uint64_t)g.batch * g.rows * g.cols * 4 <= kDst);
+        const Plan p = checked(c);
+        CHECK(p.route == Route::STREAMING && p.q16 && p.needs_x6q && p.pair && p.table && p.bands == 1 && p.fb_s == 1 && p.tail && !p.fp_s_launch && p.filled);
+        CHECK(p.xcd_map == (g.batch % 8 == 0 ? 1 : 0));
+        CHECK(std::strcmp(p.path, "k_pre_p<Q16OUT> + k_fp_q") == 0);
+        CHECK(grids_fit(p, g.batch));
+        CHECK(p.pre_grid == wave_grid(p.pre_strips, g.batch, p.xcd_map) && p.fp_q_grid == wave_grid(p.q_strips, g.batch, p.xcd_map));
+        CHECK(p.pre_grid >= (unsigned)(((uint64_t)g.batch * p.pre_strips) / 4) && p.fp_q_grid >= (unsigned)(((uint64_t)g.batch * p.q_strips) / 4));
+        CHECK(p.fill_grid == (unsigned)((p.fill_strips + 3) / 4) * (unsigned)g.batch && p.post_grid == (unsigned)((p.post_strips + 3) / 4) * (unsigned)g.batch);
+        {
+            Call u = c;
+            u.input = Input::U16; u.in_scale = 1.0f / 256.0f;
+            CHECK(checked(u).q16 && grids_fit(checked(u), g.batch) && std::strcmp(checked(u).path, "k_pre_p<U16,Q16OUT> + k_fp_q") == 0);
+        }
+        {
+            Call n = c;
+            n.flags = kFlagNormalize;
+            CHECK(!checked(n).q16 && grids_fit(checked(n), g.batch) && std::strcmp(checked(n).path, "k_pre_p<NORM> + k_fp_s") == 0);
+            CHECK(checked(n).fp_s_grid == wave_grid(checked(n).post_strips, g.batch, checked(n).xcd_map));
+            n.stop_after = kStageNormalize;
+            CHECK(checked(n).route == Route::NORMALIZE_ONLY && checked(n).out == Out::DST);
+        }
+        {
+            Call s = c;
+            s.flags = kFlagForceStaged;
+            const Plan ps = checked(s);
+            CHECK(ps.route == Route::STAGED && !ps.few && ps.tiles_x == (g.cols + TW - 1) / TW && ps.tiles_y == (g.rows + TH - 1) / TH && grids_fit(ps, g.batch));
+        }
+        {
+            Call l = c;
+            l.flags = kFlagNoExtrapolate;
+            const Plan pl = checked(l);
+            CHECK(pl.route == Route::LOCAL && pl.local_bands == 1 && std::strcmp(pl.path, "k_local") == 0 && grids_fit(pl, g.batch));
+            CHECK(pl.local_grid == wave_grid(pl.local_strips, g.batch, pl.xcd_map) && pl.local_grid >= (unsigned)(((uint64_t)g.batch * pl.local_strips) / 4));
+        }
+        {
+            Call e = c;
+            e.stop_after = kStageExtend;
+            CHECK(checked(e).out == Out::DST && std::strcmp(checked(e).path, "k_pre_p") == 0 && grids_fit(checked(e), g.batch));
+            e.stop_after = kStageMedian5;
+            e.bilateral = true;       // (what blur = BILATERAL_CLONE plans from stop_after = BLUR on: the chain up to the median)
+            e.stop_after = kStageBlur;
+            CHECK(checked(e).bilateral && std::strcmp(checked(e).path, "k_pre_p + bilateral5") == 0 && grids_fit(checked(e), g.batch));
+        }
+        for (int n_labels : {40, 1200, 3500}) {
+            Call l = c;
+            l.input = Input::LABELED; l.labels = kLabels; l.n_labels = n_labels;
+            const Plan pl = checked(l);
+            CHECK(pl.route == Route::STREAMING && pl.needs_bbox && pl.q16 && grids_fit(pl, g.batch));
+            CHECK(pl.bbox_lds == (16 * n_labels <= 48 * 1024));
+            CHECK(std::strncmp(pl.path, "k_label_bbox + k_label_stage + k_pre_p", 38) == 0);
+        }
+    }
+}
+
 // batch 16, DCMT_FP_Q16 on, DCMT_Q16_MIN_WAVES=0: one knob at a time.  The expected sets are read off the parent's dispatch: a knob
 // moves the field it names and what the dispatch derives from that field (fields a route does not reach keep their defaults).
 static void test_knobs()
@@ -255,6 +326,7 @@ static void test_env()
 int main()
 {
     test_table();
+    test_large_batches();
     test_knobs();
     test_env();
     std::printf(failures ? "%d checks failed\n" : "ok\n", failures);
