@@ -43,6 +43,7 @@ EXPORTS = (
     "dcmt_bilateral5_dev", "dcmt_bilateral5",
     "dcmt_slic_connectivity_max_labels", "dcmt_slic_connectivity_dev", "dcmt_slic_connectivity",
     "dcmt_slic_contours_dev", "dcmt_slic_cluster_means_dev", "dcmt_slic_contours", "dcmt_slic_cluster_means",
+    "dcmt_default_photo_error_params", "dcmt_photo_error_dev", "dcmt_photo_error_calib_dev", "dcmt_photo_error",
 )
 
 
@@ -102,6 +103,11 @@ class ProjectCalib(ctypes.Structure):
 class StereoCalib(ctypes.Structure):
     """Mirror of dcmt_stereo_calib (include/dcmt.h): one frame's record of dcmt_stereo_refine_calib_dev."""
     _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float)]
+
+
+class PhotoErrorParams(ctypes.Structure):
+    """Mirror of dcmt_photo_error_params (include/dcmt.h)."""
+    _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float), ("window", ctypes.c_int32)]
 
 
 class CropSrc(ctypes.Structure):
@@ -224,6 +230,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_crop_frames_dev.argtypes = [vp, vp, sz, vp, i, vp, i, i, i, vp]
         L.dcmt_depth_to_u16_dev.argtypes = [vp, vp, f32, vp, i, i, i, vp]
         L.dcmt_depth_to_u16.argtypes = [vp, vp, sz, f32, vp, sz, i, i]
+        L.dcmt_default_photo_error_params.argtypes = [vp]
+        L.dcmt_default_photo_error_params.restype = None
+        L.dcmt_photo_error_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
+        L.dcmt_photo_error_calib_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
+        L.dcmt_photo_error.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp, sz, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

@@ -15,6 +15,8 @@
         reference: src/DC_stereo_lidar/main_sl.cpp:924-965, :887-922
     unrectify_sol(depth_pre_optim, out_shape, R_rect) -> the plane forward-warped into the un-rectified camera's frame
         reference: src/DC_stereo_lidar/main_sl.cpp:967-1028 (its data, not its drawing and printing)
+    get_initial_error(depth, left, right) -> (the photometric error map, its four counts)
+        reference: src/DC_stereo_lidar/main_sl.cpp:618-712 (its data, not its drawing and printing)
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -167,6 +169,22 @@ def make_reproject_params(M=None, K=None, fx: float | None = None, fy: float | N
 
 # ---- per-frame calibration tables of the *_calib_dev calls (include/dcmt.h): structured arrays of exactly the C layouts ----------
 PROJECT_CALIB_DTYPE = np.dtype([("T", "<f4", (12,)), ("P", "<f4", (12,))])                                   # dcmt_project_calib, 96 B
+PHOTO_STATS = ("valid", "matches", "nonzero", "sum_err")           # the four uint64 words of dcmt_photo_error_dev's statistics, in order
+
+
+def make_photo_error_params(baseline: float | None = None, focal: float | None = None, window: int | None = None) -> L.PhotoErrorParams:
+    """dcmt_photo_error_params: the reference's constants (SL/main_sl.cpp:632, :634, :638: 0.54, 959.791, 2) unless overridden."""
+    p = L.PhotoErrorParams()
+    L.lib().dcmt_default_photo_error_params(ctypes.byref(p))
+    if baseline is not None:
+        p.baseline = float(baseline)
+    if focal is not None:
+        p.focal = float(focal)
+    if window is not None:
+        p.window = int(window)
+    return p
+
+
 CLOUD_CALIB_DTYPE = np.dtype([("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8")])                    # dcmt_cloud_params, 32 B
 REPROJECT_CALIB_DTYPE = np.dtype({"names": ["fx", "fy", "cx", "cy", "M", "K"], "formats": ["<f8", "<f8", "<f8", "<f8", ("<f4", (16,)), ("<f4", (9,))],
                                   "offsets": [0, 8, 16, 24, 32, 96], "itemsize": 136})                      # dcmt_reproject_params
@@ -650,6 +668,71 @@ class Context:
         _check(st, "dcmt_stereo_refine_calib_dev")
         return d_out
 
+    # ---- photometric error maps (dcmt_photo_error*) ---------------------------------------
+    def _photo_error_dev(self, d_depth, d_left, d_right, d_calib, d_err, d_stats, want_err, want_stats, stream, kw):
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        for t in (d_left, d_right):
+            assert _is_dev(t, torch.uint8) and t.shape == d_depth.shape
+        b, r, c = _brc(d_depth)
+        want_err, want_stats = want_err or d_err is not None, want_stats or d_stats is not None
+        with _on_stream(stream, d_depth):
+            if want_err and d_err is None:
+                d_err = torch.empty(tuple(d_depth.shape), dtype=torch.uint8, device=d_depth.device)
+            if want_stats and d_stats is None:
+                d_stats = torch.empty((b, 4), dtype=torch.int64, device=d_depth.device)
+        assert d_err is None or (_is_dev(d_err, torch.uint8) and d_err.numel() == b * r * c)
+        assert d_stats is None or (_is_dev(d_stats) and d_stats.element_size() == 8 and d_stats.numel() == 4 * b)
+        p = make_photo_error_params(**kw)
+        e, s = d_err.data_ptr() if want_err else None, d_stats.data_ptr() if want_stats else None
+        if d_calib is None:
+            st = L.lib().dcmt_photo_error_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), r, c, b, ctypes.byref(p), e, s,
+                                              _stream(stream, d_depth))
+            _check(st, "dcmt_photo_error_dev")
+        else:
+            st = L.lib().dcmt_photo_error_calib_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), r, c, b, ctypes.byref(p),
+                                                    _table_ptr(d_calib, b, STEREO_CALIB_DTYPE.itemsize), e, s, _stream(stream, d_depth))
+            _check(st, "dcmt_photo_error_calib_dev")
+        return (d_err, d_stats) if want_err and want_stats else d_err if want_err else d_stats
+
+    def photo_error_dev(self, d_depth, d_left, d_right, err: bool = True, stats: bool = True, d_err=None, d_stats=None,
+                        stream: int | None = None, **kw):
+        """The reference's get_initial_error on the device (dcmt_photo_error_dev; SL/main_sl.cpp:618-712, its data): a dense f32 depth
+        plane and a grey stereo pair (uint8 CUDA tensors of its shape, what bgr_convert_dev writes) -> the uint8 error map and / or the
+        int64 CUDA tensor [batch, 4] of PHOTO_STATS (valid pixels, matches, pixels with err > 0, the sum of err), without synchronising.
+        Returns (err, stats), or the one that is wanted; without err the plane is not stored.  A d_err / d_stats that is given is written
+        and wanted.  kw: baseline, focal, window (1..4) override the reference's constants.
+        Outputs that are not given are allocated on the stream the call enqueues on."""
+        return self._photo_error_dev(d_depth, d_left, d_right, None, d_err, d_stats, err, stats, stream, kw)
+
+    def photo_error_calib_dev(self, d_depth, d_left, d_right, d_calib, err: bool = True, stats: bool = True, d_err=None, d_stats=None,
+                              stream: int | None = None, **kw):
+        """photo_error_dev with each frame's own baseline and focal length (dcmt_photo_error_calib_dev): d_calib is a CUDA tensor holding
+        [batch] dcmt_stereo_calib records (make_stereo_calib, calib_to_device), read on the stream the call enqueues on.  kw: window.
+        A frame whose record has an entry that is not finite and > 0 gives a zero plane and zero counts."""
+        assert set(kw) <= {"window"}, kw
+        assert d_calib is not None
+        return self._photo_error_dev(d_depth, d_left, d_right, d_calib, d_err, d_stats, err, stats, stream, kw)
+
+    def photo_error(self, depth: np.ndarray, left: np.ndarray, right: np.ndarray, err: bool = True, stats: bool = True, **kw):
+        """One frame of host memory (dcmt_photo_error, synchronous; any row stride): (uint8 [rows][cols], uint64 [4]), or the one that
+        is wanted."""
+        d = _frame_f32(depth)
+        imgs = []
+        for a in (left, right):
+            a = np.asarray(a, dtype=np.uint8)
+            assert a.shape == d.shape
+            imgs.append(a if a.strides[1] == 1 else np.ascontiguousarray(a))
+        assert err or stats
+        e = np.empty(d.shape, dtype=np.uint8) if err else None
+        s = np.zeros(4, dtype=np.uint64) if stats else None
+        p = make_photo_error_params(**kw)
+        st = L.lib().dcmt_photo_error(self._h, d.ctypes.data, d.strides[0], imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data,
+                                      imgs[1].strides[0], d.shape[0], d.shape[1], ctypes.byref(p), e.ctypes.data if err else None,
+                                      e.strides[0] if err else 0, s.ctypes.data if stats else None)
+        _check(st, "dcmt_photo_error")
+        return (e, s) if err and stats else e if err else s
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1086,6 +1169,18 @@ def bgr_to_gray(img):
     """cv::cvtColor(img, gray, cv::COLOR_BGR2GRAY) on 8-bit pixels (SL/main_sl.cpp:1167, :1171): uint8 [...][rows][cols][3] ->
     [...][rows][cols]; numpy or CUDA tensor, as bgr_to_lab."""
     return _bgr_convert(img, False)
+
+
+def get_initial_error(depth, left, right, **params):
+    """The reference's get_initial_error (SL/main_sl.cpp:618-712) on one host frame, its data: (err, stats) -- the uint8 error map and a
+    dict of the four counts of PHOTO_STATS (the reference prints matches, nonzero and valid).  left, right: grey uint8 [rows][cols], or
+    BGR uint8 [rows][cols][3], which go through bgr_to_gray as the reference's cv::cvtColor calls do (:625, :630).  params: baseline,
+    focal, window."""
+    d = np.asarray(depth, dtype=np.float32)
+    imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
+    imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
+    e, s = _ctx_for(d.shape[0], d.shape[1], 1).photo_error(d, imgs[0], imgs[1], **params)
+    return e, {k: int(v) for k, v in zip(PHOTO_STATS, s)}
 
 
 def depth_to_u16(depth, scale: float = 256.0):

@@ -2,7 +2,8 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h),
+// dcmt_photo_error_dev and dcmt_photo_error_calib_dev (dcmt_kernels_photo.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
 
@@ -17,6 +18,7 @@
 #include "dcmt_kernels_bilateral.h"
 #include "dcmt_kernels_connect.h"
 #include "dcmt_kernels_contour.h"
+#include "dcmt_kernels_photo.h"
 
 using namespace dcmt;
 
@@ -504,6 +506,71 @@ int dcmt_slic_cluster_means_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows
     hipLaunchKernelGGL(k_means_paint, dim3(pl.px_x, batch), dim3(256), 0, st, d_labels, pl.n, nl, sums, d_bgr);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- get_initial_error (dcmt_kernels_photo.h) ------------------------------------------------------------------------------------
+// The clear of the statistics and the one kernel plan_photo_error names.  Nothing of the context is read or written but its device
+// and its limits: no scratch, no state, no allocation.
+template <typename G>
+static void photo_launch(const plan::PhotoPlan& pl, const uint32_t* depth, const uint8_t* left, const uint8_t* right, uint8_t* err,
+                         unsigned long long* stats, int rows, int cols, int window, G P, hipStream_t st)
+{
+    const dim3 grid(pl.grid_x, pl.grid_y);
+    if (!pl.lds_route) {
+        hipLaunchKernelGGL(k_photo_error_global<G>, grid, dim3(kPhotoThreads), 0, st, depth, left, right, err, stats, rows, cols, window, P);
+        return;
+    }
+    with_value<1, 2, 3, 4>(window, [&](auto w) {
+        hipLaunchKernelGGL((k_photo_error<decltype(w)::value, G>), grid, dim3(kPhotoThreads), pl.lds, st, depth, left, right, err, stats, rows, cols,
+                           pl.band, pl.pitch, pl.vec ? 1 : 0, P);
+    });
+}
+
+// params: baseline and focal of the uniform call, or (table) only the window, with the device's [batch] records
+static int photo_error(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols, int batch,
+                       const dcmt_photo_error_params* params, const dcmt_stereo_calib* d_table, bool table, uint8_t* d_err, uint64_t* d_stats,
+                       void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if (!table && (!finite_bits(params->baseline) || !finite_bits(params->focal) || !(params->baseline > 0.0f) || !(params->focal > 0.0f)))
+        return DCMT_E_INVALID;
+    const plan::PhotoPlan pl = plan::plan_photo_error(rows, cols, batch, params->window, (uintptr_t)d_depth, (uintptr_t)d_left, (uintptr_t)d_right, table,
+                                                      (uintptr_t)d_table, (uintptr_t)d_err, (uintptr_t)d_stats);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_stats, 0, pl.clear_bytes, st));
+    const uint32_t* depth = reinterpret_cast<const uint32_t*>(d_depth);
+    unsigned long long* stats = reinterpret_cast<unsigned long long*>(d_stats);
+    if (table) photo_launch(pl, depth, d_left, d_right, d_err, stats, rows, cols, params->window, PhotoTable{d_table}, st);
+    else photo_launch(pl, depth, d_left, d_right, d_err, stats, rows, cols, params->window, PhotoK{params->baseline, params->focal}, st);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+void dcmt_default_photo_error_params(dcmt_photo_error_params* p)
+{
+    if (!p) return;
+    p->baseline = 0.54f;          // main_sl.cpp:632
+    p->focal = 9.597910e+02f;     // :634
+    p->window = 2;                // :638
+}
+
+int dcmt_photo_error_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols, int batch,
+                         const dcmt_photo_error_params* params, uint8_t* d_err, uint64_t* d_stats, void* stream)
+{
+    return photo_error(ctx, d_depth, d_left, d_right, rows, cols, batch, params, nullptr, false, d_err, d_stats, stream);
+}
+
+int dcmt_photo_error_calib_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_left, const uint8_t* d_right, int rows, int cols, int batch,
+                               const dcmt_photo_error_params* params, const dcmt_stereo_calib* d_calib, uint8_t* d_err, uint64_t* d_stats,
+                               void* stream)
+{
+    return photo_error(ctx, d_depth, d_left, d_right, rows, cols, batch, params, d_calib, true, d_err, d_stats, stream);
 }
 
 }  // extern "C"

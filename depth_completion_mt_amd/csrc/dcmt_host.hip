@@ -178,6 +178,20 @@ int dcmt_stereo_refine(dcmt_ctx* ctx, const float* depth, size_t drs, const uint
     return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
 }
 
+int dcmt_photo_error(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols,
+                     const dcmt_photo_error_params* params, uint8_t* err, size_t ers, uint64_t* stats)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !left || !right || (!err && !stats) || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    Plane d(depth, drs, sizeof(float) * (size_t)cols, rows), l(left, lrs, cols, rows), r(right, rrs, cols, rows);
+    Plane e(err, ers, cols, rows), s(stats, 4 * sizeof(uint64_t));
+    int rc = stage(ctx, {&d, &l, &r}, {&e, &s});
+    if (rc == DCMT_OK)
+        rc = dcmt_photo_error_dev(ctx, (const float*)d.dev, (const uint8_t*)l.dev, (const uint8_t*)r.dev, rows, cols, 1, params, (uint8_t*)e.dev,
+                                  (uint64_t*)s.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&e, &s}) : rc;
+}
+
 int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred, size_t prs, int rows, int cols, float thresh, int mode,
                   dcmt_eval_frame* out)
 {

@@ -13,6 +13,7 @@
 #include "dcmt_connect.h"
 #include "dcmt_contour.h"
 #include "dcmt_crop.h"
+#include "dcmt_photo.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_tiles.h"
 
@@ -523,6 +524,69 @@ inline U16Plan plan_depth_to_u16(size_t px, uintptr_t depth, uintptr_t out)
     p.status = kOk;
     p.count = (px + kU16SegPx - 1) / kU16SegPx;
     p.aligned = depth % 16 == 0 && out % 16 == 0;
+    return p;
+}
+
+// ---- dcmt_photo_error_dev, dcmt_photo_error_calib_dev ----------------------------------------------------------------------
+// A clear of the statistics (where they are wanted) and ONE kernel (dcmt_kernels_photo.h), whatever the data.  The route depends on
+// the shape and the window alone: the LDS route (k_photo_error: a workgroup stages the band's rows of both images, full width) where
+// a band of at least one row fits kPhotoLdsBudget, the global route (k_photo_error_global: a thread per pixel, the taps from global
+// memory) for wider frames.  The band starts at kPhotoBandRows and is halved while it does not fit, and then while the call makes
+// fewer than 512 workgroups (a single frame on 256 CUs), but not below 2 rows for that: a band of b rows reads b + 2 * window - 1.
+// `vec` says whether the kernels may use their wide accesses (16-byte loads of depth and images, 4-byte stores of the map): columns
+// a multiple of 16, so that every row of every frame starts as aligned as its plane does, and the planes aligned.  The same bytes
+// either way.  The checks on the buffers are here as well, tested without a device: every overlap between an output and an input,
+// the table included, and between the two outputs, is refused.
+struct PhotoPlan {
+    int status;                      // kInvalid: a null input, no output, window outside 1..4, a misaligned depth plane, statistics or
+                                     // table, more than 65535 frames, buffers that overlap
+    bool lds_route;                  // k_photo_error<window>; otherwise k_photo_error_global
+    bool vec;
+    uint32_t band;                   // LDS route: output rows per workgroup
+    uint32_t pitch;                  // ... bytes between staged rows
+    size_t lds;                      // ... dynamic LDS: two images of photo_staged_rows(band, window) rows (0 on the global route)
+    unsigned grid_x, grid_y;         // (bands, frames) or (ceil(rows * cols / kPhotoGlobalPx), frames)
+    size_t clear_bytes;              // hipMemsetAsync of the statistics: 32 bytes a frame (0: no statistics wanted)
+};
+
+inline size_t photo_lds_bytes(uint32_t band, uint32_t window, uint32_t cols)
+{
+    return (size_t)2 * photo_staged_rows(band, window) * photo_pitch(cols);
+}
+
+// rows, cols, batch >= 1 and within the context's limits; table: 0 for the uniform call (table_call says which call it is)
+inline PhotoPlan plan_photo_error(int rows, int cols, int batch, int window, uintptr_t depth, uintptr_t left, uintptr_t right, bool table_call,
+                                  uintptr_t table, uintptr_t err, uintptr_t stats)
+{
+    PhotoPlan p = {};
+    p.status = kInvalid;
+    if (!depth || !left || !right || (!err && !stats) || window < 1 || window > kPhotoMaxWindow || batch > 65535) return p;
+    if (depth % 4 != 0 || stats % 8 != 0) return p;
+    if (table_call && !calib_table_aligned(table, 8)) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols, sb = (size_t)32 * (size_t)batch;
+    const auto clear_of_inputs = [&](uintptr_t out, size_t ob) {
+        return !out || (!ranges_overlap(out, ob, depth, 4 * px) && !ranges_overlap(out, ob, left, px) && !ranges_overlap(out, ob, right, px) &&
+                        (!table_call || calib_table_clear_of(table, 8, batch, out, ob)));
+    };
+    if (!clear_of_inputs(err, px) || !clear_of_inputs(stats, sb)) return p;
+    if (err && stats && ranges_overlap(err, px, stats, sb)) return p;
+    p.status = kOk;
+    const uint32_t w = (uint32_t)window, c = (uint32_t)cols, r = (uint32_t)rows;
+    p.vec = c % 16 == 0 && depth % 16 == 0 && left % 16 == 0 && right % 16 == 0 && err % 4 == 0;
+    p.grid_y = (unsigned)batch;
+    p.clear_bytes = stats ? sb : 0;
+    p.lds_route = photo_lds_bytes(1, w, c) <= kPhotoLdsBudget;
+    if (!p.lds_route) {
+        p.grid_x = (unsigned)(((size_t)r * c + kPhotoGlobalPx - 1) / kPhotoGlobalPx);
+        return p;
+    }
+    p.band = (uint32_t)kPhotoBandRows;
+    const auto bands = [&] { return (r + p.band - 1) / p.band; };
+    while (photo_lds_bytes(p.band, w, c) > kPhotoLdsBudget) p.band /= 2;
+    while (p.band > 2 && (size_t)bands() * (size_t)batch < 512) p.band /= 2;
+    p.pitch = photo_pitch(c);
+    p.lds = photo_lds_bytes(p.band, w, c);
+    p.grid_x = bands();
     return p;
 }
 

@@ -806,6 +806,66 @@ int dcmt_depth_to_u16_dev(dcmt_ctx *ctx, const float *d_depth, float scale /* 25
 int dcmt_depth_to_u16(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, float scale,
                       uint16_t *out, size_t out_row_stride, int rows, int cols);
 
+/* ---- photometric error maps: get_initial_error ---------------------------------------------------------- */
+
+/* get_initial_error(optimized_depth, img_left_copy, img_right_copy) (DC_stereo_lidar/main_sl.cpp:618-712, called at :1273), its data:
+ * for every pixel of a dense depth plane, how well the right image agrees with the left one at the disparity that depth implies --
+ * a confidence plane for the completion, the before / after picture of dcmt_stereo_refine_dev.  Not reproduced: error_map_show, which
+ * is drawn with cv::circle (:689-701), the imshow and the prints.  The grey images are the caller's step (dcmt_bgr_convert_dev writes
+ * what cv::cvtColor(BGR2GRAY) of :625, :630 writes), as for dcmt_stereo_refine_dev.
+ * Per frame: depth f32 [rows][cols], left and right uint8 grey [rows][cols]; err uint8 [rows][cols].  For pixel (i = row, j = column):
+ *   1. !(depth > 0): err = 0 and nothing is counted -- 0, -0, negatives and NaN (:646).
+ *   2. disparity = (baseline * focal) / depth in f32: one rounded product, one rounded quotient (:648).
+ *   3. t = (float)j - disparity in f32, pr = (int)t, truncated toward zero (:649).  Where t is NaN or outside int's range the
+ *      reference's conversion is undefined; here such a pixel is "not inside": 0 < trunc(t) < cols is decided on the float
+ *      (1 <= t < 2^31, then the exact integer against cols), before any conversion.
+ *   4. !(pr > 0 && pr < cols): err = 0 (:656; both bounds as written, so column 0 is never a target).
+ *   5. otherwise the pixel is VALID and ssd = sum of (left[i+p][j+k] - right[i+p][pr+k])^2 over k and p in [-window, window), a tap kept
+ *      iff i+p > 0 && i+p < rows && j+k > 0 && j+k < cols && pr+k > 0 && pr+k < cols (:660-663: every lower bound strict, row 0 and
+ *      column 0 are never read).  Each kept tap is one MATCH.
+ *   6. err = min(255, floor(sqrt(ssd))).  The reference takes float e = sqrt(int), clamps at 255 and casts to uchar (:676-678); over
+ *      every ssd a window of up to 8 x 8 taps can give, that f32 square root never crosses an integer, so the result is the integer
+ *      square root (tests/test_photo_error.py checks all of them), and that is what the kernel computes, in integers.
+ * Everything decided about a float is decided on its bit pattern (the library is built with -ffinite-math-only).
+ * stats, four uint64 per frame: [0] valid pixels (the reference's row_cols, :657), [1] matches (:669), [2] pixels with err > 0 (counts,
+ * :696), [3] the sum of err (not in the reference: the mean error without reading the plane back).  Integer sums: the same bits in
+ * any order.
+ *
+ * DEVICE pointers, stream-ordered.  d_depth contiguous f32 [batch][rows][cols], 4-byte aligned; d_left, d_right, d_err uint8 of that
+ * shape, any alignment; d_stats [batch][4] uint64, 8-byte aligned.  d_err or d_stats may be NULL, not both: without d_err the plane is
+ * not stored.  16-byte aligned inputs, a 4-byte aligned d_err and cols a multiple of 16 take the wide accesses; the same bytes either
+ * way.  Two enqueues whatever the data: a clear of d_stats (where given) and one kernel.  Never synchronises, never allocates, uses no
+ * ctx scratch and touches none of the state a ctx carries (no flag ring, no winner plane, not what dcmt_last_path reports); may be
+ * enqueued in front of or behind any other *_dev call of the ctx on the same stream, like dcmt_gaussian5_dev.
+ * DCMT_E_INVALID: a null ctx, input or params, both outputs NULL, sizes beyond the ctx limits, window outside 1..4, a baseline or
+ * focal that is not finite and > 0, d_depth not 4-byte or d_stats not 8-byte aligned, any overlap between an output and an input or
+ * between the two outputs.  Nothing is written then. */
+typedef struct {
+    float   baseline;     /* 0.54f           main_sl.cpp:632 */
+    float   focal;        /* 9.597910e+02f   :634            */
+    int32_t window;       /* 2               :638; 1..4      */
+} dcmt_photo_error_params;
+void dcmt_default_photo_error_params(dcmt_photo_error_params *p);
+int dcmt_photo_error_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_left, const uint8_t *d_right,
+                         int rows, int cols, int batch, const dcmt_photo_error_params *params,
+                         uint8_t *d_err /* or NULL */, uint64_t *d_stats /* [batch][4] or NULL */, void *stream);
+/* The same with each frame's own baseline and focal length: d_calib holds [batch] of the 8-byte records dcmt_stereo_refine_calib_dev
+ * takes, on the device, 8-byte aligned, read by the kernel on the caller's stream with the rules of the calibration tables above;
+ * params gives the window only.  Frame f is, bit for bit, what the uniform call returns for it alone with record f.  A record is
+ * tested on the device, on its bits, as the uniform call tests its params (both entries finite and > 0); a frame whose record fails
+ * has an all-zero plane and zero stats, and no other frame is touched.  Also DCMT_E_INVALID: a null or misaligned d_calib, or one
+ * that overlaps an output. */
+int dcmt_photo_error_calib_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_left, const uint8_t *d_right,
+                               int rows, int cols, int batch, const dcmt_photo_error_params *params,
+                               const dcmt_stereo_calib *d_calib /* [batch], 8-byte aligned */,
+                               uint8_t *d_err /* or NULL */, uint64_t *d_stats /* [batch][4] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: depth >= 4 * cols, the images and err >= cols; the stride of a NULL
+ * err is ignored); stats: four uint64 or NULL.  The same bits as the device call.  What dcmt_shim::get_initial_error calls. */
+int dcmt_photo_error(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
+                     const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
+                     int rows, int cols, const dcmt_photo_error_params *params,
+                     uint8_t *err /* or NULL */, size_t err_row_stride, uint64_t *stats /* [4] or NULL */);
+
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 
 /* Each copies its inputs to the device, runs the device entry point above and copies the result back; device buffers

@@ -343,6 +343,31 @@ inline void bilateral_filter5(const cv::Mat& src, cv::Mat& dst, float sigma_colo
     dst = out;
 }
 
+// get_initial_error (DC_stereo_lidar/main_sl.cpp:618-712, called at :1273 on the refined depth), its data: the CV_8UC1 error map the
+// reference fills (:641-682) -- per pixel min(255, floor(sqrt(ssd))) of a (2 window)^2 window of the left image against the right image at
+// the disparity the depth implies, as dcmt.h states it (dcmt_photo_error) -- returned instead of shown: error_map_show's cv::circle
+// drawing, the imshow and the prints are not reproduced.  depth: CV_32FC1; left_gray, right_gray: CV_8UC1 of its size (the reference
+// converts its BGR images itself, :625, :630: bgr_to_gray above).  params == nullptr: the reference's constants (:632-638).  stats, where
+// given: valid pixels (the reference's row_cols), matches, pixels with error > 0 (its counts), the sum of the errors.
+inline cv::Mat get_initial_error(const cv::Mat& depth, const cv::Mat& left_gray, const cv::Mat& right_gray,
+                                 const dcmt_photo_error_params* params = nullptr, uint64_t* stats = nullptr)
+{
+    check_input(depth);
+    const int rows = depth.rows, cols = depth.cols;
+    if (left_gray.type() != CV_8UC1 || right_gray.type() != CV_8UC1 || left_gray.rows != rows || left_gray.cols != cols ||
+        right_gray.rows != rows || right_gray.cols != cols)
+        throw std::runtime_error("get_initial_error: the images must be CV_8UC1 of the depth's size");
+    dcmt_photo_error_params def;
+    dcmt_default_photo_error_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_8UC1);
+    raise(dcmt_photo_error(thread_ctx().get(rows, cols), depth.ptr<float>(), depth.step[0], left_gray.ptr<unsigned char>(), left_gray.step[0],
+                           right_gray.ptr<unsigned char>(), right_gray.step[0], rows, cols, params ? params : &def, out.ptr<unsigned char>(),
+                           out.step[0], stats),
+          "get_initial_error");
+    return out;
+}
+
 // reproject_pc_colors / reproject_pc (DC_stereo_lidar/main_sl.cpp:924-965, :887-922): the records of the ordered point cloud of a
 // CV_32FC1 depth plane, one per pixel with depth > 0, row-major.  bgr: CV_8UC3 of the depth's size, or an empty Mat (then the
 // fourth dword of every record is 1.0f).  params == nullptr: the reference's intrinsics (:927-930).
