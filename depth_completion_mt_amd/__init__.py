@@ -9,7 +9,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   calib_to_device, make_cloud_calib, make_project_calib, make_reproject_calib, make_stereo_calib,
                   depth_to_u16, kitti_crop_origin, make_crop_table, pack_ragged, bilateral_filter5,
                   slic_connectivity_max_labels, slic_enforce_connectivity, slic_display_contours,
-                  slic_colour_with_cluster_means, get_initial_error, make_photo_error_params)
+                  slic_colour_with_cluster_means, get_initial_error, make_photo_error_params, make_sgm_params,
+                  sgm_workspace_bytes, stereo_sgm)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -18,7 +19,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "bgr_to_lab", "bgr_to_gray", "make_project_calib", "make_cloud_calib", "make_reproject_calib", "make_stereo_calib",
            "calib_to_device", "depth_to_u16", "kitti_crop_origin", "make_crop_table", "pack_ragged",
            "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity",
-           "slic_display_contours", "slic_colour_with_cluster_means", "get_initial_error", "make_photo_error_params"]
+           "slic_display_contours", "slic_colour_with_cluster_means", "get_initial_error", "make_photo_error_params",
+           "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm"]
 
 
 def __getattr__(name):

@@ -44,6 +44,7 @@ EXPORTS = (
     "dcmt_slic_connectivity_max_labels", "dcmt_slic_connectivity_dev", "dcmt_slic_connectivity",
     "dcmt_slic_contours_dev", "dcmt_slic_cluster_means_dev", "dcmt_slic_contours", "dcmt_slic_cluster_means",
     "dcmt_default_photo_error_params", "dcmt_photo_error_dev", "dcmt_photo_error_calib_dev", "dcmt_photo_error",
+    "dcmt_default_sgm_params", "dcmt_sgm_workspace_bytes", "dcmt_sgm_dev", "dcmt_sgm",
 )
 
 
@@ -108,6 +109,12 @@ class StereoCalib(ctypes.Structure):
 class PhotoErrorParams(ctypes.Structure):
     """Mirror of dcmt_photo_error_params (include/dcmt.h)."""
     _fields_ = [("baseline", ctypes.c_float), ("focal", ctypes.c_float), ("window", ctypes.c_int32)]
+
+
+class SgmParams(ctypes.Structure):
+    """Mirror of dcmt_sgm_params (include/dcmt.h)."""
+    _fields_ = [("num_disparities", ctypes.c_int32), ("p1", ctypes.c_int32), ("p2", ctypes.c_int32), ("uniqueness", ctypes.c_int32),
+                ("disp12_max_diff", ctypes.c_int32), ("baseline", ctypes.c_float), ("focal", ctypes.c_float), ("max_depth", ctypes.c_float)]
 
 
 class CropSrc(ctypes.Structure):
@@ -235,6 +242,12 @@ def lib() -> ctypes.CDLL:
         L.dcmt_photo_error_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
         L.dcmt_photo_error_calib_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp]
         L.dcmt_photo_error.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp, sz, vp]
+        L.dcmt_default_sgm_params.argtypes = [vp]
+        L.dcmt_default_sgm_params.restype = None
+        L.dcmt_sgm_workspace_bytes.argtypes = [i, i, i, i]
+        L.dcmt_sgm_workspace_bytes.restype = sz
+        L.dcmt_sgm_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, sz, vp]
+        L.dcmt_sgm.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

@@ -17,6 +17,8 @@
         reference: src/DC_stereo_lidar/main_sl.cpp:967-1028 (its data, not its drawing and printing)
     get_initial_error(depth, left, right) -> (the photometric error map, its four counts)
         reference: src/DC_stereo_lidar/main_sl.cpp:618-712 (its data, not its drawing and printing)
+    stereo_sgm(left, right) -> the int16 disparity map of a rectified grey pair, in sixteenths of a pixel (-16: none)
+        reference: src/DC_stereo_lidar/main_sl.cpp:1293-1339 (cv::StereoSGBM's role and output convention; the matcher is dcmt.h's)
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -183,6 +185,41 @@ def make_photo_error_params(baseline: float | None = None, focal: float | None =
     if window is not None:
         p.window = int(window)
     return p
+
+
+def make_sgm_params(num_disparities: int | None = None, p1: int | None = None, p2: int | None = None, uniqueness: int | None = None,
+                    disp12_max_diff: int | None = None, baseline: float | None = None, focal: float | None = None,
+                    max_depth: float | None = None, for_depth: bool = True) -> L.SgmParams:
+    """dcmt_sgm_params: the reference's matcher (SL/main_sl.cpp:1306: 64 disparities) and this library's penalties unless overridden.
+    Raises ValueError on what dcmt_sgm_dev refuses of them: num_disparities not a multiple of 16 in 16..128, p1 < 0, p1 > p2,
+    p2 > 10000, uniqueness outside 0..100 and, for a call that writes the depth plane (for_depth, as the C call tests them only with a
+    d_depth), a baseline, focal or max_depth that is not finite and > 0."""
+    p = L.SgmParams()
+    L.lib().dcmt_default_sgm_params(ctypes.byref(p))
+    for name, v in (("num_disparities", num_disparities), ("p1", p1), ("p2", p2), ("uniqueness", uniqueness), ("disp12_max_diff", disp12_max_diff)):
+        if v is not None:
+            if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} = {v!r} is not an int32")
+            setattr(p, name, int(v))
+    for name, v in (("baseline", baseline), ("focal", focal), ("max_depth", max_depth)):
+        if v is not None:
+            setattr(p, name, float(v))
+    if p.num_disparities % 16 != 0 or not 16 <= p.num_disparities <= 128:
+        raise ValueError(f"num_disparities = {p.num_disparities}: a multiple of 16 in 16..128")
+    if not 0 <= p.p1 <= p.p2 <= 10000:
+        raise ValueError(f"p1 = {p.p1}, p2 = {p.p2}: 0 <= p1 <= p2 <= 10000")
+    if not 0 <= p.uniqueness <= 100:
+        raise ValueError(f"uniqueness = {p.uniqueness}: 0..100")
+    for name in ("baseline", "focal", "max_depth") if for_depth else ():
+        v = getattr(p, name)
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name} = {v!r}: finite and > 0")
+    return p
+
+
+def sgm_workspace_bytes(rows: int, cols: int, num_disparities: int = 64, frames: int = 1) -> int:
+    """dcmt_sgm_workspace_bytes: the bytes of workspace that hold `frames` frames in flight (0 for sizes the call refuses)."""
+    return int(L.lib().dcmt_sgm_workspace_bytes(rows, cols, num_disparities, frames))
 
 
 CLOUD_CALIB_DTYPE = np.dtype([("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8")])                    # dcmt_cloud_params, 32 B
@@ -733,6 +770,61 @@ class Context:
         _check(st, "dcmt_photo_error")
         return (e, s) if err and stats else e if err else s
 
+    # ---- dense stereo matching (dcmt_sgm*) --------------------------------------------------
+    def sgm_dev(self, d_left, d_right, disp16: bool = True, depth: bool = False, d_disp16=None, d_depth=None, d_work=None,
+                frames_in_flight: int | None = None, stream: int | None = None, **kw):
+        """Semi-global stereo matching on the device (dcmt_sgm_dev, as include/dcmt.h states it; the reference's cv::StereoSGBM block,
+        SL/main_sl.cpp:1293-1339): a rectified grey pair (uint8 CUDA tensors [batch][rows][cols], what bgr_convert_dev(gray=True) writes)
+        -> the int16 disparity map in sixteenths of a pixel (-16: invalid) and / or the f32 depth plane stereo_refine_dev,
+        photo_error_dev, evaluate_dev and colorize_dev take, without synchronising.  Returns (disp16, depth), or the one that is wanted;
+        a d_disp16 / d_depth that is given is written and wanted.  d_work: the workspace, a CUDA tensor of at least
+        sgm_workspace_bytes(rows, cols, D, 1) bytes, 16-byte aligned; the batch is worked through in chunks of as many frames as it
+        holds.  Without one a workspace for frames_in_flight frames (default: the batch, but no more than 1 GiB and at least one frame)
+        is allocated on the stream the call enqueues on.  kw: the fields of make_sgm_params."""
+        import torch
+        assert _is_dev(d_left, torch.uint8) and _is_dev(d_right, torch.uint8) and d_left.shape == d_right.shape
+        b, r, c = _brc(d_left)
+        want_disp, want_depth = disp16 or d_disp16 is not None, depth or d_depth is not None
+        p = make_sgm_params(for_depth=want_depth, **kw)
+        assert want_disp or want_depth
+        one = sgm_workspace_bytes(r, c, p.num_disparities, 1)
+        with _on_stream(stream, d_left):
+            if want_disp and d_disp16 is None:
+                d_disp16 = torch.empty(tuple(d_left.shape), dtype=torch.int16, device=d_left.device)
+            if want_depth and d_depth is None:
+                d_depth = torch.empty(tuple(d_left.shape), dtype=torch.float32, device=d_left.device)
+            if d_work is None:
+                n = frames_in_flight if frames_in_flight is not None else max(1, min(b, (1 << 30) // max(one, 1)))
+                assert n >= 1
+                d_work = torch.empty(min(n, b) * one, dtype=torch.uint8, device=d_left.device)
+        assert d_disp16 is None or (_is_dev(d_disp16, torch.int16) and d_disp16.numel() == b * r * c)
+        assert d_depth is None or (_is_dev(d_depth, torch.float32) and d_depth.numel() == b * r * c)
+        assert _is_dev(d_work)
+        st = L.lib().dcmt_sgm_dev(self._h, d_left.data_ptr(), d_right.data_ptr(), d_disp16.data_ptr() if want_disp else None,
+                                  d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p), d_work.data_ptr(),
+                                  d_work.numel() * d_work.element_size(), _stream(stream, d_left))
+        _check(st, "dcmt_sgm_dev")
+        return (d_disp16, d_depth) if want_disp and want_depth else d_disp16 if want_disp else d_depth
+
+    def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, **kw):
+        """One pair of host memory (dcmt_sgm, synchronous; any row stride): (int16 [rows][cols], f32 [rows][cols]), or the one that is
+        wanted."""
+        imgs = []
+        for a in (left, right):
+            a = np.asarray(a, dtype=np.uint8)
+            assert a.ndim == 2
+            imgs.append(a if a.strides[1] == 1 else np.ascontiguousarray(a))
+        assert imgs[0].shape == imgs[1].shape and (disp16 or depth)
+        rows, cols = imgs[0].shape
+        d = np.empty((rows, cols), dtype=np.int16) if disp16 else None
+        z = np.empty((rows, cols), dtype=np.float32) if depth else None
+        p = make_sgm_params(for_depth=depth, **kw)
+        st = L.lib().dcmt_sgm(self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0], rows, cols, ctypes.byref(p),
+                              d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None,
+                              z.strides[0] if depth else 0)
+        _check(st, "dcmt_sgm")
+        return (d, z) if disp16 and depth else d if disp16 else z
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1181,6 +1273,15 @@ def get_initial_error(depth, left, right, **params):
     imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
     e, s = _ctx_for(d.shape[0], d.shape[1], 1).photo_error(d, imgs[0], imgs[1], **params)
     return e, {k: int(v) for k, v in zip(PHOTO_STATS, s)}
+
+
+def stereo_sgm(left, right, depth: bool = False, **params):
+    """Semi-global matching of one rectified host pair (dcmt_sgm): the int16 disparity map in sixteenths of a pixel, -16 where invalid,
+    as cv::StereoSGBM::compute returns it (SL/main_sl.cpp:1293-1339); with depth=True (disp16, depth).  left, right: grey uint8
+    [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params."""
+    imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
+    imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
+    return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, **params)
 
 
 def depth_to_u16(depth, scale: float = 256.0):

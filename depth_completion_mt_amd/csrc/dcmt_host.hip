@@ -192,6 +192,27 @@ int dcmt_photo_error(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_
     return rc == DCMT_OK ? fetch(ctx, {&e, &s}) : rc;
 }
 
+int dcmt_sgm(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols, const dcmt_sgm_params* params,
+             int16_t* disp16, size_t drs, float* depth, size_t zrs)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !left || !right || (!disp16 && !depth) || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t work_bytes = dcmt_sgm_workspace_bytes(rows, cols, params->num_disparities, 1);
+    if (!work_bytes) return DCMT_E_INVALID;
+    Plane l(left, lrs, cols, rows), r(right, rrs, cols, rows);
+    Plane d(disp16, drs, sizeof(int16_t) * (size_t)cols, rows), z(depth, zrs, sizeof(float) * (size_t)cols, rows);
+    struct Workspace {                      // the one frame of workspace: device memory only, freed when the call returns
+        void* dev = nullptr;
+        ~Workspace() { if (dev) (void)hipFree(dev); }
+    } work;
+    DCMT_HIP(ctx, hipMalloc(&work.dev, work_bytes));        // before stage(): nothing of the call is in the stream if it fails
+    int rc = stage(ctx, {&l, &r}, {&d, &z});
+    if (rc == DCMT_OK)
+        rc = dcmt_sgm_dev(ctx, (const uint8_t*)l.dev, (const uint8_t*)r.dev, (int16_t*)d.dev, (float*)z.dev, rows, cols, 1, params, work.dev, work_bytes,
+                          ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&d, &z}) : rc;
+}
+
 int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred, size_t prs, int rows, int cols, float thresh, int mode,
                   dcmt_eval_frame* out)
 {

@@ -1,0 +1,295 @@
+// dcmt_kernels_sgm.h -- semi-global stereo matching as include/dcmt.h states it (dcmt_sgm_dev), three kernels per chunk of frames:
+//   k_sgm_rows    one wave per image row, lane = disparity (D = 128: lanes carry d and d + 64).  The grey rows y-2..y+2 of both images
+//                 are staged in LDS, packed by column (four rows in one dword, the fifth in the next), so that the column sum of
+//                 absolute differences of one (x, d) is two v_sad_u8; the 5-column box runs along the row in registers.  C is written,
+//                 the left->right path is carried in registers and written as S; then the wave walks back over the C it has just
+//                 written (every lane reads what it wrote itself) and adds the right->left path into S.
+//   k_sgm_cols    one wave per image column: down, then up, adding both paths into S.
+//   k_sgm_winner  one wave per 64 pixels of a row, four pixels in flight: steps 4..9 of the definition; the right disparity is a strided
+//                 read of S.  Lane i keeps pixel i's result, so the outputs are stored coalesced.
+// A path step is two DPP wave shifts (the neighbours d-1, d+1), a DPP min-scan whose result is read from lane 63, and four v_min.
+// Volumes are uint16 [y][x][d], d innermost: a wave's access is one contiguous 2 D-byte run in every kernel.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "dcmt_sgm.h"
+
+namespace dcmt {
+
+constexpr int kSgmAbsent = 1 << 24;          // a disparity that does not exist: larger than any L_r + p2, small enough to add to
+
+struct SgmK {                                // the scalars of the winner kernel
+    int disparities, uniqueness, disp12;
+    float bf, max_depth;                     // baseline * focal, rounded once
+};
+
+__device__ __forceinline__ int sgm_lane() { return (int)(threadIdx.x & 63u); }
+
+// lane i <- lane i - 1 (lane 0 keeps `edge`), lane i <- lane i + 1 (lane 63 keeps `edge`)
+__device__ __forceinline__ int sgm_from_below(int v, int edge) { return __builtin_amdgcn_update_dpp(edge, v, 0x138 /*wave_shr:1*/, 0xf, 0xf, false); }
+__device__ __forceinline__ int sgm_from_above(int v, int edge) { return __builtin_amdgcn_update_dpp(edge, v, 0x130 /*wave_shl:1*/, 0xf, 0xf, false); }
+
+// the minimum over the wave, in every lane: a DPP scan inside each row of 16, two row broadcasts, lane 63 read back
+__device__ __forceinline__ unsigned sgm_wave_min(unsigned v)
+{
+    int x = (int)v;
+#define DCMT_SGM_MIN_STEP(ctrl, rows) x = (int)min((unsigned)x, (unsigned)__builtin_amdgcn_update_dpp(x, x, ctrl, rows, 0xf, false))
+    DCMT_SGM_MIN_STEP(0x111 /*row_shr:1*/, 0xf);
+    DCMT_SGM_MIN_STEP(0x112 /*row_shr:2*/, 0xf);
+    DCMT_SGM_MIN_STEP(0x114 /*row_shr:4*/, 0xf);
+    DCMT_SGM_MIN_STEP(0x118 /*row_shr:8*/, 0xf);
+    DCMT_SGM_MIN_STEP(0x142 /*row_bcast:15*/, 0xa);
+    DCMT_SGM_MIN_STEP(0x143 /*row_bcast:31*/, 0xc);
+#undef DCMT_SGM_MIN_STEP
+    return (unsigned)__builtin_amdgcn_readlane(x, 63);
+}
+
+// One path of one wave: prev[k] is L_r of the previous pixel for disparity lane + 64 k (kSgmAbsent where that is >= D).
+template <int NPL>
+struct SgmPath {
+    int prev[NPL];
+    // the first pixel of a path
+    __device__ __forceinline__ void start(const int (&c)[NPL])
+    {
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) prev[k] = c[k];
+    }
+    // every other pixel: c[k] is C of this pixel (kSgmAbsent for an absent disparity); prev becomes this pixel's L_r
+    __device__ __forceinline__ void step(const int (&c)[NPL], int p1, int p2)
+    {
+        unsigned mm = (unsigned)prev[0];
+#pragma unroll
+        for (int k = 1; k < NPL; ++k) mm = min(mm, (unsigned)prev[k]);
+        const int m = (int)sgm_wave_min(mm);
+        int next[NPL];
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const int below_edge = k > 0 ? __builtin_amdgcn_readlane(prev[k > 0 ? k - 1 : 0], 63) : kSgmAbsent;
+            const int above_edge = k + 1 < NPL ? __builtin_amdgcn_readlane(prev[k + 1 < NPL ? k + 1 : k], 0) : kSgmAbsent;
+            const int lo = sgm_from_below(prev[k], below_edge) + p1;
+            const int hi = sgm_from_above(prev[k], above_edge) + p1;
+            const int best = min(min(prev[k], m + p2), min(lo, hi));
+            next[k] = c[k] >= kSgmAbsent ? kSgmAbsent : c[k] + best - m;
+        }
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) prev[k] = next[k];
+    }
+};
+
+// One path along a line of n pixels of a frame's volumes, added into S: pixel i is at element first + i * stride (+ the lane's
+// disparity) of C and of S.  The loads run kSgmAhead pixels in front of the dependent chain of path steps; within a line every
+// pixel has its own addresses, and every lane reads and writes only its own disparities.
+constexpr int kSgmAhead = 4;
+template <int NPL>
+__device__ __forceinline__ void sgm_line(const uint16_t* C, uint16_t* S, ptrdiff_t first, ptrdiff_t stride, int n, int lane, int D, int p1, int p2)
+{
+    int cb[kSgmAhead][NPL], sb[kSgmAhead][NPL];
+    const auto load = [&](int i, int (&c)[NPL], int (&sv)[NPL]) {
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const bool have = i < n && lane + 64 * k < D;
+            const ptrdiff_t at = first + (ptrdiff_t)i * stride + (ptrdiff_t)(lane + 64 * k);
+            c[k] = have ? (int)C[at] : kSgmAbsent;
+            sv[k] = have ? (int)S[at] : 0;
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < kSgmAhead; ++j) load(j, cb[j], sb[j]);
+    SgmPath<NPL> path;
+    for (int i = 0; i < n; i += kSgmAhead) {
+#pragma unroll
+        for (int j = 0; j < kSgmAhead; ++j) {
+            if (i + j < n) {
+                if (i + j == 0) path.start(cb[j]); else path.step(cb[j], p1, p2);
+#pragma unroll
+                for (int k = 0; k < NPL; ++k)
+                    if (lane + 64 * k < D)
+                        S[first + (ptrdiff_t)(i + j) * stride + (ptrdiff_t)(lane + 64 * k)] = (uint16_t)(sb[j][k] + path.prev[k]);
+            }
+            load(i + j + kSgmAhead, cb[j], sb[j]);
+        }
+    }
+}
+
+// rows y-2..y+1 of column x of an image in one dword (byte i = row clamp(y - 2 + i)), row y+2 in the low byte of the next
+__device__ __forceinline__ uint2 sgm_pack_column(const uint8_t* img, int rows, int cols, int y, int x)
+{
+    uint32_t w[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int yy = min(max(y - 2 + i, 0), rows - 1);
+        w[i] = img[(size_t)yy * (size_t)cols + (size_t)x];
+    }
+    return make_uint2(w[0] | (w[1] << 8) | (w[2] << 16) | (w[3] << 24), w[4]);
+}
+
+// left, right: [frames][rows][cols]; vol: the chunk's workspace, per frame C then S ([rows][cols][D] uint16 each)
+template <int NPL, bool LDS>
+__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                             uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2)
+{
+    extern __shared__ uint2 sgm_lds[];                      // [cols] left, then [cols] right
+    const int y = (int)blockIdx.x, lane = sgm_lane();
+    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
+    const uint8_t* L = left + frame * px;
+    const uint8_t* R = right + frame * px;
+    uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
+    uint16_t* S = C + ve;
+    if constexpr (LDS) {
+        for (int x = lane; x < cols; x += 64) {
+            sgm_lds[x] = sgm_pack_column(L, rows, cols, y, x);
+            sgm_lds[cols + x] = sgm_pack_column(R, rows, cols, y, x);
+        }
+        __syncthreads();
+    }
+    bool have[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
+    // V(x, d): the sum over the five rows of |left(., x) - right(., max(x - d, 0))|
+    const auto column_sad = [&](int x, int d) -> int {
+        const int xr = max(x - d, 0);
+        uint2 l, r;
+        if constexpr (LDS) { l = sgm_lds[x]; r = sgm_lds[cols + xr]; }
+        else { l = sgm_pack_column(L, rows, cols, y, x); r = sgm_pack_column(R, rows, cols, y, xr); }
+        return (int)__builtin_amdgcn_sad_u8(l.x, r.x, __builtin_amdgcn_sad_u8(l.y, r.y, 0u));
+    };
+    // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
+    int v[NPL][5], box[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int d = lane + 64 * k;
+        const int v0 = column_sad(0, d), v1 = column_sad(min(1, cols - 1), d), v2 = column_sad(min(2, cols - 1), d);
+        v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
+        box[k] = 3 * v0 + v1 + v2;
+    }
+    SgmPath<NPL> path;
+    for (int x = 0; x < cols; ++x) {
+        int c[NPL];
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) c[k] = have[k] ? box[k] : kSgmAbsent;
+        if (x == 0) path.start(c); else path.step(c, p1, p2);
+#pragma unroll
+        for (int k = 0; k < NPL; ++k)
+            if (have[k]) {
+                const size_t at = (size_t)x * (size_t)D + (size_t)(lane + 64 * k);
+                C[at] = (uint16_t)box[k];
+                S[at] = (uint16_t)path.prev[k];
+            }
+        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const int in = x + 3 <= cols - 1 ? column_sad(x + 3, lane + 64 * k) : v[k][4];
+            box[k] += in - v[k][0];
+            v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
+        }
+    }
+    // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
+    sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);
+}
+
+template <int NPL>
+__global__ __launch_bounds__(64 * kSgmWaves) void k_sgm_cols(uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2)
+{
+    const int x = (int)(blockIdx.x * kSgmWaves + threadIdx.x / 64u), lane = sgm_lane();
+    if (x >= cols) return;                                  // whole waves: no barrier follows
+    const size_t frame = blockIdx.y, ve = (size_t)rows * (size_t)cols * (size_t)D, pitch = (size_t)cols * (size_t)D;
+    const uint16_t* C = vol + frame * 2 * ve + (size_t)x * (size_t)D;
+    uint16_t* S = vol + frame * 2 * ve + ve + (size_t)x * (size_t)D;
+    sgm_line<NPL>(C, S, 0, (ptrdiff_t)pitch, rows, lane, D, p1, p2);                                   // top -> bottom
+    sgm_line<NPL>(C, S, (ptrdiff_t)(rows - 1) * (ptrdiff_t)pitch, -(ptrdiff_t)pitch, rows, lane, D, p1, p2);   // bottom -> top
+}
+
+// disp16 and depth: [frames][rows][cols], either may be null
+template <int NPL>
+__global__ __launch_bounds__(64 * kSgmWaves) void k_sgm_winner(const uint16_t* __restrict__ vol, int16_t* __restrict__ disp16,
+                                                               float* __restrict__ depth, int rows, int cols, unsigned segments, SgmK K)
+{
+    const uint64_t wave = (uint64_t)blockIdx.x * kSgmWaves + threadIdx.x / 64u;
+    if (wave >= (uint64_t)rows * segments) return;
+    const int y = (int)(wave / segments), x0 = (int)(wave % segments) * kSgmSegment, lane = sgm_lane();
+    const int D = K.disparities;
+    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
+    const uint16_t* S = vol + frame * 2 * ve + ve + (size_t)y * (size_t)cols * (size_t)D;
+    const int n = min(kSgmSegment, cols - x0);
+    int mine = -16;
+    // S of disparity d of a pixel whose S the wave holds (sv[k]: disparity lane + 64 k); d is the same in every lane
+    const auto held = [&](const unsigned (&sv)[NPL], int d) -> unsigned {
+        unsigned v = (unsigned)__builtin_amdgcn_readlane((int)sv[0], d & 63);
+        if constexpr (NPL > 1) { if (d >= 64) v = (unsigned)__builtin_amdgcn_readlane((int)sv[1], d & 63); }
+        return v;
+    };
+    // kSgmAhead pixels at a time, so that their loads, reductions and gathers overlap; a pixel beyond the segment repeats the last one
+    for (int i0 = 0; i0 < n; i0 += kSgmAhead) {
+        unsigned s[kSgmAhead][NPL], key[kSgmAhead], rkey[kSgmAhead];
+        int xs[kSgmAhead];
+        bool ok[kSgmAhead];
+        // 4. the lowest d of the least S: the minimum of S << 8 | d
+#pragma unroll
+        for (int u = 0; u < kSgmAhead; ++u) {
+            xs[u] = x0 + min(i0 + u, n - 1);
+            const uint16_t* Sp = S + (size_t)xs[u] * (size_t)D;
+            key[u] = 0xffffffffu;
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                const int d = lane + 64 * k;
+                s[u][k] = d < D ? (unsigned)Sp[d] : 0u;
+                if (d < D) key[u] = min(key[u], (s[u][k] << 8) | (unsigned)d);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kSgmAhead; ++u) key[u] = sgm_wave_min(key[u]);
+#pragma unroll
+        for (int u = 0; u < kSgmAhead; ++u) {
+            const int dstar = (int)(key[u] & 0xffu);
+            const unsigned best = key[u] >> 8;
+            // 5. uniqueness
+            bool rival = false;
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                const int d = lane + 64 * k;
+                rival = rival || (d < D && abs(d - dstar) > 1 && s[u][k] * (unsigned)(100 - K.uniqueness) < best * 100u);
+            }
+            // 6. inside
+            ok[u] = __ballot(rival) == 0ull && xs[u] - dstar >= 0;
+            // 7. left-right check: the gather (from column 0 for a pixel that is not inside: its result is not used)
+            rkey[u] = 0xffffffffu;
+            if (K.disp12 >= 0) {
+                const int xp = max(xs[u] - dstar, 0);
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) {
+                    const int d = lane + 64 * k;
+                    if (d < D && xp + d < cols) rkey[u] = min(rkey[u], ((unsigned)S[(size_t)(xp + d) * (size_t)D + (size_t)d] << 8) | (unsigned)d);
+                }
+            }
+        }
+        if (K.disp12 >= 0) {
+#pragma unroll
+            for (int u = 0; u < kSgmAhead; ++u) {
+                const int dr = (int)(sgm_wave_min(rkey[u]) & 0xffu);
+                ok[u] = ok[u] && abs(dr - (int)(key[u] & 0xffu)) <= K.disp12;
+            }
+        }
+        // 8. sub-pixel
+#pragma unroll
+        for (int u = 0; u < kSgmAhead; ++u) {
+            const int dstar = (int)(key[u] & 0xffu);
+            const unsigned best = key[u] >> 8;
+            int d16 = 16 * dstar;
+            if (dstar > 0 && dstar < D - 1) {
+                const unsigned a = held(s[u], dstar - 1), b = held(s[u], dstar + 1);
+                const unsigned den = max(a + b - 2u * best, 1u);
+                d16 += (int)(((a - b + den) * 16u + den) / (2u * den)) - 8;
+            }
+            if (lane == i0 + u) mine = ok[u] ? d16 : -16;       // (a repeated pixel has no lane: i0 + u >= n > every lane that stores)
+        }
+    }
+    if (lane < n) {
+        const size_t at = frame * px + (size_t)y * (size_t)cols + (size_t)(x0 + lane);
+        if (disp16) disp16[at] = (int16_t)mine;
+        if (depth) depth[at] = mine > 0 ? fminf(K.bf / ((float)mine / 16.0f), K.max_depth) : 0.0f;
+    }
+}
+
+}  // namespace dcmt

@@ -1,0 +1,91 @@
+// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_cols, k_sgm_winner) shares with its plan, and the plan itself
+// (plan_sgm): the checks on the arguments of dcmt_sgm_dev, the workspace layout, the chunking of the batch and the launch shapes.
+// Plain C++, no HIP: the plan is tested on a CPU (tests/plan_sgm_test.cpp).
+#ifndef DCMT_SGM_H
+#define DCMT_SGM_H
+
+#include <cstddef>
+#include <cstdint>
+
+#include "dcmt_plan_side.h"    // kOk, kInvalid, ranges_overlap
+
+namespace dcmt {
+
+constexpr int kSgmMinDisp = 16, kSgmMaxDisp = 128;      // D: a multiple of 16 in this range; D > 64: two disparities a lane
+constexpr int kSgmMaxP2 = 10000;                        // S <= 4 * (6375 + p2) <= 65500 fits uint16
+constexpr int kSgmRowThreads = 64;                      // k_sgm_rows: one wave = one row, lane = disparity
+constexpr int kSgmWaves = 4;                            // k_sgm_cols, k_sgm_winner: waves per workgroup
+constexpr int kSgmSegment = 64;                         // k_sgm_winner: pixels of a row per wave, one result a lane
+constexpr size_t kSgmLdsBudget = 64 * 1024;             // k_sgm_rows stages 16 bytes a column: up to 4096 columns, wider rows from global memory
+constexpr uint32_t kSgmLdsPerCol = 16;                  // rows y-2..y+2 of one column, left (8 bytes: 4 + 1 used) and right (8 bytes)
+
+namespace plan {
+
+// bytes of one frame's two volumes (C and S, uint16 [rows][cols][D] each), a multiple of 16 since D is one
+inline size_t sgm_frame_bytes(int rows, int cols, int disparities)
+{
+    return (size_t)4 * (size_t)rows * (size_t)cols * (size_t)disparities;
+}
+
+inline bool sgm_disparities_ok(int d) { return d >= kSgmMinDisp && d <= kSgmMaxDisp && d % 16 == 0; }
+
+struct SgmPlan {
+    int status;                      // kInvalid: see dcmt.h's list for dcmt_sgm_dev (the float parameters are the caller's check)
+    size_t frame_bytes;              // one frame of the workspace
+    size_t volume_elems;             // uint16 elements of one volume of one frame: S of frame f starts volume_elems behind its C
+    int chunk;                       // frames per chunk: min(batch, frames work_bytes holds, 65535)
+    int n_chunks;                    // ceil(batch / chunk); chunk i covers frames [i * chunk, min(batch, (i + 1) * chunk))
+    int per_lane;                    // disparities a lane carries: 1 (D <= 64) or 2
+    bool lds_route;                  // k_sgm_rows stages its five rows in LDS; otherwise it reads them from global memory
+    size_t lds;                      // its dynamic LDS bytes (0 on the global route)
+    unsigned rows_grid_x;            // k_sgm_rows: (rows, frames of the chunk), kSgmRowThreads threads
+    unsigned cols_grid_x;            // k_sgm_cols: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a column
+    unsigned winner_grid_x;          // k_sgm_winner: (ceil(rows * ceil(cols / kSgmSegment) / kSgmWaves), frames), a wave a segment
+    unsigned segments;               // ceil(cols / kSgmSegment)
+};
+
+// frames of chunk i
+inline int sgm_chunk_frames(const SgmPlan& p, int batch, int i)
+{
+    const long long first = (long long)i * p.chunk;
+    return (int)(first + p.chunk <= batch ? p.chunk : batch - first);
+}
+
+// rows, cols, batch >= 1 and within the context's limits
+inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, int p2, int uniqueness, uintptr_t left, uintptr_t right,
+                        uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes)
+{
+    SgmPlan p = {};
+    p.status = kInvalid;
+    if (!left || !right || (!disp16 && !depth) || !work || !sgm_disparities_ok(disparities)) return p;
+    if (p1 < 0 || p1 > p2 || p2 > kSgmMaxP2 || uniqueness < 0 || uniqueness > 100) return p;
+    if (disp16 % 2 != 0 || depth % 4 != 0 || work % 16 != 0) return p;
+    p.frame_bytes = sgm_frame_bytes(rows, cols, disparities);
+    if (work_bytes < p.frame_bytes) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    const uintptr_t at[5] = {left, right, disp16, depth, work};
+    const size_t bytes[5] = {px, px, 2 * px, 4 * px, work_bytes};
+    for (int i = 0; i < 5; ++i)
+        for (int j = (i < 2 ? 2 : i + 1); j < 5; ++j)         // the two inputs may be one image; every other pair is apart
+            if (at[i] && at[j] && ranges_overlap(at[i], bytes[i], at[j], bytes[j])) return p;
+    p.status = kOk;
+    p.volume_elems = p.frame_bytes / 4;
+    const size_t fit = work_bytes / p.frame_bytes;
+    p.chunk = (int)(fit < (size_t)batch ? fit : (size_t)batch);
+    if (p.chunk > 65535) p.chunk = 65535;
+    p.n_chunks = (batch + p.chunk - 1) / p.chunk;
+    p.per_lane = disparities > 64 ? 2 : 1;
+    const size_t lds = (size_t)kSgmLdsPerCol * (size_t)cols;
+    p.lds_route = lds <= kSgmLdsBudget;
+    p.lds = p.lds_route ? lds : 0;
+    p.rows_grid_x = (unsigned)rows;
+    p.cols_grid_x = ((unsigned)cols + kSgmWaves - 1) / kSgmWaves;
+    p.segments = ((unsigned)cols + kSgmSegment - 1) / kSgmSegment;
+    p.winner_grid_x = (unsigned)(((uint64_t)rows * p.segments + kSgmWaves - 1) / kSgmWaves);
+    return p;
+}
+
+}  // namespace plan
+}  // namespace dcmt
+
+#endif

@@ -1,0 +1,74 @@
+// dcmt_sgm.hip -- semi-global stereo matching (dcmt_kernels_sgm.h), a code object of its own: dcmt_default_sgm_params,
+// dcmt_sgm_workspace_bytes and dcmt_sgm_dev.  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's workspace out
+// and cuts the batch into chunks; this file launches what it says.  The single-pair host form, dcmt_sgm, is in dcmt_host.hip.
+#include <initializer_list>
+
+#include "dcmt.h"
+#include "dcmt_ctx.h"
+#include "dcmt_sgm.h"
+#include "dcmt_kernels_sgm.h"
+
+using namespace dcmt;
+
+template <int NPL>
+static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_t* right, int16_t* disp16, float* depth, uint16_t* vol, int rows,
+                      int cols, int frames, const dcmt_sgm_params& P, hipStream_t st)
+{
+    const int D = P.num_disparities;
+    const dim3 rows_grid(pl.rows_grid_x, (unsigned)frames), cols_grid(pl.cols_grid_x, (unsigned)frames), winner_grid(pl.winner_grid_x, (unsigned)frames);
+    if (pl.lds_route)
+        hipLaunchKernelGGL((k_sgm_rows<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2);
+    else
+        hipLaunchKernelGGL((k_sgm_rows<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2);
+    hipLaunchKernelGGL((k_sgm_cols<NPL>), cols_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
+    const SgmK K = {D, P.uniqueness, P.disp12_max_diff, P.baseline * P.focal, P.max_depth};
+    hipLaunchKernelGGL((k_sgm_winner<NPL>), winner_grid, dim3(64 * kSgmWaves), 0, st, (const uint16_t*)vol, disp16, depth, rows, cols, pl.segments, K);
+}
+
+extern "C" {
+
+void dcmt_default_sgm_params(dcmt_sgm_params* p)
+{
+    if (!p) return;
+    p->num_disparities = 64;      // main_sl.cpp:1306: numDisparity * 16
+    p->p1 = 200;
+    p->p2 = 800;
+    p->uniqueness = 10;
+    p->disp12_max_diff = 1;
+    p->baseline = 0.54f;          // :632
+    p->focal = 9.597910e+02f;     // :634
+    p->max_depth = 100.0f;
+}
+
+size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int frames)
+{
+    if (rows < 1 || cols < 1 || frames < 1 || !plan::sgm_disparities_ok(num_disparities)) return 0;
+    return (size_t)frames * plan::sgm_frame_bytes(rows, cols, num_disparities);
+}
+
+int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
+                 const dcmt_sgm_params* params, void* d_work, size_t work_bytes, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if (d_depth)
+        for (const float v : {params->baseline, params->focal, params->max_depth})
+            if (!finite_bits(v) || !(v > 0.0f)) return DCMT_E_INVALID;
+    const plan::SgmPlan pl = plan::plan_sgm(rows, cols, batch, params->num_disparities, params->p1, params->p2, params->uniqueness, (uintptr_t)d_left,
+                                            (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t px = (size_t)rows * (size_t)cols;
+    for (int i = 0; i < pl.n_chunks; ++i) {
+        const size_t first = (size_t)i * (size_t)pl.chunk * px;
+        const int frames = plan::sgm_chunk_frames(pl, batch, i);
+        int16_t* disp = d_disp16 ? d_disp16 + first : nullptr;
+        float* depth = d_depth ? d_depth + first : nullptr;
+        if (pl.per_lane == 1) sgm_chunk<1>(pl, d_left + first, d_right + first, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
+        else sgm_chunk<2>(pl, d_left + first, d_right + first, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
+    }
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+}  // extern "C"

@@ -866,6 +866,68 @@ int dcmt_photo_error(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
                      int rows, int cols, const dcmt_photo_error_params *params,
                      uint8_t *err /* or NULL */, size_t err_row_stride, uint64_t *stats /* [4] or NULL */);
 
+/* ---- dense stereo matching: semi-global matching on a rectified grey pair ------------------------------- */
+
+/* The "PERFORM STEREO MATCHING" block of DC_stereo_lidar/main_sl.cpp:1293-1339 (cv::StereoSGBM, numDisparity * 16 = 64 disparities,
+ * block size 4, a 16-bit fixed-point disparity map of the rectified pair), as an algorithm of this library's own: OpenCV's SGBM --
+ * Birchfield-Tomasi costs on a prefiltered image, its own buffering -- cannot be restated to the bit without a running OpenCV, so the
+ * matcher is STATED HERE, in integers, and the library is bit-exact against this statement (tests/sgm_restatement.py).
+ * Per frame: left, right uint8 grey [rows][cols] (what dcmt_bgr_convert_dev writes).  D = num_disparities, the minimum disparity is 0,
+ * the block is 5 x 5 (block sizes 4 and 5 both give half-width 2 in the reference's call).
+ *   1. pixel cost  AD(y,x,d) = |left(y,x) - right(y, max(x - d, 0))|.
+ *   2. block cost  C(y,x,d) = sum over dy, dx in -2..2 of AD(clamp(y+dy, 0, rows-1), clamp(x+dx, 0, cols-1), d): the clamp replicates the
+ *      AD plane, not the images.  C <= 25 * 255 = 6375.
+ *   3. paths, four directions r (left->right, right->left, top->bottom, bottom->top).  On the first pixel of a path L_r = C; otherwise,
+ *      with m = min over k of L_r(p-r, k):
+ *        L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1) + p1, L_r(p-r,d+1) + p1, m + p2) - m,
+ *      neighbours d-1 < 0 and d+1 >= D absent.  Then C <= L_r <= C + p2, so S = sum over r of L_r <= 4 * (6375 + 10000) = 65500: S and
+ *      every L_r fit uint16, which is why p2 <= 10000.  With p1 = p2 = 0: L_r = C, S = 4 C, plain block matching.
+ *   4. winner      d* = the lowest d that minimises S(y,x,.).
+ *   5. uniqueness  invalid if some d with |d - d*| > 1 has S(d) * (100 - uniqueness) < S(d*) * 100.
+ *   6. inside      invalid if x - d* < 0.
+ *   7. left-right check, if disp12_max_diff >= 0: dR(y,x') = the lowest k that minimises S(y, x'+k, k) over k < D with x'+k < cols;
+ *      invalid if |dR(y, x - d*) - d*| > disp12_max_diff.
+ *   8. sub-pixel   d* = 0 or d* = D-1: frac = 0.  Otherwise a = S(d*-1), b = S(d*+1), den = max(a + b - 2 S(d*), 1),
+ *      frac = floor(((a - b) * 16 + den) / (2 den)) -- the floor, not C's truncation; since |a - b| <= den the unsigned form
+ *      ((a - b + den) * 16 + den) / (2 den) - 8 is the same number.  disp16 = 16 d* + frac.
+ *   9. outputs     d_disp16 int16 [batch][rows][cols]: disp16, -16 where invalid (StereoSGBM::compute's CV_16S convention: 4 fractional
+ *      bits, (minDisparity - 1) * 16).  d_depth f32 [batch][rows][cols]: where disp16 > 0,
+ *      min((baseline * focal) / (disp16 / 16.0f), max_depth), one rounded product and one rounded quotient in f32 (the disparity > 0 /
+ *      clamp rule of retrieve_optimized_depth, :871-879); otherwise 0.  dcmt_stereo_refine_dev, dcmt_photo_error_dev, dcmt_evaluate_dev
+ *      and dcmt_colorize_dev take this plane as it is.  Either output may be NULL, not both.
+ *
+ * DEVICE pointers, stream-ordered.  d_work is the CALLER's workspace (the cost volume C and the sum volume S, uint16 [rows][cols][D]
+ * each, per frame in flight): dcmt_sgm_workspace_bytes(rows, cols, D, frames) bytes hold `frames` frames (0 for arguments the call
+ * would refuse); the call works through the batch in chunks of as many frames as work_bytes holds, at most `batch`.  At
+ * 352 x 1216 x 64 one frame is 110 MB, which is why the workspace is not a context buffer sized by max_batch.  Nothing is carried in
+ * it from call to call and nothing in it need be initialised.  Three kernels per chunk (rows, columns, winner).  Never synchronises,
+ * never allocates, touches none of the state a ctx carries; may be enqueued in front of or behind any other *_dev call.
+ * DCMT_E_INVALID, nothing written: a null ctx, image, params or workspace; both outputs NULL; sizes beyond the ctx limits;
+ * num_disparities not a multiple of 16 in 16..128; p1 < 0, p1 > p2 or p2 > 10000; uniqueness outside 0..100; with d_depth, a baseline,
+ * focal or max_depth that is not finite and > 0; d_disp16 not 2-byte, d_depth not 4-byte or d_work not 16-byte aligned; work_bytes
+ * below one frame; any overlap among the outputs, the inputs and the workspace. */
+typedef struct {
+    int32_t num_disparities;  /* 64      main_sl.cpp:1306 (numDisparity * 16); a multiple of 16 in 16..128 */
+    int32_t p1;               /* 200     0 <= p1 <= p2                                                      */
+    int32_t p2;               /* 800     <= 10000                                                           */
+    int32_t uniqueness;       /* 10      0..100, per cent                                                   */
+    int32_t disp12_max_diff;  /* 1       < 0: no left-right check                                           */
+    float   baseline;         /* 0.54f           main_sl.cpp:632                                            */
+    float   focal;            /* 9.597910e+02f   :634                                                       */
+    float   max_depth;        /* 100.0f                                                                     */
+} dcmt_sgm_params;
+void dcmt_default_sgm_params(dcmt_sgm_params *p);
+size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int frames);
+int dcmt_sgm_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right,
+                 int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
+                 const dcmt_sgm_params *params, void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
+/* HOST pointers, one pair, synchronous (row strides in BYTES: the images >= cols, disp16 >= 2 * cols, depth >= 4 * cols; the stride
+ * of a NULL output is ignored).  The workspace of one frame is allocated for the call.  The same bits as the device call.  What
+ * dcmt_shim::stereo_sgm calls. */
+int dcmt_sgm(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
+             int rows, int cols, const dcmt_sgm_params *params,
+             int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride);
+
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 
 /* Each copies its inputs to the device, runs the device entry point above and copies the result back; device buffers

@@ -368,6 +368,28 @@ inline cv::Mat get_initial_error(const cv::Mat& depth, const cv::Mat& left_gray,
     return out;
 }
 
+// The "PERFORM STEREO MATCHING" block (DC_stereo_lidar/main_sl.cpp:1293-1339: cv::StereoSGBM::compute on the rectified grey pair), as the
+// matcher dcmt.h states (dcmt_sgm): disp16 is CV_16SC1, the disparity in sixteenths of a pixel, -16 where there is none -- the convention
+// of StereoSGBM's CV_16S output -- not OpenCV's own numerics.  left_gray, right_gray: CV_8UC1 of one size (bgr_to_gray above).
+// params == nullptr: dcmt_default_sgm_params (64 disparities, :1306).
+// OpenCV defines CV_16SC1 as a macro; against a cv::Mat stand-in without 16-bit elements the function is left out.
+#ifdef CV_16SC1
+inline void stereo_sgm(const cv::Mat& left_gray, const cv::Mat& right_gray, cv::Mat& disp16, const dcmt_sgm_params* params = nullptr)
+{
+    const int rows = left_gray.rows, cols = left_gray.cols;
+    if (left_gray.empty() || left_gray.type() != CV_8UC1 || right_gray.type() != CV_8UC1 || right_gray.rows != rows || right_gray.cols != cols)
+        throw std::runtime_error("stereo_sgm: the images must be CV_8UC1 of one size");
+    dcmt_sgm_params def;
+    dcmt_default_sgm_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_16SC1);
+    raise(dcmt_sgm(thread_ctx().get(rows, cols), left_gray.ptr<unsigned char>(), left_gray.step[0], right_gray.ptr<unsigned char>(),
+                   right_gray.step[0], rows, cols, params ? params : &def, out.ptr<int16_t>(), out.step[0], nullptr, 0),
+          "stereo_sgm");
+    disp16 = out;
+}
+#endif
+
 // reproject_pc_colors / reproject_pc (DC_stereo_lidar/main_sl.cpp:924-965, :887-922): the records of the ordered point cloud of a
 // CV_32FC1 depth plane, one per pixel with depth > 0, row-major.  bgr: CV_8UC3 of the depth's size, or an empty Mat (then the
 // fourth dword of every record is 1.0f).  params == nullptr: the reference's intrinsics (:927-930).
