@@ -45,6 +45,7 @@ EXPORTS = (
     "dcmt_slic_contours_dev", "dcmt_slic_cluster_means_dev", "dcmt_slic_contours", "dcmt_slic_cluster_means",
     "dcmt_default_photo_error_params", "dcmt_photo_error_dev", "dcmt_photo_error_calib_dev", "dcmt_photo_error",
     "dcmt_default_sgm_params", "dcmt_sgm_workspace_bytes", "dcmt_sgm_dev", "dcmt_sgm",
+    "dcmt_default_speckle_params", "dcmt_filter_speckles_dev", "dcmt_filter_speckles",
 )
 
 
@@ -115,6 +116,11 @@ class SgmParams(ctypes.Structure):
     """Mirror of dcmt_sgm_params (include/dcmt.h)."""
     _fields_ = [("num_disparities", ctypes.c_int32), ("p1", ctypes.c_int32), ("p2", ctypes.c_int32), ("uniqueness", ctypes.c_int32),
                 ("disp12_max_diff", ctypes.c_int32), ("baseline", ctypes.c_float), ("focal", ctypes.c_float), ("max_depth", ctypes.c_float)]
+
+
+class SpeckleParams(ctypes.Structure):
+    """Mirror of dcmt_speckle_params (include/dcmt.h)."""
+    _fields_ = [("max_size", ctypes.c_int32), ("max_diff", ctypes.c_int32), ("new_val", ctypes.c_int32)]
 
 
 class CropSrc(ctypes.Structure):
@@ -248,6 +254,10 @@ def lib() -> ctypes.CDLL:
         L.dcmt_sgm_workspace_bytes.restype = sz
         L.dcmt_sgm_dev.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, sz, vp]
         L.dcmt_sgm.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz]
+        L.dcmt_default_speckle_params.argtypes = [vp]
+        L.dcmt_default_speckle_params.restype = None
+        L.dcmt_filter_speckles_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_filter_speckles.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

@@ -19,6 +19,8 @@
         reference: src/DC_stereo_lidar/main_sl.cpp:618-712 (its data, not its drawing and printing)
     stereo_sgm(left, right) -> the int16 disparity map of a rectified grey pair, in sixteenths of a pixel (-16: none)
         reference: src/DC_stereo_lidar/main_sl.cpp:1293-1339 (cv::StereoSGBM's role and output convention; the matcher is dcmt.h's)
+    filter_speckles(disp16) -> the map with its small components set to -16 (cv::filterSpeckles for CV_16S), and how many pixels changed
+        reference: src/DC_stereo_lidar/main_sl.cpp:1301-1302 (speckleWindowSize, speckleRange: what StereoSGBM applies to its output)
 
 numpy arrays go through the host entry point (dcmt_complete_f32: H2D, kernels, D2H, exact
 hole-closure loop); torch CUDA tensors go through the device entry point on torch's current
@@ -215,6 +217,40 @@ def make_sgm_params(num_disparities: int | None = None, p1: int | None = None, p
         if not (np.isfinite(v) and v > 0):
             raise ValueError(f"{name} = {v!r}: finite and > 0")
     return p
+
+
+def make_speckle_params(max_size: int | None = None, max_diff: int | None = None, new_val: int | None = None) -> L.SpeckleParams:
+    """dcmt_speckle_params: the reference's speckle window and range (SL/main_sl.cpp:1301-1302: 200 pixels, 2 disparities = 32
+    sixteenths) and dcmt_sgm_dev's "none" (-16) unless overridden.  Raises ValueError on what dcmt_filter_speckles_dev refuses of
+    them: max_size < 0, max_diff outside 0..65535, new_val outside int16."""
+    p = L.SpeckleParams()
+    L.lib().dcmt_default_speckle_params(ctypes.byref(p))
+    for name, v in (("max_size", max_size), ("max_diff", max_diff), ("new_val", new_val)):
+        if v is not None:
+            if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} = {v!r} is not an int32")
+            setattr(p, name, int(v))
+    if p.max_size < 0:
+        raise ValueError(f"max_size = {p.max_size}: >= 0")
+    if not 0 <= p.max_diff <= 65535:
+        raise ValueError(f"max_diff = {p.max_diff}: 0..65535")
+    if not -32768 <= p.new_val <= 32767:
+        raise ValueError(f"new_val = {p.new_val}: an int16")
+    return p
+
+
+def _speckle_kw(speckle_window, speckle_range) -> dict | None:
+    """StereoSGBM's speckleWindowSize / speckleRange (whole disparities) as the fields of make_speckle_params; None: no filter."""
+    if speckle_window is None and speckle_range is None:
+        return None
+    kw = {}
+    if speckle_window is not None:
+        kw["max_size"] = speckle_window
+    if speckle_range is not None:
+        if int(speckle_range) != speckle_range:
+            raise ValueError(f"speckle_range = {speckle_range!r}: whole disparities")
+        kw["max_diff"] = 16 * int(speckle_range)
+    return kw if make_speckle_params(**kw).max_size > 0 else None
 
 
 def sgm_workspace_bytes(rows: int, cols: int, num_disparities: int = 64, frames: int = 1) -> int:
@@ -772,7 +808,8 @@ class Context:
 
     # ---- dense stereo matching (dcmt_sgm*) --------------------------------------------------
     def sgm_dev(self, d_left, d_right, disp16: bool = True, depth: bool = False, d_disp16=None, d_depth=None, d_work=None,
-                frames_in_flight: int | None = None, stream: int | None = None, **kw):
+                frames_in_flight: int | None = None, stream: int | None = None, speckle_window: int | None = None,
+                speckle_range: int | None = None, **kw):
         """Semi-global stereo matching on the device (dcmt_sgm_dev, as include/dcmt.h states it; the reference's cv::StereoSGBM block,
         SL/main_sl.cpp:1293-1339): a rectified grey pair (uint8 CUDA tensors [batch][rows][cols], what bgr_convert_dev(gray=True) writes)
         -> the int16 disparity map in sixteenths of a pixel (-16: invalid) and / or the f32 depth plane stereo_refine_dev,
@@ -780,13 +817,18 @@ class Context:
         a d_disp16 / d_depth that is given is written and wanted.  d_work: the workspace, a CUDA tensor of at least
         sgm_workspace_bytes(rows, cols, D, 1) bytes, 16-byte aligned; the batch is worked through in chunks of as many frames as it
         holds.  Without one a workspace for frames_in_flight frames (default: the batch, but no more than 1 GiB and at least one frame)
-        is allocated on the stream the call enqueues on.  kw: the fields of make_sgm_params."""
+        is allocated on the stream the call enqueues on.  kw: the fields of make_sgm_params.
+        speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (whole disparities: max_diff = 16 *
+        speckle_range; the reference's are 200 and 2).  With both None nothing changes and no further call is made; with a window > 0
+        filter_speckles_dev is enqueued behind the matcher on the same stream, in place on both outputs."""
         import torch
         assert _is_dev(d_left, torch.uint8) and _is_dev(d_right, torch.uint8) and d_left.shape == d_right.shape
         b, r, c = _brc(d_left)
         want_disp, want_depth = disp16 or d_disp16 is not None, depth or d_depth is not None
         p = make_sgm_params(for_depth=want_depth, **kw)
         assert want_disp or want_depth
+        speckle = _speckle_kw(speckle_window, speckle_range)
+        asked_disp, want_disp = want_disp, want_disp or speckle is not None        # the filter works on the disparities
         one = sgm_workspace_bytes(r, c, p.num_disparities, 1)
         with _on_stream(stream, d_left):
             if want_disp and d_disp16 is None:
@@ -804,11 +846,14 @@ class Context:
                                   d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p), d_work.data_ptr(),
                                   d_work.numel() * d_work.element_size(), _stream(stream, d_left))
         _check(st, "dcmt_sgm_dev")
-        return (d_disp16, d_depth) if want_disp and want_depth else d_disp16 if want_disp else d_depth
+        if speckle is not None:
+            self.filter_speckles_dev(d_disp16, d_depth=d_depth if want_depth else None, d_out=d_disp16, stream=stream, **speckle)
+        return (d_disp16, d_depth) if asked_disp and want_depth else d_disp16 if asked_disp else d_depth
 
-    def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, **kw):
+    def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, speckle_window: int | None = None,
+            speckle_range: int | None = None, **kw):
         """One pair of host memory (dcmt_sgm, synchronous; any row stride): (int16 [rows][cols], f32 [rows][cols]), or the one that is
-        wanted."""
+        wanted.  speckle_window, speckle_range: as sgm_dev; the filter is a second host call (dcmt_filter_speckles), in place."""
         imgs = []
         for a in (left, right):
             a = np.asarray(a, dtype=np.uint8)
@@ -816,6 +861,8 @@ class Context:
             imgs.append(a if a.strides[1] == 1 else np.ascontiguousarray(a))
         assert imgs[0].shape == imgs[1].shape and (disp16 or depth)
         rows, cols = imgs[0].shape
+        speckle = _speckle_kw(speckle_window, speckle_range)
+        asked_disp, disp16 = disp16, disp16 or speckle is not None
         d = np.empty((rows, cols), dtype=np.int16) if disp16 else None
         z = np.empty((rows, cols), dtype=np.float32) if depth else None
         p = make_sgm_params(for_depth=depth, **kw)
@@ -823,7 +870,60 @@ class Context:
                               d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None,
                               z.strides[0] if depth else 0)
         _check(st, "dcmt_sgm")
-        return (d, z) if disp16 and depth else d if disp16 else z
+        if speckle is not None:
+            sp = make_speckle_params(**speckle)
+            st = L.lib().dcmt_filter_speckles(self._h, d.ctypes.data, d.strides[0], d.ctypes.data, d.strides[0], z.ctypes.data if depth else None,
+                                              z.strides[0] if depth else 0, rows, cols, ctypes.byref(sp), None)
+            _check(st, "dcmt_filter_speckles")
+        return (d, z) if asked_disp and depth else d if asked_disp else z
+
+    # ---- the speckle filter of a disparity map (dcmt_filter_speckles*) -------------------------
+    def filter_speckles_dev(self, d_disp16, d_depth=None, d_out=None, removed: bool = False, d_removed=None, stream: int | None = None, **kw):
+        """cv::filterSpeckles for a 16-bit disparity map on the device (dcmt_filter_speckles_dev, as include/dcmt.h states it): every
+        4-connected component of pixels != new_val under the edge relation |a - b| <= max_diff that has at most max_size pixels is
+        set to new_val, without synchronising.  d_disp16: an int16 CUDA tensor [batch][rows][cols] (what sgm_dev writes); d_out: where
+        the result goes (may be d_disp16 itself: in place), allocated where not given; d_depth: the f32 plane sgm_dev wrote beside
+        it, set to 0 IN PLACE where the call removes a disparity.  Returns d_out, or (d_out, removed) with removed=True or a
+        d_removed: the int32 CUDA tensor [batch] of the pixels changed per frame.  kw: max_size (200), max_diff (32, in sixteenths),
+        new_val (-16).  Outputs that are not given are allocated on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_disp16, torch.int16)
+        b, r, c = _brc(d_disp16)
+        p = make_speckle_params(**kw)
+        want_removed = removed or d_removed is not None
+        with _on_stream(stream, d_disp16):
+            if d_out is None:
+                d_out = torch.empty(tuple(d_disp16.shape), dtype=torch.int16, device=d_disp16.device)
+            if want_removed and d_removed is None:
+                d_removed = torch.empty((b,), dtype=torch.int32, device=d_disp16.device)
+        assert _is_dev(d_out, torch.int16) and d_out.numel() == b * r * c
+        assert d_depth is None or (_is_dev(d_depth, torch.float32) and d_depth.numel() == b * r * c)
+        assert d_removed is None or (_is_dev(d_removed) and d_removed.element_size() == 4 and d_removed.numel() == b)
+        st = L.lib().dcmt_filter_speckles_dev(self._h, d_disp16.data_ptr(), d_out.data_ptr(), d_depth.data_ptr() if d_depth is not None else None,
+                                              r, c, b, ctypes.byref(p), d_removed.data_ptr() if want_removed else None,
+                                              _stream(stream, d_disp16))
+        _check(st, "dcmt_filter_speckles_dev")
+        return (d_out, d_removed) if want_removed else d_out
+
+    def filter_speckles(self, disp16: np.ndarray, depth: np.ndarray | None = None, **kw):
+        """One frame of host memory (dcmt_filter_speckles, synchronous; any row stride): (the filtered int16 plane, the number of
+        pixels changed), or with a depth plane (f32 [rows][cols]) (plane, the depth with the removed pixels at 0, count).  Both are
+        new arrays; the arguments are not modified."""
+        d = np.asarray(disp16, dtype=np.int16)
+        assert d.ndim == 2
+        d = d if d.strides[1] == 2 else np.ascontiguousarray(d)
+        rows, cols = d.shape
+        out = np.empty((rows, cols), dtype=np.int16)
+        z = None
+        if depth is not None:
+            z = np.array(depth, dtype=np.float32, order="C")
+            assert z.shape == d.shape
+        n = ctypes.c_uint32(0)
+        p = make_speckle_params(**kw)
+        st = L.lib().dcmt_filter_speckles(self._h, d.ctypes.data, d.strides[0], out.ctypes.data, out.strides[0], z.ctypes.data if z is not None else None,
+                                          z.strides[0] if z is not None else 0, rows, cols, ctypes.byref(p), ctypes.byref(n))
+        _check(st, "dcmt_filter_speckles")
+        return (out, int(n.value)) if z is None else (out, z, int(n.value))
 
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
@@ -1275,13 +1375,23 @@ def get_initial_error(depth, left, right, **params):
     return e, {k: int(v) for k, v in zip(PHOTO_STATS, s)}
 
 
-def stereo_sgm(left, right, depth: bool = False, **params):
+def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = None, speckle_range: int | None = None, **params):
     """Semi-global matching of one rectified host pair (dcmt_sgm): the int16 disparity map in sixteenths of a pixel, -16 where invalid,
     as cv::StereoSGBM::compute returns it (SL/main_sl.cpp:1293-1339); with depth=True (disp16, depth).  left, right: grey uint8
-    [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params."""
+    [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params.
+    speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (the reference's: 200, 2); None, None: no filter."""
     imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
     imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
-    return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, **params)
+    return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, speckle_window=speckle_window,
+                                                                speckle_range=speckle_range, **params)
+
+
+def filter_speckles(disp16, depth=None, **params):
+    """cv::filterSpeckles of one int16 host disparity map (dcmt_filter_speckles, as include/dcmt.h states it): (the filtered plane,
+    the number of pixels changed), or with a depth plane (plane, depth, count).  params: max_size (200), max_diff (32, in
+    sixteenths), new_val (-16)."""
+    d = np.asarray(disp16, dtype=np.int16)
+    return _ctx_for(d.shape[0], d.shape[1], 1).filter_speckles(d, depth, **params)
 
 
 def depth_to_u16(depth, scale: float = 256.0):

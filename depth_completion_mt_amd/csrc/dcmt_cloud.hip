@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h),
 // dcmt_photo_error_dev and dcmt_photo_error_calib_dev (dcmt_kernels_photo.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "dcmt_kernels_reproject.h"
 #include "dcmt_kernels_bilateral.h"
 #include "dcmt_kernels_connect.h"
+#include "dcmt_kernels_speckle.h"
 #include "dcmt_kernels_contour.h"
 #include "dcmt_kernels_photo.h"
 
@@ -459,6 +460,46 @@ int dcmt_slic_connectivity_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows,
     hipLaunchKernelGGL(k_conn_scan, dim3(batch), dim3(256), 0, st, ctx->conn_slab.p, pl.strips, d_counts);
     hipLaunchKernelGGL(k_conn_rank, dim3(pl.strips, batch), dim3(256), 0, st, B, r, c, pl.band_rows, ctx->conn_slab.p);
     hipLaunchKernelGGL(k_conn_relabel, dim3(pl.px_x, batch), dim3(256), 0, st, A, B, pl.n, c, pl.kbits, d_out);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- the speckle filter of a disparity map (dcmt_kernels_speckle.h) ----------------------------------------------------------------
+extern "C" {
+
+void dcmt_default_speckle_params(dcmt_speckle_params* p)
+{
+    if (!p) return;
+    p->max_size = 200;      // main_sl.cpp:1301, :1315: speckleWindowSize
+    p->max_diff = 32;       // :1302, :1316: 16 * speckleRange, in the sixteenths disp16 is in
+    p->new_val = -16;       // what dcmt_sgm_dev writes for "none"
+}
+
+// The launches plan_speckles names, on pp[0] and pp[1] (scratch every completion call rewrites before it reads it).  None of the
+// context's carried state is read or written, and nothing is allocated.
+int dcmt_filter_speckles_dev(dcmt_ctx* ctx, const int16_t* d_disp16, int16_t* d_out, float* d_depth, int rows, int cols, int batch,
+                             const dcmt_speckle_params* params, uint32_t* d_removed, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const plan::SpecklePlan pl = plan::plan_speckles(rows, cols, batch, params->max_size, params->max_diff, params->new_val, (uintptr_t)d_disp16,
+                                                     (uintptr_t)d_out, (uintptr_t)d_depth, (uintptr_t)d_removed);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* A = reinterpret_cast<uint32_t*>(ctx->pp[0].p);
+    uint32_t* B = reinterpret_cast<uint32_t*>(ctx->pp[1].p);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, max_size = (uint32_t)params->max_size;
+    const int32_t nv = params->new_val, md = params->max_diff;
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_removed, 0, pl.clear_bytes, st));
+    hipLaunchKernelGGL(k_spk_local, dim3(pl.local_x, batch), dim3(256), 0, st, d_disp16, r, c, pl.tiles_x, pl.kbits, nv, md, A, B);
+    if (pl.border_x > 0) hipLaunchKernelGGL(k_spk_border, dim3(pl.border_x, batch), dim3(256), 0, st, d_disp16, r, c, pl.pairs_v, pl.pairs, pl.kbits, nv, md, A);
+    hipLaunchKernelGGL(k_conn_flatten, dim3(pl.px_x, batch), dim3(256), 0, st, pl.n, c, pl.kbits, A, B);
+    if (pl.vec == 4)
+        hipLaunchKernelGGL(k_spk_apply<4>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.n, c, pl.kbits, nv, max_size, d_out, d_depth, d_removed);
+    else
+        hipLaunchKernelGGL(k_spk_apply<1>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.n, c, pl.kbits, nv, max_size, d_out, d_depth, d_removed);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

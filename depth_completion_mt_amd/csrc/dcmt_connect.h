@@ -1,4 +1,4 @@
-// dcmt_connect.h -- what the kernels of dcmt_kernels_connect.h (compiled in dcmt_cloud.hip) share with the host code that plans
+// dcmt_connect.h -- what the kernels of dcmt_kernels_connect.h and dcmt_kernels_speckle.h (compiled in dcmt_cloud.hip) share with the host code that plans
 // their launches (dcmt_plan_side.h).  No HIP.
 #pragma once
 #include <cstdint>

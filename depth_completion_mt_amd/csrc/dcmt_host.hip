@@ -213,6 +213,19 @@ int dcmt_sgm(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* righ
     return rc == DCMT_OK ? fetch(ctx, {&d, &z}) : rc;
 }
 
+int dcmt_filter_speckles(dcmt_ctx* ctx, const int16_t* disp16, size_t drs, int16_t* out, size_t ors, float* depth, size_t zrs, int rows, int cols,
+                         const dcmt_speckle_params* params, uint32_t* removed)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !disp16 || !out || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t row = sizeof(int16_t) * (size_t)cols;
+    Plane in(disp16, drs, row, rows), o(out, ors, row, rows), z(depth, zrs, sizeof(float) * (size_t)cols, rows), n(removed, sizeof(uint32_t));
+    int rc = stage(ctx, {&in, &z}, {&o, &n});
+    if (rc == DCMT_OK)
+        rc = dcmt_filter_speckles_dev(ctx, (const int16_t*)in.dev, (int16_t*)o.dev, (float*)z.dev, rows, cols, 1, params, (uint32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &z, &n}) : rc;
+}
+
 int dcmt_evaluate(dcmt_ctx* ctx, const float* gt, size_t grs, const float* pred, size_t prs, int rows, int cols, float thresh, int mode,
                   dcmt_eval_frame* out)
 {

@@ -305,6 +305,57 @@ inline ConnPlan plan_connectivity(int rows, int cols, int batch, int n_centers, 
     return p;
 }
 
+// ---- dcmt_filter_speckles_dev ---------------------------------------------------------------------------------------------
+// The speckle filter of a 16-bit disparity map (dcmt_kernels_speckle.h): a clear of the counts (where they are wanted) and four
+// launches whose grids depend on the shape alone (the border merge is left out where a frame is one tile), on the context's two
+// 4 B/px planes; the tiles and the pairs are those of plan_connectivity.  The checks on the arguments are here as well, tested
+// without a device: out may BE disp (the last kernel is the only writer of out and depth, and a thread reads its pixels before it
+// writes them), any other overlap among disp, out, depth and removed is refused.
+struct SpecklePlan {
+    int status;                      // kInvalid: a null or misaligned pointer, max_size < 0, max_diff outside 0..65535, new_val outside
+                                     // int16, buffers that overlap
+    uint32_t n;                      // pixels per frame
+    uint32_t kbits;                  // conn_key_bits(rows)
+    uint32_t tiles_x, tiles_y;
+    unsigned local_x;                // k_spk_local: (tiles_x * tiles_y, batch)
+    uint32_t pairs_v, pairs;         // pixel pairs across vertical tile edges, across all tile edges
+    unsigned border_x;               // k_spk_border: (border_x, batch); 0: one tile, no launch
+    unsigned px_x;                   // k_conn_flatten: (px_x, batch), one thread per pixel
+    int vec;                         // k_spk_apply<vec>: 4 where a frame is a multiple of 4 pixels and disp and out are 8-byte aligned, else 1
+    unsigned apply_x;                // its grid: (apply_x, batch)
+    size_t clear_bytes;              // hipMemsetAsync of removed: 4 bytes a frame (0: no counts wanted)
+};
+
+// rows, cols, batch >= 1 and within the context's limits; depth, removed: 0 = not wanted
+inline SpecklePlan plan_speckles(int rows, int cols, int batch, int64_t max_size, int64_t max_diff, int64_t new_val, uintptr_t disp, uintptr_t out,
+                                 uintptr_t depth, uintptr_t removed)
+{
+    SpecklePlan p = {};
+    p.status = kInvalid;
+    if (!disp || !out || disp % 2 != 0 || out % 2 != 0 || depth % 4 != 0 || removed % 4 != 0) return p;
+    if (max_size < 0 || max_size > 0x7fffffff || max_diff < 0 || max_diff > 65535 || new_val < -32768 || new_val > 32767) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols, rb = sizeof(uint32_t) * (size_t)batch;
+    if (out != disp && ranges_overlap(disp, 2 * px, out, 2 * px)) return p;
+    if (depth && (ranges_overlap(depth, 4 * px, disp, 2 * px) || ranges_overlap(depth, 4 * px, out, 2 * px))) return p;
+    if (removed && (ranges_overlap(removed, rb, disp, 2 * px) || ranges_overlap(removed, rb, out, 2 * px) ||
+                    (depth && ranges_overlap(removed, rb, depth, 4 * px))))
+        return p;
+    p.status = kOk;
+    p.n = (uint32_t)rows * (uint32_t)cols;
+    p.kbits = (uint32_t)conn_key_bits(rows);
+    p.tiles_x = ((uint32_t)cols + kConnTW - 1) / kConnTW;
+    p.tiles_y = ((uint32_t)rows + kConnTH - 1) / kConnTH;
+    p.local_x = p.tiles_x * p.tiles_y;
+    p.pairs_v = (p.tiles_x - 1) * (uint32_t)rows;
+    p.pairs = p.pairs_v + (p.tiles_y - 1) * (uint32_t)cols;
+    p.border_x = (p.pairs + 255) / 256;
+    p.px_x = (p.n + 255) / 256;
+    p.vec = p.n % 4 == 0 && disp % 8 == 0 && out % 8 == 0 ? 4 : 1;
+    p.apply_x = (p.n / (uint32_t)p.vec + 255) / 256;
+    p.clear_bytes = removed ? rb : 0;
+    return p;
+}
+
 // ---- dcmt_slic_contours_dev, dcmt_slic_cluster_means_dev ------------------------------------------------------------------
 // The two pixel renderings of SLIC (dcmt_kernels_contour.h), three launches each whose grids depend on the shape alone.  The
 // contours borrow pp[0] for the code bytes and pp[1] for the taken bytes, 1 B/px each, both [batch][cols][rows]; the means borrow

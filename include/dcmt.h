@@ -928,6 +928,54 @@ int dcmt_sgm(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const u
              int rows, int cols, const dcmt_sgm_params *params,
              int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride);
 
+/* ---- the speckle filter of a disparity map ------------------------------------------------------------- */
+
+/* The step cv::StereoSGBM runs on its own output: small connected blobs of disparity that disagree with their surroundings become
+ * invalid.  The reference names its parameters beside the matcher in every stereo main (DC_stereo_lidar/main_sl.cpp:1301-1302,
+ * :1315-1316: speckleWindowSize = 200, speckleRange = 2), and StereoSGBM applies them as filterSpeckles on (disp,
+ * (minDisparity - 1) * 16, speckleWindowSize, 16 * speckleRange).  This is cv::filterSpeckles with (img, newVal, maxSpeckleSize,
+ * maxDiff) for CV_16S as OpenCV documents it: a flood fill over a symmetric neighbour relation, so its result is the connected
+ * components of a graph, independent of the scan order, and it is STATED HERE to the last bit, in integers.  No OpenCV is run; the
+ * library is bit-exact against two restatements of this statement (tests/speckle_restatement.py).
+ * Per frame: disp16 int16 [rows][cols]; parameters max_size, max_diff, new_val.
+ *   1. a pixel is LIVE iff its value != new_val.
+ *   2. two live pixels that are 4-neighbours share an EDGE iff |a - b| <= max_diff, the difference taken in int arithmetic: -32768
+ *      against 32767 is 65535, never a wrapped value.
+ *   3. a COMPONENT is a connected component of the live pixels under those edges.  The relation is not transitive: the ramp 0,
+ *      max_diff, 2 * max_diff, ... is one component.
+ *   4. a component of size <= max_size is a speckle: each of its pixels becomes new_val.  max_size = 0 changes nothing.
+ *   5. every other pixel keeps its bits; pixels equal to new_val are never touched.
+ * d_depth, f32 [batch][rows][cols], modified IN PLACE, or NULL: a pixel whose disparity this call turned into new_val becomes +0.0f,
+ * every other pixel keeps its bits -- the plane dcmt_sgm_dev wrote beside disp16 stays consistent without being recomputed.
+ * d_removed, uint32 [batch], or NULL: the number of pixels the call changed in each frame.  Integer sums: the same bits in any order.
+ * The result is independent of the batch size, the frame's position in the batch, alignment, launch geometry and the run.
+ *
+ * DEVICE pointers, stream-ordered.  d_disp16 and d_out contiguous int16 [batch][rows][cols], 2-byte aligned (8-byte aligned planes of
+ * frames of a multiple of 4 pixels take the wide accesses; the same bits either way); d_out may BE d_disp16, which gives the bits of
+ * an out-of-place call: the last kernel is the only writer of d_out and d_depth.  A clear of d_removed (where given) and four kernels,
+ * three where a frame is a single tile of 64 x 16 pixels, whatever the data.  Never synchronises, never allocates.  Scratch: the two
+ * planes of one 32-bit word per pixel the ctx allocates when it is created, the ones dcmt_slic_connectivity_dev borrows; no other
+ * ctx state is touched (no flag ring, no winner plane, not what dcmt_last_path reports): may be enqueued in front of or behind any
+ * other *_dev call of the ctx on the same stream.
+ * DCMT_E_INVALID, nothing written: a null ctx, input, output or params; sizes or batch beyond the ctx limits; max_size < 0; max_diff
+ * outside 0..65535; new_val outside int16; d_disp16 or d_out not 2-byte aligned, d_depth or d_removed not 4-byte aligned; any overlap
+ * among the buffers other than d_out == d_disp16 exactly. */
+typedef struct {
+    int32_t max_size;     /* 200   main_sl.cpp:1301 speckleWindowSize; >= 0                                  */
+    int32_t max_diff;     /* 32    16 * speckleRange (:1302), in sixteenths, the unit of disp16; 0..65535    */
+    int32_t new_val;      /* -16   what dcmt_sgm_dev writes for "none"; an int16                             */
+} dcmt_speckle_params;
+void dcmt_default_speckle_params(dcmt_speckle_params *p);
+int dcmt_filter_speckles_dev(dcmt_ctx *ctx, const int16_t *d_disp16, int16_t *d_out /* may be d_disp16 */,
+                             float *d_depth /* in place, or NULL */, int rows, int cols, int batch,
+                             const dcmt_speckle_params *params, uint32_t *d_removed /* [batch] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: disp16 and out >= 2 * cols, depth >= 4 * cols; the stride of a NULL
+ * depth is ignored); out may be disp16; removed: one uint32 or NULL.  The same bits as the device call.  What
+ * dcmt_shim::filter_speckles calls. */
+int dcmt_filter_speckles(dcmt_ctx *ctx, const int16_t *disp16, size_t row_stride, int16_t *out, size_t out_row_stride,
+                         float *depth /* or NULL */, size_t depth_row_stride, int rows, int cols,
+                         const dcmt_speckle_params *params, uint32_t *removed /* or NULL */);
+
 /* ---- the same three on HOST memory (one frame, synchronous): what the cv::Mat shim calls ---------------- */
 
 /* Each copies its inputs to the device, runs the device entry point above and copies the result back; device buffers

@@ -388,6 +388,18 @@ inline void stereo_sgm(const cv::Mat& left_gray, const cv::Mat& right_gray, cv::
           "stereo_sgm");
     disp16 = out;
 }
+
+// cv::filterSpeckles(disp16, new_val, max_size, max_diff) for a CV_16SC1 disparity map, its argument order, in place, as dcmt.h
+// states it (dcmt_filter_speckles): what StereoSGBM runs on its output with ((minDisparity - 1) * 16, speckleWindowSize,
+// 16 * speckleRange) -- (-16, 200, 32) for the reference's matcher (main_sl.cpp:1301-1302).  Arguments the C call refuses throw.
+inline void filter_speckles(cv::Mat& disp16, int new_val, int max_size, int max_diff)
+{
+    if (disp16.empty() || disp16.type() != CV_16SC1) throw std::runtime_error("filter_speckles: the map must be CV_16SC1");
+    const dcmt_speckle_params p = {max_size, max_diff, new_val};
+    raise(dcmt_filter_speckles(thread_ctx().get(disp16.rows, disp16.cols), disp16.ptr<int16_t>(), disp16.step[0], disp16.ptr<int16_t>(),
+                               disp16.step[0], nullptr, 0, disp16.rows, disp16.cols, &p, nullptr),
+          "filter_speckles");
+}
 #endif
 
 // reproject_pc_colors / reproject_pc (DC_stereo_lidar/main_sl.cpp:924-965, :887-922): the records of the ordered point cloud of a
