@@ -752,6 +752,66 @@ def reproject_case(g, calib, nearest):
     return FrameCase(name, g, (4,), sources, reference, {"out": ((g.rows, g.cols), f32)}, call, tables=tables, scratch=0 if nearest else 4 * g.total_px)
 
 
+# ---------------------------------------------------------------------------------------------------------------- stereo matching
+SGM_D, SGM_SLOTS = 16, 4096          # disparities; frames the workspace holds
+SGM_KW = dict(num_disparities=SGM_D, focal=80.0)        # baseline * focal = 43.2: no disparity from 1 px on is clamped to max_depth
+
+
+def sgm_figures(g):
+    """The chunking of dcmt_sgm_dev at SGM_D disparities through a workspace of SGM_SLOTS frames (plan_sgm, csrc/dcmt_sgm.h), restated:
+    (bytes of one frame's two volumes, chunks, frames of the last chunk, the slot that holds byte 2^32 of the workspace)."""
+    one = 4 * g.px * SGM_D
+    n_chunks = -(-g.batch // SGM_SLOTS)
+    return one, n_chunks, g.batch - (n_chunks - 1) * SGM_SLOTS, P32 // one
+
+
+def check_sgm_figures():
+    one, n_chunks, last, slot = sgm_figures(A)
+    assert one == 1_081_344 and SGM_SLOTS * one == 4_429_185_024 > P32 and (n_chunks, last) == (16, 4095)
+    assert slot == 3971 and slot * one < P32 < (slot + 1) * one and slot + 1 < last         # the boundary lies inside slot 3971, in every chunk
+    assert 2 * A.total_px > P31 and 4 * A.total_px > P32                                  # disp16 passes 2^31 bytes, depth 2^32
+
+
+check_sgm_figures()
+
+
+def sgm_extra_frames(g):
+    """Beside the plane boundaries: in the first, a middle and the last chunk the frames whose slots hold byte 2^32 of the workspace
+    and the slot behind it, and both sides of the first, a middle and the last chunk seam."""
+    one, n_chunks, last, slot = sgm_figures(g)
+    chunks = (0, n_chunks // 2, n_chunks - 1)
+    frames = [c * SGM_SLOTS + s for c in chunks for s in (slot, slot + 1)]
+    frames += [c * SGM_SLOTS + e for c in (1, n_chunks // 2, n_chunks - 1) for e in (-1, 0)]
+    assert all(0 <= f < g.batch for f in frames) and len(set(frames)) == 12
+    return frames
+
+
+def sgm_case(g):
+    """dcmt_sgm_dev, both outputs: the chunk loop's offsets into four planes, a workspace that passes 2^32 bytes itself, frames in
+    grid y.  Sources: shifted pairs, exact and half in turn, every one with a seed and (in turn) a shift of its own."""
+    import sgm_restatement as SR
+    name = f"sgm_dev {g.name}"
+    one = sgm_figures(g)[0]
+    assert api.sgm_workspace_bytes(g.rows, g.cols, SGM_D, 1) == one
+
+    def sources(lay):
+        pairs = [SR.shifted_pair(g.rows, g.cols, 2600 + s, 1 + s % 14, half=s % 2 == 1) for s in range(lay.n_src)]
+        return {"left": stack([p[0] for p in pairs]), "right": stack([p[1] for p in pairs])}
+
+    def reference(src, lay):
+        res = [SR.vectorised(l, r, **SGM_KW) for l, r in zip(src["left"], src["right"])]
+        return {"disp16": stack([r[0] for r in res]), "depth": stack([r[1] for r in res])}
+
+    def call(ctx, t, o, lay):
+        import torch
+        work = torch.empty(SGM_SLOTS * one, dtype=torch.uint8, device="cuda")
+        assert work.numel() > P32
+        ctx.sgm_dev(t["left"], t["right"], d_disp16=o["disp16"], d_depth=o["depth"], d_work=work, **SGM_KW)
+
+    return FrameCase(name, g, (1, 2, 4), sources, reference, {"disp16": ((g.rows, g.cols), np.int16), "depth": ((g.rows, g.cols), f32)}, call,
+                     scratch=SGM_SLOTS * one, extra=sgm_extra_frames(g))
+
+
 # ---------------------------------------------------------------------------------------------------------------- SLIC
 SLIC_STEP, SLIC_NC = 16, 40
 
@@ -1124,7 +1184,7 @@ def cases():
         made += [stereo_case(A, False), stereo_case(A, True), evaluate_case(A, False), evaluate_case(A, True), colorize_case(A)]
         made += [CloudCase(A, False), CloudCase(A, True), gaussian_case(A), bilateral_case(A)]
         made += [reproject_case(A, calib, nearest) for nearest in (False, True) for calib in (False, True)]
-        made += [bgr_convert_case(A), depth_to_u16_case(A), CropCase(A, 4), CropCase(A, 1)]
+        made += [bgr_convert_case(A), depth_to_u16_case(A), CropCase(A, 4), CropCase(A, 1), sgm_case(A)]
         made += [complete_case(B, "default"), complete_b_one_off_grid(), complete_u16_case(B), labeled_case(B, "synth")]
         made += [colorize_case(C), bgr_convert_case(C), depth_to_u16_case(C), CloudRefusalCase(C), evaluate_case(C, False)]
         # beyond 2^31 pixels also: the kernels that take the whole batch as ONE flat run (k_norm_write, k_u16_to_f32, k_project_resolve,

@@ -193,11 +193,17 @@ def random_pair(rows, cols, seed):
     return rng.integers(0, 256, (rows, cols), dtype=np.uint8), rng.integers(0, 256, (rows, cols), dtype=np.uint8)
 
 
-def shifted_pair(rows, cols, seed, shift=3):
-    """Noise, the right image the left one moved `shift` columns: a pair with an answer, so that most pixels are valid."""
+def shifted_pair(rows, cols, seed, shift=3, half=False):
+    """Noise, the right image the left one moved `shift` columns: a pair with an answer, so that most pixels are valid.  half: the
+    right image is the floor-mean of the left one moved `shift` and `shift + 1` columns -- the answer lies half a pixel between the
+    two, so the sub-pixel fraction takes many values."""
     rng = np.random.default_rng(seed)
-    wide = rng.integers(0, 256, (rows, cols + shift), dtype=np.uint8)
-    return np.ascontiguousarray(wide[:, :cols]), np.ascontiguousarray(wide[:, shift:])
+    wide = rng.integers(0, 256, (rows, cols + shift + (1 if half else 0)), dtype=np.uint8)
+    left = np.ascontiguousarray(wide[:, :cols])
+    if not half:
+        return left, np.ascontiguousarray(wide[:, shift:])
+    both = wide[:, shift:shift + cols].astype(np.uint16) + wide[:, shift + 1:shift + 1 + cols]
+    return left, (both // 2).astype(np.uint8)
 
 
 def stripes_pair(rows, cols, right_value=0):
@@ -227,3 +233,78 @@ def box_scene(rows, cols, D, seed):
         keep = xs - disparity >= 0
         right[ys[keep], xs[keep] - disparity] = left[ys[keep], xs[keep]]
     return left, right, truth
+
+
+def staircase_disparities(D):
+    """The disparities at which the kernels change what they do, those that exist for D: both ends of the range, and the two sides
+    of the step from a lane's first disparity register to its second (d = 63 | 64)."""
+    return sorted({d for d in (0, 1, 62, 63, 64, 65, D - 2, D - 1) if 0 <= d < D})
+
+
+def staircase_scene(rows, cols, D, seed, disparities=None):
+    """A scene with known answers across the disparity range: uniform noise in vertical bands of rising true disparity (by default
+    staircase_disparities(D)).  Band k of n starts at column k w + d_k, w = (cols - d_max) / n: every pixel of it has x >= d, and of
+    its w + d_(k+1) - d_k columns the next, nearer band hides all but w in the right image.  The right image is the left one
+    forward-warped, far first, over noise.  Returns (left, right, truth [rows][cols] in pixels)."""
+    ds = sorted(set(staircase_disparities(D) if disparities is None else [int(d) for d in disparities]))
+    assert ds and 0 <= ds[0] and ds[-1] < D
+    rng = np.random.Generator(np.random.PCG64(seed))
+    left = rng.integers(0, 256, (rows, cols)).astype(np.uint8)
+    right = rng.integers(0, 256, (rows, cols)).astype(np.uint8)
+    truth = np.empty((rows, cols), np.int64)
+    w = max((cols - ds[-1]) // len(ds), 1)
+    truth[:] = ds[0]
+    for k, d in enumerate(ds[1:], 1):                               # (a band that starts beyond the frame does not exist in it)
+        truth[:, min(k * w + d, cols):] = d
+    for disparity in sorted(set(truth.ravel().tolist())):           # far (small disparity) first, near over it
+        ys, xs = np.nonzero(truth == disparity)
+        keep = xs - disparity >= 0
+        right[ys[keep], xs[keep] - disparity] = left[ys[keep], xs[keep]]
+    return left, right, truth
+
+
+# ---- pairs whose answer is a chosen disparity --------------------------------------------------------------------------------------------
+# per D: the ends of the range and, at two disparities a lane, both sides of the step between a lane's two registers
+TARGET_SHIFTS = {16: (1, 14, 15), 48: (31, 46, 47), 128: (1, 62, 63, 64, 65, 126, 127)}
+TARGET_ROWS, TARGET_MARGIN = 8, 72              # frames of 8 x (D + 72): a pixel with x < d is invalid by definition
+
+
+def target_pair(D, shift, half):
+    return shifted_pair(TARGET_ROWS, D + TARGET_MARGIN, 1000 + 10 * D + shift + (500 if half else 0), shift, half)
+
+
+def target_pairs(D):
+    """[(shift, half)] in the order every test batches them."""
+    return [(shift, half) for shift in TARGET_SHIFTS[D] for half in (False, True)]
+
+
+def assert_targets_found(D, disp16_of):
+    """The conditions on target_pair, on the restatement's results alone (disp16_of: {(shift, half): disp16 at the default
+    parameters}): the exact pair has its shift as the integer disparity of at least 500 valid pixels, the half pair shift or
+    shift + 1 on at least 200, and the half pairs of one D show at least 12 of the 16 sub-pixel fractions."""
+    fractions = set()
+    for (shift, half), d16 in disp16_of.items():
+        valid, whole = d16 >= 0, d16 >> 4
+        if half:
+            n = int((valid & ((whole == shift) | (whole == shift + 1))).sum())
+            fractions |= set((d16[valid] & 15).tolist())
+        else:
+            n = int((valid & (whole == shift)).sum())
+        assert n >= (200 if half else 500), f"D {D} shift {shift} half {half}: {n} pixels found"
+    assert len(fractions) >= 12, (D, sorted(fractions))
+
+
+STAIR_ROWS, STAIR_BAND = 8, 16
+
+
+def staircase_cols(D):
+    """The frame width at which every band of the default staircase shows STAIR_BAND columns in the right image."""
+    return D - 1 + STAIR_BAND * len(staircase_disparities(D))
+
+
+def assert_staircase_found(D, disp16, truth):
+    """Every band of the default staircase at STAIR_ROWS x staircase_cols(D): of the 128 pixels the right image shows of it, at
+    least 50 are valid with the band's disparity as their integer part."""
+    for d in staircase_disparities(D):
+        n = int(((disp16 >= 0) & ((disp16 >> 4) == d) & (truth == d)).sum())
+        assert n >= 50, f"D {D}: the band at {d} is found on {n} pixels"

@@ -6,7 +6,20 @@ Shapes: the smallest at which the kernels can go wrong -- one pixel, one row, fe
 clamps almost everywhere), idle lanes (D = 16, 48), two disparities a lane (D = 128), one column past a multiple of 256, the full
 KITTI width at D = 64 and 128, one whole 375 x 1242 pair, and the two sides of the row kernel's LDS limit at D = 16 and 128: 3 x 4096
 (all 64 KB of LDS staged) and 3 x 4097 (the rows read from global memory; tests/plan_sgm_test.cpp pins the route of each).  References are computed once per
-(pair, D, p1, p2) and shared."""
+(pair, D, p1, p2) and shared.
+
+What is compared bit for bit beyond those shapes:
+    winners at every targeted disparity   pairs whose answer is 1, D - 2 and D - 1 at D = 16, 48 and 128, and 62, 63, 64, 65 at D = 128
+                                          (a lane carries d and d + 64: 63 | 64 is the step between its two registers), exact and half
+                                          a pixel off (many sub-pixel fractions), and a staircase of bands at 0, 1, 62 .. 65, D - 2,
+                                          D - 1; the conditions on these inputs are asserted from the restatement alone
+    the UNIQUENESS x DISP12 grid          at D = 16, 48 (idle lanes) and 128 (two disparities a lane), on such pairs, both outputs
+    both volumes                          C and S read back from the caller's workspace, every element, on both row routes and on
+                                          columns ten times the lookahead; nothing written behind the batch's frames; with two
+                                          chunks the last chunk's volumes
+    a seeded differential fuzz            12 x 8 cases over shapes, D, penalties, checks, batch, workspace and outputs
+    a 65535-frame batch                   past 2^32 bytes in the workspace and in the depth plane, 2^31 in disp16: the case
+                                          "sgm_dev A" of tests/large_batch_cases.py, run by tests/test_gpu_large_batch.py"""
 import ctypes
 import functools
 import itertools
@@ -51,6 +64,12 @@ def pair(kind, rows, cols, D, seed=0):
         out = R.comb_pair(rows, cols, D)
     elif kind == "box":
         out = R.box_scene(rows, cols, D, seed)[:2]
+    elif kind == "staircase":
+        out = R.staircase_scene(rows, cols, D, 5 + seed)[:2]
+    elif kind == "half":                                           # d* = 63 | 64 where a lane carries two disparities
+        out = R.shifted_pair(rows, cols, 400 + seed + rows + cols, min(63, D - 2), half=True)
+    elif kind == "top":                                            # d* = D - 1
+        out = R.shifted_pair(rows, cols, 500 + seed + rows + cols, D - 1)
     else:
         out = R.random_pair(rows, cols, 300 + seed + rows + cols)
     for a in out:
@@ -382,3 +401,190 @@ def test_chained_in_front_of_the_refinement_and_the_error_map_on_one_stream():
     same(host(refined), want_refined.astype(f32), "chain: refined")
     same(host(err), want_err, "chain: error map")
     same(host(stats), want_stats.astype(np.int64), "chain: counts")
+
+
+# ---- winners across the disparity range -----------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def targets(D):
+    """The target pairs of one D (tests/sgm_restatement.py: TARGET_SHIFTS, exact and half) as a batch, and their references."""
+    pairs = [R.target_pair(D, shift, half) for shift, half in R.target_pairs(D)]
+    lefts, rights = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+    want = np.stack([R.vectorised(l, r, num_disparities=D)[0] for l, r in pairs])
+    for a in (lefts, rights, want):
+        a.setflags(write=False)
+    return lefts, rights, want
+
+
+@functools.lru_cache(maxsize=None)
+def staircases(D, n=3):
+    scenes = [R.staircase_scene(R.STAIR_ROWS, R.staircase_cols(D), D, 5 + s) for s in range(n)]
+    want = np.stack([R.vectorised(l, r, num_disparities=D)[0] for l, r, _ in scenes])
+    return np.stack([s[0] for s in scenes]), np.stack([s[1] for s in scenes]), want, scenes[0][2]
+
+
+@gpu
+@pytest.mark.parametrize("D", list(R.TARGET_SHIFTS))
+def test_winners_at_every_targeted_disparity(D):
+    """Pairs whose answer is the chosen disparity -- 1, D - 2, D - 1, and 62 .. 65 where a lane carries d and d + 64 -- exact and
+    half a pixel off, and the staircase: the conditions on the inputs (from the reference alone), then disp16 and depth bit for
+    bit.  What the verified pixels pass through: held() on both registers, the sub-pixel step whose neighbours sit in different
+    registers, the left-right gather and the rival test in the second register, the d* = D - 1 and D - 2 edges of the sub-pixel rule."""
+    lefts, rights, want = targets(D)
+    R.assert_targets_found(D, dict(zip(R.target_pairs(D), want)))
+    rows, cols = lefts.shape[1:]
+    with api.Context(0, rows, cols, len(lefts)) as ctx:
+        d16, depth = ctx.sgm_dev(dev(lefts), dev(rights), depth=True, num_disparities=D)
+        for f, (shift, half) in enumerate(R.target_pairs(D)):
+            same(host(d16[f]), want[f], f"D {D} shift {shift} half {half}: disp16")
+        same(host(depth), R.depth_of(want), f"D {D} target pairs: depth")
+    lefts, rights, want, truth = staircases(D)
+    R.assert_staircase_found(D, want[0], truth)
+    rows, cols = lefts.shape[1:]
+    with api.Context(0, rows, cols, len(lefts)) as ctx:
+        d16, depth = ctx.sgm_dev(dev(lefts), dev(rights), depth=True, num_disparities=D)
+        same(host(d16), want, f"D {D} staircase: disp16")
+        same(host(depth), R.depth_of(want), f"D {D} staircase: depth")
+
+
+GRID_KINDS = ("staircase", "half", "top", "random", "comb")
+
+
+@gpu
+@pytest.mark.parametrize("p1,p2", [(200, 800), (0, 10000)])
+@pytest.mark.parametrize("D", [16, 48, 128])
+def test_parameter_grid_with_idle_lanes_and_two_disparities_a_lane(D, p1, p2):
+    """UNIQUENESS x DISP12 where lanes idle (D = 16, 48) and where a lane carries two disparities (D = 128), on pairs whose
+    winners lie across the range: without the two checks (uniqueness 0, disp12 -1) every pixel with x >= d* is valid, so the value
+    computed for it is compared."""
+    rows, cols = 12, R.staircase_cols(D)
+    lefts, rights = stack(GRID_KINDS, rows, cols, D)
+    l, r = dev(lefts), dev(rights)
+    if p2 == 10000:        # the comb: S beyond what int16 holds
+        assert volumes("comb", rows, cols, D, 0, p1, p2)[1].max() > 50000
+    if D == 128:           # the reference alone: the random pair has verified winners in the second register and on both sides of the step
+        loose = reference("random", rows, cols, D, 0, p1, p2, 0, -1)
+        whole = loose[loose >= 0] >> 4
+        assert (whole >= 64).sum() >= 100 and (whole == 63).any() and (whole == 64).any(), ((whole >= 64).sum(), (whole == 63).sum(), (whole == 64).sum())
+    with api.Context(0, rows, cols, len(GRID_KINDS)) as ctx:
+        for u, lr in itertools.product(UNIQUENESS, DISP12):
+            want = np.stack([reference(k, rows, cols, D, 0, p1, p2, u, lr) for k in GRID_KINDS])
+            got, depth = ctx.sgm_dev(l, r, depth=True, num_disparities=D, p1=p1, p2=p2, uniqueness=u, disp12_max_diff=lr)
+            same(host(got), want, f"D {D} p1 {p1} p2 {p2} uniqueness {u} disp12 {lr}: disp16")
+            same(host(depth), R.depth_of(want), f"D {D} p1 {p1} p2 {p2} uniqueness {u} disp12 {lr}: depth")
+
+
+# ---- the volumes ---------------------------------------------------------------------------------------------------------------------------
+# the two row routes at D = 16 and 128, and 40 rows: the column paths run ten times their lookahead
+VOLUME_SHAPES = [(7, 40, 64), (9, 65, 48), (11, 130, 128), (3, 4096, 16), (3, 4097, 128), (40, 200, 128)]
+VOLUME_RUNS = [(("staircase", "random", "stripes"), 200, 800), (("comb", "staircase"), 0, 10000)]
+
+
+def workspace_volumes(work, slot, rows, cols, D):
+    """(C, S) of the frame in slot `slot` of a workspace (a uint8 tensor), by the layout include/dcmt.h states: per frame in flight
+    C, then S volume_elems behind it, each uint16 [rows][cols][D]."""
+    one = api.sgm_workspace_bytes(rows, cols, D, 1)
+    elems = rows * cols * D
+    assert one == 2 * 2 * elems
+    both = host(work[slot * one:(slot + 1) * one]).view(np.uint16)
+    return both[:elems].reshape(rows, cols, D), both[elems:].reshape(rows, cols, D)
+
+
+def same_volumes(work, slot, kind, rows, cols, D, p1, p2, what):
+    C, S = workspace_volumes(work, slot, rows, cols, D)
+    wantC, wantS = volumes(kind, rows, cols, D, 0, p1, p2)
+    same(C, wantC.astype(np.uint16), f"{what}: C")
+    same(S, wantS.astype(np.uint16), f"{what}: S")
+
+
+@gpu
+@pytest.mark.parametrize("rows,cols,D", VOLUME_SHAPES)
+def test_both_volumes_are_the_restatement_element_for_element(rows, cols, D):
+    """C and S as k_sgm_rows and k_sgm_cols leave them in the caller's workspace: every element, so also the disparities that
+    neither win nor rival.  One chunk: the workspace holds the batch and a frame more, filled with 0xFF; behind the batch's frames
+    it must still hold 0xFF."""
+    import torch
+    one = api.sgm_workspace_bytes(rows, cols, D, 1)
+    for kinds, p1, p2 in VOLUME_RUNS:
+        b = len(kinds)
+        lefts, rights = stack(kinds, rows, cols, D)
+        work = torch.full(((b + 1) * one,), 0xFF, dtype=torch.uint8, device="cuda")
+        with api.Context(0, rows, cols, b) as ctx:
+            d16 = ctx.sgm_dev(dev(lefts), dev(rights), d_work=work, num_disparities=D, p1=p1, p2=p2)
+        for f, kind in enumerate(kinds):
+            same_volumes(work, f, kind, rows, cols, D, p1, p2, f"{rows}x{cols} D {D} p2 {p2} {kind}")
+        assert bool((work[b * one:] == 0xFF).all()), f"{rows}x{cols} D {D}: the workspace was written behind its {b} frames"
+        same(host(d16), np.stack([reference(k, rows, cols, D, 0, p1, p2) for k in kinds]), f"{rows}x{cols} D {D} p2 {p2}: disp16")
+        if "comb" in kinds and rows >= 7 and cols > D:
+            assert volumes("comb", rows, cols, D, 0, p1, p2)[1].max() > 32767          # S that an int16 volume could not hold
+
+
+@gpu
+def test_volumes_of_the_last_chunk_stay_in_the_workspace():
+    """Two chunks: three frames through a workspace of two.  Slot 0 ends with the volumes of frame 2 (the last chunk), slot 1 with
+    those of frame 1 (the first chunk's second frame, which nothing has written over)."""
+    import torch
+    rows, cols, D = 11, 130, 128
+    kinds = ("staircase", "random", "stripes")
+    lefts, rights = stack(kinds, rows, cols, D)
+    one = api.sgm_workspace_bytes(rows, cols, D, 1)
+    work = torch.full((3 * one,), 0xFF, dtype=torch.uint8, device="cuda")
+    with api.Context(0, rows, cols, 3) as ctx:
+        d16 = ctx.sgm_dev(dev(lefts), dev(rights), d_work=work[:2 * one], num_disparities=D)
+    same_volumes(work, 0, kinds[2], rows, cols, D, 200, 800, "two chunks, slot 0: frame 2")
+    same_volumes(work, 1, kinds[1], rows, cols, D, 200, 800, "two chunks, slot 1: frame 1")
+    assert bool((work[2 * one:] == 0xFF).all())
+    same(host(d16), np.stack([reference(k, rows, cols, D) for k in kinds]), "two chunks: disp16")
+
+
+# ---- seeded differential fuzz ---------------------------------------------------------------------------------------------------------------
+FUZZ_ELEMS = 1_500_000         # rows * cols * D * batch of one case: about 0.2 s of the vectorised restatement
+
+
+def _fuzz_pair(g, rows, cols, D):
+    kind = int(g.integers(0, 8))
+    seed = int(g.integers(0, 1 << 30))
+    if kind == 0:
+        return R.random_pair(rows, cols, seed)
+    if kind == 1:
+        return R.shifted_pair(rows, cols, seed, int(g.integers(0, D)), half=bool(g.integers(0, 2)))
+    if kind == 2:
+        return R.stripes_pair(rows, cols, int(g.choice([0, 128, 255])))
+    if kind == 3:
+        return R.comb_pair(rows, cols, D)
+    if kind == 4:
+        return R.box_scene(rows, cols, D, seed)[:2]
+    if kind == 5:                                                       # a staircase with a random set of band disparities
+        return R.staircase_scene(rows, cols, D, seed, disparities=g.choice(D, int(g.integers(1, 7)), replace=False))
+    if kind == 6:
+        return R.staircase_scene(rows, cols, D, seed)[:2]
+    left = R.random_pair(rows, cols, seed)[0]                            # the same image twice: d* = 0 wherever it is unique
+    return left, left.copy()
+
+
+@gpu
+@pytest.mark.parametrize("seed", range(12))
+def test_fuzz_against_the_restatement(seed):
+    import torch
+    g = np.random.Generator(np.random.PCG64(26000 + seed))
+    for case in range(8):
+        D = int(g.choice([16, 32, 48, 64, 80, 128]))
+        batch = int(g.choice([1, 2, 7]))
+        cols = int(g.integers(1, 301))
+        rows = min(int(g.integers(1, 41)), max(1, FUZZ_ELEMS // (cols * D * batch)))
+        p2 = int(g.integers(0, 10001)) if g.random() < 0.6 else int(g.choice([0, 800, 10000]))
+        p1 = int(g.integers(0, p2 + 1))
+        kw = dict(num_disparities=D, p1=p1, p2=p2, uniqueness=int(g.integers(0, 101)), disp12_max_diff=int(g.choice([-1, 0, 1, 2, 5])))
+        held = int(g.integers(1, batch + 1))
+        outputs = ("both", "disp16", "depth")[int(g.integers(0, 3))]
+        pairs = [_fuzz_pair(g, rows, cols, D)[:2] for _ in range(batch)]
+        what = f"seed {seed} case {case}: {batch} x {rows}x{cols} {kw} workspace of {held}, {outputs}"
+        lefts, rights = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+        want16, want_depth = R.batch(R.vectorised, lefts, rights, **kw)
+        work = torch.full((held * api.sgm_workspace_bytes(rows, cols, D, 1),), 0xFF, dtype=torch.uint8, device="cuda")
+        with api.Context(0, rows, cols, batch) as ctx:
+            got = ctx.sgm_dev(dev(lefts), dev(rights), disp16=outputs != "depth", depth=outputs != "disp16", d_work=work, **kw)
+        got16, got_depth = got if outputs == "both" else (got, None) if outputs == "disp16" else (None, got)
+        if got16 is not None:
+            same(host(got16), want16, what + ": disp16")
+        if got_depth is not None:
+            same(host(got_depth), want_depth, what + ": depth")

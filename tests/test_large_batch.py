@@ -22,6 +22,18 @@ def test_geometry_figures():
     assert LB.boundary_frames(C, (), (seg * C.px,)) == [seg - 1, seg, seg + 1]          # the last frame of segment 0, the first two of segment 1
 
 
+def test_the_matcher_s_chunks_and_unique_frames():
+    """dcmt_sgm_dev at geometry A through a workspace of 4096 frames: 4.43 GB, 16 chunks, the last of 4095 frames; byte 2^32 of the
+    workspace lies in slot 3971 of every chunk.  The unique sources sit where the case says, beside the plane boundaries."""
+    LB.check_sgm_figures()
+    assert LB.sgm_figures(LB.A) == (1_081_344, 16, 4095, 3971)
+    extra = LB.sgm_extra_frames(LB.A)
+    assert sorted(extra) == [3971, 3972, 4095, 4096, 32767, 32768, 36739, 36740, 61439, 61440, 65411, 65412]
+    lay = LB.cases()["sgm_dev A"].layout()
+    assert set(extra) | {0, 31775, 31776, 63550, 63551, 65534} == set(lay.unique)
+    assert len({lay.source_of(f) for f in lay.unique}) == len(lay.unique) == lay.n_src - lay.k
+
+
 @pytest.mark.parametrize("g", list(LB.GEOMETRIES.values()), ids=list(LB.GEOMETRIES))
 def test_boundary_frames_equal_the_frame_by_frame_statement(g):
     seg = LB.color_seg_frames(g)

@@ -1,6 +1,7 @@
 """The stereo matcher (dcmt_sgm_dev) without a GPU: the two restatements of tests/sgm_restatement.py against each other over the
 parameter grid, plain block matching at p1 = p2 = 0, the bound on S on adversarial pairs, a sanity condition on the restatement (it
-finds a known scene), the launch plan (tests/plan_sgm_test.cpp, built against the headers alone), the refusals that need no device
+finds a known scene; it finds every targeted disparity of the pairs and staircases the GPU tests use, and its two forms agree at
+D = 128 with winners at 63, 64, 100 and 127), the launch plan (tests/plan_sgm_test.cpp, built against the headers alone), the refusals that need no device
 and the ABI."""
 import ctypes
 import functools
@@ -108,6 +109,40 @@ def test_the_restatement_finds_a_known_scene(rows, cols, D, seed):
     assert valid.mean() >= 0.85 and within.mean() >= 0.99
     want = R.depth_of(d16)
     assert np.array_equal(depth.view(np.uint32), want.view(np.uint32)) and (depth[d16 <= 0] == 0).all()
+
+
+@pytest.mark.parametrize("D", list(R.TARGET_SHIFTS))
+def test_the_restatement_finds_every_targeted_disparity(D):
+    """Conditions on the inputs of the GPU tests, from the restatement alone, at the default parameters: the shifted pairs, exact
+    and half, have their answer at the chosen disparity (the ends of the range, 63 | 64 at D = 128) on at least 500 / 200 pixels,
+    the half pairs show at least 12 of the 16 fractions, and every band of the staircase is found."""
+    found = {(shift, half): R.vectorised(*R.target_pair(D, shift, half), num_disparities=D)[0] for shift, half in R.target_pairs(D)}
+    R.assert_targets_found(D, found)
+    left, right, truth = R.staircase_scene(R.STAIR_ROWS, R.staircase_cols(D), D, 5)
+    assert sorted(set(truth.ravel().tolist())) == R.staircase_disparities(D)
+    assert {63, 64} <= set(R.staircase_disparities(128)) and R.staircase_disparities(16) == [0, 1, 14, 15]
+    R.assert_staircase_found(D, R.vectorised(left, right, num_disparities=D)[0], truth)
+
+
+HIGH = [("exact", lambda: R.shifted_pair(4, 140, 31, 127)), ("half", lambda: R.shifted_pair(4, 140, 32, 64, half=True)),
+        ("staircase", lambda: R.staircase_scene(4, 140, 128, 33, disparities=(1, 63, 64, 100))[:2])]
+
+
+@pytest.mark.parametrize("name", [h[0] for h in HIGH])
+def test_restatements_agree_on_high_disparities(name):
+    """literal against vectorised on 4 x (D + 12) at D = 128 with winners far above the 12 of the TINY frames: the second half of the
+    disparity range, d* = 63 | 64, d* = D - 1."""
+    left, right = dict(HIGH)[name]()
+    C1, S1 = R.literal_volumes(left, right, 128, 200, 800)
+    C2, S2 = R.vectorised_volumes(left, right, 128, 200, 800)
+    assert np.array_equal(C1, C2) and np.array_equal(S1, S2)
+    winners = set()
+    for u, lr in ((10, 1), (0, -1), (100, 0)):
+        a, b = R.literal_select(S1, u, lr), R.vectorised_select(S2, u, lr)
+        assert np.array_equal(a, b), f"{name} uniqueness {u} disp12 {lr}: first at {tuple(np.argwhere(a != b)[0])}"
+        winners |= set((a[a >= 0] >> 4).tolist())
+    want = {"exact": {127}, "half": {64}, "staircase": {63, 64, 100}}[name]
+    assert want <= winners, (name, sorted(winners))
 
 
 def test_depth_formula():
