@@ -88,24 +88,30 @@ __device__ __forceinline__ unsigned u_right(unsigned v) { return (unsigned)__bui
 __device__ __forceinline__ unsigned u_row_shr1(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); }
 __device__ __forceinline__ unsigned u_row_shl1(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true); }
 __device__ __forceinline__ unsigned u_row_ror8(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xf, 0xf, true); }
-__device__ __forceinline__ void u_row_scans4(unsigned a, unsigned b, unsigned& pa, unsigned& sa, unsigned& pb, unsigned& sb)
+// The inclusive prefix / suffix maxima inside each 16-lane DPP row.  The first step writes the two scans from the source itself
+// (bound_ctrl: max(0, x) = x in a lane without a source): no copies.  A's scans take four steps (1, 2, 4, 8 lanes); B's are only
+// looked at in lanes 0..7 (prefix) and 56..63 (suffix) -- eight lanes each, three steps -- and only on rows with a hole in those
+// lanes (fill_step), so they are a block of their own.
+// (a DPP read of a register needs two wait states behind the VALU write: with two chains side by side, one instruction and an s_nop)
+#define DCMT_U2(N) "s_nop 0\n\t" \
+                   "v_max_u32_dpp %0, %0, %0 row_shr:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+                   "v_max_u32_dpp %1, %1, %1 row_shl:" #N " row_mask:0xf bank_mask:0xf\n\t"
+#define DCMT_U2_FIRST "s_nop 1\n\t" \
+                      "v_max_u32_dpp %0, %2, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" \
+                      "v_max_u32_dpp %1, %2, %2 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+// (the compiler does not see the writes of an asm block: whatever shifts a scan next finds its two wait states here)
+#define DCMT_U2_LAST "s_nop 1\n\t"
+__device__ __forceinline__ void u_row_scans_a(unsigned a, unsigned& pa, unsigned& sa)
 {
-    // the first step writes the four scans from a and b themselves (bound_ctrl: max(0, x) = x in a lane without a source): no copies
-#define DCMT_U4(N) "v_max_u32_dpp %0, %0, %0 row_shr:" #N " row_mask:0xf bank_mask:0xf\n\t" \
-                   "v_max_u32_dpp %1, %1, %1 row_shl:" #N " row_mask:0xf bank_mask:0xf\n\t" \
-                   "v_max_u32_dpp %2, %2, %2 row_shr:" #N " row_mask:0xf bank_mask:0xf\n\t" \
-                   "v_max_u32_dpp %3, %3, %3 row_shl:" #N " row_mask:0xf bank_mask:0xf\n\t"
-    // (b's scans are only looked at in lanes 0..7 (prefix) and 56..63 (suffix): eight lanes each, three steps)
-    asm("s_nop 1\n\t"
-        "v_max_u32_dpp %0, %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_max_u32_dpp %1, %4, %4 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_max_u32_dpp %2, %5, %5 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        "v_max_u32_dpp %3, %5, %5 row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-        DCMT_U4(2) DCMT_U4(4)
-        "v_max_u32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "v_max_u32_dpp %1, %1, %1 row_shl:8 row_mask:0xf bank_mask:0xf\n\t" : "=&v"(pa), "=&v"(sa), "=&v"(pb), "=&v"(sb) : "v"(a), "v"(b));
-#undef DCMT_U4
+    asm(DCMT_U2_FIRST DCMT_U2(2) DCMT_U2(4) DCMT_U2(8) DCMT_U2_LAST : "=&v"(pa), "=&v"(sa) : "v"(a));
 }
+__device__ __forceinline__ void u_row_scans_b(unsigned b, unsigned& pb, unsigned& sb)
+{
+    asm(DCMT_U2_FIRST DCMT_U2(2) DCMT_U2(4) DCMT_U2_LAST : "=&v"(pb), "=&v"(sb) : "v"(b));
+}
+#undef DCMT_U2_LAST
+#undef DCMT_U2_FIRST
+#undef DCMT_U2
 
 // The exact 5x5 median of dcmt_median.h on packed pairs: the two-input MERGE55 of median_shared_nets.h (the three-input forms
 // need a packed med3, which does not exist), MID20 from median_pk3_nets.h, sort5 and the closing selection below.
@@ -196,6 +202,15 @@ struct FpQ {
     static constexpr int VW = 128 - 2 * H;       // output columns per wave
 };
 
+// The output rows: written once, read by nobody in the launch (k_tail reads the few frames it redoes, a launch later).  As ordinary
+// stores the 1.75 GB of a 1024-frame call pass through the L2 beside the X6 rows and halo columns that neighbouring strips are
+// about to read again; with the `nt` bit (non-temporal: streamed, not kept) the step takes about 5 % less time -- DESIGN.md section 5.
+__device__ __forceinline__ void st2_nt(const FrameBuf& b, unsigned lane_bytes, int row, int cols, F2 v)
+{
+    const f2v f = {v.e, v.o};
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, f), b.rs, lane_bytes, row * cols * 4, 2 /* nt */);
+}
+
 // k_fp_q's tail behind the median, two columns per lane.  Step u finishes the output of image row u - 6 from the median of image
 // row u - 4.
 template <bool BLUR>
@@ -259,7 +274,7 @@ struct PostPipeP {
                     if (mo_.o >= thr) val.o = ao;
                 }
                 val = {invert_valid(val.e, max_depth, thr), invert_valid(val.o, max_depth, thr)};   // LO :191-202
-                st2(of, outlane ? ob : kDropOffset, o, cols, val);
+                st2_nt(of, outlane ? ob : kDropOffset, o, cols, val);
                 last_out = val;
             };
             const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
@@ -293,8 +308,15 @@ struct PostPipeP {
             const float re = __shfl(ce, rle, 64), ro = __shfl(co, rlo, 64);
             if (outside) { ce = re; co = ro; }
         }
-        const float s1 = __fadd_rn(from_left(co), co), s2 = __fadd_rn(ce, from_right(ce));
-        const float ue = __fadd_rn(from_left(s2), s2), wo = __fadd_rn(from_right(s1), s1);
+        // (each of the four sums is ONE v_add_f32 with the lane shift as its DPP operand -- as long as the two sums of a line are
+        // not paired into a v_pk_add_f32, which has no DPP form and takes a v_mov_b32_dpp per shift: the empty asm makes the
+        // second sum's operand a value that exists only behind the first, so the two cannot be bundled)
+        float s1 = __fadd_rn(from_left(co), co);
+        asm("" : "+v"(ce) : "v"(s1));
+        const float s2 = __fadd_rn(ce, from_right(ce));
+        const float ue = __fadd_rn(from_left(s2), s2);
+        asm("" : "+v"(s1) : "v"(ue));
+        const float wo = __fadd_rn(from_right(s1), s1);
         G1[(PP + 4) & 7] = {__builtin_fmaf(__fadd_rn(ce, s1), 4.0f, ue), __builtin_fmaf(__fadd_rn(co, s2), 4.0f, wo)};
         const int o = u - 6;
         if (MODE != BORDER || (unsigned)o < (unsigned)rows) {
@@ -304,7 +326,7 @@ struct PostPipeP {
                 const float ne = __builtin_fmaf(g0.e, 6.0f, __builtin_fmaf(__fadd_rn(u1.e, d1.e), 4.0f, __fadd_rn(u2.e, d2.e)));
                 const float no = __builtin_fmaf(g0.o, 6.0f, __builtin_fmaf(__fadd_rn(u1.o, d1.o), 4.0f, __fadd_rn(u2.o, d2.o)));
                 const F2 val = {__builtin_fmaf(ne, -0x1p-16f, top), __builtin_fmaf(no, -0x1p-16f, top)};
-                st2(of, outlane ? ob : kDropOffset, o, cols, val);
+                st2_nt(of, outlane ? ob : kDropOffset, o, cols, val);
                 last_out = val;
             };
             const F2 g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7], g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
@@ -488,15 +510,28 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
         const unsigned long long vme = __builtin_amdgcn_ballot_w64((v << 16) <= Q16::HOLE_MAX_HI), vmo = __builtin_amdgcn_ballot_w64(v <= Q16::HOLE_MAX_HI);
         if ((vme | vmo) != 0ull) {
             // horizontal 31-max (header comment) on the unpacked halves
-            const unsigned e = w31a & 0xffffu, od = w31a >> 16;
-            const unsigned bo = u_row_ror8(w31b);
-            unsigned pa, sa, pb, sb;
-            u_row_scans4(umax2(e, od), umax2(w31b, bo), pa, sa, pb, sb);
-            // exclusive scans = the inclusive ones shifted by a lane; which register a lane hands on is chosen BEFORE the shift, at
-            // the source lane (lanes 0..6 feed the halo lanes 1..7, lane 7 feeds lane 8 of A; lanes 57..63 likewise): two shifts, not four
-            const unsigned px = u_row_shr1(lane < 7 ? pb : pa), sx = u_row_shl1(lane > 56 ? sb : sa);
-            const unsigned so = umax2(b_hi ? bo : od, sx);
-            const unsigned pe = umax2(b_lo ? w31b : e, px);
+            // pp, ss: the inclusive scans a lane hands on; oo, ee: the odd / even column that closes SO / PE.  A's, and in the halo
+            // lanes B's -- but B's words reach the output only through lanes 0..7 and 56..63 (lanes 8..55 fetch from lanes 0..47
+            // and 16..63, where SO, SX / PX, PE are formed from A alone), and a fill value is looked at only in a hole lane: a row
+            // whose holes all lie in lanes 8..55 leaves B out (wave-uniform; tests/test_lane_schemes_halo_free.py)
+            unsigned ee = w31a & 0xffffu, oo = w31a >> 16;
+            unsigned pp, ss;
+            u_row_scans_a(umax2(ee, oo), pp, ss);
+            if (((vme | vmo) & 0xff000000000000ffull) != 0ull) {
+                const unsigned bo = u_row_ror8(w31b);
+                unsigned pb, sb;
+                u_row_scans_b(umax2(w31b, bo), pb, sb);
+                // which register a lane hands on is chosen at the SOURCE lane (lanes 0..6 feed the halo lanes 1..7, lane 7 feeds
+                // lane 8 of A; lanes 57..63 likewise)
+                if (lane < 7) pp = pb;
+                if (lane > 56) ss = sb;
+                if (b_hi) oo = bo;
+                if (b_lo) ee = w31b;
+            }
+            // exclusive scans = the inclusive ones shifted by a lane, the choice above made BEFORE the shift: two shifts, not four
+            const unsigned px = u_row_shr1(pp), sx = u_row_shl1(ss);
+            const unsigned so = umax2(oo, sx);
+            const unsigned pe = umax2(ee, px);
             // out_E(l) = max(SO(l-8), PX(l+8)), out_O(l) = max(SX(l-8), PE(l+8)): the two values a lane fetches from lane l-8 ride in one
             // word (SO low, SX high), so do the two from lane l+8 (PX low, PE high) -- two ds_bpermutes, not four, and their packed maximum
             // is the pair (out_E, out_O) as it is needed

@@ -12,6 +12,8 @@ __global__ __launch_bounds__(256) void k(float* out, int iters)
 {
     float a = threadIdx.x * 0.5f, b = threadIdx.x * 0.25f + 1.f, c = 3.f, d = 4.f;
     float e = 5.f + threadIdx.x, f = 6.f, g = 7.f, h = 8.f;
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    f2 pp = {a, b}, qq = {c, d};
     for (int i = 0; i < iters; ++i) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -68,12 +70,18 @@ __global__ __launch_bounds__(256) void k(float* out, int iters)
             if (MODE == 47) asm volatile("v_mov_b32_dpp %0, %1 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_max_f32 %4, %4, %5\n v_mov_b32_dpp %1, %2 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_max_f32 %5, %5, %6" OPS8);   // dpp mov + plain max
             if (MODE == 48) asm volatile("v_cmp_lt_f32 vcc, %0, %1\n v_cndmask_b32 %4, %4, %5, vcc\n v_cmp_lt_f32 vcc, %1, %2\n v_cndmask_b32 %5, %5, %6, vcc" OPS8 :: "vcc");
             if (MODE == 49) asm volatile("v_max_f32 %0, %0, %1\n v_lshrrev_b32 %4, 1, %5\n v_max_f32 %1, %1, %2\n v_ashrrev_i32 %5, 1, %6" OPS8);
+            // a lane shift folded into its add against the shift as a move and the add as half of a packed one (k_fp_q's horizontal
+            // Gaussian: four sums per row step).  No register is read through DPP less than three instructions behind its write.
+            if (MODE == 50) asm volatile("v_add_f32_dpp %4, %5, %5 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_add_f32_dpp %5, %6, %6 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+                                         "v_add_f32_dpp %6, %7, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_add_f32_dpp %7, %4, %4 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1" OPS8);   // 4 sums
+            if (MODE == 51) asm volatile("v_mov_b32_dpp %0, %4 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_mov_b32_dpp %1, %5 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_pk_add_f32 %8, %8, %9\n"
+                                         "v_mov_b32_dpp %2, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_mov_b32_dpp %3, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n v_pk_add_f32 %9, %9, %8" OPS8, "+v"(pp), "+v"(qq));   // the same 4 sums
             if (MODE == 27) asm volatile("v_cvt_f32_ubyte0 %0, %1\n v_cvt_f32_ubyte1 %1, %2\n v_cvt_f32_ubyte2 %2, %3\n v_cvt_f32_ubyte3 %3, %0" OPS8);
             if (MODE == 28) asm volatile("v_max_f32 %0, %0, %1\n v_max_f32 %1, %1, %2\n v_max_f32 %2, %2, %3\n v_max_f32 %3, %3, %0\n s_nop 3" OPS8);
             if (MODE == 29) asm volatile("v_add_f32 %4, %4, %5\n v_add_f32 %5, %5, %6\n v_add_f32 %6, %6, %7\n v_add_f32 %7, %7, %4\n s_nop 3" OPS8);
         }
     }
-    out[blockIdx.x * 256 + threadIdx.x] = a + b + c + d + e + f + g + h;
+    out[blockIdx.x * 256 + threadIdx.x] = a + b + c + d + e + f + g + h + pp.x + pp.y + qq.x + qq.y;
 }
 
 struct Mode { const char* name; int n_instr; };
@@ -118,14 +126,15 @@ int main()
         {"2 v_max + 2 v_xor", 4}, {"2 v_med3 + 2 v_add", 4}, {"2 v_max + 2 v_bitop3", 4}, {"network: 4 (v_min + 2 dependent v_xor)", 12}, {"2 v_max3 + 2 v_add", 4},
         {"2 v_max + v_and + v_or", 4}, {"2 v_max + 2 v_add_u32", 4}, {"2 v_max + v_mul + v_sub", 4}, {"4 x (v_min, dependent v_add)", 8}, {"2 v_max_dpp + 2 v_mov", 4},
         {"4 v_xor", 4}, {"4 v_bitop3", 4}, {"2 v_med3 + 2 v_mov", 4}, {"2 v_max_e64 + 2 v_add", 4}, {"2 v_med3 + 2 v_fma", 4}, {"4 S (min/max pairs) + 2 v_add", 6},
-        {"2 v_max, then 2 v_add", 4}, {"2 v_mov_dpp + 2 v_max", 4}, {"2 x (v_cmp, v_cndmask vcc)", 4}, {"2 v_max + v_lshr + v_ashr", 4}};
+        {"2 v_max, then 2 v_add", 4}, {"2 v_mov_dpp + 2 v_max", 4}, {"2 x (v_cmp, v_cndmask vcc)", 4}, {"2 v_max + v_lshr + v_ashr", 4},
+        {"4 v_add_f32_dpp (4 shifted sums)", 4}, {"4 v_mov_dpp + 2 v_pk_add_f32 (4 shifted sums)", 6}};
 #define RUN(I, W) run<I>(M[I], d, W)
 #define ALLW(I) RUN(I, 8); RUN(I, 2); RUN(I, 1)
     ALLW(0); ALLW(1); ALLW(2); ALLW(3); ALLW(4); ALLW(5); ALLW(6); ALLW(7);
     RUN(8, 8); RUN(9, 8); RUN(10, 8); RUN(11, 8); RUN(12, 8); RUN(13, 8); RUN(14, 8); RUN(15, 8); RUN(16, 8); RUN(17, 8); RUN(18, 8); RUN(19, 8);
     RUN(20, 8); RUN(21, 8); RUN(22, 8); RUN(23, 8); RUN(24, 8); RUN(25, 8); RUN(26, 8); RUN(27, 8); RUN(28, 8); RUN(29, 8);
     RUN(30, 8); RUN(31, 8); RUN(32, 8); RUN(33, 8); RUN(34, 8); RUN(35, 8); RUN(36, 8); RUN(37, 8); RUN(38, 8); RUN(39, 8); RUN(40, 8); RUN(41, 8);
-    RUN(42, 8); RUN(43, 8); RUN(44, 8); RUN(45, 8); RUN(46, 8); RUN(47, 8); RUN(48, 8); RUN(49, 8); RUN(33, 4); RUN(38, 4); RUN(45, 4); RUN(7, 4);
+    RUN(42, 8); RUN(43, 8); RUN(44, 8); RUN(45, 8); RUN(46, 8); RUN(47, 8); RUN(48, 8); RUN(49, 8); ALLW(50); RUN(50, 3); ALLW(51); RUN(51, 3); RUN(33, 4); RUN(38, 4); RUN(45, 4); RUN(7, 4);
     unsigned* u; (void)hipMalloc(&u, 16);
     hipLaunchKernelGGL(k_denorm, dim3(1), dim3(1), 0, 0, u);
     unsigned hu[4]; (void)hipMemcpy(hu, u, 16, hipMemcpyDeviceToHost);
