@@ -430,6 +430,21 @@ int dcmt_bilateral5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int row
 }  // extern "C"
 
 // ---- Slic::create_connectivity (dcmt_kernels_connect.h) -------------------------------------------------------------------------
+namespace dcmt {
+
+// The first three stages of a component labelling on the planes A and B: the tile-local kernel, the border kernel where a frame is
+// more than one tile, k_conn_flatten.  rel: what the two kernels of a relation take between kbits and the planes.
+template <class Local, class Border, class Src, class... Rel>
+static void conn_label_enqueue(Local local, Border border, const ConnGeom& g, const Src* src, uint32_t rows, uint32_t cols, int batch, uint32_t* A,
+                               uint32_t* B, hipStream_t st, Rel... rel)
+{
+    hipLaunchKernelGGL(local, dim3(g.local_x, batch), dim3(256), 0, st, src, rows, cols, g.tiles_x, g.kbits, rel..., A, B);
+    if (g.border_x > 0) hipLaunchKernelGGL(border, dim3(g.border_x, batch), dim3(256), 0, st, src, rows, cols, g.pairs_v, g.pairs, g.kbits, rel..., A);
+    hipLaunchKernelGGL(k_conn_flatten, dim3(g.px_x, batch), dim3(256), 0, st, g.n, cols, g.kbits, A, B);
+}
+
+}  // namespace dcmt
+
 extern "C" {
 
 int dcmt_slic_connectivity_max_labels(int rows, int cols, int n_centers)
@@ -453,13 +468,11 @@ int dcmt_slic_connectivity_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows,
     uint32_t* A = reinterpret_cast<uint32_t*>(ctx->pp[0].p);
     uint32_t* B = reinterpret_cast<uint32_t*>(ctx->pp[1].p);
     const uint32_t r = (uint32_t)rows, c = (uint32_t)cols;
-    hipLaunchKernelGGL(k_conn_local, dim3(pl.local_x, batch), dim3(256), 0, st, d_labels, r, c, pl.tiles_x, pl.kbits, A, B);
-    if (pl.border_x > 0) hipLaunchKernelGGL(k_conn_border, dim3(pl.border_x, batch), dim3(256), 0, st, d_labels, r, c, pl.pairs_v, pl.pairs, pl.kbits, A);
-    hipLaunchKernelGGL(k_conn_flatten, dim3(pl.px_x, batch), dim3(256), 0, st, pl.n, c, pl.kbits, A, B);
-    hipLaunchKernelGGL(k_conn_seed, dim3(pl.strips, batch), dim3(256), 0, st, A, B, r, c, pl.kbits, pl.band_rows, pl.lim4, ctx->conn_slab.p);
+    conn_label_enqueue(k_conn_local, k_conn_border, pl.g, d_labels, r, c, batch, A, B, st);
+    hipLaunchKernelGGL(k_conn_seed, dim3(pl.strips, batch), dim3(256), 0, st, A, B, r, c, pl.g.kbits, pl.band_rows, pl.lim4, ctx->conn_slab.p);
     hipLaunchKernelGGL(k_conn_scan, dim3(batch), dim3(256), 0, st, ctx->conn_slab.p, pl.strips, d_counts);
     hipLaunchKernelGGL(k_conn_rank, dim3(pl.strips, batch), dim3(256), 0, st, B, r, c, pl.band_rows, ctx->conn_slab.p);
-    hipLaunchKernelGGL(k_conn_relabel, dim3(pl.px_x, batch), dim3(256), 0, st, A, B, pl.n, c, pl.kbits, d_out);
+    hipLaunchKernelGGL(k_conn_relabel, dim3(pl.g.px_x, batch), dim3(256), 0, st, A, B, pl.g.n, c, pl.g.kbits, d_out);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
@@ -493,13 +506,11 @@ int dcmt_filter_speckles_dev(dcmt_ctx* ctx, const int16_t* d_disp16, int16_t* d_
     const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, max_size = (uint32_t)params->max_size;
     const int32_t nv = params->new_val, md = params->max_diff;
     if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_removed, 0, pl.clear_bytes, st));
-    hipLaunchKernelGGL(k_spk_local, dim3(pl.local_x, batch), dim3(256), 0, st, d_disp16, r, c, pl.tiles_x, pl.kbits, nv, md, A, B);
-    if (pl.border_x > 0) hipLaunchKernelGGL(k_spk_border, dim3(pl.border_x, batch), dim3(256), 0, st, d_disp16, r, c, pl.pairs_v, pl.pairs, pl.kbits, nv, md, A);
-    hipLaunchKernelGGL(k_conn_flatten, dim3(pl.px_x, batch), dim3(256), 0, st, pl.n, c, pl.kbits, A, B);
+    conn_label_enqueue(k_spk_local, k_spk_border, pl.g, d_disp16, r, c, batch, A, B, st, nv, md);
     if (pl.vec == 4)
-        hipLaunchKernelGGL(k_spk_apply<4>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.n, c, pl.kbits, nv, max_size, d_out, d_depth, d_removed);
+        hipLaunchKernelGGL(k_spk_apply<4>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.g.n, c, pl.g.kbits, nv, max_size, d_out, d_depth, d_removed);
     else
-        hipLaunchKernelGGL(k_spk_apply<1>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.n, c, pl.kbits, nv, max_size, d_out, d_depth, d_removed);
+        hipLaunchKernelGGL(k_spk_apply<1>, dim3(pl.apply_x, batch), dim3(256), 0, st, d_disp16, A, B, pl.g.n, c, pl.g.kbits, nv, max_size, d_out, d_depth, d_removed);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

@@ -21,4 +21,32 @@ inline int conn_key_bits(int rows)
     return k;
 }
 
+// The tiles of a frame, the pixel pairs across their edges and the grids of the first three stages of a component labelling
+// (tile-local union-find, border merge, flatten; conn_label_enqueue in dcmt_cloud.hip): the shape decides them, whatever the relation.
+struct ConnGeom {
+    uint32_t n;                      // pixels per frame
+    uint32_t kbits;                  // conn_key_bits(rows)
+    uint32_t tiles_x, tiles_y;
+    unsigned local_x;                // the tile-local kernel: (tiles_x * tiles_y, batch)
+    uint32_t pairs_v, pairs;         // pixel pairs across vertical tile edges, across all tile edges
+    unsigned border_x;               // the border kernel: (border_x, batch); 0: one tile, no launch
+    unsigned px_x;                   // k_conn_flatten (and k_conn_relabel): (px_x, batch), one thread per pixel
+};
+
+// rows, cols >= 1, a frame of fewer than 2^29 pixels
+inline ConnGeom conn_geom(int rows, int cols)
+{
+    ConnGeom g;
+    g.n = (uint32_t)rows * (uint32_t)cols;
+    g.kbits = (uint32_t)conn_key_bits(rows);
+    g.tiles_x = ((uint32_t)cols + kConnTW - 1) / kConnTW;
+    g.tiles_y = ((uint32_t)rows + kConnTH - 1) / kConnTH;
+    g.local_x = g.tiles_x * g.tiles_y;
+    g.pairs_v = (g.tiles_x - 1) * (uint32_t)rows;
+    g.pairs = g.pairs_v + (g.tiles_y - 1) * (uint32_t)cols;
+    g.border_x = (g.pairs + 255) / 256;
+    g.px_x = (g.n + 255) / 256;
+    return g;
+}
+
 }  // namespace dcmt

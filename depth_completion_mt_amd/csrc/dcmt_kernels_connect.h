@@ -6,7 +6,9 @@
 // Keys.  Pixel (x, y) has the key (x << kbits) | y, 2^kbits >= rows (dcmt_connect.h): ordered as the reference's scan (column outer,
 // row inner), taken apart without a division.  The planes are row-major like the labels; what they HOLD are keys.
 //
-// Two scratch planes of one word per pixel, A and B (the context's pp[0] and pp[1]), and a slab of one word per (frame, strip):
+// Two scratch planes of one word per pixel, A and B (the context's pp[0] and pp[1]), and a slab of one word per (frame, strip).  The
+// first two kernels are conn_local_body and conn_border_body under the relation "equal labels" (ConnLabelRel, below); the speckle
+// filter (dcmt_kernels_speckle.h) runs the same bodies under its own relation, and k_conn_flatten as it is.
 //   k_conn_local    one workgroup per tile of 64 x 16 pixels: union-find in LDS over the tile's pixels.  A[p] = the key of the
 //                   smallest pixel of p's component WITHIN the tile; B[p] = that component's pixel count at that pixel, 0 elsewhere.
 //   k_conn_border   one thread per pair of pixels across a tile edge: equal labels -> union of the two trees in A, the larger
@@ -118,10 +120,26 @@ __device__ __forceinline__ void conn_count(uint32_t* C, uint32_t r, bool active)
     }
 }
 
-// grid (tiles_x * tiles_y, frames), 256 threads: lane = column of the tile, wave w its rows 4w .. 4w + 3
-__global__ __launch_bounds__(256)
-void k_conn_local(const int32_t* __restrict__ labels, uint32_t rows, uint32_t cols, uint32_t tiles_x, uint32_t kbits,
-                  uint32_t* __restrict__ A, uint32_t* __restrict__ B)
+// The first two stages are written once, over the RELATION under which 4-neighbours are joined.  A relation R supplies
+//   R::Src                   the element type of the source plane
+//   int32_t word(Src)        a loaded element as the word a tile's LDS holds
+//   bool live(int32_t)       whether an in-frame pixel with that word takes part; one that does not is a singleton that joins nothing
+//                            and counts nothing: its B word stays 0, so k_conn_flatten passes it by
+//   bool edge(int32_t a, int32_t b)   on the words of two in-frame 4-neighbours: both take part and are joined
+// and the bodies decide "inside the frame" themselves (no word is set aside for it: a label may be any int32_t).  An edge need not be
+// transitive (|a - b| <= max_diff is not), so whatever concludes "these two are joined already" does so from EDGES, never from one
+// pixel's value compared all round: [[-32, 32], [0, 0]] at max_diff 32 is one component whose top pair is no edge.
+struct ConnLabelRel {                                      // equal labels; every in-frame pixel takes part
+    using Src = int32_t;
+    __device__ __forceinline__ int32_t word(int32_t s) const { return s; }
+    __device__ __forceinline__ bool live(int32_t) const { return true; }
+    __device__ __forceinline__ bool edge(int32_t a, int32_t b) const { return a == b; }
+};
+
+// The tile-local stage.  grid (tiles_x * tiles_y, frames), 256 threads: lane = column of the tile, wave w its rows 4w .. 4w + 3
+template <class R>
+__device__ __forceinline__ void conn_local_body(const R rel, const typename R::Src* __restrict__ src, uint32_t rows, uint32_t cols, uint32_t tiles_x,
+                                                uint32_t kbits, uint32_t* __restrict__ A, uint32_t* __restrict__ B)
 {
     __shared__ int32_t L[kConnLds];
     __shared__ uint32_t P[kConnLds];
@@ -131,24 +149,24 @@ void k_conn_local(const int32_t* __restrict__ labels, uint32_t rows, uint32_t co
     const uint32_t lx = threadIdx.x & 63, w = threadIdx.x >> 6;
     const uint32_t gx = x0 + lx;
     const size_t fo = (size_t)blockIdx.y * rows * cols;
-    int32_t lab[4];
+    int32_t v[4];
     bool in[4];
     uint32_t r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t ly = 4 * w + i, gy = y0 + ly, u = lx * kConnPad + ly;
         in[i] = gx < cols && gy < rows;
-        lab[i] = in[i] ? labels[fo + (size_t)gy * cols + gx] : 0;
-        L[u] = lab[i];
+        v[i] = in[i] ? rel.word(src[fo + (size_t)gy * cols + gx]) : 0;      // (nobody asks for the word of a pixel outside the frame)
+        L[u] = v[i];
         C[u] = 0u;
     }
     __syncthreads();
-    // a column's runs as chains: a pixel points at the pixel above it where the labels are equal (the pixel above an inside pixel
+    // a column's runs as chains: a pixel points at the pixel above it where the two are an edge (the pixel above an inside pixel
     // of the tile is inside) ...
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t ly = 4 * w + i, u = lx * kConnPad + ly;
-        P[u] = in[i] && ly > 0 && L[u - 1] == lab[i] ? u - 1 : u;
+        P[u] = in[i] && ly > 0 && rel.edge(v[i], L[u - 1]) ? u - 1 : u;
     }
     __syncthreads();
     // ... and then at the head of its run: walked while nobody writes, stored behind the barrier
@@ -170,15 +188,20 @@ void k_conn_local(const int32_t* __restrict__ labels, uint32_t rows, uint32_t co
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t u = lx * kConnPad + 4 * w + i;
-        // (not where the pixel above and its left neighbour have this label too: the two runs were joined there)
-        if (in[i] && lx > 0 && L[u - kConnPad] == lab[i] && !(4 * w + i > 0 && L[u - 1] == lab[i] && L[u - kConnPad - 1] == lab[i]))
-            conn_lds_unite(P, u, u - kConnPad);
+        if (!in[i] || lx == 0 || !rel.edge(v[i], L[u - kConnPad])) continue;
+        // Not where u-up, up-upleft and upleft-left are edges: u and left are joined through them, u-up and upleft-left by the
+        // column chains, up-upleft by its own union or, by induction up the column, by this same argument.  (Under ==, with u-left
+        // an edge, the third test follows from the other two.)
+        if (4 * w + i > 0 && rel.edge(v[i], L[u - 1]) && rel.edge(L[u - 1], L[u - kConnPad - 1]) &&
+            rel.edge(L[u - kConnPad - 1], L[u - kConnPad]))
+            continue;
+        conn_lds_unite(P, u, u - kConnPad);
     }
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         r[i] = conn_lds_find(P, lx * kConnPad + 4 * w + i);
-        conn_count(C, r[i], in[i]);
+        conn_count(C, r[i], in[i] && rel.live(v[i]));
     }
     __syncthreads();
 #pragma unroll
@@ -188,16 +211,16 @@ void k_conn_local(const int32_t* __restrict__ labels, uint32_t rows, uint32_t co
             const uint32_t rx = r[i] / kConnPad, ry = r[i] - rx * kConnPad;
             const size_t p = fo + (size_t)(y0 + ly) * cols + gx;
             A[p] = conn_key(x0 + rx, y0 + ry, kbits);
-            B[p] = r[i] == u ? C[u] : 0u;
+            B[p] = r[i] == u ? C[u] : 0u;                  // (a pixel that takes no part is its own root with a count of 0)
         }
     }
 }
 
-// grid (ceil(pairs / 256), frames), 256 threads.  Pair j < pairs_v: edge j / rows between tile columns, row j % rows; the others:
-// edge / cols between tile rows, column % cols
-__global__ __launch_bounds__(256)
-void k_conn_border(const int32_t* __restrict__ labels, uint32_t rows, uint32_t cols, uint32_t pairs_v, uint32_t pairs, uint32_t kbits,
-                   uint32_t* A)
+// The border stage.  grid (ceil(pairs / 256), frames), 256 threads.  Pair j < pairs_v: edge j / rows between tile columns, row
+// j % rows; the others: edge / cols between tile rows, column % cols
+template <class R>
+__device__ __forceinline__ void conn_border_body(const R rel, const typename R::Src* __restrict__ src, uint32_t rows, uint32_t cols, uint32_t pairs_v,
+                                                 uint32_t pairs, uint32_t kbits, uint32_t* A)
 {
     const uint32_t j = blockIdx.x * 256u + threadIdx.x;
     if (j >= pairs) return;
@@ -218,11 +241,29 @@ void k_conn_border(const int32_t* __restrict__ labels, uint32_t rows, uint32_t c
         back = xa % kConnTW != 0 ? 1 : 0;
     }
     const size_t pa = fo + (size_t)ya * cols + xa, pb = fo + (size_t)yb * cols + xb;
-    const int32_t lab = labels[pa];
-    if (lab != labels[pb]) return;
-    // those two pixels are joined to this pair's inside their tiles, and that pair joins them across the edge
-    if (back != 0 && labels[pa - back] == lab && labels[pb - back] == lab) return;
+    const int32_t a = rel.word(src[pa]), b = rel.word(src[pb]);
+    if (!rel.edge(a, b)) return;
+    if (back != 0) {
+        // Not where pa-pa', pb-pb' and pa'-pb' are edges: pa-pa' and pb-pb' are joined inside their tiles, pa'-pb' by its own union
+        // or, by induction along the edge, by this same argument.  (Under ==, the third test follows from pa-pb and the other two.)
+        const int32_t a1 = rel.word(src[pa - back]), b1 = rel.word(src[pb - back]);
+        if (rel.edge(a, a1) && rel.edge(b, b1) && rel.edge(a1, b1)) return;
+    }
     conn_unite(A + fo, conn_key(xa, ya, kbits), conn_key(xb, yb, kbits), kbits, cols);
+}
+
+__global__ __launch_bounds__(256)
+void k_conn_local(const int32_t* __restrict__ labels, uint32_t rows, uint32_t cols, uint32_t tiles_x, uint32_t kbits,
+                  uint32_t* __restrict__ A, uint32_t* __restrict__ B)
+{
+    conn_local_body(ConnLabelRel{}, labels, rows, cols, tiles_x, kbits, A, B);
+}
+
+__global__ __launch_bounds__(256)
+void k_conn_border(const int32_t* __restrict__ labels, uint32_t rows, uint32_t cols, uint32_t pairs_v, uint32_t pairs, uint32_t kbits,
+                   uint32_t* A)
+{
+    conn_border_body(ConnLabelRel{}, labels, rows, cols, pairs_v, pairs, kbits, A);
 }
 
 // grid (ceil(n / 256), frames), 256 threads

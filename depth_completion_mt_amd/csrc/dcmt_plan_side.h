@@ -256,15 +256,9 @@ inline int connectivity_max_labels(int rows, int cols, int n_centers)
 
 struct ConnPlan {
     int status;                      // kInvalid: a null or misaligned pointer, n_centers < 1, lims < 4, buffers that overlap
-    uint32_t n;                      // pixels per frame
-    uint32_t kbits;                  // conn_key_bits(rows)
+    ConnGeom g;                      // k_conn_local, k_conn_border, k_conn_flatten; k_conn_relabel: (g.px_x, batch) as well
     uint32_t lim4;                   // lims >> 2: a component is small iff size + (size >= 2) <= lim4
     int max_labels;
-    uint32_t tiles_x, tiles_y;
-    unsigned local_x;                // k_conn_local: (tiles_x * tiles_y, batch)
-    uint32_t pairs_v, pairs;         // pixel pairs across vertical tile edges, across all tile edges
-    unsigned border_x;               // k_conn_border: (border_x, batch); 0: one tile, no launch
-    unsigned px_x;                   // k_conn_flatten, k_conn_relabel: (px_x, batch), one thread per pixel
     uint32_t strips, band_rows;      // k_conn_seed, k_conn_rank: (strips, batch); k_conn_scan: (batch)
     size_t slab;                     // words of the slab this call uses: [batch][strips]
 };
@@ -289,16 +283,8 @@ inline ConnPlan plan_connectivity(int rows, int cols, int batch, int n_centers, 
                    ranges_overlap(counts, sizeof(int32_t) * (size_t)batch, out, bytes)))
         return p;
     p.status = kOk;
-    p.n = (uint32_t)rows * (uint32_t)cols;
-    p.kbits = (uint32_t)conn_key_bits(rows);
+    p.g = conn_geom(rows, cols);
     p.lim4 = (uint32_t)(connectivity_lims(rows, cols, n_centers) >> 2);
-    p.tiles_x = ((uint32_t)cols + kConnTW - 1) / kConnTW;
-    p.tiles_y = ((uint32_t)rows + kConnTH - 1) / kConnTH;
-    p.local_x = p.tiles_x * p.tiles_y;
-    p.pairs_v = (p.tiles_x - 1) * (uint32_t)rows;
-    p.pairs = p.pairs_v + (p.tiles_y - 1) * (uint32_t)cols;
-    p.border_x = (p.pairs + 255) / 256;
-    p.px_x = (p.n + 255) / 256;
     p.strips = ((uint32_t)cols + kConnStripCols - 1) / kConnStripCols;
     p.band_rows = ((uint32_t)rows + kConnWaves - 1) / kConnWaves;
     p.slab = (size_t)batch * p.strips;
@@ -308,19 +294,13 @@ inline ConnPlan plan_connectivity(int rows, int cols, int batch, int n_centers, 
 // ---- dcmt_filter_speckles_dev ---------------------------------------------------------------------------------------------
 // The speckle filter of a 16-bit disparity map (dcmt_kernels_speckle.h): a clear of the counts (where they are wanted) and four
 // launches whose grids depend on the shape alone (the border merge is left out where a frame is one tile), on the context's two
-// 4 B/px planes; the tiles and the pairs are those of plan_connectivity.  The checks on the arguments are here as well, tested
+// 4 B/px planes; the tiles and the pairs are conn_geom's, as for plan_connectivity.  The checks on the arguments are here as well, tested
 // without a device: out may BE disp (the last kernel is the only writer of out and depth, and a thread reads its pixels before it
 // writes them), any other overlap among disp, out, depth and removed is refused.
 struct SpecklePlan {
     int status;                      // kInvalid: a null or misaligned pointer, max_size < 0, max_diff outside 0..65535, new_val outside
                                      // int16, buffers that overlap
-    uint32_t n;                      // pixels per frame
-    uint32_t kbits;                  // conn_key_bits(rows)
-    uint32_t tiles_x, tiles_y;
-    unsigned local_x;                // k_spk_local: (tiles_x * tiles_y, batch)
-    uint32_t pairs_v, pairs;         // pixel pairs across vertical tile edges, across all tile edges
-    unsigned border_x;               // k_spk_border: (border_x, batch); 0: one tile, no launch
-    unsigned px_x;                   // k_conn_flatten: (px_x, batch), one thread per pixel
+    ConnGeom g;                      // k_spk_local, k_spk_border, k_conn_flatten
     int vec;                         // k_spk_apply<vec>: 4 where a frame is a multiple of 4 pixels and disp and out are 8-byte aligned, else 1
     unsigned apply_x;                // its grid: (apply_x, batch)
     size_t clear_bytes;              // hipMemsetAsync of removed: 4 bytes a frame (0: no counts wanted)
@@ -341,17 +321,9 @@ inline SpecklePlan plan_speckles(int rows, int cols, int batch, int64_t max_size
                     (depth && ranges_overlap(removed, rb, depth, 4 * px))))
         return p;
     p.status = kOk;
-    p.n = (uint32_t)rows * (uint32_t)cols;
-    p.kbits = (uint32_t)conn_key_bits(rows);
-    p.tiles_x = ((uint32_t)cols + kConnTW - 1) / kConnTW;
-    p.tiles_y = ((uint32_t)rows + kConnTH - 1) / kConnTH;
-    p.local_x = p.tiles_x * p.tiles_y;
-    p.pairs_v = (p.tiles_x - 1) * (uint32_t)rows;
-    p.pairs = p.pairs_v + (p.tiles_y - 1) * (uint32_t)cols;
-    p.border_x = (p.pairs + 255) / 256;
-    p.px_x = (p.n + 255) / 256;
-    p.vec = p.n % 4 == 0 && disp % 8 == 0 && out % 8 == 0 ? 4 : 1;
-    p.apply_x = (p.n / (uint32_t)p.vec + 255) / 256;
+    p.g = conn_geom(rows, cols);
+    p.vec = p.g.n % 4 == 0 && disp % 8 == 0 && out % 8 == 0 ? 4 : 1;
+    p.apply_x = (p.g.n / (uint32_t)p.vec + 255) / 256;
     p.clear_bytes = removed ? rb : 0;
     return p;
 }

@@ -18,28 +18,28 @@ static ConnPlan checked(int rows, int cols, int batch, int nc)
 {
     const ConnPlan p = plan_connectivity(rows, cols, batch, nc, kLab, kOut, kCnt);
     CHECK(p.status == kOk);
-    CHECK(p.n == (uint32_t)rows * (uint32_t)cols);
+    CHECK(p.g.n == (uint32_t)rows * (uint32_t)cols);
     // keys: ordered as s = x * rows + y, below 2^30, and taken apart again
-    CHECK((1u << p.kbits) >= (uint32_t)rows && (p.kbits == 0 || (1u << (p.kbits - 1)) < (uint32_t)rows));
-    CHECK(((uint64_t)(cols - 1) << p.kbits | (uint64_t)(rows - 1)) < (1ull << 30));
+    CHECK((1u << p.g.kbits) >= (uint32_t)rows && (p.g.kbits == 0 || (1u << (p.g.kbits - 1)) < (uint32_t)rows));
+    CHECK(((uint64_t)(cols - 1) << p.g.kbits | (uint64_t)(rows - 1)) < (1ull << 30));
     CHECK(p.lim4 == (uint32_t)(((rows * cols) / nc) >> 2) && p.lim4 >= 1);
     CHECK(p.max_labels == connectivity_max_labels(rows, cols, nc) && p.max_labels >= 1);
-    CHECK((uint64_t)p.max_labels * (p.lim4 + 1) <= p.n || p.max_labels == 1);
+    CHECK((uint64_t)p.max_labels * (p.lim4 + 1) <= p.g.n || p.max_labels == 1);
     // k_conn_local: every pixel in exactly one tile
-    CHECK(p.tiles_x == (uint32_t)(cols + kConnTW - 1) / kConnTW && p.tiles_y == (uint32_t)(rows + kConnTH - 1) / kConnTH);
-    CHECK(p.local_x == p.tiles_x * p.tiles_y);
+    CHECK(p.g.tiles_x == (uint32_t)(cols + kConnTW - 1) / kConnTW && p.g.tiles_y == (uint32_t)(rows + kConnTH - 1) / kConnTH);
+    CHECK(p.g.local_x == p.g.tiles_x * p.g.tiles_y);
     // k_conn_border: the pairs as the kernel takes them apart -- every pair inside the frame, across a tile edge, none twice
-    CHECK(p.pairs_v == (p.tiles_x - 1) * (uint32_t)rows && p.pairs == p.pairs_v + (p.tiles_y - 1) * (uint32_t)cols);
-    CHECK(p.border_x == (p.pairs + 255) / 256 && (p.border_x == 0) == (p.tiles_x == 1 && p.tiles_y == 1));
-    if (p.n <= 1u << 16) {
-        std::vector<unsigned char> right((size_t)p.n, 0), below((size_t)p.n, 0);
-        for (uint32_t j = 0; j < p.pairs; ++j) {
-            if (j < p.pairs_v) {
+    CHECK(p.g.pairs_v == (p.g.tiles_x - 1) * (uint32_t)rows && p.g.pairs == p.g.pairs_v + (p.g.tiles_y - 1) * (uint32_t)cols);
+    CHECK(p.g.border_x == (p.g.pairs + 255) / 256 && (p.g.border_x == 0) == (p.g.tiles_x == 1 && p.g.tiles_y == 1));
+    if (p.g.n <= 1u << 16) {
+        std::vector<unsigned char> right((size_t)p.g.n, 0), below((size_t)p.g.n, 0);
+        for (uint32_t j = 0; j < p.g.pairs; ++j) {
+            if (j < p.g.pairs_v) {
                 const uint32_t e = j / rows, y = j - e * rows, xb = (e + 1) * kConnTW;
                 CHECK(xb < (uint32_t)cols && y < (uint32_t)rows);
                 ++right[(size_t)y * cols + xb - 1];
             } else {
-                const uint32_t jj = j - p.pairs_v, e = jj / cols, x = jj - e * cols, yb = (e + 1) * kConnTH;
+                const uint32_t jj = j - p.g.pairs_v, e = jj / cols, x = jj - e * cols, yb = (e + 1) * kConnTH;
                 CHECK(yb < (uint32_t)rows && x < (uint32_t)cols);
                 ++below[(size_t)(yb - 1) * cols + x];
             }
@@ -52,7 +52,7 @@ static ConnPlan checked(int rows, int cols, int batch, int nc)
             }
         CHECK(wrong == 0);
     }
-    CHECK(p.px_x == (p.n + 255) / 256);
+    CHECK(p.g.px_x == (p.g.n + 255) / 256);
     // k_conn_seed / k_conn_rank: the strips cover the columns, the four bands the rows
     CHECK(p.strips == (uint32_t)(cols + kConnStripCols - 1) / kConnStripCols);
     CHECK(p.band_rows * kConnWaves >= (uint32_t)rows && (p.band_rows - 1) * kConnWaves < (uint32_t)rows);
@@ -70,11 +70,11 @@ static void test_plans()
                 if (n / nc >= 4) checked(s[0], s[1], batch, nc);
         }
     const ConnPlan k = checked(352, 1216, 256, 1273);
-    CHECK(k.kbits == 9 && k.lim4 == 84 && k.max_labels == 5035 && k.tiles_x == 19 && k.tiles_y == 22 && k.strips == 19 && k.band_rows == 88);
-    CHECK(checked(16, 64, 1, 4).border_x == 0 && checked(17, 64, 1, 4).border_x == 1 && checked(16, 65, 1, 4).pairs == 16);
-    CHECK(checked(1, 4, 1, 1).max_labels == 2 && checked(2, 2, 1, 1).kbits == 1 && checked(1, 70, 1, 1).kbits == 0);
+    CHECK(k.g.kbits == 9 && k.lim4 == 84 && k.max_labels == 5035 && k.g.tiles_x == 19 && k.g.tiles_y == 22 && k.strips == 19 && k.band_rows == 88);
+    CHECK(checked(16, 64, 1, 4).g.border_x == 0 && checked(17, 64, 1, 4).g.border_x == 1 && checked(16, 65, 1, 4).g.pairs == 16);
+    CHECK(checked(1, 4, 1, 1).max_labels == 2 && checked(2, 2, 1, 1).g.kbits == 1 && checked(1, 70, 1, 1).g.kbits == 0);
     // the largest frames dcmt_create admits
-    CHECK(checked(1, 0x1ffffff0, 1, 7).status == kOk && checked(0x1ffffff0, 1, 1, 7).kbits == 29);
+    CHECK(checked(1, 0x1ffffff0, 1, 7).status == kOk && checked(0x1ffffff0, 1, 1, 7).g.kbits == 29);
     CHECK(checked(16384, 32767, 1, 1200).status == kOk);
 }
 

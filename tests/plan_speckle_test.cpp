@@ -21,15 +21,15 @@ static SpecklePlan good(int rows, int cols, int batch, uintptr_t disp = kDisp, u
     const SpecklePlan p = plan_speckles(rows, cols, batch, 200, 32, -16, disp, out, depth, removed);
     CHECK(p.status == kOk);
     const uint64_t n = (uint64_t)rows * cols;
-    CHECK(p.n == n && (1u << p.kbits) >= (uint32_t)rows && (p.kbits == 0 || (1u << (p.kbits - 1)) < (uint32_t)rows));
-    CHECK(((uint64_t)(cols - 1) << p.kbits | (uint64_t)(rows - 1)) < (1ull << 32));              // every key fits a word
-    CHECK((uint64_t)p.tiles_x * kConnTW >= (uint64_t)cols && (uint64_t)(p.tiles_x - 1) * kConnTW < (uint64_t)cols);
-    CHECK((uint64_t)p.tiles_y * kConnTH >= (uint64_t)rows && (uint64_t)(p.tiles_y - 1) * kConnTH < (uint64_t)rows);
-    CHECK(p.local_x == (uint64_t)p.tiles_x * p.tiles_y && p.local_x <= 0x7fffffffu);
-    CHECK(p.pairs_v == (uint64_t)(p.tiles_x - 1) * rows && p.pairs == (uint64_t)p.pairs_v + (uint64_t)(p.tiles_y - 1) * cols);
-    CHECK((uint64_t)p.border_x * 256 >= p.pairs && (p.border_x == 0 || (uint64_t)(p.border_x - 1) * 256 < p.pairs));
-    CHECK((p.border_x == 0) == (p.tiles_x == 1 && p.tiles_y == 1));
-    CHECK((uint64_t)p.px_x * 256 >= n && (uint64_t)(p.px_x - 1) * 256 < n);
+    CHECK(p.g.n == n && (1u << p.g.kbits) >= (uint32_t)rows && (p.g.kbits == 0 || (1u << (p.g.kbits - 1)) < (uint32_t)rows));
+    CHECK(((uint64_t)(cols - 1) << p.g.kbits | (uint64_t)(rows - 1)) < (1ull << 32));              // every key fits a word
+    CHECK((uint64_t)p.g.tiles_x * kConnTW >= (uint64_t)cols && (uint64_t)(p.g.tiles_x - 1) * kConnTW < (uint64_t)cols);
+    CHECK((uint64_t)p.g.tiles_y * kConnTH >= (uint64_t)rows && (uint64_t)(p.g.tiles_y - 1) * kConnTH < (uint64_t)rows);
+    CHECK(p.g.local_x == (uint64_t)p.g.tiles_x * p.g.tiles_y && p.g.local_x <= 0x7fffffffu);
+    CHECK(p.g.pairs_v == (uint64_t)(p.g.tiles_x - 1) * rows && p.g.pairs == (uint64_t)p.g.pairs_v + (uint64_t)(p.g.tiles_y - 1) * cols);
+    CHECK((uint64_t)p.g.border_x * 256 >= p.g.pairs && (p.g.border_x == 0 || (uint64_t)(p.g.border_x - 1) * 256 < p.g.pairs));
+    CHECK((p.g.border_x == 0) == (p.g.tiles_x == 1 && p.g.tiles_y == 1));
+    CHECK((uint64_t)p.g.px_x * 256 >= n && (uint64_t)(p.g.px_x - 1) * 256 < n);
     CHECK(p.vec == 1 || p.vec == 4);
     CHECK((p.vec == 4) == (n % 4 == 0 && disp % 8 == 0 && out % 8 == 0));
     const uint64_t threads = n / p.vec;
@@ -54,12 +54,12 @@ int main()
         }
     {
         const SpecklePlan p = good(16, 64, 3);
-        CHECK(p.tiles_x == 1 && p.tiles_y == 1 && p.local_x == 1 && p.pairs == 0 && p.border_x == 0 && p.px_x == 4 && p.vec == 4 && p.apply_x == 1);
+        CHECK(p.g.tiles_x == 1 && p.g.tiles_y == 1 && p.g.local_x == 1 && p.g.pairs == 0 && p.g.border_x == 0 && p.g.px_x == 4 && p.vec == 4 && p.apply_x == 1);
         const SpecklePlan q = good(17, 65, 3);
-        CHECK(q.tiles_x == 2 && q.tiles_y == 2 && q.pairs_v == 17 && q.pairs == 17 + 65 && q.border_x == 1 && q.vec == 1 && q.apply_x == 5 && q.kbits == 5);
+        CHECK(q.g.tiles_x == 2 && q.g.tiles_y == 2 && q.g.pairs_v == 17 && q.g.pairs == 17 + 65 && q.g.border_x == 1 && q.vec == 1 && q.apply_x == 5 && q.g.kbits == 5);
         const SpecklePlan r = good(352, 1216, 64);
-        CHECK(r.tiles_x == 19 && r.tiles_y == 22 && r.pairs_v == 18 * 352 && r.pairs == 18 * 352 + 21 * 1216 && r.vec == 4 && r.apply_x == 418);
-        CHECK(good(1, 1, 1).kbits == 0 && good(1, 1, 1).local_x == 1 && good(1, 1, 1).vec == 1);
+        CHECK(r.g.tiles_x == 19 && r.g.tiles_y == 22 && r.g.pairs_v == 18 * 352 && r.g.pairs == 18 * 352 + 21 * 1216 && r.vec == 4 && r.apply_x == 418);
+        CHECK(good(1, 1, 1).g.kbits == 0 && good(1, 1, 1).g.local_x == 1 && good(1, 1, 1).vec == 1);
     }
 
     // ---- refusals --------------------------------------------------------------------------------------------------------------
