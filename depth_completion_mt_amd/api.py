@@ -253,6 +253,19 @@ def _speckle_kw(speckle_window, speckle_range) -> dict | None:
     return kw if make_speckle_params(**kw).max_size > 0 else None
 
 
+SGM_MAX_P2_EIGHT_PATHS = 1800       # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
+
+
+def _check_sgm_paths(paths, p: L.SgmParams) -> int:
+    """The `paths` keyword of sgm_dev / sgm / stereo_sgm: 4 or 8, and with 8 the tighter limit on p2.  Raises ValueError on what
+    dcmt_sgm_paths_dev refuses of them, before any call."""
+    if isinstance(paths, bool) or int(paths) != paths or int(paths) not in (4, 8):
+        raise ValueError(f"paths = {paths!r}: 4 or 8")
+    if int(paths) == 8 and p.p2 > SGM_MAX_P2_EIGHT_PATHS:
+        raise ValueError(f"p2 = {p.p2} with paths = 8: p2 <= {SGM_MAX_P2_EIGHT_PATHS}")
+    return int(paths)
+
+
 def sgm_workspace_bytes(rows: int, cols: int, num_disparities: int = 64, frames: int = 1) -> int:
     """dcmt_sgm_workspace_bytes: the bytes of workspace that hold `frames` frames in flight (0 for sizes the call refuses)."""
     return int(L.lib().dcmt_sgm_workspace_bytes(rows, cols, num_disparities, frames))
@@ -809,7 +822,7 @@ class Context:
     # ---- dense stereo matching (dcmt_sgm*) --------------------------------------------------
     def sgm_dev(self, d_left, d_right, disp16: bool = True, depth: bool = False, d_disp16=None, d_depth=None, d_work=None,
                 frames_in_flight: int | None = None, stream: int | None = None, speckle_window: int | None = None,
-                speckle_range: int | None = None, **kw):
+                speckle_range: int | None = None, paths: int = 4, **kw):
         """Semi-global stereo matching on the device (dcmt_sgm_dev, as include/dcmt.h states it; the reference's cv::StereoSGBM block,
         SL/main_sl.cpp:1293-1339): a rectified grey pair (uint8 CUDA tensors [batch][rows][cols], what bgr_convert_dev(gray=True) writes)
         -> the int16 disparity map in sixteenths of a pixel (-16: invalid) and / or the f32 depth plane stereo_refine_dev,
@@ -818,6 +831,8 @@ class Context:
         sgm_workspace_bytes(rows, cols, D, 1) bytes, 16-byte aligned; the batch is worked through in chunks of as many frames as it
         holds.  Without one a workspace for frames_in_flight frames (default: the batch, but no more than 1 GiB and at least one frame)
         is allocated on the stream the call enqueues on.  kw: the fields of make_sgm_params.
+        paths: 4 (dcmt_sgm_dev: the two horizontal and the two vertical paths) or 8 (dcmt_sgm_paths_dev: the four diagonals as well, two
+        more launches a chunk; p2 <= 1800).  Anything else, or a larger p2 with 8, raises ValueError before any call.
         speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (whole disparities: max_diff = 16 *
         speckle_range; the reference's are 200 and 2).  With both None nothing changes and no further call is made; with a window > 0
         filter_speckles_dev is enqueued behind the matcher on the same stream, in place on both outputs."""
@@ -826,6 +841,7 @@ class Context:
         b, r, c = _brc(d_left)
         want_disp, want_depth = disp16 or d_disp16 is not None, depth or d_depth is not None
         p = make_sgm_params(for_depth=want_depth, **kw)
+        paths = _check_sgm_paths(paths, p)
         assert want_disp or want_depth
         speckle = _speckle_kw(speckle_window, speckle_range)
         asked_disp, want_disp = want_disp, want_disp or speckle is not None        # the filter works on the disparities
@@ -842,18 +858,22 @@ class Context:
         assert d_disp16 is None or (_is_dev(d_disp16, torch.int16) and d_disp16.numel() == b * r * c)
         assert d_depth is None or (_is_dev(d_depth, torch.float32) and d_depth.numel() == b * r * c)
         assert _is_dev(d_work)
-        st = L.lib().dcmt_sgm_dev(self._h, d_left.data_ptr(), d_right.data_ptr(), d_disp16.data_ptr() if want_disp else None,
-                                  d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p), d_work.data_ptr(),
-                                  d_work.numel() * d_work.element_size(), _stream(stream, d_left))
-        _check(st, "dcmt_sgm_dev")
+        args = (self._h, d_left.data_ptr(), d_right.data_ptr(), d_disp16.data_ptr() if want_disp else None,
+                d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p))
+        tail = (d_work.data_ptr(), d_work.numel() * d_work.element_size(), _stream(stream, d_left))
+        if paths == 4:
+            _check(L.lib().dcmt_sgm_dev(*args, *tail), "dcmt_sgm_dev")
+        else:
+            _check(L.lib().dcmt_sgm_paths_dev(*args, paths, *tail), "dcmt_sgm_paths_dev")
         if speckle is not None:
             self.filter_speckles_dev(d_disp16, d_depth=d_depth if want_depth else None, d_out=d_disp16, stream=stream, **speckle)
         return (d_disp16, d_depth) if asked_disp and want_depth else d_disp16 if asked_disp else d_depth
 
     def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, speckle_window: int | None = None,
-            speckle_range: int | None = None, **kw):
+            speckle_range: int | None = None, paths: int = 4, **kw):
         """One pair of host memory (dcmt_sgm, synchronous; any row stride): (int16 [rows][cols], f32 [rows][cols]), or the one that is
-        wanted.  speckle_window, speckle_range: as sgm_dev; the filter is a second host call (dcmt_filter_speckles), in place."""
+        wanted.  speckle_window, speckle_range: as sgm_dev; the filter is a second host call (dcmt_filter_speckles), in place.
+        paths: as sgm_dev (8: dcmt_sgm_paths)."""
         imgs = []
         for a in (left, right):
             a = np.asarray(a, dtype=np.uint8)
@@ -866,10 +886,13 @@ class Context:
         d = np.empty((rows, cols), dtype=np.int16) if disp16 else None
         z = np.empty((rows, cols), dtype=np.float32) if depth else None
         p = make_sgm_params(for_depth=depth, **kw)
-        st = L.lib().dcmt_sgm(self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0], rows, cols, ctypes.byref(p),
-                              d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None,
-                              z.strides[0] if depth else 0)
-        _check(st, "dcmt_sgm")
+        paths = _check_sgm_paths(paths, p)
+        args = (self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0], rows, cols, ctypes.byref(p),
+                d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None, z.strides[0] if depth else 0)
+        if paths == 4:
+            _check(L.lib().dcmt_sgm(*args), "dcmt_sgm")
+        else:
+            _check(L.lib().dcmt_sgm_paths(*args, paths), "dcmt_sgm_paths")
         if speckle is not None:
             sp = make_speckle_params(**speckle)
             st = L.lib().dcmt_filter_speckles(self._h, d.ctypes.data, d.strides[0], d.ctypes.data, d.strides[0], z.ctypes.data if depth else None,
@@ -1375,15 +1398,18 @@ def get_initial_error(depth, left, right, **params):
     return e, {k: int(v) for k, v in zip(PHOTO_STATS, s)}
 
 
-def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = None, speckle_range: int | None = None, **params):
+def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = None, speckle_range: int | None = None, paths: int = 4,
+               **params):
     """Semi-global matching of one rectified host pair (dcmt_sgm): the int16 disparity map in sixteenths of a pixel, -16 where invalid,
     as cv::StereoSGBM::compute returns it (SL/main_sl.cpp:1293-1339); with depth=True (disp16, depth).  left, right: grey uint8
     [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params.
-    speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (the reference's: 200, 2); None, None: no filter."""
+    speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (the reference's: 200, 2); None, None: no filter.
+    paths: 4, or 8 for the four diagonal paths as well (p2 <= 1800 then); ValueError otherwise, before any call."""
+    _check_sgm_paths(paths, make_sgm_params(for_depth=depth, **params))
     imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
     imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
     return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, speckle_window=speckle_window,
-                                                                speckle_range=speckle_range, **params)
+                                                                speckle_range=speckle_range, paths=paths, **params)
 
 
 def filter_speckles(disp16, depth=None, **params):

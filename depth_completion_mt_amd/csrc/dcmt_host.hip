@@ -192,11 +192,12 @@ int dcmt_photo_error(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_
     return rc == DCMT_OK ? fetch(ctx, {&e, &s}) : rc;
 }
 
-int dcmt_sgm(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols, const dcmt_sgm_params* params,
-             int16_t* disp16, size_t drs, float* depth, size_t zrs)
+int dcmt_sgm_paths(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols, const dcmt_sgm_params* params,
+                   int16_t* disp16, size_t drs, float* depth, size_t zrs, int paths)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !left || !right || (!disp16 && !depth) || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    if (paths != 4 && paths != 8) return DCMT_E_INVALID;    // before anything is allocated or staged
     const size_t work_bytes = dcmt_sgm_workspace_bytes(rows, cols, params->num_disparities, 1);
     if (!work_bytes) return DCMT_E_INVALID;
     Plane l(left, lrs, cols, rows), r(right, rrs, cols, rows);
@@ -208,9 +209,15 @@ int dcmt_sgm(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* righ
     DCMT_HIP(ctx, hipMalloc(&work.dev, work_bytes));        // before stage(): nothing of the call is in the stream if it fails
     int rc = stage(ctx, {&l, &r}, {&d, &z});
     if (rc == DCMT_OK)
-        rc = dcmt_sgm_dev(ctx, (const uint8_t*)l.dev, (const uint8_t*)r.dev, (int16_t*)d.dev, (float*)z.dev, rows, cols, 1, params, work.dev, work_bytes,
-                          ctx->own_stream);
+        rc = dcmt_sgm_paths_dev(ctx, (const uint8_t*)l.dev, (const uint8_t*)r.dev, (int16_t*)d.dev, (float*)z.dev, rows, cols, 1, params, paths, work.dev,
+                                work_bytes, ctx->own_stream);
     return rc == DCMT_OK ? fetch(ctx, {&d, &z}) : rc;
+}
+
+int dcmt_sgm(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols, const dcmt_sgm_params* params,
+             int16_t* disp16, size_t drs, float* depth, size_t zrs)
+{
+    return dcmt_sgm_paths(ctx, left, lrs, right, rrs, rows, cols, params, disp16, drs, depth, zrs, 4);
 }
 
 int dcmt_filter_speckles(dcmt_ctx* ctx, const int16_t* disp16, size_t drs, int16_t* out, size_t ors, float* depth, size_t zrs, int rows, int cols,

@@ -1,10 +1,13 @@
-// dcmt_kernels_sgm.h -- semi-global stereo matching as include/dcmt.h states it (dcmt_sgm_dev), three kernels per chunk of frames:
+// dcmt_kernels_sgm.h -- semi-global stereo matching as include/dcmt.h states it (dcmt_sgm_dev), three kernels per chunk of frames
+// (five launches with eight paths):
 //   k_sgm_rows    one wave per image row, lane = disparity (D = 128: lanes carry d and d + 64).  The grey rows y-2..y+2 of both images
 //                 are staged in LDS, packed by column (four rows in one dword, the fifth in the next), so that the column sum of
 //                 absolute differences of one (x, d) is two v_sad_u8; the 5-column box runs along the row in registers.  C is written,
 //                 the left->right path is carried in registers and written as S; then the wave walks back over the C it has just
 //                 written (every lane reads what it wrote itself) and adds the right->left path into S.
 //   k_sgm_cols    one wave per image column: down, then up, adding both paths into S.
+//   k_sgm_diag    with eight paths (dcmt_sgm_paths_dev), twice between k_sgm_cols and k_sgm_winner, once per orientation of the
+//                 diagonals: one wave per start column on a line that wraps around the frame's sides, down, then up.
 //   k_sgm_winner  one wave per 64 pixels of a row, four pixels in flight: steps 4..9 of the definition; the right disparity is a strided
 //                 read of S.  Lane i keeps pixel i's result, so the outputs are stored coalesced.
 // A path step is two DPP wave shifts (the neighbours d-1, d+1), a DPP min-scan whose result is read from lane 63, and four v_min.
@@ -76,6 +79,14 @@ struct SgmPath {
 #pragma unroll
         for (int k = 0; k < NPL; ++k) prev[k] = next[k];
     }
+    // a pixel that may be the first of a path, without a branch: behind a previous pixel whose L_r is 0 at every disparity a step gives
+    // m = 0 and min(0, p1, p1, p2) = 0, that is L_r = C, which is what start() gives (an absent disparity stays absent: c decides)
+    __device__ __forceinline__ void restart_or_step(bool first, const int (&c)[NPL], int p1, int p2)
+    {
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) prev[k] = first ? 0 : prev[k];
+        step(c, p1, p2);
+    }
 };
 
 // One path along a line of n pixels of a frame's volumes, added into S: pixel i is at element first + i * stride (+ the lane's
@@ -107,6 +118,60 @@ __device__ __forceinline__ void sgm_line(const uint16_t* C, uint16_t* S, ptrdiff
                 for (int k = 0; k < NPL; ++k)
                     if (lane + 64 * k < D)
                         S[first + (ptrdiff_t)(i + j) * stride + (ptrdiff_t)(lane + 64 * k)] = (uint16_t)(sb[j][k] + path.prev[k]);
+            }
+            load(i + j + kSgmAhead, cb[j], sb[j]);
+        }
+    }
+}
+
+// One wrapped diagonal walk of a frame's volumes, added into S: the wave of start column w visits pixel (y, (w + SX y) mod cols) of
+// every row, top to bottom (dy = +1) or bottom to top (dy = -1).  The path restarts on the walk's first pixel and wherever the column
+// wrapped on the way to this pixel -- the previous pixel of the walk is then not its diagonal predecessor inside the frame -- so
+// every run between restarts is one maximal diagonal of the frame in direction (dy, SX dy), and the cols waves cover every pixel
+// once.  C, S: the frame's volumes; w, and with it every cursor, is the same in all lanes.  The loads run kSgmAhead pixels in front
+// of the path steps, as in sgm_line.
+template <int NPL, int SX>
+__device__ __forceinline__ void sgm_wrapped_line(const uint16_t* C, uint16_t* S, int w, int rows, int cols, int dy, int lane, int D, int p1, int p2)
+{
+    const ptrdiff_t pitch = (ptrdiff_t)cols * (ptrdiff_t)D;
+    const int dx = SX * dy, y0 = dy > 0 ? 0 : rows - 1;
+    int x0 = (int)(((long long)w + (long long)SX * (long long)y0) % (long long)cols);
+    if (x0 < 0) x0 += cols;
+    // a cursor: the column and the element offset of (y, x, 0); one row on, the column moves by dx and wraps
+    const ptrdiff_t onward = (ptrdiff_t)dy * pitch + (ptrdiff_t)dx * (ptrdiff_t)D, back = -(ptrdiff_t)dx * pitch;
+    const auto advance = [&](int& x, ptrdiff_t& at) {
+        x += dx;
+        at += onward;
+        const bool wrap = dx > 0 ? x == cols : x < 0;
+        x = wrap ? (dx > 0 ? 0 : cols - 1) : x;
+        at = wrap ? at + back : at;
+    };
+    int xl = x0, xp = x0;                                    // the cursor of the loads and, kSgmAhead pixels behind it, that of the path
+    ptrdiff_t al = (ptrdiff_t)y0 * pitch + (ptrdiff_t)x0 * (ptrdiff_t)D, ap = al;
+    int cb[kSgmAhead][NPL], sb[kSgmAhead][NPL];
+    // pixel i of the walk, which the load cursor stands on: called for i = 0, 1, 2, ... in turn (beyond the walk nothing is read)
+    const auto load = [&](int i, int (&c)[NPL], int (&sv)[NPL]) {
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const bool have = i < rows && lane + 64 * k < D;
+            c[k] = have ? (int)C[al + (ptrdiff_t)(lane + 64 * k)] : kSgmAbsent;
+            sv[k] = have ? (int)S[al + (ptrdiff_t)(lane + 64 * k)] : 0;
+        }
+        advance(xl, al);
+    };
+#pragma unroll
+    for (int j = 0; j < kSgmAhead; ++j) load(j, cb[j], sb[j]);
+    SgmPath<NPL> path = {};
+    for (int i = 0; i < rows; i += kSgmAhead) {
+#pragma unroll
+        for (int j = 0; j < kSgmAhead; ++j) {
+            if (i + j < rows) {
+                const bool wrapped = dx > 0 ? xp == 0 : xp == cols - 1;
+                path.restart_or_step(i + j == 0 || wrapped, cb[j], p1, p2);
+#pragma unroll
+                for (int k = 0; k < NPL; ++k)
+                    if (lane + 64 * k < D) S[ap + (ptrdiff_t)(lane + 64 * k)] = (uint16_t)(sb[j][k] + path.prev[k]);
+                advance(xp, ap);
             }
             load(i + j + kSgmAhead, cb[j], sb[j]);
         }
@@ -199,6 +264,22 @@ __global__ __launch_bounds__(64 * kSgmWaves) void k_sgm_cols(uint16_t* __restric
     uint16_t* S = vol + frame * 2 * ve + ve + (size_t)x * (size_t)D;
     sgm_line<NPL>(C, S, 0, (ptrdiff_t)pitch, rows, lane, D, p1, p2);                                   // top -> bottom
     sgm_line<NPL>(C, S, (ptrdiff_t)(rows - 1) * (ptrdiff_t)pitch, -(ptrdiff_t)pitch, rows, lane, D, p1, p2);   // bottom -> top
+}
+
+// The two diagonal paths of one orientation, added into S: SX = +1 the "\" lines, (+1,+1) going down and (-1,-1) going up; SX = -1 the
+// "/" lines, (+1,-1) and (-1,+1).  One wave per start column, walking wrapped lines (sgm_wrapped_line), so that every wave has rows
+// pixels whatever the lengths of the diagonals it is made of.  Within one orientation every pixel is on exactly one line, so S is
+// read and written plainly; the two orientations are two launches because their lines cross.
+template <int NPL, int SX>
+__global__ __launch_bounds__(64 * kSgmWaves) void k_sgm_diag(uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2)
+{
+    const int w = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * kSgmWaves + threadIdx.x / 64u)), lane = sgm_lane();
+    if (w >= cols) return;                                  // whole waves: no barrier follows
+    const size_t frame = blockIdx.y, ve = (size_t)rows * (size_t)cols * (size_t)D;
+    const uint16_t* C = vol + frame * 2 * ve;
+    uint16_t* S = vol + frame * 2 * ve + ve;
+    sgm_wrapped_line<NPL, SX>(C, S, w, rows, cols, +1, lane, D, p1, p2);
+    sgm_wrapped_line<NPL, SX>(C, S, w, rows, cols, -1, lane, D, p1, p2);
 }
 
 // disp16 and depth: [frames][rows][cols], either may be null

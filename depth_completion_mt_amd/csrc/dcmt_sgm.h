@@ -1,5 +1,6 @@
-// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_cols, k_sgm_winner) shares with its plan, and the plan itself
-// (plan_sgm): the checks on the arguments of dcmt_sgm_dev, the workspace layout, the chunking of the batch and the launch shapes.
+// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its plan, and the plan
+// itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev, the workspace layout, the chunking of the batch
+// and the launch shapes.
 // Plain C++, no HIP: the plan is tested on a CPU (tests/plan_sgm_test.cpp).
 #ifndef DCMT_SGM_H
 #define DCMT_SGM_H
@@ -13,8 +14,9 @@ namespace dcmt {
 
 constexpr int kSgmMinDisp = 16, kSgmMaxDisp = 128;      // D: a multiple of 16 in this range; D > 64: two disparities a lane
 constexpr int kSgmMaxP2 = 10000;                        // S <= 4 * (6375 + p2) <= 65500 fits uint16
+constexpr int kSgmMaxP2Eight = 1800;                    // eight paths: S <= 8 * (6375 + p2) <= 65400
 constexpr int kSgmRowThreads = 64;                      // k_sgm_rows: one wave = one row, lane = disparity
-constexpr int kSgmWaves = 4;                            // k_sgm_cols, k_sgm_winner: waves per workgroup
+constexpr int kSgmWaves = 4;                            // k_sgm_cols, k_sgm_diag, k_sgm_winner: waves per workgroup
 constexpr int kSgmSegment = 64;                         // k_sgm_winner: pixels of a row per wave, one result a lane
 constexpr size_t kSgmLdsBudget = 64 * 1024;             // k_sgm_rows stages 16 bytes a column: up to 4096 columns, wider rows from global memory
 constexpr uint32_t kSgmLdsPerCol = 16;                  // rows y-2..y+2 of one column, left (8 bytes: 4 + 1 used) and right (8 bytes)
@@ -28,6 +30,8 @@ inline size_t sgm_frame_bytes(int rows, int cols, int disparities)
 }
 
 inline bool sgm_disparities_ok(int d) { return d >= kSgmMinDisp && d <= kSgmMaxDisp && d % 16 == 0; }
+inline bool sgm_paths_ok(int paths) { return paths == 4 || paths == 8; }
+inline int sgm_max_p2(int paths) { return paths == 8 ? kSgmMaxP2Eight : kSgmMaxP2; }
 
 struct SgmPlan {
     int status;                      // kInvalid: see dcmt.h's list for dcmt_sgm_dev (the float parameters are the caller's check)
@@ -42,6 +46,8 @@ struct SgmPlan {
     unsigned cols_grid_x;            // k_sgm_cols: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a column
     unsigned winner_grid_x;          // k_sgm_winner: (ceil(rows * ceil(cols / kSgmSegment) / kSgmWaves), frames), a wave a segment
     unsigned segments;               // ceil(cols / kSgmSegment)
+    int paths;                       // 4, or 8: k_sgm_diag runs twice between k_sgm_cols and k_sgm_winner, once per orientation
+    unsigned diag_grid_x;            // k_sgm_diag: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a start column; 0 with 4 paths
 };
 
 // frames of chunk i
@@ -51,14 +57,14 @@ inline int sgm_chunk_frames(const SgmPlan& p, int batch, int i)
     return (int)(first + p.chunk <= batch ? p.chunk : batch - first);
 }
 
-// rows, cols, batch >= 1 and within the context's limits
+// rows, cols, batch >= 1 and within the context's limits; paths: 4 (dcmt_sgm_dev) or 8 (the four diagonals as well)
 inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, int p2, int uniqueness, uintptr_t left, uintptr_t right,
-                        uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes)
+                        uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes, int paths = 4)
 {
     SgmPlan p = {};
     p.status = kInvalid;
-    if (!left || !right || (!disp16 && !depth) || !work || !sgm_disparities_ok(disparities)) return p;
-    if (p1 < 0 || p1 > p2 || p2 > kSgmMaxP2 || uniqueness < 0 || uniqueness > 100) return p;
+    if (!left || !right || (!disp16 && !depth) || !work || !sgm_disparities_ok(disparities) || !sgm_paths_ok(paths)) return p;
+    if (p1 < 0 || p1 > p2 || p2 > sgm_max_p2(paths) || uniqueness < 0 || uniqueness > 100) return p;
     if (disp16 % 2 != 0 || depth % 4 != 0 || work % 16 != 0) return p;
     p.frame_bytes = sgm_frame_bytes(rows, cols, disparities);
     if (work_bytes < p.frame_bytes) return p;
@@ -82,6 +88,8 @@ inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, 
     p.cols_grid_x = ((unsigned)cols + kSgmWaves - 1) / kSgmWaves;
     p.segments = ((unsigned)cols + kSgmSegment - 1) / kSgmSegment;
     p.winner_grid_x = (unsigned)(((uint64_t)rows * p.segments + kSgmWaves - 1) / kSgmWaves);
+    p.paths = paths;
+    p.diag_grid_x = paths == 8 ? p.cols_grid_x : 0;
     return p;
 }
 

@@ -1,6 +1,7 @@
 // dcmt_sgm.hip -- semi-global stereo matching (dcmt_kernels_sgm.h), a code object of its own: dcmt_default_sgm_params,
-// dcmt_sgm_workspace_bytes and dcmt_sgm_dev.  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's workspace out
-// and cuts the batch into chunks; this file launches what it says.  The single-pair host form, dcmt_sgm, is in dcmt_host.hip.
+// dcmt_sgm_workspace_bytes, dcmt_sgm_dev and dcmt_sgm_paths_dev (of which dcmt_sgm_dev is the four-path case).  The plan (dcmt_sgm.h:
+// plan_sgm) checks the arguments, lays the caller's workspace out and cuts the batch into chunks; this file launches what it says.
+// The single-pair host forms, dcmt_sgm and dcmt_sgm_paths, are in dcmt_host.hip.
 #include <initializer_list>
 
 #include "dcmt.h"
@@ -21,6 +22,11 @@ static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_
     else
         hipLaunchKernelGGL((k_sgm_rows<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2);
     hipLaunchKernelGGL((k_sgm_cols<NPL>), cols_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
+    if (pl.paths == 8) {                                    // one launch per orientation: a "\" line and a "/" line cross
+        const dim3 diag_grid(pl.diag_grid_x, (unsigned)frames);
+        hipLaunchKernelGGL((k_sgm_diag<NPL, +1>), diag_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
+        hipLaunchKernelGGL((k_sgm_diag<NPL, -1>), diag_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
+    }
     const SgmK K = {D, P.uniqueness, P.disp12_max_diff, P.baseline * P.focal, P.max_depth};
     hipLaunchKernelGGL((k_sgm_winner<NPL>), winner_grid, dim3(64 * kSgmWaves), 0, st, (const uint16_t*)vol, disp16, depth, rows, cols, pl.segments, K);
 }
@@ -46,8 +52,8 @@ size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int fra
     return (size_t)frames * plan::sgm_frame_bytes(rows, cols, num_disparities);
 }
 
-int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
-                 const dcmt_sgm_params* params, void* d_work, size_t work_bytes, void* stream)
+int dcmt_sgm_paths_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
+                       const dcmt_sgm_params* params, int paths, void* d_work, size_t work_bytes, void* stream)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
@@ -55,7 +61,7 @@ int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, i
         for (const float v : {params->baseline, params->focal, params->max_depth})
             if (!finite_bits(v) || !(v > 0.0f)) return DCMT_E_INVALID;
     const plan::SgmPlan pl = plan::plan_sgm(rows, cols, batch, params->num_disparities, params->p1, params->p2, params->uniqueness, (uintptr_t)d_left,
-                                            (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes);
+                                            (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes, paths);
     if (pl.status != plan::kOk) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t px = (size_t)rows * (size_t)cols;
@@ -69,6 +75,12 @@ int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, i
     }
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
+                 const dcmt_sgm_params* params, void* d_work, size_t work_bytes, void* stream)
+{
+    return dcmt_sgm_paths_dev(ctx, d_left, d_right, d_disp16, d_depth, rows, cols, batch, params, 4, d_work, work_bytes, stream);
 }
 
 }  // extern "C"

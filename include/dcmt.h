@@ -882,6 +882,11 @@ int dcmt_photo_error(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
  *        L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1) + p1, L_r(p-r,d+1) + p1, m + p2) - m,
  *      neighbours d-1 < 0 and d+1 >= D absent.  Then C <= L_r <= C + p2, so S = sum over r of L_r <= 4 * (6375 + 10000) = 65500: S and
  *      every L_r fit uint16, which is why p2 <= 10000.  With p1 = p2 = 0: L_r = C, S = 4 C, plain block matching.
+ *      With paths == 8 (dcmt_sgm_paths_dev) four more directions r = (dy, dx) are added: (+1,+1), (-1,-1), (+1,-1), (-1,+1).  Each path
+ *      is a maximal diagonal line of the frame: it starts on the pixel of the line that has no predecessor p - r inside the frame,
+ *      where L_r = C, and ends where it leaves the frame; the recurrence, p1, p2 and the absent neighbours are those above.  S is the
+ *      sum of all eight L_r <= 8 * (6375 + p2), which fits uint16 for p2 <= 1816: with eight paths p2 <= 1800, so S <= 65400.  With
+ *      p1 = p2 = 0: S = 8 C.  Steps 4..9 do not depend on the number of paths.
  *   4. winner      d* = the lowest d that minimises S(y,x,.).
  *   5. uniqueness  invalid if some d with |d - d*| > 1 has S(d) * (100 - uniqueness) < S(d*) * 100.
  *   6. inside      invalid if x - d* < 0.
@@ -921,12 +926,26 @@ size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int fra
 int dcmt_sgm_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right,
                  int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
                  const dcmt_sgm_params *params, void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
+/* The same with the number of paths of step 3 as an argument: 4 (dcmt_sgm_dev itself, bit for bit and launch for launch) or 8 (the four
+ * diagonals as well: two more launches per chunk, one per orientation of the diagonals, between the columns and the winner).  The
+ * workspace (dcmt_sgm_workspace_bytes serves both), the chunking, every refusal and every guarantee are those of dcmt_sgm_dev;
+ * besides, DCMT_E_INVALID, nothing written: paths other than 4 or 8; paths == 8 with p2 > 1800. */
+int dcmt_sgm_paths_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right,
+                       int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
+                       const dcmt_sgm_params *params, int paths,
+                       void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
 /* HOST pointers, one pair, synchronous (row strides in BYTES: the images >= cols, disp16 >= 2 * cols, depth >= 4 * cols; the stride
  * of a NULL output is ignored).  The workspace of one frame is allocated for the call.  The same bits as the device call.  What
  * dcmt_shim::stereo_sgm calls. */
 int dcmt_sgm(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
              int rows, int cols, const dcmt_sgm_params *params,
              int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride);
+/* dcmt_sgm with the number of paths, 4 or 8, as dcmt_sgm_paths_dev takes it; dcmt_sgm is its paths = 4.  What
+ * dcmt_shim::stereo_sgm_paths calls. */
+int dcmt_sgm_paths(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
+                   int rows, int cols, const dcmt_sgm_params *params,
+                   int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride,
+                   int paths);
 
 /* ---- the speckle filter of a disparity map ------------------------------------------------------------- */
 

@@ -389,6 +389,23 @@ inline void stereo_sgm(const cv::Mat& left_gray, const cv::Mat& right_gray, cv::
     disp16 = out;
 }
 
+// stereo_sgm with the number of aggregation paths (dcmt_sgm_paths): 4 is stereo_sgm itself, 8 adds the four diagonals, as the full
+// mode of cv::StereoSGBM does; with 8 the library refuses p2 > 1800.  Anything else throws.
+inline void stereo_sgm_paths(const cv::Mat& left_gray, const cv::Mat& right_gray, cv::Mat& disp16, int paths, const dcmt_sgm_params* params = nullptr)
+{
+    const int rows = left_gray.rows, cols = left_gray.cols;
+    if (left_gray.empty() || left_gray.type() != CV_8UC1 || right_gray.type() != CV_8UC1 || right_gray.rows != rows || right_gray.cols != cols)
+        throw std::runtime_error("stereo_sgm_paths: the images must be CV_8UC1 of one size");
+    dcmt_sgm_params def;
+    dcmt_default_sgm_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_16SC1);
+    raise(dcmt_sgm_paths(thread_ctx().get(rows, cols), left_gray.ptr<unsigned char>(), left_gray.step[0], right_gray.ptr<unsigned char>(),
+                         right_gray.step[0], rows, cols, params ? params : &def, out.ptr<int16_t>(), out.step[0], nullptr, 0, paths),
+          "stereo_sgm_paths");
+    disp16 = out;
+}
+
 // cv::filterSpeckles(disp16, new_val, max_size, max_diff) for a CV_16SC1 disparity map, its argument order, in place, as dcmt.h
 // states it (dcmt_filter_speckles): what StereoSGBM runs on its output with ((minDisparity - 1) * 16, speckleWindowSize,
 // 16 * speckleRange) -- (-16, 200, 32) for the reference's matcher (main_sl.cpp:1301-1302).  Arguments the C call refuses throw.
