@@ -266,6 +266,33 @@ def _check_sgm_paths(paths, p: L.SgmParams) -> int:
     return int(paths)
 
 
+SGM_GUIDE_WEIGHT = 100              # the guide's penalty min(guide_weight * |d - h|, guide_cap) (include/dcmt.h, step 2b)
+SGM_GUIDE_CAP = 1000                # with the default p2 = 800 exactly the eight-path limit on p2 + guide_cap
+SGM_MAX_P2 = 10000
+SGM_MAX_GUIDE_WEIGHT = 10000
+
+
+def _check_sgm_guide(guide_weight, guide_cap, paths: int, p: L.SgmParams) -> tuple[int, int]:
+    """The guide_weight / guide_cap keywords of sgm_dev / sgm / stereo_sgm when a guide is given (without one they are not looked at).
+    Raises ValueError on what dcmt_sgm_guided_dev refuses of them and of the parameters, before any call."""
+    for name, v in (("guide_weight", guide_weight), ("guide_cap", guide_cap)):
+        if isinstance(v, bool) or int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise ValueError(f"{name} = {v!r} is not an int32")
+    w, cap = int(guide_weight), int(guide_cap)
+    if not 0 <= w <= SGM_MAX_GUIDE_WEIGHT:
+        raise ValueError(f"guide_weight = {w}: 0..{SGM_MAX_GUIDE_WEIGHT}")
+    if cap < 0:
+        raise ValueError(f"guide_cap = {cap}: >= 0")
+    limit = SGM_MAX_P2_EIGHT_PATHS if paths == 8 else SGM_MAX_P2
+    if p.p2 + cap > limit:
+        raise ValueError(f"p2 + guide_cap = {p.p2} + {cap} with paths = {paths}: <= {limit}")
+    for name in ("baseline", "focal"):                      # the hint needs them, with or without a depth plane
+        v = getattr(p, name)
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name} = {v!r}: finite and > 0 with a guide")
+    return w, cap
+
+
 def sgm_workspace_bytes(rows: int, cols: int, num_disparities: int = 64, frames: int = 1) -> int:
     """dcmt_sgm_workspace_bytes: the bytes of workspace that hold `frames` frames in flight (0 for sizes the call refuses)."""
     return int(L.lib().dcmt_sgm_workspace_bytes(rows, cols, num_disparities, frames))
@@ -822,7 +849,8 @@ class Context:
     # ---- dense stereo matching (dcmt_sgm*) --------------------------------------------------
     def sgm_dev(self, d_left, d_right, disp16: bool = True, depth: bool = False, d_disp16=None, d_depth=None, d_work=None,
                 frames_in_flight: int | None = None, stream: int | None = None, speckle_window: int | None = None,
-                speckle_range: int | None = None, paths: int = 4, **kw):
+                speckle_range: int | None = None, paths: int = 4, d_guide=None, guide_weight: int = SGM_GUIDE_WEIGHT,
+                guide_cap: int = SGM_GUIDE_CAP, **kw):
         """Semi-global stereo matching on the device (dcmt_sgm_dev, as include/dcmt.h states it; the reference's cv::StereoSGBM block,
         SL/main_sl.cpp:1293-1339): a rectified grey pair (uint8 CUDA tensors [batch][rows][cols], what bgr_convert_dev(gray=True) writes)
         -> the int16 disparity map in sixteenths of a pixel (-16: invalid) and / or the f32 depth plane stereo_refine_dev,
@@ -833,6 +861,11 @@ class Context:
         is allocated on the stream the call enqueues on.  kw: the fields of make_sgm_params.
         paths: 4 (dcmt_sgm_dev: the two horizontal and the two vertical paths) or 8 (dcmt_sgm_paths_dev: the four diagonals as well, two
         more launches a chunk; p2 <= 1800).  Anything else, or a larger p2 with 8, raises ValueError before any call.
+        d_guide: an f32 CUDA tensor of the images' shape, a depth plane in the left camera in metres with 0 where there is none (what
+        project_points_dev(nearest=True) writes, or a completed plane): dcmt_sgm_guided_dev, which adds min(guide_weight * |d - h|,
+        guide_cap) to the block cost of every pixel with a hint h = (int)(baseline * focal / z + 0.5) < D (include/dcmt.h, step 2b).
+        guide_weight in 0..10000, guide_cap >= 0 and p2 + guide_cap <= 10000 (1800 with 8 paths), baseline and focal finite and > 0, or
+        ValueError before any call; without a guide the two integers are not looked at.
         speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (whole disparities: max_diff = 16 *
         speckle_range; the reference's are 200 and 2).  With both None nothing changes and no further call is made; with a window > 0
         filter_speckles_dev is enqueued behind the matcher on the same stream, in place on both outputs."""
@@ -842,6 +875,9 @@ class Context:
         want_disp, want_depth = disp16 or d_disp16 is not None, depth or d_depth is not None
         p = make_sgm_params(for_depth=want_depth, **kw)
         paths = _check_sgm_paths(paths, p)
+        if d_guide is not None:
+            assert _is_dev(d_guide, torch.float32) and d_guide.shape == d_left.shape
+            guide_weight, guide_cap = _check_sgm_guide(guide_weight, guide_cap, paths, p)
         assert want_disp or want_depth
         speckle = _speckle_kw(speckle_window, speckle_range)
         asked_disp, want_disp = want_disp, want_disp or speckle is not None        # the filter works on the disparities
@@ -858,10 +894,13 @@ class Context:
         assert d_disp16 is None or (_is_dev(d_disp16, torch.int16) and d_disp16.numel() == b * r * c)
         assert d_depth is None or (_is_dev(d_depth, torch.float32) and d_depth.numel() == b * r * c)
         assert _is_dev(d_work)
-        args = (self._h, d_left.data_ptr(), d_right.data_ptr(), d_disp16.data_ptr() if want_disp else None,
-                d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p))
+        outs = (d_disp16.data_ptr() if want_disp else None, d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p))
+        args = (self._h, d_left.data_ptr(), d_right.data_ptr(), *outs)
         tail = (d_work.data_ptr(), d_work.numel() * d_work.element_size(), _stream(stream, d_left))
-        if paths == 4:
+        if d_guide is not None:
+            _check(L.lib().dcmt_sgm_guided_dev(self._h, d_left.data_ptr(), d_right.data_ptr(), d_guide.data_ptr(), *outs, paths, guide_weight,
+                                               guide_cap, *tail), "dcmt_sgm_guided_dev")
+        elif paths == 4:
             _check(L.lib().dcmt_sgm_dev(*args, *tail), "dcmt_sgm_dev")
         else:
             _check(L.lib().dcmt_sgm_paths_dev(*args, paths, *tail), "dcmt_sgm_paths_dev")
@@ -870,10 +909,12 @@ class Context:
         return (d_disp16, d_depth) if asked_disp and want_depth else d_disp16 if asked_disp else d_depth
 
     def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, speckle_window: int | None = None,
-            speckle_range: int | None = None, paths: int = 4, **kw):
+            speckle_range: int | None = None, paths: int = 4, guide=None, guide_weight: int = SGM_GUIDE_WEIGHT,
+            guide_cap: int = SGM_GUIDE_CAP, **kw):
         """One pair of host memory (dcmt_sgm, synchronous; any row stride): (int16 [rows][cols], f32 [rows][cols]), or the one that is
         wanted.  speckle_window, speckle_range: as sgm_dev; the filter is a second host call (dcmt_filter_speckles), in place.
-        paths: as sgm_dev (8: dcmt_sgm_paths)."""
+        paths: as sgm_dev (8: dcmt_sgm_paths).  guide, guide_weight, guide_cap: as sgm_dev's d_guide, an f32 [rows][cols] host plane of
+        any row stride (dcmt_sgm_guided)."""
         imgs = []
         for a in (left, right):
             a = np.asarray(a, dtype=np.uint8)
@@ -887,9 +928,17 @@ class Context:
         z = np.empty((rows, cols), dtype=np.float32) if depth else None
         p = make_sgm_params(for_depth=depth, **kw)
         paths = _check_sgm_paths(paths, p)
-        args = (self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0], rows, cols, ctypes.byref(p),
-                d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None, z.strides[0] if depth else 0)
-        if paths == 4:
+        pair = (self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0])
+        outs = (rows, cols, ctypes.byref(p), d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None,
+                z.strides[0] if depth else 0)
+        args = (*pair, *outs)
+        if guide is not None:
+            g = np.asarray(guide, dtype=np.float32)
+            assert g.shape == (rows, cols)
+            g = g if g.strides[1] == 4 else np.ascontiguousarray(g)
+            guide_weight, guide_cap = _check_sgm_guide(guide_weight, guide_cap, paths, p)
+            _check(L.lib().dcmt_sgm_guided(*pair, g.ctypes.data, g.strides[0], *outs, paths, guide_weight, guide_cap), "dcmt_sgm_guided")
+        elif paths == 4:
             _check(L.lib().dcmt_sgm(*args), "dcmt_sgm")
         else:
             _check(L.lib().dcmt_sgm_paths(*args, paths), "dcmt_sgm_paths")
@@ -1399,17 +1448,24 @@ def get_initial_error(depth, left, right, **params):
 
 
 def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = None, speckle_range: int | None = None, paths: int = 4,
-               **params):
+               guide=None, guide_weight: int = SGM_GUIDE_WEIGHT, guide_cap: int = SGM_GUIDE_CAP, **params):
     """Semi-global matching of one rectified host pair (dcmt_sgm): the int16 disparity map in sixteenths of a pixel, -16 where invalid,
     as cv::StereoSGBM::compute returns it (SL/main_sl.cpp:1293-1339); with depth=True (disp16, depth).  left, right: grey uint8
     [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params.
     speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (the reference's: 200, 2); None, None: no filter.
-    paths: 4, or 8 for the four diagonal paths as well (p2 <= 1800 then); ValueError otherwise, before any call."""
-    _check_sgm_paths(paths, make_sgm_params(for_depth=depth, **params))
+    paths: 4, or 8 for the four diagonal paths as well (p2 <= 1800 then); ValueError otherwise, before any call.
+    guide: an f32 depth plane [rows][cols] in the left camera, metres, 0 where there is none (project_points(..., nearest=True)):
+    LiDAR-guided matching (dcmt_sgm_guided; include/dcmt.h, step 2b) with the penalty min(guide_weight * |d - h|, guide_cap);
+    guide_weight in 0..10000, guide_cap >= 0, p2 + guide_cap <= 10000 (1800 with 8 paths), or ValueError before any call."""
+    p = make_sgm_params(for_depth=depth, **params)
+    paths = _check_sgm_paths(paths, p)
+    if guide is not None:
+        _check_sgm_guide(guide_weight, guide_cap, paths, p)
     imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
     imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
     return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, speckle_window=speckle_window,
-                                                                speckle_range=speckle_range, paths=paths, **params)
+                                                                speckle_range=speckle_range, paths=paths, guide=guide,
+                                                                guide_weight=guide_weight, guide_cap=guide_cap, **params)
 
 
 def filter_speckles(disp16, depth=None, **params):

@@ -5,6 +5,8 @@
 //                 absolute differences of one (x, d) is two v_sad_u8; the 5-column box runs along the row in registers.  C is written,
 //                 the left->right path is carried in registers and written as S; then the wave walks back over the C it has just
 //                 written (every lane reads what it wrote itself) and adds the right->left path into S.
+//   k_sgm_rows_guided  in its place with a guide (dcmt_sgm_guided_dev): the row's hints are staged beside the grey columns as int16,
+//                 and the capped penalty joins the block cost before the path and the store, so C holds C' for every later pass.
 //   k_sgm_cols    one wave per image column: down, then up, adding both paths into S.
 //   k_sgm_diag    with eight paths (dcmt_sgm_paths_dev), twice between k_sgm_cols and k_sgm_winner, once per orientation of the
 //                 diagonals: one wave per start column on a line that wraps around the frame's sides, down, then up.
@@ -190,6 +192,23 @@ __device__ __forceinline__ uint2 sgm_pack_column(const uint8_t* img, int rows, i
     return make_uint2(w[0] | (w[1] << 8) | (w[2] << 16) | (w[3] << 24), w[4]);
 }
 
+// The guide of dcmt_sgm_guided_dev as k_sgm_rows_guided takes it: the f32 depth planes [frames][rows][cols], read as their bits;
+// baseline * focal, rounded once (SgmK's); the two integers of the penalty.
+struct SgmGuide {
+    const uint32_t* plane;
+    float bf;
+    int weight, cap;
+};
+
+// Step 2b: the hint of a guide value with the bits zb, -1 where there is none.  z is finite and > 0 on its bits; bf is finite or +inf
+// and >= 0, so q is +0 .. +inf and t = q + 0.5f is 0.5 .. +inf, whose bits order as the numbers do: t < D is decided on them.
+__device__ __forceinline__ int sgm_hint(uint32_t zb, float bf, int D)
+{
+    if (!((int32_t)zb > 0 && zb < 0x7f800000u)) return -1;
+    const float t = __fadd_rn(__fdiv_rn(bf, __uint_as_float(zb)), 0.5f);
+    return __float_as_uint(t) < __float_as_uint((float)D) ? (int)t : -1;
+}
+
 // left, right: [frames][rows][cols]; vol: the chunk's workspace, per frame C then S ([rows][cols][D] uint16 each)
 template <int NPL, bool LDS>
 __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
@@ -249,6 +268,91 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows(const uint8_t* __re
             box[k] += in - v[k][0];
             v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
         }
+    }
+    // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
+    sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);
+}
+
+// k_sgm_rows with step 2b, a sibling so that k_sgm_rows keeps its instruction stream: the staging loop converts the guide row to hints
+// beside the grey columns, and C' = C + the penalty goes into the path and into the volume, so every later pass reads C'.  What differs
+// from k_sgm_rows is the guide's row, the hints, pen[] and cost[]; the rest is its text.
+template <int NPL, bool LDS>
+__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_guided(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                                    uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2, SgmGuide g)
+{
+    extern __shared__ uint2 sgm_lds[];                      // [cols] left, then [cols] right; then [cols] int16 hints (LDS route)
+    const int y = (int)blockIdx.x, lane = sgm_lane();
+    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
+    const uint8_t* L = left + frame * px;
+    const uint8_t* R = right + frame * px;
+    uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
+    uint16_t* S = C + ve;
+    const uint32_t* G = g.plane + frame * px + (size_t)y * (size_t)cols;     // the guide's row y
+    int16_t* hints = reinterpret_cast<int16_t*>(sgm_lds + 2 * (size_t)cols);
+    if constexpr (LDS) {
+        for (int x = lane; x < cols; x += 64) {
+            sgm_lds[x] = sgm_pack_column(L, rows, cols, y, x);
+            sgm_lds[cols + x] = sgm_pack_column(R, rows, cols, y, x);
+            hints[x] = (int16_t)sgm_hint(G[x], g.bf, D);      // one division a pixel
+        }
+        __syncthreads();
+    }
+    bool have[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
+    // V(x, d): the sum over the five rows of |left(., x) - right(., max(x - d, 0))|
+    const auto column_sad = [&](int x, int d) -> int {
+        const int xr = max(x - d, 0);
+        uint2 l, r;
+        if constexpr (LDS) { l = sgm_lds[x]; r = sgm_lds[cols + xr]; }
+        else { l = sgm_pack_column(L, rows, cols, y, x); r = sgm_pack_column(R, rows, cols, y, xr); }
+        return (int)__builtin_amdgcn_sad_u8(l.x, r.x, __builtin_amdgcn_sad_u8(l.y, r.y, 0u));
+    };
+    // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
+    int v[NPL][5], box[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int d = lane + 64 * k;
+        const int v0 = column_sad(0, d), v1 = column_sad(min(1, cols - 1), d), v2 = column_sad(min(2, cols - 1), d);
+        v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
+        box[k] = 3 * v0 + v1 + v2;
+    }
+    // pen[k] is the penalty of column x, min(weight |d - h|, cap) or 0 without a hint.  The hint is the same in every lane (an
+    // LDS broadcast, or a wave-uniform address on the global route) and the penalty hangs on x and the lane alone, so it is made one
+    // column ahead, beside the box, off the chain of path steps.  The hint goes to a scalar register, where "no hint" becomes a
+    // weight of 0; weight <= 10000 and |d - h| <= 127 fit the 24-bit multiply.
+    int pen[NPL];
+    const auto penalties = [&](int x) {
+        const int h = __builtin_amdgcn_readfirstlane(LDS ? (int)hints[x] : sgm_hint(G[x], g.bf, D));
+        const int weight = h >= 0 ? g.weight : 0;
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) pen[k] = min(__mul24(weight, abs(lane + 64 * k - h)), g.cap);
+    };
+    penalties(0);
+    SgmPath<NPL> path;
+    for (int x = 0; x < cols; ++x) {
+        int cost[NPL], c[NPL];                                  // C' of this column
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            cost[k] = box[k] + pen[k];
+            c[k] = have[k] ? cost[k] : kSgmAbsent;
+        }
+        if (x == 0) path.start(c); else path.step(c, p1, p2);
+#pragma unroll
+        for (int k = 0; k < NPL; ++k)
+            if (have[k]) {
+                const size_t at = (size_t)x * (size_t)D + (size_t)(lane + 64 * k);
+                C[at] = (uint16_t)cost[k];
+                S[at] = (uint16_t)path.prev[k];
+            }
+        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const int in = x + 3 <= cols - 1 ? column_sad(x + 3, lane + 64 * k) : v[k][4];
+            box[k] += in - v[k][0];
+            v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
+        }
+        if (x + 1 < cols) penalties(x + 1);
     }
     // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
     sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);

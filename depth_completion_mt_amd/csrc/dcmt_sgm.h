@@ -1,6 +1,6 @@
-// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its plan, and the plan
-// itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev, the workspace layout, the chunking of the batch
-// and the launch shapes.
+// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_rows_guided, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its
+// plan, and the plan itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev / dcmt_sgm_guided_dev, the
+// workspace layout, the chunking of the batch and the launch shapes.
 // Plain C++, no HIP: the plan is tested on a CPU (tests/plan_sgm_test.cpp).
 #ifndef DCMT_SGM_H
 #define DCMT_SGM_H
@@ -15,11 +15,13 @@ namespace dcmt {
 constexpr int kSgmMinDisp = 16, kSgmMaxDisp = 128;      // D: a multiple of 16 in this range; D > 64: two disparities a lane
 constexpr int kSgmMaxP2 = 10000;                        // S <= 4 * (6375 + p2) <= 65500 fits uint16
 constexpr int kSgmMaxP2Eight = 1800;                    // eight paths: S <= 8 * (6375 + p2) <= 65400
+constexpr int kSgmMaxGuideWeight = 10000;               // with a guide: 0 <= guide_weight <= this, and p2 + guide_cap <= the limit on p2
 constexpr int kSgmRowThreads = 64;                      // k_sgm_rows: one wave = one row, lane = disparity
 constexpr int kSgmWaves = 4;                            // k_sgm_cols, k_sgm_diag, k_sgm_winner: waves per workgroup
 constexpr int kSgmSegment = 64;                         // k_sgm_winner: pixels of a row per wave, one result a lane
 constexpr size_t kSgmLdsBudget = 64 * 1024;             // k_sgm_rows stages 16 bytes a column: up to 4096 columns, wider rows from global memory
 constexpr uint32_t kSgmLdsPerCol = 16;                  // rows y-2..y+2 of one column, left (8 bytes: 4 + 1 used) and right (8 bytes)
+constexpr uint32_t kSgmLdsPerColGuided = 18;            // k_sgm_rows_guided: the column's hint as well, an int16 behind the images: up to 3640 columns
 
 namespace plan {
 
@@ -48,6 +50,8 @@ struct SgmPlan {
     unsigned segments;               // ceil(cols / kSgmSegment)
     int paths;                       // 4, or 8: k_sgm_diag runs twice between k_sgm_cols and k_sgm_winner, once per orientation
     unsigned diag_grid_x;            // k_sgm_diag: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a start column; 0 with 4 paths
+    bool guided;                     // a guide was given: k_sgm_rows_guided in place of k_sgm_rows, kSgmLdsPerColGuided bytes a column
+    int guide_weight, guide_cap;     // its penalty min(guide_weight * |d - h|, guide_cap); 0, 0 without a guide
 };
 
 // frames of chunk i
@@ -57,22 +61,27 @@ inline int sgm_chunk_frames(const SgmPlan& p, int batch, int i)
     return (int)(first + p.chunk <= batch ? p.chunk : batch - first);
 }
 
-// rows, cols, batch >= 1 and within the context's limits; paths: 4 (dcmt_sgm_dev) or 8 (the four diagonals as well)
+// rows, cols, batch >= 1 and within the context's limits; paths: 4 (dcmt_sgm_dev) or 8 (the four diagonals as well); guide: the f32
+// depth plane of dcmt_sgm_guided_dev or 0, without which guide_weight and guide_cap are not looked at
 inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, int p2, int uniqueness, uintptr_t left, uintptr_t right,
-                        uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes, int paths = 4)
+                        uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes, int paths = 4, uintptr_t guide = 0,
+                        int guide_weight = 0, int guide_cap = 0)
 {
     SgmPlan p = {};
     p.status = kInvalid;
     if (!left || !right || (!disp16 && !depth) || !work || !sgm_disparities_ok(disparities) || !sgm_paths_ok(paths)) return p;
     if (p1 < 0 || p1 > p2 || p2 > sgm_max_p2(paths) || uniqueness < 0 || uniqueness > 100) return p;
     if (disp16 % 2 != 0 || depth % 4 != 0 || work % 16 != 0) return p;
+    if (guide && (guide % 4 != 0 || guide_weight < 0 || guide_weight > kSgmMaxGuideWeight || guide_cap < 0 ||
+                  (long long)p2 + (long long)guide_cap > (long long)sgm_max_p2(paths)))
+        return p;
     p.frame_bytes = sgm_frame_bytes(rows, cols, disparities);
     if (work_bytes < p.frame_bytes) return p;
     const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
-    const uintptr_t at[5] = {left, right, disp16, depth, work};
-    const size_t bytes[5] = {px, px, 2 * px, 4 * px, work_bytes};
-    for (int i = 0; i < 5; ++i)
-        for (int j = (i < 2 ? 2 : i + 1); j < 5; ++j)         // the two inputs may be one image; every other pair is apart
+    const uintptr_t at[6] = {left, right, guide, disp16, depth, work};
+    const size_t bytes[6] = {px, px, 4 * px, 2 * px, 4 * px, work_bytes};
+    for (int i = 0; i < 6; ++i)
+        for (int j = (i < 3 ? 3 : i + 1); j < 6; ++j)         // the inputs may share memory; every other pair is apart
             if (at[i] && at[j] && ranges_overlap(at[i], bytes[i], at[j], bytes[j])) return p;
     p.status = kOk;
     p.volume_elems = p.frame_bytes / 4;
@@ -81,7 +90,10 @@ inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, 
     if (p.chunk > 65535) p.chunk = 65535;
     p.n_chunks = (batch + p.chunk - 1) / p.chunk;
     p.per_lane = disparities > 64 ? 2 : 1;
-    const size_t lds = (size_t)kSgmLdsPerCol * (size_t)cols;
+    p.guided = guide != 0;
+    p.guide_weight = p.guided ? guide_weight : 0;
+    p.guide_cap = p.guided ? guide_cap : 0;
+    const size_t lds = (size_t)(p.guided ? kSgmLdsPerColGuided : kSgmLdsPerCol) * (size_t)cols;
     p.lds_route = lds <= kSgmLdsBudget;
     p.lds = p.lds_route ? lds : 0;
     p.rows_grid_x = (unsigned)rows;

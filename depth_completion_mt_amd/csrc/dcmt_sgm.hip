@@ -1,7 +1,8 @@
 // dcmt_sgm.hip -- semi-global stereo matching (dcmt_kernels_sgm.h), a code object of its own: dcmt_default_sgm_params,
-// dcmt_sgm_workspace_bytes, dcmt_sgm_dev and dcmt_sgm_paths_dev (of which dcmt_sgm_dev is the four-path case).  The plan (dcmt_sgm.h:
-// plan_sgm) checks the arguments, lays the caller's workspace out and cuts the batch into chunks; this file launches what it says.
-// The single-pair host forms, dcmt_sgm and dcmt_sgm_paths, are in dcmt_host.hip.
+// dcmt_sgm_workspace_bytes, dcmt_sgm_dev, dcmt_sgm_paths_dev and dcmt_sgm_guided_dev (of which dcmt_sgm_paths_dev is the case without a
+// guide, and dcmt_sgm_dev the four-path case of that).  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's
+// workspace out and cuts the batch into chunks; this file launches what it says.
+// The single-pair host forms, dcmt_sgm, dcmt_sgm_paths and dcmt_sgm_guided, are in dcmt_host.hip.
 #include <initializer_list>
 
 #include "dcmt.h"
@@ -12,12 +13,19 @@
 using namespace dcmt;
 
 template <int NPL>
-static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_t* right, int16_t* disp16, float* depth, uint16_t* vol, int rows,
-                      int cols, int frames, const dcmt_sgm_params& P, hipStream_t st)
+static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_t* right, const float* guide, int16_t* disp16, float* depth,
+                      uint16_t* vol, int rows, int cols, int frames, const dcmt_sgm_params& P, hipStream_t st)
 {
     const int D = P.num_disparities;
+    const float bf = P.baseline * P.focal;                  // rounded once: the hint's and step 9's
     const dim3 rows_grid(pl.rows_grid_x, (unsigned)frames), cols_grid(pl.cols_grid_x, (unsigned)frames), winner_grid(pl.winner_grid_x, (unsigned)frames);
-    if (pl.lds_route)
+    if (pl.guided) {
+        const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};
+        if (pl.lds_route)
+            hipLaunchKernelGGL((k_sgm_rows_guided<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
+        else
+            hipLaunchKernelGGL((k_sgm_rows_guided<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
+    } else if (pl.lds_route)
         hipLaunchKernelGGL((k_sgm_rows<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2);
     else
         hipLaunchKernelGGL((k_sgm_rows<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2);
@@ -27,7 +35,7 @@ static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_
         hipLaunchKernelGGL((k_sgm_diag<NPL, +1>), diag_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
         hipLaunchKernelGGL((k_sgm_diag<NPL, -1>), diag_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
     }
-    const SgmK K = {D, P.uniqueness, P.disp12_max_diff, P.baseline * P.focal, P.max_depth};
+    const SgmK K = {D, P.uniqueness, P.disp12_max_diff, bf, P.max_depth};
     hipLaunchKernelGGL((k_sgm_winner<NPL>), winner_grid, dim3(64 * kSgmWaves), 0, st, (const uint16_t*)vol, disp16, depth, rows, cols, pl.segments, K);
 }
 
@@ -52,16 +60,21 @@ size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int fra
     return (size_t)frames * plan::sgm_frame_bytes(rows, cols, num_disparities);
 }
 
-int dcmt_sgm_paths_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
-                       const dcmt_sgm_params* params, int paths, void* d_work, size_t work_bytes, void* stream)
+int dcmt_sgm_guided_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, const float* d_guide, int16_t* d_disp16, float* d_depth, int rows,
+                        int cols, int batch, const dcmt_sgm_params* params, int paths, int guide_weight, int guide_cap, void* d_work, size_t work_bytes,
+                        void* stream)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
     if (d_depth)
         for (const float v : {params->baseline, params->focal, params->max_depth})
             if (!finite_bits(v) || !(v > 0.0f)) return DCMT_E_INVALID;
+    if (d_guide)                                            // the hint needs them, with or without a depth plane
+        for (const float v : {params->baseline, params->focal})
+            if (!finite_bits(v) || !(v > 0.0f)) return DCMT_E_INVALID;
     const plan::SgmPlan pl = plan::plan_sgm(rows, cols, batch, params->num_disparities, params->p1, params->p2, params->uniqueness, (uintptr_t)d_left,
-                                            (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes, paths);
+                                            (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes, paths,
+                                            (uintptr_t)d_guide, guide_weight, guide_cap);
     if (pl.status != plan::kOk) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t px = (size_t)rows * (size_t)cols;
@@ -70,11 +83,18 @@ int dcmt_sgm_paths_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_ri
         const int frames = plan::sgm_chunk_frames(pl, batch, i);
         int16_t* disp = d_disp16 ? d_disp16 + first : nullptr;
         float* depth = d_depth ? d_depth + first : nullptr;
-        if (pl.per_lane == 1) sgm_chunk<1>(pl, d_left + first, d_right + first, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
-        else sgm_chunk<2>(pl, d_left + first, d_right + first, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
+        const float* guide = d_guide ? d_guide + first : nullptr;
+        if (pl.per_lane == 1) sgm_chunk<1>(pl, d_left + first, d_right + first, guide, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
+        else sgm_chunk<2>(pl, d_left + first, d_right + first, guide, disp, depth, (uint16_t*)d_work, rows, cols, frames, *params, st);
     }
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+int dcmt_sgm_paths_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,
+                       const dcmt_sgm_params* params, int paths, void* d_work, size_t work_bytes, void* stream)
+{
+    return dcmt_sgm_guided_dev(ctx, d_left, d_right, nullptr, d_disp16, d_depth, rows, cols, batch, params, paths, 0, 0, d_work, work_bytes, stream);
 }
 
 int dcmt_sgm_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,

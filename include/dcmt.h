@@ -877,6 +877,18 @@ int dcmt_photo_error(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
  *   1. pixel cost  AD(y,x,d) = |left(y,x) - right(y, max(x - d, 0))|.
  *   2. block cost  C(y,x,d) = sum over dy, dx in -2..2 of AD(clamp(y+dy, 0, rows-1), clamp(x+dx, 0, cols-1), d): the clamp replicates the
  *      AD plane, not the images.  C <= 25 * 255 = 6375.
+ *   2b. guide, only with dcmt_sgm_guided_dev and a d_guide: an f32 depth plane [rows][cols] in the left camera, in metres, 0 where there is
+ *      none -- what dcmt_project_points_nearest_dev writes, or a completed plane, in which every pixel is hinted.  With bf = baseline *
+ *      focal, one rounded f32 product (step 9's), pixel (y,x) HAS A HINT iff the bits of z = guide(y,x) are those of a finite number > 0
+ *      (decided on the bits, as dcmt_photo_error_dev decides), and t = q + 0.5f with q = bf / z, one rounded f32 quotient and one rounded
+ *      f32 sum, satisfies t < (float)D.  The hint is h = (int)t, 0 <= h <= D-1.  NaN, +-inf, negatives, -0.0 and a z so small that q
+ *      overflows or lands beyond the range give no hint; a very large z gives h = 0, which is a hint.  At a hinted pixel
+ *        C'(y,x,d) = C(y,x,d) + min(guide_weight * |d - h|, guide_cap),
+ *      elsewhere C' = C; steps 3..9 read C' wherever they read C, and the cost volume in the workspace holds C'.  The term is
+ *      additive, integer and capped: C' <= 6375 + guide_cap, C' <= L_r <= C' + p2 and S <= paths * (6375 + p2 + guide_cap), so with a
+ *      guide the limit on p2 (10000, with eight paths 1800) bounds p2 + guide_cap.  The bound is attained: a comb image with a hint of 0
+ *      on every pixel reaches S = 65500 with four paths (p1 = p2 = guide_cap = 5000) and 65400 with eight (900).  guide_weight = 0 or
+ *      guide_cap = 0 is the unguided matcher bit for bit, in both volumes.
  *   3. paths, four directions r (left->right, right->left, top->bottom, bottom->top).  On the first pixel of a path L_r = C; otherwise,
  *      with m = min over k of L_r(p-r, k):
  *        L_r(p,d) = C(p,d) + min(L_r(p-r,d), L_r(p-r,d-1) + p1, L_r(p-r,d+1) + p1, m + p2) - m,
@@ -934,6 +946,19 @@ int dcmt_sgm_paths_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_ri
                        int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
                        const dcmt_sgm_params *params, int paths,
                        void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
+/* The same with a guide (step 2b): d_guide f32 [batch][rows][cols], or NULL.  With d_guide == NULL this IS dcmt_sgm_paths_dev -- the
+ * same launches of the same kernels, guide_weight and guide_cap not looked at -- and dcmt_sgm_paths_dev is that case of this entry
+ * point.  With a guide the rows kernel is its guided variant, which converts each guide row once (one division a pixel); every
+ * other kernel, the workspace (dcmt_sgm_workspace_bytes serves all three entry points), the chunking and every guarantee are
+ * unchanged.  The defaults of the Python interface are guide_weight = 100 and guide_cap = 1000: with p2 = 800 exactly the eight-path
+ * limit.  Besides the refusals of dcmt_sgm_paths_dev, DCMT_E_INVALID, nothing written, when a guide is given: d_guide not 4-byte
+ * aligned; guide_weight outside 0..10000; guide_cap < 0; p2 + guide_cap > 10000 (with eight paths 1800); a baseline or focal that
+ * is not finite and > 0, also when d_depth is NULL (max_depth is still tested only with d_depth); any overlap of the guide with an
+ * output or the workspace (it may share memory with the images). */
+int dcmt_sgm_guided_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right, const float *d_guide /* or NULL */,
+                        int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
+                        const dcmt_sgm_params *params, int paths, int guide_weight, int guide_cap,
+                        void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
 /* HOST pointers, one pair, synchronous (row strides in BYTES: the images >= cols, disp16 >= 2 * cols, depth >= 4 * cols; the stride
  * of a NULL output is ignored).  The workspace of one frame is allocated for the call.  The same bits as the device call.  What
  * dcmt_shim::stereo_sgm calls. */
@@ -946,6 +971,12 @@ int dcmt_sgm_paths(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, c
                    int rows, int cols, const dcmt_sgm_params *params,
                    int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride,
                    int paths);
+/* dcmt_sgm_paths with a guide, as dcmt_sgm_guided_dev takes it: guide f32 [rows][cols] with a row stride in BYTES >= 4 * cols, or NULL
+ * (its stride is then ignored: dcmt_sgm_paths, which is that case).  What dcmt_shim::stereo_sgm_guided calls. */
+int dcmt_sgm_guided(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
+                    const float *guide /* or NULL */, size_t guide_row_stride, int rows, int cols, const dcmt_sgm_params *params,
+                    int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride,
+                    int paths, int guide_weight, int guide_cap);
 
 /* ---- the speckle filter of a disparity map ------------------------------------------------------------- */
 

@@ -406,6 +406,29 @@ inline void stereo_sgm_paths(const cv::Mat& left_gray, const cv::Mat& right_gray
     disp16 = out;
 }
 
+// stereo_sgm_paths with a LiDAR guide (dcmt_sgm_guided): guide is CV_32FC1 of the images' size, the depth in the left camera in metres,
+// 0 where there is none (project_points_nearest's plane, or a completed one).  A pixel whose depth gives a disparity h inside the
+// range has min(guide_weight * |d - h|, guide_cap) added to its matching cost; the library refuses guide_weight outside 0..10000,
+// guide_cap < 0 and p2 + guide_cap > 10000 (1800 with 8 paths).  Its Python defaults are 100 and 1000.  Anything refused throws.
+inline void stereo_sgm_guided(const cv::Mat& left_gray, const cv::Mat& right_gray, const cv::Mat& guide, cv::Mat& disp16, int paths,
+                              int guide_weight, int guide_cap, const dcmt_sgm_params* params = nullptr)
+{
+    const int rows = left_gray.rows, cols = left_gray.cols;
+    if (left_gray.empty() || left_gray.type() != CV_8UC1 || right_gray.type() != CV_8UC1 || right_gray.rows != rows || right_gray.cols != cols)
+        throw std::runtime_error("stereo_sgm_guided: the images must be CV_8UC1 of one size");
+    if (guide.type() != CV_32FC1 || guide.rows != rows || guide.cols != cols)
+        throw std::runtime_error("stereo_sgm_guided: the guide must be CV_32FC1 of the images' size");
+    dcmt_sgm_params def;
+    dcmt_default_sgm_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_16SC1);
+    raise(dcmt_sgm_guided(thread_ctx().get(rows, cols), left_gray.ptr<unsigned char>(), left_gray.step[0], right_gray.ptr<unsigned char>(),
+                          right_gray.step[0], guide.ptr<float>(), guide.step[0], rows, cols, params ? params : &def, out.ptr<int16_t>(),
+                          out.step[0], nullptr, 0, paths, guide_weight, guide_cap),
+          "stereo_sgm_guided");
+    disp16 = out;
+}
+
 // cv::filterSpeckles(disp16, new_val, max_size, max_diff) for a CV_16SC1 disparity map, its argument order, in place, as dcmt.h
 // states it (dcmt_filter_speckles): what StereoSGBM runs on its output with ((minDisparity - 1) * 16, speckleWindowSize,
 // 16 * speckleRange) -- (-16, 200, 32) for the reference's matcher (main_sl.cpp:1301-1302).  Arguments the C call refuses throw.
