@@ -45,7 +45,7 @@ EXPORTS = (
     "dcmt_slic_contours_dev", "dcmt_slic_cluster_means_dev", "dcmt_slic_contours", "dcmt_slic_cluster_means",
     "dcmt_default_photo_error_params", "dcmt_photo_error_dev", "dcmt_photo_error_calib_dev", "dcmt_photo_error",
     "dcmt_default_sgm_params", "dcmt_sgm_workspace_bytes", "dcmt_sgm_dev", "dcmt_sgm", "dcmt_sgm_paths_dev", "dcmt_sgm_paths",
-    "dcmt_sgm_guided_dev", "dcmt_sgm_guided",
+    "dcmt_sgm_guided_dev", "dcmt_sgm_guided", "dcmt_sgm_cost_dev", "dcmt_sgm_cost",
     "dcmt_default_speckle_params", "dcmt_filter_speckles_dev", "dcmt_filter_speckles",
 )
 
@@ -259,6 +259,8 @@ def lib() -> ctypes.CDLL:
         L.dcmt_sgm_paths.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, i]
         L.dcmt_sgm_guided_dev.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, i, i, i, vp, sz, vp]
         L.dcmt_sgm_guided.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, i, i, i]
+        L.dcmt_sgm_cost_dev.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, i, i, i, i, vp, sz, vp]
+        L.dcmt_sgm_cost.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp, sz, vp, sz, i, i, i, i]
         L.dcmt_default_speckle_params.argtypes = [vp]
         L.dcmt_default_speckle_params.restype = None
         L.dcmt_filter_speckles_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp]

@@ -293,6 +293,16 @@ def _check_sgm_guide(guide_weight, guide_cap, paths: int, p: L.SgmParams) -> tup
     return w, cap
 
 
+SGM_COSTS = {"absdiff": 0, "census": 1}     # DCMT_SGM_COST_ABSDIFF, DCMT_SGM_COST_CENSUS (include/dcmt.h, steps 1 / 2 and 1c / 2c)
+
+
+def _check_sgm_cost(cost) -> int:
+    """The cost keyword of sgm_dev / sgm / stereo_sgm: "absdiff" or "census", or ValueError before any call."""
+    if not isinstance(cost, str) or cost not in SGM_COSTS:
+        raise ValueError(f"cost = {cost!r}: one of {sorted(SGM_COSTS)}")
+    return SGM_COSTS[cost]
+
+
 def sgm_workspace_bytes(rows: int, cols: int, num_disparities: int = 64, frames: int = 1) -> int:
     """dcmt_sgm_workspace_bytes: the bytes of workspace that hold `frames` frames in flight (0 for sizes the call refuses)."""
     return int(L.lib().dcmt_sgm_workspace_bytes(rows, cols, num_disparities, frames))
@@ -850,7 +860,7 @@ class Context:
     def sgm_dev(self, d_left, d_right, disp16: bool = True, depth: bool = False, d_disp16=None, d_depth=None, d_work=None,
                 frames_in_flight: int | None = None, stream: int | None = None, speckle_window: int | None = None,
                 speckle_range: int | None = None, paths: int = 4, d_guide=None, guide_weight: int = SGM_GUIDE_WEIGHT,
-                guide_cap: int = SGM_GUIDE_CAP, **kw):
+                guide_cap: int = SGM_GUIDE_CAP, cost: str = "absdiff", **kw):
         """Semi-global stereo matching on the device (dcmt_sgm_dev, as include/dcmt.h states it; the reference's cv::StereoSGBM block,
         SL/main_sl.cpp:1293-1339): a rectified grey pair (uint8 CUDA tensors [batch][rows][cols], what bgr_convert_dev(gray=True) writes)
         -> the int16 disparity map in sixteenths of a pixel (-16: invalid) and / or the f32 depth plane stereo_refine_dev,
@@ -866,6 +876,10 @@ class Context:
         guide_cap) to the block cost of every pixel with a hint h = (int)(baseline * focal / z + 0.5) < D (include/dcmt.h, step 2b).
         guide_weight in 0..10000, guide_cap >= 0 and p2 + guide_cap <= 10000 (1800 with 8 paths), baseline and focal finite and > 0, or
         ValueError before any call; without a guide the two integers are not looked at.
+        cost: "absdiff" (the calls above, as they were) or "census" (dcmt_sgm_cost_dev with DCMT_SGM_COST_CENSUS: 24-bit census codes
+        and 10 * the Hamming distance over the block, steps 1c / 2c of include/dcmt.h, which a difference in exposure or gain between
+        the two cameras does not disturb; with or without a guide, with either path count).  Anything else raises ValueError before
+        any call.
         speckle_window, speckle_range: StereoSGBM's speckleWindowSize and speckleRange (whole disparities: max_diff = 16 *
         speckle_range; the reference's are 200 and 2).  With both None nothing changes and no further call is made; with a window > 0
         filter_speckles_dev is enqueued behind the matcher on the same stream, in place on both outputs."""
@@ -875,6 +889,7 @@ class Context:
         want_disp, want_depth = disp16 or d_disp16 is not None, depth or d_depth is not None
         p = make_sgm_params(for_depth=want_depth, **kw)
         paths = _check_sgm_paths(paths, p)
+        cost = _check_sgm_cost(cost)
         if d_guide is not None:
             assert _is_dev(d_guide, torch.float32) and d_guide.shape == d_left.shape
             guide_weight, guide_cap = _check_sgm_guide(guide_weight, guide_cap, paths, p)
@@ -897,7 +912,11 @@ class Context:
         outs = (d_disp16.data_ptr() if want_disp else None, d_depth.data_ptr() if want_depth else None, r, c, b, ctypes.byref(p))
         args = (self._h, d_left.data_ptr(), d_right.data_ptr(), *outs)
         tail = (d_work.data_ptr(), d_work.numel() * d_work.element_size(), _stream(stream, d_left))
-        if d_guide is not None:
+        if cost != 0:
+            guided = d_guide is not None
+            _check(L.lib().dcmt_sgm_cost_dev(self._h, d_left.data_ptr(), d_right.data_ptr(), d_guide.data_ptr() if guided else None, *outs, paths,
+                                             guide_weight if guided else 0, guide_cap if guided else 0, cost, *tail), "dcmt_sgm_cost_dev")
+        elif d_guide is not None:
             _check(L.lib().dcmt_sgm_guided_dev(self._h, d_left.data_ptr(), d_right.data_ptr(), d_guide.data_ptr(), *outs, paths, guide_weight,
                                                guide_cap, *tail), "dcmt_sgm_guided_dev")
         elif paths == 4:
@@ -910,11 +929,11 @@ class Context:
 
     def sgm(self, left: np.ndarray, right: np.ndarray, disp16: bool = True, depth: bool = False, speckle_window: int | None = None,
             speckle_range: int | None = None, paths: int = 4, guide=None, guide_weight: int = SGM_GUIDE_WEIGHT,
-            guide_cap: int = SGM_GUIDE_CAP, **kw):
+            guide_cap: int = SGM_GUIDE_CAP, cost: str = "absdiff", **kw):
         """One pair of host memory (dcmt_sgm, synchronous; any row stride): (int16 [rows][cols], f32 [rows][cols]), or the one that is
         wanted.  speckle_window, speckle_range: as sgm_dev; the filter is a second host call (dcmt_filter_speckles), in place.
         paths: as sgm_dev (8: dcmt_sgm_paths).  guide, guide_weight, guide_cap: as sgm_dev's d_guide, an f32 [rows][cols] host plane of
-        any row stride (dcmt_sgm_guided)."""
+        any row stride (dcmt_sgm_guided).  cost: as sgm_dev ("census": dcmt_sgm_cost)."""
         imgs = []
         for a in (left, right):
             a = np.asarray(a, dtype=np.uint8)
@@ -928,6 +947,7 @@ class Context:
         z = np.empty((rows, cols), dtype=np.float32) if depth else None
         p = make_sgm_params(for_depth=depth, **kw)
         paths = _check_sgm_paths(paths, p)
+        cost = _check_sgm_cost(cost)
         pair = (self._h, imgs[0].ctypes.data, imgs[0].strides[0], imgs[1].ctypes.data, imgs[1].strides[0])
         outs = (rows, cols, ctypes.byref(p), d.ctypes.data if disp16 else None, d.strides[0] if disp16 else 0, z.ctypes.data if depth else None,
                 z.strides[0] if depth else 0)
@@ -937,6 +957,10 @@ class Context:
             assert g.shape == (rows, cols)
             g = g if g.strides[1] == 4 else np.ascontiguousarray(g)
             guide_weight, guide_cap = _check_sgm_guide(guide_weight, guide_cap, paths, p)
+        if cost != 0:
+            plane = (g.ctypes.data, g.strides[0], *outs, paths, guide_weight, guide_cap) if guide is not None else (None, 0, *outs, paths, 0, 0)
+            _check(L.lib().dcmt_sgm_cost(*pair, *plane, cost), "dcmt_sgm_cost")
+        elif guide is not None:
             _check(L.lib().dcmt_sgm_guided(*pair, g.ctypes.data, g.strides[0], *outs, paths, guide_weight, guide_cap), "dcmt_sgm_guided")
         elif paths == 4:
             _check(L.lib().dcmt_sgm(*args), "dcmt_sgm")
@@ -1448,7 +1472,7 @@ def get_initial_error(depth, left, right, **params):
 
 
 def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = None, speckle_range: int | None = None, paths: int = 4,
-               guide=None, guide_weight: int = SGM_GUIDE_WEIGHT, guide_cap: int = SGM_GUIDE_CAP, **params):
+               guide=None, guide_weight: int = SGM_GUIDE_WEIGHT, guide_cap: int = SGM_GUIDE_CAP, cost: str = "absdiff", **params):
     """Semi-global matching of one rectified host pair (dcmt_sgm): the int16 disparity map in sixteenths of a pixel, -16 where invalid,
     as cv::StereoSGBM::compute returns it (SL/main_sl.cpp:1293-1339); with depth=True (disp16, depth).  left, right: grey uint8
     [rows][cols], or BGR uint8 [rows][cols][3], which go through bgr_to_gray.  params: the fields of make_sgm_params.
@@ -1456,16 +1480,19 @@ def stereo_sgm(left, right, depth: bool = False, speckle_window: int | None = No
     paths: 4, or 8 for the four diagonal paths as well (p2 <= 1800 then); ValueError otherwise, before any call.
     guide: an f32 depth plane [rows][cols] in the left camera, metres, 0 where there is none (project_points(..., nearest=True)):
     LiDAR-guided matching (dcmt_sgm_guided; include/dcmt.h, step 2b) with the penalty min(guide_weight * |d - h|, guide_cap);
-    guide_weight in 0..10000, guide_cap >= 0, p2 + guide_cap <= 10000 (1800 with 8 paths), or ValueError before any call."""
+    guide_weight in 0..10000, guide_cap >= 0, p2 + guide_cap <= 10000 (1800 with 8 paths), or ValueError before any call.
+    cost: "absdiff", or "census" for the census matching cost (dcmt_sgm_cost; include/dcmt.h, steps 1c / 2c), which differences in
+    exposure and gain between the two images do not disturb; ValueError otherwise, before any call."""
     p = make_sgm_params(for_depth=depth, **params)
     paths = _check_sgm_paths(paths, p)
+    _check_sgm_cost(cost)
     if guide is not None:
         _check_sgm_guide(guide_weight, guide_cap, paths, p)
     imgs = [np.asarray(a, dtype=np.uint8) for a in (left, right)]
     imgs = [bgr_to_gray(a) if a.ndim == 3 else a for a in imgs]
     return _ctx_for(imgs[0].shape[0], imgs[0].shape[1], 1).sgm(imgs[0], imgs[1], depth=depth, speckle_window=speckle_window,
                                                                 speckle_range=speckle_range, paths=paths, guide=guide,
-                                                                guide_weight=guide_weight, guide_cap=guide_cap, **params)
+                                                                guide_weight=guide_weight, guide_cap=guide_cap, cost=cost, **params)
 
 
 def filter_speckles(disp16, depth=None, **params):

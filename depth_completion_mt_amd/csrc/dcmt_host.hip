@@ -192,12 +192,13 @@ int dcmt_photo_error(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_
     return rc == DCMT_OK ? fetch(ctx, {&e, &s}) : rc;
 }
 
-int dcmt_sgm_guided(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, const float* guide, size_t grs, int rows, int cols,
-                    const dcmt_sgm_params* params, int16_t* disp16, size_t drs, float* depth, size_t zrs, int paths, int guide_weight, int guide_cap)
+int dcmt_sgm_cost(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, const float* guide, size_t grs, int rows, int cols,
+                  const dcmt_sgm_params* params, int16_t* disp16, size_t drs, float* depth, size_t zrs, int paths, int guide_weight, int guide_cap, int cost)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !left || !right || (!disp16 && !depth) || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
     if (paths != 4 && paths != 8) return DCMT_E_INVALID;    // before anything is allocated or staged
+    if (cost != DCMT_SGM_COST_ABSDIFF && cost != DCMT_SGM_COST_CENSUS) return DCMT_E_INVALID;
     const size_t work_bytes = dcmt_sgm_workspace_bytes(rows, cols, params->num_disparities, 1);
     if (!work_bytes) return DCMT_E_INVALID;
     Plane l(left, lrs, cols, rows), r(right, rrs, cols, rows), g(guide, grs, sizeof(float) * (size_t)cols, rows);     // a null guide: no plane
@@ -209,9 +210,16 @@ int dcmt_sgm_guided(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_
     DCMT_HIP(ctx, hipMalloc(&work.dev, work_bytes));        // before stage(): nothing of the call is in the stream if it fails
     int rc = stage(ctx, {&l, &r, &g}, {&d, &z});
     if (rc == DCMT_OK)
-        rc = dcmt_sgm_guided_dev(ctx, (const uint8_t*)l.dev, (const uint8_t*)r.dev, (const float*)g.dev, (int16_t*)d.dev, (float*)z.dev, rows, cols, 1, params,
-                                 paths, guide_weight, guide_cap, work.dev, work_bytes, ctx->own_stream);
+        rc = dcmt_sgm_cost_dev(ctx, (const uint8_t*)l.dev, (const uint8_t*)r.dev, (const float*)g.dev, (int16_t*)d.dev, (float*)z.dev, rows, cols, 1, params,
+                               paths, guide_weight, guide_cap, cost, work.dev, work_bytes, ctx->own_stream);
     return rc == DCMT_OK ? fetch(ctx, {&d, &z}) : rc;
+}
+
+int dcmt_sgm_guided(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, const float* guide, size_t grs, int rows, int cols,
+                    const dcmt_sgm_params* params, int16_t* disp16, size_t drs, float* depth, size_t zrs, int paths, int guide_weight, int guide_cap)
+{
+    return dcmt_sgm_cost(ctx, left, lrs, right, rrs, guide, grs, rows, cols, params, disp16, drs, depth, zrs, paths, guide_weight, guide_cap,
+                         DCMT_SGM_COST_ABSDIFF);
 }
 
 int dcmt_sgm_paths(dcmt_ctx* ctx, const uint8_t* left, size_t lrs, const uint8_t* right, size_t rrs, int rows, int cols, const dcmt_sgm_params* params,

@@ -7,6 +7,10 @@
 //                 written (every lane reads what it wrote itself) and adds the right->left path into S.
 //   k_sgm_rows_guided  in its place with a guide (dcmt_sgm_guided_dev): the row's hints are staged beside the grey columns as int16,
 //                 and the capped penalty joins the block cost before the path and the store, so C holds C' for every later pass.
+//   k_sgm_rows_census  in the place of either with the census cost (dcmt_sgm_cost_dev, DCMT_SGM_COST_CENSUS): the staging loop makes the
+//                 24-bit census codes of rows y-2..y+2 of the right image from its grey rows y-4..y+4, five codes of a column in one
+//                 uint4 in LDS; the left image's stay in registers, 64 columns at a time; the column sum of Hamming distances of one
+//                 (x, d) is four v_xor and four v_bcnt; 10 * the box is the block cost.
 //   k_sgm_cols    one wave per image column: down, then up, adding both paths into S.
 //   k_sgm_diag    with eight paths (dcmt_sgm_paths_dev), twice between k_sgm_cols and k_sgm_winner, once per orientation of the
 //                 diagonals: one wave per start column on a line that wraps around the frame's sides, down, then up.
@@ -353,6 +357,160 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_guided(const uint8_
             v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
         }
         if (x + 1 < cols) penalties(x + 1);
+    }
+    // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
+    sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);
+}
+
+// Step 1c for one column of an image: the census codes of rows clamp(y-2) .. clamp(y+2) of column x, 24 bits each, in one uint4
+// (code i in bits 24 i .. 24 i + 23 of the 128; codes straddle dwords, which is free: only the popcount of the XOR of two such
+// words is ever taken).  w[j][c] is the grey value at (clamp(y - 4 + j), clamp(x - 2 + c)); for a row y - 2 + i inside the frame the
+// window of its code is w[i..i+4][.].  A row beyond the frame is the nearest row inside -- the clamp of step 2c replicates the H
+// plane -- so its code is that row's code, not the code of the window around it.
+__device__ __forceinline__ uint4 sgm_census_column(const uint8_t* img, int rows, int cols, int y, int x)
+{
+    int xs[5], w[9][5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) xs[c] = min(max(x - 2 + c, 0), cols - 1);
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const uint8_t* row = img + (size_t)min(max(y - 4 + j, 0), rows - 1) * (size_t)cols;
+#pragma unroll
+        for (int c = 0; c < 5; ++c) w[j][c] = row[xs[c]];
+    }
+    uint32_t code[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int centre = w[i + 2][2];
+        uint32_t k = 0;
+#pragma unroll
+        for (int n = 0; n < 25; ++n)
+            if (n != 12) k |= (uint32_t)(w[i + n / 5][n % 5] < centre) << (n < 12 ? n : n - 1);       // strict: equal is 0
+        code[i] = k;
+    }
+    code[1] = y - 1 >= 0 ? code[1] : code[2];
+    code[0] = y - 2 >= 0 ? code[0] : code[1];
+    code[3] = y + 1 <= rows - 1 ? code[3] : code[2];
+    code[4] = y + 2 <= rows - 1 ? code[4] : code[3];
+    const uint64_t lo = (uint64_t)code[0] | (uint64_t)code[1] << 24 | (uint64_t)code[2] << 48;            // code 2's upper byte: in hi
+    const uint64_t hi = (uint64_t)(code[2] >> 16) | (uint64_t)code[3] << 8 | (uint64_t)code[4] << 32;
+    return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
+// k_sgm_rows / k_sgm_rows_guided with the census cost (steps 1c and 2c; dcmt_sgm_cost_dev with DCMT_SGM_COST_CENSUS), a sibling so that
+// both keep their instruction streams.  The staging loop makes the codes of rows y-2..y+2 of the RIGHT image from its grey rows
+// y-4..y+4 and keeps them in LDS, one uint4 a column: 16 bytes a column (18 with the guide's hint), what k_sgm_rows stages, so as
+// many workgroups share a CU -- the chain of path steps is bound by latency, and with both images' codes in LDS (32 bytes a column,
+// half the workgroups) this kernel took 1.7 times as long.  The LEFT column of a step is the same in every lane, so its codes stay
+// in registers: the wave holds those of 64 columns at a time, a column a lane, reads column x's with four v_readlane and makes the
+// next 64 when the walk reaches them.  The column sum of the five Hamming distances of one (x, d) is four v_xor and four
+// accumulating v_bcnt; 10 * the box goes into the path and into C.  GUIDED: step 2b as in k_sgm_rows_guided, the int16 hints behind
+// the codes.  The box, the path, the stores and the walk back are k_sgm_rows' text.
+template <int NPL, bool LDS, bool GUIDED>
+__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                                    uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2, SgmGuide g)
+{
+    extern __shared__ uint4 sgm_lds_census[];               // [cols] the right image's codes; then [cols] int16 hints (GUIDED, LDS route)
+    const int y = (int)blockIdx.x, lane = sgm_lane();
+    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
+    const uint8_t* L = left + frame * px;
+    const uint8_t* R = right + frame * px;
+    uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
+    uint16_t* S = C + ve;
+    const uint32_t* G = GUIDED ? g.plane + frame * px + (size_t)y * (size_t)cols : nullptr;      // the guide's row y
+    int16_t* hints = reinterpret_cast<int16_t*>(sgm_lds_census + (size_t)cols);
+    if constexpr (LDS) {
+        for (int x = lane; x < cols; x += 64) {
+            sgm_lds_census[x] = sgm_census_column(R, rows, cols, y, x);
+            if constexpr (GUIDED) hints[x] = (int16_t)sgm_hint(G[x], g.bf, D);
+        }
+        __syncthreads();
+    }
+    // the left image's codes of columns 64 j .. 64 j + 63, lane i those of column 64 j + i (the last column again beyond the row's end,
+    // which is never asked for); column x of the window is read from lane x & 63, x the same in every lane
+    uint4 window = sgm_census_column(L, rows, cols, y, min(lane, cols - 1));
+    const auto left_codes = [&](int x) -> uint4 {
+        const int at = x & 63;
+        return make_uint4((uint32_t)__builtin_amdgcn_readlane((int)window.x, at), (uint32_t)__builtin_amdgcn_readlane((int)window.y, at),
+                          (uint32_t)__builtin_amdgcn_readlane((int)window.z, at), (uint32_t)__builtin_amdgcn_readlane((int)window.w, at));
+    };
+    bool have[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
+    // V(x, d): the sum over the five rows of popcount(K_left(., x) ^ K_right(., max(x - d, 0))), 0..120, in two halves: the codes are
+    // asked for, and their distance is taken when it is needed, a path step later
+    const auto codes_of = [&](int x, int d, uint4& l, uint4& r) {
+        const int xr = max(x - d, 0);
+        l = left_codes(x);
+        if constexpr (LDS) r = sgm_lds_census[xr]; else r = sgm_census_column(R, rows, cols, y, xr);
+    };
+    const auto hamming = [](const uint4& l, const uint4& r) -> int {
+        return __builtin_popcount(l.x ^ r.x) + __builtin_popcount(l.y ^ r.y) + __builtin_popcount(l.z ^ r.z) + __builtin_popcount(l.w ^ r.w);
+    };
+    const auto column_hamming = [&](int x, int d) -> int {
+        uint4 l, r;
+        codes_of(x, d, l, r);
+        return hamming(l, r);
+    };
+    // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
+    int v[NPL][5], box[NPL];
+#pragma unroll
+    for (int k = 0; k < NPL; ++k) {
+        const int d = lane + 64 * k;
+        const int v0 = column_hamming(0, d), v1 = column_hamming(min(1, cols - 1), d), v2 = column_hamming(min(2, cols - 1), d);
+        v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
+        box[k] = 3 * v0 + v1 + v2;
+    }
+    // the penalty of a column from its hint, as in k_sgm_rows_guided; the hint is read one column ahead
+    int pen[NPL];
+    const auto hint_of = [&](int x) -> int { return LDS ? (int)hints[x] : sgm_hint(G[x], g.bf, D); };
+    const auto penalties = [&](int hint) {
+        if constexpr (GUIDED) {
+            const int h = __builtin_amdgcn_readfirstlane(hint);
+            const int weight = h >= 0 ? g.weight : 0;
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) pen[k] = min(__mul24(weight, abs(lane + 64 * k - h)), g.cap);
+        } else {
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) pen[k] = 0;
+        }
+    };
+    penalties(GUIDED ? hint_of(0) : -1);
+    SgmPath<NPL> path;
+    for (int x = 0; x < cols; ++x) {
+        // the codes of column x + 3 and the hint of column x + 1 are asked for here and used behind the path step, which hides their
+        // way from LDS; column x + 3 may be the first of the next 64 of the left image
+        uint4 nl[NPL], nr[NPL];
+        const bool more = x + 3 <= cols - 1;
+        if (more) {
+            if (((x + 3) & 63) == 0) window = sgm_census_column(L, rows, cols, y, min(x + 3 + lane, cols - 1));
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) codes_of(x + 3, lane + 64 * k, nl[k], nr[k]);
+        }
+        int next_hint = -1;
+        if constexpr (GUIDED) { if (x + 1 < cols) next_hint = hint_of(x + 1); }
+        int cost[NPL], c[NPL];                                  // C (C' with a guide) of this column: 10 * the box <= 6000
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            cost[k] = 10 * box[k] + pen[k];
+            c[k] = have[k] ? cost[k] : kSgmAbsent;
+        }
+        if (x == 0) path.start(c); else path.step(c, p1, p2);
+#pragma unroll
+        for (int k = 0; k < NPL; ++k)
+            if (have[k]) {
+                const size_t at = (size_t)x * (size_t)D + (size_t)(lane + 64 * k);
+                C[at] = (uint16_t)cost[k];
+                S[at] = (uint16_t)path.prev[k];
+            }
+        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
+#pragma unroll
+        for (int k = 0; k < NPL; ++k) {
+            const int in = more ? hamming(nl[k], nr[k]) : v[k][4];
+            box[k] += in - v[k][0];
+            v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
+        }
+        if (x + 1 < cols) penalties(next_hint);
     }
     // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
     sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);

@@ -1,5 +1,5 @@
-// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_rows_guided, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its
-// plan, and the plan itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev / dcmt_sgm_guided_dev, the
+// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_rows_guided, k_sgm_rows_census, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its
+// plan, and the plan itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev / dcmt_sgm_guided_dev / dcmt_sgm_cost_dev, the
 // workspace layout, the chunking of the batch and the launch shapes.
 // Plain C++, no HIP: the plan is tested on a CPU (tests/plan_sgm_test.cpp).
 #ifndef DCMT_SGM_H
@@ -22,6 +22,10 @@ constexpr int kSgmSegment = 64;                         // k_sgm_winner: pixels 
 constexpr size_t kSgmLdsBudget = 64 * 1024;             // k_sgm_rows stages 16 bytes a column: up to 4096 columns, wider rows from global memory
 constexpr uint32_t kSgmLdsPerCol = 16;                  // rows y-2..y+2 of one column, left (8 bytes: 4 + 1 used) and right (8 bytes)
 constexpr uint32_t kSgmLdsPerColGuided = 18;            // k_sgm_rows_guided: the column's hint as well, an int16 behind the images: up to 3640 columns
+constexpr int kSgmCostAbsdiff = 0, kSgmCostCensus = 1;  // DCMT_SGM_COST_*: the pixel cost of steps 1 / 2, or of steps 1c / 2c
+constexpr uint32_t kSgmLdsPerColCensus = 16;            // k_sgm_rows_census: the five 24-bit codes of one column of the right image in a uint4 (the left
+                                                        // image's stay in registers): up to 4096 columns, as many workgroups a CU as k_sgm_rows
+constexpr uint32_t kSgmLdsPerColCensusGuided = 18;      // and the column's int16 hint behind them: up to 3640 columns
 
 namespace plan {
 
@@ -52,7 +56,15 @@ struct SgmPlan {
     unsigned diag_grid_x;            // k_sgm_diag: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a start column; 0 with 4 paths
     bool guided;                     // a guide was given: k_sgm_rows_guided in place of k_sgm_rows, kSgmLdsPerColGuided bytes a column
     int guide_weight, guide_cap;     // its penalty min(guide_weight * |d - h|, guide_cap); 0, 0 without a guide
+    int cost;                        // kSgmCostAbsdiff, or kSgmCostCensus: k_sgm_rows_census in place of either rows kernel, kSgmLdsPerColCensus(Guided) bytes a column
 };
+
+// the LDS bytes a column of the rows kernel of (cost, guided)
+inline uint32_t sgm_lds_per_col(int cost, bool guided)
+{
+    if (cost == kSgmCostCensus) return guided ? kSgmLdsPerColCensusGuided : kSgmLdsPerColCensus;
+    return guided ? kSgmLdsPerColGuided : kSgmLdsPerCol;
+}
 
 // frames of chunk i
 inline int sgm_chunk_frames(const SgmPlan& p, int batch, int i)
@@ -62,14 +74,16 @@ inline int sgm_chunk_frames(const SgmPlan& p, int batch, int i)
 }
 
 // rows, cols, batch >= 1 and within the context's limits; paths: 4 (dcmt_sgm_dev) or 8 (the four diagonals as well); guide: the f32
-// depth plane of dcmt_sgm_guided_dev or 0, without which guide_weight and guide_cap are not looked at
+// depth plane of dcmt_sgm_guided_dev or 0, without which guide_weight and guide_cap are not looked at; cost: dcmt_sgm_cost_dev's, with
+// kSgmCostAbsdiff every field is what it was before there was a choice
 inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, int p2, int uniqueness, uintptr_t left, uintptr_t right,
                         uintptr_t disp16, uintptr_t depth, uintptr_t work, size_t work_bytes, int paths = 4, uintptr_t guide = 0,
-                        int guide_weight = 0, int guide_cap = 0)
+                        int guide_weight = 0, int guide_cap = 0, int cost = kSgmCostAbsdiff)
 {
     SgmPlan p = {};
     p.status = kInvalid;
     if (!left || !right || (!disp16 && !depth) || !work || !sgm_disparities_ok(disparities) || !sgm_paths_ok(paths)) return p;
+    if (cost != kSgmCostAbsdiff && cost != kSgmCostCensus) return p;
     if (p1 < 0 || p1 > p2 || p2 > sgm_max_p2(paths) || uniqueness < 0 || uniqueness > 100) return p;
     if (disp16 % 2 != 0 || depth % 4 != 0 || work % 16 != 0) return p;
     if (guide && (guide % 4 != 0 || guide_weight < 0 || guide_weight > kSgmMaxGuideWeight || guide_cap < 0 ||
@@ -93,7 +107,8 @@ inline SgmPlan plan_sgm(int rows, int cols, int batch, int disparities, int p1, 
     p.guided = guide != 0;
     p.guide_weight = p.guided ? guide_weight : 0;
     p.guide_cap = p.guided ? guide_cap : 0;
-    const size_t lds = (size_t)(p.guided ? kSgmLdsPerColGuided : kSgmLdsPerCol) * (size_t)cols;
+    p.cost = cost;
+    const size_t lds = (size_t)sgm_lds_per_col(cost, p.guided) * (size_t)cols;
     p.lds_route = lds <= kSgmLdsBudget;
     p.lds = p.lds_route ? lds : 0;
     p.rows_grid_x = (unsigned)rows;

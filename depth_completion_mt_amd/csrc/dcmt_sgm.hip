@@ -1,8 +1,8 @@
 // dcmt_sgm.hip -- semi-global stereo matching (dcmt_kernels_sgm.h), a code object of its own: dcmt_default_sgm_params,
-// dcmt_sgm_workspace_bytes, dcmt_sgm_dev, dcmt_sgm_paths_dev and dcmt_sgm_guided_dev (of which dcmt_sgm_paths_dev is the case without a
-// guide, and dcmt_sgm_dev the four-path case of that).  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's
+// dcmt_sgm_workspace_bytes, dcmt_sgm_dev, dcmt_sgm_paths_dev, dcmt_sgm_guided_dev and dcmt_sgm_cost_dev (of which dcmt_sgm_guided_dev is the
+// absolute-difference case, dcmt_sgm_paths_dev the case of that without a guide, and dcmt_sgm_dev the four-path case of that).  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's
 // workspace out and cuts the batch into chunks; this file launches what it says.
-// The single-pair host forms, dcmt_sgm, dcmt_sgm_paths and dcmt_sgm_guided, are in dcmt_host.hip.
+// The single-pair host forms, dcmt_sgm, dcmt_sgm_paths, dcmt_sgm_guided and dcmt_sgm_cost, are in dcmt_host.hip.
 #include <initializer_list>
 
 #include "dcmt.h"
@@ -19,7 +19,14 @@ static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_
     const int D = P.num_disparities;
     const float bf = P.baseline * P.focal;                  // rounded once: the hint's and step 9's
     const dim3 rows_grid(pl.rows_grid_x, (unsigned)frames), cols_grid(pl.cols_grid_x, (unsigned)frames), winner_grid(pl.winner_grid_x, (unsigned)frames);
-    if (pl.guided) {
+    if (pl.cost == kSgmCostCensus) {                        // one sibling for both: the guide is a template parameter of it
+        const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};
+        const auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
+        };
+        if (pl.guided) { if (pl.lds_route) launch(k_sgm_rows_census<NPL, true, true>); else launch(k_sgm_rows_census<NPL, false, true>); }
+        else { if (pl.lds_route) launch(k_sgm_rows_census<NPL, true, false>); else launch(k_sgm_rows_census<NPL, false, false>); }
+    } else if (pl.guided) {
         const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};
         if (pl.lds_route)
             hipLaunchKernelGGL((k_sgm_rows_guided<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
@@ -60,9 +67,9 @@ size_t dcmt_sgm_workspace_bytes(int rows, int cols, int num_disparities, int fra
     return (size_t)frames * plan::sgm_frame_bytes(rows, cols, num_disparities);
 }
 
-int dcmt_sgm_guided_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, const float* d_guide, int16_t* d_disp16, float* d_depth, int rows,
-                        int cols, int batch, const dcmt_sgm_params* params, int paths, int guide_weight, int guide_cap, void* d_work, size_t work_bytes,
-                        void* stream)
+int dcmt_sgm_cost_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, const float* d_guide, int16_t* d_disp16, float* d_depth, int rows,
+                      int cols, int batch, const dcmt_sgm_params* params, int paths, int guide_weight, int guide_cap, int cost, void* d_work,
+                      size_t work_bytes, void* stream)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
@@ -74,7 +81,7 @@ int dcmt_sgm_guided_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_r
             if (!finite_bits(v) || !(v > 0.0f)) return DCMT_E_INVALID;
     const plan::SgmPlan pl = plan::plan_sgm(rows, cols, batch, params->num_disparities, params->p1, params->p2, params->uniqueness, (uintptr_t)d_left,
                                             (uintptr_t)d_right, (uintptr_t)d_disp16, (uintptr_t)d_depth, (uintptr_t)d_work, work_bytes, paths,
-                                            (uintptr_t)d_guide, guide_weight, guide_cap);
+                                            (uintptr_t)d_guide, guide_weight, guide_cap, cost);
     if (pl.status != plan::kOk) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const size_t px = (size_t)rows * (size_t)cols;
@@ -89,6 +96,14 @@ int dcmt_sgm_guided_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_r
     }
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+int dcmt_sgm_guided_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, const float* d_guide, int16_t* d_disp16, float* d_depth, int rows,
+                        int cols, int batch, const dcmt_sgm_params* params, int paths, int guide_weight, int guide_cap, void* d_work, size_t work_bytes,
+                        void* stream)
+{
+    return dcmt_sgm_cost_dev(ctx, d_left, d_right, d_guide, d_disp16, d_depth, rows, cols, batch, params, paths, guide_weight, guide_cap,
+                             DCMT_SGM_COST_ABSDIFF, d_work, work_bytes, stream);
 }
 
 int dcmt_sgm_paths_dev(dcmt_ctx* ctx, const uint8_t* d_left, const uint8_t* d_right, int16_t* d_disp16, float* d_depth, int rows, int cols, int batch,

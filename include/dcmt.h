@@ -877,6 +877,19 @@ int dcmt_photo_error(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride,
  *   1. pixel cost  AD(y,x,d) = |left(y,x) - right(y, max(x - d, 0))|.
  *   2. block cost  C(y,x,d) = sum over dy, dx in -2..2 of AD(clamp(y+dy, 0, rows-1), clamp(x+dx, 0, cols-1), d): the clamp replicates the
  *      AD plane, not the images.  C <= 25 * 255 = 6375.
+ *   1c, 2c. the census cost, only with dcmt_sgm_cost_dev and cost == DCMT_SGM_COST_CENSUS, in place of steps 1 and 2 (two cameras of a rig
+ *      never share exposure, gain and vignetting; a census code depends only on the order of the grey values around a pixel):
+ *      1c. codes: each image I gets a 24-bit code per pixel, K_I(y,x), one bit per (dy,dx) in -2..2 x -2..2 without the centre, set iff
+ *          I(clamp(y+dy, 0, rows-1), clamp(x+dx, 0, cols-1)) < I(y,x): the comparison is strict (equal is 0) and the clamp replicates
+ *          the image.  Only the popcount of an XOR of two codes is ever used, so the order of the bits is the implementation's own.
+ *          pixel cost  H(y,x,d) = popcount(K_left(y,x) ^ K_right(y, max(x - d, 0))), 0..24.
+ *      2c. block cost  C(y,x,d) = 10 * sum over dy, dx in -2..2 of H(clamp(y+dy, 0, rows-1), clamp(x+dx, 0, cols-1), d): this clamp
+ *          replicates the H plane, exactly as step 2 replicates the AD plane.  C <= 10 * 25 * 24 = 6000.
+ *      The factor 10 is part of the definition, not a tunable: it puts C on the scale of the absolute-difference cost (on uniform
+ *      noise the largest C is about 4500 with census and about 4000 with absolute differences), so p1, p2, guide_weight and guide_cap
+ *      keep their meaning and their defaults.  Since 6000 <= 6375 every bound of this statement holds as written with either cost:
+ *      S <= paths * (6375 + p2 + guide_cap), the limits 10000 and 1800 on p2 (+ guide_cap), and uint16 volumes.  Steps 2b and 3..9
+ *      read C as before.
  *   2b. guide, only with dcmt_sgm_guided_dev and a d_guide: an f32 depth plane [rows][cols] in the left camera, in metres, 0 where there is
  *      none -- what dcmt_project_points_nearest_dev writes, or a completed plane, in which every pixel is hinted.  With bf = baseline *
  *      focal, one rounded f32 product (step 9's), pixel (y,x) HAS A HINT iff the bits of z = guide(y,x) are those of a finite number > 0
@@ -959,6 +972,18 @@ int dcmt_sgm_guided_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_r
                         int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
                         const dcmt_sgm_params *params, int paths, int guide_weight, int guide_cap,
                         void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
+/* The same with the pixel cost as an argument: DCMT_SGM_COST_ABSDIFF (steps 1 and 2: dcmt_sgm_guided_dev itself, which is that case of
+ * this entry point -- the same launches of the same kernels) or DCMT_SGM_COST_CENSUS (steps 1c and 2c).  With census the rows kernel is
+ * its census variant, with or without a guide, which makes the codes of the rows it needs while it stages them (16 bytes of LDS a column,
+ * 18 with a guide, as with absolute differences); every other kernel, the workspace (dcmt_sgm_workspace_bytes serves all four entry points: census needs nothing
+ * beyond C and S), the chunking, every refusal and every guarantee are those of dcmt_sgm_guided_dev.  Besides, DCMT_E_INVALID,
+ * nothing written: a cost other than these two. */
+#define DCMT_SGM_COST_ABSDIFF 0
+#define DCMT_SGM_COST_CENSUS 1
+int dcmt_sgm_cost_dev(dcmt_ctx *ctx, const uint8_t *d_left, const uint8_t *d_right, const float *d_guide /* or NULL */,
+                      int16_t *d_disp16 /* or NULL */, float *d_depth /* or NULL */, int rows, int cols, int batch,
+                      const dcmt_sgm_params *params, int paths, int guide_weight, int guide_cap, int cost,
+                      void *d_work /* 16-byte aligned */, size_t work_bytes, void *stream);
 /* HOST pointers, one pair, synchronous (row strides in BYTES: the images >= cols, disp16 >= 2 * cols, depth >= 4 * cols; the stride
  * of a NULL output is ignored).  The workspace of one frame is allocated for the call.  The same bits as the device call.  What
  * dcmt_shim::stereo_sgm calls. */
@@ -977,6 +1002,12 @@ int dcmt_sgm_guided(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, 
                     const float *guide /* or NULL */, size_t guide_row_stride, int rows, int cols, const dcmt_sgm_params *params,
                     int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride,
                     int paths, int guide_weight, int guide_cap);
+/* dcmt_sgm_guided with the pixel cost, as dcmt_sgm_cost_dev takes it; dcmt_sgm_guided is its DCMT_SGM_COST_ABSDIFF.  What
+ * dcmt_shim::stereo_sgm_cost calls. */
+int dcmt_sgm_cost(dcmt_ctx *ctx, const uint8_t *left, size_t left_row_stride, const uint8_t *right, size_t right_row_stride,
+                  const float *guide /* or NULL */, size_t guide_row_stride, int rows, int cols, const dcmt_sgm_params *params,
+                  int16_t *disp16 /* or NULL */, size_t disp16_row_stride, float *depth /* or NULL */, size_t depth_row_stride,
+                  int paths, int guide_weight, int guide_cap, int cost);
 
 /* ---- the speckle filter of a disparity map ------------------------------------------------------------- */
 

@@ -429,6 +429,30 @@ inline void stereo_sgm_guided(const cv::Mat& left_gray, const cv::Mat& right_gra
     disp16 = out;
 }
 
+// stereo_sgm_guided with the matching cost (dcmt_sgm_cost): DCMT_SGM_COST_ABSDIFF is stereo_sgm_guided itself, DCMT_SGM_COST_CENSUS
+// matches on 24-bit census codes (10 * the Hamming distance over the 5 x 5 block), which a difference in exposure, gain or vignetting
+// between the two cameras does not disturb.  guide: as above, or an empty cv::Mat for none (guide_weight and guide_cap are then not
+// looked at).  A cost other than the two throws, as does everything stereo_sgm_guided refuses.
+inline void stereo_sgm_cost(const cv::Mat& left_gray, const cv::Mat& right_gray, const cv::Mat& guide, cv::Mat& disp16, int paths,
+                            int guide_weight, int guide_cap, int cost, const dcmt_sgm_params* params = nullptr)
+{
+    const int rows = left_gray.rows, cols = left_gray.cols;
+    if (left_gray.empty() || left_gray.type() != CV_8UC1 || right_gray.type() != CV_8UC1 || right_gray.rows != rows || right_gray.cols != cols)
+        throw std::runtime_error("stereo_sgm_cost: the images must be CV_8UC1 of one size");
+    const bool guided = !guide.empty();
+    if (guided && (guide.type() != CV_32FC1 || guide.rows != rows || guide.cols != cols))
+        throw std::runtime_error("stereo_sgm_cost: the guide must be CV_32FC1 of the images' size, or empty");
+    dcmt_sgm_params def;
+    dcmt_default_sgm_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_16SC1);
+    raise(dcmt_sgm_cost(thread_ctx().get(rows, cols), left_gray.ptr<unsigned char>(), left_gray.step[0], right_gray.ptr<unsigned char>(),
+                        right_gray.step[0], guided ? guide.ptr<float>() : nullptr, guided ? guide.step[0] : 0, rows, cols, params ? params : &def,
+                        out.ptr<int16_t>(), out.step[0], nullptr, 0, paths, guide_weight, guide_cap, cost),
+          "stereo_sgm_cost");
+    disp16 = out;
+}
+
 // cv::filterSpeckles(disp16, new_val, max_size, max_diff) for a CV_16SC1 disparity map, its argument order, in place, as dcmt.h
 // states it (dcmt_filter_speckles): what StereoSGBM runs on its output with ((minDisparity - 1) * 16, speckleWindowSize,
 // 16 * speckleRange) -- (-16, 200, 32) for the reference's matcher (main_sl.cpp:1301-1302).  Arguments the C call refuses throw.
