@@ -5,10 +5,10 @@
 //                 absolute differences of one (x, d) is two v_sad_u8; the 5-column box runs along the row in registers.  C is written,
 //                 the left->right path is carried in registers and written as S; then the wave walks back over the C it has just
 //                 written (every lane reads what it wrote itself) and adds the right->left path into S.
-//   k_sgm_rows_guided  in its place with a guide (dcmt_sgm_guided_dev): the row's hints are staged beside the grey columns as int16,
-//                 and the capped penalty joins the block cost before the path and the store, so C holds C' for every later pass.
-//   k_sgm_rows_census  in the place of either with the census cost (dcmt_sgm_cost_dev, DCMT_SGM_COST_CENSUS): the staging loop makes the
-//                 24-bit census codes of rows y-2..y+2 of the right image from its grey rows y-4..y+4, five codes of a column in one
+//                 Template parameters choose the variant, <NPL, LDS, GUIDED, COST>.  GUIDED (dcmt_sgm_guided_dev): the row's hints are
+//                 staged behind the columns as int16, and the capped penalty joins the block cost before the path and the store, so C
+//                 holds C' for every later pass.  COST = kSgmCostCensus (dcmt_sgm_cost_dev, DCMT_SGM_COST_CENSUS): the staging loop makes
+//                 the 24-bit census codes of rows y-2..y+2 of the right image from its grey rows y-4..y+4, five codes of a column in one
 //                 uint4 in LDS; the left image's stay in registers, 64 columns at a time; the column sum of Hamming distances of one
 //                 (x, d) is four v_xor and four v_bcnt; 10 * the box is the block cost.
 //   k_sgm_cols    one wave per image column: down, then up, adding both paths into S.
@@ -196,7 +196,7 @@ __device__ __forceinline__ uint2 sgm_pack_column(const uint8_t* img, int rows, i
     return make_uint2(w[0] | (w[1] << 8) | (w[2] << 16) | (w[3] << 24), w[4]);
 }
 
-// The guide of dcmt_sgm_guided_dev as k_sgm_rows_guided takes it: the f32 depth planes [frames][rows][cols], read as their bits;
+// The guide of dcmt_sgm_guided_dev as k_sgm_rows takes it (all zero without one): the f32 depth planes [frames][rows][cols], read as their bits;
 // baseline * focal, rounded once (SgmK's); the two integers of the penalty.
 struct SgmGuide {
     const uint32_t* plane;
@@ -211,155 +211,6 @@ __device__ __forceinline__ int sgm_hint(uint32_t zb, float bf, int D)
     if (!((int32_t)zb > 0 && zb < 0x7f800000u)) return -1;
     const float t = __fadd_rn(__fdiv_rn(bf, __uint_as_float(zb)), 0.5f);
     return __float_as_uint(t) < __float_as_uint((float)D) ? (int)t : -1;
-}
-
-// left, right: [frames][rows][cols]; vol: the chunk's workspace, per frame C then S ([rows][cols][D] uint16 each)
-template <int NPL, bool LDS>
-__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                                                             uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2)
-{
-    extern __shared__ uint2 sgm_lds[];                      // [cols] left, then [cols] right
-    const int y = (int)blockIdx.x, lane = sgm_lane();
-    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
-    const uint8_t* L = left + frame * px;
-    const uint8_t* R = right + frame * px;
-    uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
-    uint16_t* S = C + ve;
-    if constexpr (LDS) {
-        for (int x = lane; x < cols; x += 64) {
-            sgm_lds[x] = sgm_pack_column(L, rows, cols, y, x);
-            sgm_lds[cols + x] = sgm_pack_column(R, rows, cols, y, x);
-        }
-        __syncthreads();
-    }
-    bool have[NPL];
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
-    // V(x, d): the sum over the five rows of |left(., x) - right(., max(x - d, 0))|
-    const auto column_sad = [&](int x, int d) -> int {
-        const int xr = max(x - d, 0);
-        uint2 l, r;
-        if constexpr (LDS) { l = sgm_lds[x]; r = sgm_lds[cols + xr]; }
-        else { l = sgm_pack_column(L, rows, cols, y, x); r = sgm_pack_column(R, rows, cols, y, xr); }
-        return (int)__builtin_amdgcn_sad_u8(l.x, r.x, __builtin_amdgcn_sad_u8(l.y, r.y, 0u));
-    };
-    // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
-    int v[NPL][5], box[NPL];
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-        const int d = lane + 64 * k;
-        const int v0 = column_sad(0, d), v1 = column_sad(min(1, cols - 1), d), v2 = column_sad(min(2, cols - 1), d);
-        v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
-        box[k] = 3 * v0 + v1 + v2;
-    }
-    SgmPath<NPL> path;
-    for (int x = 0; x < cols; ++x) {
-        int c[NPL];
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) c[k] = have[k] ? box[k] : kSgmAbsent;
-        if (x == 0) path.start(c); else path.step(c, p1, p2);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k)
-            if (have[k]) {
-                const size_t at = (size_t)x * (size_t)D + (size_t)(lane + 64 * k);
-                C[at] = (uint16_t)box[k];
-                S[at] = (uint16_t)path.prev[k];
-            }
-        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            const int in = x + 3 <= cols - 1 ? column_sad(x + 3, lane + 64 * k) : v[k][4];
-            box[k] += in - v[k][0];
-            v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
-        }
-    }
-    // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
-    sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);
-}
-
-// k_sgm_rows with step 2b, a sibling so that k_sgm_rows keeps its instruction stream: the staging loop converts the guide row to hints
-// beside the grey columns, and C' = C + the penalty goes into the path and into the volume, so every later pass reads C'.  What differs
-// from k_sgm_rows is the guide's row, the hints, pen[] and cost[]; the rest is its text.
-template <int NPL, bool LDS>
-__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_guided(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                                                                    uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2, SgmGuide g)
-{
-    extern __shared__ uint2 sgm_lds[];                      // [cols] left, then [cols] right; then [cols] int16 hints (LDS route)
-    const int y = (int)blockIdx.x, lane = sgm_lane();
-    const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
-    const uint8_t* L = left + frame * px;
-    const uint8_t* R = right + frame * px;
-    uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
-    uint16_t* S = C + ve;
-    const uint32_t* G = g.plane + frame * px + (size_t)y * (size_t)cols;     // the guide's row y
-    int16_t* hints = reinterpret_cast<int16_t*>(sgm_lds + 2 * (size_t)cols);
-    if constexpr (LDS) {
-        for (int x = lane; x < cols; x += 64) {
-            sgm_lds[x] = sgm_pack_column(L, rows, cols, y, x);
-            sgm_lds[cols + x] = sgm_pack_column(R, rows, cols, y, x);
-            hints[x] = (int16_t)sgm_hint(G[x], g.bf, D);      // one division a pixel
-        }
-        __syncthreads();
-    }
-    bool have[NPL];
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
-    // V(x, d): the sum over the five rows of |left(., x) - right(., max(x - d, 0))|
-    const auto column_sad = [&](int x, int d) -> int {
-        const int xr = max(x - d, 0);
-        uint2 l, r;
-        if constexpr (LDS) { l = sgm_lds[x]; r = sgm_lds[cols + xr]; }
-        else { l = sgm_pack_column(L, rows, cols, y, x); r = sgm_pack_column(R, rows, cols, y, xr); }
-        return (int)__builtin_amdgcn_sad_u8(l.x, r.x, __builtin_amdgcn_sad_u8(l.y, r.y, 0u));
-    };
-    // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
-    int v[NPL][5], box[NPL];
-#pragma unroll
-    for (int k = 0; k < NPL; ++k) {
-        const int d = lane + 64 * k;
-        const int v0 = column_sad(0, d), v1 = column_sad(min(1, cols - 1), d), v2 = column_sad(min(2, cols - 1), d);
-        v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
-        box[k] = 3 * v0 + v1 + v2;
-    }
-    // pen[k] is the penalty of column x, min(weight |d - h|, cap) or 0 without a hint.  The hint is the same in every lane (an
-    // LDS broadcast, or a wave-uniform address on the global route) and the penalty hangs on x and the lane alone, so it is made one
-    // column ahead, beside the box, off the chain of path steps.  The hint goes to a scalar register, where "no hint" becomes a
-    // weight of 0; weight <= 10000 and |d - h| <= 127 fit the 24-bit multiply.
-    int pen[NPL];
-    const auto penalties = [&](int x) {
-        const int h = __builtin_amdgcn_readfirstlane(LDS ? (int)hints[x] : sgm_hint(G[x], g.bf, D));
-        const int weight = h >= 0 ? g.weight : 0;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) pen[k] = min(__mul24(weight, abs(lane + 64 * k - h)), g.cap);
-    };
-    penalties(0);
-    SgmPath<NPL> path;
-    for (int x = 0; x < cols; ++x) {
-        int cost[NPL], c[NPL];                                  // C' of this column
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            cost[k] = box[k] + pen[k];
-            c[k] = have[k] ? cost[k] : kSgmAbsent;
-        }
-        if (x == 0) path.start(c); else path.step(c, p1, p2);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k)
-            if (have[k]) {
-                const size_t at = (size_t)x * (size_t)D + (size_t)(lane + 64 * k);
-                C[at] = (uint16_t)cost[k];
-                S[at] = (uint16_t)path.prev[k];
-            }
-        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            const int in = x + 3 <= cols - 1 ? column_sad(x + 3, lane + 64 * k) : v[k][4];
-            box[k] += in - v[k][0];
-            v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
-        }
-        if (x + 1 < cols) penalties(x + 1);
-    }
-    // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
-    sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);
 }
 
 // Step 1c for one column of an image: the census codes of rows clamp(y-2) .. clamp(y+2) of column x, 24 bits each, in one uint4
@@ -397,20 +248,29 @@ __device__ __forceinline__ uint4 sgm_census_column(const uint8_t* img, int rows,
     return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
 }
 
-// k_sgm_rows / k_sgm_rows_guided with the census cost (steps 1c and 2c; dcmt_sgm_cost_dev with DCMT_SGM_COST_CENSUS), a sibling so that
-// both keep their instruction streams.  The staging loop makes the codes of rows y-2..y+2 of the RIGHT image from its grey rows
-// y-4..y+4 and keeps them in LDS, one uint4 a column: 16 bytes a column (18 with the guide's hint), what k_sgm_rows stages, so as
-// many workgroups share a CU -- the chain of path steps is bound by latency, and with both images' codes in LDS (32 bytes a column,
-// half the workgroups) this kernel took 1.7 times as long.  The LEFT column of a step is the same in every lane, so its codes stay
-// in registers: the wave holds those of 64 columns at a time, a column a lane, reads column x's with four v_readlane and makes the
-// next 64 when the walk reaches them.  The column sum of the five Hamming distances of one (x, d) is four v_xor and four
-// accumulating v_bcnt; 10 * the box goes into the path and into C.  GUIDED: step 2b as in k_sgm_rows_guided, the int16 hints behind
-// the codes.  The box, the path, the stores and the walk back are k_sgm_rows' text.
-template <int NPL, bool LDS, bool GUIDED>
-__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
-                                                                    uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2, SgmGuide g)
+// The rows kernel, one template for every variant.  left, right: [frames][rows][cols]; vol: the chunk's workspace, per frame C then S
+// ([rows][cols][D] uint16 each); g: the guide, looked at only if GUIDED.
+//   NPL     disparities a lane (1: D <= 64; 2).
+//   LDS     the row's operands are staged in LDS; otherwise every column is made from global memory where it is used.
+//   GUIDED  step 2b: the staging loop converts the guide row to hints, a lane per column -- one division a pixel -- and keeps them as
+//           int16 behind the staged columns; C' = C + the penalty goes into the path and into the volume, so every later pass reads C'.
+//   COST    kSgmCostAbsdiff (steps 1, 2): the grey rows y-2..y+2 of both images are staged packed by column (sgm_pack_column), 8 + 8
+//           bytes a column, and the column sum of one (x, d) is two v_sad_u8.  kSgmCostCensus (steps 1c, 2c): the staging loop makes
+//           the codes of rows y-2..y+2 of the RIGHT image from its grey rows y-4..y+4, one uint4 a column: 16 bytes a column as well,
+//           so as many workgroups share a CU -- the chain of path steps is bound by latency, and with both images' codes in LDS (32
+//           bytes a column, half the workgroups) the kernel took 1.7 times as long.  The LEFT column of a step is the same in every
+//           lane, so its codes stay in registers: the wave holds those of 64 columns at a time, a column a lane, reads column x's
+//           with four v_readlane and makes the next 64 when the walk reaches them.  The column sum of the five Hamming distances of
+//           one (x, d) is four v_xor and four accumulating v_bcnt; 10 * the box is the block cost.
+// The two costs also differ in when column x + 3 is fetched: absolute differences behind the path step, census -- its codes and the
+// hint of column x + 1 -- ahead of it, used behind it (sections 30 and 31).
+template <int NPL, bool LDS, bool GUIDED, int COST>
+__global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows(const uint8_t* __restrict__ left, const uint8_t* __restrict__ right,
+                                                             uint16_t* __restrict__ vol, int rows, int cols, int D, int p1, int p2, SgmGuide g)
 {
-    extern __shared__ uint4 sgm_lds_census[];               // [cols] the right image's codes; then [cols] int16 hints (GUIDED, LDS route)
+    constexpr bool CENSUS = COST == kSgmCostCensus;
+    extern __shared__ uint2 sgm_lds[];                      // absolute differences: [cols] left, then [cols] right
+    extern __shared__ uint4 sgm_lds_census[];               // census: [cols] the right image's codes
     const int y = (int)blockIdx.x, lane = sgm_lane();
     const size_t frame = blockIdx.y, px = (size_t)rows * (size_t)cols, ve = px * (size_t)D;
     const uint8_t* L = left + frame * px;
@@ -418,17 +278,24 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_
     uint16_t* C = vol + frame * 2 * ve + (size_t)y * (size_t)cols * (size_t)D;
     uint16_t* S = C + ve;
     const uint32_t* G = GUIDED ? g.plane + frame * px + (size_t)y * (size_t)cols : nullptr;      // the guide's row y
-    int16_t* hints = reinterpret_cast<int16_t*>(sgm_lds_census + (size_t)cols);
+    int16_t* hints = CENSUS ? reinterpret_cast<int16_t*>(sgm_lds_census + (size_t)cols)           // behind either: [cols] int16 hints
+                            : reinterpret_cast<int16_t*>(sgm_lds + 2 * (size_t)cols);
     if constexpr (LDS) {
         for (int x = lane; x < cols; x += 64) {
-            sgm_lds_census[x] = sgm_census_column(R, rows, cols, y, x);
+            if constexpr (CENSUS) {
+                sgm_lds_census[x] = sgm_census_column(R, rows, cols, y, x);
+            } else {
+                sgm_lds[x] = sgm_pack_column(L, rows, cols, y, x);
+                sgm_lds[cols + x] = sgm_pack_column(R, rows, cols, y, x);
+            }
             if constexpr (GUIDED) hints[x] = (int16_t)sgm_hint(G[x], g.bf, D);
         }
         __syncthreads();
     }
-    // the left image's codes of columns 64 j .. 64 j + 63, lane i those of column 64 j + i (the last column again beyond the row's end,
-    // which is never asked for); column x of the window is read from lane x & 63, x the same in every lane
-    uint4 window = sgm_census_column(L, rows, cols, y, min(lane, cols - 1));
+    // census: the left image's codes of columns 64 j .. 64 j + 63, lane i those of column 64 j + i (the last column again beyond the
+    // row's end, which is never asked for); column x of the window is read from lane x & 63, x the same in every lane
+    uint4 window = {};
+    if constexpr (CENSUS) window = sgm_census_column(L, rows, cols, y, min(lane, cols - 1));
     const auto left_codes = [&](int x) -> uint4 {
         const int at = x & 63;
         return make_uint4((uint32_t)__builtin_amdgcn_readlane((int)window.x, at), (uint32_t)__builtin_amdgcn_readlane((int)window.y, at),
@@ -437,8 +304,8 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_
     bool have[NPL];
 #pragma unroll
     for (int k = 0; k < NPL; ++k) have[k] = lane + 64 * k < D;
-    // V(x, d): the sum over the five rows of popcount(K_left(., x) ^ K_right(., max(x - d, 0))), 0..120, in two halves: the codes are
-    // asked for, and their distance is taken when it is needed, a path step later
+    // census, V(x, d): the sum over the five rows of popcount(K_left(., x) ^ K_right(., max(x - d, 0))), 0..120, in two halves: the
+    // codes are asked for, and their distance is taken when it is needed, a path step later
     const auto codes_of = [&](int x, int d, uint4& l, uint4& r) {
         const int xr = max(x - d, 0);
         l = left_codes(x);
@@ -447,52 +314,62 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_
     const auto hamming = [](const uint4& l, const uint4& r) -> int {
         return __builtin_popcount(l.x ^ r.x) + __builtin_popcount(l.y ^ r.y) + __builtin_popcount(l.z ^ r.z) + __builtin_popcount(l.w ^ r.w);
     };
-    const auto column_hamming = [&](int x, int d) -> int {
-        uint4 l, r;
-        codes_of(x, d, l, r);
-        return hamming(l, r);
+    // V(x, d) of either cost; absolute differences: the sum over the five rows of |left(., x) - right(., max(x - d, 0))|
+    const auto column_sum = [&](int x, int d) -> int {
+        if constexpr (CENSUS) {
+            uint4 l, r;
+            codes_of(x, d, l, r);
+            return hamming(l, r);
+        } else {
+            const int xr = max(x - d, 0);
+            uint2 l, r;
+            if constexpr (LDS) { l = sgm_lds[x]; r = sgm_lds[cols + xr]; }
+            else { l = sgm_pack_column(L, rows, cols, y, x); r = sgm_pack_column(R, rows, cols, y, xr); }
+            return (int)__builtin_amdgcn_sad_u8(l.x, r.x, __builtin_amdgcn_sad_u8(l.y, r.y, 0u));
+        }
     };
     // the box over columns x-2..x+2, clamped: v[k][0..4] its five column sums
     int v[NPL][5], box[NPL];
 #pragma unroll
     for (int k = 0; k < NPL; ++k) {
         const int d = lane + 64 * k;
-        const int v0 = column_hamming(0, d), v1 = column_hamming(min(1, cols - 1), d), v2 = column_hamming(min(2, cols - 1), d);
+        const int v0 = column_sum(0, d), v1 = column_sum(min(1, cols - 1), d), v2 = column_sum(min(2, cols - 1), d);
         v[k][0] = v[k][1] = v[k][2] = v0; v[k][3] = v1; v[k][4] = v2;
         box[k] = 3 * v0 + v1 + v2;
     }
-    // the penalty of a column from its hint, as in k_sgm_rows_guided; the hint is read one column ahead
-    int pen[NPL];
+    // pen[k] is the penalty of column x, min(weight |d - h|, cap) or 0 without a hint.  The hint is the same in every lane (an
+    // LDS broadcast, or a wave-uniform address on the global route) and the penalty hangs on x and the lane alone, so it is made one
+    // column ahead, beside the box, off the chain of path steps.  The hint goes to a scalar register, where "no hint" becomes a
+    // weight of 0; weight <= 10000 and |d - h| <= 127 fit the 24-bit multiply.  Absolute differences read the hint of column x here;
+    // census has asked for it ahead of the path step and hands it in as `fetched`.
+    int pen[NPL] = {};
     const auto hint_of = [&](int x) -> int { return LDS ? (int)hints[x] : sgm_hint(G[x], g.bf, D); };
-    const auto penalties = [&](int hint) {
-        if constexpr (GUIDED) {
-            const int h = __builtin_amdgcn_readfirstlane(hint);
-            const int weight = h >= 0 ? g.weight : 0;
+    const auto penalties = [&](int x, int fetched) {
+        const int h = __builtin_amdgcn_readfirstlane(CENSUS ? fetched : hint_of(x));
+        const int weight = h >= 0 ? g.weight : 0;
 #pragma unroll
-            for (int k = 0; k < NPL; ++k) pen[k] = min(__mul24(weight, abs(lane + 64 * k - h)), g.cap);
-        } else {
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) pen[k] = 0;
-        }
+        for (int k = 0; k < NPL; ++k) pen[k] = min(__mul24(weight, abs(lane + 64 * k - h)), g.cap);
     };
-    penalties(GUIDED ? hint_of(0) : -1);
+    if constexpr (GUIDED) penalties(0, CENSUS ? hint_of(0) : -1);
     SgmPath<NPL> path;
     for (int x = 0; x < cols; ++x) {
-        // the codes of column x + 3 and the hint of column x + 1 are asked for here and used behind the path step, which hides their
-        // way from LDS; column x + 3 may be the first of the next 64 of the left image
-        uint4 nl[NPL], nr[NPL];
+        // census: the codes of column x + 3 and the hint of column x + 1 are asked for here and used behind the path step, which hides
+        // their way from LDS; column x + 3 may be the first of the next 64 of the left image
+        [[maybe_unused]] uint4 nl[NPL], nr[NPL];
         const bool more = x + 3 <= cols - 1;
-        if (more) {
-            if (((x + 3) & 63) == 0) window = sgm_census_column(L, rows, cols, y, min(x + 3 + lane, cols - 1));
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) codes_of(x + 3, lane + 64 * k, nl[k], nr[k]);
-        }
         int next_hint = -1;
-        if constexpr (GUIDED) { if (x + 1 < cols) next_hint = hint_of(x + 1); }
-        int cost[NPL], c[NPL];                                  // C (C' with a guide) of this column: 10 * the box <= 6000
+        if constexpr (CENSUS) {
+            if (more) {
+                if (((x + 3) & 63) == 0) window = sgm_census_column(L, rows, cols, y, min(x + 3 + lane, cols - 1));
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) codes_of(x + 3, lane + 64 * k, nl[k], nr[k]);
+            }
+            if constexpr (GUIDED) { if (x + 1 < cols) next_hint = hint_of(x + 1); }
+        }
+        int cost[NPL], c[NPL];                                  // C (C' with a guide) of this column; census: 10 * the box <= 6000
 #pragma unroll
         for (int k = 0; k < NPL; ++k) {
-            cost[k] = 10 * box[k] + pen[k];
+            cost[k] = (CENSUS ? 10 * box[k] : box[k]) + pen[k];
             c[k] = have[k] ? cost[k] : kSgmAbsent;
         }
         if (x == 0) path.start(c); else path.step(c, p1, p2);
@@ -503,14 +380,15 @@ __global__ __launch_bounds__(kSgmRowThreads) void k_sgm_rows_census(const uint8_
                 C[at] = (uint16_t)cost[k];
                 S[at] = (uint16_t)path.prev[k];
             }
-        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge), column x - 2 goes out
+        // the box of column x + 1: column x + 3 comes in (the last column again beyond the edge; absolute differences fetch it
+        // here), column x - 2 goes out
 #pragma unroll
         for (int k = 0; k < NPL; ++k) {
-            const int in = more ? hamming(nl[k], nr[k]) : v[k][4];
+            const int in = more ? (CENSUS ? hamming(nl[k], nr[k]) : column_sum(x + 3, lane + 64 * k)) : v[k][4];
             box[k] += in - v[k][0];
             v[k][0] = v[k][1]; v[k][1] = v[k][2]; v[k][2] = v[k][3]; v[k][3] = v[k][4]; v[k][4] = in;
         }
-        if (x + 1 < cols) penalties(next_hint);
+        if constexpr (GUIDED) { if (x + 1 < cols) penalties(x + 1, next_hint); }
     }
     // right -> left over the C this wave wrote: lane d reads the addresses lane d stored
     sgm_line<NPL>(C, S, (ptrdiff_t)(cols - 1) * D, -(ptrdiff_t)D, cols, lane, D, p1, p2);

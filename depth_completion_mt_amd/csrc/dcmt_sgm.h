@@ -1,4 +1,4 @@
-// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_rows_guided, k_sgm_rows_census, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its
+// dcmt_sgm.h -- the constants dcmt_kernels_sgm.h (k_sgm_rows, k_sgm_cols, k_sgm_diag, k_sgm_winner) shares with its
 // plan, and the plan itself (plan_sgm): the checks on the arguments of dcmt_sgm_dev / dcmt_sgm_paths_dev / dcmt_sgm_guided_dev / dcmt_sgm_cost_dev, the
 // workspace layout, the chunking of the batch and the launch shapes.
 // Plain C++, no HIP: the plan is tested on a CPU (tests/plan_sgm_test.cpp).
@@ -21,10 +21,10 @@ constexpr int kSgmWaves = 4;                            // k_sgm_cols, k_sgm_dia
 constexpr int kSgmSegment = 64;                         // k_sgm_winner: pixels of a row per wave, one result a lane
 constexpr size_t kSgmLdsBudget = 64 * 1024;             // k_sgm_rows stages 16 bytes a column: up to 4096 columns, wider rows from global memory
 constexpr uint32_t kSgmLdsPerCol = 16;                  // rows y-2..y+2 of one column, left (8 bytes: 4 + 1 used) and right (8 bytes)
-constexpr uint32_t kSgmLdsPerColGuided = 18;            // k_sgm_rows_guided: the column's hint as well, an int16 behind the images: up to 3640 columns
+constexpr uint32_t kSgmLdsPerColGuided = 18;            // GUIDED: the column's hint as well, an int16 behind the images: up to 3640 columns
 constexpr int kSgmCostAbsdiff = 0, kSgmCostCensus = 1;  // DCMT_SGM_COST_*: the pixel cost of steps 1 / 2, or of steps 1c / 2c
-constexpr uint32_t kSgmLdsPerColCensus = 16;            // k_sgm_rows_census: the five 24-bit codes of one column of the right image in a uint4 (the left
-                                                        // image's stay in registers): up to 4096 columns, as many workgroups a CU as k_sgm_rows
+constexpr uint32_t kSgmLdsPerColCensus = 16;            // census: the five 24-bit codes of one column of the right image in a uint4 (the left
+                                                        // image's stay in registers): up to 4096 columns, as many workgroups a CU as with absolute differences
 constexpr uint32_t kSgmLdsPerColCensusGuided = 18;      // and the column's int16 hint behind them: up to 3640 columns
 
 namespace plan {
@@ -54,9 +54,9 @@ struct SgmPlan {
     unsigned segments;               // ceil(cols / kSgmSegment)
     int paths;                       // 4, or 8: k_sgm_diag runs twice between k_sgm_cols and k_sgm_winner, once per orientation
     unsigned diag_grid_x;            // k_sgm_diag: (ceil(cols / kSgmWaves), frames), 64 * kSgmWaves threads, a wave a start column; 0 with 4 paths
-    bool guided;                     // a guide was given: k_sgm_rows_guided in place of k_sgm_rows, kSgmLdsPerColGuided bytes a column
+    bool guided;                     // a guide was given: the GUIDED instances of k_sgm_rows, kSgmLdsPerColGuided bytes a column
     int guide_weight, guide_cap;     // its penalty min(guide_weight * |d - h|, guide_cap); 0, 0 without a guide
-    int cost;                        // kSgmCostAbsdiff, or kSgmCostCensus: k_sgm_rows_census in place of either rows kernel, kSgmLdsPerColCensus(Guided) bytes a column
+    int cost;                        // kSgmCostAbsdiff, or kSgmCostCensus: k_sgm_rows' COST, with census kSgmLdsPerColCensus(Guided) bytes a column
 };
 
 // the LDS bytes a column of the rows kernel of (cost, guided)

@@ -1,7 +1,8 @@
 // dcmt_sgm.hip -- semi-global stereo matching (dcmt_kernels_sgm.h), a code object of its own: dcmt_default_sgm_params,
 // dcmt_sgm_workspace_bytes, dcmt_sgm_dev, dcmt_sgm_paths_dev, dcmt_sgm_guided_dev and dcmt_sgm_cost_dev (of which dcmt_sgm_guided_dev is the
 // absolute-difference case, dcmt_sgm_paths_dev the case of that without a guide, and dcmt_sgm_dev the four-path case of that).  The plan (dcmt_sgm.h: plan_sgm) checks the arguments, lays the caller's
-// workspace out and cuts the batch into chunks; this file launches what it says.
+// workspace out and cuts the batch into chunks; this file launches what it says: per chunk the instance of k_sgm_rows<NPL, LDS, GUIDED, COST>
+// that the plan's (per_lane, lds_route, guided, cost) name, k_sgm_cols, with eight paths k_sgm_diag twice, and k_sgm_winner.
 // The single-pair host forms, dcmt_sgm, dcmt_sgm_paths, dcmt_sgm_guided and dcmt_sgm_cost, are in dcmt_host.hip.
 #include <initializer_list>
 
@@ -12,6 +13,19 @@
 
 using namespace dcmt;
 
+// the instance of k_sgm_rows the plan asks for
+using SgmRowsKernel = void (*)(const uint8_t*, const uint8_t*, uint16_t*, int, int, int, int, int, SgmGuide);
+template <int NPL>
+static SgmRowsKernel sgm_rows_kernel(const plan::SgmPlan& pl)
+{
+    constexpr int A = kSgmCostAbsdiff, C = kSgmCostCensus;
+    static constexpr SgmRowsKernel table[2][2][2] = {                                   // [cost][lds_route][guided]
+        {{k_sgm_rows<NPL, false, false, A>, k_sgm_rows<NPL, false, true, A>}, {k_sgm_rows<NPL, true, false, A>, k_sgm_rows<NPL, true, true, A>}},
+        {{k_sgm_rows<NPL, false, false, C>, k_sgm_rows<NPL, false, true, C>}, {k_sgm_rows<NPL, true, false, C>, k_sgm_rows<NPL, true, true, C>}},
+    };
+    return table[pl.cost == kSgmCostCensus][pl.lds_route][pl.guided];
+}
+
 template <int NPL>
 static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_t* right, const float* guide, int16_t* disp16, float* depth,
                       uint16_t* vol, int rows, int cols, int frames, const dcmt_sgm_params& P, hipStream_t st)
@@ -19,23 +33,8 @@ static void sgm_chunk(const plan::SgmPlan& pl, const uint8_t* left, const uint8_
     const int D = P.num_disparities;
     const float bf = P.baseline * P.focal;                  // rounded once: the hint's and step 9's
     const dim3 rows_grid(pl.rows_grid_x, (unsigned)frames), cols_grid(pl.cols_grid_x, (unsigned)frames), winner_grid(pl.winner_grid_x, (unsigned)frames);
-    if (pl.cost == kSgmCostCensus) {                        // one sibling for both: the guide is a template parameter of it
-        const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};
-        const auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
-        };
-        if (pl.guided) { if (pl.lds_route) launch(k_sgm_rows_census<NPL, true, true>); else launch(k_sgm_rows_census<NPL, false, true>); }
-        else { if (pl.lds_route) launch(k_sgm_rows_census<NPL, true, false>); else launch(k_sgm_rows_census<NPL, false, false>); }
-    } else if (pl.guided) {
-        const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};
-        if (pl.lds_route)
-            hipLaunchKernelGGL((k_sgm_rows_guided<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
-        else
-            hipLaunchKernelGGL((k_sgm_rows_guided<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
-    } else if (pl.lds_route)
-        hipLaunchKernelGGL((k_sgm_rows<NPL, true>), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2);
-    else
-        hipLaunchKernelGGL((k_sgm_rows<NPL, false>), rows_grid, dim3(kSgmRowThreads), 0, st, left, right, vol, rows, cols, D, P.p1, P.p2);
+    const SgmGuide g = {reinterpret_cast<const uint32_t*>(guide), bf, pl.guide_weight, pl.guide_cap};     // all zero but bf without a guide
+    hipLaunchKernelGGL(sgm_rows_kernel<NPL>(pl), rows_grid, dim3(kSgmRowThreads), pl.lds, st, left, right, vol, rows, cols, D, P.p1, P.p2, g);
     hipLaunchKernelGGL((k_sgm_cols<NPL>), cols_grid, dim3(64 * kSgmWaves), 0, st, vol, rows, cols, D, P.p1, P.p2);
     if (pl.paths == 8) {                                    // one launch per orientation: a "\" line and a "/" line cross
         const dim3 diag_grid(pl.diag_grid_x, (unsigned)frames);

@@ -1,21 +1,31 @@
 """Semi-global matching with the census cost on the device against the absolute-difference call (352x1216, 64 pairs, D = 64, a workspace
-of 16 frames: four chunks; the pairs and sizes of tools/time_sgm_guided.py): sgm_dev(cost="census") against sgm_dev(cost="absdiff")
+of 16 frames: four chunks; the pairs and sizes of tools/time_sgm_guided.py; --rows, --cols and --disparities change them: --disparities
+128 reaches the instances of k_sgm_rows with two disparities a lane, --cols 4100 with a small --rows those that do not stage their row
+in LDS): sgm_dev(cost="census") against sgm_dev(cost="absdiff")
 with four and with eight paths, and with a dense guide (every pixel hinted) on both, both outputs, in one alternating session.
 Medians of REPS alternating repetitions in one process, with the range.  The comparison partner of every census figure is the
 absolute-difference call of the same session.
 Then the rows kernel: the tool starts itself once more as a fresh child process under the kernel trace,
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o sgm -- python3 tools/time_sgm_census.py --profile
 (--profile: three four-path calls each with absolute differences and with census, without a guide and with the dense one), and prints
-the mean time of k_sgm_rows, k_sgm_rows_guided and the two k_sgm_rows_census instances per launch, that is per chunk of 16 frames,
-beside the other kernels, from DIR's kernel_stats.csv.  --no-kernels leaves that step out."""
-import csv, glob, os, shutil, statistics, subprocess, sys, tempfile
+the mean time of the four instances of k_sgm_rows<NPL, LDS, GUIDED, COST> per launch, that is per chunk of 16 frames, beside the other
+kernels, from DIR's kernel_stats.csv; every census instance beside the absolute-difference instance of the same <NPL, LDS, GUIDED>.
+--no-kernels leaves that step out."""
+import argparse, csv, glob, os, re, shutil, statistics, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from depth_completion_mt_amd import Context, sgm_workspace_bytes, synth
-B, R, C, D, HELD = 64, 352, 1216, 64, 16
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, default=352)
+ap.add_argument("--cols", type=int, default=1216)
+ap.add_argument("--disparities", type=int, default=64)
+ap.add_argument("--profile", action="store_true")
+ap.add_argument("--no-kernels", action="store_true")
+args = ap.parse_args()
+B, R, C, D, HELD = 64, args.rows, args.cols, args.disparities, 16
 REPS = 5
-PROFILE = "--profile" in sys.argv[1:]
+PROFILE = args.profile
 pairs = [synth.synth_stereo(R, C, seed) for seed in range(4)]
 left = torch.from_numpy(np.stack([p[0] for p in pairs])).cuda().repeat(B // 4, 1, 1).contiguous()
 right = torch.from_numpy(np.stack([p[1] for p in pairs])).cuda().repeat(B // 4, 1, 1).contiguous()
@@ -82,14 +92,15 @@ with Context(0, R, C, B) as ctx:
 
 
 # ---- the kernels, from a kernel trace of a child process (the context above is closed; the child opens its own) ----------------------
-if "--no-kernels" not in sys.argv[1:]:
+if not args.no_kernels:
     tracer = shutil.which("rocprofv3")
     if tracer is None:
         print("the kernels: rocprofv3 not found, not measured")
         sys.exit(0)
     with tempfile.TemporaryDirectory() as out:
         r = subprocess.run([tracer, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "sgm", "--", sys.executable,
-                            os.path.abspath(__file__), "--profile"], capture_output=True, text=True, timeout=600)
+                            os.path.abspath(__file__), "--profile", "--rows", str(R), "--cols", str(C), "--disparities", str(D)],
+                           capture_output=True, text=True, timeout=600)
         found = glob.glob(os.path.join(out, "**", "*kernel_stats.csv"), recursive=True)
         if r.returncode != 0 or not found:
             print(f"the kernels: the traced run failed (status {r.returncode})\n{r.stderr[-2000:]}")
@@ -102,10 +113,8 @@ if "--no-kernels" not in sys.argv[1:]:
         mean[name] = float(row["AverageNs"]) / 1e6
         print(f"{name}: {mean[name]:.3f} ms a launch ({HELD} frames) [{float(row['MinNs']) / 1e6:.3f} .. {float(row['MaxNs']) / 1e6:.3f}], "
               f"{row['Calls']} launches")
-    plain = [v for k, v in mean.items() if k.startswith("k_sgm_rows<")]
-    guided = [v for k, v in mean.items() if k.startswith("k_sgm_rows_guided<")]
     for k, v in mean.items():
-        if "k_sgm_rows_census" in k:
-            partner = guided if k.rstrip(">").endswith("true") and guided else plain        # <NPL, LDS, GUIDED>
-            if partner:
-                print(f"{k} / its absolute-difference kernel = {v / partner[0]:.3f}, {v - partner[0]:+.3f} ms a launch")
+        m = re.fullmatch(r"k_sgm_rows<(.+), 1>", k)                  # <NPL, LDS, GUIDED, COST>: COST 1 is census, 0 its partner
+        partner = mean.get(f"k_sgm_rows<{m.group(1)}, 0>") if m else None
+        if partner:
+            print(f"{k} / its absolute-difference instance = {v / partner:.3f}, {v - partner:+.3f} ms a launch")

@@ -6,9 +6,10 @@ changing from pixel to pixel.
 Then the rows kernel: the tool starts itself once more as a fresh child process under the kernel trace,
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o sgm -- python3 tools/time_sgm_guided.py --profile
 (--profile: three four-path calls each without a guide, with the sparse and with the dense one), and prints the mean time of
-k_sgm_rows and k_sgm_rows_guided per launch, that is per chunk of 16 frames, beside the other kernels, from DIR's kernel_stats.csv.
+the unguided and the guided instance of k_sgm_rows<NPL, LDS, GUIDED, COST> per launch, that is per chunk of 16 frames, beside the other
+kernels, from DIR's kernel_stats.csv.
 --no-kernels leaves that step out."""
-import csv, glob, os, shutil, statistics, subprocess, sys, tempfile
+import csv, glob, os, re, shutil, statistics, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -96,7 +97,8 @@ if "--no-kernels" not in sys.argv[1:]:
         mean[name] = float(row["AverageNs"]) / 1e6
         print(f"{name}: {mean[name]:.3f} ms a launch ({HELD} frames) [{float(row['MinNs']) / 1e6:.3f} .. {float(row['MaxNs']) / 1e6:.3f}], "
               f"{row['Calls']} launches")
-    plain = [v for k, v in mean.items() if k.startswith("k_sgm_rows<")]
     for k, v in mean.items():
-        if "k_sgm_rows_guided" in k and plain:
-            print(f"{k} / k_sgm_rows = {v / plain[0]:.3f} (sparse and dense launches together), {v - plain[0]:+.3f} ms a launch")
+        m = re.fullmatch(r"k_sgm_rows<(.+), true, (\d+)>", k)        # <NPL, LDS, GUIDED, COST>
+        plain = mean.get(f"k_sgm_rows<{m.group(1)}, false, {m.group(2)}>") if m else None
+        if plain:
+            print(f"{k} / its unguided instance = {v / plain:.3f} (sparse and dense launches together), {v - plain:+.3f} ms a launch")
