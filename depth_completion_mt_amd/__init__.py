@@ -10,7 +10,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   depth_to_u16, kitti_crop_origin, make_crop_table, pack_ragged, bilateral_filter5,
                   slic_connectivity_max_labels, slic_enforce_connectivity, slic_display_contours,
                   slic_colour_with_cluster_means, get_initial_error, make_photo_error_params, make_sgm_params,
-                  sgm_workspace_bytes, stereo_sgm, make_speckle_params, filter_speckles)
+                  sgm_workspace_bytes, stereo_sgm, make_speckle_params, filter_speckles,
+                  RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -20,7 +21,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "calib_to_device", "depth_to_u16", "kitti_crop_origin", "make_crop_table", "pack_ragged",
            "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity",
            "slic_display_contours", "slic_colour_with_cluster_means", "get_initial_error", "make_photo_error_params",
-           "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm", "make_speckle_params", "filter_speckles"]
+           "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm", "make_speckle_params", "filter_speckles",
+           "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify"]
 
 
 def __getattr__(name):

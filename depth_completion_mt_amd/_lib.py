@@ -22,6 +22,7 @@ FLAG_NORMALIZE = 4
 FLAG_NO_EXTRAPOLATE = 8
 STAGE_FILL31, STAGE_FILLLOOP, STAGE_MEDIAN5, STAGE_BLUR, STAGE_FINAL = 7, 8, 9, 10, 11
 EVAL_GT, EVAL_BOTH = 0, 1
+RECTIFY_FORCE_GATHER = 1
 
 # every symbol include/dcmt.h declares (tests check the library exports exactly these)
 EXPORTS = (
@@ -47,6 +48,7 @@ EXPORTS = (
     "dcmt_default_sgm_params", "dcmt_sgm_workspace_bytes", "dcmt_sgm_dev", "dcmt_sgm", "dcmt_sgm_paths_dev", "dcmt_sgm_paths",
     "dcmt_sgm_guided_dev", "dcmt_sgm_guided", "dcmt_sgm_cost_dev", "dcmt_sgm_cost",
     "dcmt_default_speckle_params", "dcmt_filter_speckles_dev", "dcmt_filter_speckles",
+    "dcmt_rectify_map_dev", "dcmt_rectify_dev", "dcmt_rectify",
 )
 
 
@@ -128,6 +130,14 @@ class CropSrc(ctypes.Structure):
     """Mirror of dcmt_crop_src (include/dcmt.h): one frame's record of dcmt_crop_frames_dev, 32 bytes."""
     _fields_ = [("offset", ctypes.c_uint64), ("row_stride", ctypes.c_uint32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
                 ("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("reserved", ctypes.c_uint32)]
+
+
+class RectifyCalib(ctypes.Structure):
+    """Mirror of dcmt_rectify_calib (include/dcmt.h): one camera's record of dcmt_rectify_map_dev, 22 doubles."""
+    _fields_ = [("fx", ctypes.c_double), ("fy", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+                ("k1", ctypes.c_double), ("k2", ctypes.c_double), ("p1", ctypes.c_double), ("p2", ctypes.c_double), ("k3", ctypes.c_double),
+                ("R", ctypes.c_double * 9),
+                ("fxp", ctypes.c_double), ("fyp", ctypes.c_double), ("cxp", ctypes.c_double), ("cyp", ctypes.c_double)]
 
 
 def nearest_name(twin: str) -> str:
@@ -265,6 +275,9 @@ def lib() -> ctypes.CDLL:
         L.dcmt_default_speckle_params.restype = None
         L.dcmt_filter_speckles_dev.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_filter_speckles.argtypes = [vp, vp, sz, vp, sz, vp, sz, i, i, vp, vp]
+        L.dcmt_rectify_map_dev.argtypes = [vp, vp, i, i, i, vp, vp]
+        L.dcmt_rectify_dev.argtypes = [vp, vp, i, i, i, vp, i, vp, ctypes.c_uint32, vp, i, i, i, vp]
+        L.dcmt_rectify.argtypes = [vp, vp, sz, i, i, i, vp, vp, sz, i, i]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

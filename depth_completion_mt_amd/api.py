@@ -394,6 +394,39 @@ def make_stereo_calib(baseline, focal) -> np.ndarray:
     return out
 
 
+RECTIFY_CALIB_DTYPE = np.dtype([("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("k1", "<f8"), ("k2", "<f8"), ("p1", "<f8"),
+                                ("p2", "<f8"), ("k3", "<f8"), ("R", "<f8", (9,)), ("fxp", "<f8"), ("fyp", "<f8"), ("cxp", "<f8"),
+                                ("cyp", "<f8")])                                                             # dcmt_rectify_calib, 176 B
+
+
+def make_rectify_calib(K, D, R, P, device="cuda"):
+    """The table of Context.rectify_map_dev: one record per camera out of what calib_cam_to_cam.txt gives -- K [3][3] the distorted
+    camera, D [5] = k1 k2 p1 p2 k3, R [3][3] the rectifying rotation (R_rect), P [3][3] or [3][4] the new camera (P_rect: its left
+    3 x 3 is used) --, each one entry or a [b] stack (a single entry is repeated).  Raises ValueError for what the device answers with
+    an all-outside map: a non-finite entry, fxp or fyp zero.  Returns the table on the device (calib_to_device: one synchronous
+    upload, outside the hot loop); device=None returns the numpy table instead."""
+    K, D, R, P = (np.asarray(a, dtype=np.float64) for a in (K, D, R, P))
+    if K.shape[-2:] != (3, 3) or D.shape[-1:] != (5,) or R.shape[-2:] != (3, 3) or P.shape[-2:] not in ((3, 3), (3, 4)):
+        raise ValueError(f"K [3][3], D [5], R [3][3], P [3][3] or [3][4], each alone or stacked [b]; got {K.shape}, {D.shape}, {R.shape}, {P.shape}")
+    stacks = [a.shape[0] for a, nd in ((K, 2), (D, 1), (R, 2), (P, 2)) if a.ndim == nd + 1]
+    if any(a.ndim not in (nd, nd + 1) for a, nd in ((K, 2), (D, 1), (R, 2), (P, 2))) or len(set(stacks)) > 1:
+        raise ValueError(f"stacks of one common length [b]; got {K.shape}, {D.shape}, {R.shape}, {P.shape}")
+    b = stacks[0] if stacks else 1
+    K, R, P = (np.broadcast_to(a, (b,) + a.shape[-2:]) for a in (K, R, P))
+    D = np.broadcast_to(D, (b, 5))
+    out = np.zeros(b, RECTIFY_CALIB_DTYPE)
+    out["fx"], out["fy"], out["cx"], out["cy"] = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+    for i, k in enumerate(("k1", "k2", "p1", "p2", "k3")):
+        out[k] = D[:, i]
+    out["R"] = R.reshape(b, 9)
+    out["fxp"], out["fyp"], out["cxp"], out["cyp"] = P[:, 0, 0], P[:, 1, 1], P[:, 0, 2], P[:, 1, 2]
+    for k in RECTIFY_CALIB_DTYPE.names:
+        _finite_or_raise(k, out[k])
+    _nonzero_or_raise("fxp", out["fxp"])
+    _nonzero_or_raise("fyp", out["fyp"])
+    return out if device is None else calib_to_device(out, device)
+
+
 CROP_SRC_DTYPE = np.dtype([("offset", "<u8"), ("row_stride", "<u4"), ("rows", "<i4"), ("cols", "<i4"), ("x0", "<i4"), ("y0", "<i4"),
                            ("reserved", "<u4")])                                                              # dcmt_crop_src, 32 B
 
@@ -1180,6 +1213,75 @@ class Context:
         _check(st, "dcmt_bgr_convert")
         return (o_lab, o_gray) if lab and gray else o_lab if lab else o_gray
 
+    # ---- undistortion and rectification of camera frames (dcmt_rectify*) --------------------------------------------
+    def rectify_map_dev(self, d_table, rows: int, cols: int, d_map=None, stream: int | None = None):
+        """The undistort-and-rectify maps of a table of cameras (dcmt_rectify_map_dev: cv::initUndistortRectifyMap as include/dcmt.h
+        states it; the reference's rectify(), SL/main_sl.cpp:1350-1381).  d_table: a CUDA tensor holding [n_maps] dcmt_rectify_calib
+        records (make_rectify_calib), read on the stream the call enqueues on.  Returns the int32 CUDA tensor
+        [n_maps][rows][cols][2] of 1/32-pixel source positions (sx, sy), without synchronising; a bad record's map is all outside.
+        Computed once per calibration.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_table)
+        n_maps, rem = divmod(d_table.numel() * d_table.element_size(), RECTIFY_CALIB_DTYPE.itemsize)
+        assert n_maps >= 1 and rem == 0, tuple(d_table.shape)
+        if d_map is None:
+            with _on_stream(stream, d_table):
+                d_map = torch.empty((n_maps, rows, cols, 2), dtype=torch.int32, device=d_table.device)
+        assert _is_dev(d_map, torch.int32) and d_map.numel() == n_maps * rows * cols * 2
+        st = L.lib().dcmt_rectify_map_dev(self._h, d_table.data_ptr(), n_maps, rows, cols, d_map.data_ptr(), _stream(stream, d_table))
+        _check(st, "dcmt_rectify_map_dev")
+        return d_map
+
+    def rectify_dev(self, d_src, d_map, out=None, d_map_index=None, force_gather: bool = False, stream: int | None = None):
+        """cv::remap(..., cv::INTER_LINEAR) of a batch through rectify_map_dev's maps (dcmt_rectify_dev), in front of crop_frames_dev
+        and bgr_convert_dev.  d_src: uint8 CUDA tensor [b][r][c] (grey) or [b][r][c][3], any byte alignment; d_map: int32
+        [n_maps][rows][cols][2] (or [rows][cols][2]).  Frame f goes through map d_map_index[f] (an int32 CUDA tensor [b]; an index
+        outside 0 .. n_maps - 1 gives a zero frame), without one through map f % n_maps: one map for the batch, two for interleaved
+        left and right frames.  Returns uint8 [b][rows][cols] or [b][rows][cols][3] -- the shape comes from the map --, without
+        synchronising; samples outside the source are 0.  force_gather: the global-gather route for every tile (tests, timing; the
+        same bytes).  last_path() names the routes taken once the call has run.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_src, torch.uint8) and d_src.dim() in (3, 4) and (d_src.dim() == 3 or d_src.shape[3] == 3), tuple(d_src.shape)
+        assert _is_dev(d_map, torch.int32) and d_map.dim() in (3, 4) and d_map.shape[-1] == 2, tuple(d_map.shape)
+        b, sr, sc = d_src.shape[:3]
+        ch = 1 if d_src.dim() == 3 else 3
+        n_maps = 1 if d_map.dim() == 3 else d_map.shape[0]
+        rows, cols = d_map.shape[-3], d_map.shape[-2]
+        if out is None:
+            with _on_stream(stream, d_src):
+                out = torch.empty((b, rows, cols) + tuple(d_src.shape[3:]), dtype=torch.uint8, device=d_src.device)
+        assert _is_dev(out, torch.uint8) and out.numel() == b * rows * cols * ch
+        assert d_map_index is None or (_is_dev(d_map_index, torch.int32) and d_map_index.numel() == b)
+        st = L.lib().dcmt_rectify_dev(self._h, d_src.data_ptr(), sr, sc, ch, d_map.data_ptr(), n_maps,
+                                      d_map_index.data_ptr() if d_map_index is not None else None,
+                                      L.RECTIFY_FORCE_GATHER if force_gather else 0, out.data_ptr(), rows, cols, b, _stream(stream, d_src))
+        _check(st, "dcmt_rectify_dev")
+        return out
+
+    def rectify(self, img, K, D, R, P, out_shape):
+        """One frame, undistorted and rectified: img uint8 [r][c] or [r][c][3], the camera as make_rectify_calib takes it (single
+        entries), out_shape = (rows, cols).  A numpy frame goes through the host entry point (dcmt_rectify, synchronous; any row
+        stride); a CUDA tensor through the two device calls, on torch's current stream, and comes back as a CUDA tensor without
+        synchronising (the record's upload apart)."""
+        rows, cols = out_shape
+        if hasattr(img, "is_cuda") and img.is_cuda:
+            d_map = self.rectify_map_dev(make_rectify_calib(K, D, R, P, device=img.device), rows, cols)
+            return self.rectify_dev(img[None].contiguous(), d_map)[0]
+        rec = make_rectify_calib(K, D, R, P, device=None)
+        assert len(rec) == 1
+        a = np.asarray(img, dtype=np.uint8)
+        assert a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3), a.shape
+        ch = 1 if a.ndim == 2 else 3
+        if a.strides[1] != ch or (ch == 3 and a.strides[2] != 1):
+            a = np.ascontiguousarray(a)
+        o = np.empty((rows, cols) + a.shape[2:], dtype=np.uint8)
+        st = L.lib().dcmt_rectify(self._h, a.ctypes.data, a.strides[0], a.shape[0], a.shape[1], ch, rec.ctypes.data, o.ctypes.data,
+                                  o.strides[0], rows, cols)
+        _check(st, "dcmt_rectify")
+        return o
+
     # ---- point cloud of a dense plane (dcmt_depth_to_cloud*) and the blur in front of it (dcmt_gaussian5*) -----------
     def depth_to_cloud_dev(self, d_depth, d_bgr=None, params: L.CloudParams | None = None, d_points=None, d_offsets=None,
                            capacity: int | None = None, stream: int | None = None):
@@ -1457,6 +1559,17 @@ def bgr_to_gray(img):
     """cv::cvtColor(img, gray, cv::COLOR_BGR2GRAY) on 8-bit pixels (SL/main_sl.cpp:1167, :1171): uint8 [...][rows][cols][3] ->
     [...][rows][cols]; numpy or CUDA tensor, as bgr_to_lab."""
     return _bgr_convert(img, False)
+
+
+def undistort_rectify(img, K, D, R, P, out_shape):
+    """The reference's rectify() for one camera (SL/main_sl.cpp:1350-1381: cv::initUndistortRectifyMap, then cv::remap with
+    INTER_LINEAR), as include/dcmt.h states it: img uint8 [rows][cols] or [rows][cols][3] -> the undistorted, rectified frame of
+    out_shape = (rows, cols).  K, D, R, P: K_0x, D_0x, R_rect_0x, P_rect_0x of calib_cam_to_cam.txt.  numpy or CUDA tensor, as
+    bgr_to_lab."""
+    rows, cols = out_shape
+    if hasattr(img, "is_cuda") and img.is_cuda:
+        return _ctx_for(rows, cols, 1, img.device.index or 0).rectify(img, K, D, R, P, out_shape)
+    return _ctx_for(rows, cols, 1).rectify(img, K, D, R, P, out_shape)
 
 
 def get_initial_error(depth, left, right, **params):

@@ -720,8 +720,9 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     if (!mem(ctx->tb, 2 * (size_t)max_cols * tb_slots) || !mem(ctx->norm_stats, 2 * mb)) return fail(DCMT_E_NOMEM);
     if (hipMemset(ctx->norm_stats, 0, sizeof(uint32_t) * 2 * mb) != hipSuccess) return fail(DCMT_E_HIP);
     if (!mem(ctx->norm_coef, 2 * mb) || !mem(ctx->color_slab, kColorSlabStride * chunks * mb) || !mem(ctx->cloud_slab, kCloudWaves * chunks * mb) ||
-        !mem(ctx->h_counters, kCntStride * mb))
+        !mem(ctx->h_counters, kCntStride * mb) || !mem(ctx->rectify_route, 2))
         return fail(DCMT_E_NOMEM);
+    if (hipMemset(ctx->rectify_route, 0, sizeof(uint32_t) * 2) != hipSuccess) return fail(DCMT_E_HIP);
     *out = ctx;
     return DCMT_OK;
 }
@@ -979,7 +980,20 @@ int dcmt_last_holes_after_extend(dcmt_ctx* ctx, int* out, int n)
 
 int dcmt_last_hip_error(const dcmt_ctx* ctx) { return ctx ? ctx->last_hip_error : 0; }
 
-const char* dcmt_last_path(const dcmt_ctx* ctx) { return ctx ? ctx->last_path : ""; }
+// a dcmt_rectify_dev call leaves "k_rectify" here (dcmt_rectify.hip): which routes its tiles took is the kernel's to say, in the two
+// words of rectify_route
+const char* dcmt_last_path(const dcmt_ctx* ctx)
+{
+    if (!ctx) return "";
+    if (std::strcmp(ctx->last_path, "k_rectify") != 0) return ctx->last_path;
+    uint32_t w[2] = {0, 0};
+    if (hipMemcpy(w, ctx->rectify_route.p, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return ctx->last_path;
+    }
+    const bool lds = w[0] == ctx->rectify_call, gather = w[1] == ctx->rectify_call;
+    return lds && gather ? "k_rectify<lds+gather>" : lds ? "k_rectify<lds>" : gather ? "k_rectify<gather>" : ctx->last_path;
+}
 
 int dcmt_set_kernel_timing(dcmt_ctx* ctx, int on)
 {

@@ -106,6 +106,10 @@ struct dcmt_ctx {
                                       // color_slab, kCloudWaves entries per chunk
     Dev<uint32_t> conn_slab;          // dcmt_slic_connectivity_dev: per (frame, strip of 64 columns) counts of non-small seeds, then their exclusive
                                       // bases; max_batch x ceil(max_cols / 64) words, allocated by the first such call
+    Dev<uint32_t> rectify_route;      // dcmt_rectify_dev's probe: two words (kRectifyRouteLds, kRectifyRouteGather, dcmt_rectify.h), each the id of
+                                      // the last call of which a tile took that route; written by k_rectify, read by dcmt_last_path.  Nothing
+                                      // else of a rectify call stays behind
+    uint32_t rectify_call = 0;        // id of the last dcmt_rectify_dev call (0: none yet; last_path then starts with "k_rectify")
 };
 
 namespace dcmt {

@@ -382,6 +382,25 @@ int dcmt_bgr_convert(dcmt_ctx* ctx, const uint8_t* bgr, size_t brs, int rows, in
     return rc == DCMT_OK ? fetch(ctx, {&l, &g}) : rc;
 }
 
+// the record goes up as a table of one, and its map is a plane of the call that is never fetched (its host pointer only marks it
+// as wanted)
+int dcmt_rectify(dcmt_ctx* ctx, const uint8_t* src, size_t srs, int src_rows, int src_cols, int channels, const dcmt_rectify_calib* calib,
+                 uint8_t* dst, size_t drs, int rows, int cols)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !src || !calib || !dst || !dims_ok(ctx, rows, cols, 1) || (channels != 1 && channels != 3)) return DCMT_E_INVALID;
+    if (src_rows < 1 || src_cols < 1 || src_rows > 16384 || src_cols > 16384) return DCMT_E_INVALID;
+    const size_t ch = (size_t)channels;
+    Plane in(src, srs, ch * (size_t)src_cols, src_rows), table(calib, sizeof *calib), map(dst, 8 * (size_t)rows * (size_t)cols),
+        out(dst, drs, ch * (size_t)cols, rows);
+    int rc = stage(ctx, {&in, &table}, {&map, &out});
+    if (rc == DCMT_OK) rc = dcmt_rectify_map_dev(ctx, (const dcmt_rectify_calib*)table.dev, 1, rows, cols, (int32_t*)map.dev, ctx->own_stream);
+    if (rc == DCMT_OK)
+        rc = dcmt_rectify_dev(ctx, (const uint8_t*)in.dev, src_rows, src_cols, channels, (const int32_t*)map.dev, 1, nullptr, 0, (uint8_t*)out.dev, rows,
+                              cols, 1, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
+}
+
 int dcmt_depth_to_u16(dcmt_ctx* ctx, const float* depth, size_t drs, float scale, uint16_t* out, size_t ors, int rows, int cols)
 {
     DCMT_ON_DEVICE(ctx);

@@ -15,6 +15,7 @@
 #include "dcmt_crop.h"
 #include "dcmt_photo.h"
 #include "dcmt_plan.h"         // ranges_overlap
+#include "dcmt_rectify.h"
 #include "dcmt_tiles.h"
 
 #pragma GCC visibility push(hidden)       // internal names: none of them in libdcmt_hip.so's dynamic symbol table
@@ -547,6 +548,78 @@ inline U16Plan plan_depth_to_u16(size_t px, uintptr_t depth, uintptr_t out)
     p.status = kOk;
     p.count = (px + kU16SegPx - 1) / kU16SegPx;
     p.aligned = depth % 16 == 0 && out % 16 == 0;
+    return p;
+}
+
+// ---- dcmt_rectify_map_dev, dcmt_rectify_dev ------------------------------------------------------------------------------
+// The map: one kernel, a lane per element, grid (ceil(rows * cols / kRectifyThreads), n_maps).  The remap: ONE launch of k_rectify
+// (dcmt_kernels_rectify.h), grid (tiles, groups, chunks).  Without an index table a group is a map and the frames that use it
+// (f % n_maps), so that a workgroup reads its tile of the map once for all of them: min(n_maps, batch) groups, and the frames of a
+// group are split into `chunks` runs of per_chunk while the call has fewer than kRectifyTargetWgs workgroups (one map and a large
+// batch would otherwise be one round of tiles, each looping over the whole batch).  With an index table a group is a frame: nothing
+// is known about the table's contents here, and the bytes are the same.  The route, LDS or gather, is the kernel's, per tile.  The
+// checks on the buffers are here as well, tested without a device.
+struct RectifyMapPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, n_maps outside 1..65535, a map that overlaps the table
+    unsigned grid_x, grid_y;
+    size_t map_bytes;
+};
+
+// rows, cols >= 1 and within the context's limits (rows * cols <= 0x1ffffff0)
+inline RectifyMapPlan plan_rectify_map(int rows, int cols, int n_maps, uintptr_t table, uintptr_t map)
+{
+    RectifyMapPlan p = {kInvalid, 0, 0, 0};
+    if (!table || !map || n_maps < 1 || n_maps > 65535 || table % 8 != 0 || map % 8 != 0) return p;
+    const size_t n = (size_t)rows * (size_t)cols;
+    p.map_bytes = 8 * n * (size_t)n_maps;
+    if (ranges_overlap(map, p.map_bytes, table, (size_t)176 * (size_t)n_maps)) return p;
+    p.status = kOk;
+    p.grid_x = (unsigned)((n + kRectifyThreads - 1) / kRectifyThreads);
+    p.grid_y = (unsigned)n_maps;
+    return p;
+}
+
+struct RectifyPlan {
+    int status;                      // kInvalid: see dcmt.h
+    bool indexed;                    // a group is a frame and its map comes from the table
+    uint32_t tiles_x, per_chunk;     // kernel arguments: tiles per tile row, frames of a group per chunk
+    unsigned grid_x, grid_y, grid_z; // (tiles, groups, chunks)
+    size_t src_bytes, dst_bytes, map_bytes;
+};
+
+// rows, cols, batch >= 1 and within the context's limits (batch <= 65535)
+inline RectifyPlan plan_rectify(int src_rows, int src_cols, int channels, int rows, int cols, int batch, int n_maps, uint32_t flags, uintptr_t src,
+                                uintptr_t map, uintptr_t index, uintptr_t dst)
+{
+    RectifyPlan p = {kInvalid, false, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!src || !map || !dst || (channels != 1 && channels != 3) || n_maps < 1 || (flags & ~1u) != 0) return p;
+    if (src_rows < 1 || src_cols < 1 || src_rows > kRectifyMaxSrcSide || src_cols > kRectifyMaxSrcSide) return p;
+    if (map % 8 != 0 || index % 4 != 0) return p;
+    const size_t n = (size_t)rows * (size_t)cols;
+    if ((size_t)n_maps > SIZE_MAX / 8 / n) return p;
+    p.src_bytes = (size_t)batch * (size_t)src_rows * (size_t)src_cols * (size_t)channels;
+    p.dst_bytes = (size_t)batch * n * (size_t)channels;
+    p.map_bytes = 8 * n * (size_t)n_maps;
+    if (ranges_overlap(dst, p.dst_bytes, src, p.src_bytes) || ranges_overlap(dst, p.dst_bytes, map, p.map_bytes) ||
+        (index && ranges_overlap(dst, p.dst_bytes, index, sizeof(int32_t) * (size_t)batch)))
+        return p;
+    p.status = kOk;
+    p.indexed = index != 0;
+    p.tiles_x = ((uint32_t)cols + kRectifyTileW - 1) / kRectifyTileW;
+    const uint32_t tiles_y = ((uint32_t)rows + kRectifyTileH - 1) / kRectifyTileH;
+    p.grid_x = p.tiles_x * tiles_y;
+    if (p.indexed) {
+        p.grid_y = (unsigned)batch; p.grid_z = 1; p.per_chunk = 1;
+        return p;
+    }
+    const uint32_t groups = (uint32_t)(n_maps < batch ? n_maps : batch);
+    const uint32_t frames = ((uint32_t)batch + groups - 1) / groups;          // of the largest group: map 0's
+    const size_t wgs = (size_t)p.grid_x * groups;
+    uint32_t chunks = wgs >= kRectifyTargetWgs ? 1u : (uint32_t)((kRectifyTargetWgs + wgs - 1) / wgs);
+    if (chunks > frames) chunks = frames;
+    p.per_chunk = (frames + chunks - 1) / chunks;
+    p.grid_y = groups;
+    p.grid_z = (frames + p.per_chunk - 1) / p.per_chunk;
     return p;
 }
 

@@ -806,6 +806,81 @@ int dcmt_depth_to_u16_dev(dcmt_ctx *ctx, const float *d_depth, float scale /* 25
 int dcmt_depth_to_u16(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, float scale,
                       uint16_t *out, size_t out_row_stride, int rows, int cols);
 
+/* ---- in front of the stereo calls: undistortion and rectification of camera frames ---------------------- */
+
+/* Every stereo call of this header takes a RECTIFIED pair.  The reference's stereo-lidar main carries the step that makes one as its
+ * rectify() (DC_stereo_lidar/main_sl.cpp:1350-1381, commented out there): cv::initUndistortRectifyMap on each camera's K, D, R, P,
+ * then cv::remap(..., cv::INTER_LINEAR).  KITTI's unsynced+unrectified recordings and a rig of one's own deliver distorted frames
+ * with exactly K_0x, D_0x (five coefficients), R_rect_0x and P_rect_0x (calib_cam_to_cam.txt).  Two device calls: the map of a
+ * calibration, computed once, and the remap of a batch through it, in front of dcmt_crop_frames_dev and dcmt_bgr_convert_dev.
+ * cv::stereoRectify itself is not here (the caller brings R and P), nor the rational or thin-prism models, 16-bit or f32 images, or a
+ * nearest-neighbour remap of depth.  Sources of one call have ONE size: for ragged sources crop first and shift cx, cy by the
+ * window's origin.
+ *
+ * The definition below is OURS, as with BGR->Lab and the bilateral filter: it is stated here, restated in numpy
+ * (tests/rectify_restatement.py) and bit-exact from there on -- stated, never compared with an executing OpenCV.
+ *
+ * RECORD: dcmt_rectify_calib, 22 doubles: the distorted camera fx fy cx cy; k1 k2 p1 p2 k3; R[9] row-major, the rectifying rotation,
+ * taken as orthonormal and not checked; the new camera fxp fyp cxp cyp (P_rect's left 3x3).
+ *
+ * MAP: for destination pixel (u, v), in f64, every operation rounded once, in exactly this order (no contraction):
+ *     x  = (u - cxp) / fxp                 y  = (v - cyp) / fyp
+ *     X  = (R[0]*x + R[3]*y) + R[6]        Y  = (R[1]*x + R[4]*y) + R[7]        W = (R[2]*x + R[5]*y) + R[8]     (R^T (x, y, 1))
+ *     xn = X / W     yn = Y / W            x2 = xn*xn    y2 = yn*yn    r2 = x2 + y2    xy2 = (2*xn)*yn
+ *     kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *     xd = (xn*kr + p1*xy2) + p2*(r2 + 2*x2)
+ *     yd = (yn*kr + p1*(r2 + 2*y2)) + p2*xy2
+ *     mx = fx*xd + cx                      my = fy*yd + cy
+ *     sx = rint(mx * 32)   sy = rint(my * 32)      ties to even: 1/32-pixel fixed point (OpenCV's INTER_BITS = 5)
+ * The map element is int32 (sx, sy), 8 bytes; the map is [n_maps][rows][cols][2].  OUTSIDE is decided on the bit patterns of mx*32
+ * and my*32 (the library is built with -ffinite-math-only): if either is NaN or +-Inf or has magnitude >= 2^30, BOTH coordinates of
+ * the element are INT32_MIN.  A record is tested on its bits too, once per wave, as the calibration tables are: any entry that is
+ * not finite, or fxp or fyp +-0, makes the whole map all-outside.
+ *
+ * REMAP: the source is 8-bit, 1 or 3 channels, every channel remapped on its own; samples outside the source are 0
+ * (BORDER_CONSTANT).  With arithmetic shifts
+ *     ix = sx >> 5   ax = sx & 31   iy = sy >> 5   ay = sy & 31
+ *     out = ( (32-ay)*((32-ax)*p(iy,ix) + ax*p(iy,ix+1)) + ay*((32-ax)*p(iy+1,ix) + ax*p(iy+1,ix+1)) + 512 ) >> 10
+ * where p(y, x) = 0 wherever y is not in [0, src_rows) or x not in [0, src_cols) -- which is where an outside element puts all
+ * four samples.  The range test stands in front of any address arithmetic: for ANY map contents the call reads no byte outside the
+ * source batch and writes none outside d_dst's.  This is OpenCV's 32 x 32 table of 15-bit bilinear weights: there 32 * wx * wy is
+ * exact (an integer below 2^15), so no table is needed and none is kept.
+ *
+ * WHICH MAP: frame f uses map d_map_index[f]; with a NULL index, map f % n_maps -- one map for a whole batch, n_maps = 2 for
+ * interleaved left and right frames, n_maps = batch for a map per frame.  An index outside 0 .. n_maps - 1 gives an all-zero frame
+ * and touches no other (the convention of the *_calib_dev calls).
+ *
+ * rows x cols and batch are bounded by the ctx limits; the SOURCE may be larger, up to 16384 a side.  d_src and d_dst may have ANY
+ * byte alignment (4-byte-aligned addresses take the wide accesses; the same bytes either way).  Two routes, bit-identical, chosen
+ * per destination tile by the kernel: the tile's source bounding box staged in LDS once per frame ("lds"), or, where that box
+ * exceeds the LDS budget (strong minification or rotation) or DCMT_RECTIFY_FORCE_GATHER asks, range-checked byte loads from global
+ * memory ("gather").  dcmt_last_path names the routes the tiles of the last dcmt_rectify_dev call took, once that call has run:
+ * "k_rectify<lds>", "k_rectify<gather>" or "k_rectify<lds+gather>".
+ * Neither call synchronises, allocates or uses ctx scratch, and nothing is carried from call to call but that probe; both may be
+ * enqueued in front of or behind any other *_dev call of the ctx on the same stream.  Table, map and index are read on the stream:
+ * earlier work on it may have written them.
+ * DCMT_E_INVALID: a null pointer (d_map_index may be NULL), channels not 1 or 3, n_maps < 1, rows x cols or batch beyond the ctx
+ * limits, a source side outside 1 .. 16384, a table or map that is not 8-byte or an index that is not 4-byte aligned, unknown flag
+ * bits, any overlap of d_dst with the source, the map or the index (there is no in-place form), or of d_map with the table. */
+typedef struct {
+    double fx, fy, cx, cy;          /* the distorted camera: K                                       */
+    double k1, k2, p1, p2, k3;      /* D, in OpenCV's order                                          */
+    double R[9];                    /* row-major rectifying rotation                                 */
+    double fxp, fyp, cxp, cyp;      /* the new camera: P_rect's left 3x3                             */
+} dcmt_rectify_calib;               /* 176 bytes; table 8-byte aligned                               */
+
+#define DCMT_RECTIFY_FORCE_GATHER 1u /* every tile takes the gather route: tests and timing          */
+
+int dcmt_rectify_map_dev(dcmt_ctx *ctx, const dcmt_rectify_calib *d_table /* [n_maps], device */, int n_maps, int rows, int cols,
+                         int32_t *d_map /* [n_maps][rows][cols][2] */, void *stream);
+int dcmt_rectify_dev(dcmt_ctx *ctx, const uint8_t *d_src /* [batch][src_rows][src_cols][channels] */, int src_rows, int src_cols,
+                     int channels, const int32_t *d_map, int n_maps, const int32_t *d_map_index /* [batch] or NULL */, uint32_t flags,
+                     uint8_t *d_dst /* [batch][rows][cols][channels] */, int rows, int cols, int batch, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); the map is computed for the call.  The same bytes as the device
+ * calls.  What dcmt_shim::undistort_rectify calls. */
+int dcmt_rectify(dcmt_ctx *ctx, const uint8_t *src, size_t src_row_stride, int src_rows, int src_cols, int channels,
+                 const dcmt_rectify_calib *calib, uint8_t *dst, size_t dst_row_stride, int rows, int cols);
+
 /* ---- photometric error maps: get_initial_error ---------------------------------------------------------- */
 
 /* get_initial_error(optimized_depth, img_left_copy, img_right_copy) (DC_stereo_lidar/main_sl.cpp:618-712, called at :1273), its data:
@@ -1084,7 +1159,10 @@ int dcmt_last_holes_after_extend(dcmt_ctx *ctx, int *out, int n);
 const char *dcmt_strerror(int status);
 int dcmt_last_hip_error(const dcmt_ctx *ctx);
 /* The kernels the last cascade call on ctx dispatched, e.g. "k_pre_p<Q16OUT> + k_fp_q" (the dispatch depends on batch size,
- * frame shape, alignment and -- for the 16-bit form -- on what earlier calls found in their frames).  Owned by ctx. */
+ * frame shape, alignment and -- for the 16-bit form -- on what earlier calls found in their frames).  Owned by ctx.  After a
+ * dcmt_rectify_dev call: the routes its tiles took, "k_rectify<lds>", "k_rectify<gather>" or "k_rectify<lds+gather>" (static
+ * strings); the kernel says which, so this copies two words back from the device and is meaningful once that call has run (plain
+ * "k_rectify" before). */
 const char *dcmt_last_path(const dcmt_ctx *ctx);
 
 /* Measurement aid (bench.py's live per-kernel split).  With timing on, the streaming path of every following *_dev call

@@ -517,6 +517,22 @@ inline void unrectify_sol_nearest(const cv::Mat& depth, cv::Mat& depth_unrect, c
     unrectify_sol_with(dcmt_reproject_depth_nearest, "unrectify_sol_nearest", depth, depth_unrect, Minv);
 }
 
+// rectify() of DC_stereo_lidar/main_sl.cpp:1350-1381 for one camera, as dcmt.h states it (dcmt_rectify): cv::initUndistortRectifyMap
+// on the record's K, D, R, P and cv::remap(..., cv::INTER_LINEAR) of `src` (CV_8UC1 or CV_8UC3) into a rows x cols `dst` of its type;
+// samples outside the source are 0.
+inline void undistort_rectify(const cv::Mat& src, cv::Mat& dst, const dcmt_rectify_calib& calib, int rows, int cols)
+{
+    if ((src.type() != CV_8UC1 && src.type() != CV_8UC3) || src.rows < 1 || src.cols < 1)
+        throw std::runtime_error("undistort_rectify: image must be CV_8UC1 or CV_8UC3");
+    if (rows < 1 || cols < 1) throw std::runtime_error("undistort_rectify: empty output");
+    cv::Mat out;
+    out.create(rows, cols, src.type());
+    raise(dcmt_rectify(thread_ctx().get(rows, cols), src.ptr<unsigned char>(), src.step[0], src.rows, src.cols, src.type() == CV_8UC3 ? 3 : 1,
+                       &calib, out.ptr<unsigned char>(), out.step[0], rows, cols),
+          "undistort_rectify");
+    dst = out;
+}
+
 }  // namespace dcmt_shim
 
 // reference: src/DC_lidar_only/img_completion.cpp:17-20.  `extr` is accepted and ignored, as there (the cascade without its
