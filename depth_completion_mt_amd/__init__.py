@@ -11,7 +11,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   slic_connectivity_max_labels, slic_enforce_connectivity, slic_display_contours,
                   slic_colour_with_cluster_means, get_initial_error, make_photo_error_params, make_sgm_params,
                   sgm_workspace_bytes, stereo_sgm, make_speckle_params, filter_speckles,
-                  RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify)
+                  RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify,
+                  PLANE_FIT_DTYPE, make_planes_params, fit_superpixel_planes, superpixel_planes_max_labels)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -22,7 +23,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "bilateral_filter5", "slic_connectivity_max_labels", "slic_enforce_connectivity",
            "slic_display_contours", "slic_colour_with_cluster_means", "get_initial_error", "make_photo_error_params",
            "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm", "make_speckle_params", "filter_speckles",
-           "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify"]
+           "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify",
+           "PLANE_FIT_DTYPE", "make_planes_params", "fit_superpixel_planes", "superpixel_planes_max_labels"]
 
 
 def __getattr__(name):

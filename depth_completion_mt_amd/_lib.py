@@ -49,6 +49,7 @@ EXPORTS = (
     "dcmt_sgm_guided_dev", "dcmt_sgm_guided", "dcmt_sgm_cost_dev", "dcmt_sgm_cost",
     "dcmt_default_speckle_params", "dcmt_filter_speckles_dev", "dcmt_filter_speckles",
     "dcmt_rectify_map_dev", "dcmt_rectify_dev", "dcmt_rectify",
+    "dcmt_default_planes_params", "dcmt_superpixel_planes_max_labels", "dcmt_superpixel_planes_dev", "dcmt_superpixel_planes",
 )
 
 
@@ -124,6 +125,18 @@ class SgmParams(ctypes.Structure):
 class SpeckleParams(ctypes.Structure):
     """Mirror of dcmt_speckle_params (include/dcmt.h)."""
     _fields_ = [("max_size", ctypes.c_int32), ("max_diff", ctypes.c_int32), ("new_val", ctypes.c_int32)]
+
+
+class PlanesParams(ctypes.Structure):
+    """Mirror of dcmt_planes_params (include/dcmt.h), 24 bytes."""
+    _fields_ = [("valid_thresh", ctypes.c_float), ("max_depth", ctypes.c_float), ("min_points", ctypes.c_int32),
+                ("min_extent", ctypes.c_int32), ("refit_tol", ctypes.c_float), ("keep_returns", ctypes.c_int32)]
+
+
+class PlaneFit(ctypes.Structure):
+    """Mirror of dcmt_plane_fit (include/dcmt.h): one label's record of dcmt_superpixel_planes_dev, 48 bytes."""
+    _fields_ = [("a", ctypes.c_double), ("b", ctypes.c_double), ("c", ctypes.c_double), ("seen", ctypes.c_uint32), ("used", ctypes.c_uint32),
+                ("wmin", ctypes.c_uint32), ("wmax", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class CropSrc(ctypes.Structure):
@@ -278,6 +291,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_rectify_map_dev.argtypes = [vp, vp, i, i, i, vp, vp]
         L.dcmt_rectify_dev.argtypes = [vp, vp, i, i, i, vp, i, vp, ctypes.c_uint32, vp, i, i, i, vp]
         L.dcmt_rectify.argtypes = [vp, vp, sz, i, i, i, vp, vp, sz, i, i]
+        L.dcmt_default_planes_params.argtypes = [vp]
+        L.dcmt_default_planes_params.restype = None
+        L.dcmt_superpixel_planes_max_labels.argtypes = [i, i, i, i]
+        L.dcmt_superpixel_planes_dev.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
+        L.dcmt_superpixel_planes.argtypes = [vp, vp, sz, vp, sz, i, i, i, vp, vp, sz, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

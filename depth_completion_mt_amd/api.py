@@ -253,7 +253,52 @@ def _speckle_kw(speckle_window, speckle_range) -> dict | None:
     return kw if make_speckle_params(**kw).max_size > 0 else None
 
 
-SGM_MAX_P2_EIGHT_PATHS = 1800       # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
+PLANE_FIT_DTYPE = np.dtype([("a", "<f8"), ("b", "<f8"), ("c", "<f8"), ("seen", "<u4"), ("used", "<u4"), ("wmin", "<u4"), ("wmax", "<u4"),
+                            ("kind", "<u4"), ("reserved", "<u4")])     # dcmt_plane_fit, 48 bytes
+PLANES_MAX_PIXELS = 1 << 21         # rows * cols of a frame dcmt_superpixel_planes_dev takes (include/dcmt.h: the bounds of its sums)
+
+
+def make_planes_params(valid_thresh: float | None = None, max_depth: float | None = None, min_points: int | None = None,
+                       min_extent: int | None = None, refit_tol: float | None = None, keep_returns: bool | None = None) -> L.PlanesParams:
+    """dcmt_planes_params: valid_thresh 0.1, max_depth 100, min_points 3, min_extent 2, refit_tol 0 (no refit), keep_returns True unless
+    overridden.  Raises ValueError on what dcmt_superpixel_planes_dev refuses of them: valid_thresh not finite or < 0.0625, max_depth
+    not finite, < valid_thresh or > 16384, min_points < 3, min_extent < 1, refit_tol outside [0, 1), keep_returns no bool."""
+    p = L.PlanesParams()
+    L.lib().dcmt_default_planes_params(ctypes.byref(p))
+    for name, v in (("valid_thresh", valid_thresh), ("max_depth", max_depth), ("refit_tol", refit_tol)):
+        if v is not None:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} = {v!r}: a finite float")
+            setattr(p, name, float(v))
+    for name, v in (("min_points", min_points), ("min_extent", min_extent)):
+        if v is not None:
+            if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} = {v!r} is not an int32")
+            setattr(p, name, int(v))
+    if keep_returns is not None:
+        if keep_returns not in (0, 1, False, True):
+            raise ValueError(f"keep_returns = {keep_returns!r}: a bool")
+        p.keep_returns = int(keep_returns)
+    if not p.valid_thresh >= 0.0625:
+        raise ValueError(f"valid_thresh = {p.valid_thresh}: >= 0.0625 (the codes stay at or below 2^20)")
+    if not p.valid_thresh <= p.max_depth <= 16384.0:
+        raise ValueError(f"max_depth = {p.max_depth}: valid_thresh .. 16384")
+    if p.min_points < 3:
+        raise ValueError(f"min_points = {p.min_points}: >= 3")
+    if p.min_extent < 1:
+        raise ValueError(f"min_extent = {p.min_extent}: >= 1")
+    if not 0.0 <= p.refit_tol < 1.0:
+        raise ValueError(f"refit_tol = {p.refit_tol}: in [0, 1)")
+    return p
+
+
+def superpixel_planes_max_labels(max_rows: int, max_cols: int, max_batch: int, batch: int = 1) -> int:
+    """The largest n_labels superpixel_planes_dev takes for `batch` frames on a Context(device, max_rows, max_cols, max_batch):
+    96 bytes of moments a label and frame in one of the context's scratch planes (dcmt_superpixel_planes_max_labels)."""
+    return int(L.lib().dcmt_superpixel_planes_max_labels(int(max_rows), int(max_cols), int(max_batch), int(batch)))
+
+
+SGM_MAX_P2_EIGHT_PATHS = 1800      # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
 
 
 def _check_sgm_paths(paths, p: L.SgmParams) -> int:
@@ -1054,6 +1099,50 @@ class Context:
         _check(st, "dcmt_filter_speckles")
         return (out, int(n.value)) if z is None else (out, z, int(n.value))
 
+    # ---- per-superpixel plane fitting of sparse depth (dcmt_superpixel_planes*) ----------------
+    def superpixel_planes_dev(self, d_depth, d_labels, n_labels: int, d_out=None, d_fits=None, stream: int | None = None, **kw):
+        """One least-squares plane of inverse depth per superpixel through the returns that fall in it, painted over the label's
+        pixels (dcmt_superpixel_planes_dev, as include/dcmt.h states it), without synchronising: between slic_labels_dev /
+        slic_connectivity_dev and complete_dev, which then fills only what the planes left open.  d_depth: f32 CUDA tensor
+        [batch][rows][cols] (or [rows][cols]), metres, 0 = no return; d_labels: int32 of the same shape; d_out: where the result goes
+        (may be d_depth itself: in place), allocated where not given.  d_fits: None: not wanted; True: created; or a uint8 CUDA tensor
+        of batch * n_labels * 48 bytes (PLANE_FIT_DTYPE records once on the host).  kw: the fields of make_planes_params.  Returns
+        d_out, or (d_out, d_fits) where fits were asked for.  Outputs that are not given are allocated on the stream the call
+        enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32) and _is_dev(d_labels, torch.int32)
+        b, r, c = _brc(d_depth)
+        assert d_labels.numel() == b * r * c
+        p = make_planes_params(**kw)
+        want_fits = d_fits is not None
+        with _on_stream(stream, d_depth):
+            if d_out is None:
+                d_out = torch.empty(tuple(d_depth.shape), dtype=torch.float32, device=d_depth.device)
+            if d_fits is True:
+                d_fits = torch.full((b, max(int(n_labels), 0), PLANE_FIT_DTYPE.itemsize), 0xA5, dtype=torch.uint8, device=d_depth.device)
+        assert _is_dev(d_out, torch.float32) and d_out.numel() == b * r * c
+        assert d_fits is None or (_is_dev(d_fits, torch.uint8) and d_fits.numel() == b * int(n_labels) * PLANE_FIT_DTYPE.itemsize)
+        st = L.lib().dcmt_superpixel_planes_dev(self._h, d_depth.data_ptr(), d_labels.data_ptr(), r, c, b, int(n_labels), ctypes.byref(p),
+                                                d_out.data_ptr(), d_fits.data_ptr() if want_fits else None, _stream(stream, d_depth))
+        _check(st, "dcmt_superpixel_planes_dev")
+        return (d_out, d_fits) if want_fits else d_out
+
+    def superpixel_planes(self, depth: np.ndarray, labels: np.ndarray, n_labels: int, **kw):
+        """One frame of host memory (dcmt_superpixel_planes, synchronous; any row stride): (the painted f32 plane, the fits as a
+        PLANE_FIT_DTYPE array [n_labels]).  Both are new arrays; the arguments are not modified."""
+        z = np.asarray(depth, dtype=np.float32)
+        a = np.asarray(labels, dtype=np.int32)
+        assert z.ndim == 2 and a.shape == z.shape
+        z = z if z.strides[1] == 4 else np.ascontiguousarray(z)
+        a = a if a.strides[1] == 4 else np.ascontiguousarray(a)
+        out = np.empty(z.shape, dtype=np.float32)
+        fits = np.zeros(max(int(n_labels), 0), dtype=PLANE_FIT_DTYPE)
+        p = make_planes_params(**kw)
+        st = L.lib().dcmt_superpixel_planes(self._h, z.ctypes.data, z.strides[0], a.ctypes.data, a.strides[0], z.shape[0], z.shape[1], int(n_labels),
+                                            ctypes.byref(p), out.ctypes.data, out.strides[0], fits.ctypes.data)
+        _check(st, "dcmt_superpixel_planes")
+        return out, fits
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1614,6 +1703,14 @@ def filter_speckles(disp16, depth=None, **params):
     sixteenths), new_val (-16)."""
     d = np.asarray(disp16, dtype=np.int16)
     return _ctx_for(d.shape[0], d.shape[1], 1).filter_speckles(d, depth, **params)
+
+
+def fit_superpixel_planes(depth, labels, n_labels: int, **params):
+    """One plane of inverse depth per superpixel of one host frame (dcmt_superpixel_planes, as include/dcmt.h states it): depth f32
+    [rows][cols] in metres with 0 = no return, labels int32 [rows][cols] -> (the painted plane, the fits [n_labels] as
+    PLANE_FIT_DTYPE).  params: the fields of make_planes_params."""
+    z = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).superpixel_planes(z, labels, n_labels, **params)
 
 
 def depth_to_u16(depth, scale: float = 256.0):

@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h),
 // dcmt_photo_error_dev and dcmt_photo_error_calib_dev (dcmt_kernels_photo.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
 // are in dcmt_host.hip.
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "dcmt_kernels_speckle.h"
 #include "dcmt_kernels_contour.h"
 #include "dcmt_kernels_photo.h"
+#include "dcmt_kernels_planes.h"
 
 using namespace dcmt;
 
@@ -556,6 +557,73 @@ int dcmt_slic_cluster_means_dev(dcmt_ctx* ctx, const int32_t* d_labels, int rows
     hipLaunchKernelGGL(k_means_clear, dim3(pl.clear_grid), dim3(256), 0, st, sums, pl.words);
     hipLaunchKernelGGL(k_means_sum, dim3(pl.sum_grid, batch), dim3(256), 0, st, d_labels, d_bgr, r, c, pl.tiles_x, nl, sums);
     hipLaunchKernelGGL(k_means_paint, dim3(pl.px_x, batch), dim3(256), 0, st, d_labels, pl.n, nl, sums, d_bgr);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- per-superpixel plane fitting of sparse depth (dcmt_kernels_planes.h) ----------------------------------------------------------
+static uint32_t planes_bits(const float* v)
+{
+    uint32_t b;
+    std::memcpy(&b, v, sizeof b);                     // the bits as they lie in the struct: nothing the compiler may assume finite
+    return b;
+}
+
+extern "C" {
+
+void dcmt_default_planes_params(dcmt_planes_params* p)
+{
+    if (!p) return;
+    p->valid_thresh = 0.1f;
+    p->max_depth = 100.0f;
+    p->min_points = 3;
+    p->min_extent = 2;
+    p->refit_tol = 0.0f;
+    p->keep_returns = 1;
+}
+
+int dcmt_superpixel_planes_max_labels(int max_rows, int max_cols, int max_batch, int batch)
+{
+    if (max_rows < 1 || max_cols < 1 || max_batch < 1 || batch < 1 || batch > max_batch) return 0;
+    return plan::planes_max_labels(sizeof(float) * (size_t)max_rows * (size_t)max_cols * (size_t)max_batch, batch);
+}
+
+// The launches plan_superpixel_planes names: the moment records on pp[0], the fits in the caller's d_fits or, without one, on pp[1]
+// (scratch every completion call rewrites before it reads it).  None of the context's carried state is read or written, and
+// nothing is allocated.
+int dcmt_superpixel_planes_dev(dcmt_ctx* ctx, const float* d_depth, const int32_t* d_labels, int rows, int cols, int batch, int n_labels,
+                               const dcmt_planes_params* params, float* d_out, dcmt_plane_fit* d_fits, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const uint32_t lo = planes_bits(&params->valid_thresh), hi = planes_bits(&params->max_depth), tb = planes_bits(&params->refit_tol);
+    const bool ok = plan::planes_params_ok(lo, hi, params->min_points, params->min_extent, tb, params->keep_returns);
+    const size_t plane_bytes = sizeof(float) * ctx->frame_elems * (size_t)ctx->max_batch;
+    const plan::PlanesPlan pl = plan::plan_superpixel_planes(rows, cols, batch, n_labels, plane_bytes, ok, ok && (tb << 1) != 0u, (uintptr_t)d_depth,
+                                                             (uintptr_t)d_labels, (uintptr_t)d_out, (uintptr_t)d_fits);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* mom = reinterpret_cast<unsigned long long*>(ctx->pp[0].p);
+    dcmt_plane_fit* fits = d_fits ? d_fits : reinterpret_cast<dcmt_plane_fit*>(ctx->pp[1].p);
+    const uint32_t* depth = reinterpret_cast<const uint32_t*>(d_depth);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, nl = (uint32_t)n_labels;
+    const uint32_t mp = (uint32_t)params->min_points, me = (uint32_t)params->min_extent;
+    const double tol = (double)params->refit_tol;
+    hipLaunchKernelGGL(k_planes_clear, dim3(pl.clear_grid), dim3(256), 0, st, reinterpret_cast<uint32_t*>(mom), pl.words);
+    hipLaunchKernelGGL(k_planes_sum<false>, dim3(pl.sum_grid, batch), dim3(256), 0, st, depth, d_labels, r, c, pl.tiles_x, nl, lo, hi, fits, tol, mom);
+    hipLaunchKernelGGL(k_planes_solve<false>, dim3(pl.solve_grid), dim3(256), 0, st, mom, pl.records, mp, me, fits);
+    if (pl.refit) {
+        hipLaunchKernelGGL(k_planes_clear, dim3(pl.clear_grid), dim3(256), 0, st, reinterpret_cast<uint32_t*>(mom), pl.words);
+        hipLaunchKernelGGL(k_planes_sum<true>, dim3(pl.sum_grid, batch), dim3(256), 0, st, depth, d_labels, r, c, pl.tiles_x, nl, lo, hi, fits, tol, mom);
+        hipLaunchKernelGGL(k_planes_solve<true>, dim3(pl.solve_grid), dim3(256), 0, st, mom, pl.records, mp, me, fits);
+    }
+    uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
+    if (pl.vec == 4)
+        hipLaunchKernelGGL(k_planes_paint<4>, dim3(pl.paint_x, batch), dim3(256), 0, st, depth, d_labels, pl.n, c, nl, lo, hi, params->keep_returns, fits, out);
+    else
+        hipLaunchKernelGGL(k_planes_paint<1>, dim3(pl.paint_x, batch), dim3(256), 0, st, depth, d_labels, pl.n, c, nl, lo, hi, params->keep_returns, fits, out);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

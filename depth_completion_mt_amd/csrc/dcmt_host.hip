@@ -347,6 +347,19 @@ int dcmt_slic_cluster_means(dcmt_ctx* ctx, const int32_t* labels, size_t lrs, in
     return rc == DCMT_OK ? fetch(ctx, {&img, &s}) : rc;
 }
 
+int dcmt_superpixel_planes(dcmt_ctx* ctx, const float* depth, size_t drs, const int32_t* labels, size_t lrs, int rows, int cols, int n_labels,
+                           const dcmt_planes_params* params, float* out, size_t ors, dcmt_plane_fit* fits)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !labels || !out || !params || n_labels < 1 || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    if (n_labels > dcmt_superpixel_planes_max_labels(ctx->max_rows, ctx->max_cols, ctx->max_batch, 1)) return DCMT_E_INVALID;   // the *_dev call's bound, before anything is staged
+    const size_t rb = sizeof(float) * (size_t)cols;
+    Plane z(depth, drs, rb, rows), l(labels, lrs, rb, rows), o(out, ors, rb, rows), f(fits, sizeof(dcmt_plane_fit) * (size_t)n_labels);
+    int rc = stage(ctx, {&z, &l}, {&o, &f});
+    if (rc == DCMT_OK) rc = dcmt_superpixel_planes_dev(ctx, (const float*)z.dev, (const int32_t*)l.dev, rows, cols, 1, n_labels, params, (float*)o.dev, (dcmt_plane_fit*)f.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &f}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -15,6 +15,7 @@
 #include "dcmt_crop.h"
 #include "dcmt_photo.h"
 #include "dcmt_plan.h"         // ranges_overlap
+#include "dcmt_planes.h"
 #include "dcmt_rectify.h"
 #include "dcmt_tiles.h"
 
@@ -406,6 +407,82 @@ inline MeansPlan plan_cluster_means(int rows, int cols, int batch, int n_labels,
     p.px_x = (p.n + 255) / 256;
     const size_t blocks = (p.words + 255) / 256;
     p.clear_grid = blocks > 4096 ? 4096u : (unsigned)blocks;
+    return p;
+}
+
+// ---- dcmt_superpixel_planes_dev -------------------------------------------------------------------------------------------
+// One plane of inverse depth per superpixel (dcmt_kernels_planes.h): clear, sum, solve, paint, with clear, sum and solve a second
+// time in front of the paint where a refit is asked for; the grids depend on the shape and n_labels alone.  The moment records
+// borrow pp[0], the fits pp[1] where the caller passes none.  The checks on the arguments are here as well, tested without a
+// device: out may BE depth (k_planes_paint is the only writer of out, and a lane reads its pixels before it writes them), every
+// other overlap is refused.  The float parameters come as their bits: the library is built with -ffinite-math-only.
+
+// the largest n_labels a call with `batch` frames may name: batch * n_labels * 96 bytes of moment records fit in one borrowed plane
+// of plane_bytes (4 * max_batch * max_rows * max_cols)
+inline int planes_max_labels(size_t plane_bytes, int batch)
+{
+    const size_t m = plane_bytes / (8 * (size_t)kPlanesMomWords) / (size_t)(batch < 1 ? 1 : batch);
+    return m > 0x00ffffff ? 0x00ffffff : (int)m;
+}
+
+// what dcmt_planes_params may hold (dcmt.h); positive finite floats order as their bits do
+inline bool planes_params_ok(uint32_t valid_thresh_bits, uint32_t max_depth_bits, int64_t min_points, int64_t min_extent, uint32_t refit_tol_bits,
+                             int64_t keep_returns)
+{
+    if (valid_thresh_bits < kPlanesMinThreshBits || valid_thresh_bits >= 0x7f800000u) return false;
+    if (max_depth_bits < valid_thresh_bits || max_depth_bits > kPlanesMaxDepthBits) return false;
+    if (min_points < 3 || min_points > 0x7fffffff || min_extent < 1 || min_extent > 0x7fffffff) return false;
+    if (refit_tol_bits >= 0x3f800000u && refit_tol_bits != 0x80000000u) return false;      // [0, 1), -0.0 included; NaN, inf, negatives: above 1.0f's bits
+    return keep_returns == 0 || keep_returns == 1;
+}
+
+struct PlanesPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, n_labels < 1 or beyond planes_max_labels, more than
+                                     // kPlanesMaxPixels pixels a frame, bad parameters, buffers that overlap
+    uint32_t n;                      // pixels per frame
+    uint32_t tiles_x, tiles_y;
+    unsigned sum_grid;               // k_planes_sum: (sum_grid, batch)
+    int vec;                         // k_planes_paint<vec>: 4 where a frame is a multiple of 4 pixels and depth, labels and out are 16-byte aligned, else 1
+    unsigned paint_x;                // its grid: (paint_x, batch)
+    size_t records;                  // batch * n_labels: the lanes of k_planes_solve
+    unsigned solve_grid;
+    size_t words;                    // the moment records as 32-bit words: records * 24
+    unsigned clear_grid;             // k_planes_clear
+    bool refit;                      // refit_tol > 0: clear, sum<true>, solve<true> in front of the paint
+    int launches;                    // 4 or 7
+    size_t scratch0, scratch1;       // bytes of pp[0] and of pp[1] this call uses (scratch1 = 0 where the caller gives d_fits)
+};
+
+// rows, cols, batch >= 1 and within the context's limits; params_ok: planes_params_ok of the call's parameters
+inline PlanesPlan plan_superpixel_planes(int rows, int cols, int batch, int n_labels, size_t plane_bytes, bool params_ok, bool refit,
+                                         uintptr_t depth, uintptr_t labels, uintptr_t out, uintptr_t fits)
+{
+    PlanesPlan p = {};
+    p.status = kInvalid;
+    if (!depth || !labels || !out || depth % 4 != 0 || labels % 4 != 0 || out % 4 != 0 || fits % 8 != 0 || !params_ok) return p;
+    if (n_labels < 1 || n_labels > planes_max_labels(plane_bytes, batch)) return p;
+    if ((uint64_t)rows * (uint64_t)cols > kPlanesMaxPixels) return p;
+    const size_t px = 4 * (size_t)batch * (size_t)rows * (size_t)cols;
+    p.records = (size_t)batch * (size_t)n_labels;
+    const size_t fb = p.records * (size_t)kPlanesFitBytes;
+    if (out != depth && ranges_overlap(depth, px, out, px)) return p;
+    if (ranges_overlap(labels, px, depth, px) || ranges_overlap(labels, px, out, px)) return p;
+    if (fits && (ranges_overlap(fits, fb, depth, px) || ranges_overlap(fits, fb, labels, px) || ranges_overlap(fits, fb, out, px))) return p;
+    p.status = kOk;
+    p.n = (uint32_t)rows * (uint32_t)cols;
+    p.tiles_x = ((uint32_t)cols + kPlanesTile - 1) / kPlanesTile;
+    p.tiles_y = ((uint32_t)rows + kPlanesTile - 1) / kPlanesTile;
+    p.sum_grid = p.tiles_x * p.tiles_y;
+    p.vec = p.n % 4 == 0 && depth % 16 == 0 && labels % 16 == 0 && out % 16 == 0 ? 4 : 1;
+    p.paint_x = (p.n / (uint32_t)p.vec + 255) / 256;
+    p.solve_grid = (unsigned)((p.records + 255) / 256);
+    p.words = p.records * 2 * (size_t)kPlanesMomWords;
+    const size_t blocks = (p.words + 255) / 256;
+    p.clear_grid = blocks > 4096 ? 4096u : (unsigned)blocks;
+    p.refit = refit;
+    p.launches = refit ? 7 : 4;
+    p.scratch0 = 4 * p.words;
+    p.scratch1 = fits ? 0 : fb;
     return p;
 }
 

@@ -399,6 +399,91 @@ int dcmt_slic_contours(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, 
 int dcmt_slic_cluster_means(dcmt_ctx *ctx, const int32_t *labels, size_t row_stride, int rows, int cols, int n_labels, uint8_t *bgr,
                             size_t bgr_row_stride, int32_t *sums /* [n_labels][4] or NULL */);
 
+/* ---- per-superpixel plane fitting of sparse depth ------------------------------------------------------ */
+
+/* Image-guided completion of a sparse depth plane from a label plane (dcmt_slic_labels_dev, dcmt_slic_connectivity_dev): one
+ * superpixel is, to first order, one planar facet, and a planar facet seen by a pinhole camera is AFFINE IN INVERSE DEPTH over the
+ * pixel coordinates.  So every label gets one least-squares plane of inverse depth through the returns that fall in it, and the
+ * label's pixels are painted with it.  A label without a return stays empty: nothing is invented.  Not in the reference; stated
+ * here to the last bit.  An opt-in between the labels and dcmt_complete_*_dev, which then fills only what the planes left open.
+ * u is the column, v the row.  Per frame:
+ *
+ * RETURN.  A pixel is a return of label k iff its label is k with 0 <= k < n_labels and its depth z is a finite float with
+ *   valid_thresh <= z <= max_depth, decided on the bit pattern: NaN, +-inf, negatives and -0.0 are no returns.
+ * CODE.  w = (uint32) rne(W / z): one correctly rounded f32 division with W = 65536.0f, then round to nearest even.  With
+ *   valid_thresh >= 0.0625 and max_depth <= 16384 (both enforced) 4 <= w <= 2^20.
+ * MOMENTS.  Per label, over its returns, as exact integers: n, Su, Sv, Suu, Suv, Svv, Sw, Suw, Svw (the sums of 1, u, v, u u, u v,
+ *   v v, w, u w, v w) and the minima and maxima of u, v and w.  Integer adds commute: nothing below depends on the batch size, the
+ *   frame's position in the batch, the launch geometry or the run.
+ *   Bounds.  rows * cols <= 2^21 is enforced.  Then n <= 2^21 and, with u < cols, v < rows: Suu <= rows cols cols^2 < 2^63 (the
+ *   largest of the sums: a frame of one row), Suw, Svw < 2^21 2^21 2^20 = 2^62: the sums are kept in unsigned 64-bit words.  The
+ *   centred terms below are formed in 128-bit integers: |n Suw| and |Su Sw| < 2^21 2^62 = 2^83; Cuu <= n^2 (cols-1)^2 / 4 and Cvv
+ *   likewise, so Cuu Cvv <= n^4 ((cols-1)(rows-1))^2 / 16 < 2^84 2^42 / 16 = 2^122, and Cuv^2 <= Cuu Cvv (Cauchy-Schwarz): the
+ *   determinant is exact in a signed 128-bit integer, and "collinear" is an exact decision.
+ * FIT.  With a label's moments, in this order:
+ *   n = 0: kind NONE.
+ *   wbar = f64(Sw) / f64(n)                                  (every f64 operation here rounded once, no contraction; f64(i) is the
+ *                                                             integer i rounded to the nearest double, ties to even)
+ *   Exact integers: Cuu = n Suu - Su Su, Cuv = n Suv - Su Sv, Cvv = n Svv - Sv Sv, Cuw = n Suw - Su Sw, Cvw = n Svw - Sv Sw,
+ *   D = Cuu Cvv - Cuv Cuv: n^2 times the centred normal matrix, right-hand side and determinant.  Centring is what makes this
+ *   well conditioned at u ~ 1200.
+ *   kind PLANE iff n >= min_points and umax - umin + 1 >= min_extent and vmax - vmin + 1 >= min_extent and D > 0; then
+ *     a = (f64(Cuw) f64(Cvv) - f64(Cvw) f64(Cuv)) / f64(D)
+ *     b = (f64(Cvw) f64(Cuu) - f64(Cuw) f64(Cuv)) / f64(D)
+ *     c = (wbar - a (f64(Su) / f64(n))) - b (f64(Sv) / f64(n))
+ *   otherwise kind CONSTANT: a = b = +0.0, c = wbar.
+ *   The fit at a pixel is w^(u, v) = (a f64(u) + b f64(v)) + c; for a constant that is c.
+ * TRIMMED REFIT, where refit_tol > 0, for the labels whose first fit is a plane: the moments are accumulated a second time over only
+ *   the returns with |f64(w) - w^| <= f64(refit_tol) w^ (w^ the first fit at that pixel, not clamped; the product rounded once) and
+ *   fitted by the same rules.  If that fit is a plane it replaces the first, with the trimmed set's count, wmin and wmax; if not,
+ *   the first fit stands.  One refit, not an iteration.
+ * OUTPUT.  A pixel whose label is outside [0, n_labels) or of kind none: +0.0f, whatever its depth (it is no return of any label).
+ *   A return, with keep_returns: its own bits.  Every other pixel of a label with a fit, and a return without keep_returns:
+ *   (float)(65536.0 / clamp(w^(u, v), f64(wmin), f64(wmax))), an f64 division rounded to f32; wmin and wmax are the extremes of the
+ *   codes of the returns the final fit used, so a plane never leaves its label's measured range.
+ * d_fits, or NULL: [batch][n_labels] records dcmt_plane_fit of 48 bytes; a label of kind none (one that owns no pixel, or no return)
+ *   gets zeros.  seen: the label's returns; used: those the final fit used.
+ *
+ * DEVICE pointers, stream-ordered; never synchronises, never allocates; four launches (clear, sum, solve, paint) and seven with a
+ * refit (clear, sum and solve a second time), whatever the data.  d_out may BE d_depth: the moments are complete before a pixel is
+ * written, and the result has the bits of an out-of-place call.  Scratch: the two planes dcmt_create allocates (the ones
+ * dcmt_slic_cluster_means_dev borrows): the moment records, 96 bytes a label, in the first; the fits in the second where d_fits is
+ * NULL.  Of the context's carried state it touches none: same standing behind other *_dev calls as dcmt_slic_cluster_means_dev.
+ * DCMT_E_INVALID, nothing written: a null ctx, depth, labels, output or params; sizes beyond the context's limits; rows * cols > 2^21;
+ * d_depth, d_labels or d_out not 4-byte aligned, d_fits not 8-byte aligned; any overlap among the buffers other than d_out == d_depth
+ * exactly; n_labels < 1 or batch * n_labels * 96 bytes more than ONE scratch plane holds, that is n_labels >
+ * (max_rows * max_cols * max_batch) / (24 * batch) of dcmt_create's arguments, with d_fits given as well; valid_thresh not finite or
+ * < 0.0625; max_depth not finite, < valid_thresh or > 16384; min_points < 3; min_extent < 1; refit_tol not finite, < 0 or >= 1;
+ * keep_returns neither 0 nor 1. */
+typedef struct {
+    float   valid_thresh;   /* 0.1   the smallest depth that is a return, metres; >= 0.0625                        */
+    float   max_depth;      /* 100   the largest; <= 16384                                                         */
+    int32_t min_points;     /* 3     returns a plane needs; >= 3                                                   */
+    int32_t min_extent;     /* 2     columns and rows the returns of a plane must span, in pixels; >= 1            */
+    float   refit_tol;      /* 0     0: no refit; else the relative tolerance of the trimmed refit, in (0, 1)      */
+    int32_t keep_returns;   /* 1     1: a return keeps its bits; 0: it is painted like its label's other pixels    */
+} dcmt_planes_params;       /* 24 bytes */
+typedef struct {
+    double   a, b, c;       /* w^ = a u + b v + c, in codes (65536 / metres)                                       */
+    uint32_t seen, used;    /* the label's returns; those of the final fit                                         */
+    uint32_t wmin, wmax;    /* the extremes of the codes the final fit used                                        */
+    uint32_t kind;          /* 0 none, 1 constant, 2 plane                                                         */
+    uint32_t reserved;      /* 0                                                                                   */
+} dcmt_plane_fit;           /* 48 bytes */
+#define DCMT_PLANES_NONE 0
+#define DCMT_PLANES_CONSTANT 1
+#define DCMT_PLANES_PLANE 2
+void dcmt_default_planes_params(dcmt_planes_params *p);
+int dcmt_superpixel_planes_max_labels(int max_rows, int max_cols, int max_batch, int batch);
+int dcmt_superpixel_planes_dev(dcmt_ctx *ctx, const float *d_depth, const int32_t *d_labels, int rows, int cols, int batch, int n_labels,
+                               const dcmt_planes_params *params, float *d_out /* may be d_depth */,
+                               dcmt_plane_fit *d_fits /* [batch][n_labels] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES, >= 4 * cols); out may be depth; fits [n_labels] or NULL.  The same
+ * bits as the device call.  What dcmt_shim::fit_superpixel_planes calls. */
+int dcmt_superpixel_planes(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, const int32_t *labels, size_t labels_row_stride,
+                           int rows, int cols, int n_labels, const dcmt_planes_params *params, float *out, size_t out_row_stride,
+                           dcmt_plane_fit *fits);
+
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 
 /* What DC_stereo_lidar/main_sl.cpp does with the dense depth (:1165-1246): depth -> disparity (get_initial_disparity

@@ -486,6 +486,33 @@ inline void depth_to_cloud(const cv::Mat& depth, const cv::Mat& bgr, std::vector
     out.resize((size_t)n);
 }
 
+// One least-squares plane of inverse depth per superpixel through the returns that fall in it, as dcmt.h states it
+// (dcmt_superpixel_planes): `clusters` [col][row] as Slic::clusters, n_labels = slic.centers.size() or the count
+// slic_enforce_connectivity returns, sparse_r_img CV_32FC1 in metres with 0 = no return.  planes_img is overwritten with a fresh
+// CV_32FC1 image: the returns, the planes over their labels, 0 where a label holds no return -- what interpolate_with_labels then
+// takes as its sparse image.  params == nullptr: dcmt_default_planes_params; fits, where given, receives the n_labels records.
+inline void fit_superpixel_planes(const std::vector<std::vector<int> >& clusters, int n_labels, const cv::Mat& sparse_r_img, cv::Mat& planes_img,
+                                  const dcmt_planes_params* params = nullptr, std::vector<dcmt_plane_fit>* fits = nullptr)
+{
+    check_input(sparse_r_img);
+    const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
+    if ((int)clusters.size() != cols) throw std::runtime_error("fit_superpixel_planes: clusters does not have the image's size");
+    std::vector<int32_t> lab((size_t)rows * cols);
+    for (int j = 0; j < cols; ++j) {
+        if ((int)clusters[j].size() != rows) throw std::runtime_error("fit_superpixel_planes: clusters does not have the image's size");
+        for (int i = 0; i < rows; ++i) lab[(size_t)i * cols + j] = clusters[j][i];
+    }
+    dcmt_planes_params def;
+    dcmt_default_planes_params(&def);
+    if (fits) fits->assign(n_labels > 0 ? (size_t)n_labels : 0, dcmt_plane_fit());
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    raise(dcmt_superpixel_planes(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], lab.data(), sizeof(int32_t) * (size_t)cols,
+                                 rows, cols, n_labels, params ? params : &def, out.ptr<float>(), out.step[0], fits && n_labels > 0 ? fits->data() : nullptr),
+          "fit_superpixel_planes");
+    planes_img = out;
+}
+
 // unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
 // takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
