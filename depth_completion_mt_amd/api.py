@@ -652,6 +652,22 @@ class Context:
         _check(st, "dcmt_complete_u16_dev")
         return d_dst
 
+    def _project_points_dev(self, d_points, d_offsets, name, geo, rows, cols, d_sparse, stream):
+        """project_points_dev / project_points_calib_dev: `name` the entry point, geo(batch) what it takes between batch and d_sparse."""
+        import torch
+        assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
+        assert _is_dev(d_offsets, torch.int32)
+        batch = d_offsets.numel() - 1
+        n = d_points.numel() // 4
+        if d_sparse is None:
+            with _on_stream(stream, d_points):
+                d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
+        assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
+        st = getattr(L.lib(), name)(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch, *geo(batch), d_sparse.data_ptr(), rows, cols,
+                                    _stream(stream, d_points))
+        _check(st, name)
+        return d_sparse
+
     def project_points_dev(self, d_points, d_offsets, T, P, rows: int, cols: int, d_sparse=None, stream: int | None = None,
                            nearest: bool = False):
         """N2 (SL/main_sl.cpp:478-520): velodyne points -> sparse depth images on the device.  d_points: f32 CUDA tensor
@@ -660,22 +676,10 @@ class Context:
         A pixel several points land on keeps the last in file order (the reference's rule) or, with nearest=True, the closest: the
         smallest p.z (dcmt_project_points_nearest_dev; d_sparse must then overlap none of the inputs).
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
-        import torch
-        assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
-        assert _is_dev(d_offsets, torch.int32)
-        batch = d_offsets.numel() - 1
-        n = d_points.numel() // 4
-        if d_sparse is None:
-            with _on_stream(stream, d_points):
-                d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
-        assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
         t = np.ascontiguousarray(T, dtype=np.float32).reshape(16)
         p = np.ascontiguousarray(P, dtype=np.float32).reshape(12)
-        name = _rule("dcmt_project_points_dev", nearest)
-        st = getattr(L.lib(), name)(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch, t.ctypes.data, p.ctypes.data,
-                                    d_sparse.data_ptr(), rows, cols, _stream(stream, d_points))
-        _check(st, name)
-        return d_sparse
+        return self._project_points_dev(d_points, d_offsets, _rule("dcmt_project_points_dev", nearest), lambda batch: (t.ctypes.data, p.ctypes.data),
+                                        rows, cols, d_sparse, stream)
 
     def project_points_calib_dev(self, d_points, d_offsets, d_calib, rows: int, cols: int, d_sparse=None, stream: int | None = None,
                                  nearest: bool = False):
@@ -683,21 +687,8 @@ class Context:
         holding [batch] dcmt_project_calib records (make_project_calib, calib_to_device), read on the stream the call enqueues on.
         A sweep whose record has a non-finite entry gives a zero plane.  nearest: as for project_points_dev.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
-        import torch
-        assert _is_dev(d_points, torch.float32) and d_points.shape[-1] == 4
-        assert _is_dev(d_offsets, torch.int32)
-        batch = d_offsets.numel() - 1
-        n = d_points.numel() // 4
-        if d_sparse is None:
-            with _on_stream(stream, d_points):
-                d_sparse = torch.full((batch, rows, cols), float("nan"), dtype=torch.float32, device=d_points.device)
-        assert _is_dev(d_sparse, torch.float32) and tuple(d_sparse.shape) == (batch, rows, cols)
-        name = _rule("dcmt_project_points_calib_dev", nearest)
-        st = getattr(L.lib(), name)(self._h, d_points.data_ptr(), d_offsets.data_ptr(), n, batch,
-                                    _table_ptr(d_calib, batch, PROJECT_CALIB_DTYPE.itemsize), d_sparse.data_ptr(), rows, cols,
-                                    _stream(stream, d_points))
-        _check(st, name)
-        return d_sparse
+        return self._project_points_dev(d_points, d_offsets, _rule("dcmt_project_points_calib_dev", nearest),
+                                        lambda batch: (_table_ptr(d_calib, batch, PROJECT_CALIB_DTYPE.itemsize),), rows, cols, d_sparse, stream)
 
     def slic_labels_dev(self, d_lab, step: int, nc: int, d_labels=None, return_centers: bool = False, stream: int | None = None):
         """N3, Slic::generate_superpixels (LC/slic.cpp:101-182) on the device.  d_lab: uint8 CUDA tensor [batch][rows][cols][3]
@@ -820,10 +811,7 @@ class Context:
         _check(st, "dcmt_slic_cluster_means")
         return img, sums
 
-    def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
-        """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
-        kw: baseline, focal, damp, max_depth override the reference's constants.
-        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+    def _stereo_refine_dev(self, d_depth, d_left, d_right, d_calib, d_out, iterations, stream, kw):
         import torch
         assert _is_dev(d_depth, torch.float32)
         for t in (d_left, d_right):
@@ -835,39 +823,30 @@ class Context:
         sp = L.StereoParams()
         L.lib().dcmt_default_stereo_params(ctypes.byref(sp))
         for k, v in kw.items():
+            assert d_calib is None or k in ("damp", "max_depth"), k
             setattr(sp, k, float(v))
         if iterations is not None:
             sp.iterations = int(iterations)
-        st = L.lib().dcmt_stereo_refine_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(),
-                                            r, c, b, ctypes.byref(sp), _stream(stream, d_depth))
-        _check(st, "dcmt_stereo_refine_dev")
+        name = "dcmt_stereo_refine_dev" if d_calib is None else "dcmt_stereo_refine_calib_dev"
+        table = () if d_calib is None else (_table_ptr(d_calib, b, STEREO_CALIB_DTYPE.itemsize),)
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(), r, c, b, ctypes.byref(sp),
+                                    *table, _stream(stream, d_depth))
+        _check(st, name)
         return d_out
+
+    def stereo_refine_dev(self, d_depth, d_left, d_right, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
+        """N4 (SL/main_sl.cpp:715-885): dense depth + grey stereo pair (uint8 CUDA tensors) -> refined depth.
+        kw: baseline, focal, damp, max_depth override the reference's constants.
+        Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        return self._stereo_refine_dev(d_depth, d_left, d_right, None, d_out, iterations, stream, kw)
 
     def stereo_refine_calib_dev(self, d_depth, d_left, d_right, d_calib, d_out=None, iterations: int | None = None, stream: int | None = None, **kw):
         """stereo_refine_dev with each frame's own baseline and focal length (dcmt_stereo_refine_calib_dev): d_calib is a CUDA tensor
         holding [batch] dcmt_stereo_calib records (make_stereo_calib, calib_to_device), read on the stream the call enqueues on.
         kw: damp, max_depth.  A frame whose record has a non-finite entry or focal zero gives a zero plane.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
-        import torch
-        assert _is_dev(d_depth, torch.float32)
-        for t in (d_left, d_right):
-            assert _is_dev(t, torch.uint8) and t.shape == d_depth.shape
-        b, r, c = _brc(d_depth)
-        if d_out is None:
-            with _on_stream(stream, d_depth):
-                d_out = torch.full_like(d_depth, float("nan"))
-        sp = L.StereoParams()
-        L.lib().dcmt_default_stereo_params(ctypes.byref(sp))
-        for k, v in kw.items():
-            assert k in ("damp", "max_depth"), k
-            setattr(sp, k, float(v))
-        if iterations is not None:
-            sp.iterations = int(iterations)
-        st = L.lib().dcmt_stereo_refine_calib_dev(self._h, d_depth.data_ptr(), d_left.data_ptr(), d_right.data_ptr(), d_out.data_ptr(),
-                                                  r, c, b, ctypes.byref(sp), _table_ptr(d_calib, b, STEREO_CALIB_DTYPE.itemsize),
-                                                  _stream(stream, d_depth))
-        _check(st, "dcmt_stereo_refine_calib_dev")
-        return d_out
+        assert d_calib is not None
+        return self._stereo_refine_dev(d_depth, d_left, d_right, d_calib, d_out, iterations, stream, kw)
 
     # ---- photometric error maps (dcmt_photo_error*) ---------------------------------------
     def _photo_error_dev(self, d_depth, d_left, d_right, d_calib, d_err, d_stats, want_err, want_stats, stream, kw):
@@ -1382,6 +1361,11 @@ class Context:
         offsets int32 [batch + 1]; frame f owns points[offsets[f]:offsets[f + 1]].  Rows of points from offsets[batch] on are not
         written.  No synchronisation.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        p = params or make_cloud_params()
+        return self._depth_to_cloud_dev(d_depth, d_bgr, "dcmt_depth_to_cloud_dev", lambda b: (ctypes.byref(p),), d_points, d_offsets, capacity, stream)
+
+    def _depth_to_cloud_dev(self, d_depth, d_bgr, name, geo, d_points, d_offsets, capacity, stream):
+        """depth_to_cloud_dev / depth_to_cloud_calib_dev: `name` the entry point, geo(batch) what it takes between batch and d_points."""
         import torch
         assert _is_dev(d_depth, torch.float32)
         b, r, c = _brc(d_depth)
@@ -1396,11 +1380,9 @@ class Context:
                 d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
         assert _is_dev(d_points, torch.float32) and d_points.numel() >= 4 * capacity
         assert _is_dev(d_offsets, torch.int32) and d_offsets.numel() == b + 1
-        p = params or make_cloud_params()
-        st = L.lib().dcmt_depth_to_cloud_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
-                                             ctypes.byref(p), d_points.data_ptr(), int(capacity), d_offsets.data_ptr(),
-                                             _stream(stream, d_depth))
-        _check(st, "dcmt_depth_to_cloud_dev")
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b, *geo(b),
+                                    d_points.data_ptr(), int(capacity), d_offsets.data_ptr(), _stream(stream, d_depth))
+        _check(st, name)
         return d_points, d_offsets
 
     def depth_to_cloud_calib_dev(self, d_depth, d_calib, d_bgr=None, d_points=None, d_offsets=None, capacity: int | None = None,
@@ -1409,25 +1391,8 @@ class Context:
         [batch] dcmt_cloud_params records (make_cloud_calib, calib_to_device), read on the stream the call enqueues on.  A frame
         whose record has a non-finite entry or fx or fy zero gives no records: offsets[f + 1] == offsets[f].
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
-        import torch
-        assert _is_dev(d_depth, torch.float32)
-        b, r, c = _brc(d_depth)
-        if d_bgr is not None:
-            assert _is_dev(d_bgr, torch.uint8) and d_bgr.numel() == 3 * b * r * c
-        if capacity is None:
-            capacity = d_points.numel() // 4 if d_points is not None else b * r * c
-        with _on_stream(stream, d_depth):
-            if d_points is None:
-                d_points = torch.empty((capacity, 4), dtype=torch.float32, device=d_depth.device)
-            if d_offsets is None:
-                d_offsets = torch.empty((b + 1,), dtype=torch.int32, device=d_depth.device)
-        assert _is_dev(d_points, torch.float32) and d_points.numel() >= 4 * capacity
-        assert _is_dev(d_offsets, torch.int32) and d_offsets.numel() == b + 1
-        st = L.lib().dcmt_depth_to_cloud_calib_dev(self._h, d_depth.data_ptr(), d_bgr.data_ptr() if d_bgr is not None else None, r, c, b,
-                                                   _table_ptr(d_calib, b, CLOUD_CALIB_DTYPE.itemsize), d_points.data_ptr(), int(capacity),
-                                                   d_offsets.data_ptr(), _stream(stream, d_depth))
-        _check(st, "dcmt_depth_to_cloud_calib_dev")
-        return d_points, d_offsets
+        return self._depth_to_cloud_dev(d_depth, d_bgr, "dcmt_depth_to_cloud_calib_dev", lambda b: (_table_ptr(d_calib, b, CLOUD_CALIB_DTYPE.itemsize),),
+                                        d_points, d_offsets, capacity, stream)
 
     def depth_to_cloud(self, depth: np.ndarray, bgr: np.ndarray | None = None, params: L.CloudParams | None = None) -> np.ndarray:
         """One frame of host memory (dcmt_depth_to_cloud, synchronous; any row stride): a structured array (CLOUD_DTYPE: x y z f32,
@@ -1508,6 +1473,11 @@ class Context:
         [out_rows][out_cols]), which must not overlap d_depth.  No synchronisation.  nearest=True: a z-buffer -- a destination pixel
         keeps the smallest new depth that lands on it instead of the last (dcmt_reproject_depth_nearest_dev).
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
+        p = params or make_reproject_params()
+        return self._reproject_depth_dev(d_depth, out_rows, out_cols, _rule("dcmt_reproject_depth_dev", nearest), lambda b: (ctypes.byref(p),), d_out, stream)
+
+    def _reproject_depth_dev(self, d_depth, out_rows, out_cols, name, geo, d_out, stream):
+        """reproject_depth_dev / reproject_depth_calib_dev: `name` the entry point, geo(batch) what it takes between batch and d_out."""
         import torch
         assert _is_dev(d_depth, torch.float32)
         b, r, c = _brc(d_depth)
@@ -1515,10 +1485,8 @@ class Context:
             with _on_stream(stream, d_depth):
                 d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
         assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
-        p = params or make_reproject_params()
-        name = _rule("dcmt_reproject_depth_dev", nearest)
-        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, ctypes.byref(p), d_out.data_ptr(), int(out_rows),
-                                    int(out_cols), _stream(stream, d_depth))
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, *geo(b), d_out.data_ptr(), int(out_rows), int(out_cols),
+                                    _stream(stream, d_depth))
         _check(st, name)
         return d_out
 
@@ -1528,18 +1496,8 @@ class Context:
         holding [batch] dcmt_reproject_params records (make_reproject_calib, calib_to_device), read on the stream the call enqueues
         on.  A frame whose record the uniform call would refuse gives a zero plane.  nearest: as for reproject_depth_dev.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
-        import torch
-        assert _is_dev(d_depth, torch.float32)
-        b, r, c = _brc(d_depth)
-        if d_out is None:
-            with _on_stream(stream, d_depth):
-                d_out = torch.full(tuple(d_depth.shape[:-2]) + (out_rows, out_cols), float("nan"), dtype=torch.float32, device=d_depth.device)
-        assert _is_dev(d_out, torch.float32) and d_out.numel() == b * out_rows * out_cols
-        name = _rule("dcmt_reproject_depth_calib_dev", nearest)
-        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, _table_ptr(d_calib, b, REPROJECT_CALIB_DTYPE.itemsize),
-                                    d_out.data_ptr(), int(out_rows), int(out_cols), _stream(stream, d_depth))
-        _check(st, name)
-        return d_out
+        return self._reproject_depth_dev(d_depth, out_rows, out_cols, _rule("dcmt_reproject_depth_calib_dev", nearest),
+                                         lambda b: (_table_ptr(d_calib, b, REPROJECT_CALIB_DTYPE.itemsize),), d_out, stream)
 
     def reproject_depth(self, depth: np.ndarray, out_rows: int, out_cols: int, params: L.ReprojectParams | None = None,
                         nearest: bool = False) -> np.ndarray:

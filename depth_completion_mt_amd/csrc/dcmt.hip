@@ -25,6 +25,7 @@
 #include "dcmt_plan_side.h"
 #include "dcmt_ctx.h"
 #include "dcmt_kernels_v1.h"
+#include "dcmt_kernels_project.h"
 #include "dcmt_kernels_fused.h"
 #include "dcmt_kernels_pair.h"
 #include "dcmt_kernels_fp_q16.h"
@@ -783,27 +784,18 @@ static int project_points(dcmt_ctx* ctx, const float* d_points, const int32_t* d
     const int rc = winner_generation(ctx, n_px, (size_t)n_points, st, &gen_tag);      // (2^30 points per call: 16 GiB of records)
     if (rc != DCMT_OK) return rc;
     unsigned* winner = ctx->winner;
-    if (d_table) {
+    const auto launch = [&](auto src) {                // ProjMats or ProjTable
+        using Src = decltype(src);
         if (n_points > 0)
-            hipLaunchKernelGGL(k_project_scatter_calib, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, d_table,
+            hipLaunchKernelGGL(k_project_scatter<Src>, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, src,
                                winner, rows, cols, gen_tag);
         with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_sparse), [&](auto v) {
-            hipLaunchKernelGGL(k_project_resolve_calib<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, d_table, winner,
-                               d_sparse, (uint32_t)rows * (uint32_t)cols, n_px, gen_tag, ctx->winner_bits);
+            hipLaunchKernelGGL((k_project_resolve<decltype(v)::value, Src>), dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, src, winner,
+                               d_sparse, n_px, gen_tag, ctx->winner_bits, (uint32_t)rows * (uint32_t)cols);
         });
-        DCMT_HIP(ctx, hipGetLastError());
-        return DCMT_OK;
-    }
-    ProjMats M;
-    std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
-    std::memcpy(M.P, P, sizeof(float) * 12);
-    if (n_points > 0)
-        hipLaunchKernelGGL(k_project_scatter, dim3((n_points + 255) / 256), dim3(256), 0, st, d_points, d_offsets, n_points, batch, M,
-                           winner, rows, cols, gen_tag);
-    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_sparse), [&](auto v) {
-        hipLaunchKernelGGL(k_project_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_points, M, winner, d_sparse, n_px,
-                           gen_tag, ctx->winner_bits);
-    });
+    };
+    if (d_table) launch(ProjTable{d_table});
+    else launch(proj_mats(T, P));
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
@@ -822,16 +814,14 @@ static int stereo_refine(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_l
     const plan::StereoPlan pl = plan::plan_stereo(rows, cols, batch);
     if (pl.status != DCMT_OK) return pl.status;
     const dim3 sg(pl.gx, pl.gy, pl.gz);
-    if (table) {
-        const StereoTable PT{d_table, P.damp, P.max_depth, P.iterations};
-        if (pl.lds_row)
-            hipLaunchKernelGGL((k_stereo_refine<true, StereoTable>), sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, PT);
-        else
-            hipLaunchKernelGGL((k_stereo_refine<false, StereoTable>), sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, PT);
-    } else if (pl.lds_row)
-        hipLaunchKernelGGL(k_stereo_refine<true>, sg, dim3(256), pl.lds, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
-    else
-        hipLaunchKernelGGL(k_stereo_refine<false>, sg, dim3(256), 0, (hipStream_t)stream, d_depth, d_left, d_right, d_refined, rows, cols, batch, P);
+    const auto launch = [&](auto src) {                // StereoP or StereoTable
+        with_bool(pl.lds_row, [&](auto lds_row) {
+            hipLaunchKernelGGL((k_stereo_refine<decltype(lds_row)::value, decltype(src)>), sg, dim3(256), lds_row ? pl.lds : 0, (hipStream_t)stream, d_depth,
+                               d_left, d_right, d_refined, rows, cols, batch, src);
+        });
+    };
+    if (table) launch(StereoTable{d_table, P.damp, P.max_depth, P.iterations});
+    else launch(P);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

@@ -1,4 +1,4 @@
-// dcmt_calib.h -- per-frame calibration tables as the *_calib kernels read them (dcmt_project_points_calib_dev,
+// dcmt_calib.h -- per-frame calibration tables as the kernels' table instances read them (dcmt_project_points_calib_dev,
 // dcmt_depth_to_cloud_calib_dev, dcmt_reproject_depth_calib_dev, dcmt_stereo_refine_calib_dev): device arrays of [batch] records in
 // the layouts of include/dcmt.h, only ever read.
 //

@@ -3,8 +3,10 @@
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
 // dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h),
-// dcmt_photo_error_dev and dcmt_photo_error_calib_dev (dcmt_kernels_photo.h), the *_calib_dev twins of the cloud and the reprojection, the defaults of their parameter structs and dcmt_lab_tables.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame host variants
-// are in dcmt_host.hip.
+// dcmt_photo_error_dev (dcmt_kernels_photo.h), the defaults of their parameter structs and dcmt_lab_tables.  A *_calib_dev entry point
+// shares its one launch sequence with the uniform entry point beside it: the calibration source (one record by value, or the device
+// table) is the kernels' template type.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame
+// host variants are in dcmt_host.hip.
 #include <algorithm>
 
 #include "dcmt_chunks.h"
@@ -58,24 +60,17 @@ static int depth_to_cloud(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_
     const dim3 grid(chunks, batch);
     const uint32_t per = chunks * kCloudWaves;      // slab: [batch][chunks][kCloudWaves] uint32
     uint4* points = reinterpret_cast<uint4*>(d_points);
-    if (d_table) {
-        hipLaunchKernelGGL(k_cloud_count_calib, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, d_table, ctx->cloud_slab);
+    const auto launch = [&](auto src) {                // CloudK or CloudTable
+        using Src = decltype(src);
+        hipLaunchKernelGGL(k_cloud_count<Src>, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, ctx->cloud_slab, src);
         hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, ctx->cloud_slab, per * (uint32_t)batch, per, (uint32_t)batch, d_offsets);
-        const CloudTable kt{d_table};
-        if (d_bgr)
-            hipLaunchKernelGGL((k_cloud_scatter<true, CloudTable>), grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, kt, ctx->cloud_slab, points, room);
-        else
-            hipLaunchKernelGGL((k_cloud_scatter<false, CloudTable>), grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, kt, ctx->cloud_slab, points, room);
-        DCMT_HIP(ctx, hipGetLastError());
-        return DCMT_OK;
-    }
-    const CloudK k = {params->fx, params->fy, params->cx, params->cy};
-    hipLaunchKernelGGL(k_cloud_count, grid, dim3(kCloudThreads), 0, st, d_depth, n, groups, ctx->cloud_slab);
-    hipLaunchKernelGGL(k_cloud_scan, dim3(1), dim3(kCloudScanThreads), 0, st, ctx->cloud_slab, per * (uint32_t)batch, per, (uint32_t)batch, d_offsets);
-    if (d_bgr)
-        hipLaunchKernelGGL(k_cloud_scatter<true>, grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, k, ctx->cloud_slab, points, room);
-    else
-        hipLaunchKernelGGL(k_cloud_scatter<false>, grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, k, ctx->cloud_slab, points, room);
+        with_value<true, false>(d_bgr != nullptr, [&](auto color) {
+            hipLaunchKernelGGL((k_cloud_scatter<decltype(color)::value, Src>), grid, dim3(kCloudThreads), 0, st, d_depth, d_bgr, n, groups, (uint32_t)cols, src,
+                               ctx->cloud_slab, points, room);
+        });
+    };
+    if (d_table) launch(CloudTable{d_table});
+    else launch(CloudK{params->fx, params->fy, params->cx, params->cy});
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
@@ -120,23 +115,17 @@ static int reproject_depth(dcmt_ctx* ctx, const float* d_depth, int rows, int co
     const int rc = winner_generation(ctx, n_px, n, st, &gen_tag);
     if (rc != DCMT_OK) return rc;
     const dim3 scatter_grid((n + kReprojectPxPerWg - 1) / kReprojectPxPerWg, batch);
-    if (d_table) {
-        hipLaunchKernelGGL(k_reproject_scatter_calib, scatter_grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, d_table, ctx->winner,
+    const auto launch = [&](auto src) {                // ReprojK or ReprojTable
+        using Src = decltype(src);
+        hipLaunchKernelGGL(k_reproject_scatter<Src>, scatter_grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, src, ctx->winner,
                            (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
         with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
-            hipLaunchKernelGGL(k_reproject_resolve_calib<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols,
-                               d_table, ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
+            hipLaunchKernelGGL((k_reproject_resolve<decltype(v)::value, Src>), dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols,
+                               src, ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
         });
-        DCMT_HIP(ctx, hipGetLastError());
-        return DCMT_OK;
-    }
-    const ReprojK k = reproject_k(params);
-    hipLaunchKernelGGL(k_reproject_scatter, scatter_grid, dim3(256), 0, st, d_depth, n,
-                       (uint32_t)cols, k, ctx->winner, (uint32_t)out_rows, (uint32_t)out_cols, gen_tag);
-    with_value<4, 2, 1>(plan::resolve_vec(n_px, (uintptr_t)d_out), [&](auto v) {
-        hipLaunchKernelGGL(k_reproject_resolve<decltype(v)::value>, dim3((unsigned)((n_px / v + 255) / 256)), dim3(256), 0, st, d_depth, n, (uint32_t)cols, k,
-                           ctx->winner, d_out, dst_n, n_px, gen_tag, ctx->winner_bits);
-    });
+    };
+    if (d_table) launch(ReprojTable{d_table});
+    else launch(reproject_k(params));
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }
@@ -234,16 +223,12 @@ static int project_points_nearest(dcmt_ctx* ctx, const float* d_points, const in
                                                             (uintptr_t)d_table, (uintptr_t)d_sparse);
     if (pl.status != plan::kOk) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    if (d_table)
+    const auto launch = [&](auto src) {                // ProjMats or ProjTable
         return nearest_launch(ctx, pl, d_sparse, st, [&](dim3 grid, unsigned* keys) {
-            hipLaunchKernelGGL(k_project_nearest_scatter_calib, grid, dim3(256), 0, st, d_points, d_offsets, n_points, batch, d_table, keys, rows, cols);
+            hipLaunchKernelGGL(k_project_nearest_scatter<decltype(src)>, grid, dim3(256), 0, st, d_points, d_offsets, n_points, batch, src, keys, rows, cols);
         });
-    ProjMats M;
-    std::memcpy(M.T, T, sizeof(float) * 12);       // the bottom row of T is never used (SL :483-485)
-    std::memcpy(M.P, P, sizeof(float) * 12);
-    return nearest_launch(ctx, pl, d_sparse, st, [&](dim3 grid, unsigned* keys) {
-        hipLaunchKernelGGL(k_project_nearest_scatter, grid, dim3(256), 0, st, d_points, d_offsets, n_points, batch, M, keys, rows, cols);
-    });
+    };
+    return d_table ? launch(ProjTable{d_table}) : launch(proj_mats(T, P));
 }
 
 // params / d_table as for reproject_depth
@@ -259,14 +244,13 @@ static int reproject_depth_nearest(dcmt_ctx* ctx, const float* d_depth, int rows
     if (pl.status != plan::kOk) return DCMT_E_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t n = (uint32_t)rows * (uint32_t)cols;
-    if (d_table)
+    const auto launch = [&](auto src) {                // ReprojK or ReprojTable
         return nearest_launch(ctx, pl, d_out, st, [&](dim3 grid, unsigned* keys) {
-            hipLaunchKernelGGL(k_reproject_nearest_scatter_calib, grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, d_table, keys, (uint32_t)out_rows, (uint32_t)out_cols);
+            hipLaunchKernelGGL(k_reproject_nearest_scatter<decltype(src)>, grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, src, keys, (uint32_t)out_rows,
+                               (uint32_t)out_cols);
         });
-    const ReprojK k = reproject_k(params);
-    return nearest_launch(ctx, pl, d_out, st, [&](dim3 grid, unsigned* keys) {
-        hipLaunchKernelGGL(k_reproject_nearest_scatter, grid, dim3(256), 0, st, d_depth, n, (uint32_t)cols, k, keys, (uint32_t)out_rows, (uint32_t)out_cols);
-    });
+    };
+    return d_table ? launch(ReprojTable{d_table}) : launch(reproject_k(params));
 }
 
 extern "C" {

@@ -77,9 +77,28 @@ __device__ __forceinline__ void cloud_load4(const float* __restrict__ p, uint32_
     }
 }
 
-// the counting of one workgroup (k_cloud_count, k_cloud_count_calib)
-__device__ __forceinline__ void cloud_count_run(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
+// The intrinsics as the argument `geo` of k_cloud_count and k_cloud_scatter: CloudK itself, by value (dcmt_depth_to_cloud_dev), or a
+// table of per-frame records (dcmt_depth_to_cloud_calib_dev, dcmt_calib.h), of which the workgroup takes record blockIdx.y -- loaded
+// once per wave through the scalar cache in front of the pixel loop, into the SGPRs where the by-value argument lies
+struct CloudTable { const dcmt_cloud_params* __restrict__ records; };
+__device__ __forceinline__ const CloudK& cloud_k(const CloudK& arg, const CloudK&) { return arg; }
+__device__ __forceinline__ const CloudK& cloud_k(const CloudTable&, const CloudK& rec) { return rec; }
+
+// grid (eval_chunks(n), frames), 256 threads; G = eval_chunk_groups(n).  slab: [frames][chunks][kCloudWaves] counts.  The count does
+// not depend on the intrinsics: the CloudK instance takes them last and reads nothing of them (its text is that of a kernel without
+// the argument but for the offset of the hidden gridDim.x behind it: DESIGN.md section 34); the CloudTable instance tests the frame's record, and a frame whose record is bad counts nothing, so the scan's
+// offsets stay true and k_cloud_scatter<.., CloudTable>, which skips the frame, leaves no gap
+template <typename KSrc = CloudK>
+__global__ __launch_bounds__(kCloudThreads)
+void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab, KSrc geo)
 {
+    if constexpr (std::is_same_v<KSrc, CloudTable>) {
+        CloudK rec;
+        if (!load_cloud_record(geo.records, blockIdx.y, rec)) {         // wave-uniform: one scalar load per wave
+            if ((threadIdx.x & 63) == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + threadIdx.x / 64] = 0u;
+            return;
+        }
+    }
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
     const float* __restrict__ p = depth + (size_t)blockIdx.y * n;
     uint32_t ws, we;
@@ -92,27 +111,6 @@ __device__ __forceinline__ void cloud_count_run(const float* __restrict__ depth,
         for (int i = 0; i < 4; ++i) cnt += (uint32_t)__popcll(__ballot(d[i] > 0.0f));
     }
     if (l == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + w] = cnt;
-}
-
-// grid (eval_chunks(n), frames), 256 threads; G = eval_chunk_groups(n).  slab: [frames][chunks][kCloudWaves] counts
-__global__ __launch_bounds__(kCloudThreads)
-void k_cloud_count(const float* __restrict__ depth, uint32_t n, uint32_t G, uint32_t* __restrict__ slab)
-{
-    cloud_count_run(depth, n, G, slab);
-}
-
-// the same with a table of per-frame intrinsics (dcmt_calib.h): a frame whose record is bad counts nothing, so the scan's offsets
-// stay true and k_cloud_scatter<.., CloudTable>, which skips the frame, leaves no gap
-__global__ __launch_bounds__(kCloudThreads)
-void k_cloud_count_calib(const float* __restrict__ depth, uint32_t n, uint32_t G, const dcmt_cloud_params* __restrict__ table,
-                         uint32_t* __restrict__ slab)
-{
-    CloudK k;
-    if (!load_cloud_record(table, blockIdx.y, k)) {                 // wave-uniform: one scalar load per wave
-        if ((threadIdx.x & 63) == 0) slab[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * kCloudWaves + threadIdx.x / 64] = 0u;
-        return;
-    }
-    cloud_count_run(depth, n, G, slab);
 }
 
 // one workgroup of 1024 threads.  slab: entries counts in, exclusive bases out; per = entries per frame (chunks * kCloudWaves, a
@@ -154,15 +152,8 @@ void k_cloud_scan(uint32_t* __restrict__ slab, uint32_t entries, uint32_t per, u
     }
 }
 
-// The intrinsics as k_cloud_scatter's argument `geo`: CloudK itself, by value (dcmt_depth_to_cloud_dev), or a table of per-frame
-// records (dcmt_depth_to_cloud_calib_dev, dcmt_calib.h), of which the workgroup takes record blockIdx.y -- loaded once per wave
-// through the scalar cache in front of the pixel loop, into the SGPRs where the by-value argument lies.  A frame whose record is bad
-// was counted as empty (k_cloud_count_calib) and is skipped
-struct CloudTable { const dcmt_cloud_params* __restrict__ records; };
-__device__ __forceinline__ const CloudK& cloud_k(const CloudK& arg, const CloudK&) { return arg; }
-__device__ __forceinline__ const CloudK& cloud_k(const CloudTable&, const CloudK& rec) { return rec; }
-
-// grid (eval_chunks(n), frames), 256 threads.  slab: the bases k_cloud_scan left.  bgr: [frames][n][3] bytes or null.
+// grid (eval_chunks(n), frames), 256 threads.  slab: the bases k_cloud_scan left.  bgr: [frames][n][3] bytes or null.  geo: as for
+// k_cloud_count; a frame whose record is bad was counted as empty there and is skipped
 template <bool kColor, typename KSrc = CloudK>
 __global__ __launch_bounds__(kCloudThreads)
 void k_cloud_scatter(const float* __restrict__ depth, const uint8_t* __restrict__ bgr, uint32_t n, uint32_t G, uint32_t cols, KSrc geo,

@@ -1,8 +1,8 @@
 // dcmt_kernels_nearest.h -- the two geometric scatter calls under the rule every producer of sparse depth uses: a pixel hit by
 // several points (dcmt_project_points_nearest*_dev) or source pixels (dcmt_reproject_depth_nearest*_dev) keeps the NEAREST, the
-// smallest of the values the last-wins kernels (k_project_scatter, dcmt_kernels_v1.h; k_reproject_scatter,
+// smallest of the values the last-wins kernels (k_project_scatter, dcmt_kernels_project.h; k_reproject_scatter,
 // dcmt_kernels_reproject.h) would have stored there.  A point or pixel is transformed, accepted and rejected by the very statements
-// of those kernels -- project_point / project_scatter_calib_run (dcmt_project.h), reproject_scatter_run -- so the set of occupied
+// of those kernels -- project_scatter_run / project_scatter_calib_run (dcmt_project.h), reproject_scatter_run -- so the set of occupied
 // pixels is the same; only the store differs.
 //
 // The depth is the payload, so there is no index and no winner plane: an order-preserving integer key (dcmt_depth_key.h) goes into
@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dcmt_depth_key.h"
 #include "dcmt_kernels_reproject.h"
 #include "dcmt_project.h"
@@ -33,33 +35,23 @@ __device__ __forceinline__ void nearest_store(unsigned* __restrict__ keys, size_
     atomicMax(&keys[px], depth_key(__float_as_uint(v)));
 }
 
-// k_project_scatter's shape: one point per thread, the workgroup's frame search over d_offsets.  keys: the output plane,
-// [batch][rows][cols], zeroed
+// k_project_scatter's shape, instance by instance: ProjMats -- one point per thread, the workgroup's frame search over d_offsets
+// (project_scatter_run); ProjTable -- the scalar-cache record path with its ballot test and its per-lane fallback
+// (project_scatter_calib_run), where a frame with a bad record scatters nothing: its part of the plane stays zero.  keys: the output
+// plane, [batch][rows][cols], zeroed
+template <typename MSrc = ProjMats>
 __global__ __launch_bounds__(256)
 void k_project_nearest_scatter(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
-                               ProjMats M, unsigned* __restrict__ keys, int rows, int cols)
+                               MSrc geo, unsigned* __restrict__ keys, int rows, int cols)
 {
-    const int i0 = blockIdx.x * 256;
-    const int lo_wg = project_wg_frame(offsets, batch, i0);
-    const int i = i0 + threadIdx.x;
-    if (i >= n_points) return;
-    int lo = lo_wg;
-    while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;            // lo_wg <= lo < batch whatever the offsets hold
-    const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
-    int u, v; float d;
-    if (!project_point(M, p.x, p.y, p.z, rows, cols, u, v, d)) return;
-    if ((unsigned)u < (unsigned)cols && (unsigned)v < (unsigned)rows)             // (as project_scatter_calib_run explains)
-        nearest_store(keys, ((size_t)lo * rows + (unsigned)v) * cols + (unsigned)u, d);
-}
-
-// k_project_scatter_calib's: the scalar-cache record path with its ballot test and its per-lane fallback.  A frame with a bad
-// record scatters nothing: its part of the plane stays zero
-__global__ __launch_bounds__(256)
-void k_project_nearest_scatter_calib(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
-                                     const dcmt_project_calib* __restrict__ table, unsigned* __restrict__ keys, int rows, int cols)
-{
-    project_scatter_calib_run(pts, offsets, n_points, batch, table, rows, cols,
-                              [&](size_t px, unsigned, float d) { nearest_store(keys, px, d); });
+    if constexpr (std::is_same_v<MSrc, ProjTable>)
+        project_scatter_calib_run(pts, offsets, n_points, batch, geo.records, rows, cols,
+                                  [&](size_t px, unsigned, float d) { nearest_store(keys, px, d); });
+    else
+        project_scatter_run(pts, offsets, n_points, batch, geo, rows, cols, [=](int lo, int u, int v, int, float d) {
+            if ((unsigned)u < (unsigned)cols && (unsigned)v < (unsigned)rows)     // (as project_scatter_calib_run explains)
+                nearest_store(keys, ((size_t)lo * rows + (unsigned)v) * cols + (unsigned)u, d);
+        });
 }
 
 // k_reproject_scatter's: grid (ceil(n / 1024), frames), four loads in flight per thread.  The stored value is t_2 > 0
@@ -69,20 +61,15 @@ __device__ __forceinline__ auto reproject_nearest_store(unsigned* __restrict__ k
     return [=](size_t px, uint32_t, float t2) { nearest_store(plane, px, t2); };
 }
 
+template <typename KSrc = ReprojK>
 __global__ __launch_bounds__(256)
-void k_reproject_nearest_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, unsigned* __restrict__ keys,
+void k_reproject_nearest_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, KSrc geo, unsigned* __restrict__ keys,
                                  uint32_t dst_rows, uint32_t dst_cols)
 {
-    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_nearest_store(keys, dst_rows, dst_cols));
-}
-
-__global__ __launch_bounds__(256)
-void k_reproject_nearest_scatter_calib(const float* __restrict__ depth, uint32_t n, uint32_t cols, const dcmt_reproject_params* __restrict__ table,
-                                       unsigned* __restrict__ keys, uint32_t dst_rows, uint32_t dst_cols)
-{
-    ReprojK k;
-    if (!load_reproject_record(table, blockIdx.y, k)) return;
-    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_nearest_store(keys, dst_rows, dst_cols));
+    [[maybe_unused]] ReprojK rec;
+    if constexpr (std::is_same_v<KSrc, ReprojTable>)
+        if (!load_reproject_record(geo.records, blockIdx.y, rec)) return;
+    reproject_scatter_run(depth, n, cols, reproj_k(geo, rec), dst_rows, dst_cols, reproject_nearest_store(keys, dst_rows, dst_cols));
 }
 
 // One thread per PW neighbouring pixels of the whole batch, in place: n_px is a multiple of PW and the plane aligned to 4 * PW bytes
@@ -93,15 +80,11 @@ void k_nearest_fixup(unsigned* __restrict__ plane, size_t n_px)
 {
     const size_t i = (blockIdx.x * (size_t)256 + threadIdx.x) * PW;
     if (i >= n_px) return;
-    if constexpr (PW == 4) {
-        uint4 w = *reinterpret_cast<const uint4*>(plane + i);
-        w.x = depth_key_to_bits(w.x); w.y = depth_key_to_bits(w.y); w.z = depth_key_to_bits(w.z); w.w = depth_key_to_bits(w.w);
-        *reinterpret_cast<uint4*>(plane + i) = w;
-    } else if constexpr (PW == 2) {
-        uint2 w = *reinterpret_cast<const uint2*>(plane + i);
-        w.x = depth_key_to_bits(w.x); w.y = depth_key_to_bits(w.y);
-        *reinterpret_cast<uint2*>(plane + i) = w;
-    } else plane[i] = depth_key_to_bits(plane[i]);
+    uint32_t w[PW];
+    load_words<PW>(plane + i, w);
+#pragma unroll
+    for (int j = 0; j < PW; ++j) w[j] = depth_key_to_bits(w[j]);
+    store_words<PW>(plane + i, w);
 }
 
 }  // namespace dcmt

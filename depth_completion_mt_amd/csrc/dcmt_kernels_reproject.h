@@ -11,7 +11,7 @@
 //     dst[(int)vf][(int)uf] = t_2                                                                    (:1011-1015)
 // in row-major source order, so a later source pixel overwrites an earlier one that fell into the same destination pixel.
 //
-// Two passes, the shape of N2 (k_project_scatter / k_project_resolve, dcmt_kernels_v1.h), on the same winner plane:
+// Two passes, the shape of N2 (k_project_scatter / k_project_resolve, dcmt_kernels_project.h), on the same winner plane:
 //   k_reproject_scatter   per source pixel: atomicMax of the tag generation | frame-local source pixel index into the winner plane
 //                         at the destination pixel (no value returned).  The largest index is the last writer; an integer max does
 //                         not depend on arrival order, so the result is the same bits on every run.
@@ -24,6 +24,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "dcmt_calib.h"
 #include "dcmt_cloud.h"
@@ -79,104 +81,78 @@ __device__ __forceinline__ auto reproject_tag_store(unsigned* __restrict__ winne
     return [=](size_t px, uint32_t q, float) { atomicMax(&win[px], gen_tag | q); };
 }
 
+// The record as the kernels' argument `geo`, the idiom of k_cloud_scatter (dcmt_kernels_cloud.h): ReprojK itself, by value
+// (dcmt_reproject_depth*_dev), or a table of per-frame records (dcmt_reproject_depth*_calib_dev, dcmt_calib.h)
+struct ReprojTable { const dcmt_reproject_params* __restrict__ records; };
+__device__ __forceinline__ const ReprojK& reproj_k(const ReprojK& arg, const ReprojK&) { return arg; }
+__device__ __forceinline__ const ReprojK& reproj_k(const ReprojTable&, const ReprojK& rec) { return rec; }
+
+// ReprojTable: the frame's own record, record blockIdx.y of the table, loaded once per wave through the scalar cache in front of the
+// pixel loop.  A frame with a bad record scatters nothing: its part of the winner plane keeps no tag of this generation and
+// k_reproject_resolve writes zeros there
+template <typename KSrc = ReprojK>
 __global__ __launch_bounds__(256)
-void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, unsigned* __restrict__ winner,
+void k_reproject_scatter(const float* __restrict__ depth, uint32_t n, uint32_t cols, KSrc geo, unsigned* __restrict__ winner,
                          uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
 {
-    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_tag_store(winner, dst_rows, dst_cols, gen_tag));
-}
-
-// the same with the frame's own record: record blockIdx.y of the table (dcmt_calib.h), loaded once per wave through the scalar cache
-// in front of the pixel loop.  A frame with a bad record scatters nothing: its part of the winner plane keeps no tag of this
-// generation and k_reproject_resolve_calib writes zeros there
-__global__ __launch_bounds__(256)
-void k_reproject_scatter_calib(const float* __restrict__ depth, uint32_t n, uint32_t cols, const dcmt_reproject_params* __restrict__ table,
-                               unsigned* __restrict__ winner, uint32_t dst_rows, uint32_t dst_cols, unsigned gen_tag)
-{
-    ReprojK k;
-    if (!load_reproject_record(table, blockIdx.y, k)) return;
-    reproject_scatter_run(depth, n, cols, k, dst_rows, dst_cols, reproject_tag_store(winner, dst_rows, dst_cols, gen_tag));
+    [[maybe_unused]] ReprojK rec;
+    if constexpr (std::is_same_v<KSrc, ReprojTable>)
+        if (!load_reproject_record(geo.records, blockIdx.y, rec)) return;
+    reproject_scatter_run(depth, n, cols, reproj_k(geo, rec), dst_rows, dst_cols, reproject_tag_store(winner, dst_rows, dst_cols, gen_tag));
 }
 
 // One thread per PW neighbouring destination pixels of the whole batch (a thread's pixels may lie in two frames): 8- / 16-byte
 // accesses where the batch's pixel count and d_out's alignment allow, the scheme of k_project_resolve.  dst_n = dst_rows * dst_cols,
 // n_px = frames * dst_n.
-template <int PW>
-__global__ __launch_bounds__(256)
-void k_reproject_resolve(const float* __restrict__ depth, uint32_t n, uint32_t cols, ReprojK k, const unsigned* __restrict__ winner,
-                         float* __restrict__ out, uint32_t dst_n, size_t n_px, unsigned gen_tag, int idx_bits)
-{
-    const size_t i = (blockIdx.x * (size_t)256 + threadIdx.x) * PW;
-    if (i >= n_px) return;
-    unsigned w[PW];
-    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
-    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
-    else w[0] = winner[i];
-    const unsigned mask = (1u << idx_bits) - 1u;
-    size_t f = i / dst_n;                                     // the frame of the thread's first pixel, and the pixel's place in it
-    uint32_t r = (uint32_t)(i - f * dst_n);
-    float o[PW];
-#pragma unroll
-    for (int j = 0; j < PW; ++j) {
-        if (j > 0 && ++r == dst_n) { r = 0; ++f; }
-        o[j] = 0.0f;
-        const uint32_t q = w[j] & mask;
-        if ((w[j] & ~mask) == gen_tag && q < n) {             // (q < n holds for every tag this call's scatter wrote)
-            const float z = depth[f * n + q];
-            const uint32_t y = q / cols, x = q - y * cols;
-            float x_, y_;
-            o[j] = reproject_t2(k, x, y, z, x_, y_);
-        }
-    }
-    if constexpr (PW == 4) *reinterpret_cast<float4*>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    else if constexpr (PW == 2) *reinterpret_cast<float2*>(out + i) = make_float2(o[0], o[1]);
-    else out[i] = o[0];
-}
-
-// k_reproject_resolve with the record of each pixel's OWN frame, the scheme of k_project_resolve_calib (dcmt_kernels_v1.h): the frame
-// of the wave's first pixel and that pixel's place in it from one division per wave on the scalar unit; where the wave's 64 * PW
-// pixels end inside that frame -- almost always -- its record comes through the scalar cache once per wave, as the by-value
-// argument of the uniform kernel does, and no lane divides.  Otherwise each lane finds the frame of its first pixel and each pixel
+// ReprojTable: the record of each pixel's OWN frame, the scheme of k_project_resolve<PW, ProjTable> (dcmt_kernels_project.h): the
+// frame of the wave's first pixel and that pixel's place in it from one division per wave on the scalar unit; where the wave's
+// 64 * PW pixels end inside that frame -- almost always -- its record comes through the scalar cache once per wave, as the by-value
+// argument of the uniform instance does, and no lane divides.  Otherwise each lane finds the frame of its first pixel and each pixel
 // that holds a winner gathers the 48 bytes reproject_t2 reads from its own frame's record.  Either way the arithmetic is
 // reproject_t2's.
-template <int PW>
+template <int PW, typename KSrc = ReprojK>
 __global__ __launch_bounds__(256)
-void k_reproject_resolve_calib(const float* __restrict__ depth, uint32_t n, uint32_t cols, const dcmt_reproject_params* __restrict__ table,
-                               const unsigned* __restrict__ winner, float* __restrict__ out, uint32_t dst_n, size_t n_px, unsigned gen_tag, int idx_bits)
+void k_reproject_resolve(const float* __restrict__ depth, uint32_t n, uint32_t cols, KSrc geo, const unsigned* __restrict__ winner,
+                         float* __restrict__ out, uint32_t dst_n, size_t n_px, unsigned gen_tag, int idx_bits)
 {
+    constexpr bool kTable = std::is_same_v<KSrc, ReprojTable>;
     const uint32_t l = threadIdx.x & 63;
     const size_t i_wave = (blockIdx.x * (size_t)256 + __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u)) * PW;     // the wave's first pixel
-    const size_t i = i_wave + (size_t)l * PW;
+    const size_t i = kTable ? i_wave + (size_t)l * PW : (blockIdx.x * (size_t)256 + threadIdx.x) * PW;
     if (i >= n_px) return;
-    unsigned w[PW];
-    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
-    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
-    else w[0] = winner[i];
+    uint32_t w[PW], o[PW];
+    load_words<PW>(winner + i, w);
     const unsigned mask = (1u << idx_bits) - 1u;
-    const uint32_t f_wave = (uint32_t)(i_wave / dst_n);                           // i_wave < n_px here, so f_wave < frames
-    const uint32_t r_wave = (uint32_t)(i_wave - (size_t)f_wave * dst_n);
-    const bool one_frame = r_wave + 64u * PW <= dst_n;                            // (a frame has < 2^29 pixels: no overflow)
-    uint32_t f = f_wave, r = r_wave + l * PW;                                     // r < dst_n + 256
-    ReprojK k;
-    if (one_frame) load_reproject_t2_record(table, f_wave, k);
-    else { const uint32_t df = r / dst_n; f += df; r -= df * dst_n; }             // i < n_px, so f < frames, and so is every frame below:
-    float o[PW];                                                                  // i + PW <= n_px (the pixel count is a multiple of PW)
+    std::conditional_t<kTable, uint32_t, size_t> f;           // the frame of the thread's first pixel (as wide as the division it comes
+    uint32_t r;                                               // from: 32 bits behind the wave's, 64 without), and the pixel's place in it
+    bool one_frame = false;                                   // (table) the wave's pixels lie in one frame, whose record is in `rec`
+    [[maybe_unused]] ReprojK rec;
+    if constexpr (kTable) {
+        const uint32_t f_wave = (uint32_t)(i_wave / dst_n);                       // i_wave < n_px here, so f_wave < frames
+        const uint32_t r_wave = (uint32_t)(i_wave - (size_t)f_wave * dst_n);
+        one_frame = r_wave + 64u * PW <= dst_n;                                   // (a frame has < 2^29 pixels: no overflow)
+        f = f_wave; r = r_wave + l * PW;                                          // r < dst_n + 256
+        if (one_frame) load_reproject_t2_record(geo.records, f_wave, rec);
+        else { const uint32_t df = r / dst_n; f += df; r -= df * dst_n; }         // i < n_px, so f < frames, and so is every frame below:
+    } else {                                                                      // i + PW <= n_px (the pixel count is a multiple of PW)
+        f = i / dst_n;
+        r = (uint32_t)(i - f * dst_n);
+    }
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
         if (!one_frame && j > 0 && ++r == dst_n) { r = 0; ++f; }
-        o[j] = 0.0f;
+        o[j] = 0u;
         const uint32_t q = w[j] & mask;
         if ((w[j] & ~mask) == gen_tag && q < n) {             // (q < n holds for every tag this call's scatter wrote)
-            if (!one_frame) load_reproject_t2_record(table, f, k);
+            if constexpr (kTable)
+                if (!one_frame) load_reproject_t2_record(geo.records, f, rec);
             const float z = depth[(size_t)f * n + q];
             const uint32_t y = q / cols, x = q - y * cols;
             float x_, y_;
-            o[j] = reproject_t2(k, x, y, z, x_, y_);
+            o[j] = __float_as_uint(reproject_t2(reproj_k(geo, rec), x, y, z, x_, y_));
         }
     }
-    if constexpr (PW == 4) *reinterpret_cast<float4*>(out + i) = make_float4(o[0], o[1], o[2], o[3]);
-    else if constexpr (PW == 2) *reinterpret_cast<float2*>(out + i) = make_float2(o[0], o[1]);
-    else out[i] = o[0];
+    store_words<PW>(reinterpret_cast<uint32_t*>(out) + i, o);
 }
 
 }  // namespace dcmt

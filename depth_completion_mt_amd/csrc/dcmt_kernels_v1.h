@@ -22,8 +22,6 @@
 #include <hip/hip_runtime.h>
 #include "dcmt_calib.h"
 #include "dcmt_gauss.h"
-#include "dcmt_dot_rn.h"
-#include "dcmt_project.h"
 #include <float.h>
 #include <stdint.h>
 #include <type_traits>
@@ -134,132 +132,6 @@ void k_norm_write(const float* __restrict__ src, float* __restrict__ dst, const 
         const size_t f = i / frame_elems;
         dst[i] = norm_apply(src[i], coef[2 * f], coef[2 * f + 1]);
     }
-}
-
-// ---------------------------------------------------------------------------------
-// N2: LiDAR points -> sparse depth image (SL/main_sl.cpp:478-520).  Pass 1: one thread per point; the pixel's winner
-// is the LAST point in file order = the largest point index (atomicMax on an int plane, -1 = empty).  Pass 2: one
-// thread per pixel recomputes the winning point's depth (the same deterministic arithmetic) or writes 0.
-// Every product and sum is rounded separately (__fmul_rn / __fadd_rn: no FMA contraction), sums left to right.
-// ---------------------------------------------------------------------------------
-// ProjMats, project_point, point_depth, project_wg_frame: dcmt_project.h (shared with the nearest-wins kernels of dcmt_kernels_nearest.h)
-
-// The winner plane holds TAGS: (generation << idx_bits) | global point index.  A call only looks at tags of its own generation, so
-// the plane is not cleared between calls (one 0.48 GB memset per 256 sweeps less); the host clears it when the generations run out
-// or a call needs more index bits than the plane's layout has.  Within a generation the larger tag is the larger point index =
-// the later point in file order (a frame's points are contiguous), the reference's "last writer wins".
-__global__ __launch_bounds__(256)
-void k_project_scatter(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
-                       ProjMats M, unsigned* __restrict__ winner, int rows, int cols, unsigned gen_tag)
-{
-    const int i0 = blockIdx.x * 256;
-    const int lo_wg = project_wg_frame(offsets, batch, i0);
-    const int i = i0 + threadIdx.x;
-    if (i >= n_points) return;
-    int lo = lo_wg;
-    while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;
-    const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
-    int u, v; float d;
-    if (!project_point(M, p.x, p.y, p.z, rows, cols, u, v, d)) return;
-    atomicMax(&winner[((size_t)lo * rows + v) * cols + u], gen_tag | (unsigned)i);
-}
-
-// One thread per PW neighbouring pixels of the whole batch (the tags hold global point indices, so a thread's pixels may lie in two
-// frames): 8- / 16-byte accesses where the batch size and the buffers allow.  Most pixels have no point of this generation and are a
-// zero; the winners' depths are recomputed from their points (the depth alone: the pixel is known, so the two divisions and the bounds
-// test of the first pass are not repeated).
-template <int PW>
-__global__ __launch_bounds__(256)
-void k_project_resolve(const float* __restrict__ pts, ProjMats M, const unsigned* __restrict__ winner, float* __restrict__ sparse,
-                       size_t n_px, unsigned gen_tag, int idx_bits)
-{
-    const size_t i = (blockIdx.x * (size_t)256 + threadIdx.x) * PW;
-    if (i >= n_px) return;
-    unsigned w[PW];
-    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
-    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
-    else w[0] = winner[i];
-    const unsigned mask = (1u << idx_bits) - 1u;
-    float o[PW];
-#pragma unroll
-    for (int k = 0; k < PW; ++k) {
-        o[k] = 0.0f;
-        if ((w[k] & ~mask) == gen_tag) {
-            const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)(w[k] & mask));
-            o[k] = point_depth(M, p.x, p.y, p.z);
-        }
-    }
-    if constexpr (PW == 4) *reinterpret_cast<float4*>(sparse + i) = make_float4(o[0], o[1], o[2], o[3]);
-    else if constexpr (PW == 2) *reinterpret_cast<float2*>(sparse + i) = make_float2(o[0], o[1]);
-    else sparse[i] = o[0];
-}
-
-// ---- N2 with a table of per-frame matrices (dcmt_project_calib, dcmt_calib.h; the record loaders: dcmt_project.h) --------------
-// k_project_scatter with the record of each point's OWN frame: project_scatter_calib_run (dcmt_project.h) storing the tag.  Measured
-// 13 % behind the uniform call, all of it here.  A frame with a bad record scatters nothing: its part of the
-// winner plane keeps no tag of this generation and the resolve writes zeros there.
-__global__ __launch_bounds__(256)
-void k_project_scatter_calib(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
-                             const dcmt_project_calib* __restrict__ table, unsigned* __restrict__ winner, int rows, int cols, unsigned gen_tag)
-{
-    project_scatter_calib_run(pts, offsets, n_points, batch, table, rows, cols,
-                              [&](size_t px, unsigned i, float) { atomicMax(&winner[px], gen_tag | i); });
-}
-
-// k_project_resolve with the record of each pixel's OWN frame: the winning point's frame is the frame of the pixel it won.  A
-// wave's 64 * PW consecutive pixels lie in one frame almost always (a frame of 352 x 1216 has 1672 such runs, one of which holds its
-// end): the frame of the wave's first pixel and that pixel's place in it are wave-uniform -- one division per wave, on the scalar
-// unit -- and where the run ends inside the frame, that frame's record comes through the scalar cache once per wave and no lane
-// divides.  Otherwise each lane finds the frame of its first pixel (a 32-bit division) and each pixel that holds a winner gathers
-// the 64 bytes point_depth reads from its own frame's record.  frame_px = rows * cols.
-template <int PW>
-__global__ __launch_bounds__(256)
-void k_project_resolve_calib(const float* __restrict__ pts, const dcmt_project_calib* __restrict__ table, const unsigned* __restrict__ winner,
-                             float* __restrict__ sparse, uint32_t frame_px, size_t n_px, unsigned gen_tag, int idx_bits)
-{
-    const uint32_t l = threadIdx.x & 63;
-    const size_t i_wave = (blockIdx.x * (size_t)256 + __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u)) * PW;     // the wave's first pixel
-    const size_t i = i_wave + (size_t)l * PW;
-    if (i >= n_px) return;
-    unsigned w[PW];
-    if constexpr (PW == 4) { const uint4 ww = *reinterpret_cast<const uint4*>(winner + i); w[0] = ww.x; w[1] = ww.y; w[2] = ww.z; w[3] = ww.w; }
-    else if constexpr (PW == 2) { const uint2 ww = *reinterpret_cast<const uint2*>(winner + i); w[0] = ww.x; w[1] = ww.y; }
-    else w[0] = winner[i];
-    const unsigned mask = (1u << idx_bits) - 1u;
-    const uint32_t f_wave = (uint32_t)(i_wave / frame_px);                        // i_wave < n_px here, so f_wave < batch
-    const uint32_t r_wave = (uint32_t)(i_wave - (size_t)f_wave * frame_px);
-    float o[PW];
-    if (r_wave + 64u * PW <= frame_px) {                                          // (a frame has < 2^29 pixels: no overflow)
-        ProjMats M;
-        load_project_depth_record(table, f_wave, M);
-#pragma unroll
-        for (int k = 0; k < PW; ++k) {
-            o[k] = 0.0f;
-            if ((w[k] & ~mask) == gen_tag) {
-                const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)(w[k] & mask));
-                o[k] = point_depth(M, p.x, p.y, p.z);
-            }
-        }
-    } else {
-        uint32_t r = r_wave + l * PW;                                             // < frame_px + 256
-        const uint32_t df = r / frame_px;
-        uint32_t f = f_wave + df;                                                 // i < n_px, so f < batch, and so is every frame below:
-        r -= df * frame_px;                                                       // i + PW <= n_px (the pixel count is a multiple of PW)
-#pragma unroll
-        for (int k = 0; k < PW; ++k) {
-            if (k > 0 && ++r == frame_px) { r = 0; ++f; }
-            o[k] = 0.0f;
-            if ((w[k] & ~mask) == gen_tag) {
-                ProjMats M;
-                load_project_depth_record(table, f, M);
-                const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)(w[k] & mask));
-                o[k] = point_depth(M, p.x, p.y, p.z);
-            }
-        }
-    }
-    if constexpr (PW == 4) *reinterpret_cast<float4*>(sparse + i) = make_float4(o[0], o[1], o[2], o[3]);
-    else if constexpr (PW == 2) *reinterpret_cast<float2*>(sparse + i) = make_float2(o[0], o[1]);
-    else sparse[i] = o[0];
 }
 
 // ---------------------------------------------------------------------------------

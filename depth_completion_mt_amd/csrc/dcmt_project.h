@@ -1,7 +1,8 @@
 // dcmt_project.h -- what the kernels of N2 (LiDAR points -> sparse depth image, SL/main_sl.cpp:478-520) share across the two code
-// objects: the last-wins kernels k_project_* (dcmt_kernels_v1.h, dcmt.hip) and the nearest-wins ones (dcmt_kernels_nearest.h,
-// dcmt_cloud.hip) transform, accept and reject a point with the very same statements, find a point's frame the same way and read a
-// per-frame record (dcmt_project_calib, dcmt_calib.h) through the same loaders; only what is stored at the landing pixel differs.
+// objects: the last-wins kernels k_project_* (dcmt_kernels_project.h, dcmt.hip) and the nearest-wins ones (dcmt_kernels_nearest.h,
+// dcmt_cloud.hip) transform, accept and reject a point with the very same statements (project_scatter_run, project_scatter_calib_run),
+// find a point's frame the same way and read a per-frame record (dcmt_project_calib, dcmt_calib.h; ProjTable) through the same
+// loaders; only what is stored at the landing pixel differs.
 // Every product and sum is rounded separately (__fmul_rn / __fadd_rn: no FMA contraction), sums left to right.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +14,15 @@
 namespace dcmt {
 
 struct ProjMats { float T[12]; float P[12]; };   // the three rows of T that are used; P
+
+// the host's T (4x4) and P (3x4) as the kernels take them: the bottom row of T is never used (SL :483-485)
+inline ProjMats proj_mats(const float* T, const float* P)
+{
+    ProjMats M;
+    __builtin_memcpy(M.T, T, sizeof M.T);
+    __builtin_memcpy(M.P, P, sizeof M.P);
+    return M;
+}
 
 // dot4_rn: dcmt_dot_rn.h
 
@@ -51,7 +61,34 @@ __device__ __forceinline__ int project_wg_frame(const int* __restrict__ offsets,
     return s_lo;
 }
 
+// The scatter with one pair of matrices for the whole batch, one point per thread of a 256-thread workgroup: the workgroup's frame
+// search, the thread's own frame, the point's record, project_point.  store(frame, u, v, i, depth): what is done at the landing pixel
+// (u, v) of that frame with the global point index i -- the store decides whether the bound is tested again in the integer domain
+// before the address is formed (the nearest-wins rule does; the last-wins rule never did: DESIGN.md section 16).
+template <typename Store>
+__device__ __forceinline__ void project_scatter_run(const float* __restrict__ pts, const int* __restrict__ offsets, int n_points, int batch,
+                                                    const ProjMats& M, int rows, int cols, Store store)
+{
+    const int i0 = blockIdx.x * 256;
+    const int lo_wg = project_wg_frame(offsets, batch, i0);
+    const int i = i0 + threadIdx.x;
+    if (i >= n_points) return;
+    int lo = lo_wg;
+    while (lo + 1 < batch && offsets[lo + 1] <= i) ++lo;            // lo_wg <= lo < batch whatever the offsets hold
+    const float4 p = *reinterpret_cast<const float4*>(pts + 4 * (size_t)i);       // x, y, z, reflectance (16-byte records)
+    int u, v; float d;
+    if (!project_point(M, p.x, p.y, p.z, rows, cols, u, v, d)) return;
+    store(lo, u, v, i, d);
+}
+
 // ---- a table of per-frame matrices (dcmt_project_calib, dcmt_calib.h) ---------------------------------------------------------
+// The matrices as the kernels' argument `geo`, the idiom of k_cloud_scatter (dcmt_kernels_cloud.h): ProjMats itself, by value
+// (dcmt_project_points*_dev), or the table (dcmt_project_points*_calib_dev)
+struct ProjTable { const dcmt_project_calib* __restrict__ records; };
+__device__ __forceinline__ const ProjMats& proj_m(const ProjMats& arg, const ProjMats&) { return arg; }
+__device__ __forceinline__ const ProjMats& proj_m(const ProjTable&, const ProjMats& rec) { return rec; }
+
+
 // A record as ProjMats; `ok`: every one of its 24 entries is finite, tested on the bits
 __device__ __forceinline__ bool load_project_record(const dcmt_project_calib* __restrict__ table, uint32_t f, ProjMats& M)
 {

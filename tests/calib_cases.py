@@ -200,6 +200,9 @@ def cases():
             project_case("project sweeps 16x24", 16, 24, (100, 0, 300, 37, 256, 1), 1),
             # 4 x 35 pixels: with PW == 4 the thread of pixels 32..35 has three of frame 0 and one of frame 1
             project_case("project straddle 5x7", 5, 7, (60, 60, 60, 60), 2),
+            # 600 pixels a frame: waves of the resolve inside a frame and across pixels 600 and 1200 at every store width; a sweep boundary
+            # inside a wave, one empty sweep (test_gpu_geo_instances.py)
+            project_case("project 20x30", 20, 30, (300, 0, 200), 3),
             reproject_case("reproject 6x9 -> 5x7", 4, 6, 9, 5, 7, 25),
             reproject_case("reproject 40x50 -> 33x41", 4, 40, 50, 33, 41, 8),          # two scatter workgroups per frame
             reproject_case("reproject 352x1216 pair", 2, 352, 1216, 352, 1216, 0, records=kitti, frames=full),
