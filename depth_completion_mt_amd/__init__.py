@@ -12,7 +12,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   slic_colour_with_cluster_means, get_initial_error, make_photo_error_params, make_sgm_params,
                   sgm_workspace_bytes, stereo_sgm, make_speckle_params, filter_speckles,
                   RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify,
-                  PLANE_FIT_DTYPE, make_planes_params, fit_superpixel_planes, superpixel_planes_max_labels)
+                  PLANE_FIT_DTYPE, make_planes_params, fit_superpixel_planes, superpixel_planes_max_labels,
+                  make_occlusion_params, filter_occluded_returns)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -24,7 +25,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "slic_display_contours", "slic_colour_with_cluster_means", "get_initial_error", "make_photo_error_params",
            "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm", "make_speckle_params", "filter_speckles",
            "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify",
-           "PLANE_FIT_DTYPE", "make_planes_params", "fit_superpixel_planes", "superpixel_planes_max_labels"]
+           "PLANE_FIT_DTYPE", "make_planes_params", "fit_superpixel_planes", "superpixel_planes_max_labels",
+           "make_occlusion_params", "filter_occluded_returns"]
 
 
 def __getattr__(name):

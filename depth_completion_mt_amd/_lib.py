@@ -50,6 +50,7 @@ EXPORTS = (
     "dcmt_default_speckle_params", "dcmt_filter_speckles_dev", "dcmt_filter_speckles",
     "dcmt_rectify_map_dev", "dcmt_rectify_dev", "dcmt_rectify",
     "dcmt_default_planes_params", "dcmt_superpixel_planes_max_labels", "dcmt_superpixel_planes_dev", "dcmt_superpixel_planes",
+    "dcmt_default_occlusion_params", "dcmt_sparse_occlusion_dev", "dcmt_sparse_occlusion_u16_dev", "dcmt_sparse_occlusion",
 )
 
 
@@ -137,6 +138,12 @@ class PlaneFit(ctypes.Structure):
     """Mirror of dcmt_plane_fit (include/dcmt.h): one label's record of dcmt_superpixel_planes_dev, 48 bytes."""
     _fields_ = [("a", ctypes.c_double), ("b", ctypes.c_double), ("c", ctypes.c_double), ("seen", ctypes.c_uint32), ("used", ctypes.c_uint32),
                 ("wmin", ctypes.c_uint32), ("wmax", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class OcclusionParams(ctypes.Structure):
+    """Mirror of dcmt_occlusion_params (include/dcmt.h), 20 bytes."""
+    _fields_ = [("rx", ctypes.c_int32), ("ry", ctypes.c_int32), ("tol_code", ctypes.c_int32), ("valid_thresh", ctypes.c_float),
+                ("max_depth", ctypes.c_float)]
 
 
 class CropSrc(ctypes.Structure):
@@ -296,6 +303,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_superpixel_planes_max_labels.argtypes = [i, i, i, i]
         L.dcmt_superpixel_planes_dev.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
         L.dcmt_superpixel_planes.argtypes = [vp, vp, sz, vp, sz, i, i, i, vp, vp, sz, vp]
+        L.dcmt_default_occlusion_params.argtypes = [vp]
+        L.dcmt_default_occlusion_params.restype = None
+        L.dcmt_sparse_occlusion_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_sparse_occlusion_u16_dev.argtypes = [vp, vp, ctypes.c_float, vp, i, i, i, vp, vp, vp]
+        L.dcmt_sparse_occlusion.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

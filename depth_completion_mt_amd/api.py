@@ -298,6 +298,43 @@ def superpixel_planes_max_labels(max_rows: int, max_cols: int, max_batch: int, b
     return int(L.lib().dcmt_superpixel_planes_max_labels(int(max_rows), int(max_cols), int(max_batch), int(batch)))
 
 
+def make_occlusion_params(rx: int | None = None, ry: int | None = None, inv_depth_tol: float | None = None, valid_thresh: float | None = None,
+                          max_depth: float | None = None, tol_code: int | None = None) -> L.OcclusionParams:
+    """dcmt_occlusion_params: rx 3, ry 6, tol_code 655 (0.01 / m), valid_thresh 0.1, max_depth 100 unless overridden.  The tolerance is
+    given in inverse metres (inv_depth_tol, converted as round(65536 * tol)) or in codes (tol_code), not both.  Raises ValueError on
+    what dcmt_sparse_occlusion_dev refuses of them: rx outside 0..8, ry outside 0..16, a tolerance outside 0..2^20 codes,
+    valid_thresh not finite or < 0.0625, max_depth not finite, < valid_thresh or > 16384."""
+    p = L.OcclusionParams()
+    L.lib().dcmt_default_occlusion_params(ctypes.byref(p))
+    if inv_depth_tol is not None:
+        if tol_code is not None:
+            raise ValueError("inv_depth_tol and tol_code: one of them")
+        if not np.isfinite(np.float64(inv_depth_tol)):
+            raise ValueError(f"inv_depth_tol = {inv_depth_tol!r}: a finite float")
+        tol_code = int(round(65536.0 * float(inv_depth_tol)))
+    for name, v in (("rx", rx), ("ry", ry), ("tol_code", tol_code)):
+        if v is not None:
+            if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+                raise ValueError(f"{name} = {v!r} is not an int32")
+            setattr(p, name, int(v))
+    for name, v in (("valid_thresh", valid_thresh), ("max_depth", max_depth)):
+        if v is not None:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} = {v!r}: a finite float")
+            setattr(p, name, float(v))
+    if not 0 <= p.rx <= 8:
+        raise ValueError(f"rx = {p.rx}: 0 .. 8")
+    if not 0 <= p.ry <= 16:
+        raise ValueError(f"ry = {p.ry}: 0 .. 16")
+    if not 0 <= p.tol_code <= 1 << 20:
+        raise ValueError(f"tol_code = {p.tol_code}: 0 .. 2^20 (inv_depth_tol 0 .. 16)")
+    if not p.valid_thresh >= 0.0625:
+        raise ValueError(f"valid_thresh = {p.valid_thresh}: >= 0.0625 (the codes stay at or below 2^20)")
+    if not p.valid_thresh <= p.max_depth <= 16384.0:
+        raise ValueError(f"max_depth = {p.max_depth}: valid_thresh .. 16384")
+    return p
+
+
 SGM_MAX_P2_EIGHT_PATHS = 1800      # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
 
 
@@ -1122,6 +1159,52 @@ class Context:
         _check(st, "dcmt_superpixel_planes")
         return out, fits
 
+    # ---- occlusion filter of projected LiDAR returns (dcmt_sparse_occlusion*) ------------------
+    def sparse_occlusion_dev(self, d_sparse, d_out=None, removed: bool = False, d_removed=None, u16: bool = False, scale: float = 1.0 / 256.0,
+                             stream: int | None = None, **kw):
+        """Removes from a sparse depth plane every return that a nearer return in the window (2 rx + 1) x (2 ry + 1) around it shows to
+        be hidden from the camera (dcmt_sparse_occlusion_dev, as include/dcmt.h states it), without synchronising: between
+        project_points_dev(nearest=True) and complete_dev, superpixel_planes_dev or sgm_dev(d_guide=...).  d_sparse: f32 CUDA tensor
+        [batch][rows][cols] (or [rows][cols]), metres, 0 = no return; with u16=True the KITTI uint16 payload complete_u16_dev
+        ingests (a uint16 or int16 tensor, metres = value * scale; dcmt_sparse_occlusion_u16_dev).  d_out: where the result goes (may
+        be d_sparse itself: in place), allocated where not given.  Returns d_out, or (d_out, removed) with removed=True or a
+        d_removed: the int32 CUDA tensor [batch] of the pixels changed per frame.  kw: the fields of make_occlusion_params.  Outputs
+        that are not given are allocated on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_sparse) and (d_sparse.element_size() == 2 and not d_sparse.is_floating_point() if u16 else d_sparse.dtype == torch.float32)
+        b, r, c = _brc(d_sparse)
+        p = make_occlusion_params(**kw)
+        want_removed = removed or d_removed is not None
+        with _on_stream(stream, d_sparse):
+            if d_out is None:
+                d_out = torch.empty(tuple(d_sparse.shape), dtype=d_sparse.dtype, device=d_sparse.device)
+            if want_removed and d_removed is None:
+                d_removed = torch.empty((b,), dtype=torch.int32, device=d_sparse.device)
+        assert _is_dev(d_out, d_sparse.dtype) and d_out.numel() == b * r * c
+        assert d_removed is None or (_is_dev(d_removed) and d_removed.element_size() == 4 and d_removed.numel() == b)
+        rem = d_removed.data_ptr() if want_removed else None
+        if u16:
+            st = L.lib().dcmt_sparse_occlusion_u16_dev(self._h, d_sparse.data_ptr(), float(scale), d_out.data_ptr(), r, c, b, ctypes.byref(p), rem,
+                                                       _stream(stream, d_sparse))
+        else:
+            st = L.lib().dcmt_sparse_occlusion_dev(self._h, d_sparse.data_ptr(), d_out.data_ptr(), r, c, b, ctypes.byref(p), rem, _stream(stream, d_sparse))
+        _check(st, "dcmt_sparse_occlusion_u16_dev" if u16 else "dcmt_sparse_occlusion_dev")
+        return (d_out, d_removed) if want_removed else d_out
+
+    def sparse_occlusion(self, depth: np.ndarray, **kw):
+        """One frame of host memory (dcmt_sparse_occlusion, synchronous; any row stride): (the filtered f32 plane, the number of
+        returns removed).  The plane is a new array; the argument is not modified."""
+        z = np.asarray(depth, dtype=np.float32)
+        assert z.ndim == 2
+        z = z if z.strides[1] == 4 else np.ascontiguousarray(z)
+        out = np.empty(z.shape, dtype=np.float32)
+        n = ctypes.c_uint32(0)
+        p = make_occlusion_params(**kw)
+        st = L.lib().dcmt_sparse_occlusion(self._h, z.ctypes.data, z.strides[0], out.ctypes.data, out.strides[0], z.shape[0], z.shape[1], ctypes.byref(p),
+                                           ctypes.byref(n))
+        _check(st, "dcmt_sparse_occlusion")
+        return out, int(n.value)
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1669,6 +1752,14 @@ def fit_superpixel_planes(depth, labels, n_labels: int, **params):
     PLANE_FIT_DTYPE).  params: the fields of make_planes_params."""
     z = np.asarray(depth, dtype=np.float32)
     return _ctx_for(z.shape[0], z.shape[1], 1).superpixel_planes(z, labels, n_labels, **params)
+
+
+def filter_occluded_returns(depth, **params):
+    """The occlusion filter of one host frame (dcmt_sparse_occlusion, as include/dcmt.h states it): depth f32 [rows][cols] in metres
+    with 0 = no return -> the plane without the returns a nearer return in the window shows to be hidden from the camera (a new
+    array).  params: the fields of make_occlusion_params."""
+    z = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).sparse_occlusion(z, **params)[0]
 
 
 def depth_to_u16(depth, scale: float = 256.0):

@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h),
 // dcmt_photo_error_dev (dcmt_kernels_photo.h), the defaults of their parameter structs and dcmt_lab_tables.  A *_calib_dev entry point
 // shares its one launch sequence with the uniform entry point beside it: the calibration source (one record by value, or the device
 // table) is the kernels' template type.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame
@@ -23,6 +23,7 @@
 #include "dcmt_kernels_contour.h"
 #include "dcmt_kernels_photo.h"
 #include "dcmt_kernels_planes.h"
+#include "dcmt_kernels_occlusion.h"
 
 using namespace dcmt;
 
@@ -610,6 +611,66 @@ int dcmt_superpixel_planes_dev(dcmt_ctx* ctx, const float* d_depth, const int32_
         hipLaunchKernelGGL(k_planes_paint<1>, dim3(pl.paint_x, batch), dim3(256), 0, st, depth, d_labels, pl.n, c, nl, lo, hi, params->keep_returns, fits, out);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- the occlusion filter of a sparse depth plane (dcmt_kernels_occlusion.h) ------------------------------------------------------
+// The launches plan_sparse_occlusion names, for an f32 plane (T = its bits) or the uint16 payload: the mask of an in-place call on
+// pp[0] (scratch every completion call rewrites before it reads it).  None of the context's carried state is read or written, and
+// nothing is allocated.
+template <typename T>
+static int sparse_occlusion_enqueue(dcmt_ctx* ctx, const T* d_sparse, float scale, bool scale_ok, T* d_out, int rows, int cols, int batch,
+                                    const dcmt_occlusion_params* params, uint32_t* d_removed, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const uint32_t lo = planes_bits(&params->valid_thresh), hi = planes_bits(&params->max_depth);
+    const bool ok = scale_ok && plan::occlusion_params_ok(params->rx, params->ry, params->tol_code, lo, hi);
+    const plan::OcclusionPlan pl = plan::plan_sparse_occlusion(rows, cols, batch, (int)sizeof(T), ok, params->rx, params->ry, (uintptr_t)d_sparse,
+                                                               (uintptr_t)d_out, (uintptr_t)d_removed);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, tol = (uint32_t)params->tol_code;
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_removed, 0, pl.clear_bytes, st));
+    if (pl.in_place) {
+        uint32_t* mask = reinterpret_cast<uint32_t*>(ctx->pp[0].p);
+        hipLaunchKernelGGL((k_occl<T, false>), dim3(pl.grid, batch), dim3(256), pl.lds_bytes, st, d_sparse, r, c, pl.tiles_x, params->rx, params->ry, tol, lo, hi,
+                           scale, (T*)nullptr, mask, pl.words_x, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_occl_apply<T>), dim3(pl.apply_x, batch), dim3(256), 0, st, mask, r, c, pl.words_x, d_out, d_removed);
+    } else {
+        hipLaunchKernelGGL((k_occl<T, true>), dim3(pl.grid, batch), dim3(256), pl.lds_bytes, st, d_sparse, r, c, pl.tiles_x, params->rx, params->ry, tol, lo, hi,
+                           scale, d_out, (uint32_t*)nullptr, pl.words_x, d_removed);
+    }
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+void dcmt_default_occlusion_params(dcmt_occlusion_params* p)
+{
+    if (!p) return;
+    p->rx = 3;              // dcmt.h derives the three: an HDL-64's azimuth step is at most 2.3 columns at f = 721.5,
+    p->ry = 6;              // its ring spacing 5.04 rows,
+    p->tol_code = 655;      // and 0.01 / m is twice what a 1.65 m ground plane changes over ry rows
+    p->valid_thresh = 0.1f; // the planes' defaults
+    p->max_depth = 100.0f;
+}
+
+int dcmt_sparse_occlusion_dev(dcmt_ctx* ctx, const float* d_sparse, float* d_out, int rows, int cols, int batch, const dcmt_occlusion_params* params,
+                              uint32_t* d_removed, void* stream)
+{
+    return sparse_occlusion_enqueue(ctx, reinterpret_cast<const uint32_t*>(d_sparse), 1.0f, true, reinterpret_cast<uint32_t*>(d_out), rows, cols, batch,
+                                    params, d_removed, stream);
+}
+
+int dcmt_sparse_occlusion_u16_dev(dcmt_ctx* ctx, const uint16_t* d_sparse, float scale, uint16_t* d_out, int rows, int cols, int batch,
+                                  const dcmt_occlusion_params* params, uint32_t* d_removed, void* stream)
+{
+    volatile float m = scale;                         // read through memory, as finite_bits does: the compiler may assume an argument finite
+    const float s = m;
+    return sparse_occlusion_enqueue(ctx, d_sparse, s, plan::occlusion_scale_ok(planes_bits(&s)), d_out, rows, cols, batch, params, d_removed, stream);
 }
 
 }  // extern "C"

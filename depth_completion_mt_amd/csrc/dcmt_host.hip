@@ -360,6 +360,18 @@ int dcmt_superpixel_planes(dcmt_ctx* ctx, const float* depth, size_t drs, const 
     return rc == DCMT_OK ? fetch(ctx, {&o, &f}) : rc;
 }
 
+int dcmt_sparse_occlusion(dcmt_ctx* ctx, const float* sparse, size_t srs, float* out, size_t ors, int rows, int cols, const dcmt_occlusion_params* params,
+                          uint32_t* removed)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !sparse || !out || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t rb = sizeof(float) * (size_t)cols;
+    Plane z(sparse, srs, rb, rows), o(out, ors, rb, rows), n(removed, sizeof(uint32_t));
+    int rc = stage(ctx, {&z}, {&o, &n});
+    if (rc == DCMT_OK) rc = dcmt_sparse_occlusion_dev(ctx, (const float*)z.dev, (float*)o.dev, rows, cols, 1, params, (uint32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

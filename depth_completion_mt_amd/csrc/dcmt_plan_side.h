@@ -13,6 +13,7 @@
 #include "dcmt_connect.h"
 #include "dcmt_contour.h"
 #include "dcmt_crop.h"
+#include "dcmt_occlusion.h"
 #include "dcmt_photo.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_planes.h"
@@ -483,6 +484,67 @@ inline PlanesPlan plan_superpixel_planes(int rows, int cols, int batch, int n_la
     p.launches = refit ? 7 : 4;
     p.scratch0 = 4 * p.words;
     p.scratch1 = fits ? 0 : fb;
+    return p;
+}
+
+// ---- dcmt_sparse_occlusion_dev, dcmt_sparse_occlusion_u16_dev --------------------------------------------------------------
+// The occlusion filter of a sparse depth plane (dcmt_kernels_occlusion.h).  Out of place: one fused kernel that decides and writes.
+// In place (out == sparse exactly): a neighbouring workgroup may already have zeroed a pixel of another workgroup's halo, and every
+// decision is taken on the input; so k_occl<T, false> decides into a mask plane of one bit per pixel on pp[0], [frame][row][words_x]
+// 32-bit words, and k_occl_apply zeroes and counts.  words_x <= cols, so the mask of a call never exceeds the borrowed plane.  A clear
+// of `removed` goes in front where it is given.  The checks on the arguments are here as well, tested without a device.
+
+// what dcmt_occlusion_params may hold (dcmt.h); the depth bounds are the planes' and come as their bits
+inline bool occlusion_params_ok(int64_t rx, int64_t ry, int64_t tol_code, uint32_t valid_thresh_bits, uint32_t max_depth_bits)
+{
+    if (rx < 0 || rx > kOcclMaxRx || ry < 0 || ry > kOcclMaxRy || tol_code < 0 || tol_code > kOcclMaxTol) return false;
+    if (valid_thresh_bits < kPlanesMinThreshBits || valid_thresh_bits >= 0x7f800000u) return false;
+    return max_depth_bits >= valid_thresh_bits && max_depth_bits <= kPlanesMaxDepthBits;
+}
+
+// the payload's metres per unit: a positive finite float
+inline bool occlusion_scale_ok(uint32_t scale_bits) { return scale_bits > 0u && scale_bits < 0x7f800000u; }
+
+struct OcclusionPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, bad parameters, buffers that overlap
+    bool in_place;                   // out == sparse: decide into the mask, then apply; else the fused kernel
+    uint32_t tiles_x, tiles_y;
+    unsigned grid;                   // k_occl: (grid, batch)
+    uint32_t lds_bytes;              // ... its dynamic LDS
+    uint32_t words_x;                // mask words per row: ceil(cols / 32)
+    size_t frame_words;              // ... per frame: rows * words_x
+    unsigned apply_x;                // k_occl_apply: (apply_x, batch); 0 out of place
+    size_t scratch;                  // bytes of pp[0] the call uses: 4 * batch * frame_words in place, 0 out of place
+    size_t plane_bytes;              // batch * rows * cols * elem: what the kernels' 64-bit offsets span
+    size_t clear_bytes;              // hipMemsetAsync of removed: 4 bytes a frame (0: no counts wanted)
+    int launches;                    // 1 or 2, one more with removed
+};
+
+// rows, cols, batch >= 1 and within the context's limits; elem: 4 (f32) or 2 (the payload); params_ok: occlusion_params_ok (and
+// occlusion_scale_ok) of the call's parameters; removed: 0 = not wanted
+inline OcclusionPlan plan_sparse_occlusion(int rows, int cols, int batch, int elem, bool params_ok, int rx, int ry, uintptr_t sparse,
+                                           uintptr_t out, uintptr_t removed)
+{
+    OcclusionPlan p = {};
+    p.status = kInvalid;
+    if (!sparse || !out || !params_ok || (elem != 2 && elem != 4)) return p;
+    if (sparse % (uintptr_t)elem != 0 || out % (uintptr_t)elem != 0 || removed % 4 != 0) return p;
+    const size_t bytes = (size_t)elem * (size_t)batch * (size_t)rows * (size_t)cols, rb = sizeof(uint32_t) * (size_t)batch;
+    if (out != sparse && ranges_overlap(sparse, bytes, out, bytes)) return p;
+    if (removed && (ranges_overlap(removed, rb, sparse, bytes) || ranges_overlap(removed, rb, out, bytes))) return p;
+    p.status = kOk;
+    p.in_place = out == sparse;
+    p.tiles_x = ((uint32_t)cols + kOcclTile - 1) / kOcclTile;
+    p.tiles_y = ((uint32_t)rows + kOcclTile - 1) / kOcclTile;
+    p.grid = p.tiles_x * p.tiles_y;
+    p.lds_bytes = occl_lds_bytes(rx, ry);
+    p.words_x = ((uint32_t)cols + 31) / 32;
+    p.frame_words = (size_t)rows * p.words_x;
+    p.apply_x = p.in_place ? (unsigned)((p.frame_words + 255) / 256) : 0u;
+    p.scratch = p.in_place ? 4 * (size_t)batch * p.frame_words : 0;
+    p.plane_bytes = bytes;
+    p.clear_bytes = removed ? rb : 0;
+    p.launches = (p.in_place ? 2 : 1) + (removed ? 1 : 0);
     return p;
 }
 

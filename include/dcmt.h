@@ -484,6 +484,70 @@ int dcmt_superpixel_planes(dcmt_ctx *ctx, const float *depth, size_t depth_row_s
                            int rows, int cols, int n_labels, const dcmt_planes_params *params, float *out, size_t out_row_stride,
                            dcmt_plane_fit *fits);
 
+/* ---- occlusion filter of projected LiDAR returns ------------------------------------------------------- */
+
+/* The LiDAR and the camera sit in different places, so a sweep holds returns from surfaces the camera cannot see; projected, those
+ * background returns land inside the silhouette of the foreground object that hides them, between its own returns.
+ * dcmt_project_points_nearest_dev settles only two points on the SAME pixel; a background return one pixel beside a foreground one
+ * survives, and the cascade, the planes above and the guided matcher all take it at its word.  This call removes from a sparse depth
+ * plane every return that a nearer return in a small window shows to be hidden.  Not in the reference; stated here to the last bit:
+ * all integers after one division per return.  It belongs between the projection and dcmt_complete_*_dev,
+ * dcmt_superpixel_planes_dev and dcmt_sgm_guided_dev.  Per frame, on an f32 plane [rows][cols]:
+ *
+ * RETURN.  A pixel is a return iff its depth z is a finite float with valid_thresh <= z <= max_depth, decided on the bit pattern
+ *   exactly as dcmt_superpixel_planes_dev decides it: NaN, +-inf, negatives and -0.0 are no returns.
+ * CODE.  w = (uint32) rne(65536.0f / z): the planes' code (one correctly rounded f32 division, then round to nearest even).  With
+ *   valid_thresh >= 0.0625 and max_depth <= 16384 (both enforced, as there) 4 <= w <= 2^20.  A pixel that is no return has code 0.
+ * WINDOW MAXIMUM.  m(y, x) = the largest code over the pixels (y + dy, x + dx) with |dy| <= ry, |dx| <= rx that lie inside the
+ *   frame.  The window is clipped: no border replication, and it never reaches into another frame of the batch.
+ * OCCLUDED.  A return is occluded iff m - w > tol_code, in integers.  Every decision is taken on the INPUT plane: a return that is
+ *   itself removed still hides others, so the result depends on no order.
+ * OUTPUT.  An occluded return becomes +0.0f.  Every other pixel, the pixels that are no returns included, keeps its bits.
+ * d_removed, or NULL: uint32 [batch], the number of pixels changed per frame.
+ * Nothing depends on the batch size, the frame's position in the batch, alignment, the launch geometry, the run, or on whether
+ * the call is in place.
+ *
+ * Why inverse depth: a planar surface is affine in inverse depth over the image, so a fixed tolerance in codes does not eat slanted
+ * surfaces at range; a relative tolerance in metres does (on a ground plane 1.65 m below the camera, neighbouring rings at 50 m
+ * differ by 20 % in depth).  The defaults are derived, not tuned.  rx = 3, ry = 6: an HDL-64's ring spacing of 0.4 deg is 5.04 rows
+ * at KITTI's focal length of 721.5 and its azimuth step at most 2.3 columns, so the window holds a foreground return wherever the
+ * foreground covers it.  tol_code = 655 (0.01 / m): a ground plane 1.65 m below the camera changes by 55 codes a row, 330 over
+ * ry = 6: a margin of 2; and a background return whose gap to the foreground is below the tolerance is misplaced by under 0.01 f b ~ 2 pixels for a
+ * sensor offset b of 0.3 m.  valid_thresh and max_depth are the planes' defaults.
+ *
+ * The payload form, dcmt_sparse_occlusion_u16_dev, is the same filter on the KITTI uint16 payload dcmt_complete_u16_dev ingests:
+ * the depth of a payload value v is what that ingest states, the f32 product (float) v * scale rounded once; an occluded return
+ * becomes 0.  The same kernels, instantiated on the element type.
+ *
+ * DEVICE pointers, stream-ordered; never synchronises, never allocates.  Out of place: one launch, which decides and writes.  In
+ * place (d_out == d_sparse): two, because a neighbouring workgroup may already have zeroed what another still has to read: the
+ * decisions go to a mask of one bit per pixel, then they are applied.  A clear of d_removed goes in front where it is given.  Both
+ * routes give the same bytes.  Scratch: the first of the two planes dcmt_create allocates (the ones dcmt_slic_connectivity_dev and
+ * dcmt_filter_speckles_dev borrow), in place only.  Of the context's carried state it touches none, dcmt_last_path included: it can
+ * be queued in front of or behind any other *_dev call.
+ * DCMT_E_INVALID, nothing written: a null ctx, plane, output or params; sizes or a batch beyond the context's limits; rx outside
+ * 0..8, ry outside 0..16, tol_code outside 0..2^20; valid_thresh not finite or < 0.0625; max_depth not finite, < valid_thresh or
+ * > 16384; scale not finite or <= 0 (the payload form); planes not aligned to their element, d_removed not 4-byte aligned; any
+ * overlap among the buffers other than d_out == d_sparse exactly. */
+typedef struct {
+    int32_t rx;             /* 3     half width of the window, columns; 0..8                                       */
+    int32_t ry;             /* 6     half height of the window, rows; 0..16                                        */
+    int32_t tol_code;       /* 655   a return is occluded where the window's largest code exceeds its own by more  */
+                            /*       than this; in codes of 1 / 65536 per metre (655 = 0.01 / m); 0..2^20          */
+    float   valid_thresh;   /* 0.1   the smallest depth that is a return, metres; >= 0.0625                        */
+    float   max_depth;      /* 100   the largest; <= 16384                                                         */
+} dcmt_occlusion_params;    /* 20 bytes */
+void dcmt_default_occlusion_params(dcmt_occlusion_params *p);
+int dcmt_sparse_occlusion_dev(dcmt_ctx *ctx, const float *d_sparse, float *d_out /* may be d_sparse */, int rows, int cols, int batch,
+                              const dcmt_occlusion_params *params, uint32_t *d_removed /* [batch] or NULL */, void *stream);
+int dcmt_sparse_occlusion_u16_dev(dcmt_ctx *ctx, const uint16_t *d_sparse, float scale /* 1./256 for KITTI */,
+                                  uint16_t *d_out /* may be d_sparse */, int rows, int cols, int batch,
+                                  const dcmt_occlusion_params *params, uint32_t *d_removed /* [batch] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES, >= 4 * cols); out may be sparse; removed: one count or NULL.  The
+ * same bits as the device call.  What dcmt_shim::filter_occluded_returns calls. */
+int dcmt_sparse_occlusion(dcmt_ctx *ctx, const float *sparse, size_t sparse_row_stride, float *out, size_t out_row_stride, int rows, int cols,
+                          const dcmt_occlusion_params *params, uint32_t *removed);
+
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 
 /* What DC_stereo_lidar/main_sl.cpp does with the dense depth (:1165-1246): depth -> disparity (get_initial_disparity

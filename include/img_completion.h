@@ -513,6 +513,26 @@ inline void fit_superpixel_planes(const std::vector<std::vector<int> >& clusters
     planes_img = out;
 }
 
+// The occlusion filter of projected LiDAR returns, as dcmt.h states it (dcmt_sparse_occlusion): sparse_r_img CV_32FC1 in metres with
+// 0 = no return, as project_points leaves it; filtered_img is overwritten with a fresh CV_32FC1 image in which every return that a
+// nearer return in the window shows to be hidden from the camera is 0 -- what img_completion, fit_superpixel_planes and the guided
+// matcher then take.  params == nullptr: dcmt_default_occlusion_params.  Returns the number of returns removed.
+inline unsigned filter_occluded_returns(const cv::Mat& sparse_r_img, cv::Mat& filtered_img, const dcmt_occlusion_params* params = nullptr)
+{
+    check_input(sparse_r_img);
+    const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
+    dcmt_occlusion_params def;
+    dcmt_default_occlusion_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    uint32_t removed = 0;
+    raise(dcmt_sparse_occlusion(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], out.ptr<float>(), out.step[0], rows, cols,
+                                params ? params : &def, &removed),
+          "filter_occluded_returns");
+    filtered_img = out;
+    return removed;
+}
+
 // unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
 // takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
