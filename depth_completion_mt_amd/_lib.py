@@ -51,6 +51,7 @@ EXPORTS = (
     "dcmt_rectify_map_dev", "dcmt_rectify_dev", "dcmt_rectify",
     "dcmt_default_planes_params", "dcmt_superpixel_planes_max_labels", "dcmt_superpixel_planes_dev", "dcmt_superpixel_planes",
     "dcmt_default_occlusion_params", "dcmt_sparse_occlusion_dev", "dcmt_sparse_occlusion_u16_dev", "dcmt_sparse_occlusion",
+    "dcmt_default_support_params", "dcmt_support_distance_dev", "dcmt_support_distance_u16_dev", "dcmt_support_distance",
 )
 
 
@@ -144,6 +145,11 @@ class OcclusionParams(ctypes.Structure):
     """Mirror of dcmt_occlusion_params (include/dcmt.h), 20 bytes."""
     _fields_ = [("rx", ctypes.c_int32), ("ry", ctypes.c_int32), ("tol_code", ctypes.c_int32), ("valid_thresh", ctypes.c_float),
                 ("max_depth", ctypes.c_float)]
+
+
+class SupportParams(ctypes.Structure):
+    """Mirror of dcmt_support_params (include/dcmt.h), 12 bytes."""
+    _fields_ = [("max_radius", ctypes.c_int32), ("valid_thresh", ctypes.c_float), ("max_depth", ctypes.c_float)]
 
 
 class CropSrc(ctypes.Structure):
@@ -308,6 +314,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_sparse_occlusion_dev.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_sparse_occlusion_u16_dev.argtypes = [vp, vp, ctypes.c_float, vp, i, i, i, vp, vp, vp]
         L.dcmt_sparse_occlusion.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp]
+        L.dcmt_default_support_params.argtypes = [vp]
+        L.dcmt_default_support_params.restype = None
+        L.dcmt_support_distance_dev.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_support_distance_u16_dev.argtypes = [vp, vp, ctypes.c_float, vp, vp, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_support_distance.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, i, i, vp, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

@@ -335,6 +335,30 @@ def make_occlusion_params(rx: int | None = None, ry: int | None = None, inv_dept
     return p
 
 
+def make_support_params(max_radius: int | None = None, valid_thresh: float | None = None, max_depth: float | None = None) -> L.SupportParams:
+    """dcmt_support_params: max_radius 9, valid_thresh 0.1, max_depth 100 unless overridden.  Raises ValueError on what
+    dcmt_support_distance_dev refuses of them: max_radius outside 1..255, valid_thresh not finite or < 0.0625, max_depth not finite,
+    < valid_thresh or > 16384."""
+    p = L.SupportParams()
+    L.lib().dcmt_default_support_params(ctypes.byref(p))
+    if max_radius is not None:
+        if isinstance(max_radius, bool) or int(max_radius) != max_radius or not -2 ** 31 <= int(max_radius) < 2 ** 31:
+            raise ValueError(f"max_radius = {max_radius!r} is not an int32")
+        p.max_radius = int(max_radius)
+    for name, v in (("valid_thresh", valid_thresh), ("max_depth", max_depth)):
+        if v is not None:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} = {v!r}: a finite float")
+            setattr(p, name, float(v))
+    if not 1 <= p.max_radius <= 255:
+        raise ValueError(f"max_radius = {p.max_radius}: 1 .. 255 (255^2 stays below the marker 65535)")
+    if not p.valid_thresh >= 0.0625:
+        raise ValueError(f"valid_thresh = {p.valid_thresh}: >= 0.0625")
+    if not p.valid_thresh <= p.max_depth <= 16384.0:
+        raise ValueError(f"max_depth = {p.max_depth}: valid_thresh .. 16384")
+    return p
+
+
 SGM_MAX_P2_EIGHT_PATHS = 1800      # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
 
 
@@ -1205,6 +1229,72 @@ class Context:
         _check(st, "dcmt_sparse_occlusion")
         return out, int(n.value)
 
+    # ---- distance to the nearest return and the trust mask (dcmt_support_distance*) -------------
+    def support_distance_dev(self, d_sparse, d_dense=None, d_fallback=None, d_out=None, dist2: bool = False, d_dist2=None, beyond: bool = False,
+                             d_beyond=None, u16: bool = False, scale: float = 1.0 / 256.0, stream: int | None = None, **kw):
+        """The support map of a sparse depth plane and the trust mask of a dense one (dcmt_support_distance_dev, as include/dcmt.h
+        states it), without synchronising.  d_sparse: f32 CUDA tensor [batch][rows][cols] (or [rows][cols]), metres; with u16=True the
+        KITTI uint16 payload (a uint16 or int16 tensor, metres = value * scale; dcmt_support_distance_u16_dev).  With d_dense (f32, the
+        same shape) the trust mask goes to d_out (may be d_dense itself: in place; allocated where not given): d_dense within
+        max_radius of a return, beyond it d_fallback (f32) or +0.0.  dist2=True or a d_dist2 (any 2-byte dtype): the uint16 plane of
+        squared distances, 65535 beyond max_radius; it is also what a call without d_dense produces.  beyond=True or a d_beyond
+        (any 4-byte dtype, [batch]): the pixels beyond max_radius per frame, as int32.  Returns the outputs wanted in the order
+        (d_out, d_dist2, d_beyond): the tensor itself where that is one, else a tuple.  kw: the fields of make_support_params.
+        Outputs that are not given are allocated on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_sparse) and (d_sparse.element_size() == 2 and not d_sparse.is_floating_point() if u16 else d_sparse.dtype == torch.float32)
+        b, r, c = _brc(d_sparse)
+        p = make_support_params(**kw)
+        if d_dense is None and (d_out is not None or d_fallback is not None):
+            raise ValueError("d_out and d_fallback go with a d_dense")
+        want_out = d_dense is not None
+        want_dist2 = dist2 or d_dist2 is not None or not want_out
+        want_beyond = beyond or d_beyond is not None
+        with _on_stream(stream, d_sparse):
+            if want_out and d_out is None:
+                d_out = torch.empty(tuple(d_sparse.shape), dtype=torch.float32, device=d_sparse.device)
+            if want_dist2 and d_dist2 is None:
+                d_dist2 = torch.empty(tuple(d_sparse.shape), dtype=torch.uint16, device=d_sparse.device)
+            if want_beyond and d_beyond is None:
+                d_beyond = torch.empty((b,), dtype=torch.int32, device=d_sparse.device)
+        for t in (d_dense, d_fallback, d_out):
+            assert t is None or (_is_dev(t, torch.float32) and t.numel() == b * r * c)
+        assert d_dist2 is None or (_is_dev(d_dist2) and d_dist2.element_size() == 2 and d_dist2.numel() == b * r * c)
+        assert d_beyond is None or (_is_dev(d_beyond) and d_beyond.element_size() == 4 and d_beyond.numel() == b)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        tail = (ptr(d_dense), ptr(d_fallback), ptr(d_out), ptr(d_dist2), r, c, b, ctypes.byref(p), ptr(d_beyond), _stream(stream, d_sparse))
+        if u16:
+            st = L.lib().dcmt_support_distance_u16_dev(self._h, d_sparse.data_ptr(), float(scale), *tail)
+        else:
+            st = L.lib().dcmt_support_distance_dev(self._h, d_sparse.data_ptr(), *tail)
+        _check(st, "dcmt_support_distance_u16_dev" if u16 else "dcmt_support_distance_dev")
+        got = tuple(t for t, w in ((d_out, want_out), (d_dist2, want_dist2), (d_beyond, want_beyond)) if w)
+        return got[0] if len(got) == 1 else got
+
+    def support_distance(self, sparse: np.ndarray, dense=None, fallback=None, **kw):
+        """One frame of host memory (dcmt_support_distance, synchronous; any row stride).  Without dense: (the uint16 plane of squared
+        distances to the nearest return, 65535 beyond max_radius; the number of pixels beyond it).  With dense: (the trust mask, a new
+        f32 array: dense within max_radius of a return, elsewhere fallback or +0.0; that plane of distances; that count)."""
+        z = _frame_f32(sparse)
+        rows, cols = z.shape
+        d = f = out = None
+        if dense is not None:
+            d = _frame_f32(dense)
+            assert d.shape == z.shape
+            out = np.empty(z.shape, dtype=np.float32)
+        if fallback is not None:
+            if dense is None:
+                raise ValueError("a fallback goes with a dense plane")
+            f = _frame_f32(fallback)
+            assert f.shape == z.shape
+        dist2 = np.empty(z.shape, dtype=np.uint16)
+        n = ctypes.c_uint32(0)
+        p = make_support_params(**kw)
+        at = lambda a: (None, 0) if a is None else (a.ctypes.data, a.strides[0])
+        st = L.lib().dcmt_support_distance(self._h, *at(z), *at(d), *at(f), *at(out), *at(dist2), rows, cols, ctypes.byref(p), ctypes.byref(n))
+        _check(st, "dcmt_support_distance")
+        return (dist2, int(n.value)) if out is None else (out, dist2, int(n.value))
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1760,6 +1850,22 @@ def filter_occluded_returns(depth, **params):
     array).  params: the fields of make_occlusion_params."""
     z = np.asarray(depth, dtype=np.float32)
     return _ctx_for(z.shape[0], z.shape[1], 1).sparse_occlusion(z, **params)[0]
+
+
+def distance_to_returns(sparse, **params):
+    """The support map of one host frame (dcmt_support_distance, as include/dcmt.h states it): sparse f32 [rows][cols] in metres ->
+    uint16 [rows][cols], the exact squared Euclidean distance to the nearest return where that is at most max_radius^2 (default 9),
+    65535 everywhere else.  params: the fields of make_support_params."""
+    z = np.asarray(sparse, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).support_distance(z, **params)[0]
+
+
+def trust_mask(sparse, dense, fallback=None, **params):
+    """The trust mask of one host frame (dcmt_support_distance): dense where a return of sparse lies within max_radius (default 9),
+    elsewhere fallback (the stereo matcher's depth, say) or 0 -- a new f32 array; the bits are copied, a NaN keeps its own.
+    params: the fields of make_support_params."""
+    z = np.asarray(sparse, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).support_distance(z, dense, fallback, **params)[0]
 
 
 def depth_to_u16(depth, scale: float = 256.0):

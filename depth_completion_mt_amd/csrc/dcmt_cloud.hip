@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h), dcmt_support_distance_dev and dcmt_support_distance_u16_dev (dcmt_kernels_support.h),
 // dcmt_photo_error_dev (dcmt_kernels_photo.h), the defaults of their parameter structs and dcmt_lab_tables.  A *_calib_dev entry point
 // shares its one launch sequence with the uniform entry point beside it: the calibration source (one record by value, or the device
 // table) is the kernels' template type.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame
@@ -24,6 +24,7 @@
 #include "dcmt_kernels_photo.h"
 #include "dcmt_kernels_planes.h"
 #include "dcmt_kernels_occlusion.h"
+#include "dcmt_kernels_support.h"
 
 using namespace dcmt;
 
@@ -671,6 +672,64 @@ int dcmt_sparse_occlusion_u16_dev(dcmt_ctx* ctx, const uint16_t* d_sparse, float
     volatile float m = scale;                         // read through memory, as finite_bits does: the compiler may assume an argument finite
     const float s = m;
     return sparse_occlusion_enqueue(ctx, d_sparse, s, plan::occlusion_scale_ok(planes_bits(&s)), d_out, rows, cols, batch, params, d_removed, stream);
+}
+
+}  // extern "C"
+
+// ---- the distance to the nearest return and the trust mask (dcmt_kernels_support.h) -----------------------------------------------
+// The launches plan_support_distance names, for an f32 sparse plane (T = its bits) or the uint16 payload: the column distances on
+// pp[0] (scratch every completion call rewrites before it reads it), then the row pass, which writes every output.  None of the
+// context's carried state is read or written, and nothing is allocated.
+template <typename T>
+static int support_distance_enqueue(dcmt_ctx* ctx, const T* d_sparse, float scale, bool scale_ok, const float* d_dense, const float* d_fallback, float* d_out,
+                                    uint16_t* d_dist2, int rows, int cols, int batch, const dcmt_support_params* params, uint32_t* d_beyond, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const uint32_t lo = planes_bits(&params->valid_thresh), hi = planes_bits(&params->max_depth);
+    const bool ok = scale_ok && plan::support_params_ok(params->max_radius, lo, hi);
+    const plan::SupportPlan pl = plan::plan_support_distance(rows, cols, batch, (int)sizeof(T), ok, params->max_radius, (uintptr_t)d_sparse, (uintptr_t)d_dense,
+                                                             (uintptr_t)d_fallback, (uintptr_t)d_out, (uintptr_t)d_dist2, (uintptr_t)d_beyond);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols, cap = (uint32_t)params->max_radius + 1u;
+    uint16_t* g = reinterpret_cast<uint16_t*>(ctx->pp[0].p);
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_beyond, 0, pl.clear_bytes, st));
+    if (pl.ballots)
+        hipLaunchKernelGGL((k_support_cols<T, true>), dim3(pl.cols_grid, batch), dim3(kSupportColsWave), pl.cols_lds, st, d_sparse, r, c, cap, lo, hi, scale, g);
+    else
+        hipLaunchKernelGGL((k_support_cols<T, false>), dim3(pl.cols_grid, batch), dim3(kSupportColsWave), 0, st, d_sparse, r, c, cap, lo, hi, scale, g);
+    hipLaunchKernelGGL(k_support_rows, dim3(pl.rows_grid, batch), dim3(256), pl.rows_lds, st, g, r, c, pl.tiles_x, (int)params->max_radius,
+                       reinterpret_cast<const uint32_t*>(d_dense), reinterpret_cast<const uint32_t*>(d_fallback), reinterpret_cast<uint32_t*>(d_out), d_dist2,
+                       d_beyond);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+void dcmt_default_support_params(dcmt_support_params* p)
+{
+    if (!p) return;
+    p->max_radius = 9;      // the reach of H3..H5 per axis (2 + 4 + 3): dcmt.h says what that bounds
+    p->valid_thresh = 0.1f; // the planes' and the occlusion filter's defaults
+    p->max_depth = 100.0f;
+}
+
+int dcmt_support_distance_dev(dcmt_ctx* ctx, const float* d_sparse, const float* d_dense, const float* d_fallback, float* d_out, uint16_t* d_dist2, int rows,
+                              int cols, int batch, const dcmt_support_params* params, uint32_t* d_beyond, void* stream)
+{
+    return support_distance_enqueue(ctx, reinterpret_cast<const uint32_t*>(d_sparse), 1.0f, true, d_dense, d_fallback, d_out, d_dist2, rows, cols, batch, params,
+                                    d_beyond, stream);
+}
+
+int dcmt_support_distance_u16_dev(dcmt_ctx* ctx, const uint16_t* d_sparse, float scale, const float* d_dense, const float* d_fallback, float* d_out,
+                                  uint16_t* d_dist2, int rows, int cols, int batch, const dcmt_support_params* params, uint32_t* d_beyond, void* stream)
+{
+    volatile float m = scale;                         // read through memory, as finite_bits does: the compiler may assume an argument finite
+    const float s = m;
+    return support_distance_enqueue(ctx, d_sparse, s, plan::occlusion_scale_ok(planes_bits(&s)), d_dense, d_fallback, d_out, d_dist2, rows, cols, batch, params,
+                                    d_beyond, stream);
 }
 
 }  // extern "C"

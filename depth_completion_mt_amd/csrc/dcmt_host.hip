@@ -372,6 +372,22 @@ int dcmt_sparse_occlusion(dcmt_ctx* ctx, const float* sparse, size_t srs, float*
     return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
 }
 
+int dcmt_support_distance(dcmt_ctx* ctx, const float* sparse, size_t srs, const float* dense, size_t drs, const float* fallback, size_t frs, float* out, size_t ors,
+                          uint16_t* dist2, size_t d2rs, int rows, int cols, const dcmt_support_params* params, uint32_t* beyond)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !sparse || !params || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    if ((!out && !dist2) || (out && !dense) || (fallback && !out)) return DCMT_E_INVALID;
+    const size_t rb = sizeof(float) * (size_t)cols;
+    Plane z(sparse, srs, rb, rows), d(out ? dense : nullptr, drs, rb, rows), f(fallback, frs, rb, rows), o(out, ors, rb, rows);
+    Plane q(dist2, d2rs, sizeof(uint16_t) * (size_t)cols, rows), n(beyond, sizeof(uint32_t));
+    int rc = stage(ctx, {&z, &d, &f}, {&o, &q, &n});
+    if (rc == DCMT_OK)
+        rc = dcmt_support_distance_dev(ctx, (const float*)z.dev, (const float*)d.dev, (const float*)f.dev, (float*)o.dev, (uint16_t*)q.dev, rows, cols, 1, params,
+                                       (uint32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &q, &n}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -24,13 +24,26 @@
 
 namespace dcmt {
 
+// the bits of an element's depth: its own (an f32 plane), or of the payload's ingest, the f32 product rounded once
+template <typename T>
+__device__ __forceinline__ uint32_t occl_depth_bits(T v, float scale)
+{
+    if constexpr (sizeof(T) == 4) return v;
+    else return __float_as_uint(__fmul_rn((float)v, scale));
+}
+
+// an element is a return: the planes' test on its depth (dcmt_kernels_support.h shares it)
+template <typename T>
+__device__ __forceinline__ bool occl_is_return(T v, float scale, uint32_t lo_bits, uint32_t hi_bits)
+{
+    return planes_is_return(occl_depth_bits<T>(v, scale), lo_bits, hi_bits);
+}
+
 // the code of an element: the planes' code of its depth where that is a return, else 0
 template <typename T>
 __device__ __forceinline__ uint32_t occl_code(T v, float scale, uint32_t lo_bits, uint32_t hi_bits)
 {
-    uint32_t zb;
-    if constexpr (sizeof(T) == 4) zb = v;
-    else zb = __float_as_uint(__fmul_rn((float)v, scale));
+    const uint32_t zb = occl_depth_bits<T>(v, scale);
     return planes_is_return(zb, lo_bits, hi_bits) ? planes_code(zb) : 0u;
 }
 

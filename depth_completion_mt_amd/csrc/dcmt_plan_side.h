@@ -18,6 +18,7 @@
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_planes.h"
 #include "dcmt_rectify.h"
+#include "dcmt_support.h"
 #include "dcmt_tiles.h"
 
 #pragma GCC visibility push(hidden)       // internal names: none of them in libdcmt_hip.so's dynamic symbol table
@@ -545,6 +546,70 @@ inline OcclusionPlan plan_sparse_occlusion(int rows, int cols, int batch, int el
     p.plane_bytes = bytes;
     p.clear_bytes = removed ? rb : 0;
     p.launches = (p.in_place ? 2 : 1) + (removed ? 1 : 0);
+    return p;
+}
+
+// ---- dcmt_support_distance_dev, dcmt_support_distance_u16_dev ----------------------------------------------------------------
+// The distance to the nearest return and the trust mask (dcmt_kernels_support.h): k_support_cols leaves the capped column distances
+// of every pixel as uint16 on pp[0], [frame][row][col] (2 bytes a pixel on a plane of 4: the scratch of a call never exceeds the
+// borrowed plane), k_support_rows takes the minimum along the row and writes dist2, selects into out and counts.  Two launches, in
+// place or not; a clear of `beyond` goes in front where it is given.  The checks on the arguments are here as well, tested without a
+// device.
+
+// what dcmt_support_params may hold (dcmt.h); the depth bounds are the occlusion filter's
+inline bool support_params_ok(int64_t max_radius, uint32_t valid_thresh_bits, uint32_t max_depth_bits)
+{
+    return max_radius >= 1 && max_radius <= kSupportMaxRadius && occlusion_params_ok(0, 0, 0, valid_thresh_bits, max_depth_bits);
+}
+
+struct SupportPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, bad parameters, outputs that do not go together, buffers that overlap
+    bool in_place;                   // out == dense: k_support_rows touches only the pixels beyond the radius
+    bool ballots;                    // k_support_cols keeps the rows' ballots in LDS; false: it reads the sparse plane twice
+    unsigned cols_grid;              // k_support_cols: (cols_grid, batch), 64 threads
+    uint32_t cols_lds;               // ... its dynamic LDS
+    uint32_t tiles_x, bands, groups; // segments of 256 columns; bands of 4 rows; groups of 4 bands, one workgroup each
+    unsigned rows_grid;              // k_support_rows: (rows_grid, batch) = (tiles_x * groups, batch), 256 threads
+    uint32_t rows_lds;               // ... its dynamic LDS
+    size_t scratch;                  // bytes of pp[0] the call uses: 2 * batch * rows * cols
+    size_t plane_bytes;              // batch * rows * cols * 4: what the kernels' 64-bit offsets span on an f32 plane
+    size_t clear_bytes;              // hipMemsetAsync of beyond: 4 bytes a frame (0: no counts wanted)
+    int launches;                    // 2, one more with beyond
+};
+
+// rows, cols, batch >= 1 and within the context's limits; elem: 4 (f32) or 2 (the payload), of the sparse plane alone; params_ok:
+// support_params_ok (and occlusion_scale_ok) of the call's parameters; dense, fallback, out, dist2, beyond: 0 = not given
+inline SupportPlan plan_support_distance(int rows, int cols, int batch, int elem, bool params_ok, int max_radius, uintptr_t sparse, uintptr_t dense,
+                                         uintptr_t fallback, uintptr_t out, uintptr_t dist2, uintptr_t beyond)
+{
+    SupportPlan p = {};
+    p.status = kInvalid;
+    if (!sparse || !params_ok || (elem != 2 && elem != 4)) return p;
+    if ((!out && !dist2) || (out && !dense) || (fallback && !out)) return p;
+    if (sparse % (uintptr_t)elem != 0 || dense % 4 != 0 || fallback % 4 != 0 || out % 4 != 0 || dist2 % 2 != 0 || beyond % 4 != 0) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    const uintptr_t at[6] = {sparse, dense, fallback, out, dist2, beyond};
+    const size_t bytes[6] = {(size_t)elem * px, 4 * px, 4 * px, 4 * px, 2 * px, sizeof(uint32_t) * (size_t)batch};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j) {
+            if (!at[i] || !at[j]) continue;
+            if (i == 1 && j == 3 && dense == out) continue;            // the one overlap allowed: in place, exactly
+            if (ranges_overlap(at[i], bytes[i], at[j], bytes[j])) return p;
+        }
+    p.status = kOk;
+    p.in_place = out && out == dense;
+    p.ballots = rows <= kSupportLdsRows;
+    p.cols_grid = ((unsigned)cols + kSupportColsWave - 1) / kSupportColsWave;
+    p.cols_lds = support_cols_lds_bytes(rows);
+    p.tiles_x = ((uint32_t)cols + kSupportTile - 1) / kSupportTile;
+    p.bands = ((uint32_t)rows + kSupportBand - 1) / kSupportBand;
+    p.groups = (p.bands + kSupportGroup - 1) / kSupportGroup;
+    p.rows_grid = p.tiles_x * p.groups;
+    p.rows_lds = support_rows_lds_bytes(max_radius);
+    p.scratch = 2 * px;
+    p.plane_bytes = 4 * px;
+    p.clear_bytes = beyond ? sizeof(uint32_t) * (size_t)batch : 0;
+    p.launches = 2 + (beyond ? 1 : 0);
     return p;
 }
 

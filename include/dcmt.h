@@ -548,6 +548,71 @@ int dcmt_sparse_occlusion_u16_dev(dcmt_ctx *ctx, const uint16_t *d_sparse, float
 int dcmt_sparse_occlusion(dcmt_ctx *ctx, const float *sparse, size_t sparse_row_stride, float *out, size_t out_row_stride, int rows, int cols,
                           const dcmt_occlusion_params *params, uint32_t *removed);
 
+/* ---- distance to the nearest LiDAR return, and the trust mask ------------------------------------------ */
+
+/* Every call that produces a dense plane (the cascade, dcmt_superpixel_planes_dev, the Gaussian and bilateral finishes, dcmt_sgm_dev
+ * with its fallback depth) invents depth where nothing was measured, and none of them tells the consumer which pixels rest on a
+ * measurement.  This call gives the support map of a sparse plane: for every pixel the exact squared Euclidean distance to the
+ * nearest return; and one use of it fused behind: keep a dense plane within a trust radius of a return and write zero, or a second
+ * plane (the stereo matcher's depth, say), beyond it.  Not in the reference; stated here to the last bit: integers throughout.  Per
+ * frame, on a sparse plane [rows][cols]:
+ *
+ * RETURN.  Exactly the occlusion filter's rule above (dcmt_sparse_occlusion_dev), decided on the bit pattern: a finite float with
+ *   valid_thresh <= z <= max_depth; NaN, +-inf, negatives and -0.0 are no returns.  The same bounds are enforced:
+ *   valid_thresh >= 0.0625, max_depth <= 16384.
+ * DISTANCE.  D2(y, x) = the minimum over the returns (y', x') of the same frame of (y - y')^2 + (x - x')^2, in integers: 0 at a
+ *   return, infinite in a frame without returns.  It never reaches into another frame of the batch.
+ * d_dist2, or NULL: uint16 [batch][rows][cols].  D2 where D2 <= R^2, R = max_radius in 1..255, and 65535 everywhere else:
+ *   255^2 = 65025 < 65535, so the marker is never a distance, and no value between R^2 + 1 and 65534 is ever written.
+ * d_out, or NULL: f32 [batch][rows][cols]; needs d_dense.  A pixel takes the four bytes of d_dense where D2 <= R^2; elsewhere the
+ *   four bytes of d_fallback, or +0.0f where d_fallback is NULL.  The copy is opaque: a NaN keeps its bits.  d_out may BE d_dense.
+ * d_beyond, or NULL: uint32 [batch], the pixels of the frame with D2 > R^2.
+ * At least one of d_dist2 and d_out must be given; d_fallback without d_out is refused.
+ * Nothing depends on the batch size, the frame's position in the batch, alignment, the launch geometry, the run, or on whether
+ * the call is in place.
+ *
+ * The default R = 9 is the reach of H3..H5 (2 + 4 + 3): beyond it no value of the plane behind the 7x7 fill depends on
+ * a measurement except through the column extension and the 31x31 fills.  Checked against the kernels of the no-extrapolation
+ * cascade (dcmt_kernels_local.h, dcmt_kernels_fused.h): that holds for the plane behind H5, whose rows lag the input by PreS::LAT = 9
+ * and whose strips lose PreS::HR = 2 + 2 + 2 + 3 = 9 columns, and it is a reach PER AXIS, a box of 19 x 19: the disc of R = 9 lies
+ * inside it, so the default trusts nothing H3..H5 could not have reached, and leaves out the box's corners (up to 9 sqrt(2) = 12.7
+ * away).  The FINISHED plane of that cascade reaches further: LocalS::REACH = 13 rows, the median and the Gaussian adding 2 + 2 (and
+ * 4 columns either side); max_radius = 13 covers it in the same sense.
+ *
+ * The payload form, dcmt_support_distance_u16_dev, takes the sparse plane as the KITTI uint16 payload dcmt_complete_u16_dev ingests:
+ * the depth of a payload value v is what that ingest states, the f32 product (float) v * scale rounded once.  Dense, fallback and
+ * out stay f32.  The same kernels, instantiated on the element type.
+ *
+ * DEVICE pointers, stream-ordered; never synchronises, never allocates.  Two launches, in place or not: the distance in rows to the
+ * nearest return of every pixel's own column, capped at R + 1 and kept as uint16 (so that 255 is told from "none within reach" on one
+ * route for every R); then the minimum along the row, which writes d_dist2, selects into d_out and counts.  A clear of d_beyond goes
+ * in front where it is given: three.  Scratch: the first of the two planes dcmt_create allocates (the one the occlusion filter,
+ * dcmt_slic_connectivity_dev and dcmt_filter_speckles_dev borrow), half of it.  Of the context's carried state it touches none,
+ * dcmt_last_path included: it can be queued in front of or behind any other *_dev call.
+ * DCMT_E_INVALID, nothing written: a null ctx, sparse plane or params; neither d_dist2 nor d_out; d_out without d_dense; d_fallback
+ * without d_out; sizes or a batch beyond the context's limits; max_radius outside 1..255; valid_thresh not finite or < 0.0625;
+ * max_depth not finite, < valid_thresh or > 16384; scale not finite or <= 0 (the payload form); a plane not aligned to its element,
+ * d_beyond not 4-byte aligned; any overlap among the buffers other than d_out == d_dense exactly. */
+typedef struct {
+    int32_t max_radius;     /* 9     R: distances up to R^2 are reported and trusted; 1..255                       */
+    float   valid_thresh;   /* 0.1   the smallest depth that is a return, metres; >= 0.0625                        */
+    float   max_depth;      /* 100   the largest; <= 16384                                                         */
+} dcmt_support_params;      /* 12 bytes */
+void dcmt_default_support_params(dcmt_support_params *p);
+int dcmt_support_distance_dev(dcmt_ctx *ctx, const float *d_sparse, const float *d_dense /* or NULL */, const float *d_fallback /* or NULL */,
+                              float *d_out /* may be d_dense, or NULL */, uint16_t *d_dist2 /* or NULL */, int rows, int cols, int batch,
+                              const dcmt_support_params *params, uint32_t *d_beyond /* [batch] or NULL */, void *stream);
+int dcmt_support_distance_u16_dev(dcmt_ctx *ctx, const uint16_t *d_sparse, float scale /* 1./256 for KITTI */, const float *d_dense /* or NULL */,
+                                  const float *d_fallback /* or NULL */, float *d_out /* may be d_dense, or NULL */, uint16_t *d_dist2 /* or NULL */,
+                                  int rows, int cols, int batch, const dcmt_support_params *params, uint32_t *d_beyond /* [batch] or NULL */,
+                                  void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES, >= 4 * cols, dist2's >= 2 * cols; the stride of a plane that is not
+ * given is not looked at); out may be dense; beyond: one count or NULL.  The same bits as the device call.  What
+ * dcmt_shim::distance_to_returns and dcmt_shim::trust_mask call. */
+int dcmt_support_distance(dcmt_ctx *ctx, const float *sparse, size_t sparse_row_stride, const float *dense, size_t dense_row_stride,
+                          const float *fallback, size_t fallback_row_stride, float *out, size_t out_row_stride, uint16_t *dist2,
+                          size_t dist2_row_stride, int rows, int cols, const dcmt_support_params *params, uint32_t *beyond);
+
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 
 /* What DC_stereo_lidar/main_sl.cpp does with the dense depth (:1165-1246): depth -> disparity (get_initial_disparity

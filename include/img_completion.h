@@ -533,6 +533,55 @@ inline unsigned filter_occluded_returns(const cv::Mat& sparse_r_img, cv::Mat& fi
     return removed;
 }
 
+// The support map of a sparse plane, as dcmt.h states it (dcmt_support_distance): sparse_r_img CV_32FC1 in metres; dist2_img is
+// overwritten with a fresh CV_32FC1 image holding, for every pixel, the squared Euclidean distance to the nearest return where that
+// is at most max_radius^2 (an integer, exact as a float) and 65535 everywhere else.  params == nullptr: dcmt_default_support_params
+// (max_radius 9).  Returns the number of pixels beyond max_radius.
+inline unsigned distance_to_returns(const cv::Mat& sparse_r_img, cv::Mat& dist2_img, const dcmt_support_params* params = nullptr)
+{
+    check_input(sparse_r_img);
+    const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
+    dcmt_support_params def;
+    dcmt_default_support_params(&def);
+    std::vector<uint16_t> d2((size_t)rows * cols);
+    uint32_t beyond = 0;
+    raise(dcmt_support_distance(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], nullptr, 0, nullptr, 0, nullptr, 0, d2.data(),
+                                sizeof(uint16_t) * (size_t)cols, rows, cols, params ? params : &def, &beyond),
+          "distance_to_returns");
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) out.ptr<float>(i)[j] = (float)d2[(size_t)i * cols + j];
+    dist2_img = out;
+    return beyond;
+}
+
+// The trust mask of a dense plane (dcmt_support_distance): trusted_img is overwritten with a fresh CV_32FC1 image that holds
+// dense_img where a return of sparse_r_img lies within max_radius and, beyond it, fallback_img -- the stereo matcher's depth, say --
+// or 0 where fallback_img is null.  The pixels are copied bit for bit.  All images CV_32FC1 of one size.  params == nullptr:
+// dcmt_default_support_params.  Returns the number of pixels beyond max_radius.
+inline unsigned trust_mask(const cv::Mat& sparse_r_img, const cv::Mat& dense_img, cv::Mat& trusted_img, const cv::Mat* fallback_img = nullptr,
+                           const dcmt_support_params* params = nullptr)
+{
+    check_input(sparse_r_img);
+    const int rows = sparse_r_img.rows, cols = sparse_r_img.cols;
+    if (dense_img.type() != CV_32FC1 || dense_img.rows != rows || dense_img.cols != cols)
+        throw std::runtime_error("trust_mask: the dense image must be CV_32FC1 of the sparse image's size");
+    if (fallback_img && (fallback_img->type() != CV_32FC1 || fallback_img->rows != rows || fallback_img->cols != cols))
+        throw std::runtime_error("trust_mask: the fallback image must be CV_32FC1 of the sparse image's size");
+    dcmt_support_params def;
+    dcmt_default_support_params(&def);
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    uint32_t beyond = 0;
+    raise(dcmt_support_distance(thread_ctx().get(rows, cols), sparse_r_img.ptr<float>(), sparse_r_img.step[0], dense_img.ptr<float>(), dense_img.step[0],
+                                fallback_img ? fallback_img->ptr<float>() : nullptr, fallback_img ? fallback_img->step[0] : 0, out.ptr<float>(), out.step[0],
+                                nullptr, 0, rows, cols, params ? params : &def, &beyond),
+          "trust_mask");
+    trusted_img = out;
+    return beyond;
+}
+
 // unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
 // takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
