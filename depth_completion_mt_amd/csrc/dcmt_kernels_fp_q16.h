@@ -572,19 +572,21 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     // steps 32..rows+34: post step u = t - 29 takes X7 row u - 2 = t - 31, the row this step's fill front end returns
     const int nsteps = rows + 35;
     int t0 = 32;
+    // The V rows above the stream equal output row 0 of the shifted frame (image row V).  That row's value is kept (top_val) and the V
+    // rows leave behind the wave's last row step, non-temporal like every other output row: stored where the value first exists (step
+    // t = 35) they are a burst of V back-to-back stores in front of the wave's load lookahead, in every wave of the launch at once
+    // (DESIGN.md section 5 has the series: the burst in place with `nt`, paced one row per step, and this).
+    F2 top_val = {0.f, 0.f};
     auto main_step = [&](auto P_) {
         constexpr int p = decltype(P_)::value;
         const int t = t0 + p, u = t - 29;
         const unsigned x7 = fill_step(P_, BorderMode{}, t);
         post_step(std::integral_constant<int, ((p + 3) & 7)>{}, BorderMode{}, x7, u);
         if constexpr (p == 3) {
-            // u == 6: output row 0 of the shifted frame (image row V) has just been stored; the V rows above it are equal
-            if (t0 == 32 && V > 0) {
-                FrameBuf top;
-                top.init(dst + fo, (size_t)V * cols);
-                const unsigned tbo = pipe.outlane ? pipe.ob : kDropOffset;
-                for (int r = 0; r < V; ++r) st2(top, tbo, r, cols, pipe.last_out);
-            }
+            // u == 6: output row 0 of the shifted frame has just been stored.  (Selects, not a branch: with the assignment under
+            // `if (t0 == 32)` the allocation of <false, false> and <true, true> is 187 and 202 VGPRs, two waves per SIMD.)
+            const bool first = t0 == 32;
+            top_val.e = first ? pipe.last_out.e : top_val.e; top_val.o = first ? pipe.last_out.o : top_val.o;
         }
     };
     // (the sixteen steps of a block in four quarters with a way out behind each: the last block of a wave is 7.5 steps too long on
@@ -596,7 +598,7 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
     // [2, rows - 3] (t0 >= 48 for the first, the load rows' bound covers the last), every row-range test of the step has one known
     // answer.  Such blocks are one contiguous run of t0; they take a body without the clamps, the tests and the selects, with one
     // dword load for (E, O).  Everything else -- the first and the last blocks, ragged tops and bottoms -- takes the border body
-    // above, which also keeps the quarter exits and the V top rows.
+    // above, which also keeps the quarter exits and picks up the value of the V top rows.
     // edge_strip is a wave-uniform branch in both bodies.  As a compile-time property of the interior body (two loops chosen per
     // wave, or one loop with the choice per block) it took k_fp_q<true, true> from 148 to 216..221 VGPRs -- the register allocator
     // keeps the state of both instantiations apart -- and to 58..70 spilled VGPRs with three waves per SIMD asked for.
@@ -630,6 +632,12 @@ void k_fp_q(const void* __restrict__ x6_, float* __restrict__ dst, int* __restri
         static_for<8, 12>(main_step);
         if (t0 + 12 >= nsteps) break;
         static_for<12, 16>(main_step);
+    }
+    if (V > 0) {
+        FrameBuf top;
+        top.init(dst + fo, (size_t)V * cols);
+        const unsigned tbo = pipe.outlane ? pipe.ob : kDropOffset;
+        for (int r = 0; r < V; ++r) st2_nt(top, tbo, r, cols, top_val);
     }
     if (lane == 0) {
         if (before) atomicAdd(&cnt[0], before);

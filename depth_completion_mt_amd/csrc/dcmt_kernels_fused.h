@@ -70,6 +70,11 @@ struct FrameBuf {
     {
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, lane_bytes, row * cols * 4, 0);
     }
+    // the same with the `nt` bit (non-temporal: streamed, not kept): for rows that nobody in the launch reads again
+    __device__ __forceinline__ void st_nt(unsigned lane_bytes, int row, int cols, float v) const
+    {
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs, lane_bytes, row * cols * 4, 2 /* nt */);
+    }
     // per-lane rows: the whole byte offset in the VGPR
     __device__ __forceinline__ float ld_at(unsigned bytes) const
     {
@@ -702,7 +707,7 @@ struct PostS {
 // FILLED: the caller guarantees that every frame whose X7 still holds a hole is recomputed afterwards (k_fp_s followed by the
 // redo chain).  A frame without holes has every median >= thr, so the masked select of LO :184 always takes the blurred value
 // and its compare + select (two of the slow instructions per pixel) are left out; what a frame WITH holes gets is overwritten.
-template <int MODE, bool BLUR, bool FILLED = false>
+template <int MODE, bool BLUR, bool FILLED = false, bool NT = false>
 struct PostPipe {
     static constexpr bool do_blur = BLUR && MODE >= 10;
     MedianColumn mc;         // the vertical half of the median (dcmt_median.h)
@@ -769,7 +774,8 @@ struct PostPipe {
                     if (FILLED || mo >= thr) val = acc;                 // LO :184
                 }
                 if constexpr (MODE >= 11) val = invert_valid(val, max_depth, thr);  // LO :191-202
-                of.st(outlane ? ob : kDropOffset, o, cols, val);     // every lane stores; halo lanes aim past the buffer (dropped)
+                if constexpr (NT) of.st_nt(outlane ? ob : kDropOffset, o, cols, val);
+                else of.st(outlane ? ob : kDropOffset, o, cols, val);    // every lane stores; halo lanes aim past the buffer (dropped)
                 last_out = val;
             };
             const float g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7];
@@ -1079,7 +1085,7 @@ __device__ __forceinline__ void fp_s_unit(float* delay, const float* x6, float* 
     float (*dl_b)[32] = reinterpret_cast<float (*)[32]>(delay + 16 * 128);
     const int lb = lane <= 14 ? lane : (lane >= 48 ? lane - 32 : 15);   // B's live lanes 0..14, 48..63 -> words 0..14, 16..31; the dead lanes share word 15
 
-    PostPipe<11, BLUR, FILLED> pipe;
+    PostPipe<11, BLUR, FILLED, /*NT=*/true> pipe;      // output rows: read by nobody in the launch
     pipe.init(dst + (size_t)V * cols, rows, cols, gx0, lane, max_depth, thr);
     pipe.so0 = so0; pipe.so1 = so1;
 
@@ -1191,20 +1197,13 @@ __device__ __forceinline__ void fp_s_unit(float* delay, const float* x6, float* 
     // steps 32..rows+34: fill + post; post step u = t - FpS::LAG takes X7 row u - 2 = t - 31, the row this step's fill front end returns
     const int nsteps = rows + 35;
     int t0 = 32;
+    float top_val = 0.f;             // output row 0 of the shifted frame: the V rows above it are equal and leave behind the last step (k_fp_q has the reasons)
     auto main_step = [&](auto P_) {
         constexpr int p = decltype(P_)::value;
         const int t = t0 + p, u = t - FpS::LAG;
         const float x7 = fill_step(P_, t);
         pipe.template step<((p + 3) & 7)>(x7, u);
-        if constexpr (p == 3) {
-            // u == 6: output row 0 of the shifted frame (image row V) has just been stored; the V rows above it are equal
-            if (t0 == 32 && V > 0 && band == 0) {
-                FrameBuf top;
-                top.init(dst, (size_t)V * cols);
-                const unsigned tb = pipe.outlane ? pipe.ob : kDropOffset;
-                for (int r = 0; r < V; ++r) top.st(tb, r, cols, pipe.last_out);
-            }
-        }
+        if constexpr (p == 3) top_val = t0 == 32 ? pipe.last_out : top_val;   // u == 6: output row 0 of the shifted frame has just been stored (a select: see k_fp_q)
     };
     for (; t0 < nsteps; t0 += 16) {                                  // (four quarters with a way out behind each: see k_fp_q)
         static_for<0, 4>(main_step);
@@ -1214,6 +1213,12 @@ __device__ __forceinline__ void fp_s_unit(float* delay, const float* x6, float* 
         static_for<8, 12>(main_step);
         if (t0 + 12 >= nsteps) break;
         static_for<12, 16>(main_step);
+    }
+    if (V > 0 && band == 0) {
+        FrameBuf top;
+        top.init(dst, (size_t)V * cols);
+        const unsigned tbo = pipe.outlane ? pipe.ob : kDropOffset;
+        for (int r = 0; r < V; ++r) top.st_nt(tbo, r, cols, top_val);
     }
     if (lane == 0) {
         if (before) atomicAdd(&cnt[0], before);
