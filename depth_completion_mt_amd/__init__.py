@@ -13,7 +13,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   sgm_workspace_bytes, stereo_sgm, make_speckle_params, filter_speckles,
                   RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify,
                   PLANE_FIT_DTYPE, make_planes_params, fit_superpixel_planes, superpixel_planes_max_labels,
-                  make_occlusion_params, filter_occluded_returns, make_support_params, distance_to_returns, trust_mask)
+                  make_occlusion_params, filter_occluded_returns, make_support_params, distance_to_returns, trust_mask,
+                  JOINT_TABLES_DTYPE, make_joint_params, make_joint_tables, joint_bilateral_fill)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -26,7 +27,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "make_sgm_params", "sgm_workspace_bytes", "stereo_sgm", "make_speckle_params", "filter_speckles",
            "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify",
            "PLANE_FIT_DTYPE", "make_planes_params", "fit_superpixel_planes", "superpixel_planes_max_labels",
-           "make_occlusion_params", "filter_occluded_returns", "make_support_params", "distance_to_returns", "trust_mask"]
+           "make_occlusion_params", "filter_occluded_returns", "make_support_params", "distance_to_returns", "trust_mask",
+           "JOINT_TABLES_DTYPE", "make_joint_params", "make_joint_tables", "joint_bilateral_fill"]
 
 
 def __getattr__(name):

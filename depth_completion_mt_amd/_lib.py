@@ -52,6 +52,7 @@ EXPORTS = (
     "dcmt_default_planes_params", "dcmt_superpixel_planes_max_labels", "dcmt_superpixel_planes_dev", "dcmt_superpixel_planes",
     "dcmt_default_occlusion_params", "dcmt_sparse_occlusion_dev", "dcmt_sparse_occlusion_u16_dev", "dcmt_sparse_occlusion",
     "dcmt_default_support_params", "dcmt_support_distance_dev", "dcmt_support_distance_u16_dev", "dcmt_support_distance",
+    "dcmt_default_joint_params", "dcmt_make_joint_tables", "dcmt_joint_bilateral_dev", "dcmt_joint_bilateral",
 )
 
 
@@ -150,6 +151,20 @@ class OcclusionParams(ctypes.Structure):
 class SupportParams(ctypes.Structure):
     """Mirror of dcmt_support_params (include/dcmt.h), 12 bytes."""
     _fields_ = [("max_radius", ctypes.c_int32), ("valid_thresh", ctypes.c_float), ("max_depth", ctypes.c_float)]
+
+
+JOINT_FILL, JOINT_SMOOTH = 1, 2          # DCMT_JOINT_FILL, DCMT_JOINT_SMOOTH
+
+
+class JointParams(ctypes.Structure):
+    """Mirror of dcmt_joint_params (include/dcmt.h), 20 bytes."""
+    _fields_ = [("radius", ctypes.c_int32), ("flags", ctypes.c_uint32), ("min_weight", ctypes.c_uint32), ("valid_thresh", ctypes.c_float),
+                ("max_depth", ctypes.c_float)]
+
+
+class JointTables(ctypes.Structure):
+    """Mirror of dcmt_joint_tables (include/dcmt.h), 1792 bytes."""
+    _fields_ = [("w_space", ctypes.c_uint16 * 128), ("w_guide", ctypes.c_uint16 * 768)]
 
 
 class CropSrc(ctypes.Structure):
@@ -319,6 +334,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_support_distance_dev.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_support_distance_u16_dev.argtypes = [vp, vp, ctypes.c_float, vp, vp, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_support_distance.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, i, i, vp, vp]
+        L.dcmt_default_joint_params.argtypes = [vp]
+        L.dcmt_default_joint_params.restype = None
+        L.dcmt_make_joint_tables.argtypes = [i, ctypes.c_double, ctypes.c_double, vp]
+        L.dcmt_joint_bilateral_dev.argtypes = [vp, vp, vp, i, vp, vp, i, i, i, vp, vp, vp]
+        L.dcmt_joint_bilateral.argtypes = [vp, vp, sz, vp, sz, i, vp, vp, sz, i, i, vp, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

@@ -359,6 +359,58 @@ def make_support_params(max_radius: int | None = None, valid_thresh: float | Non
     return p
 
 
+JOINT_TABLES_DTYPE = np.dtype([("w_space", "<u2", (128,)), ("w_guide", "<u2", (768,))])                         # dcmt_joint_tables, 1792 B
+
+
+def make_joint_params(radius: int | None = None, fill: bool | None = None, smooth: bool | None = None, min_weight: int | None = None,
+                      valid_thresh: float | None = None, max_depth: float | None = None) -> L.JointParams:
+    """dcmt_joint_params: radius 6, fill alone, min_weight 1, valid_thresh 0.1, max_depth 100 unless overridden.  Raises ValueError on
+    what dcmt_joint_bilateral_dev refuses of them: radius outside 1..9, neither fill nor smooth, min_weight outside 1..2^32 - 1,
+    valid_thresh not finite or < 0.0625, max_depth not finite, < valid_thresh or > 16384."""
+    p = L.JointParams()
+    L.lib().dcmt_default_joint_params(ctypes.byref(p))
+    if radius is not None:
+        if isinstance(radius, bool) or int(radius) != radius or not -2 ** 31 <= int(radius) < 2 ** 31:
+            raise ValueError(f"radius = {radius!r} is not an int32")
+        p.radius = int(radius)
+    for flag, bit in ((fill, L.JOINT_FILL), (smooth, L.JOINT_SMOOTH)):
+        if flag is not None:
+            p.flags = (p.flags | bit) if flag else (p.flags & ~bit)
+    if min_weight is not None:
+        if isinstance(min_weight, bool) or int(min_weight) != min_weight or not 1 <= int(min_weight) < 2 ** 32:
+            raise ValueError(f"min_weight = {min_weight!r}: 1 .. 2^32 - 1")
+        p.min_weight = int(min_weight)
+    for name, v in (("valid_thresh", valid_thresh), ("max_depth", max_depth)):
+        if v is not None:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} = {v!r}: a finite float")
+            setattr(p, name, float(v))
+    if not 1 <= p.radius <= 9:
+        raise ValueError(f"radius = {p.radius}: 1 .. 9 (253 taps of weight 255 * 255 stay below 2^24)")
+    if p.flags == 0:
+        raise ValueError("neither fill nor smooth: nothing to do")
+    if not p.valid_thresh >= 0.0625:
+        raise ValueError(f"valid_thresh = {p.valid_thresh}: >= 0.0625")
+    if not p.valid_thresh <= p.max_depth <= 16384.0:
+        raise ValueError(f"max_depth = {p.max_depth}: valid_thresh .. 16384")
+    return p
+
+
+def make_joint_tables(radius: int = 6, sigma_space: float = 3.0, sigma_guide: float = 10.0) -> np.ndarray:
+    """The weight tables of the joint bilateral filter (dcmt_make_joint_tables, as include/dcmt.h states them): one JOINT_TABLES_DTYPE
+    record, w_space[d2] = rne(255 exp(-d2 / (2 sigma_space^2))) for d2 <= radius^2 and 0 beyond, w_guide[s] = rne(255 exp(-s^2 /
+    (2 sigma_guide^2))), in f64.  Raises ValueError on a radius outside 1..9 and on a sigma that is not finite or not > 0.  Upload it
+    once with calib_to_device; any other table of that layout is as good an input (the device uses min(entry, 255))."""
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= 9:
+        raise ValueError(f"radius = {radius!r}: 1 .. 9")
+    for name, v in (("sigma_space", sigma_space), ("sigma_guide", sigma_guide)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{name} = {v!r}: finite and > 0")
+    t = L.JointTables()
+    _check(L.lib().dcmt_make_joint_tables(int(radius), float(sigma_space), float(sigma_guide), ctypes.byref(t)), "dcmt_make_joint_tables")
+    return np.frombuffer(bytes(t), dtype=JOINT_TABLES_DTYPE).copy()
+
+
 SGM_MAX_P2_EIGHT_PATHS = 1800      # S <= 8 * (6375 + p2) must fit uint16 (include/dcmt.h, step 3)
 
 
@@ -1295,6 +1347,58 @@ class Context:
         _check(st, "dcmt_support_distance")
         return (dist2, int(n.value)) if out is None else (out, dist2, int(n.value))
 
+    # ---- image-guided filling: the joint bilateral filter (dcmt_joint_bilateral*) ------------------
+    def joint_bilateral_dev(self, d_depth, d_guide, d_tables, d_out=None, counts: bool = False, d_counts=None, stream: int | None = None, **kw):
+        """Fill (and with smooth=True smooth) a depth plane under the guidance of a camera image (dcmt_joint_bilateral_dev, as
+        include/dcmt.h states it), without synchronising.  d_depth: f32 CUDA tensor [batch][rows][cols] (or [rows][cols]), metres.
+        d_guide: uint8 [batch][rows][cols] (grey) or [batch][rows][cols][3] (BGR, Lab): what bgr_convert_dev and rectify_dev write.
+        d_tables: one JOINT_TABLES_DTYPE record on the device (make_joint_tables, calib_to_device).  d_out: f32, the same shape, not
+        d_depth (allocated where not given).  counts=True or a d_counts (any 4-byte dtype, [batch][2]): {holes filled, holes left}
+        per frame, as int32; then (d_out, d_counts) is returned, else d_out.  kw: the fields of make_joint_params.  Outputs that are
+        not given are allocated on the stream the call enqueues on."""
+        import torch
+        assert _is_dev(d_depth, torch.float32) and _is_dev(d_guide, torch.uint8)
+        b, r, c = _brc(d_depth)
+        ch = d_guide.numel() // (b * r * c)
+        assert ch in (1, 3) and d_guide.numel() == b * r * c * ch and (ch == 1 or d_guide.shape[-1] == 3), tuple(d_guide.shape)
+        p = make_joint_params(**kw)
+        want_counts = counts or d_counts is not None
+        with _on_stream(stream, d_depth):
+            if d_out is None:
+                d_out = torch.empty(tuple(d_depth.shape), dtype=torch.float32, device=d_depth.device)
+            if want_counts and d_counts is None:
+                d_counts = torch.empty((b, 2), dtype=torch.int32, device=d_depth.device)
+        assert _is_dev(d_out, torch.float32) and d_out.numel() == b * r * c
+        assert d_counts is None or (_is_dev(d_counts) and d_counts.element_size() == 4 and d_counts.numel() == 2 * b)
+        st = L.lib().dcmt_joint_bilateral_dev(self._h, d_depth.data_ptr(), d_guide.data_ptr(), ch, _table_ptr(d_tables, 1, JOINT_TABLES_DTYPE.itemsize),
+                                              d_out.data_ptr(), r, c, b, ctypes.byref(p), None if d_counts is None else d_counts.data_ptr(),
+                                              _stream(stream, d_depth))
+        _check(st, "dcmt_joint_bilateral_dev")
+        return (d_out, d_counts) if want_counts else d_out
+
+    def joint_bilateral(self, depth: np.ndarray, guide: np.ndarray, tables=None, **kw):
+        """One frame of host memory (dcmt_joint_bilateral, synchronous; any row stride).  depth: f32 [rows][cols]; guide: uint8
+        [rows][cols] or [rows][cols][3]; tables: a make_joint_tables record (by default make_joint_tables() at the call's radius).
+        Returns (the filled plane, a new f32 array; holes filled; holes left).  kw: the fields of make_joint_params."""
+        z = _frame_f32(depth)
+        rows, cols = z.shape
+        g = np.asarray(guide)
+        assert g.dtype == np.uint8 and g.shape[:2] == z.shape and (g.ndim == 2 or (g.ndim == 3 and g.shape[2] in (1, 3))), (g.dtype, g.shape)
+        ch = 1 if g.ndim == 2 else g.shape[2]
+        if g.strides[-1] != 1 or (g.ndim == 3 and g.strides[1] != ch):
+            g = np.ascontiguousarray(g)
+        p = make_joint_params(**kw)
+        if tables is None:
+            tables = make_joint_tables(radius=p.radius)
+        t = np.ascontiguousarray(tables)
+        assert t.dtype == JOINT_TABLES_DTYPE and t.size == 1
+        out = np.empty(z.shape, dtype=np.float32)
+        n = (ctypes.c_uint32 * 2)()
+        st = L.lib().dcmt_joint_bilateral(self._h, z.ctypes.data, z.strides[0], g.ctypes.data, g.strides[0], ch, t.ctypes.data, out.ctypes.data,
+                                          out.strides[0], rows, cols, ctypes.byref(p), n)
+        _check(st, "dcmt_joint_bilateral")
+        return out, int(n[0]), int(n[1])
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1866,6 +1970,14 @@ def trust_mask(sparse, dense, fallback=None, **params):
     params: the fields of make_support_params."""
     z = np.asarray(sparse, dtype=np.float32)
     return _ctx_for(z.shape[0], z.shape[1], 1).support_distance(z, dense, fallback, **params)[0]
+
+
+def joint_bilateral_fill(depth, guide, tables=None, **params):
+    """Fill the holes of one host depth frame from the measured depths around them whose camera pixels look like theirs
+    (dcmt_joint_bilateral, as include/dcmt.h states it): depth f32 [rows][cols] in metres, guide uint8 [rows][cols] or
+    [rows][cols][3] -> a new f32 array; valid pixels keep their bytes unless smooth=True.  params: the fields of make_joint_params."""
+    z = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).joint_bilateral(z, guide, tables, **params)[0]
 
 
 def depth_to_u16(depth, scale: float = 256.0):

@@ -2,12 +2,13 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h), dcmt_support_distance_dev and dcmt_support_distance_u16_dev (dcmt_kernels_support.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h), dcmt_support_distance_dev and dcmt_support_distance_u16_dev (dcmt_kernels_support.h), dcmt_joint_bilateral_dev (dcmt_kernels_joint.h),
 // dcmt_photo_error_dev (dcmt_kernels_photo.h), the defaults of their parameter structs and dcmt_lab_tables.  A *_calib_dev entry point
 // shares its one launch sequence with the uniform entry point beside it: the calibration source (one record by value, or the device
 // table) is the kernels' template type.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame
 // host variants are in dcmt_host.hip.
 #include <algorithm>
+#include <cmath>
 
 #include "dcmt_chunks.h"
 #include "dcmt_plan_side.h"
@@ -25,6 +26,7 @@
 #include "dcmt_kernels_planes.h"
 #include "dcmt_kernels_occlusion.h"
 #include "dcmt_kernels_support.h"
+#include "dcmt_kernels_joint.h"
 
 using namespace dcmt;
 
@@ -730,6 +732,52 @@ int dcmt_support_distance_u16_dev(dcmt_ctx* ctx, const uint16_t* d_sparse, float
     const float s = m;
     return support_distance_enqueue(ctx, d_sparse, s, plan::occlusion_scale_ok(planes_bits(&s)), d_dense, d_fallback, d_out, d_dist2, rows, cols, batch, params,
                                     d_beyond, stream);
+}
+
+}  // extern "C"
+
+// ---- the joint bilateral filter (dcmt_kernels_joint.h) ---------------------------------------------------------------------------
+// The clear of the counts and the one kernel plan_joint_bilateral names.  Nothing of the context is read or written but its device
+// and its limits: no scratch, no state, no allocation.
+extern "C" {
+
+void dcmt_default_joint_params(dcmt_joint_params* p)
+{
+    if (!p) return;
+    p->radius = 6;           // DESIGN.md section 37 says how radius and the sigmas of dcmt_make_joint_tables were picked
+    p->flags = DCMT_JOINT_FILL;
+    p->min_weight = 1;
+    p->valid_thresh = 0.1f;  // the support map's defaults
+    p->max_depth = 100.0f;
+}
+
+int dcmt_make_joint_tables(int radius, double sigma_space, double sigma_guide, dcmt_joint_tables* tables)
+{
+    if (!tables || radius < 1 || radius > kJointMaxRadius) return DCMT_E_INVALID;
+    if (!finite_bits64(sigma_space) || !finite_bits64(sigma_guide) || !(sigma_space > 0.0) || !(sigma_guide > 0.0)) return DCMT_E_INVALID;
+    for (int d2 = 0; d2 < kJointSpace; ++d2)
+        tables->w_space[d2] = d2 <= radius * radius ? (uint16_t)std::nearbyint(255.0 * std::exp(-(double)d2 / (2.0 * sigma_space * sigma_space))) : (uint16_t)0;
+    for (int s = 0; s < kJointGuide; ++s)
+        tables->w_guide[s] = (uint16_t)std::nearbyint(255.0 * std::exp(-((double)s * (double)s) / (2.0 * sigma_guide * sigma_guide)));
+    return DCMT_OK;
+}
+
+int dcmt_joint_bilateral_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t* d_guide, int guide_channels, const dcmt_joint_tables* d_tables, float* d_out,
+                             int rows, int cols, int batch, const dcmt_joint_params* params, uint32_t* d_counts, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const uint32_t lo = planes_bits(&params->valid_thresh), hi = planes_bits(&params->max_depth);
+    const plan::JointPlan pl = plan::plan_joint_bilateral(rows, cols, batch, guide_channels, params->radius, params->flags, params->min_weight, lo, hi,
+                                                          (uintptr_t)d_depth, (uintptr_t)d_guide, (uintptr_t)d_tables, (uintptr_t)d_out, (uintptr_t)d_counts);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_counts, 0, pl.clear_bytes, st));
+    hipLaunchKernelGGL(k_joint, dim3(pl.grid, batch), dim3(256), pl.lds_bytes, st, reinterpret_cast<const uint32_t*>(d_depth), d_guide, guide_channels, d_tables,
+                       reinterpret_cast<uint32_t*>(d_out), (uint32_t)rows, (uint32_t)cols, pl.tiles_x, (int)params->radius, params->flags, params->min_weight, lo,
+                       hi, d_counts);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
 }
 
 }  // extern "C"

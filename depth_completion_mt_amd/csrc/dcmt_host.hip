@@ -388,6 +388,22 @@ int dcmt_support_distance(dcmt_ctx* ctx, const float* sparse, size_t srs, const 
     return rc == DCMT_OK ? fetch(ctx, {&o, &q, &n}) : rc;
 }
 
+// the tables go up as one more input plane
+int dcmt_joint_bilateral(dcmt_ctx* ctx, const float* depth, size_t drs, const uint8_t* guide, size_t grs, int channels, const dcmt_joint_tables* tables,
+                         float* out, size_t ors, int rows, int cols, const dcmt_joint_params* params, uint32_t* counts)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !guide || !tables || !out || !params || !dims_ok(ctx, rows, cols, 1) || (channels != 1 && channels != 3)) return DCMT_E_INVALID;
+    const size_t rb = sizeof(float) * (size_t)cols;
+    Plane z(depth, drs, rb, rows), g(guide, grs, (size_t)channels * (size_t)cols, rows), t(tables, sizeof *tables), o(out, ors, rb, rows),
+        n(counts, 2 * sizeof(uint32_t));
+    int rc = stage(ctx, {&z, &g, &t}, {&o, &n});
+    if (rc == DCMT_OK)
+        rc = dcmt_joint_bilateral_dev(ctx, (const float*)z.dev, (const uint8_t*)g.dev, channels, (const dcmt_joint_tables*)t.dev, (float*)o.dev, rows, cols, 1,
+                                      params, (uint32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -15,6 +15,7 @@
 #include "dcmt_crop.h"
 #include "dcmt_occlusion.h"
 #include "dcmt_photo.h"
+#include "dcmt_joint.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_planes.h"
 #include "dcmt_rectify.h"
@@ -610,6 +611,58 @@ inline SupportPlan plan_support_distance(int rows, int cols, int batch, int elem
     p.plane_bytes = 4 * px;
     p.clear_bytes = beyond ? sizeof(uint32_t) * (size_t)batch : 0;
     p.launches = 2 + (beyond ? 1 : 0);
+    return p;
+}
+
+// ---- dcmt_joint_bilateral_dev ---------------------------------------------------------------------------------------------
+// The joint bilateral filter (dcmt_kernels_joint.h): one kernel, one workgroup per tile of 64 x 16 outputs, whatever the frame; a clear
+// of `counts` goes in front where they are given.  No scratch.  Every refusal of the call that needs no context is here, tested
+// without a device.
+
+// what dcmt_joint_params may hold (dcmt.h); the depth bounds are the occlusion filter's
+inline bool joint_params_ok(int64_t radius, uint32_t flags, uint32_t min_weight, uint32_t valid_thresh_bits, uint32_t max_depth_bits)
+{
+    return radius >= 1 && radius <= kJointMaxRadius && flags != 0u && (flags & ~kJointFlags) == 0u && min_weight >= 1u &&
+           occlusion_params_ok(0, 0, 0, valid_thresh_bits, max_depth_bits);
+}
+
+struct JointPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, bad channels or parameters, buffers that overlap
+    uint32_t tiles_x, tiles_y;       // tiles of 64 x 16 outputs
+    unsigned grid;                   // k_joint: (grid, batch) = (tiles_x * tiles_y, batch), 256 threads
+    uint32_t lds_bytes;              // ... its dynamic LDS (the tile with its halo; the tables are static LDS beside it)
+    size_t plane_bytes;              // batch * rows * cols * 4: what the kernel's 64-bit offsets span on the depth plane
+    size_t guide_bytes;              // batch * rows * cols * channels
+    size_t clear_bytes;              // hipMemsetAsync of counts: 8 bytes a frame (0: no counts wanted)
+    int launches;                    // 1, one more with counts
+};
+
+// rows, cols, batch >= 1 and within the context's limits; the fields of dcmt_joint_params, the two bounds as their bits; counts: 0 =
+// not wanted
+inline JointPlan plan_joint_bilateral(int rows, int cols, int batch, int channels, int64_t radius, uint32_t flags, uint32_t min_weight,
+                                      uint32_t valid_thresh_bits, uint32_t max_depth_bits, uintptr_t depth, uintptr_t guide, uintptr_t tables,
+                                      uintptr_t out, uintptr_t counts)
+{
+    JointPlan p = {};
+    p.status = kInvalid;
+    if (!depth || !guide || !tables || !out || (channels != 1 && channels != 3)) return p;
+    if (!joint_params_ok(radius, flags, min_weight, valid_thresh_bits, max_depth_bits)) return p;
+    if (depth % 4 != 0 || out % 4 != 0 || counts % 4 != 0 || tables % 2 != 0) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    const uintptr_t at[5] = {depth, guide, tables, out, counts};
+    const size_t bytes[5] = {4 * px, (size_t)channels * px, 2 * (size_t)(kJointSpace + kJointGuide), 4 * px, 2 * sizeof(uint32_t) * (size_t)batch};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (at[i] && at[j] && ranges_overlap(at[i], bytes[i], at[j], bytes[j])) return p;
+    p.status = kOk;
+    p.tiles_x = ((uint32_t)cols + kJointTileX - 1) / kJointTileX;
+    p.tiles_y = ((uint32_t)rows + kJointTileY - 1) / kJointTileY;
+    p.grid = p.tiles_x * p.tiles_y;
+    p.lds_bytes = joint_lds_bytes((int)radius);
+    p.plane_bytes = 4 * px;
+    p.guide_bytes = (size_t)channels * px;
+    p.clear_bytes = counts ? 2 * sizeof(uint32_t) * (size_t)batch : 0;
+    p.launches = 1 + (counts ? 1 : 0);
     return p;
 }
 

@@ -613,6 +613,73 @@ int dcmt_support_distance(dcmt_ctx *ctx, const float *sparse, size_t sparse_row_
                           const float *fallback, size_t fallback_row_stride, float *out, size_t out_row_stride, uint16_t *dist2,
                           size_t dist2_row_stride, int rows, int cols, const dcmt_support_params *params, uint32_t *beyond);
 
+/* ---- image-guided filling of a depth plane: the joint (cross) bilateral filter ---------------------------- */
+
+/* Every finish of a depth plane so far is blind to the camera image, and dcmt_support_distance_dev leaves zeros beyond its radius
+ * that nothing fills but a second plane or the cascade again.  This call fills (and, where asked, smooths) a depth plane under the
+ * guidance of the camera image, as joint bilateral upsampling does (Kopf et al.): a pixel takes a weighted mean of the MEASURED
+ * depths around it, a tap weighing more the closer it is and the more its camera pixel looks like the centre's.  Not in the
+ * reference; stated here to the last bit.  The weights are integers out of two tables the host builds: no device exp is part of it.
+ * Per frame, on a depth plane [rows][cols] and a guide [rows][cols][guide_channels] (uint8; 1 channel: grey, 3: BGR, Lab, any):
+ *
+ * VALID.  A pixel is valid when its bits pass the planes' return test (dcmt_superpixel_planes_dev, the occlusion filter, the support
+ *   map): a finite float with valid_thresh <= v <= max_depth, decided on the bit pattern.  Everything else -- 0, NaN, +-inf,
+ *   negatives, -0.0 -- is a HOLE.  The same bounds are enforced: valid_thresh >= 0.0625, max_depth <= 16384.
+ * WHICH PIXELS.  A valid centre without DCMT_JOINT_SMOOTH and a hole without DCMT_JOINT_FILL are copied: the four bytes, opaque.
+ *   Every other pixel is PROCESSED:
+ * TAPS.  The offsets (dy, dx) with d2 = dy^2 + dx^2 <= R^2, R = radius in 1..9 (a disc; 253 taps at R = 9), in row-major order
+ *   (dy ascending, then dx ascending).  A tap outside the frame or on a hole contributes nothing: nothing ever crosses a frame of the
+ *   batch or wraps a row.
+ * WEIGHT.  w = min(w_space[d2], 255) * min(w_guide[s], 255), s = the sum over the channels of |guide(tap) - guide(centre)|
+ *   (0 .. 765): an integer <= 65025, exact as a float.
+ * BASE.  base = the centre's value where the centre is valid; otherwise the value of the first tap in tap order with w > 0.
+ * SUMS.  sw += w in integers: at most 253 * 65025 = 16 451 325 < 2^24, so (float) sw is exact -- this bound is why R stops at 9.
+ *   acc = fadd_rn(acc, fmul_rn((float) w, fsub_rn(v, base))) in tap order from acc = +0.0f, every operation rounded once, nothing
+ *   contracted.  (A valid tap with w = 0 adds +-0 to a sum that is never -0: skipping it changes no bit.)
+ * RESULT.  sw < min_weight: the centre's four bytes are copied; a hole stays a hole.  Otherwise
+ *   y = fadd_rn(base, fdiv_rn(acc, (float) sw)).
+ * The difference form with this base is part of the statement: a constant region comes back bit for bit, and a hole whose only
+ * weighted taps hold one value is filled with exactly that value.
+ * d_counts, or NULL: uint32 [batch][2] = {holes filled, holes left}: a hole of the input that was processed and reached min_weight
+ *   is filled; every other hole of the input is left, processed or not.  The two add up to the holes of the frame.
+ * d_tables: ONE dcmt_joint_tables record for the whole call, built once per configuration (dcmt_make_joint_tables) and uploaded once.
+ *   The device uses min(entry, 255): any bytes are a defined input, and w_space is only ever read at d2 <= R^2.
+ * Nothing depends on the batch size, the frame's position in the batch, alignment, the launch geometry or the run.
+ *
+ * DEVICE pointers, stream-ordered; never synchronises, never allocates.  One launch; a clear of d_counts goes in front where they
+ * are given: two.  No scratch plane of the context is touched and none of its carried state, dcmt_last_path included: it can be
+ * queued in front of or behind any other *_dev call.
+ * DCMT_E_INVALID, nothing written: a null ctx, depth plane, guide, tables, output or params; sizes or a batch beyond the context's
+ * limits; guide_channels other than 1 or 3; radius outside 1..9; flags without DCMT_JOINT_FILL and DCMT_JOINT_SMOOTH, or with any
+ * other bit; min_weight 0; valid_thresh not finite or < 0.0625; max_depth not finite, < valid_thresh or > 16384; d_depth, d_out or
+ * d_counts not 4-byte aligned, d_tables not 2-byte aligned (the guide may start at any byte); any overlap between two of the
+ * buffers, d_out with d_depth included: a neighbour's input would already be output. */
+enum { DCMT_JOINT_FILL = 1, DCMT_JOINT_SMOOTH = 2 };
+typedef struct {
+    int32_t  radius;        /* 6     R: the taps are the disc dy^2 + dx^2 <= R^2; 1..9                              */
+    uint32_t flags;         /* FILL  DCMT_JOINT_FILL: holes are processed; DCMT_JOINT_SMOOTH: valid pixels are      */
+    uint32_t min_weight;    /* 1     a processed pixel whose sw stays below it is copied; >= 1                      */
+    float    valid_thresh;  /* 0.1   the smallest depth that is valid, metres; >= 0.0625                            */
+    float    max_depth;     /* 100   the largest; <= 16384                                                          */
+} dcmt_joint_params;        /* 20 bytes */
+typedef struct {
+    uint16_t w_space[128];  /* indexed by dy^2 + dx^2 (read at <= R^2 <= 81 only)                                   */
+    uint16_t w_guide[768];  /* indexed by the L1 distance of the guide pixels, 0 .. 765                              */
+} dcmt_joint_tables;        /* 1792 bytes */
+void dcmt_default_joint_params(dcmt_joint_params *p);
+/* Host, no GPU: w_space[d2] = rne(255 exp(-d2 / (2 sigma_space^2))) for d2 <= radius^2, else 0; w_guide[s] = rne(255 exp(-s^2 /
+ * (2 sigma_guide^2))); both in f64, rounded to nearest even.  DCMT_E_INVALID, nothing written: a null record, radius outside 1..9, a
+ * sigma that is not finite or not > 0. */
+int dcmt_make_joint_tables(int radius, double sigma_space, double sigma_guide, dcmt_joint_tables *tables);
+int dcmt_joint_bilateral_dev(dcmt_ctx *ctx, const float *d_depth, const uint8_t *d_guide, int guide_channels, const dcmt_joint_tables *d_tables,
+                             float *d_out, int rows, int cols, int batch, const dcmt_joint_params *params, uint32_t *d_counts /* [batch][2] or NULL */,
+                             void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: depth's and out's >= 4 * cols, the guide's >= guide_channels * cols);
+ * tables: a HOST record; counts: two values or NULL.  The same bits as the device call.  What dcmt_shim::joint_bilateral_fill calls. */
+int dcmt_joint_bilateral(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, const uint8_t *guide, size_t guide_row_stride,
+                         int guide_channels, const dcmt_joint_tables *tables, float *out, size_t out_row_stride, int rows, int cols,
+                         const dcmt_joint_params *params, uint32_t *counts);
+
 /* ---- consumer of the path's output: stereo photometric refinement (N4) ----------------- */
 
 /* What DC_stereo_lidar/main_sl.cpp does with the dense depth (:1165-1246): depth -> disparity (get_initial_disparity

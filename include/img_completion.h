@@ -582,6 +582,34 @@ inline unsigned trust_mask(const cv::Mat& sparse_r_img, const cv::Mat& dense_img
     return beyond;
 }
 
+// The joint bilateral filter, as dcmt.h states it (dcmt_joint_bilateral): filled_img is overwritten with a fresh CV_32FC1 image in
+// which every hole of depth_img (CV_32FC1, metres) that has measured depths around it whose pixels of guide_img (CV_8UC1 or CV_8UC3, of
+// depth_img's size) look like its own holds their weighted mean; with DCMT_JOINT_SMOOTH among params->flags the valid pixels are
+// smoothed the same way, else they keep their bytes.  params == nullptr: dcmt_default_joint_params; tables == nullptr:
+// dcmt_make_joint_tables(params->radius, sigma_space, sigma_guide).  Returns the number of holes filled; *left: the holes that stay.
+inline unsigned joint_bilateral_fill(const cv::Mat& depth_img, const cv::Mat& guide_img, cv::Mat& filled_img, const dcmt_joint_params* params = nullptr,
+                                     const dcmt_joint_tables* tables = nullptr, double sigma_space = 3.0, double sigma_guide = 10.0, unsigned* left = nullptr)
+{
+    check_input(depth_img);
+    const int rows = depth_img.rows, cols = depth_img.cols;
+    if ((guide_img.type() != CV_8UC1 && guide_img.type() != CV_8UC3) || guide_img.rows != rows || guide_img.cols != cols)
+        throw std::runtime_error("joint_bilateral_fill: the guide must be CV_8UC1 or CV_8UC3 of the depth image's size");
+    dcmt_joint_params def;
+    dcmt_default_joint_params(&def);
+    const dcmt_joint_params* p = params ? params : &def;
+    dcmt_joint_tables own;
+    if (!tables) raise(dcmt_make_joint_tables(p->radius, sigma_space, sigma_guide, &own), "joint_bilateral_fill");
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    uint32_t counts[2] = {0, 0};
+    raise(dcmt_joint_bilateral(thread_ctx().get(rows, cols), depth_img.ptr<float>(), depth_img.step[0], guide_img.ptr<unsigned char>(), guide_img.step[0],
+                               guide_img.type() == CV_8UC3 ? 3 : 1, tables ? tables : &own, out.ptr<float>(), out.step[0], rows, cols, p, counts),
+          "joint_bilateral_fill");
+    filled_img = out;
+    if (left) *left = counts[1];
+    return counts[0];
+}
+
 // unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
 // takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
