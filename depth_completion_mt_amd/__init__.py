@@ -14,7 +14,8 @@ from .api import (CLOUD_DTYPE, Context, DcmtError, bgr_to_gray, bgr_to_lab, eval
                   RECTIFY_CALIB_DTYPE, make_rectify_calib, undistort_rectify,
                   PLANE_FIT_DTYPE, make_planes_params, fit_superpixel_planes, superpixel_planes_max_labels,
                   make_occlusion_params, filter_occluded_returns, make_support_params, distance_to_returns, trust_mask,
-                  JOINT_TABLES_DTYPE, make_joint_params, make_joint_tables, joint_bilateral_fill)
+                  JOINT_TABLES_DTYPE, make_joint_params, make_joint_tables, joint_bilateral_fill,
+                  make_normals_params, make_normals_calib, depth_normals, filter_flying_pixels, reproject_pc_normals)
 from . import synth  # noqa: F401
 
 __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_completion", "interpolate_with_superpixels",
@@ -28,7 +29,8 @@ __all__ = ["Context", "DcmtError", "eval_summary", "evaluate_performance", "img_
            "RECTIFY_CALIB_DTYPE", "make_rectify_calib", "undistort_rectify",
            "PLANE_FIT_DTYPE", "make_planes_params", "fit_superpixel_planes", "superpixel_planes_max_labels",
            "make_occlusion_params", "filter_occluded_returns", "make_support_params", "distance_to_returns", "trust_mask",
-           "JOINT_TABLES_DTYPE", "make_joint_params", "make_joint_tables", "joint_bilateral_fill"]
+           "JOINT_TABLES_DTYPE", "make_joint_params", "make_joint_tables", "joint_bilateral_fill",
+           "make_normals_params", "make_normals_calib", "depth_normals", "filter_flying_pixels", "reproject_pc_normals"]
 
 
 def __getattr__(name):

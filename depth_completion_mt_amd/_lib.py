@@ -53,6 +53,7 @@ EXPORTS = (
     "dcmt_default_occlusion_params", "dcmt_sparse_occlusion_dev", "dcmt_sparse_occlusion_u16_dev", "dcmt_sparse_occlusion",
     "dcmt_default_support_params", "dcmt_support_distance_dev", "dcmt_support_distance_u16_dev", "dcmt_support_distance",
     "dcmt_default_joint_params", "dcmt_make_joint_tables", "dcmt_joint_bilateral_dev", "dcmt_joint_bilateral",
+    "dcmt_default_normals_params", "dcmt_depth_normals_dev", "dcmt_depth_normals_calib_dev", "dcmt_depth_normals",
 )
 
 
@@ -165,6 +166,11 @@ class JointParams(ctypes.Structure):
 class JointTables(ctypes.Structure):
     """Mirror of dcmt_joint_tables (include/dcmt.h), 1792 bytes."""
     _fields_ = [("w_space", ctypes.c_uint16 * 128), ("w_guide", ctypes.c_uint16 * 768)]
+
+
+class NormalsParams(ctypes.Structure):
+    """Mirror of dcmt_normals_params (include/dcmt.h), 12 bytes."""
+    _fields_ = [("min_plane_dist", ctypes.c_float), ("valid_thresh", ctypes.c_float), ("max_depth", ctypes.c_float)]
 
 
 class CropSrc(ctypes.Structure):
@@ -339,6 +345,11 @@ def lib() -> ctypes.CDLL:
         L.dcmt_make_joint_tables.argtypes = [i, ctypes.c_double, ctypes.c_double, vp]
         L.dcmt_joint_bilateral_dev.argtypes = [vp, vp, vp, i, vp, vp, i, i, i, vp, vp, vp]
         L.dcmt_joint_bilateral.argtypes = [vp, vp, sz, vp, sz, i, vp, vp, sz, i, i, vp, vp]
+        L.dcmt_default_normals_params.argtypes = [vp]
+        L.dcmt_default_normals_params.restype = None
+        L.dcmt_depth_normals_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        L.dcmt_depth_normals_calib_dev.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp]
+        L.dcmt_depth_normals.argtypes = [vp, vp, sz, i, i, vp, vp, vp, sz, vp, sz, vp]
         for twin in ("dcmt_project_points_dev", "dcmt_project_points_calib_dev", "dcmt_reproject_depth_dev", "dcmt_reproject_depth_calib_dev",
                      "dcmt_project_points", "dcmt_reproject_depth"):           # the nearest-wins forms take their twins' arguments
             getattr(L, nearest_name(twin)).argtypes = getattr(L, twin).argtypes

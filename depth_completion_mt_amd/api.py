@@ -359,6 +359,37 @@ def make_support_params(max_radius: int | None = None, valid_thresh: float | Non
     return p
 
 
+def make_normals_params(min_plane_dist: float | None = None, valid_thresh: float | None = None, max_depth: float | None = None) -> L.NormalsParams:
+    """dcmt_normals_params: min_plane_dist 0.4, valid_thresh 0.1, max_depth 100 unless overridden.  Raises ValueError on what
+    dcmt_depth_normals_dev refuses of them: min_plane_dist not finite or outside 0..1024, valid_thresh not finite or < 0.0625,
+    max_depth not finite, < valid_thresh or > 16384."""
+    p = L.NormalsParams()
+    L.lib().dcmt_default_normals_params(ctypes.byref(p))
+    for name, v in (("min_plane_dist", min_plane_dist), ("valid_thresh", valid_thresh), ("max_depth", max_depth)):
+        if v is not None:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} = {v!r}: a finite float")
+            setattr(p, name, float(v))
+    if not 0.0 <= p.min_plane_dist <= 1024.0:
+        raise ValueError(f"min_plane_dist = {p.min_plane_dist}: 0 .. 1024")
+    if not p.valid_thresh >= 0.0625:
+        raise ValueError(f"valid_thresh = {p.valid_thresh}: >= 0.0625")
+    if not p.valid_thresh <= p.max_depth <= 16384.0:
+        raise ValueError(f"max_depth = {p.max_depth}: valid_thresh .. 16384")
+    return p
+
+
+def _normals_intrinsics_or_raise(fx, fy, cx, cy) -> None:
+    """The bounds dcmt_depth_normals_dev puts on a dcmt_cloud_params record (scalars or arrays): fx, fy finite with
+    2^-10 <= |.| <= 2^20, |cx|, |cy| <= 2^20."""
+    for name, v, lo in (("fx", fx, 2.0 ** -10), ("fy", fy, 2.0 ** -10), ("cx", cx, 0.0), ("cy", cy, 0.0)):
+        a = np.abs(np.atleast_1d(np.asarray(v, dtype=np.float64)))
+        bad = ~(np.isfinite(a) & (a >= lo) & (a <= 2.0 ** 20))
+        if bad.any():
+            raise ValueError(f"{name} = {np.atleast_1d(v)[int(np.argwhere(bad)[0][0])]!r} in record {int(np.argwhere(bad)[0][0])}: finite, "
+                             f"{'2^-10 <= ' if lo else ''}|{name}| <= 2^20")
+
+
 JOINT_TABLES_DTYPE = np.dtype([("w_space", "<u2", (128,)), ("w_guide", "<u2", (768,))])                         # dcmt_joint_tables, 1792 B
 
 
@@ -523,6 +554,14 @@ def make_cloud_calib(fx, fy, cx, cy) -> np.ndarray:
     must be an array).  Raises ValueError on a non-finite entry and on fx or fy zero, what dcmt_depth_to_cloud_dev refuses."""
     out = np.zeros(_batch_of(fx=fx, fy=fy, cx=cx, cy=cy), CLOUD_CALIB_DTYPE)
     _intrinsics(out, len(out), fx, fy, cx, cy)
+    return out
+
+
+def make_normals_calib(fx, fy, cx, cy) -> np.ndarray:
+    """The table of Context.depth_normals_calib_dev: make_cloud_calib's table (the one depth_to_cloud_calib_dev takes), refused with
+    ValueError where dcmt_depth_normals_dev refuses a record: fx, fy outside 2^-10 <= |.| <= 2^20, |cx| or |cy| above 2^20."""
+    out = make_cloud_calib(fx, fy, cx, cy)
+    _normals_intrinsics_or_raise(out["fx"], out["fy"], out["cx"], out["cy"])
     return out
 
 
@@ -1399,6 +1438,74 @@ class Context:
         _check(st, "dcmt_joint_bilateral")
         return out, int(n[0]), int(n[1])
 
+    # ---- surface normals and the flying-pixel filter (dcmt_depth_normals*) ------------------
+    def depth_normals_dev(self, d_depth, params: L.CloudParams | None = None, normals: bool = True, d_normals=None, d_out=None, counts: bool = False,
+                          d_counts=None, stream: int | None = None, filtered: bool = False, **kw):
+        """The unit normal and plane distance of every pixel of a depth plane, and the flying-pixel filter (dcmt_depth_normals_dev, as
+        include/dcmt.h states it), without synchronising.  d_depth: f32 CUDA tensor [batch][rows][cols] (or [rows][cols]), metres.
+        params: the intrinsics (make_cloud_params; the reference's by default).  normals=True or a d_normals (f32, [..][rows][cols][4]:
+        nx ny nz dist): the records.  d_out (f32, the same shape; may be d_depth itself: in place): the plane without the pixels whose
+        local plane passes closer to the camera centre than min_plane_dist; with filtered=True, or with normals=False, it is allocated.
+        counts=True or a d_counts (any 4-byte dtype, [batch][2]): {removed, valid pixels with no normal} per frame, as int32.  Returns
+        the outputs wanted in the order (d_normals, d_out, d_counts): the tensor itself where that is one, else a tuple.  kw: the
+        fields of make_normals_params.  Outputs that are not given are allocated on the stream the call enqueues on."""
+        p = params or make_cloud_params()
+        _normals_intrinsics_or_raise(p.fx, p.fy, p.cx, p.cy)
+        return self._depth_normals_dev(d_depth, "dcmt_depth_normals_dev", lambda b: ctypes.byref(p), normals, d_normals, d_out, filtered, counts, d_counts, stream, kw)
+
+    def depth_normals_calib_dev(self, d_depth, d_calib, normals: bool = True, d_normals=None, d_out=None, counts: bool = False, d_counts=None,
+                                stream: int | None = None, filtered: bool = False, **kw):
+        """depth_normals_dev with each frame's own intrinsics (dcmt_depth_normals_calib_dev): d_calib is a CUDA tensor holding [batch]
+        dcmt_cloud_params records (make_normals_calib or make_cloud_calib, calib_to_device), read on the stream the call enqueues on.
+        A frame whose record is outside the call's bounds gets no normals and loses no pixel: its counts are {0, its valid pixels}."""
+        return self._depth_normals_dev(d_depth, "dcmt_depth_normals_calib_dev", lambda b: _table_ptr(d_calib, b, CLOUD_CALIB_DTYPE.itemsize), normals,
+                                       d_normals, d_out, filtered, counts, d_counts, stream, kw)
+
+    def _depth_normals_dev(self, d_depth, name, geo, normals, d_normals, d_out, filtered, counts, d_counts, stream, kw):
+        """depth_normals_dev / depth_normals_calib_dev: `name` the entry point, geo(batch) what it takes behind batch."""
+        import torch
+        assert _is_dev(d_depth, torch.float32)
+        b, r, c = _brc(d_depth)
+        p = make_normals_params(**kw)
+        want_normals = normals or d_normals is not None
+        want_out = filtered or d_out is not None or not want_normals
+        want_counts = counts or d_counts is not None
+        with _on_stream(stream, d_depth):
+            if want_normals and d_normals is None:
+                d_normals = torch.empty(tuple(d_depth.shape) + (4,), dtype=torch.float32, device=d_depth.device)
+            if want_out and d_out is None:
+                d_out = torch.empty(tuple(d_depth.shape), dtype=torch.float32, device=d_depth.device)
+            if want_counts and d_counts is None:
+                d_counts = torch.empty((b, 2), dtype=torch.int32, device=d_depth.device)
+        assert d_normals is None or (_is_dev(d_normals, torch.float32) and d_normals.numel() == 4 * b * r * c)
+        assert d_out is None or (_is_dev(d_out, torch.float32) and d_out.numel() == b * r * c)
+        assert d_counts is None or (_is_dev(d_counts) and d_counts.element_size() == 4 and d_counts.numel() == 2 * b)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        st = getattr(L.lib(), name)(self._h, d_depth.data_ptr(), r, c, b, geo(b), ctypes.byref(p), ptr(d_normals), ptr(d_out), ptr(d_counts),
+                                    _stream(stream, d_depth))
+        _check(st, name)
+        got = tuple(t for t, w in ((d_normals, want_normals), (d_out, want_out), (d_counts, want_counts)) if w)
+        return got[0] if len(got) == 1 else got
+
+    def depth_normals(self, depth: np.ndarray, params: L.CloudParams | None = None, normals: bool = True, filtered: bool = True, **kw):
+        """One frame of host memory (dcmt_depth_normals, synchronous; any row stride): (the records, f32 [rows][cols][4] = nx ny nz
+        dist, or None with normals=False; the filtered plane, a new f32 array, or None with filtered=False; the pixels removed; the
+        valid pixels with no normal).  params: the intrinsics (make_cloud_params); kw: the fields of make_normals_params."""
+        z = _frame_f32(depth)
+        rows, cols = z.shape
+        if not normals and not filtered:
+            raise ValueError("normals or filtered: at least one of them")
+        cp = params or make_cloud_params()
+        _normals_intrinsics_or_raise(cp.fx, cp.fy, cp.cx, cp.cy)
+        p = make_normals_params(**kw)
+        nrm = np.empty((rows, cols, 4), dtype=np.float32) if normals else None
+        out = np.empty(z.shape, dtype=np.float32) if filtered else None
+        n = (ctypes.c_uint32 * 2)()
+        at = lambda a: (None, 0) if a is None else (a.ctypes.data, a.strides[0])
+        st = L.lib().dcmt_depth_normals(self._h, z.ctypes.data, z.strides[0], rows, cols, ctypes.byref(cp), ctypes.byref(p), *at(nrm), *at(out), n)
+        _check(st, "dcmt_depth_normals")
+        return nrm, out, int(n[0]), int(n[1])
+
     # ---- accuracy against ground truth (dcmt_evaluate*) ------------------------------
     def evaluate_dev(self, d_gt, d_pred, thresh: float = 0.0, mode="both", gt_scale: float = 1.0 / 256.0, d_out=None,
                      stream: int | None = None):
@@ -1980,6 +2087,23 @@ def joint_bilateral_fill(depth, guide, tables=None, **params):
     return _ctx_for(z.shape[0], z.shape[1], 1).joint_bilateral(z, guide, tables, **params)[0]
 
 
+def depth_normals(depth, params=None, **kw):
+    """The surface normals of one host depth frame (dcmt_depth_normals, as include/dcmt.h states it): depth f32 [rows][cols] in
+    metres -> f32 [rows][cols][4], the unit normal towards the camera and the distance of the pixel's local plane from the camera
+    centre; four zeros on a hole and where no normal is defined.  params: the intrinsics (make_cloud_params; the reference's by
+    default); kw: the fields of make_normals_params."""
+    z = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).depth_normals(z, params, filtered=False, **kw)[0]
+
+
+def filter_flying_pixels(depth, params=None, **kw):
+    """The flying-pixel filter of one host depth frame (dcmt_depth_normals): a new f32 array, 0 where the pixel's local plane passes
+    closer to the camera centre than min_plane_dist (default 0.4 m) -- the veil a blur strings between an object and the wall
+    behind it --, elsewhere the input's bits.  params: the intrinsics; kw: the fields of make_normals_params."""
+    z = np.asarray(depth, dtype=np.float32)
+    return _ctx_for(z.shape[0], z.shape[1], 1).depth_normals(z, params, normals=False, **kw)[1]
+
+
 def depth_to_u16(depth, scale: float = 256.0):
     """A depth plane in metres as KITTI stores it: uint16 round(depth * scale), ties to even, saturated (what the reference's
     commented imwrite lines intend, LC/main_lc.cpp:233-234).  A numpy frame goes through the host entry point; a CUDA tensor
@@ -2047,6 +2171,14 @@ def reproject_pc(depth):
     return reproject_pc_colors(depth, None)
 
 
+def reproject_pc_normals(depth, bgr=None):
+    """reproject_pc_colors (reproject_pc without bgr) of one host frame with the normal of every point: (the cloud, f32 [n][4] = nx ny
+    nz dist).  The cloud's records are the pixels with depth > 0 in row-major order, so the row-major selection of the normals is
+    their order.  Both under the reference's intrinsics (make_cloud_params)."""
+    a = np.asarray(depth, dtype=np.float32)
+    return reproject_pc_colors(a, bgr), depth_normals(a)[a > 0]
+
+
 def unrectify_sol(depth_pre_optim, out_shape, R_rect, nearest: bool = False) -> np.ndarray:
     """The reference's unrectify_sol (SL/main_sl.cpp:967-1028, called at :1228) on one host frame, without its drawing and printing:
     depth_pre_optim forward-warped into the un-rectified camera's frame, a new f32 array of out_shape = (rows, cols) that is 0 where
@@ -2059,25 +2191,38 @@ def unrectify_sol(depth_pre_optim, out_shape, R_rect, nearest: bool = False) -> 
     return ctx.reproject_depth(a, rows, cols, make_reproject_params(M=inverse_f32(R_rect)), nearest=nearest)
 
 
-def write_pcd(path, points) -> None:
+def write_pcd(path, points, normals=None) -> None:
     """Writes a cloud (CLOUD_DTYPE records, or anything of 16 bytes per record such as a float32 [n, 4] array) as the binary
     .pcd pcl::PCDWriter::writeBinary makes of a PointXYZRGB cloud (SL/main_sl.cpp:962-963): FIELDS x y z rgb, SIZE 4 4 4 4,
-    TYPE F F F F, COUNT 1 1 1 1, WIDTH n, HEIGHT 1, POINTS n, DATA binary, then the records as they are.  The header text is
+    TYPE F F F F, COUNT 1 1 1 1, WIDTH n, HEIGHT 1, POINTS n, DATA binary, then the records as they are.  With normals (f32 [n][3]
+    or [n][4] as reproject_pc_normals gives them: nx ny nz and a fourth column that is not written) every record is followed by
+    normal_x normal_y normal_z curvature, the fields of PCL's PointXYZRGBNormal, curvature written as 0.  The header text is
     what PCL's file-format page documents; neither PCL nor a file written by it was available to compare with, so it is checked
     only by the round trip through read_pcd."""
     rec = np.ascontiguousarray(points)
     if rec.dtype != CLOUD_DTYPE:
         rec = rec.view(np.uint8).reshape(-1, 16).view(CLOUD_DTYPE).reshape(-1)
     n = rec.shape[0]
-    head = ("# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F F\nCOUNT 1 1 1 1\n"
+    fields, k = "x y z rgb", 4
+    body = rec.view(np.uint8).reshape(n, 16)
+    if normals is not None:
+        nrm = np.asarray(normals, dtype=np.float32)
+        if nrm.ndim != 2 or nrm.shape[0] != n or nrm.shape[1] not in (3, 4):
+            raise ValueError(f"write_pcd: normals of shape {nrm.shape} for {n} points; [n][3] or [n][4]")
+        tail = np.zeros((n, 4), dtype=np.float32)
+        tail[:, :3] = nrm[:, :3]
+        body = np.concatenate([body, tail.view(np.uint8).reshape(n, 16)], axis=1)
+        fields, k = fields + " normal_x normal_y normal_z curvature", 8
+    head = (f"# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS {fields}\nSIZE{' 4' * k}\nTYPE{' F' * k}\nCOUNT{' 1' * k}\n"
             f"WIDTH {n}\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS {n}\nDATA binary\n")
     with open(path, "wb") as f:
         f.write(head.encode("ascii"))
-        f.write(rec.tobytes())
+        f.write(np.ascontiguousarray(body).tobytes())
 
 
-def read_pcd(path) -> np.ndarray:
-    """Reads a binary .pcd of four 4-byte fields per point (what write_pcd writes) back into CLOUD_DTYPE records."""
+def read_pcd(path, normals: bool = False):
+    """Reads a binary .pcd of four or eight 4-byte fields per point (what write_pcd writes) back into CLOUD_DTYPE records; with
+    normals=True (the records, f32 [n][3] = normal_x normal_y normal_z), and ValueError for a file without them."""
     with open(path, "rb") as f:
         blob = f.read()
     fields, pos = {}, 0
@@ -2091,12 +2236,22 @@ def read_pcd(path) -> np.ndarray:
         fields[key] = val.strip()
         if key == "DATA":
             break
-    if fields["DATA"] != "binary" or fields.get("SIZE") != "4 4 4 4" or fields.get("COUNT") != "1 1 1 1":
-        raise ValueError("read_pcd: only binary files of four 4-byte fields per point are supported")
+    names = fields.get("FIELDS", "").split()
+    k = len(names)
+    if fields["DATA"] != "binary" or k not in (4, 8) or fields.get("SIZE") != " ".join(["4"] * k) or fields.get("COUNT") != " ".join(["1"] * k):
+        raise ValueError("read_pcd: only binary files of four or eight 4-byte fields per point are supported")
+    if k == 8 and names[4:7] != ["normal_x", "normal_y", "normal_z"]:
+        raise ValueError("read_pcd: eight fields that are not x y z rgb normal_x normal_y normal_z curvature")
+    if normals and k != 8:
+        raise ValueError("read_pcd: the file has no normals")
     n = int(fields["POINTS"])
-    if len(blob) - pos < 16 * n:
+    if len(blob) - pos < 4 * k * n:
         raise ValueError("read_pcd: file shorter than its POINTS line says")
-    return np.frombuffer(blob, dtype=CLOUD_DTYPE, count=n, offset=pos).copy()
+    body = np.frombuffer(blob, dtype=np.uint8, count=4 * k * n, offset=pos).reshape(n, 4 * k)
+    pts = np.ascontiguousarray(body[:, :16]).view(CLOUD_DTYPE).reshape(n).copy()
+    if not normals:
+        return pts
+    return pts, np.ascontiguousarray(body[:, 16:28]).view(np.float32).reshape(n, 3).copy()
 
 
 _jet = None

@@ -2,7 +2,7 @@
 // object of their own, and the entry points that launch them: dcmt_depth_to_cloud_dev, dcmt_gaussian5_dev, dcmt_reproject_depth_dev,
 // the four nearest-wins scatter calls (dcmt_kernels_nearest.h: dcmt_project_points_nearest*_dev, dcmt_reproject_depth_nearest*_dev),
 // dcmt_bgr_convert_dev, dcmt_crop_frames_dev, dcmt_depth_to_u16_dev, dcmt_bilateral5_dev (dcmt_kernels_bilateral.h; the cascade's bilateral finish launches the same kernel through bilateral5_enqueue),
-// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h), dcmt_support_distance_dev and dcmt_support_distance_u16_dev (dcmt_kernels_support.h), dcmt_joint_bilateral_dev (dcmt_kernels_joint.h),
+// dcmt_slic_connectivity_dev (dcmt_kernels_connect.h), dcmt_filter_speckles_dev (dcmt_kernels_speckle.h), dcmt_slic_contours_dev and dcmt_slic_cluster_means_dev (dcmt_kernels_contour.h), dcmt_superpixel_planes_dev (dcmt_kernels_planes.h), dcmt_sparse_occlusion_dev and dcmt_sparse_occlusion_u16_dev (dcmt_kernels_occlusion.h), dcmt_support_distance_dev and dcmt_support_distance_u16_dev (dcmt_kernels_support.h), dcmt_joint_bilateral_dev (dcmt_kernels_joint.h), dcmt_depth_normals_dev and dcmt_depth_normals_calib_dev (dcmt_kernels_normals.h),
 // dcmt_photo_error_dev (dcmt_kernels_photo.h), the defaults of their parameter structs and dcmt_lab_tables.  A *_calib_dev entry point
 // shares its one launch sequence with the uniform entry point beside it: the calibration source (one record by value, or the device
 // table) is the kernels' template type.  The context and the checks they share with dcmt.hip come from dcmt_ctx.h; their single-frame
@@ -27,6 +27,7 @@
 #include "dcmt_kernels_occlusion.h"
 #include "dcmt_kernels_support.h"
 #include "dcmt_kernels_joint.h"
+#include "dcmt_kernels_normals.h"
 
 using namespace dcmt;
 
@@ -778,6 +779,80 @@ int dcmt_joint_bilateral_dev(dcmt_ctx* ctx, const float* d_depth, const uint8_t*
                        hi, d_counts);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
+}
+
+}  // extern "C"
+
+// ---- surface normals and the flying-pixel filter (dcmt_kernels_normals.h) ---------------------------------------------------------
+static uint64_t normals_bits64(const double* v)
+{
+    uint64_t b;
+    std::memcpy(&b, v, sizeof b);                     // the bits as they lie in the struct: nothing the compiler may assume finite
+    return b;
+}
+
+// The launches plan_depth_normals names: the clear of the counts, k_normals and, in place, k_occl_apply on the mask the kernel left
+// on pp[0] (scratch every completion call rewrites before it reads it).  None of the context's carried state is read or written,
+// and nothing is allocated.  cloud / d_table as for depth_to_cloud
+static int depth_normals(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_cloud_params* cloud,
+                         const dcmt_cloud_params* d_table, const dcmt_normals_params* params, dcmt_normal* d_normals, float* d_out, uint32_t* d_counts,
+                         void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !params || (!cloud && !d_table) || !dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    const uint32_t db = planes_bits(&params->min_plane_dist), lo = planes_bits(&params->valid_thresh), hi = planes_bits(&params->max_depth);
+    const bool ok = plan::normals_params_ok(db, lo, hi) &&
+                    (!cloud || normals_intrinsics_ok(normals_bits64(&cloud->fx), normals_bits64(&cloud->fy), normals_bits64(&cloud->cx), normals_bits64(&cloud->cy)));
+    const plan::NormalsPlan pl = plan::plan_depth_normals(rows, cols, batch, ok, (uintptr_t)d_depth, d_table != nullptr, (uintptr_t)d_table, (uintptr_t)d_normals,
+                                                          (uintptr_t)d_out, (uintptr_t)d_counts);
+    if (pl.status != plan::kOk) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    volatile float dm = params->min_plane_dist;       // one f32 product, rounded once: never contracted, never widened
+    volatile float dmin2 = dm * dm;
+    const uint32_t* depth = reinterpret_cast<const uint32_t*>(d_depth);
+    uint32_t* out = reinterpret_cast<uint32_t*>(d_out);
+    uint32_t* mask = pl.in_place ? reinterpret_cast<uint32_t*>(ctx->pp[0].p) : nullptr;
+    uint4* recs = reinterpret_cast<uint4*>(d_normals);
+    const uint32_t r = (uint32_t)rows, c = (uint32_t)cols;
+    if (pl.clear_bytes) DCMT_HIP(ctx, hipMemsetAsync(d_counts, 0, pl.clear_bytes, st));
+    const auto launch = [&](auto src) {                // NormK or NormTable
+        with_value<true, false>(d_normals != nullptr, [&](auto nrm) {
+            with_value<kNormOutNone, kNormOutFused, kNormOutMask>(pl.out_mode, [&](auto om) {
+                if constexpr (decltype(nrm)::value || decltype(om)::value != kNormOutNone)
+                    hipLaunchKernelGGL((k_normals<decltype(nrm)::value, decltype(om)::value, decltype(src)>), dim3(pl.grid_x, batch), dim3(256), 0, st, depth, r, c,
+                                       pl.strips, pl.bands, pl.band_rows, src, lo, hi, (float)dmin2, recs, out, mask, pl.words_x, d_counts);
+            });
+        });
+    };
+    if (d_table) launch(NormTable{d_table});
+    else launch(NormK{(float)cloud->fx, (float)cloud->fy, (float)cloud->cx, (float)cloud->cy});
+    if (pl.in_place) hipLaunchKernelGGL((k_occl_apply<uint32_t>), dim3(pl.apply_x, batch), dim3(256), 0, st, mask, r, c, pl.words_x, out, (uint32_t*)nullptr);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+extern "C" {
+
+void dcmt_default_normals_params(dcmt_normals_params* p)
+{
+    if (!p) return;
+    p->min_plane_dist = 0.4f;   // measured on the cascade's output, whose ground bends to 0.50 m at the frame's sides: DESIGN.md section 38
+    p->valid_thresh = 0.1f;     // the planes' defaults
+    p->max_depth = 100.0f;
+}
+
+int dcmt_depth_normals_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_cloud_params* cloud,
+                           const dcmt_normals_params* params, dcmt_normal* d_normals, float* d_out, uint32_t* d_counts, void* stream)
+{
+    if (!cloud) return DCMT_E_INVALID;
+    return depth_normals(ctx, d_depth, rows, cols, batch, cloud, nullptr, params, d_normals, d_out, d_counts, stream);
+}
+
+int dcmt_depth_normals_calib_dev(dcmt_ctx* ctx, const float* d_depth, int rows, int cols, int batch, const dcmt_cloud_params* d_cloud,
+                                 const dcmt_normals_params* params, dcmt_normal* d_normals, float* d_out, uint32_t* d_counts, void* stream)
+{
+    if (!d_cloud) return DCMT_E_INVALID;
+    return depth_normals(ctx, d_depth, rows, cols, batch, nullptr, d_cloud, params, d_normals, d_out, d_counts, stream);
 }
 
 }  // extern "C"

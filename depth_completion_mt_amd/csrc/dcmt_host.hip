@@ -404,6 +404,19 @@ int dcmt_joint_bilateral(dcmt_ctx* ctx, const float* depth, size_t drs, const ui
     return rc == DCMT_OK ? fetch(ctx, {&o, &n}) : rc;
 }
 
+int dcmt_depth_normals(dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols, const dcmt_cloud_params* cloud, const dcmt_normals_params* params,
+                       dcmt_normal* normals, size_t nrs, float* out, size_t ors, uint32_t* counts)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !depth || !cloud || !params || (!normals && !out) || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t rb = sizeof(float) * (size_t)cols;
+    Plane z(depth, drs, rb, rows), q(normals, nrs, sizeof(dcmt_normal) * (size_t)cols, rows), o(out, ors, rb, rows), n(counts, 2 * sizeof(uint32_t));
+    int rc = stage(ctx, {&z}, {&q, &o, &n});
+    if (rc == DCMT_OK)
+        rc = dcmt_depth_normals_dev(ctx, (const float*)z.dev, rows, cols, 1, cloud, params, (dcmt_normal*)q.dev, (float*)o.dev, (uint32_t*)n.dev, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&q, &o, &n}) : rc;
+}
+
 // dcmt_reproject_depth and dcmt_reproject_depth_nearest, likewise
 static int reproject_depth_host(decltype(&dcmt_reproject_depth_dev) dev_call, dcmt_ctx* ctx, const float* depth, size_t drs, int rows, int cols,
                                 const dcmt_reproject_params* params, float* out, size_t ors, int out_rows, int out_cols)

@@ -16,6 +16,7 @@
 #include "dcmt_occlusion.h"
 #include "dcmt_photo.h"
 #include "dcmt_joint.h"
+#include "dcmt_normals.h"
 #include "dcmt_plan.h"         // ranges_overlap
 #include "dcmt_planes.h"
 #include "dcmt_rectify.h"
@@ -940,6 +941,70 @@ inline PhotoPlan plan_photo_error(int rows, int cols, int batch, int window, uin
     p.pitch = photo_pitch(c);
     p.lds = photo_lds_bytes(p.band, w, c);
     p.grid_x = bands();
+    return p;
+}
+
+// ---- dcmt_depth_normals_dev, dcmt_depth_normals_calib_dev --------------------------------------------------------------------
+// Normals and the flying-pixel filter of a depth plane (dcmt_kernels_normals.h): one kernel in k_gauss5's shape and with its short-band
+// rule, one wave per (strip of kNormCols columns, band of band_rows rows).  Out of place it writes the records and the filtered
+// plane itself.  In place (out == depth exactly) a neighbouring wave may already have zeroed what another still has to read, and
+// every decision is taken on the input: the decisions go to a mask of one bit per pixel on pp[0], in the occlusion filter's layout
+// ([frame][row][words_x] 32-bit words; words_x <= cols, so the mask never exceeds the borrowed plane), and k_occl_apply zeroes.  A
+// clear of `counts` goes in front where they are given.  The checks on the arguments are here as well, tested without a device.
+
+// what dcmt_normals_params may hold (dcmt.h), as the bits of its three floats; the depth bounds are the occlusion filter's
+inline bool normals_params_ok(uint32_t min_plane_dist_bits, uint32_t valid_thresh_bits, uint32_t max_depth_bits)
+{
+    return min_plane_dist_bits <= kNormMaxDistBits && occlusion_params_ok(0, 0, 0, valid_thresh_bits, max_depth_bits);
+}
+
+struct NormalsPlan {
+    int status;                      // kInvalid: a null or misaligned pointer, no output, bad parameters, buffers that overlap
+    bool in_place;                   // out == depth: decide into the mask, then apply
+    int out_mode;                    // k_normals' OUT: 0 none, 1 fused, 2 mask
+    uint32_t strips, band_rows, bands;
+    unsigned grid_x;                 // k_normals: (grid_x, batch), four waves per workgroup
+    uint32_t words_x;                // mask words per row: ceil(cols / 32)
+    unsigned apply_x;                // k_occl_apply: (apply_x, batch); 0 unless in place
+    size_t scratch;                  // bytes of pp[0] the call uses: 4 * batch * rows * words_x in place, else 0
+    size_t normals_bytes;            // 16 * batch * rows * cols: what the kernel's 64-bit offsets span (0 without records)
+    size_t clear_bytes;              // hipMemsetAsync of counts: 8 bytes a frame (0: no counts wanted)
+    int launches;                    // 1 or 2, one more with counts
+};
+
+// rows, cols, batch >= 1 and within the context's limits; params_ok: normals_params_ok, and normals_intrinsics_ok of the uniform
+// call's record; normals, out, counts: 0 = not given; table: looked at in a table call only
+inline NormalsPlan plan_depth_normals(int rows, int cols, int batch, bool params_ok, uintptr_t depth, bool table_call, uintptr_t table,
+                                      uintptr_t normals, uintptr_t out, uintptr_t counts)
+{
+    NormalsPlan p = {};
+    p.status = kInvalid;
+    if (!depth || (!normals && !out) || !params_ok) return p;
+    if (depth % 4 != 0 || normals % 16 != 0 || out % 4 != 0 || counts % 4 != 0) return p;
+    if (table_call && !calib_table_aligned(table, 8)) return p;
+    const size_t px = (size_t)batch * (size_t)rows * (size_t)cols;
+    const uintptr_t at[4] = {depth, normals, out, counts};
+    const size_t bytes[4] = {4 * px, 16 * px, 4 * px, 2 * sizeof(uint32_t) * (size_t)batch};
+    for (int i = 0; i < 4; ++i) {
+        if (!at[i]) continue;
+        if (table_call && i > 0 && !calib_table_clear_of(table, 32, batch, at[i], bytes[i])) return p;
+        for (int j = i + 1; j < 4; ++j)
+            if (at[j] && !(i == 0 && j == 2 && out == depth) && ranges_overlap(at[i], bytes[i], at[j], bytes[j])) return p;
+    }
+    p.status = kOk;
+    p.in_place = out == depth;
+    p.out_mode = !out ? 0 : (p.in_place ? 2 : 1);
+    p.strips = ((uint32_t)cols + kNormCols - 1) / kNormCols;
+    p.band_rows = kNormRows;                         // shorter bands while the call makes fewer than ~2 waves per SIMD
+    while (p.band_rows > 8 && (size_t)p.strips * (((uint32_t)rows + p.band_rows - 1) / p.band_rows) * (size_t)batch < 2048) p.band_rows /= 2;
+    p.bands = ((uint32_t)rows + p.band_rows - 1) / p.band_rows;
+    p.grid_x = (unsigned)(((size_t)p.strips * p.bands + 3) / 4);
+    p.words_x = ((uint32_t)cols + 31) / 32;
+    p.apply_x = p.in_place ? (unsigned)(((size_t)rows * p.words_x + 255) / 256) : 0u;
+    p.scratch = p.in_place ? 4 * (size_t)batch * (size_t)rows * p.words_x : 0;
+    p.normals_bytes = normals ? 16 * px : 0;
+    p.clear_bytes = counts ? bytes[3] : 0;
+    p.launches = (p.in_place ? 2 : 1) + (counts ? 1 : 0);
     return p;
 }
 

@@ -950,6 +950,95 @@ int dcmt_stereo_refine_calib_dev(dcmt_ctx *ctx, const float *d_depth, const uint
                                  float *d_refined, int rows, int cols, int batch, const dcmt_stereo_params *params,
                                  const dcmt_stereo_calib *d_calib /* [batch], 8-byte aligned */, void *stream);
 
+/* ---- surface normals of a depth plane, and the flying-pixel filter ---------------------------------------- */
+
+/* Every dense plane this library produces has been through a Gaussian or a weighted mean, and at a depth edge those write values
+ * BETWEEN foreground and background: back-projected, a veil of points strung along the viewing rays.  And every consumer of a cloud
+ * asks for normals next.  One observation serves both, the one dcmt_superpixel_planes_dev rests on: a pinhole camera sees a plane
+ * affine in inverse depth.  With w = 1 / z and its gradient (gx, gy) per pixel, the local plane is n . P = 1 with
+ * n = (fx gx, fy gy, w - gx (x - cx) - gy (y - cy)): P = z ((x - cx) / fx, (y - cy) / fy, 1) gives n . P = z w = 1.  So -n / |n| is the
+ * unit normal towards the camera and 1 / |n| the distance of that plane from the camera centre.  A veil runs along viewing rays: a
+ * plane through (nearly) the camera centre, 1 / |n| ~ 0, while a real surface cannot pass closer to the camera than the camera's
+ * clearance (KITTI's ground: 1.65 m at every range, where an angle-of-incidence test would delete the far road).  Not in the
+ * reference; stated here to the last bit.  Per frame, on a depth plane [rows][cols] f32 with intrinsics fx, fy, cx, cy:
+ *
+ * INTRINSICS.  A dcmt_cloud_params record, converted once to f32: fxf = (float) fx, and so on.
+ * VALID.  The planes' return test (dcmt_superpixel_planes_dev), on the bit pattern: a finite float with valid_thresh <= z <=
+ *   max_depth.  The same bounds are enforced: valid_thresh >= 0.0625, max_depth <= 16384.  Everything else is a HOLE.
+ * INVERSE DEPTH.  w = fdiv_rn(1.0f, z) on a valid pixel.
+ * GRADIENT, per axis.  F = fsub_rn(w(next), w(here)) where the next pixel on the axis lies in the frame and is valid;
+ *   B = fsub_rn(w(here), w(previous)) likewise.  With both: g = F where |F| <= |B|, else B (a tie takes F).  With one: that one.  A
+ *   valid pixel that has neither on one of the two axes (or on both) has NO NORMAL: a gradient that was not observed is not taken
+ *   for zero, so a frame of one row or one column has none at all.  The smaller one-sided difference, not the central one, is part
+ *   of the statement: it keeps the last pixel of a surface at a clean step on its own surface, so sharp planes lose nothing.
+ *   Nothing crosses a frame of the batch or wraps a row.
+ * PLANE.  a = fmul_rn(fxf, gx), b = fmul_rn(fyf, gy), dx = fsub_rn((float) x, cxf), dy = fsub_rn((float) y, cyf),
+ *   c = fsub_rn(fsub_rn(w, fmul_rn(gx, dx)), fmul_rn(gy, dy)), len2 = fadd_rn(fadd_rn(fmul_rn(a, a), fmul_rn(b, b)), fmul_rn(c, c)):
+ *   every operation rounded once, nothing contracted.  len2 > 0 always: a = b = 0 forces c = w > 0.
+ * RECORD (dcmt_normal, 16 bytes a pixel).  len = fsqrt_rn(len2), dist = fdiv_rn(1.0f, len), nx = fmul_rn(-a, dist), ny =
+ *   fmul_rn(-b, dist), nz = fmul_rn(-c, dist).  A hole or a pixel with no normal gets four +0.0f.
+ * REMOVED.  dmin2 = fmul_rn(dmin, dmin), dmin = min_plane_dist, computed once on the host.  A valid pixel with a normal is removed
+ *   when fmul_rn(len2, dmin2) > 1.0f.  min_plane_dist = 0 removes nothing.  Every decision is taken on the INPUT.
+ * d_out (f32 plane), or NULL: +0.0f where removed; elsewhere the input's four bytes, opaque, so a NaN keeps its bits.
+ * d_counts, or NULL: uint32 [batch][2] = {removed, valid pixels with no normal}.
+ * Nothing depends on the batch size, the frame's position in the batch, alignment, the launch geometry, the run, or on whether
+ * the call is in place.
+ *
+ * What the statement gives at its edges: a clean step loses nothing (each side's last pixel takes the difference on its own side),
+ * and a column ONE pixel wide in front of a wall is removed: both its row differences cross the step, so its plane is a veil's.
+ * Objects two pixels wide and wider keep their pixels.
+ *
+ * Bounds, enforced so that no operation above can overflow: fx, fy finite with 2^-10 <= |.| <= 2^20; |cx|, |cy| <= 2^20;
+ * min_plane_dist finite in [0, 1024].  Then 2^-14 <= w <= 16, a difference of two w is 0 or at least 2^-37, |a|, |b| <= 2^24,
+ * |c| < 2^27, len2 < 2^55 and, with a normal, len2 >= 2^-94, 2^-28 < dist <= 2^47.  Underflow is not excluded altogether, and the
+ * statement is IEEE-754 binary32 WITH subnormals in every operation (what the kernel and the restatements compute).  Where |cx| and
+ * |cy| are each zero or at least 2^-60 -- any calibration -- every intermediate is zero or a normal number but for three products
+ * whose underflow changes no bit of the result: c * c where c has cancelled below 2^-63 (a or b is not zero then, and a * a + b * b
+ * >= 2^-94 absorbs it as it absorbs zero), and dmin * dmin and len2 * dmin2, which underflow only far below the 1.0f the second is
+ * compared with.  Checked: tests/test_normals.py asserts over the extreme inputs, through the literal restatement of
+ * tests/normals_restatement.py, that every intermediate is finite and that none but those three is subnormal.
+ *
+ * The default min_plane_dist = 0.4 is a quarter of KITTI's camera height.  It is measured, not derived: on the cascade's output the
+ * ground towards the left and right edges of a KITTI frame bends (within 0.25 m of the truth) into local planes as close as 0.50 m,
+ * and 0.4 is the largest of the values tried that removes none of them; DESIGN.md section 38 has the table, with what 0.8 and 1.6
+ * remove and keep.
+ *
+ * dcmt_depth_normals_calib_dev is the same call over a device table of per-frame dcmt_cloud_params records (what
+ * dcmt_depth_to_cloud_calib_dev takes): frame f is bit for bit the uniform call on that frame alone with record f.  A record that
+ * is bad on the device (outside the bounds above, tested on its bits) gives its frame no normals and removes nothing: its records
+ * are zeros, d_out is the copy, its counts {0, its valid pixels}; no other frame is touched.
+ *
+ * DEVICE pointers, stream-ordered; never synchronises, never allocates.  Out of place: one launch.  In place (d_out == d_depth):
+ * two, as the occlusion filter does it: a mask of one bit per pixel, then it is applied.  A clear of d_counts goes in front where
+ * they are given.  Both routes give the same bytes.  Scratch: the first of the two planes dcmt_create allocates (the one the
+ * occlusion filter borrows), in place only.  Of the context's carried state it touches none, dcmt_last_path included: it can be
+ * queued in front of or behind any other *_dev call.
+ * DCMT_E_INVALID, nothing written: a null ctx, plane, intrinsics (record or table) or params; neither d_normals nor d_out; sizes
+ * or a batch beyond the context's limits; anything outside the bounds above; d_depth, d_out or d_counts not 4-byte aligned,
+ * d_normals not 16-byte aligned, the table not 8-byte aligned; any overlap among the buffers other than d_out == d_depth exactly. */
+typedef struct {
+    float min_plane_dist;   /* 0.4   a pixel whose local plane passes closer to the camera centre is removed, metres; 0..1024 */
+    float valid_thresh;     /* 0.1   the smallest depth that is valid, metres; >= 0.0625                                      */
+    float max_depth;        /* 100   the largest; <= 16384                                                                    */
+} dcmt_normals_params;      /* 12 bytes */
+typedef struct {
+    float nx, ny, nz;       /* the unit normal, towards the camera (nz < 0 on a surface that faces it)                        */
+    float dist;             /* the distance of the pixel's local plane from the camera centre, metres                         */
+} dcmt_normal;              /* 16 bytes */
+void dcmt_default_normals_params(dcmt_normals_params *p);
+int dcmt_depth_normals_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch, const dcmt_cloud_params *cloud,
+                           const dcmt_normals_params *params, dcmt_normal *d_normals /* or NULL */, float *d_out /* may be d_depth, or NULL */,
+                           uint32_t *d_counts /* [batch][2] or NULL */, void *stream);
+int dcmt_depth_normals_calib_dev(dcmt_ctx *ctx, const float *d_depth, int rows, int cols, int batch, const dcmt_cloud_params *d_cloud /* [batch] */,
+                                 const dcmt_normals_params *params, dcmt_normal *d_normals /* or NULL */, float *d_out /* may be d_depth, or NULL */,
+                                 uint32_t *d_counts /* [batch][2] or NULL */, void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES: depth's and out's >= 4 * cols, the normals' >= 16 * cols; the stride
+ * of a plane that is not given is not looked at); counts: two values or NULL.  The same bits as the device call.  What
+ * dcmt_shim::depth_normals and dcmt_shim::filter_flying_pixels call. */
+int dcmt_depth_normals(dcmt_ctx *ctx, const float *depth, size_t depth_row_stride, int rows, int cols, const dcmt_cloud_params *cloud,
+                       const dcmt_normals_params *params, dcmt_normal *normals, size_t normals_row_stride, float *out, size_t out_row_stride,
+                       uint32_t *counts);
+
 /* ---- nearest wins: the two scatter calls as a z-buffer ------------------------------------------------ */
 
 /* dcmt_project_points_dev and dcmt_reproject_depth_dev resolve a pixel that several points (source pixels) land on the way the

@@ -610,6 +610,53 @@ inline unsigned joint_bilateral_fill(const cv::Mat& depth_img, const cv::Mat& gu
     return counts[0];
 }
 
+// The flying-pixel filter of a dense plane, as dcmt.h states it (dcmt_depth_normals): filtered_img is overwritten with a fresh CV_32FC1
+// image in which every pixel of depth_img (CV_32FC1, metres) whose local plane passes closer to the camera centre than
+// params->min_plane_dist is 0 -- the veil a blur strings between an object and what lies behind it -- and every other pixel keeps its
+// bytes.  cloud == nullptr: dcmt_default_cloud_params, the intrinsics reproject_pc_colors uses; params == nullptr:
+// dcmt_default_normals_params.  normals, where given, receives the rows * cols records of depth_normals below (of the INPUT plane).
+// Returns the number of pixels removed.  It belongs between the blur and reproject_pc_colors.
+inline unsigned filter_flying_pixels(const cv::Mat& depth_img, cv::Mat& filtered_img, const dcmt_cloud_params* cloud = nullptr,
+                                     const dcmt_normals_params* params = nullptr, std::vector<dcmt_normal>* normals = nullptr)
+{
+    check_input(depth_img);
+    const int rows = depth_img.rows, cols = depth_img.cols;
+    dcmt_cloud_params cdef;
+    dcmt_default_cloud_params(&cdef);
+    dcmt_normals_params def;
+    dcmt_default_normals_params(&def);
+    if (normals) normals->assign((size_t)rows * cols, dcmt_normal());
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    uint32_t counts[2] = {0, 0};
+    raise(dcmt_depth_normals(thread_ctx().get(rows, cols), depth_img.ptr<float>(), depth_img.step[0], rows, cols, cloud ? cloud : &cdef, params ? params : &def,
+                             normals ? normals->data() : nullptr, sizeof(dcmt_normal) * (size_t)cols, out.ptr<float>(), out.step[0], counts),
+          "filter_flying_pixels");
+    filtered_img = out;
+    return counts[0];
+}
+
+// The surface normals of a dense plane (dcmt_depth_normals): normals is overwritten with rows * cols records, row-major -- the unit
+// normal towards the camera and the distance of the pixel's local plane from the camera centre; four zeros on a hole and where no
+// normal is defined.  The records of the pixels with depth > 0, in this order, are the normals of reproject_pc_colors' points.
+// cloud, params: as above.  Returns the number of valid pixels without a normal.
+inline unsigned depth_normals(const cv::Mat& depth_img, std::vector<dcmt_normal>& normals, const dcmt_cloud_params* cloud = nullptr,
+                              const dcmt_normals_params* params = nullptr)
+{
+    check_input(depth_img);
+    const int rows = depth_img.rows, cols = depth_img.cols;
+    dcmt_cloud_params cdef;
+    dcmt_default_cloud_params(&cdef);
+    dcmt_normals_params def;
+    dcmt_default_normals_params(&def);
+    normals.assign((size_t)rows * cols, dcmt_normal());
+    uint32_t counts[2] = {0, 0};
+    raise(dcmt_depth_normals(thread_ctx().get(rows, cols), depth_img.ptr<float>(), depth_img.step[0], rows, cols, cloud ? cloud : &cdef, params ? params : &def,
+                             normals.data(), sizeof(dcmt_normal) * (size_t)cols, nullptr, 0, counts),
+          "depth_normals");
+    return counts[1];
+}
+
 // unrectify_sol (DC_stereo_lidar/main_sl.cpp:967-1028, called at :1228) without its cv::circle / imshow / std::cout lines, so it
 // takes no image: depth (CV_32FC1) forward-warped into depth_unrect, which the caller has sized (CV_32FC1, as at :1227) and which is
 // overwritten completely -- 0 where nothing lands.  Minv: the 4x4 matrix that is applied, ROW-major: the inverse of the R_rect the
