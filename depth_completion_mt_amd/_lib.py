@@ -13,7 +13,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(_CSRC, "libdcmt_hip.so")
 
 OK, E_INVALID, E_UNSUPPORTED, E_NOMEM, E_HIP, E_NOT_CONVERGED, E_NO_DEVICE = 0, -1, -2, -3, -4, -5, -6
-BLUR_NONE, BLUR_GAUSSIAN, BLUR_BILATERAL, BLUR_BILATERAL_CLONE = 0, 1, 2, 3
+BLUR_NONE, BLUR_GAUSSIAN, BLUR_BILATERAL, BLUR_BILATERAL_CLONE, BLUR_GAUSSIAN_VALID = 0, 1, 2, 3, 5
 STAGE_NORMALIZE = 1
 STAGE_INVERT, STAGE_DILATE_K, STAGE_CLOSE5, STAGE_FILL7, STAGE_EXTEND = 2, 3, 4, 5, 6
 FLAG_FORCE_STAGED = 1
@@ -54,6 +54,7 @@ EXPORTS = (
     "dcmt_default_support_params", "dcmt_support_distance_dev", "dcmt_support_distance_u16_dev", "dcmt_support_distance",
     "dcmt_default_joint_params", "dcmt_make_joint_tables", "dcmt_joint_bilateral_dev", "dcmt_joint_bilateral",
     "dcmt_default_normals_params", "dcmt_depth_normals_dev", "dcmt_depth_normals_calib_dev", "dcmt_depth_normals",
+    "dcmt_gaussian5_valid_dev", "dcmt_gaussian5_valid",
 )
 
 
@@ -284,6 +285,8 @@ def lib() -> ctypes.CDLL:
         L.dcmt_depth_to_cloud.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i64, ctypes.POINTER(i64)]
         L.dcmt_gaussian5_dev.argtypes = [vp, vp, vp, i, i, i, vp]
         L.dcmt_gaussian5.argtypes = [vp, vp, sz, vp, sz, i, i]
+        L.dcmt_gaussian5_valid_dev.argtypes = [vp, vp, vp, i, i, i, f32, vp]
+        L.dcmt_gaussian5_valid.argtypes = [vp, vp, sz, vp, sz, i, i, f32]
         L.dcmt_bilateral5_dev.argtypes = [vp, vp, vp, i, i, i, f32, f32, vp]
         L.dcmt_bilateral5.argtypes = [vp, vp, sz, vp, sz, i, i, f32, f32]
         L.dcmt_default_reproject_params.argtypes = [vp]

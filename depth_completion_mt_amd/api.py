@@ -125,7 +125,10 @@ def make_params(k0="as_compiled", blur_type: str = "gaussian", stop_after: int =
             p.k0[i] = int(arr[i])
     # the reference compares strings: "bilateral" / "gaussian" / anything else = no blur; "bilateral_clone" is this project's opt-in:
     # what the reference's in-place bilateral call computes when it is given a copy (DCMT_BLUR_BILATERAL_CLONE)
-    p.blur = {"gaussian": L.BLUR_GAUSSIAN, "bilateral": L.BLUR_BILATERAL, "bilateral_clone": L.BLUR_BILATERAL_CLONE}.get(blur_type, L.BLUR_NONE)
+    # "gaussian_valid" is another: the Gaussian that takes its weights from the valid taps only (DCMT_BLUR_GAUSSIAN_VALID), the finish
+    # for extrapolate=False, where the plain Gaussian averages the region's border pixels with the holes beside them
+    p.blur = {"gaussian": L.BLUR_GAUSSIAN, "bilateral": L.BLUR_BILATERAL, "bilateral_clone": L.BLUR_BILATERAL_CLONE,
+              "gaussian_valid": L.BLUR_GAUSSIAN_VALID}.get(blur_type, L.BLUR_NONE)
     p.stop_after = int(stop_after)
     p.max_fill_iters = int(max_fill_iters)
     p.spec_fill_iters = int(spec_fill_iters)
@@ -1798,10 +1801,12 @@ class Context:
         _check(st, "dcmt_depth_to_cloud")
         return out[:n.value].copy()
 
-    def gaussian5_dev(self, d_src, d_dst=None, stream: int | None = None):
+    def gaussian5_dev(self, d_src, d_dst=None, stream: int | None = None, valid_thresh: float | None = None):
         """cv::GaussianBlur(src, dst, Size(5, 5), 0) on the device (dcmt_gaussian5_dev; SL/main_sl.cpp:1253), without the cascade's
         masked select.  d_src: contiguous f32 CUDA tensor [batch][rows][cols] (or [rows][cols]); d_dst may be d_src (in place).
         Returns d_dst without synchronising.
+        valid_thresh=t: the Gaussian that ignores holes (dcmt_gaussian5_valid_dev, include/dcmt.h): a pixel >= t becomes the
+        average of its taps >= t, weighted as the Gaussian weights them; any other pixel comes back as it is.
         Outputs that are not given are allocated (and, where they have a fill, filled) on the stream the call enqueues on."""
         import torch
         assert _is_dev(d_src, torch.float32)
@@ -1810,14 +1815,24 @@ class Context:
             with _on_stream(stream, d_src):
                 d_dst = torch.full_like(d_src, float("nan"))
         assert _is_dev(d_dst, torch.float32) and d_dst.numel() == d_src.numel()
+        if valid_thresh is not None:
+            st = L.lib().dcmt_gaussian5_valid_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, float(valid_thresh), _stream(stream, d_src))
+            _check(st, "dcmt_gaussian5_valid_dev")
+            return d_dst
         st = L.lib().dcmt_gaussian5_dev(self._h, d_src.data_ptr(), d_dst.data_ptr(), r, c, b, _stream(stream, d_src))
         _check(st, "dcmt_gaussian5_dev")
         return d_dst
 
-    def gaussian5(self, frame: np.ndarray) -> np.ndarray:
-        """One frame of host memory (dcmt_gaussian5, synchronous; any row stride): a new f32 array."""
+    def gaussian5(self, frame: np.ndarray, valid_thresh: float | None = None) -> np.ndarray:
+        """One frame of host memory (dcmt_gaussian5, synchronous; any row stride): a new f32 array.  valid_thresh: as gaussian5_dev
+        (dcmt_gaussian5_valid)."""
         a = _frame_f32(frame)
         out = np.empty(a.shape, dtype=np.float32)
+        if valid_thresh is not None:
+            st = L.lib().dcmt_gaussian5_valid(self._h, a.ctypes.data, a.strides[0], out.ctypes.data, out.strides[0], a.shape[0], a.shape[1],
+                                              float(valid_thresh))
+            _check(st, "dcmt_gaussian5_valid")
+            return out
         st = L.lib().dcmt_gaussian5(self._h, a.ctypes.data, a.strides[0], out.ctypes.data, out.strides[0], a.shape[0], a.shape[1])
         _check(st, "dcmt_gaussian5")
         return out
@@ -1953,10 +1968,11 @@ def interpolate_with_superpixels(labels: np.ndarray, n_labels: int, sparse_r_img
                                  blur_type: str = "gaussian", use_superpixel: int = 1, **kw) -> np.ndarray:
     """Drop-in for LC/img_completion_lc.cpp:34.  `labels` is int32 [rows][cols] (the reference's
     Slic::clusters is [col][row]: pass clusters.T), n_labels = slic.centers.size().  blur_type is
-    accepted and ignored, as in the reference (:37, :183 always blurs)."""
+    accepted and ignored, as in the reference (:37, :183 always blurs) -- except "gaussian_valid", this project's own finish."""
     a = np.asarray(sparse_r_img, dtype=np.float32)
     b = 1 if a.ndim == 2 else a.shape[0]
-    return _ctx_for(a.shape[-2], a.shape[-1], b).complete(a, make_params(blur_type="gaussian", **kw), labels=labels,
+    blur = "gaussian_valid" if blur_type == "gaussian_valid" else "gaussian"
+    return _ctx_for(a.shape[-2], a.shape[-1], b).complete(a, make_params(blur_type=blur, **kw), labels=labels,
                                                           n_labels=n_labels, use_superpixel=use_superpixel)
 
 

@@ -335,7 +335,8 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
 {
     const int rows = fr.rows, cols = fr.cols, batch = fr.batch, stop = p->stop_after;
     const uint32_t kb = k0_bits(p->k0);
-    const int blur = force_gaussian ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
+    // (the labeled entry points force the reference's Gaussian, except for this project's own opt-in)
+    const int blur = force_gaussian && p->blur != DCMT_BLUR_GAUSSIAN_VALID ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
     ctx->tev_valid = 0;
     if ((p->flags & DCMT_FLAG_NORMALIZE) && fr.src16) return DCMT_E_UNSUPPORTED;
     plan::Call c;
@@ -348,14 +349,17 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     c.k0kind = k0_preset(kb);
     c.gaussian = blur == DCMT_BLUR_GAUSSIAN;
     c.bilateral = blur == DCMT_BLUR_BILATERAL_CLONE;
+    c.valid = blur == DCMT_BLUR_GAUSSIAN_VALID;
     c.max_fill_iters = p->max_fill_iters; c.spec_fill_iters = p->spec_fill_iters; c.stop_after = stop; c.flags = p->flags;
     c.sync_loop = sync_loop;
     c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && q16_allowed_now(ctx);
     const plan::Plan pl = plan::plan_call(ctx->knobs, c);
-    if (!pl.bilateral) return run_plan(ctx, pl, fr, p, blur, st, sync_loop);
+    if (!pl.bilateral && !pl.gauss_valid) return run_plan(ctx, pl, fr, p, blur, st, sync_loop);
 
     // The bilateral finish: the plan's chain up to the median into the context's median plane (allocated by the first such call,
     // before anything is enqueued), then k_bilateral5 from there into dst.  A loop that hit max_fill_iters is filtered like any other.
+    // The Gaussian that ignores holes with the extrapolation: the same, with k_gauss5<VALID> -- where the loop hit max_fill_iters
+    // it is what keeps the holes that are left out of their neighbours.
     DCMT_TRY(ctx->median.reserve(ctx, ctx->frame_elems * (size_t)ctx->max_batch));
     Frames fm = fr;
     fm.dst = ctx->median;
@@ -363,6 +367,9 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     q.stop_after = DCMT_STAGE_MEDIAN5;
     const int rc = run_plan(ctx, pl, fm, &q, DCMT_BLUR_NONE, st, sync_loop);
     if (rc != DCMT_OK && rc != DCMT_E_NOT_CONVERGED) return rc;
+    if (pl.gauss_valid)
+        DCMT_TRY(gauss5_valid_enqueue(ctx, ctx->median, fr.dst, rows, cols, batch, p->valid_thresh, pl.gauss_valid_invert, p->max_depth, st));
+    else
     DCMT_TRY(bilateral5_enqueue(ctx, ctx->median, fr.dst, rows, cols, batch, kBilateralSigmaColor, kBilateralSigmaSpace, pl.bilateral_invert,
                                 p->max_depth, p->valid_thresh, st));
     return rc;
@@ -467,10 +474,10 @@ int run_plan(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dcmt_p
     }
     if (pl.no_extrapolate) {
         // H9..H11 on X5 itself: with no application launched k_post_v1 reads its first plane and never looks at the counters
-        with_tile_h(pl.few, [&](auto th) {
-            hipLaunchKernelGGL((k_post_v1<decltype(th)::value, TW>), grid, block, 0, st, ctx->x5, ctx->x5, d_dst, ctx->counters, 0,
+        with_tile_h(pl.few, [&](auto th) { with_bool(pl.valid_kind, [&](auto valid) {
+            hipLaunchKernelGGL((k_post_v1<decltype(th)::value, TW, decltype(valid)::value>), grid, block, 0, st, ctx->x5, ctx->x5, d_dst, ctx->counters, 0,
                                rows, cols, p->max_depth, p->valid_thresh, blur, stop);
-        });
+        }); });
         DCMT_HIP(ctx, hipGetLastError());
         return DCMT_OK;
     }
@@ -560,11 +567,14 @@ int launch_local(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, const dc
     const int input = labeled ? LOCAL_START4 : fr.src16 ? LOCAL_U16 : cf ? LOCAL_NORM : LOCAL_F32;
     const float scale = fr.src16 ? fr.in_scale : 1.0f;
     float* out = out_plane(ctx, pl.out, fr.dst);
-    // bit 0: the Gaussian runs, bit 1: the final invert runs (stop_after = MEDIAN5 is PostPipe<10, false>: dcmt_kernels_local.h)
-    const int variant = (blur == DCMT_BLUR_GAUSSIAN && p->stop_after >= DCMT_STAGE_BLUR ? 1 : 0) | (p->stop_after == DCMT_STAGE_FINAL ? 2 : 0);
-    with_k0(pl.k0kind, [&](auto kind) { with_value<0, 1, 2, 3>(input, [&](auto in_) { with_value<0, 1, 2, 3>(variant, [&](auto v) {
+    // bit 0: the Gaussian runs, bit 2: the Gaussian that ignores holes runs, bit 1: the final invert runs (stop_after = MEDIAN5 is
+    // PostPipe<10, POST_BLUR_NONE>: dcmt_kernels_local.h)
+    const int variant = (blur == DCMT_BLUR_GAUSSIAN && p->stop_after >= DCMT_STAGE_BLUR ? 1 : 0) | (pl.valid_kind ? 4 : 0) |
+                        (p->stop_after == DCMT_STAGE_FINAL ? 2 : 0);
+    with_k0(pl.k0kind, [&](auto kind) { with_value<0, 1, 2, 3>(input, [&](auto in_) { with_value<0, 1, 2, 3, 4, 6>(variant, [&](auto v) {
         constexpr int V = decltype(v)::value;
-        hipLaunchKernelGGL((k_local<decltype(kind)::value, decltype(in_)::value, (V & 2) ? 11 : 10, (V & 1) != 0>), dim3(pl.local_grid), dim3(256), 0, st,
+        constexpr int BLUR = (V & 4) ? POST_BLUR_VALID : (V & 1) ? POST_BLUR_GAUSSIAN : POST_BLUR_NONE;
+        hipLaunchKernelGGL((k_local<decltype(kind)::value, decltype(in_)::value, (V & 2) ? 11 : 10, BLUR>), dim3(pl.local_grid), dim3(256), 0, st,
                            in, out, rows, cols, pl.local_strips, pl.local_bands, batch, pl.xcd_map, p->max_depth, p->valid_thresh, scale, cf);
     }); }); });
     DCMT_HIP(ctx, hipGetLastError());
@@ -590,7 +600,8 @@ int check_params(const dcmt_ctx* ctx, const void* a, const void* b, int rows, in
     if ((mb & 0x7f800000u) == 0x7f800000u || (tb & 0x7f800000u) == 0x7f800000u) return DCMT_E_INVALID;
     if ((tb >> 31) != 0 || (tb << 1) == 0) return DCMT_E_INVALID;
     if (p->blur == DCMT_BLUR_BILATERAL) return DCMT_E_UNSUPPORTED;
-    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN && p->blur != DCMT_BLUR_BILATERAL_CLONE) return DCMT_E_INVALID;
+    if (p->blur != DCMT_BLUR_NONE && p->blur != DCMT_BLUR_GAUSSIAN && p->blur != DCMT_BLUR_BILATERAL_CLONE && p->blur != DCMT_BLUR_GAUSSIAN_VALID)
+        return DCMT_E_INVALID;
     if (p->max_fill_iters < 1 || p->max_fill_iters > kMaxIters) return DCMT_E_INVALID;
     if (p->spec_fill_iters < 0 || p->spec_fill_iters > kMaxIters) return DCMT_E_INVALID;
     const bool norm = (p->flags & DCMT_FLAG_NORMALIZE) != 0;

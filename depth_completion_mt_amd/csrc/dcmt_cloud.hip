@@ -165,8 +165,30 @@ int dcmt_gaussian5_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows
     if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
     float* out = in_place ? ctx->pp[0] : d_dst;
     const plan::GaussPlan pl = plan::plan_gauss5(rows, cols, batch);
-    hipLaunchKernelGGL(k_gauss5, dim3(pl.grid_x, batch), dim3(256), 0, st, d_src, out, rows, cols, pl.strips, pl.bands, pl.band_rows);
+    hipLaunchKernelGGL((k_gauss5<false, false>), dim3(pl.grid_x, batch), dim3(256), 0, st, d_src, out, rows, cols, pl.strips, pl.bands, pl.band_rows,
+                       0.0f, 0.0f);
     DCMT_HIP(ctx, hipGetLastError());
+    if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
+    return DCMT_OK;
+}
+
+// as dcmt_gaussian5_dev, with k_gauss5<VALID>
+int dcmt_gaussian5_valid_dev(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float valid_thresh, void* stream)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !d_src || !d_dst) return DCMT_E_INVALID;
+    if (!dims_ok(ctx, rows, cols, batch)) return DCMT_E_INVALID;
+    if ((uintptr_t)d_src % 4 != 0 || (uintptr_t)d_dst % 4 != 0) return DCMT_E_INVALID;
+    // as dcmt_params.valid_thresh (check_params): finite, sign clear, not zero -- on its bits (-ffinite-math-only)
+    uint32_t tb;
+    std::memcpy(&tb, &valid_thresh, sizeof tb);
+    if ((tb & 0x7f800000u) == 0x7f800000u || (tb >> 31) != 0 || (tb << 1) == 0) return DCMT_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t bytes = sizeof(float) * (size_t)batch * rows * cols;
+    const bool in_place = d_dst == d_src;
+    if (!in_place && plan::ranges_overlap((uintptr_t)d_src, bytes, (uintptr_t)d_dst, bytes)) return DCMT_E_INVALID;
+    float* out = in_place ? ctx->pp[0] : d_dst;
+    DCMT_TRY(gauss5_valid_enqueue(ctx, d_src, out, rows, cols, batch, valid_thresh, false, 0.0f, st));
     if (in_place) DCMT_HIP(ctx, hipMemcpyAsync(d_dst, out, bytes, hipMemcpyDeviceToDevice, st));
     return DCMT_OK;
 }
@@ -391,6 +413,20 @@ int bilateral5_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows
         hipLaunchKernelGGL(k_bilateral5<true>, grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, k, max_depth, thr);
     else
         hipLaunchKernelGGL(k_bilateral5<false>, grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, k, max_depth, thr);
+    DCMT_HIP(ctx, hipGetLastError());
+    return DCMT_OK;
+}
+
+// (dcmt_ctx.h)
+int gauss5_valid_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float thr, bool invert, float max_depth,
+                         hipStream_t st)
+{
+    const plan::GaussPlan pl = plan::plan_gauss5(rows, cols, batch);
+    const dim3 grid(pl.grid_x, batch);
+    if (invert)
+        hipLaunchKernelGGL((k_gauss5<true, true>), grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, thr, max_depth);
+    else
+        hipLaunchKernelGGL((k_gauss5<true, false>), grid, dim3(256), 0, st, d_src, d_dst, rows, cols, pl.strips, pl.bands, pl.band_rows, thr, max_depth);
     DCMT_HIP(ctx, hipGetLastError());
     return DCMT_OK;
 }

@@ -242,4 +242,10 @@ DCMT_LOCAL int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params*
 DCMT_LOCAL int bilateral5_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float sigma_color,
                                   float sigma_space, bool invert, float max_depth, float thr, hipStream_t st);
 
+// k_gauss5<VALID> (dcmt_kernels_cloud.h) enqueued on `st`, for dcmt_gaussian5_valid_dev and the extrapolating cascade's
+// DCMT_BLUR_GAUSSIAN_VALID finish: d_src and d_dst must not overlap; invert: the cascade's final invert with (max_depth, thr) in the
+// store.  Defined in dcmt_cloud.hip, where the kernel is compiled.
+DCMT_LOCAL int gauss5_valid_enqueue(dcmt_ctx* ctx, const float* d_src, float* d_dst, int rows, int cols, int batch, float thr, bool invert,
+                                    float max_depth, hipStream_t st);
+
 }  // namespace dcmt

@@ -301,6 +301,17 @@ int dcmt_gaussian5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size
     return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
 }
 
+int dcmt_gaussian5_valid(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size_t drs, int rows, int cols, float valid_thresh)
+{
+    DCMT_ON_DEVICE(ctx);
+    if (!ctx || !src || !dst || !dims_ok(ctx, rows, cols, 1)) return DCMT_E_INVALID;
+    const size_t frow = sizeof(float) * (size_t)cols;
+    Plane in(src, srs, frow, rows), out(dst, drs, frow, rows);
+    int rc = stage(ctx, {&in}, {&out});
+    if (rc == DCMT_OK) rc = dcmt_gaussian5_valid_dev(ctx, (const float*)in.dev, (float*)out.dev, rows, cols, 1, valid_thresh, ctx->own_stream);
+    return rc == DCMT_OK ? fetch(ctx, {&out}) : rc;
+}
+
 int dcmt_bilateral5(dcmt_ctx* ctx, const float* src, size_t srs, float* dst, size_t drs, int rows, int cols, float sigma_color, float sigma_space)
 {
     DCMT_ON_DEVICE(ctx);

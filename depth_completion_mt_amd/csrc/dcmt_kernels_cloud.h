@@ -253,8 +253,16 @@ constexpr int kGaussBatch = 6;      // (kGaussCols, kGaussRows: dcmt_cloud.h)
 
 // grid (ceil(strips * bands / 4), frames), 256 threads: one wave per (strip, band); strips = ceil(cols / kGaussCols),
 // bands = ceil(rows / band_rows)
+//
+// VALID: the Gaussian that ignores holes (dcmt_gaussian5_valid_dev, and the cascade's "gaussian_valid" finish), dcmt.h's GV: with
+// v(x) = x >= thr, num = G5(v ? x : 0) and den = G5(v ? 1 : 0) run side by side through the same shuffles and rings -- den is exact,
+// a multiple of 1/256 -- and a valid pixel stores num / den (one IEEE division), an invalid one its own bits.  A wave whose output
+// lanes all have den == 1 (every tap valid: the interior of a filled region) skips the division: num / 1.0f is num.
+// INVERT: the cascade's final invert (y >= thr ? max_depth - y : y) in the store.  thr and max_depth are read by those instances only.
+template <bool VALID = false, bool INVERT = false>
 __global__ __launch_bounds__(256)
-void k_gauss5(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols, int strips, int bands, int band_rows)
+void k_gauss5(const float* __restrict__ src, float* __restrict__ dst, int rows, int cols, int strips, int bands, int band_rows, float thr,
+              float max_depth)
 {
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / 64), l = threadIdx.x & 63;
     const int id = blockIdx.x * 4 + w;
@@ -268,6 +276,8 @@ void k_gauss5(const float* __restrict__ src, float* __restrict__ dst, int rows, 
     const bool out_col = l >= 2 && l < 62 && gx < cols;
     const int y0 = band * band_rows, R = min(band_rows, rows - y0);
     float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, h3 = 0.0f, h4 = 0.0f;
+    [[maybe_unused]] float k0 = 0.0f, k1 = 0.0f, k2 = 0.0f, k3 = 0.0f, k4 = 0.0f;     // VALID: the row pass of the mask
+    [[maybe_unused]] float c0 = 0.0f, c1 = 0.0f, c2 = 0.0f;                           // VALID: the source rows i - 2, i - 1, i
     for (int i0 = 0; i0 < R + 4; i0 += kGaussBatch) {          // input row i of the band is frame row y0 + i - 2
         float v[kGaussBatch];
 #pragma unroll
@@ -279,12 +289,32 @@ void k_gauss5(const float* __restrict__ src, float* __restrict__ dst, int rows, 
         for (int j = 0; j < kGaussBatch; ++j) {
             const int i = i0 + j;
             if (i < R + 4) {                                   // wave-uniform
-                const float l1 = __shfl_up(v[j], 1, 64), r1 = __shfl_down(v[j], 1, 64);
-                const float l2 = __shfl_up(v[j], 2, 64), r2 = __shfl_down(v[j], 2, 64);
+                float x = v[j];
+                if constexpr (VALID) {
+                    const bool ok = x >= thr;                  // (NaN: not valid)
+                    const float m = ok ? 1.0f : 0.0f;
+                    c0 = c1; c1 = c2; c2 = x;
+                    x = ok ? x : 0.0f;                         // a select, not a product: +inf stays +inf
+                    const float ml1 = __shfl_up(m, 1, 64), mr1 = __shfl_down(m, 1, 64);
+                    const float ml2 = __shfl_up(m, 2, 64), mr2 = __shfl_down(m, 2, 64);
+                    k0 = k1; k1 = k2; k2 = k3; k3 = k4;
+                    k4 = gauss_taps(m, __fadd_rn(ml1, mr1), __fadd_rn(ml2, mr2));
+                }
+                const float l1 = __shfl_up(x, 1, 64), r1 = __shfl_down(x, 1, 64);
+                const float l2 = __shfl_up(x, 2, 64), r2 = __shfl_down(x, 2, 64);
                 h0 = h1; h1 = h2; h2 = h3; h3 = h4;
-                h4 = gauss_taps(v[j], __fadd_rn(l1, r1), __fadd_rn(l2, r2));
-                if (i >= 4 && out_col)
-                    dst[fo + (size_t)(y0 + i - 4) * cols + gx] = gauss_taps(h2, __fadd_rn(h1, h3), __fadd_rn(h0, h4));
+                h4 = gauss_taps(x, __fadd_rn(l1, r1), __fadd_rn(l2, r2));
+                if constexpr (!VALID) {
+                    if (i >= 4 && out_col)
+                        dst[fo + (size_t)(y0 + i - 4) * cols + gx] = gauss_taps(h2, __fadd_rn(h1, h3), __fadd_rn(h0, h4));
+                } else if (i >= 4) {                           // wave-uniform
+                    float num = gauss_taps(h2, __fadd_rn(h1, h3), __fadd_rn(h0, h4));
+                    const float den = gauss_taps(k2, __fadd_rn(k1, k3), __fadd_rn(k0, k4));
+                    if (__builtin_amdgcn_ballot_w64(out_col && den != 1.0f) != 0ull) num = __fdiv_rn(num, den);
+                    float y = c0 >= thr ? num : c0;            // c0: the source row of this output row (a valid one has den >= 0.375^2)
+                    if constexpr (INVERT) y = y >= thr ? __fsub_rn(max_depth, y) : y;
+                    if (out_col) dst[fo + (size_t)(y0 + i - 4) * cols + gx] = y;
+                }
             }
         }
     }

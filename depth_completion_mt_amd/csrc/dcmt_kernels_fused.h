@@ -707,11 +707,18 @@ struct PostS {
 // FILLED: the caller guarantees that every frame whose X7 still holds a hole is recomputed afterwards (k_fp_s followed by the
 // redo chain).  A frame without holes has every median >= thr, so the masked select of LO :184 always takes the blurred value
 // and its compare + select (two of the slow instructions per pixel) are left out; what a frame WITH holes gets is overwritten.
-template <int MODE, bool BLUR, bool FILLED = false, bool NT = false>
+// BLUR is a kind: POST_BLUR_NONE, POST_BLUR_GAUSSIAN (what `true` converts to), or POST_BLUR_VALID, the Gaussian that ignores holes
+// (dcmt.h's GV, k_local only): the horizontal pass runs on m >= thr ? m : 0 and, in a second ring G2, on the mask m >= thr ? 1 : 0 --
+// the same lane shifts, the same reflect-101 source lane and rows -- and a valid pixel takes num / den.
+enum { POST_BLUR_NONE = 0, POST_BLUR_GAUSSIAN = 1, POST_BLUR_VALID = 2 };
+template <int MODE, int BLUR, bool FILLED = false, bool NT = false>
 struct PostPipe {
-    static constexpr bool do_blur = BLUR && MODE >= 10;
+    static constexpr bool do_blur = BLUR != POST_BLUR_NONE && MODE >= 10;
+    static constexpr bool do_valid = BLUR == POST_BLUR_VALID && MODE >= 10;
+    static_assert(!(do_valid && FILLED), "the valid kind is for planes with holes");
     MedianColumn mc;         // the vertical half of the median (dcmt_median.h)
     float G1[8], MR[8];      // horizontal Gaussian / median rows, slot (image row) & 7
+    float G2[do_valid ? 8 : 1];   // POST_BLUR_VALID: the horizontal pass of the mask
     float last_out;          // the value this lane stored last (k_fp_s repeats output row 0 above a shifted origin)
     // per-lane constants
     FrameBuf of;             // output frame
@@ -734,6 +741,10 @@ struct PostPipe {
         last_out = 0.f;
 #pragma unroll
         for (int q = 0; q < 8; ++q) { G1[q] = 0.f; MR[q] = 0.f; }
+        if constexpr (do_valid) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) G2[q] = 0.f;
+        }
     }
 
     template <int PP>
@@ -757,6 +768,14 @@ struct PostPipe {
         if constexpr (do_blur) {
             float mf = m;
             if (edge_strip) { const float mr = __shfl(m, rl, 64); mf = (gx < 0 || gx >= cols) ? mr : m; }
+            if constexpr (do_valid) {
+                const bool ok = mf >= thr;                              // (NaN: not valid)
+                const float kf = ok ? 1.0f : 0.0f;
+                mf = ok ? mf : 0.0f;                                    // a select, not a product: +inf stays +inf
+                const float kl1 = from_left(kf), kr1 = from_right(kf);
+                const float kl2 = from_left(kl1), kr2 = from_right(kr1);
+                G2[(PP + 4) & 7] = gauss_taps(kf, __fadd_rn(kl1, kr1), __fadd_rn(kl2, kr2));     // exact: a multiple of 1/16
+            }
             const float ml1 = from_left(mf), mr1 = from_right(mf);
             const float ml2 = from_left(ml1), mr2 = from_right(mr1);
             G1[(PP + 4) & 7] = gauss_taps(mf, __fadd_rn(ml1, mr1), __fadd_rn(ml2, mr2));
@@ -767,10 +786,17 @@ struct PostPipe {
             // slots: row o -> (PP+2)&7, o+1 -> PP+3, o+2 -> PP+4, o-1 -> PP+1, o-2 -> PP
             const float mo = MR[(PP + 2) & 7];
             // the rest of the row, given the four vertical neighbours of the horizontal pass
-            auto finish = [&](float u1, float u2, float d1, float d2) {
+            // (ku1 .. kd2: the same neighbours of the mask's pass, POST_BLUR_VALID only)
+            auto finish = [&](float u1, float u2, float d1, float d2, float ku1 = 0.f, float ku2 = 0.f, float kd1 = 0.f, float kd2 = 0.f) {
                 float val = mo;
                 if constexpr (do_blur) {
-                    const float acc = gauss_taps(G1[(PP + 2) & 7], __fadd_rn(u1, d1), __fadd_rn(u2, d2));
+                    float acc = gauss_taps(G1[(PP + 2) & 7], __fadd_rn(u1, d1), __fadd_rn(u2, d2));
+                    if constexpr (do_valid) {
+                        // den == 1 on every output lane (all 25 taps valid: the interior of the filled region): num / 1.0f is num, no
+                        // division.  A valid pixel has den >= 0.375^2; what an invalid one divides by is not selected below
+                        const float den = gauss_taps(G2[(PP + 2) & 7], __fadd_rn(ku1, kd1), __fadd_rn(ku2, kd2));
+                        if (__builtin_amdgcn_ballot_w64(outlane && den != 1.0f) != 0ull) acc = __fdiv_rn(acc, den);
+                    }
                     if (FILLED || mo >= thr) val = acc;                 // LO :184
                 }
                 if constexpr (MODE >= 11) val = invert_valid(val, max_depth, thr);  // LO :191-202
@@ -780,6 +806,18 @@ struct PostPipe {
             };
             const float g_p2 = G1[(PP + 4) & 7], g_p1 = G1[(PP + 3) & 7], g_0 = G1[(PP + 2) & 7];
             const float g_m1 = G1[(PP + 1) & 7], g_m2 = G1[PP];
+            if constexpr (do_valid) {
+                const float k_p2 = G2[(PP + 4) & 7], k_p1 = G2[(PP + 3) & 7], k_0 = G2[(PP + 2) & 7];
+                const float k_m1 = G2[(PP + 1) & 7], k_m2 = G2[PP];
+                if (o < 2 || o + 2 >= rows) {
+                    finish(o >= 1 ? g_m1 : g_p1, o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),
+                           o + 1 < rows ? g_p1 : g_m1, o + 2 < rows ? g_p2 : (o + 2 == rows ? g_0 : g_m2),
+                           o >= 1 ? k_m1 : k_p1, o >= 2 ? k_m2 : (o == 1 ? k_0 : k_p2),
+                           o + 1 < rows ? k_p1 : k_m1, o + 2 < rows ? k_p2 : (o + 2 == rows ? k_0 : k_m2));
+                } else {
+                    finish(g_m1, g_m2, g_p1, g_p2, k_m1, k_m2, k_p1, k_p2);
+                }
+            } else
             if (do_blur && (o < 2 || o + 2 >= rows)) {                    // reflect-101 rows (rows >= 8 guaranteed): the first and
                 finish(o >= 1 ? g_m1 : g_p1,                             // last two rows get their own copy of the tail, so the
                        o >= 2 ? g_m2 : (o == 1 ? g_0 : g_p2),            // common path reads the ring registers in place

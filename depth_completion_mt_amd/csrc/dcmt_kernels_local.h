@@ -23,7 +23,7 @@
 //  * leading empty rows: a wave first looks for the first row of its range that holds a non-zero value, stores zeros above
 //    its reach and treats the row where values may begin as the top of its band.
 //
-// MODE / BLUR as PostPipe's, except that MODE 9 is never instantiated: PostPipe<9> stores the median of every row it sees, whatever
+// MODE / BLUR (a POST_BLUR_* kind) as PostPipe's, except that MODE 9 is never instantiated: PostPipe<9> stores the median of every row it sees, whatever
 // the band; the median alone is PostPipe<10, false>, which stores through the band test.
 #pragma once
 
@@ -42,7 +42,7 @@ struct LocalS {
     static constexpr int LAT = F::LAT + 6;                                     // rows between the input row and the finished output row
 };
 
-template <int K0KIND, int IN, int MODE, bool BLUR>
+template <int K0KIND, int IN, int MODE, int BLUR>
 __global__ __launch_bounds__(256)
 void k_local(const void* __restrict__ src_, float* __restrict__ dst, int rows, int cols, int strips, int bands,
              int batch, int xcd_map, float max_depth, float thr, float in_scale, const float* __restrict__ coef)

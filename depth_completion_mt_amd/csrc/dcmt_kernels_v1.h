@@ -664,6 +664,8 @@ void k_fill31_v1(const float* __restrict__ in, float* __restrict__ out, const in
 //            (BORDER_REFLECT_101) + masked select, H11 invert.  Reads the buffer that holds
 //            the frame after its last fill application.
 // mode: 8 = copy only (probe of H8), 9 = stop after the median, 10 = after the blur, 11 = all
+// VALID: the instance for blur = DCMT_BLUR_GAUSSIAN_VALID (dcmt.h's GV).  Both passes run on m >= thr ? m : 0 and on the mask
+// m >= thr ? 1 : 0, whose horizontal pass goes to A (dead once the medians are in B); a valid pixel takes num / den.
 // ---------------------------------------------------------------------------------
 // reflect101 (BORDER_REFLECT_101): dcmt_gauss.h
 
@@ -675,7 +677,7 @@ __device__ __forceinline__ int apps_done(const int* cnt, int n_apps_launched)
     return a;
 }
 
-template <int TH, int TW>
+template <int TH, int TW, bool VALID = false>
 __global__ __launch_bounds__(kThreads)
 void k_post_v1(const float* __restrict__ pp0, const float* __restrict__ pp1, float* __restrict__ dst,
                const int* __restrict__ counters, int n_apps_launched, int rows, int cols,
@@ -730,16 +732,24 @@ void k_post_v1(const float* __restrict__ pp0, const float* __restrict__ pp1, flo
         }
     }
     __syncthreads();
-    const bool do_blur = blur == 1 && mode >= 10;
+    const bool do_blur = blur == (VALID ? 5 : 1) && mode >= 10;     // DCMT_BLUR_GAUSSIAN_VALID : DCMT_BLUR_GAUSSIAN
     if (do_blur) {
         // horizontal pass for the in-image rows of tile +- 2 (LO :179); reflect-101 in image coordinates
         for_rect(2, RH - 2, R, RW - R, [&](int y, int x) {
             const int gy = ty0 + y, gx = tx0 + x;
             if (gy < 0 || gy >= rows || gx >= cols) return;
             const float* b = B + y * P;
-            const float c0 = b[x];
-            const float l1 = b[reflect101(gx - 1, cols) - tx0], r1 = b[reflect101(gx + 1, cols) - tx0];
-            const float l2 = b[reflect101(gx - 2, cols) - tx0], r2 = b[reflect101(gx + 2, cols) - tx0];
+            float c0 = b[x];
+            float l1 = b[reflect101(gx - 1, cols) - tx0], r1 = b[reflect101(gx + 1, cols) - tx0];
+            float l2 = b[reflect101(gx - 2, cols) - tx0], r2 = b[reflect101(gx + 2, cols) - tx0];
+            if constexpr (VALID) {
+                auto mask = [&](float& t) { const bool ok = t >= thr; t = ok ? t : 0.0f; return ok ? 1.0f : 0.0f; };   // selects: NaN is not valid
+                const float kc = mask(c0), kl1 = mask(l1), kr1 = mask(r1), kl2 = mask(l2), kr2 = mask(r2);
+                float kacc = __fmul_rn(kc, 0.375f);
+                kacc = __fadd_rn(kacc, __fmul_rn(__fadd_rn(kl1, kr1), 0.25f));
+                kacc = __fadd_rn(kacc, __fmul_rn(__fadd_rn(kl2, kr2), 0.0625f));
+                A[(y - 2) * TW + (x - R)] = kacc;
+            }
             float acc = __fmul_rn(c0, 0.375f);
             acc = __fadd_rn(acc, __fmul_rn(__fadd_rn(l1, r1), 0.25f));
             acc = __fadd_rn(acc, __fmul_rn(__fadd_rn(l2, r2), 0.0625f));
@@ -759,6 +769,12 @@ void k_post_v1(const float* __restrict__ pp0, const float* __restrict__ pp1, flo
             float acc = __fmul_rn(C[(y - 2) * TW + cx], 0.375f);
             acc = __fadd_rn(acc, __fmul_rn(__fadd_rn(C[yu1 * TW + cx], C[yd1 * TW + cx]), 0.25f));
             acc = __fadd_rn(acc, __fmul_rn(__fadd_rn(C[yu2 * TW + cx], C[yd2 * TW + cx]), 0.0625f));
+            if constexpr (VALID) {
+                float den = __fmul_rn(A[(y - 2) * TW + cx], 0.375f);
+                den = __fadd_rn(den, __fmul_rn(__fadd_rn(A[yu1 * TW + cx], A[yd1 * TW + cx]), 0.25f));
+                den = __fadd_rn(den, __fmul_rn(__fadd_rn(A[yu2 * TW + cx], A[yd2 * TW + cx]), 0.0625f));
+                if (m >= thr) acc = __fdiv_rn(acc, den);       // den >= 0.375^2 there; == 1 where every tap is valid
+            }
             if (m >= thr) v = acc;               // LO :184 `> 0.1`
         }
         if (mode >= 11) v = invert_valid(v, max_depth, thr);   // H11 (LO :191-202)

@@ -110,6 +110,7 @@ struct Call {
     int k0kind = kK0AsCompiled;
     bool gaussian = true;
     bool bilateral = false;                  // DCMT_BLUR_BILATERAL_CLONE (never with gaussian)
+    bool valid = false;                      // DCMT_BLUR_GAUSSIAN_VALID (never with gaussian or bilateral; the labeled entry points keep it)
     int max_fill_iters = 64, spec_fill_iters = 1, stop_after = kStageFinal, flags = 0;
     bool sync_loop = false;                  // host entry points: the hole counters are read back between applications
     bool q16_allowed = false;                // a 16-bit attempt is allowed now (the context's skip state, dcmt.hip: q16_allowed_now)
@@ -145,6 +146,11 @@ struct Plan {
     // the bilateral finish: everything above is the plan of the same call with stop_after = MEDIAN5 and the context's median plane as
     // its dst; k_bilateral5 then reads that plane and writes dst, with the final invert for stop_after = FINAL
     bool bilateral = false, bilateral_invert = false;
+    // the Gaussian that ignores holes.  With the extrapolation it is planned like the bilateral finish: the chain to MEDIAN5 into the
+    // median plane, then k_gauss5<VALID> from there into dst (gauss_valid, and its invert for stop_after = FINAL).  Without it
+    // (no_extrapolate below) it is a kind of the kernel that finishes the call: valid_kind, k_local<.., VALID> / k_post_v1<.., VALID>
+    bool gauss_valid = false, gauss_valid_invert = false;
+    bool valid_kind = false;
     // DCMT_FLAG_NO_EXTRAPOLATE from stop_after = MEDIAN5 on: H6..H8 do not run.  Route::LOCAL: k_local, every strip in local_bands row
     // bands; Route::STAGED: k_pre*_v1 into X5, k_post_v1 from there
     bool no_extrapolate = false;
@@ -211,6 +217,18 @@ inline Plan plan_call(const Knobs& k, const Call& c)
         p.bilateral = true;
         p.bilateral_invert = c.stop_after == kStageFinal;
         path_append(p.path, " + bilateral5");
+        return p;
+    }
+    if (c.valid && c.stop_after >= kStageBlur && !no_extrapolate(c)) {
+        // as above, with k_gauss5<VALID> as the last kernel.  (Without the extrapolation the finish is part of the kernel that reads X5: below.)
+        Call m = c;
+        m.valid = false; m.gaussian = false;
+        m.stop_after = kStageMedian5;
+        m.dst = 0;
+        Plan p = plan_call(k, m);
+        p.gauss_valid = true;
+        p.gauss_valid_invert = c.stop_after == kStageFinal;
+        path_append(p.path, " + gauss5_valid");
         return p;
     }
     Plan p;
@@ -287,7 +305,10 @@ inline Plan plan_call(const Knobs& k, const Call& c)
         if (bands < 1) bands = 1;
         p.local_bands = bands;
         p.local_grid = wave_grid(p.local_strips * bands, batch, p.xcd_map);
+        p.valid_kind = c.valid && stop >= kStageBlur;
         if (labeled) path_append(p.path, "k_label_bbox + k_label_stage + ");
+        if (p.valid_kind) path_append(p.path, labeled ? "k_local<START4,VALID>" : u16 ? "k_local<U16,VALID>" : p.norm ? "k_local<NORM,VALID>" : "k_local<VALID>");
+        else
         path_append(p.path, labeled ? "k_local<START4>" : u16 ? "k_local<U16>" : p.norm ? "k_local<NORM>" : "k_local");
         if (bands > 1) path_append(p.path, " (row bands)");
         if (p.out != Out::DST) path_append(p.path, kPathCopy);
@@ -385,7 +406,9 @@ inline Plan plan_call(const Knobs& k, const Call& c)
     path_append(p.path, labeled ? "k_pre_labeled_v1" : "k_pre_v1");
     // (no extrapolation: k_post_v1 reads X5, behind the only kernel that reads the frames -- an overlapping dst needs no copy)
     p.no_extrapolate = no_extrapolate(c);
-    path_append(p.path, p.no_extrapolate ? " + k_post_v1 (staged tile kernels)" : " + k_fill31_v1 + k_post_v1 (staged tile kernels)");
+    p.valid_kind = p.no_extrapolate && c.valid && stop >= kStageBlur;
+    path_append(p.path, p.valid_kind ? " + k_post_v1<VALID> (staged tile kernels)" :
+                        p.no_extrapolate ? " + k_post_v1 (staged tile kernels)" : " + k_fill31_v1 + k_post_v1 (staged tile kernels)");
     if (p.out != Out::DST) path_append(p.path, kPathCopy);
     return p;
 }

@@ -95,7 +95,17 @@ typedef enum {
      * context plane that the first such call allocates, never to d_dst), then one more kernel writes d_dst, as the call's only and
      * last writer: every promise of the "In place" paragraph above holds.  dcmt_last_path ends in "+ bilateral5".  stop_after <=
      * DCMT_STAGE_MEDIAN5 ignores the blur, as with every value.  The labeled entry points force the Gaussian whatever this is. */
-    DCMT_BLUR_BILATERAL_CLONE = 3
+    DCMT_BLUR_BILATERAL_CLONE = 3,
+    /* "gaussian_valid": the Gaussian that ignores holes (an opt-in of this project; normalised convolution), X10 = GV(X9) as
+     * dcmt_gaussian5_valid_dev states GV, then the unchanged final invert.  Made for DCMT_FLAG_NO_EXTRAPOLATE, whose X9 is full of holes:
+     * there DCMT_BLUR_GAUSSIAN averages a valid pixel next to a hole with the hole's zeros (a pixel 10 m away, 90 in inverted space,
+     * becomes about 45 and the output says 55 m), along every border of the completed region.  On a plane without holes it is
+     * DCMT_BLUR_GAUSSIAN bit for bit.  With the flag it is part of the one kernel (k_local) or of the staged post kernel.  Without
+     * the flag it is planned as DCMT_BLUR_BILATERAL_CLONE is: the chain as for stop_after = DCMT_STAGE_MEDIAN5 into the context's
+     * median plane, then one more kernel, the call's only and last writer of d_dst; dcmt_last_path ends in "+ gauss5_valid".  There it
+     * differs from DCMT_BLUR_GAUSSIAN only in a frame whose hole-closure loop hit max_fill_iters.  stop_after <= DCMT_STAGE_MEDIAN5
+     * ignores it, as with every value.  The labeled entry points honour it (every other value they replace by the Gaussian). */
+    DCMT_BLUR_GAUSSIAN_VALID = 5 /* (4 is no blur and stays refused with DCMT_E_INVALID, as every value outside this enum) */
 } dcmt_blur;
 
 /* Stages of the cascade, for `stop_after` (parity probes; 11 = the whole chain). */
@@ -172,10 +182,15 @@ typedef struct {
  *     X9  = medianBlur5(X5)                                  (:170, replicated border)
  *     X10 = DCMT_BLUR_GAUSSIAN:        X9 >= thr ? GaussianBlur5(X9) : X9   (:178-188, reflect-101; forced by the labeled entry points)
  *           DCMT_BLUR_NONE:            X9
+ *           DCMT_BLUR_GAUSSIAN_VALID:  GV(X9), as dcmt_gaussian5_valid_dev states it: weights from the valid taps only (honoured by the
+ *                                      labeled entry points too)
  *           DCMT_BLUR_BILATERAL_CLONE: bilateral5(X9) over the whole plane, as dcmt_bilateral5_dev states it
  *           DCMT_BLUR_BILATERAL:       DCMT_E_UNSUPPORTED, as always
  *     X11 = X10 >= thr ? max_depth - X10 : X10               (:191-202)
  * A pixel whose median is valid but whose blurred value falls below thr is not inverted: those are the reference's statements.
+ * X9 is full of holes here, and DCMT_BLUR_GAUSSIAN (the default) averages every valid pixel that has a hole among its 25 taps with
+ * that hole's zeros, in inverted space: the depth along every border of the completed region comes out too large, by tens of metres
+ * at worst.  DCMT_BLUR_GAUSSIAN_VALID is the finish that does not.
  * stop_after <= DCMT_STAGE_FILL7: the call without the flag, bit for bit (the flag is ignored).  DCMT_STAGE_EXTEND, _FILL31 and
  * _FILLLOOP: DCMT_E_UNSUPPORTED before anything is enqueued.  DCMT_STAGE_MEDIAN5, _BLUR, _FINAL: X9, X10, X11.
  * max_fill_iters and spec_fill_iters are ignored; dcmt_last_fill_iters and dcmt_last_holes_after_extend report 0 for every frame,
@@ -834,6 +849,27 @@ int dcmt_depth_to_cloud(dcmt_ctx *ctx, const float *depth, size_t depth_row_stri
 int dcmt_gaussian5_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, void *stream);
 /* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
 int dcmt_gaussian5(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols);
+
+/* The 5x5 Gaussian that ignores holes (normalised convolution): for a plane with holes -- the cascade under DCMT_FLAG_NO_EXTRAPOLATE,
+ * a trust-masked plane, dcmt_sgm_dev's depth, a speckle-filtered plane.  With G5 the filter of dcmt_gaussian5_dev, thr = valid_thresh
+ * and v(x) = x >= thr (NaN is not valid):
+ *     num   = G5( v(X) ? X : 0 )          a select, not a product: +inf stays +inf, nothing makes a NaN
+ *     den   = G5( v(X) ? 1.0f : 0.0f )    exact: a multiple of 1/256
+ *     GV(X) = v(X) ? num / den : X        one IEEE f32 division, round to nearest even
+ * Consequences: at a valid pixel den >= 0.375^2 = 0.140625 (its own tap).  Where all 25 taps are valid den == 1.0f and GV(X) is
+ * G5(X) bit for bit, so on a plane without holes this call is dcmt_gaussian5_dev.  An invalid pixel comes back bit for bit: zero,
+ * -0.0, negatives, NaN.  A valid result lies in [min, max] of its valid taps up to the rounding of about 15 f32 operations on
+ * non-negative terms (a few ulp; so does a constant region with holes: close, not bit for bit).  No NaN comes out of a
+ * plane without one.
+ * valid_thresh: finite and > 0, as dcmt_params.valid_thresh (DCMT_E_INVALID otherwise, nothing written).  Buffers, alignment,
+ * d_dst == d_src (through context scratch and one copy), any other overlap (DCMT_E_INVALID), limits and the standing behind other
+ * *_dev calls: as dcmt_gaussian5_dev.  A pixel's bits do not depend on batch, its frame's position in the batch or the launch
+ * geometry.  Stream-ordered, never synchronises, never allocates. */
+int dcmt_gaussian5_valid_dev(dcmt_ctx *ctx, const float *d_src, float *d_dst, int rows, int cols, int batch, float valid_thresh,
+                             void *stream);
+/* HOST pointers, one frame, synchronous (row strides in BYTES); src may be dst. */
+int dcmt_gaussian5_valid(dcmt_ctx *ctx, const float *src, size_t src_row_stride, float *dst, size_t dst_row_stride, int rows, int cols,
+                         float valid_thresh);
 
 /* cv::bilateralFilter(src, dst, 5, sigma_color, sigma_space) for CV_32FC1 with BORDER_DEFAULT, as this project states it (OpenCV is
  * never executed, and its 4096-bin interpolated exp table is not restated: DESIGN.md section 19): the edge-preserving alternative to

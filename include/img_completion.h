@@ -75,6 +75,7 @@ inline int blur_from_string(const std::string& blur_type)
     if (blur_type == "gaussian") return DCMT_BLUR_GAUSSIAN;   // img_completion.cpp:176
     if (blur_type == "bilateral") return DCMT_BLUR_BILATERAL; // :172 -- cv::bilateralFilter in place throws; so do we
     if (blur_type == "bilateral_clone") return DCMT_BLUR_BILATERAL_CLONE;   // this project's opt-in: :174 given a copy (dcmt.h)
+    if (blur_type == "gaussian_valid") return DCMT_BLUR_GAUSSIAN_VALID;     // this project's opt-in: the Gaussian that ignores holes (dcmt.h)
     return DCMT_BLUR_NONE;                                    // any other string: no blur
 }
 
@@ -325,6 +326,20 @@ inline void gaussian_blur5(const cv::Mat& src, cv::Mat& dst)
     out.create(rows, cols, CV_32FC1);
     raise(dcmt_gaussian5(thread_ctx().get(rows, cols), src.ptr<float>(), src.step[0], out.ptr<float>(), out.step[0], rows, cols),
           "gaussian_blur5");
+    dst = out;
+}
+
+// The 5x5 Gaussian that ignores holes (dcmt_gaussian5_valid, dcmt.h's GV): a pixel >= valid_thresh becomes the average of its taps
+// >= valid_thresh under the Gaussian's weights, every other pixel comes back as it is.  For planes with holes: the cascade without its
+// extrapolation, a trust-masked plane, stereo depth.  src and dst may be the same Mat.  CV_32FC1 in, a fresh CV_32FC1 out.
+inline void gaussian_blur5_valid(const cv::Mat& src, cv::Mat& dst, float valid_thresh = 0.1f)
+{
+    check_input(src);
+    const int rows = src.rows, cols = src.cols;
+    cv::Mat out;
+    out.create(rows, cols, CV_32FC1);
+    raise(dcmt_gaussian5_valid(thread_ctx().get(rows, cols), src.ptr<float>(), src.step[0], out.ptr<float>(), out.step[0], rows, cols, valid_thresh),
+          "gaussian_blur5_valid");
     dst = out;
 }
 
