@@ -220,7 +220,12 @@ int launch_streaming(dcmt_ctx* ctx, const plan::Plan& pl, const Frames& fr, cons
                            p->valid_thresh, scale, cf, tc, cnt, qbad, gate, ctx->q16_seen_dev, qclr);
     };
     int* qbad = ctx->q16_bad;               // the flag of this call's 16-bit attempt
-    if (q16) {
+    if (q16 && pl.q16_own_flag) {
+        // a captured call: every replay clears the captured calls' flag itself and leaves the ring, which only the host can move round, alone
+        qbad = ctx->q16_bad + kQ16Flags;
+        DCMT_HIP(ctx, hipMemsetAsync(qbad, 0, sizeof(int), st));
+        with_k0(pl.k0kind, [&](auto kind) { pre_p(kind, std::true_type{}, reinterpret_cast<float*>(ctx->x6q.p), qbad, nullptr, nullptr); });
+    } else if (q16) {
         // this attempt's flag (cleared by the previous attempt's kernel, or by dcmt_create) and the next one's, which this attempt's kernel clears
         qbad = ctx->q16_bad + ctx->q16_attempts % kQ16Flags;
         int* qnext = ctx->q16_bad + (ctx->q16_attempts + 1) % kQ16Flags;
@@ -337,6 +342,10 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     const uint32_t kb = k0_bits(p->k0);
     // (the labeled entry points force the reference's Gaussian, except for this project's own opt-in)
     const int blur = force_gaussian && p->blur != DCMT_BLUR_GAUSSIAN_VALID ? (int)DCMT_BLUR_GAUSSIAN : p->blur;
+    // A call whose stream is being captured into a graph (dcmt.h, "Graph capture") runs later, on every replay: events recorded or
+    // lines printed once, now, would mean nothing then -- refused before anything is enqueued
+    const bool capturing = !sync_loop && stream_capturing(st);
+    if (capturing && (ctx->timing || p->verbose)) return DCMT_E_INVALID;
     ctx->tev_valid = 0;
     if ((p->flags & DCMT_FLAG_NORMALIZE) && fr.src16) return DCMT_E_UNSUPPORTED;
     plan::Call c;
@@ -352,7 +361,10 @@ int run_chain(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool force_
     c.valid = blur == DCMT_BLUR_GAUSSIAN_VALID;
     c.max_fill_iters = p->max_fill_iters; c.spec_fill_iters = p->spec_fill_iters; c.stop_after = stop; c.flags = p->flags;
     c.sync_loop = sync_loop;
-    c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && q16_allowed_now(ctx);
+    // The context's skip state is the eager calls': a captured call neither reads nor advances it (what it decided now would hold for
+    // every replay).  It makes the attempt wherever the plan allows one, on the flag the captured calls have to themselves
+    c.capturing = capturing;
+    c.q16_allowed = plan::route_of(ctx->knobs, c) == plan::Route::STREAMING && (capturing ? ctx->knobs.fp_q16 != 0 : q16_allowed_now(ctx));
     const plan::Plan pl = plan::plan_call(ctx->knobs, c);
     if (!pl.bilateral && !pl.gauss_valid) return run_plan(ctx, pl, fr, p, blur, st, sync_loop);
 
@@ -621,7 +633,8 @@ int complete_sync(dcmt_ctx* ctx, const Frames& fr, const dcmt_params* p, bool fo
 int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st, unsigned* gen_tag)
 {
     const bool fresh = n_px > ctx->winner.n;                // what reserve is about to replace
-    const plan::Winner w = plan::winner_next(ctx->winner_bits, ctx->winner_gen, fresh, n_index);
+    // (a call that is being captured clears on every replay and leaves the context at generation 0: plan::winner_next)
+    const plan::Winner w = plan::winner_next(ctx->winner_bits, ctx->winner_gen, fresh, n_index, stream_capturing(st));
     if (w.status != DCMT_OK) return w.status;
     DCMT_TRY(ctx->winner.reserve(ctx, n_px));
     if (w.clear) {
@@ -629,7 +642,7 @@ int winner_generation(dcmt_ctx* ctx, size_t n_px, size_t n_index, hipStream_t st
         DCMT_HIP(ctx, hipMemsetAsync(ctx->winner, 0, sizeof(unsigned) * ctx->winner.n, st));
     }
     ctx->winner_bits = w.bits;
-    ctx->winner_gen = w.gen;
+    ctx->winner_gen = w.keep;
     *gen_tag = w.tag;
     return DCMT_OK;
 }
@@ -721,8 +734,8 @@ int dcmt_create(int device, int max_rows, int max_cols, int max_batch, dcmt_ctx*
     const size_t mb = (size_t)max_batch, chunks = eval_chunks((uint32_t)ctx->frame_elems);
     if (!mem(ctx->pp[0], plane) || !mem(ctx->pp[1], plane)) return fail(DCMT_E_NOMEM);
     ctx->x5 = ctx->pp[1];
-    if (!mem(ctx->counters, kCntStride * mb) || !mem(ctx->q16_bad, kQ16Flags)) return fail(DCMT_E_NOMEM);
-    if (hipMemset(ctx->q16_bad, 0, sizeof(int) * kQ16Flags) != hipSuccess) return fail(DCMT_E_HIP);
+    if (!mem(ctx->counters, kCntStride * mb) || !mem(ctx->q16_bad, kQ16Flags + 1)) return fail(DCMT_E_NOMEM);      // the ring, and the captured calls' flag
+    if (hipMemset(ctx->q16_bad, 0, sizeof(int) * (kQ16Flags + 1)) != hipSuccess) return fail(DCMT_E_HIP);
     if (!mem(ctx->q16_seen, 64 / sizeof(int))) return fail(DCMT_E_NOMEM);
     *ctx->q16_seen = 0;
     if (hipHostGetDevicePointer((void**)&ctx->q16_seen_dev, ctx->q16_seen, 0) != hipSuccess) return fail(DCMT_E_HIP);
@@ -954,6 +967,7 @@ int dcmt_last_fill_iters(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
+    if (stream_capturing(ctx->last_stream)) return DCMT_E_INVALID;                     // nothing of the call has run, and its stream cannot be waited for
     if (ctx->last_no_extrapolate) { std::fill(out, out + n, 0); return DCMT_OK; }      // no loop ran
     if (!ctx->last_has_loop) return DCMT_E_INVALID;
     int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
@@ -972,6 +986,7 @@ int dcmt_last_holes_after_extend(dcmt_ctx* ctx, int* out, int n)
 {
     DCMT_ON_DEVICE(ctx);
     if (!ctx || !out || n < 0 || n > ctx->last_batch) return DCMT_E_INVALID;
+    if (stream_capturing(ctx->last_stream)) return DCMT_E_INVALID;
     if (ctx->last_no_extrapolate) { std::fill(out, out + n, 0); return DCMT_OK; }      // no extension ran
     int rc = read_counters(ctx, ctx->last_stream, ctx->last_batch);
     if (rc != DCMT_OK) return rc;

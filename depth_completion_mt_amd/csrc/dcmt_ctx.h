@@ -81,7 +81,9 @@ struct dcmt_ctx {
     Dev<unsigned short> x6q;          // [max_batch][rows][cols] X6 as 16-bit codes (k_pre_p<Q16OUT> -> k_fp_q) and 16 bytes of slack; the first
                                       // call whose plan names it
     Dev<int> q16_bad;                 // a ring of kQ16Flags flags; attempt n uses flag n % kQ16Flags: raised by k_pre_p<Q16OUT> when a value it stored was
-                                      // not a code, and cleared one attempt ahead by that kernel too (no memset in the stream)
+                                      // not a code, and cleared one attempt ahead by that kernel too (no memset in the stream).  One more flag
+                                      // behind the ring is the captured calls': a replay cannot move round a ring, so a call made while its
+                                      // stream is capturing uses this one and clears it itself, with a node in front of its kernels
     unsigned q16_attempts = 0;
     dcmt::Buf<int, dcmt::Mem::MAPPED> q16_seen;     // pinned host word (and its device address) the same kernel sets: the NEXT calls skip the 16-bit attempt
     int* q16_seen_dev = nullptr;      // (an alias, owns nothing)
@@ -184,6 +186,19 @@ void with_value(T v, F f)
     if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<decltype(V), V>{});
     else if (v == V) f(std::integral_constant<decltype(V), V>{});
     else with_value<Rest...>(v, f);
+}
+
+// `st` is being captured into a graph (dcmt.h, "Graph capture"): what the call enqueues runs later, any number of times, with the
+// arguments it is given now.  A stream that cannot be asked (the null stream while another one captures) is not capturing; the
+// error does not stay behind.
+inline bool stream_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &s) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return s != hipStreamCaptureStatusNone;
 }
 
 // rows x cols x batch is a size the context was created for

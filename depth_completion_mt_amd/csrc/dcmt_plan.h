@@ -114,6 +114,7 @@ struct Call {
     int max_fill_iters = 64, spec_fill_iters = 1, stop_after = kStageFinal, flags = 0;
     bool sync_loop = false;                  // host entry points: the hole counters are read back between applications
     bool q16_allowed = false;                // a 16-bit attempt is allowed now (the context's skip state, dcmt.hip: q16_allowed_now)
+    bool capturing = false;                  // the call's stream is being captured into a graph: its kernels run later, on every replay
 };
 
 enum class Route { NORMALIZE_ONLY, STAGED, LABEL_PROBE, STREAMING, LOCAL };     // LOCAL: k_local (DCMT_FLAG_NO_EXTRAPOLATE)
@@ -137,6 +138,8 @@ struct Plan {
     // streaming kernels
     bool table = false;              // X6 through the per-column (first, last) table
     bool wide = false, pair = false, q16 = false;
+    bool q16_own_flag = false;       // the 16-bit attempt of a captured call: its flag is the context's one flag behind the ring, cleared by a
+                                     // node in front of the call's kernels on every replay, and it clears no flag for a next attempt
     int bands = 1, fb_s = 1;         // row bands of k_pre_p (= table slots per frame) / of k_fp_s
     int pre_strips = 0, fill_strips = 0, post_strips = 0, q_strips = 0;
     unsigned pre_grid = 0, fill_grid = 0, post_grid = 0, fp_s_grid = 0, fp_q_grid = 0;
@@ -349,6 +352,7 @@ inline Plan plan_call(const Knobs& k, const Call& c)
         p.q16 = k.fp_q16 && c.q16_allowed && (long long)batch * p.q_strips >= k.q16_min_waves && p.pair && p.table && !cf &&
                 q16_params_ok(c.max_depth, c.valid_thresh) && c.dst % 8 == 0 && (!u16 || c.in_scale == 0.00390625f) && !overlap;
         p.needs_x6q = p.q16;
+        p.q16_own_flag = p.q16 && c.capturing;
         const int vw = p.pair ? pre_p_vw(c.k0kind, labeled) : pre_s_vw(c.k0kind, p.wide);
         p.pre_strips = (cols + vw - 1) / vw;
         p.pre_grid = wave_grid(p.pre_strips * p.bands, batch, p.xcd_map);

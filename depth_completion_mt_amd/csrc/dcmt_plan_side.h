@@ -85,26 +85,31 @@ inline ColorPlan plan_colorize(uint32_t n, int batch, uintptr_t src_addr, uintpt
 // One call's step of the plane's state: (bits, gen) = the index bits of the tag layout and the last call's generation, fresh = the
 // plane has just been (re)allocated, n_index = the call stores indices below n_index.  The plane is cleared when it is fresh,
 // when the call needs more index bits than the layout has, and when the generations have run out.
+// capturing = the call's stream is being captured into a graph: the call's kernels run later, any number of times, with the tag
+// they were given here, and what the plane holds by then is anybody's.  Such a call always clears (the clear is a node of the graph,
+// in front of its kernels), takes generation 1 and leaves `keep` = 0 for the context, so that the next call clears as well: a call
+// that runs between two replays finds the replay's tags of generation 1 under whatever generation it would have taken.
 struct Winner {
     int status;                      // kInvalid: 2^30 indices or more (nothing else is meaningful then)
     int bits;
     unsigned gen;
     bool clear;                      // zero the plane before the call's kernels
     unsigned tag;                    // gen << bits
+    unsigned keep;                   // the generation the context remembers: gen, or 0 behind a captured call
 };
 
-inline Winner winner_next(int bits, unsigned gen, bool fresh, size_t n_index)
+inline Winner winner_next(int bits, unsigned gen, bool fresh, size_t n_index, bool capturing = false)
 {
     int need_bits = 1;
     while (need_bits < 31 && ((size_t)1 << need_bits) <= n_index) ++need_bits;
-    if (need_bits > 30) return {kInvalid, bits, gen, false, 0};
+    if (need_bits > 30) return {kInvalid, bits, gen, false, 0, gen};
     if (fresh) { bits = 0; gen = 0; }
     const bool relayout = need_bits > bits;
     if (relayout) bits = need_bits < 24 ? 24 : need_bits;                  // (room for 16 M indices per call before the next re-layout)
     const unsigned gen_max = (1u << (32 - bits)) - 1u;
-    const bool clear = relayout || gen == 0 || gen >= gen_max;
+    const bool clear = capturing || relayout || gen == 0 || gen >= gen_max;
     gen = clear ? 1 : gen + 1;
-    return {kOk, bits, gen, clear, gen << bits};
+    return {kOk, bits, gen, clear, gen << bits, capturing ? 0u : gen};
 }
 
 // k_project_resolve / k_reproject_resolve: pixels per thread, as wide as the pixel count and the output's address allow

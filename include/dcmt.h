@@ -56,6 +56,39 @@
  * because no fill runs, one copy follows and dcmt_last_path ends in "+ copy to dst"; the labeled entry point's kernel reads the
  * label stage's output and needs no copy, nor do the staged kernels or the bilateral finish.  d_labels must not overlap d_dst.  The host entry points stage through device buffers of their
  * own: src may be dst there too.
+ *
+ * Graph capture: every *_dev entry point may be called while its stream is being captured into a graph (hipStreamBeginCapture,
+ * torch.cuda.graph) and the graph replayed any number of times; each replay gives the bits of the same call made eagerly on what
+ * the buffers hold then (tests/test_gpu_graph_replay.py: every entry point, every route of the cascade, whole pipelines as one
+ * graph, eager calls on the same context between the replays).  The rules:
+ *   - Warm up first: make the same call -- same shapes, batch, parameters, n_labels, step -- once eagerly on that context.  It makes
+ *     the documented first-use allocations; a capture in the strict mode (the default) fails on an allocation, and a call that has
+ *     to allocate while its stream is capturing returns an error and leaves the capture invalid.  One warm-up is enough on every
+ *     route.  A later call that GROWS context scratch (more labels, a smaller SLIC step, a larger projection target: the calls that
+ *     say "grown on demand") frees what earlier graphs point to: capture them again.
+ *   - One stream: capture a ctx's calls on one stream, as a straight line.  Graphs with parallel branches, captures that fork to
+ *     other streams and multi-GPU captures are not supported.  Replays and eager calls on one ctx must be ordered on the device
+ *     like any two calls (above); with that, they may be mixed freely.
+ *   - What is frozen: every pointer and every by-value argument -- the parameter structs, scales, rows, cols, batch, n_points,
+ *     n_labels, T and P of dcmt_project_points_dev, the workspace size -- as it was at capture time.  What is free to change between
+ *     replays: the contents of every buffer, the *_calib_dev tables, d_offsets and the label planes among them.
+ *   - The 16-bit form (above) of a captured call uses a flag of its own, cleared by a node in front of its kernels, and does not
+ *     take part in the context's 63-call back-off: it is attempted on every replay, so a graph that is fed depths off the 1/256 m
+ *     grid runs both large kernels twice every time.  Capture with DCMT_FP_Q16=0 in dcmt_create's environment for such data.  A frame
+ *     off the grid in a replay still sends the context's EAGER calls into their back-off.
+ *   - dcmt_project_points_dev, dcmt_reproject_depth_dev and their _calib twins clear the context's winner plane on every replay (a
+ *     memset node of 4 bytes per output pixel of the largest such call so far), which their eager form does once in 255 calls.
+ *   - dcmt_last_fill_iters and dcmt_last_holes_after_extend after a replay report THAT replay, once the caller has synchronised
+ *     the stream the graph was launched on (they wait for the stream the call was captured on, not for the replay's; a replay on
+ *     the capture stream needs no more).  While the last call's stream is capturing they return DCMT_E_INVALID: nothing has run.
+ *     dcmt_last_path names the captured route; after a dcmt_rectify_dev it copies from the device, so it must not be called while
+ *     a capture is open, and its route suffix describes the last rectify call made through the API only while no graph holding
+ *     an older one has been replayed since.
+ *   - Refused while the stream is capturing, with DCMT_E_INVALID and before anything is enqueued: a completion call with
+ *     dcmt_set_kernel_timing on (its events would be recorded into the graph, not timed) or with params->verbose set.
+ *   - The host (synchronous) entry points synchronise by design and stay eager-only.
+ * What a replayed graph saves over eager calls (launch cost at batch 1-8, where it dominates) and what the extra clear and the
+ * unconditional attempt cost has not been measured.
  * Empty pixels: the sign of a zero in an output pixel that stays empty (an all-empty frame) is +0.0 where the input held +0.0; an
  * input -0.0 counts as 0.0 (empty) and may come out as either zero.
  */

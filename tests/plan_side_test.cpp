@@ -136,6 +136,31 @@ static void test_winner()
     w = checked_winner(30, 2, true, 0);                          // fresh resets both fields
     CHECK(w.status == kOk && w.clear && w.bits == 24 && w.gen == 1);
     CHECK(checked_winner(24, 0, false, 0).clear);                // generation 0: nothing written yet
+    // an eager call keeps the generation it took: the state it leaves is the plan it always was
+    for (unsigned gen : {0u, 1u, 7u, 254u, 255u}) {
+        const Winner a = winner_next(24, gen, false, 1000), b = winner_next(24, gen, false, 1000, false);
+        CHECK(a.keep == a.gen && a.status == b.status && a.bits == b.bits && a.gen == b.gen && a.clear == b.clear && a.tag == b.tag && a.keep == b.keep);
+    }
+    // a call whose stream is being captured: the clear is part of every replay, the generation is 1 whatever the context's was, and
+    // the context is left at generation 0, so that the next call clears as well
+    for (unsigned gen : {0u, 1u, 7u, 254u, 255u}) {
+        const Winner c = winner_next(24, gen, false, 1000, true);
+        CHECK(c.status == kOk && c.clear && c.gen == 1 && c.bits == 24 && c.tag == 1u << 24 && c.keep == 0);
+        const Winner next = checked_winner(c.bits, c.keep, false, 1000);             // the eager call behind the capture
+        CHECK(next.clear && next.gen == 1 && next.keep == 1);
+        const Winner after = checked_winner(next.bits, next.keep, false, 1000);      // ... and the one behind that: above every replay's tags
+        CHECK(!after.clear && after.gen == 2 && after.tag > (c.tag | 999u));
+    }
+    {
+        const Winner c = winner_next(24, 7, false, (size_t)1 << 24, true);           // a captured call that needs a new layout
+        CHECK(c.clear && c.bits == 25 && c.gen == 1 && c.tag == 1u << 25 && c.keep == 0);
+        const Winner f = winner_next(30, 2, true, 5, true);                          // ... and one on a fresh plane
+        CHECK(f.clear && f.bits == 24 && f.gen == 1 && f.keep == 0);
+        CHECK(winner_next(24, 7, false, (size_t)1 << 30, true).status == kInvalid);
+        // a graph captured under an older, narrower layout: an eager call of a later generation stays above its tags
+        const Winner wide = checked_winner(25, 1, false, 5);
+        CHECK(wide.gen == 2 && wide.tag > ((1u << 24) | ((1u << 24) - 1u)));
+    }
 }
 
 // ---- SLIC ---------------------------------------------------------------------------------------------------------------

@@ -37,6 +37,7 @@ static Plan checked(const Knobs& k, const Call& c)
 {
     const Plan p = plan_call(k, c);
     CHECK(p.needs_x6q == p.q16);
+    CHECK(p.q16_own_flag == (p.q16 && c.capturing));
     CHECK(!p.q16 || (p.route == Route::STREAMING && p.pair && p.table && p.fuse_fp));
     CHECK(p.needs_colstat == (p.route == Route::STAGED));
     CHECK(p.needs_bbox == (c.input == Input::LABELED && (p.route == Route::LABEL_PROBE || p.route == Route::STREAMING)));
@@ -61,7 +62,7 @@ static std::string diff(const Plan& a, const Plan& b)
     F(route) F(k0kind) F(norm) F(xcd_map) F(out) F(needs_x6q) F(needs_colstat) F(needs_bbox) F(few) F(tile_h) F(tiles_x) F(tiles_y)
     F(u16_convert) F(dump) F(bbox_lds) F(lpair) F(label_pairs) F(label_group) F(label_grid_x) F(table) F(wide) F(pair) F(q16) F(bands)
     F(fb_s) F(pre_strips) F(fill_strips) F(post_strips) F(q_strips) F(pre_grid) F(fill_grid) F(post_grid) F(fp_s_grid) F(fp_q_grid)
-    F(fuse_fp) F(filled) F(tail) F(fp_s_launch) F(n_redo)
+    F(fuse_fp) F(filled) F(tail) F(fp_s_launch) F(n_redo) F(q16_own_flag)
 #undef F
     if (std::strcmp(a.path, b.path) != 0) d += std::string(d.empty() ? "" : ",") + "path";
     return d;
@@ -100,6 +101,29 @@ static void test_table()
         Knobs off;
         off.fp_q16 = 0;
         CHECK(!checked(off, call(1024)).q16);
+        // the same call while its stream is being captured into a graph: the same kernels on the same grids, the attempt's flag its own
+        Call g = call(1024);
+        g.capturing = true;
+        CHECK_DIFF(p, checked(g), "q16_own_flag");
+        CHECK(checked(g).q16_own_flag && !p.q16_own_flag);
+        g.q16_allowed = false;
+        CHECK_DIFF(checked(c), checked(g), "");            // no attempt: capturing changes nothing
+        CHECK(!checked(off, g).q16 && !checked(off, g).q16_own_flag);
+    }
+    for (int batch : {1, 2, 8, 128, 236}) {               // every plan without an attempt is the eager plan, field for field
+        Call g = call(batch);
+        g.capturing = true;
+        CHECK_DIFF(checked(call(batch)), checked(g), "");
+        Call l = labeled_call(batch, 1200), lg = l;
+        lg.capturing = true;
+        CHECK_DIFF(checked(l), checked(lg), "");
+    }
+    for (int blur = 0; blur < 2; ++blur) {                // the two finishes plan their chain with the call's fields: capturing among them
+        Call f = call(1024);
+        f.gaussian = false; f.bilateral = blur == 0; f.valid = blur == 1;
+        Call g = f;
+        g.capturing = true;
+        CHECK_DIFF(checked(f), checked(g), checked(f).q16 ? "q16_own_flag" : "");
     }
     {
         Call c = call(1024);

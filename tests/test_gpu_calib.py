@@ -373,25 +373,72 @@ def _none(_):
     return None
 
 
+_stream_sets = {}
+
+
+def _stream_set(kind, which):
+    """calib_cases.stream_case(kind, which): sets 0 and 1 are the ones test_calib.py checks without a GPU; further sets (tests/
+    test_gpu_graph_replay.py) come from the same generator with further seeds."""
+    if which in (0, 1):
+        return C.cases()[f"stream {kind} 24x40 {'decoy' if which else 'real'}"]
+    if (kind, which) not in _stream_sets:
+        _stream_sets[kind, which] = C.stream_case(kind, which)
+    return _stream_sets[kind, which]
+
+
 def _ordered_case(kind, name, dims, inputs_of, outputs, call, expect_of):
     """A test_gpu_stream_order.Case whose inputs (the table among them) are calib_cases.stream_case(kind, which): the sets that
     test_calib.py checks, without a GPU, to tell every frame's record from every other."""
     import test_gpu_stream_order as S
-    sets = {which: C.cases()[f"stream {kind} 24x40 {'decoy' if which else 'real'}"] for which in (0, 1)}
+    seen = {}
 
     def inputs(which):
-        c = sets[which]
+        c = seen[which] = _stream_set(kind, which)
         d = inputs_of(c)
         d["calib"] = c.table.view(np.uint8).reshape(c.b, -1)
         return d
 
     def expect(inp):
-        for c in sets.values():
-            if c.table.tobytes() == inp["calib"].tobytes():
+        for c in seen.values():
+            if c.table.tobytes() == inp["calib"].tobytes() and all(np.array_equal(v, inp[k]) for k, v in inputs_of(c).items()):
                 return expect_of(c, c.want)
         raise AssertionError("unknown input set")
 
     return S.Case(name, dims, inputs, outputs, call, expect)
+
+
+def stream_order_case(which):
+    """The stream-order case of one of the four table calls ("project", "cloud", "reproject", "stereo")."""
+    import test_gpu_stream_order as S
+    rows, cols, b = C.STREAM_ROWS, C.STREAM_COLS, C.STREAM_B
+    if which == "project":
+        return _ordered_case(which, "project_points_calib 24x40", (rows, cols, b),
+                             lambda c: {"pts": c.points, "off": c.offsets}, {"sparse": S.Out((b, rows, cols), f32)},
+                             lambda ctx, t, st: _none(ctx.project_points_calib_dev(t["pts"], t["off"], t["calib"], rows, cols, t["sparse"], stream=st)),
+                             lambda c, fr: {"sparse": np.stack([fr(f) for f in range(b)])})
+    if which == "reproject":
+        return _ordered_case(which, "reproject_depth_calib 24x40 -> 20x36", (rows, cols, b),
+                             lambda c: {"depth": c.frames}, {"out": S.Out((b, 20, 36), f32)},
+                             lambda ctx, t, st: _none(ctx.reproject_depth_calib_dev(t["depth"], 20, 36, t["calib"], t["out"], stream=st)),
+                             lambda c, fr: {"out": np.stack([fr(f) for f in range(b)])})
+    if which == "stereo":
+        return _ordered_case(which, "stereo_refine_calib 24x40", (rows, cols, b),
+                             lambda c: {"depth": c.depth, "left": c.left, "right": c.right}, {"out": S.Out((b, rows, cols), f32)},
+                             lambda ctx, t, st: _none(ctx.stereo_refine_calib_dev(t["depth"], t["left"], t["right"], t["calib"], t["out"], iterations=4, stream=st)),
+                             lambda c, fr: {"out": np.stack([fr(f) for f in range(b)])})
+
+    def cloud_expect(c, fr):
+        recs = [fr(f) for f in range(b)]
+        pts = np.full((b * rows * cols, 4), S.fill_of(f32), f32)          # rows from offsets[batch] on keep the fill
+        allr = np.concatenate(recs)
+        pts.view(np.uint32)[:len(allr)] = allr
+        return {"points": pts, "offsets": np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int32)}
+
+    return _ordered_case(which, "depth_to_cloud_calib 24x40", (rows, cols, b),
+                         lambda c: {"depth": c.frames, "bgr": c.bgr},
+                         {"points": S.Out((b * rows * cols, 4), f32, per_frame=False), "offsets": S.Out((b + 1,), np.int32, per_frame=False)},
+                         lambda ctx, t, st: _none(ctx.depth_to_cloud_calib_dev(t["depth"], t["calib"], t["bgr"], d_points=t["points"], d_offsets=t["offsets"], stream=st)),
+                         cloud_expect)
 
 
 @gpu
@@ -402,33 +449,4 @@ def test_table_call_queued_behind_a_delay_reads_its_table_in_stream_order(which)
     behind it, and the marker behind the delay must still be pending when the call returns.  A call that read the table too early or
     too late, or not on its stream, gives the decoy's bits."""
     import test_gpu_stream_order as S
-    rows, cols, b = C.STREAM_ROWS, C.STREAM_COLS, C.STREAM_B
-    if which == "project":
-        case = _ordered_case(which, "project_points_calib 24x40", (rows, cols, b),
-                             lambda c: {"pts": c.points, "off": c.offsets}, {"sparse": S.Out((b, rows, cols), f32)},
-                             lambda ctx, t, st: _none(ctx.project_points_calib_dev(t["pts"], t["off"], t["calib"], rows, cols, t["sparse"], stream=st)),
-                             lambda c, fr: {"sparse": np.stack([fr(f) for f in range(b)])})
-    elif which == "reproject":
-        case = _ordered_case(which, "reproject_depth_calib 24x40 -> 20x36", (rows, cols, b),
-                             lambda c: {"depth": c.frames}, {"out": S.Out((b, 20, 36), f32)},
-                             lambda ctx, t, st: _none(ctx.reproject_depth_calib_dev(t["depth"], 20, 36, t["calib"], t["out"], stream=st)),
-                             lambda c, fr: {"out": np.stack([fr(f) for f in range(b)])})
-    elif which == "stereo":
-        case = _ordered_case(which, "stereo_refine_calib 24x40", (rows, cols, b),
-                             lambda c: {"depth": c.depth, "left": c.left, "right": c.right}, {"out": S.Out((b, rows, cols), f32)},
-                             lambda ctx, t, st: _none(ctx.stereo_refine_calib_dev(t["depth"], t["left"], t["right"], t["calib"], t["out"], iterations=4, stream=st)),
-                             lambda c, fr: {"out": np.stack([fr(f) for f in range(b)])})
-    else:
-        def cloud_expect(c, fr):
-            recs = [fr(f) for f in range(b)]
-            pts = np.full((b * rows * cols, 4), S.fill_of(f32), f32)          # rows from offsets[batch] on keep the fill
-            allr = np.concatenate(recs)
-            pts.view(np.uint32)[:len(allr)] = allr
-            return {"points": pts, "offsets": np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int32)}
-
-        case = _ordered_case(which, "depth_to_cloud_calib 24x40", (rows, cols, b),
-                             lambda c: {"depth": c.frames, "bgr": c.bgr},
-                             {"points": S.Out((b * rows * cols, 4), f32, per_frame=False), "offsets": S.Out((b + 1,), np.int32, per_frame=False)},
-                             lambda ctx, t, st: _none(ctx.depth_to_cloud_calib_dev(t["depth"], t["calib"], t["bgr"], d_points=t["points"], d_offsets=t["offsets"], stream=st)),
-                             cloud_expect)
-    S.run_ordered(case)
+    S.run_ordered(stream_order_case(which))

@@ -339,7 +339,8 @@ def stream_project_case(table):
     recs = [R.project_record(rows, cols, k) for k in range(3)]
     T, P = recs[0]
     tab_bytes = project_table(recs).view(np.uint8).reshape(3, 96)
-    offs = {0: np.array([0, 800, 800, 1500], np.int32), 1: np.array([0, 500, 1500, 1500], np.int32)}      # the empty sweep moves
+    offs = {0: np.array([0, 800, 800, 1500], np.int32), 1: np.array([0, 500, 1500, 1500], np.int32),      # the empty sweep moves
+            2: np.array([0, 0, 700, 1500], np.int32), 3: np.array([0, 400, 1100, 1500], np.int32)}        # (further sets: tests/test_gpu_graph_replay.py)
 
     def inputs(which):
         d = {"pts": np.array(R.project_inputs(rows, cols, seed=which)["points"]), "off": offs[which]}

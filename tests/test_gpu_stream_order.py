@@ -746,9 +746,17 @@ def run_pipeline(name, dims, input_sets, decoy, outputs, calls, expectations, de
             assert_same(got[i][k], e[k], f"{name}: iteration {i}: {k}", k)
 
 
-@gpu
-def test_lidar_camera_pipeline_repeated_in_reused_buffers():
-    """bgr_convert -> slic_labels -> complete(d_labels) -> evaluate, three times through the same buffers behind one delay."""
+class Pipeline:
+    """A chain of calls through one set of buffers: what run_pipeline takes (tests/test_gpu_graph_replay.py replays the same
+    chains from a captured graph).  inputs(k) -> {name: array}; outputs {name: (shape, dtype, per_frame)}; calls(ctx, t, stream);
+    expect(inputs) -> {name: array}."""
+
+    def __init__(self, name, dims, inputs, outputs, calls, expect):
+        self.name, self.dims, self.inputs, self.outputs, self.calls, self.expect = name, dims, inputs, outputs, calls, expect
+
+
+def lidar_camera_pipeline():
+    """bgr_convert -> slic_labels -> complete(d_labels) -> evaluate."""
     rows, cols, b, step, nc = 70, 130, 2, 16, 40
     dims = (rows, cols, b)
     nl = L.lib().dcmt_slic_num_centers(rows, cols, step)
@@ -781,17 +789,27 @@ def test_lidar_camera_pipeline_repeated_in_reused_buffers():
         sums, = alone_on(dims, lambda c: [c.evaluate_dev(dev(inp["gt"]), dev(dense), 0.0, "both")])
         return {"lab": lab, "labels": labels, "dense": dense, "sums": sums}
 
-    sets = [inputs(k) for k in range(3)]
     outs = {"lab": ((b, rows, cols, 3), np.uint8, True), "labels": ((b, rows, cols), np.int32, True), "dense": ((b, rows, cols), f32, True),
             "sums": ((b, 7), np.float64, True)}
-    run_pipeline("pipeline lidar + camera", dims, sets, inputs(3), outs, calls, [expect(i) for i in sets], expect(inputs(3)))
+    return Pipeline("pipeline lidar + camera", dims, inputs, outs, calls, expect)
+
+
+def run_repeated(p):
+    """The pipeline three times through the same buffers behind one delay: input sets 0..2, set 3 the decoys."""
+    sets = [p.inputs(k) for k in range(3)]
+    run_pipeline(p.name, p.dims, sets, p.inputs(3), p.outputs, p.calls, [p.expect(i) for i in sets], p.expect(p.inputs(3)))
 
 
 @gpu
-def test_stereo_lidar_pipeline_repeated_in_reused_buffers():
+def test_lidar_camera_pipeline_repeated_in_reused_buffers():
+    """bgr_convert -> slic_labels -> complete(d_labels) -> evaluate, three times through the same buffers behind one delay."""
+    run_repeated(lidar_camera_pipeline())
+
+
+def stereo_lidar_pipeline():
     """project_points -> complete(normalize) -> bgr_convert(gray) left, right -> stereo_refine -> reproject_depth -> evaluate ->
-    gaussian5 in place -> colorize -> depth_to_cloud, three times through the same buffers behind one delay.  The cloud is made of the
-    warped plane (zero where nothing landed, so its counts differ from set to set) with the colourised refined plane as its colours."""
+    gaussian5 in place -> colorize -> depth_to_cloud.  The cloud is made of the warped plane (zero where nothing landed, so its counts
+    differ from set to set) with the colourised refined plane as its colours."""
     rows, cols, b, n = 40, 133, 3, 6000
     dims = (rows, cols, b)
     pc = project_case()
@@ -845,11 +863,17 @@ def test_stereo_lidar_pipeline_repeated_in_reused_buffers():
         return {"sparse": sparse, "dense": dense, "gray_l": gl, "gray_r": gr, "refined": blurred, "warped": warped, "sums": sums,
                 "colour": colour, "points": pts, "offsets": offs}
 
-    sets = [inputs(k) for k in range(3)]
     img, px = ((b, rows, cols), f32, True), ((b, rows, cols), np.uint8, True)
     outs = {"sparse": img, "dense": img, "gray_l": px, "gray_r": px, "refined": img, "warped": img, "sums": ((b, 7), np.float64, True),
             "colour": ((b, rows, cols, 3), np.uint8, True), "points": ((b * rows * cols, 4), f32, False), "offsets": ((b + 1,), np.int32, False)}
-    run_pipeline("pipeline stereo + lidar", dims, sets, inputs(3), outs, calls, [expect(i) for i in sets], expect(inputs(3)))
+    return Pipeline("pipeline stereo + lidar", dims, inputs, outs, calls, expect)
+
+
+@gpu
+def test_stereo_lidar_pipeline_repeated_in_reused_buffers():
+    """project_points -> complete(normalize) -> bgr_convert(gray) left, right -> stereo_refine -> reproject_depth -> evaluate ->
+    gaussian5 in place -> colorize -> depth_to_cloud, three times through the same buffers behind one delay."""
+    run_repeated(stereo_lidar_pipeline())
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. growth
